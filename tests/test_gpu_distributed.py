@@ -195,27 +195,30 @@ def test_bench_two_ranks_dry_run_on_one_device():
     assert d["pipeline"]["lane_results_reproducible_alone"] and d["quality"]["gate"] == "pass"
 
 
-def test_bench_eight_ranks_dry_run_on_one_device():
-    """The 8-rank code path without an 8-GPU box: bench.py as the driver launches it for N = 8, with
-    gloo and all eight ranks on the one device: spawn path, shard_by_scene over eight ranks (4 scenes each), the gather of
-    eight shards with every instance back in order and the rank's own shard bit-exact through the gather, the `collective`
-    object with eight rows and the lane decision (lanes per rank = what fits the cgroup quota at the measured cores per lane)."""
+def test_bench_four_ranks_dry_run_on_one_device():
+    """The N > 2 code path without a multi-GPU box: bench.py as the driver launches it, with gloo and
+    four ranks on the one device -- the most a shared card takes next to the test runner, which allows six processes with the
+    GPU open at once (eight ranks on one card are beyond that; the eight-rank sharding and lane rule are CPU tests in
+    test_parallel_cpu.py): spawn path, shard_by_scene over the ranks (4 scenes each), the gather of every shard with every
+    instance back in order and the rank's own shard bit-exact through the gather, the `collective` object with a row per rank
+    and the lane decision (lanes per rank = what fits the cgroup quota at the measured cores per lane)."""
     import json
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--same-device", "--steps", "4", "--warmup", "1",
+    world = 4
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--same-device", "--steps", "4", "--warmup", "1",
            "--merge", "1", "--repeats", "1", "--scenes-per-gpu", "4", "--no-cpu-baseline"]
     res = subprocess.run(cmd, env=dict(os.environ, MASTER_ADDR="127.0.0.1"), capture_output=True, text=True, timeout=1500)
     assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
     d = _bench_lines(res.stdout)
-    assert d["n_gpus"] == 8 and d["steps"] == 4 and d["scaling"] == "weak"
+    assert d["n_gpus"] == world and d["steps"] == 4 and d["scaling"] == "weak"
     ss = d["scene_sharded"]
-    assert ss["instances"] == 8 * 4 * 8 and ss["all_instances_returned"] and ss["own_shard_round_trip_exact"]
+    assert ss["instances"] == world * 4 * 8 and ss["all_instances_returned"] and ss["own_shard_round_trip_exact"]
     assert ss["max_joint_limit_violation"] <= 1e-8
     col = d["collective"]
-    assert col["world_size"] == 8 and len(col["ranks"]) == 8 and sorted(r["rank"] for r in col["ranks"]) == list(range(8))
+    assert col["world_size"] == world and len(col["ranks"]) == world and sorted(r["rank"] for r in col["ranks"]) == list(range(world))
     assert 1 <= col["lanes_per_rank"] <= 4 and col["lane_decision"]
     q = col["cgroup_cpu_quota_cores"]
-    if q is not None:  # lanes that fit the quota at the measured 0.27 cores per lane + 0.5 per rank: four at quota 16 / 8 ranks
-        assert col["lanes_per_rank"] == max(1, min(4, int((q / 8 - 0.5) / 0.27 + 1e-9)))
+    if q is not None:  # lanes that fit the quota at the measured 0.27 cores per lane + 0.5 per rank
+        assert col["lanes_per_rank"] == max(1, min(4, int((q / world - 0.5) / 0.27 + 1e-9)))
     assert col["host_cpu_cores_busy_all_ranks"] > 0
     assert d["quality"]["gate"] == "pass"
 

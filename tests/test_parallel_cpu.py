@@ -314,3 +314,51 @@ def test_bench_lanes_per_rank_fit_the_cgroup_quota():
         lanes, why = bench.lanes_that_fit(asked, world, quota)
         assert 1 <= lanes <= asked and str(lanes) in why
         assert lanes == 1 or world * (bench.RANK_CORES + lanes * bench.LANE_CORES) <= quota + 1e-9
+
+
+def test_bench_dump_outputs_float64_within_the_limit(tmp_path):
+    """bench.py --dump-outputs: every array as DIR/<name>.npy in float64 (integers exactly), instances along axis 0; beyond
+    DUMP_LIMIT bytes the same fixed seeded sample of instances in every array, and the same sample from run to run."""
+    import importlib.util
+    import pathlib
+    spec = importlib.util.spec_from_file_location("bench", pathlib.Path(__file__).resolve().parents[1] / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(1)
+    arrays = {"Q": rng.standard_normal((40, 3, 5)), "cost": rng.random(40), "iterations": np.arange(40, dtype=np.int32)}
+    assert bench.write_dump(str(tmp_path / "all"), arrays) == (40, 40)
+    for k, a in arrays.items():
+        back = np.load(tmp_path / "all" / f"{k}.npy")
+        assert back.dtype == np.float64 and back.shape == a.shape
+        np.testing.assert_array_equal(back, a)
+    bench.DUMP_LIMIT = 10 * 17 * 8 + 1024 * 3  # room for ten instances of 17 float64 each
+    for d in ("s1", "s2"):
+        assert bench.write_dump(str(tmp_path / d), arrays) == (10, 40)
+    it = np.load(tmp_path / "s1" / "iterations.npy")
+    assert len(it) == 10 and np.all(np.diff(it) > 0)
+    np.testing.assert_array_equal(np.load(tmp_path / "s1" / "Q.npy"), arrays["Q"][it.astype(np.int64)])
+    for k in arrays:
+        np.testing.assert_array_equal(np.load(tmp_path / "s1" / f"{k}.npy"), np.load(tmp_path / "s2" / f"{k}.npy"))
+    assert sum((tmp_path / "s1" / f"{k}.npy").stat().st_size for k in arrays) <= bench.DUMP_LIMIT
+
+
+def test_batch_pipeline_region_of_depth_calls_runs_every_handle():
+    """bench.py --dump-outputs relies on it: whatever order the handles came back in, a run of at least `depth` calls takes
+    every handle at least once (the idle handles are taken first in, first out)."""
+    import random
+    import time
+    from grasptrajopt_amd.parallel import BatchPipeline
+
+    class Slow:
+        def __init__(self, i):
+            self.i = i
+
+        def work(self):
+            time.sleep(random.random() * 2e-3)
+            return self.i
+
+    random.seed(0)
+    with BatchPipeline([Slow(i) for i in range(4)]) as pipe:
+        for n in (4, 5, 8, 13) * 5:
+            futs = [pipe.submit("work") for _ in range(n)]
+            assert sorted(set(f.result() for f in futs)) == [0, 1, 2, 3]
