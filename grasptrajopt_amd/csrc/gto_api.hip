@@ -5,12 +5,14 @@
 
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <chrono>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <utility>
@@ -28,7 +30,114 @@
 static std::string g_create_error;
 
 #define GTO_SWEEP_WGS 64   // workgroups of the crew behind an itemized obstacle launch laid out over an estimate (launch_obstacle)
+
 #define GTO_MAX_LANES 8  // lanes of one solve call (streams, list sets, progress words)
+#define GTO_NAP_US 50      // the throttle's naps (the host thread of a lane sleep-polls two pinned words); 10-50 us change nothing
+#define GTO_NAP_FEW_US 10  // ... in launches with few instances in flight; 50-200 us change nothing either
+// the deep-gather obstacle variant only up to this many instances in flight (two workgroups per CU: beyond that the
+// five-per-CU variant gets through a launch faster)
+#define GTO_OBS_DEEP_MAX 32
+
+// Every knob a GTO_* environment variable sets, with its default.  read_tunables fills it once per handle, in gto_create.
+struct Tunables {
+  int ahead = 8;           // GTO_AHEAD: rounds the host may enqueue beyond the last one it has seen running
+  int ahead_few = 4;       // ... in launches with few instances in flight (short rounds: four of them cover the host's launch time, and every round enqueued beyond the last instance's end runs empty)
+  // speculation (gto_kernels.h GTO_KSPEC): candidates a step generates ahead of their evaluation in launches with few
+  // instances in flight (more work, fewer dependent rounds).  Every candidate is a job of the next obstacle launch, and
+  // that launch stays one wave of workgroups up to about `spec_jobs` jobs: with n instances in flight a step hands out
+  // up to spec_jobs / n candidates (at most spec_acc after an accepted evaluation, spec_rej after a round without one);
+  // beyond that, after a rejection only, spec_rej_few while at most spec_few are in flight.  spec_deep caps n for the
+  // candidates after an accepted evaluation.
+  int spec_rej = 4, spec_acc = 4, spec_deep = 32;  // GTO_SPEC_REJ, GTO_SPEC_ACC, GTO_SPEC_DEEP
+  int spec_rej_few = 2, spec_jobs = 20;            // GTO_SPEC_REJ_FEW, GTO_SPEC_JOBS
+  int spec_streak = 4;  // GTO_SPEC_STREAK: first candidate accepted this many rounds in a row -> one candidate after the next accepted evaluation (0: off)
+  // The tail of a LARGE call (more than spec_deep instances from the start) shares the GPU with the other lanes' launches,
+  // and there an evaluation that turns out not to be needed costs more than the round it might save: fewer candidates
+  // after an accepted evaluation, the single candidate after a shorter run of first-try accepts, three waypoints per
+  // obstacle workgroup (GTO_SPEC_ACC_TAIL, GTO_SPEC_STREAK_TAIL, GTO_OBS_TG_FEW_TAIL; the driver's 20-step call 253 -> 262 k).
+  // A call that is small from its first round (one grasp, a batch of a few) is alone on the GPU and keeps the settings
+  // that give the shortest chain of rounds (one instance: 0.66 ms; with the tail's settings 0.90 ms).
+  int spec_acc_tail = 2, spec_streak_tail = 2, obs_tg_few_tail = 3;
+  int spec_few = 64;  // GTO_SPEC_FEW: speculation starts once at most this many instances are in flight: before that the GPU is full and every extra evaluation costs time
+  int obs_deep = 1;   // GTO_OBS_DEEP: launches with few instances in flight use the obstacle kernel variant with deep gather batches
+  int dbg_cut = 0;    // GTO_DEBUG_CUT: cut the obstacle kernel short after a phase (timing experiments: results are garbage)
+  int dist_relax = 0;  // GTO_DIST_RELAX: build the distance fields by relaxation sweeps instead of the separable passes
+  // GTO_OBS_INTERLEAVE: waypoints of an obstacle workgroup nG apart instead of consecutive, so that the waypoints next to
+  // the obstacles (neighbours in time) land in different workgroups: 0 never, 1 always, 2 (default) in launches with few
+  // instances in flight, where the longest workgroup decides the round (+5 % for one batch at a time, -2 % at saturation)
+  int obs_interleave = 2;
+  int static_pos = 1;  // GTO_STATIC_POS=0: every instance draws its list positions from the counters in every round
+  int pb_merge = 4;  // GTO_PB_MERGE: chunks of a link under one sphere of the step kernel's broad phase
+  int prebroad = 1;  // GTO_PREBROAD=0: every (job, group) gets a workgroup of the obstacle kernel in every round
+  double pb_min_gain = 0.10;  // GTO_PB_MIN_GAIN: a call whose step-kernel broad phase settles less than this share of the groups stops running it
+  int obs_tg = 3;  // GTO_OBS_TG: waypoints per workgroup of the obstacle kernel: they share the table staging, the FK barriers and the launch overhead
+  int obs_tg_few = 2;  // GTO_OBS_TG_FEW: ... when few instances are in flight (one small batch, the tail of a call): lower latency per round; results do not depend on the group size
+  int obs_tg_wide = 5;  // GTO_OBS_TG_WIDE: ... for the wide robots (gto_create)
+  bool obs_tg_given = false;  // GTO_OBS_TG was set: it is the group size of every robot, the wide ones included
+  int few_instances = 192;  // GTO_FEW_INSTANCES: launches with at most this many instances in flight count as few
+  int step_nw_few = 8;  // GTO_STEP_NW_FEW: wavefronts per workgroup of the step kernel in launches with few instances in flight (4 or 8)
+  int slots = 512;  // GTO_SLOTS: instances in flight per lane of a solve call; a finished instance hands its slot to the next one
+  // lanes of a solve call (gto_solve_batch_device): at most lanes_max, each with at least lane_min instances; a lane with
+  // at most adopt_below instances left hands them to lane 0 (0: never).  gto_set_lanes / GTO_LANES, GTO_LANE_MIN, GTO_ADOPT
+  int lanes_max = 1, lane_min = 256, adopt_below = 0;
+  int item_hint_forced = 0;  // GTO_ITEM_HINT: the estimate itself (tests of the crew)
+  int item_grid = 1;  // GTO_ITEM_GRID=0: itemized launches laid out over the upper bound of their item lists
+  bool debug_timing = false;  // GTO_DEBUG_TIMING: phase stamps of the kernels on stderr after every solve call
+  bool lane_debug = false;    // GTO_LANE_DEBUG: host-side stamps of a call with lanes on stderr
+};
+
+// One row per variable, in the order they are applied: a row may also set up to two more fields (GTO_AHEAD sets both
+// aheads, GTO_OBS_TG all three group sizes ...), and a later row overrides them.  Values are clamped to [lo, hi]; a [0, 1]
+// row is a switch that any non-zero value turns on.
+static void read_tunables(Tunables& t) {
+  using F = int Tunables::*;
+  struct Row { const char* name; F f, also1, also2; int lo, hi; };
+  const int BIG = INT_MAX;
+  static const Row rows[] = {
+      {"GTO_AHEAD", &Tunables::ahead, &Tunables::ahead_few, nullptr, 1, BIG},
+      {"GTO_SPEC_REJ", &Tunables::spec_rej, nullptr, nullptr, 1, GTO_KSPEC},
+      {"GTO_SPEC_REJ_FEW", &Tunables::spec_rej_few, nullptr, nullptr, 1, GTO_KSPEC},
+      {"GTO_SPEC_STREAK", &Tunables::spec_streak, &Tunables::spec_streak_tail, nullptr, 0, BIG},
+      {"GTO_SPEC_STREAK_TAIL", &Tunables::spec_streak_tail, nullptr, nullptr, 0, BIG},
+      {"GTO_SPEC_JOBS", &Tunables::spec_jobs, nullptr, nullptr, 1, BIG},
+      {"GTO_SPEC_ACC", &Tunables::spec_acc, &Tunables::spec_acc_tail, nullptr, 1, GTO_KSPEC},
+      {"GTO_SPEC_ACC_TAIL", &Tunables::spec_acc_tail, nullptr, nullptr, 1, GTO_KSPEC},
+      {"GTO_SPEC_DEEP", &Tunables::spec_deep, nullptr, nullptr, 0, BIG},
+      {"GTO_SPEC_FEW", &Tunables::spec_few, nullptr, nullptr, 0, BIG},
+      {"GTO_OBS_DEEP", &Tunables::obs_deep, nullptr, nullptr, 0, 1},
+      {"GTO_PREBROAD", &Tunables::prebroad, nullptr, nullptr, 0, 1},
+      {"GTO_PB_MERGE", &Tunables::pb_merge, nullptr, nullptr, 1, BIG},
+      {"GTO_STATIC_POS", &Tunables::static_pos, nullptr, nullptr, 0, 1},
+      {"GTO_OBS_INTERLEAVE", &Tunables::obs_interleave, nullptr, nullptr, 0, 2},
+      {"GTO_DIST_RELAX", &Tunables::dist_relax, nullptr, nullptr, 0, 1},
+      {"GTO_DEBUG_CUT", &Tunables::dbg_cut, nullptr, nullptr, INT_MIN, INT_MAX},
+      {"GTO_ITEM_GRID", &Tunables::item_grid, nullptr, nullptr, 0, 1},
+      {"GTO_ITEM_HINT", &Tunables::item_hint_forced, nullptr, nullptr, 0, BIG},
+      {"GTO_SLOTS", &Tunables::slots, nullptr, nullptr, 1, BIG},
+      {"GTO_LANES", &Tunables::lanes_max, nullptr, nullptr, 1, GTO_MAX_LANES},
+      {"GTO_LANE_MIN", &Tunables::lane_min, nullptr, nullptr, 1, BIG},
+      {"GTO_ADOPT", &Tunables::adopt_below, nullptr, nullptr, 0, BIG},
+      {"GTO_OBS_TG", &Tunables::obs_tg, &Tunables::obs_tg_few, &Tunables::obs_tg_few_tail, 1, GTO_MAX_TG},
+      {"GTO_OBS_TG_FEW", &Tunables::obs_tg_few, &Tunables::obs_tg_few_tail, nullptr, 1, GTO_MAX_TG},
+      {"GTO_OBS_TG_FEW_TAIL", &Tunables::obs_tg_few_tail, nullptr, nullptr, 1, GTO_MAX_TG},
+      {"GTO_OBS_TG_WIDE", &Tunables::obs_tg_wide, nullptr, nullptr, 1, GTO_MAX_TG},
+      {"GTO_FEW_INSTANCES", &Tunables::few_instances, nullptr, nullptr, INT_MIN, INT_MAX},
+  };
+  for (const Row& r : rows) {
+    const char* e = getenv(r.name);
+    if (!e) continue;
+    int v = atoi(e);
+    v = r.lo == 0 && r.hi == 1 ? (v != 0) : std::max(r.lo, std::min(r.hi, v));
+    for (F f : {r.f, r.also1, r.also2})
+      if (f) t.*f = v;
+  }
+  t.obs_tg_given = getenv("GTO_OBS_TG") != nullptr;
+  if (const char* e = getenv("GTO_STEP_NW_FEW")) t.step_nw_few = atoi(e) == 8 ? 8 : 4;
+  if (const char* e = getenv("GTO_PB_MIN_GAIN")) t.pb_min_gain = atof(e);
+  t.debug_timing = getenv("GTO_DEBUG_TIMING") != nullptr;
+  t.lane_debug = getenv("GTO_LANE_DEBUG") != nullptr;
+  if (t.dbg_cut) fprintf(stderr, "[gto] WARNING: GTO_DEBUG_CUT=%d cuts the obstacle kernel short: timing experiments only, RESULTS ARE GARBAGE\n", t.dbg_cut);
+}
 
 struct DevBuf {
   void* p = nullptr;
@@ -54,7 +163,6 @@ struct gto_handle {
   // solve workspace (grown on demand)
   DevBuf state, Qcur, Qtry, vis, screw, blocks, goalblk, ssfixed, ndone, qf, livebuf, qfs, wrecbuf, itembuf;
   DevBuf counters;  // work counters of a profiled solve
-  int mode = GTO_MODE_ROUNDS;  // gto_set_mode: rounds of two launches over the instances in flight (the only mode left)
   unsigned long long last_counters[4] = {0, 0, 0, 0};
   int32_t* h_ndone = nullptr;  // pinned
   // pinned, device-visible, written by the first workgroup of every step launch: word 0 = call tag << 32 | instances
@@ -63,42 +171,8 @@ struct gto_handle {
   unsigned long long* h_progress = nullptr;
   unsigned long long* d_progress = nullptr;  // its device address
   unsigned progress_tag = 0;
-  int ahead = 8;           // GTO_AHEAD: rounds the host may enqueue beyond the last one it has seen running
-  int nap_us = 50, nap_few_us = 10;  // GTO_NAP_US / GTO_NAP_FEW_US: the throttle's naps (the host thread of a lane sleep-polls two pinned words)
-  int ahead_few = 4;       // ... in launches with few instances in flight (short rounds: four of them cover the host's launch time, and every round enqueued beyond the last instance's end runs empty)
-  // speculation (gto_kernels.h GTO_KSPEC): candidates a step generates ahead of their evaluation in launches with few
-  // instances in flight (more work, fewer dependent rounds).  Every candidate is a job of the next obstacle launch, and
-  // that launch stays one wave of workgroups up to about `spec_jobs` jobs: with n instances in flight a step hands out
-  // up to spec_jobs / n candidates (at most spec_acc after an accepted evaluation, spec_rej after a round without one);
-  // beyond that, after a rejection only, spec_rej_few while at most spec_few are in flight.  spec_deep caps n for the
-  // candidates after an accepted evaluation.
-  int spec_rej = 4, spec_acc = 4, spec_deep = 32, spec_kmax = 1;
-  int spec_rej_few = 2, spec_jobs = 20;
-  int spec_streak = 4;  // GTO_SPEC_STREAK: first candidate accepted this many rounds in a row -> one candidate after the next accepted evaluation (0: off)
-  int obs_deep_max = 32;  // GTO_OBS_DEEP_MAX: ... only up to this many instances in flight (two workgroups per CU: beyond that the five-per-CU variant gets through a launch faster)
-  int obs_deep = 1;   // GTO_OBS_DEEP: launches with few instances in flight use the obstacle kernel variant with deep gather batches
-  // The tail of a LARGE call (more than spec_deep instances from the start) shares the GPU with the other lanes' launches,
-  // and there an evaluation that turns out not to be needed costs more than the round it might save: fewer candidates
-  // after an accepted evaluation, the single candidate after a shorter run of first-try accepts, three waypoints per
-  // obstacle workgroup (GTO_SPEC_ACC_TAIL, GTO_SPEC_STREAK_TAIL, GTO_OBS_TG_FEW_TAIL; the driver's 20-step call 253 -> 262 k).
-  // A call that is small from its first round (one grasp, a batch of a few) is alone on the GPU and keeps the settings
-  // that give the shortest chain of rounds (one instance: 0.66 ms; with the tail's settings 0.90 ms).
-  int spec_acc_tail = 2, spec_streak_tail = 2, obs_tg_few_tail = 3;
-  int spec_few = 64;  // GTO_SPEC_FEW: speculation starts once at most this many instances are in flight: before that the GPU is full and every extra evaluation costs time
-  int dbg_cut = 0;
-  int dist_relax = 0;  // GTO_DIST_RELAX: build the distance fields by relaxation sweeps instead of the separable passes
-  // GTO_OBS_INTERLEAVE: waypoints of an obstacle workgroup nG apart instead of consecutive, so that the waypoints next to
-  // the obstacles (neighbours in time) land in different workgroups: 0 never, 1 always, 2 (default) in launches with few
-  // instances in flight, where the longest workgroup decides the round (+5 % for one batch at a time, -2 % at saturation)
-  int obs_interleave = 2;
-  int static_pos = 1;  // GTO_STATIC_POS=0: every instance draws its list positions from the counters in every round
-  int pb_merge = 4;  // GTO_PB_MERGE: chunks of a link under one sphere of the step kernel's broad phase
-  int prebroad = 1;  // GTO_PREBROAD=0: every (job, group) gets a workgroup of the obstacle kernel in every round
-  double pb_min_gain = 0.10;  // GTO_PB_MIN_GAIN: a call whose step-kernel broad phase settles less than this share of the groups stops running it
-  int obs_tg_few = 2;  // ... when few instances are in flight (one small batch, the tail of a call): lower latency per round; results do not depend on the group size
-  int few_instances = 192;
-  int step_nw_few = 8;  // GTO_STEP_NW_FEW: wavefronts per workgroup of the step kernel in launches with few instances in flight (4 or 8)
-  int obs_tg = 3;  // waypoints per workgroup of the obstacle kernel: they share the table staging, the FK barriers and the launch overhead
+  Tunables tu;  // the GTO_* knobs, read at gto_create
+  int spec_kmax = 1;  // candidates per step the eight-wave step kernel's LDS has room for at this T
   long long* dbg = nullptr;
   // staging for the host-pointer entry points
   // buffers of the scene that the last gto_set_scene replaced: the next replacement of the same size takes them instead of
@@ -125,20 +199,13 @@ struct gto_handle {
   size_t lm_lds = 0;
   int np = GTO_NB;     // block width of the normal equations: 8 (up to eight optimised joints) or 16
   DevBuf zws;          // k_lm_step_wide: block inverses [slots][T-2][np*np]
-  int slots = 512;  // instances in flight per lane of a solve call (GTO_SLOTS); a finished instance hands its slot to the next one
-  // lanes of a solve call (gto_solve_batch_device): at most lanes_max, each with at least lane_min instances; a lane with
-  // at most adopt_below instances left hands them to lane 0 (0: never).  gto_set_lanes / GTO_LANES, GTO_LANE_MIN, GTO_ADOPT
-  int lanes_max = 1, lane_min = 256, adopt_below = 0;
   hipStream_t lane_stream[GTO_MAX_LANES] = {};
   hipEvent_t lane_event[GTO_MAX_LANES] = {};
   hipStream_t user_lane_stream[GTO_MAX_LANES] = {};  // gto_set_lane_streams: the caller's streams for the lanes
   int n_user_lane_streams = 0;
   // items (job, group pairs with something to gather) per evaluation job: the largest ratio the rounds of the last call
-  // published (the prior of the next call's launches until its own counts arrive), and of the call that is running
-  double items_per_job_prior = 0.0, items_per_job_call = 0.0;
-  int item_hint_forced = 0;  // GTO_ITEM_HINT: the estimate itself (tests of the crew)
-  int hot_variants = 1;  // GTO_OBS_HOT=0: the solve loop's evaluation launches use the general kernel variants
-  int item_grid = 1;  // GTO_ITEM_GRID=0: itemized launches laid out over the upper bound of their item lists
+  // published (the prior of the next call's launches until its own counts arrive)
+  double items_per_job_prior = 0.0;
   std::mutex* prof_mu = nullptr;  // set while a call with several lanes (host threads) runs: guards the profiling records
 };
 
@@ -224,68 +291,52 @@ static hipError_t raise_dynamic_lds(const void* kernel, size_t bytes) {
   return e;
 }
 
-int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device, gto_handle** out) {
-  if (!d || !opts || !out) return fail(nullptr, GTO_ERR_INVALID_ARG, "null argument");
-  *out = nullptr;
-  std::string why;
-  if (!validate_opts(opts, why)) return fail(nullptr, GTO_ERR_INVALID_ARG, why);
-  if (d->n_frames < 1 || d->n_frames > GTO_MAX_FRAMES) return fail(nullptr, GTO_ERR_UNSUPPORTED, "n_frames out of range (max 32)");
-  if (d->n_links < 1 || d->n_links > GTO_MAX_LINKS) return fail(nullptr, GTO_ERR_UNSUPPORTED, "n_links out of range (max 32)");
-  if (d->n_opt < 1 || d->n_opt > GTO_MAX_OPT) return fail(nullptr, GTO_ERR_UNSUPPORTED, "n_opt out of range (max 16)");
-  if (d->ndof < d->n_opt || d->ndof > GTO_MAX_DOF) return fail(nullptr, GTO_ERR_UNSUPPORTED, "ndof out of range (max 32)");
-  if (d->n_points < 1) return fail(nullptr, GTO_ERR_INVALID_ARG, "robot has no surface points");
-  if (d->n_gripper_points < 1) return fail(nullptr, GTO_ERR_INVALID_ARG, "robot has no gripper points");
-  if (d->frame_ee < 0 || d->frame_ee >= d->n_frames || d->frame_gripper < 0 || d->frame_gripper >= d->n_frames)
-    return fail(nullptr, GTO_ERR_INVALID_ARG, "frame_ee / frame_gripper out of range");
+// The obstacle kernel variant of a launch: np-wide blocks; deep gather batches (launches with few instances in flight);
+// the crew behind an itemized launch laid out over an estimate; the hot variants of the solve loop's evaluations (central
+// differences: the value-only gather, the init pass's virtual waypoints and the static-link bookkeeping compiled out).
+// The wide robots have two variants, the crew has one.  gto_create raises the dynamic LDS of every variant this returns.
+using ObsKernel = decltype(&k_obstacle_gram<GTO_NB>);
+static ObsKernel obstacle_kernel(int np, bool deep, bool sweep, bool hot) {
+  // [wide, 8-wide, 8-wide deep]; the first reference to a variant decides where the code object places it, so they keep
+  // the order they have always had
+  static const ObsKernel cold[3] = {k_obstacle_gram<16>, k_obstacle_gram<GTO_NB>, k_obstacle_gram<GTO_NB, GTO_OBS_DEEP_PD>};
+  static const ObsKernel crew = k_obstacle_gram<GTO_NB, GTO_OBS_MAIN_PD, true>;
+  static const ObsKernel warm[3] = {k_obstacle_gram<16, GTO_OBS_MAIN_PD, false, true>, k_obstacle_gram<GTO_NB, GTO_OBS_MAIN_PD, false, true>,
+                                    k_obstacle_gram<GTO_NB, GTO_OBS_DEEP_PD, false, true>};
+  if (sweep && np == GTO_NB) return crew;
+  const int i = np != GTO_NB ? 0 : deep ? 2 : 1;
+  return hot ? warm[i] : cold[i];
+}
 
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(nullptr, GTO_ERR_NO_DEVICE, "no HIP device visible: the GTO solve path has no CPU fallback");
-  if (device >= ndev) return fail(nullptr, GTO_ERR_INVALID_ARG, "device index out of range");
-
-  gto_handle* h = new gto_handle();
-  if (device >= 0) {
-    if (hipSetDevice(device) != hipSuccess) { delete h; return fail(nullptr, GTO_ERR_HIP, "hipSetDevice failed"); }
-    h->device = device;
-  } else {
-    (void)hipGetDevice(&h->device);
+// Rounds of pointer jumping that FK needs over a tree listed parents first: a frame at depth d is the product of d + 1
+// local transforms, and r rounds compose 2^r of them.
+static int fk_rounds(const int* parent, int n) {
+  int depth[GTO_MAX_FRAMES], maxd = 1, r = 0;
+  for (int i = 0; i < n; ++i) {
+    depth[i] = parent[i] < 0 ? 0 : depth[parent[i]] + 1;
+    maxd = std::max(maxd, depth[i]);
   }
-  h->opts = *opts;
-  if (const char* e = getenv("GTO_AHEAD")) h->ahead = h->ahead_few = std::max(1, atoi(e));
-  if (const char* e = getenv("GTO_NAP_US")) h->nap_us = std::max(1, atoi(e));
-  if (const char* e = getenv("GTO_NAP_FEW_US")) h->nap_few_us = std::max(1, atoi(e));
-  if (const char* e = getenv("GTO_SPEC_REJ")) h->spec_rej = std::max(1, std::min(GTO_KSPEC, atoi(e)));
-  if (const char* e = getenv("GTO_SPEC_REJ_FEW")) h->spec_rej_few = std::max(1, std::min(GTO_KSPEC, atoi(e)));
-  if (const char* e = getenv("GTO_SPEC_STREAK")) h->spec_streak = h->spec_streak_tail = std::max(0, atoi(e));
-  if (const char* e = getenv("GTO_SPEC_STREAK_TAIL")) h->spec_streak_tail = std::max(0, atoi(e));
-  if (const char* e = getenv("GTO_SPEC_JOBS")) h->spec_jobs = std::max(1, atoi(e));
-  if (const char* e = getenv("GTO_SPEC_ACC")) h->spec_acc = h->spec_acc_tail = std::max(1, std::min(GTO_KSPEC, atoi(e)));
-  if (const char* e = getenv("GTO_SPEC_ACC_TAIL")) h->spec_acc_tail = std::max(1, std::min(GTO_KSPEC, atoi(e)));
-  if (const char* e = getenv("GTO_SPEC_DEEP")) h->spec_deep = std::max(0, atoi(e));
-  if (const char* e = getenv("GTO_SPEC_FEW")) h->spec_few = std::max(0, atoi(e));
-  if (const char* e = getenv("GTO_OBS_DEEP")) h->obs_deep = atoi(e) ? 1 : 0;
-  if (const char* e = getenv("GTO_PREBROAD")) h->prebroad = atoi(e) != 0;
-  if (const char* e = getenv("GTO_PB_MERGE")) h->pb_merge = std::max(1, atoi(e));
-  if (const char* e = getenv("GTO_STATIC_POS")) h->static_pos = atoi(e) != 0;
-  if (const char* e = getenv("GTO_PB_MIN_GAIN")) h->pb_min_gain = atof(e);
-  if (const char* e = getenv("GTO_OBS_INTERLEAVE")) h->obs_interleave = std::max(0, std::min(2, atoi(e)));
-  if (const char* e = getenv("GTO_DIST_RELAX")) h->dist_relax = atoi(e) ? 1 : 0;
-  if (const char* e = getenv("GTO_DEBUG_CUT")) h->dbg_cut = atoi(e);
-  if (h->dbg_cut) fprintf(stderr, "[gto] WARNING: GTO_DEBUG_CUT=%d cuts the obstacle kernel short: timing experiments only, RESULTS ARE GARBAGE\n", h->dbg_cut);
-  if (const char* e = getenv("GTO_ITEM_GRID")) h->item_grid = atoi(e) != 0;
-  if (const char* e = getenv("GTO_OBS_HOT")) h->hot_variants = atoi(e) != 0;
-  if (const char* e = getenv("GTO_ITEM_HINT")) h->item_hint_forced = std::max(0, atoi(e));
-  if (const char* e = getenv("GTO_SLOTS")) h->slots = std::max(1, atoi(e));
-  if (const char* e = getenv("GTO_LANES")) h->lanes_max = std::max(1, std::min(GTO_MAX_LANES, atoi(e)));
-  if (const char* e = getenv("GTO_LANE_MIN")) h->lane_min = std::max(1, atoi(e));
-  if (const char* e = getenv("GTO_ADOPT")) h->adopt_below = std::max(0, atoi(e));
-  if (const char* e = getenv("GTO_OBS_TG")) h->obs_tg = h->obs_tg_few = h->obs_tg_few_tail = std::max(1, std::min(GTO_MAX_TG, atoi(e)));
-  if (const char* e = getenv("GTO_OBS_TG_FEW")) h->obs_tg_few = h->obs_tg_few_tail = std::max(1, std::min(GTO_MAX_TG, atoi(e)));
-  if (const char* e = getenv("GTO_OBS_TG_FEW_TAIL")) h->obs_tg_few_tail = std::max(1, std::min(GTO_MAX_TG, atoi(e)));
-  if (const char* e = getenv("GTO_FEW_INSTANCES")) h->few_instances = atoi(e);
-  if (const char* e = getenv("GTO_STEP_NW_FEW")) h->step_nw_few = atoi(e) == 8 ? 8 : 4;
-  if (getenv("GTO_DEBUG_TIMING")) { (void)hipMalloc((void**)&h->dbg, 256 * sizeof(long long)); (void)hipMemset(h->dbg, 0, 256 * sizeof(long long)); }
-  RobotDev& rb = h->rb;
+  while ((1 << r) < maxd + 1) ++r;
+  return r;
+}
+
+// Everything gto_create uploads for a robot, built on the host from the descriptor alone.
+struct RobotTables {
+  RobotDev rb;
+  std::vector<double> px, py, pz;  // surface points sorted by link, and inside a link along a Morton curve
+  std::vector<int32_t> plink, perm;  // their links, and the descriptor's index of each
+  std::vector<Chunk> chunks;  // runs of <= 64 points of one link
+  std::vector<PbChunk> pbchunks;  // the step kernel's spheres (one dummy entry if no link moves)
+  int pb_C = 0;  // spheres in pbchunks
+};
+
+// Validates the descriptor and builds its tables; no HIP call.  GTO_OK, or an error code with its message in `why`.
+static int build_robot(const gto_robot_desc* d, int pb_merge, RobotTables& t, std::string& why) {
+  auto bad = [&](int code, const char* msg) {
+    why = msg;
+    return code;
+  };
+  RobotDev& rb = t.rb;
   memset(&rb, 0, sizeof rb);
   rb.n_frames = d->n_frames;
   rb.ndof = d->ndof;
@@ -297,25 +348,19 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
   rb.frame_gripper = d->frame_gripper;
   for (int i = 0; i < GTO_MAX_DOF; ++i) rb.opt_of_dof[i] = -1;
   for (int j = 0; j < d->n_opt; ++j) {
-    if (d->opt_index[j] < 0 || d->opt_index[j] >= d->ndof) { delete h; return fail(nullptr, GTO_ERR_INVALID_ARG, "opt_index out of range"); }
+    if (d->opt_index[j] < 0 || d->opt_index[j] >= d->ndof) return bad(GTO_ERR_INVALID_ARG, "opt_index out of range");
     rb.opt_index[j] = d->opt_index[j];
     rb.opt_of_dof[d->opt_index[j]] = j;
     rb.lower[j] = d->lower[j];
     rb.upper[j] = d->upper[j];
-    if (!(d->lower[j] <= d->upper[j])) { delete h; return fail(nullptr, GTO_ERR_INVALID_ARG, "lower > upper"); }
+    if (!(d->lower[j] <= d->upper[j])) return bad(GTO_ERR_INVALID_ARG, "lower > upper");
   }
   for (int i = 0; i < d->n_frames; ++i) {
     int p = d->parent[i];
-    if (p >= i || p < -1) { delete h; return fail(nullptr, GTO_ERR_INVALID_ARG, "frames must list parents before children"); }
+    if (p >= i || p < -1) return bad(GTO_ERR_INVALID_ARG, "frames must list parents before children");
     int jt = d->joint_type[i];
-    if (jt != GTO_JOINT_FIXED && jt != GTO_JOINT_REVOLUTE && jt != GTO_JOINT_PRISMATIC) {
-      delete h;
-      return fail(nullptr, GTO_ERR_UNSUPPORTED, "joint type not supported (optas/models.py:865-866)");
-    }
-    if (jt != GTO_JOINT_FIXED && (d->q_index[i] < 0 || d->q_index[i] >= d->ndof)) {
-      delete h;
-      return fail(nullptr, GTO_ERR_INVALID_ARG, "q_index out of range for an actuated joint");
-    }
+    if (jt != GTO_JOINT_FIXED && jt != GTO_JOINT_REVOLUTE && jt != GTO_JOINT_PRISMATIC) return bad(GTO_ERR_UNSUPPORTED, "joint type not supported (optas/models.py:865-866)");
+    if (jt != GTO_JOINT_FIXED && (d->q_index[i] < 0 || d->q_index[i] >= d->ndof)) return bad(GTO_ERR_INVALID_ARG, "q_index out of range for an actuated joint");
     rb.parent[i] = p;
     rb.joint_type[i] = jt;
     rb.q_index[i] = (jt == GTO_JOINT_FIXED) ? -1 : d->q_index[i];
@@ -324,7 +369,7 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
     rt2aff(R, d->origin_xyz + 3 * i, rb.origin[i]);
     const double* ax = d->axis + 3 * i;
     double nrm = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-    if (jt != GTO_JOINT_FIXED && !(nrm > 0)) { delete h; return fail(nullptr, GTO_ERR_INVALID_ARG, "zero joint axis"); }
+    if (jt != GTO_JOINT_FIXED && !(nrm > 0)) return bad(GTO_ERR_INVALID_ARG, "zero joint axis");
     for (int k = 0; k < 3; ++k) rb.axis_unit[i][k] = (nrm > 0) ? ax[k] / nrm : 0.0;
     rb.opt_of_frame[i] = -1;
     uint32_t anc = (p >= 0) ? rb.frame_anc[p] : 0u;
@@ -336,19 +381,10 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
         }
     rb.frame_anc[i] = anc;
   }
-  {
-    int depth[GTO_MAX_FRAMES], maxd = 1;
-    for (int i = 0; i < d->n_frames; ++i) {
-      depth[i] = rb.parent[i] < 0 ? 0 : depth[rb.parent[i]] + 1;
-      maxd = std::max(maxd, depth[i]);
-    }
-    // a frame at depth d is the product of d + 1 local transforms, and r rounds of pointer jumping compose 2^r of them
-    rb.fk_rounds = 0;
-    while ((1 << rb.fk_rounds) < maxd + 1) ++rb.fk_rounds;
-  }
+  rb.fk_rounds = fk_rounds(rb.parent, d->n_frames);
   for (int l = 0; l < d->n_links; ++l) {
     int f = d->link_frame[l];
-    if (f < 0 || f >= d->n_frames) { delete h; return fail(nullptr, GTO_ERR_INVALID_ARG, "link_frame out of range"); }
+    if (f < 0 || f >= d->n_frames) return bad(GTO_ERR_INVALID_ARG, "link_frame out of range");
     rb.link_frame[l] = f;
     rb.link_anc[l] = rb.frame_anc[f];
     double R[9];
@@ -367,7 +403,7 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
   }
   for (int i = 0; i < d->n_frames; ++i) rb.link_of_frame[i] = -1, rb.xst_slot[i] = -1;
   for (int l = 0; l < d->n_links; ++l) {
-    if (rb.link_of_frame[rb.link_frame[l]] >= 0) { delete h; return fail(nullptr, GTO_ERR_INVALID_ARG, "two collision links on one frame"); }
+    if (rb.link_of_frame[rb.link_frame[l]] >= 0) return bad(GTO_ERR_INVALID_ARG, "two collision links on one frame");
     rb.link_of_frame[rb.link_frame[l]] = l;
   }
   rb.n_xst = 0;
@@ -494,14 +530,10 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
     }
     build(rb.fk_tab_c, nc, corg, caxu, rb.cf_type, cpar, coptj, clf, cvis, copt_frame);
     rb.n_cframes = nc;
-    int depth[GTO_MAX_FRAMES], maxd = 1;
-    for (int i = 0; i < nc; ++i) {
-      depth[i] = cpar[i] < 0 ? 0 : depth[cpar[i]] + 1;
-      maxd = std::max(maxd, depth[i]);
-    }
-    rb.fk_rounds_c = 0;
-    while ((1 << rb.fk_rounds_c) < maxd + 1) ++rb.fk_rounds_c;
+    rb.fk_rounds_c = fk_rounds(cpar, nc);
   }
+  for (int i = 0; i < d->n_points; ++i)  // (before anything is indexed by it)
+    if (d->point_link[i] < 0 || d->point_link[i] >= d->n_links) return bad(GTO_ERR_INVALID_ARG, "point_link out of range");
   // moments of the gripper point cloud
   rb.grip_count = (double)d->n_gripper_points;
   for (int k = 0; k < d->n_gripper_points; ++k) {
@@ -551,10 +583,7 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
   // points sorted by link (stable), chunk table of <= 64 link-uniform points
   const int P = d->n_points;
   std::vector<int32_t> perm(P);
-  for (int i = 0; i < P; ++i) {
-    perm[i] = i;
-    if (d->point_link[i] < 0 || d->point_link[i] >= d->n_links) { delete h; return fail(nullptr, GTO_ERR_INVALID_ARG, "point_link out of range"); }
-  }
+  for (int i = 0; i < P; ++i) perm[i] = i;
   // sort by link, and inside a link along a Morton (Z-order) curve of the link-local coordinates, so
   // that the 64 lanes of a chunk (and consecutive chunks) gather from neighbouring voxels/cache lines
   std::vector<uint32_t> morton(P, 0);
@@ -616,7 +645,7 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
   }
   rb.n_chunks = (int)chunks.size();
   std::vector<PbChunk> pbchunks;
-  // The step kernel's spheres: runs of h->pb_merge consecutive chunks of a moving link under one sphere (the chunks follow a
+  // The step kernel's spheres: runs of pb_merge consecutive chunks of a moving link under one sphere (the chunks follow a
   // Morton curve, so a run is a compact patch; centre = mean of its points, radius = the farthest of them).  Coarser than
   // the obstacle kernel's own test, which stays per chunk and exact: a sphere more lists a group more, never one less.
   // Centre in the coordinates of the link's FRAME (visual origin applied here, in double: the tail's walk stops at the frames).
@@ -625,7 +654,7 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
     if (c.pad) { ++ci; continue; }
     size_t cj = ci;
     int i0 = c.start, i1 = c.start;
-    while (cj < chunks.size() && cj - ci < (size_t)h->pb_merge && !chunks[cj].pad && chunks[cj].link == c.link) i1 = chunks[cj].start + chunks[cj].count, ++cj;
+    while (cj < chunks.size() && cj - ci < (size_t)pb_merge && !chunks[cj].pad && chunks[cj].link == c.link) i1 = chunks[cj].start + chunks[cj].count, ++cj;
     double cx = 0, cy = 0, cz = 0, r2 = 0;
     for (int k = i0; k < i1; ++k) cx += px[k], cy += py[k], cz += pz[k];
     cx /= (i1 - i0), cy /= (i1 - i0), cz /= (i1 - i0);
@@ -635,57 +664,95 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
                                std::sqrt(r2) * (1.0 + 1e-9) + 1e-12, rb.link_frame[c.link], 0});
     ci = cj;
   }
-  h->pb_C = (int)pbchunks.size();
+  t.pb_C = (int)pbchunks.size();
   if (pbchunks.empty()) pbchunks.push_back(PbChunk{0, 0, 0, 0, 0, 0});  // (a robot none of whose links moves: the table is never read)
-  if (rb.n_chunks > GTO_MAX_ACTIVE) { delete h; return fail(nullptr, GTO_ERR_UNSUPPORTED, "too many surface points (max 16384)"); }
+  if (rb.n_chunks > GTO_MAX_ACTIVE) return bad(GTO_ERR_UNSUPPORTED, "too many surface points (max 16384)");
+  t.perm = std::move(perm);
+  t.px = std::move(px), t.py = std::move(py), t.pz = std::move(pz);
+  t.plink = std::move(plink);
+  t.chunks = std::move(chunks);
+  t.pbchunks = std::move(pbchunks);
+  return GTO_OK;
+}
 
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return fail(nullptr, GTO_ERR_HIP, "hipStreamCreate failed"); }
+int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device, gto_handle** out) {
+  if (!d || !opts || !out) return fail(nullptr, GTO_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  std::string why;
+  if (!validate_opts(opts, why)) return fail(nullptr, GTO_ERR_INVALID_ARG, why);
+  if (d->n_frames < 1 || d->n_frames > GTO_MAX_FRAMES) return fail(nullptr, GTO_ERR_UNSUPPORTED, "n_frames out of range (max 32)");
+  if (d->n_links < 1 || d->n_links > GTO_MAX_LINKS) return fail(nullptr, GTO_ERR_UNSUPPORTED, "n_links out of range (max 32)");
+  if (d->n_opt < 1 || d->n_opt > GTO_MAX_OPT) return fail(nullptr, GTO_ERR_UNSUPPORTED, "n_opt out of range (max 16)");
+  if (d->ndof < d->n_opt || d->ndof > GTO_MAX_DOF) return fail(nullptr, GTO_ERR_UNSUPPORTED, "ndof out of range (max 32)");
+  if (d->n_points < 1) return fail(nullptr, GTO_ERR_INVALID_ARG, "robot has no surface points");
+  if (d->n_gripper_points < 1) return fail(nullptr, GTO_ERR_INVALID_ARG, "robot has no gripper points");
+  if (d->frame_ee < 0 || d->frame_ee >= d->n_frames || d->frame_gripper < 0 || d->frame_gripper >= d->n_frames)
+    return fail(nullptr, GTO_ERR_INVALID_ARG, "frame_ee / frame_gripper out of range");
+  Tunables tu;
+  read_tunables(tu);
+  std::unique_ptr<RobotTables> t(new RobotTables());
+  if (int rc = build_robot(d, tu.pb_merge, *t, why)) return fail(nullptr, rc, why);
+  const RobotDev& rb = t->rb;
+  const int np = rb.n_opt <= GTO_NB ? GTO_NB : 16;
+  const size_t lm_lds = np == GTO_NB ? lm_lds_bytes(opts->T, 1) : lm_wide_lds_bytes(opts->T, 16);
+  if (lm_lds > 160 * 1024) return fail(nullptr, GTO_ERR_UNSUPPORTED, "T too large for the step kernel's LDS");
+  const bool wide = np != GTO_NB;
+  // waypoints per obstacle workgroup of the wide robots (GTO_OBS_TG_WIDE; GTO_OBS_TG, when given, is the group size of
+  // every robot), fewer if the robot's tables would not fit the CU's LDS.  The fixed part of a 16-wide workgroup (tables,
+  // matrix-core prefix, projection onto sixteen screws) is larger than an 8-wide one's, and since round 6 the epilogue
+  // projects one waypoint at a time (ObsLds: its scratch no longer grows with the group): configs[4] with 2 / 3 / 4 / 5 /
+  // 6 / 8 waypoints per workgroup 29.0 / 33.1 / 35.4 / 36.6 / 34.8 / 28.7 k trajectories/s (until round 6: two, 28.2 k)
+  int tg_w = tu.obs_tg_wide;
+  if (wide && tu.obs_tg_given) tg_w = std::max(tg_w, tu.obs_tg);
+  while (wide && tg_w > 1 && (size_t)ObsLds(tg_w, rb.n_frames, rb.n_links, tg_w * rb.n_chunks, np).total_doubles * sizeof(double) > 150 * 1024) --tg_w;
+  const int tg_lds = wide ? tg_w : GTO_MAX_TG;
+  const ObsLds lay(tg_lds, rb.n_frames, rb.n_links, tg_lds * rb.n_chunks, np);
+  if ((size_t)lay.total_doubles * sizeof(double) > 150 * 1024) return fail(nullptr, GTO_ERR_UNSUPPORTED, "robot too large for the obstacle kernel's LDS");
+  if (wide) {
+    tu.obs_tg = tu.obs_tg_given ? std::min(tu.obs_tg, tg_w) : tg_w;
+    tu.obs_tg_few = std::min(tu.obs_tg_few, tu.obs_tg), tu.obs_tg_few_tail = std::min(tu.obs_tg_few_tail, tu.obs_tg);
+  }
+  // candidates per step the eight-wave step kernel's LDS has room for at this T
+  int spec_kmax = 1;
+  if (!wide)
+    while (spec_kmax < GTO_KSPEC && lm_lds_bytes(opts->T, spec_kmax + 1) <= 160 * 1024 - 256) ++spec_kmax;
+
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return fail(nullptr, GTO_ERR_NO_DEVICE, "no HIP device visible: the GTO solve path has no CPU fallback");
+  if (device >= ndev) return fail(nullptr, GTO_ERR_INVALID_ARG, "device index out of range");
+  if (device >= 0 && hipSetDevice(device) != hipSuccess) return fail(nullptr, GTO_ERR_HIP, "hipSetDevice failed");
+
+  gto_handle* h = new gto_handle();
+  if (device >= 0) h->device = device;
+  else (void)hipGetDevice(&h->device);
+  h->opts = *opts;
+  h->tu = tu;
+  std::memcpy(&h->rb, &rb, sizeof rb);
+  h->pb_C = t->pb_C;
+  h->np = np;
+  h->lm_lds = lm_lds;
+  h->spec_kmax = spec_kmax;
+  if (tu.debug_timing) { (void)hipMalloc((void**)&h->dbg, 256 * sizeof(long long)); (void)hipMemset(h->dbg, 0, 256 * sizeof(long long)); }
   auto up = [&](void** dst, const void* src, size_t bytes) -> bool {
     if (hipMalloc(dst, bytes) != hipSuccess) return false;
     return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
   };
-  bool ok = up((void**)&h->d_rb, &rb, sizeof rb) && up((void**)&h->d_px, px.data(), P * sizeof(double)) &&
-            up((void**)&h->d_py, py.data(), P * sizeof(double)) && up((void**)&h->d_pz, pz.data(), P * sizeof(double)) &&
-            up((void**)&h->d_plink, plink.data(), P * sizeof(int32_t)) && up((void**)&h->d_perm, perm.data(), P * sizeof(int32_t)) &&
-            up((void**)&h->d_chunks, chunks.data(), chunks.size() * sizeof(Chunk)) &&
-            up((void**)&h->d_pbchunks, pbchunks.data(), std::max<size_t>(1, pbchunks.size()) * sizeof(PbChunk));
+  const size_t P = t->px.size();
+  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { gto_destroy(h); return fail(nullptr, GTO_ERR_HIP, "hipStreamCreate failed"); }
+  const bool ok = up((void**)&h->d_rb, &h->rb, sizeof h->rb) && up((void**)&h->d_px, t->px.data(), P * sizeof(double)) &&
+                  up((void**)&h->d_py, t->py.data(), P * sizeof(double)) && up((void**)&h->d_pz, t->pz.data(), P * sizeof(double)) &&
+                  up((void**)&h->d_plink, t->plink.data(), P * sizeof(int32_t)) && up((void**)&h->d_perm, t->perm.data(), P * sizeof(int32_t)) &&
+                  up((void**)&h->d_chunks, t->chunks.data(), t->chunks.size() * sizeof(Chunk)) &&
+                  up((void**)&h->d_pbchunks, t->pbchunks.data(), t->pbchunks.size() * sizeof(PbChunk));
   if (!ok) { gto_destroy(h); return fail(nullptr, GTO_ERR_ALLOC, "device allocation failed in gto_create"); }
-  h->np = rb.n_opt <= GTO_NB ? GTO_NB : 16;
-  h->lm_lds = h->np == GTO_NB ? lm_lds_bytes(opts->T, 1) : lm_wide_lds_bytes(opts->T, 16);
-  if (h->lm_lds > 160 * 1024) { gto_destroy(h); return fail(nullptr, GTO_ERR_UNSUPPORTED, "T too large for the step kernel's LDS"); }
-  // candidates per step the eight-wave step kernel's LDS has room for at this T
-  h->spec_kmax = 1;
-  if (h->np == GTO_NB)
-    while (h->spec_kmax < GTO_KSPEC && lm_lds_bytes(opts->T, h->spec_kmax + 1) <= 160 * 1024 - 256) ++h->spec_kmax;
-  {
-    const int w = h->np == GTO_NB ? 0 : 1;
-    // waypoints per obstacle workgroup of the wide robots (see below), fewer if the robot's tables would not fit the CU's LDS
-    int tg_w = getenv("GTO_OBS_TG_WIDE") ? std::max(1, std::min(GTO_MAX_TG, atoi(getenv("GTO_OBS_TG_WIDE")))) : 5;
-    if (w && getenv("GTO_OBS_TG")) tg_w = std::max(tg_w, h->obs_tg);  // (GTO_OBS_TG, when given, is the group size of every robot)
-    while (w && tg_w > 1 && (size_t)ObsLds(tg_w, rb.n_frames, rb.n_links, tg_w * rb.n_chunks, h->np).total_doubles * sizeof(double) > 150 * 1024) --tg_w;
-    const int tg_lds = w ? tg_w : GTO_MAX_TG;
-    const ObsLds lay(tg_lds, rb.n_frames, rb.n_links, tg_lds * rb.n_chunks, h->np);
-    const size_t lds = std::min<size_t>((size_t)lay.total_doubles * sizeof(double), 160 * 1024);
-    if ((size_t)lay.total_doubles * sizeof(double) > 150 * 1024) { gto_destroy(h); return fail(nullptr, GTO_ERR_UNSUPPORTED, "robot too large for the obstacle kernel's LDS"); }
-    hipError_t e1 = raise_dynamic_lds(w ? (const void*)k_obstacle_gram<16> : (const void*)k_obstacle_gram<GTO_NB>, lds);
-    if (!w && e1 == hipSuccess) e1 = raise_dynamic_lds((const void*)k_obstacle_gram<GTO_NB, GTO_OBS_DEEP_PD>, lds);
-    if (!w && e1 == hipSuccess) e1 = raise_dynamic_lds((const void*)k_obstacle_gram<GTO_NB, GTO_OBS_MAIN_PD, true>, lds);
-    if (e1 == hipSuccess) e1 = raise_dynamic_lds(w ? (const void*)k_obstacle_gram<16, GTO_OBS_MAIN_PD, false, true> : (const void*)k_obstacle_gram<GTO_NB, GTO_OBS_MAIN_PD, false, true>, lds);
-    if (!w && e1 == hipSuccess) e1 = raise_dynamic_lds((const void*)k_obstacle_gram<GTO_NB, GTO_OBS_DEEP_PD, false, true>, lds);
-    hipError_t e2 = w ? raise_dynamic_lds((const void*)k_lm_step_wide<16>, h->lm_lds) : raise_dynamic_lds((const void*)k_lm_step<4, 1>, h->lm_lds);
-    if (!w && e2 == hipSuccess) e2 = raise_dynamic_lds((const void*)k_lm_step<8, GTO_KSPEC>, lm_lds_bytes(opts->T, h->spec_kmax));
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-      gto_destroy(h);
-      return fail(nullptr, GTO_ERR_HIP, "hipFuncSetAttribute failed");
-    }
-    if (w) {  // wider blocks (GTO_OBS_TG_WIDE): five waypoints per workgroup.  The fixed part of a 16-wide workgroup (tables, matrix-core
-      // prefix, projection onto sixteen screws) is larger than an 8-wide one's, and since round 6 the epilogue projects one
-      // waypoint at a time (ObsLds: its scratch no longer grows with the group): configs[4] with 2 / 3 / 4 / 5 / 6 / 8 waypoints
-      // per workgroup 29.0 / 33.1 / 35.4 / 36.6 / 34.8 / 28.7 k trajectories/s (until round 6: two, 28.2 k)
-      h->obs_tg = getenv("GTO_OBS_TG") ? std::min(h->obs_tg, tg_w) : tg_w;
-      h->obs_tg_few = std::min(h->obs_tg_few, h->obs_tg), h->obs_tg_few_tail = std::min(h->obs_tg_few_tail, h->obs_tg);
-    }
-  }
+  // dynamic LDS of every kernel variant the handle can launch (obstacle_kernel, the step kernels)
+  const size_t lds = std::min<size_t>((size_t)lay.total_doubles * sizeof(double), 160 * 1024);
+  hipError_t e = hipSuccess;
+  for (int v = 0; v < 8 && e == hipSuccess; ++v) e = raise_dynamic_lds((const void*)obstacle_kernel(np, v & 1, v & 2, v & 4), lds);
+  if (e == hipSuccess) e = wide ? raise_dynamic_lds((const void*)k_lm_step_wide<16>, lm_lds) : raise_dynamic_lds((const void*)k_lm_step<4, 1>, lm_lds);
+  if (e == hipSuccess && !wide) e = raise_dynamic_lds((const void*)k_lm_step<8, GTO_KSPEC>, lm_lds_bytes(opts->T, spec_kmax));
+  if (e != hipSuccess) { gto_destroy(h); return fail(nullptr, GTO_ERR_HIP, "hipFuncSetAttribute failed"); }
   *out = h;
   return GTO_OK;
 }
@@ -862,7 +929,7 @@ static int set_scene_impl(gto_handle* h, int32_t id, const float* c_all, const f
   for (int which = 0; which < (rob != ra ? 2 : 1); ++which) {
     uint8_t* d0 = nullptr;
     SCN(dalloc((void**)&d0, nvox));
-    if (h->dist_relax) {  // GTO_DIST_RELAX=1: the reference construction, GTO_DIST_CAP sweeps of 3x3x3 min-plus-one (A/B and tests)
+    if (h->tu.dist_relax) {  // GTO_DIST_RELAX=1: the reference construction, GTO_DIST_CAP sweeps of 3x3x3 min-plus-one (A/B and tests)
       uint8_t* d1 = scratch;
       hipLaunchKernelGGL(k_dist_init, dim3(nblk), dim3(256), 0, h->stream, which ? rob : ra, d0, (long)nvox);
       for (int it = 0; it < GTO_DIST_CAP; ++it) {
@@ -955,7 +1022,6 @@ int gto_set_mode(gto_handle* h, int32_t mode) {
   // (the single-launch kernel of rounds 1-3, one workgroup running an instance's whole solve, was 2.4-2.9x slower than the
   // rounds and had been a test-only second implementation since round 3: removed in round 4; the mode number stays reserved)
   if (mode == GTO_MODE_SINGLE_LAUNCH) return fail(h, GTO_ERR_UNSUPPORTED, "GTO_MODE_SINGLE_LAUNCH was removed: the rounds mode is the solver");
-  h->mode = mode;
   return GTO_OK;
 }
 
@@ -963,7 +1029,7 @@ int gto_set_lanes(gto_handle* h, int32_t max_lanes, int32_t min_per_lane, int32_
   if (!h) return GTO_ERR_INVALID_ARG;
   if (max_lanes < 1 || max_lanes > GTO_MAX_LANES || min_per_lane < 1 || adopt_below < 0)
     return fail(h, GTO_ERR_INVALID_ARG, "gto_set_lanes: 1 <= max_lanes <= 8, min_per_lane >= 1, adopt_below >= 0");
-  h->lanes_max = max_lanes, h->lane_min = min_per_lane, h->adopt_below = adopt_below;
+  h->tu.lanes_max = max_lanes, h->tu.lane_min = min_per_lane, h->tu.adopt_below = adopt_below;
   return GTO_OK;
 }
 
@@ -1040,8 +1106,8 @@ static SolveParams make_params(const gto_handle* h, int n_max, bool use_standoff
   sp.tol_step = o.tol_step;
   sp.tol_rel_f = o.tol_rel_f;
   sp.lambda0 = o.lambda0;
-  sp.dbg_cut = h->dbg_cut;
-  sp.interleave = h->obs_interleave == 1;
+  sp.dbg_cut = h->tu.dbg_cut;
+  sp.interleave = h->tu.obs_interleave == 1;
   sp.static_pos = 0;
   sp.pb_next = 0, sp.pb_tg = 1, sp.pb_ng = 1, sp.pb_pw = 1, sp.pb_verify = 0;
   sp.pb_C = h->pb_C, sp.pb_tab0 = 0, sp.pb_mC = ObsGeom::magic(std::max(1, h->pb_C)), sp.pb_mF = ObsGeom::magic(h->rb.n_frames);
@@ -1050,7 +1116,7 @@ static SolveParams make_params(const gto_handle* h, int n_max, bool use_standoff
   sp.round = sp.parity = 0;
   sp.kcap = h->np == GTO_NB ? GTO_KSPEC : 1;  // candidate copies of the workspace (the wide step kernel generates one)
   sp.k_acc = sp.k_rej = sp.k_eval = 1;
-  sp.spec_streak = h->spec_streak;
+  sp.spec_streak = h->tu.spec_streak;
   return sp;
 }
 
@@ -1140,62 +1206,64 @@ static int prof_end(gto_handle* h, hipStream_t st) {
   return GTO_OK;
 }
 
-static int launch_obstacle(gto_handle* h, hipStream_t st, const BatchPtrs& bp, const SolveParams& sp, int B, int t_begin,
-                           int nT, int fixed_mode, bool timed, bool with_goal_terms = false, int n_jobs = 0, int tg = 0, bool deep = false,
-                           bool itemized = false, int items_hint = 0) {
-  // waypoints per workgroup: groups of h->obs_tg (the two pinned waypoints form one group)
-  const int TG = fixed_mode ? 1 : std::max(1, std::min(tg > 0 ? tg : h->obs_tg, nT));  // the init pass has 4 virtual waypoints
-  const ObsGeom geo(h->rb.n_cframes, h->rb.n_frames, h->rb.fk_rounds_c, h->rb.n_links, h->rb.n_opt, h->rb.n_chunks, TG, nT, h->np);
+using InitKernel = decltype(&k_lm_init<GTO_NB>);
+static InitKernel lm_init_kernel(int np) { return np == GTO_NB ? k_lm_init<GTO_NB> : k_lm_init<16>; }
+
+// What one obstacle launch covers.  The defaults are an evaluation of waypoints t_begin .. t_begin + nT - 1 of the batch.
+struct ObsLaunch {
+  int t_begin = 2, nT = 0;
+  int fixed_mode = 0;       // 1: the init pass over the four virtual waypoints of the pinned ends (t_begin 0, nT 4)
+  bool timed = false;       // profiling events around the launch (gto_set_profiling)
+  bool goal_terms = false;  // goal-term workgroups in front of the obstacle workgroups (the solve loop's evaluations)
+  int n_jobs = 0;           // evaluation jobs the grid is laid out for (0: the batch)
+  int tg = 0;               // waypoints per workgroup (0: GTO_OBS_TG)
+  bool deep = false;        // the variant with deep gather batches (few instances in flight)
+  bool itemized = false;    // the regular workgroups walk the step kernel's list of (job, group) pairs
+  int items_hint = 0;       // estimate of that list's length (0: its upper bound)
+};
+static ObsLaunch init_pass() {
+  ObsLaunch o;
+  o.t_begin = 0, o.nT = 4, o.fixed_mode = 1;
+  return o;
+}
+
+static int launch_obstacle(gto_handle* h, hipStream_t st, const BatchPtrs& bp, const SolveParams& sp, int B, const ObsLaunch& o) {
+  // waypoints per workgroup: groups of h->tu.obs_tg (the two pinned waypoints form one group)
+  const int TG = o.fixed_mode ? 1 : std::max(1, std::min(o.tg > 0 ? o.tg : h->tu.obs_tg, o.nT));  // the init pass has 4 virtual waypoints
+  const ObsGeom geo(h->rb.n_cframes, h->rb.n_frames, h->rb.fk_rounds_c, h->rb.n_links, h->rb.n_opt, h->rb.n_chunks, TG, o.nT, h->np);
   const int nG = geo.nG;
-  const int nb = n_jobs > 0 ? n_jobs : B;  // workgroups are laid out for the evaluation jobs there can be; B stays the batch (strides)
+  const int nb = o.n_jobs > 0 ? o.n_jobs : B;  // workgroups are laid out for the evaluation jobs there can be; B stays the batch (strides)
   int n_regular = obstacle_grid(nb, nG);
   // Itemized launches: laid out over the caller's estimate of the item list's length instead of its upper bound (nine
   // tenths of the workgroups of the upper bound find no item and leave; they cost the other lanes' launches dispatch
   // slots: +7 % trajectories/s without them); a crew of GTO_SWEEP_WGS workgroups behind the launch walks whatever the
   // estimate missed (the kernel's SWEEP variant), so the result does not depend on it.
-  const bool sweep = itemized && items_hint > 0 && items_hint + GTO_SWEEP_WGS < n_regular && bp.live != nullptr && !fixed_mode && !deep && h->np == GTO_NB;  // (the wide robots' launches are never itemized)
-  if (sweep) n_regular = 8 * ((items_hint + 7) / 8);
+  const bool sweep = o.itemized && o.items_hint > 0 && o.items_hint + GTO_SWEEP_WGS < n_regular && bp.live != nullptr && !o.fixed_mode && !o.deep && h->np == GTO_NB;  // (the wide robots' launches are never itemized)
+  if (sweep) n_regular = 8 * ((o.items_hint + 7) / 8);
   const size_t lds = (size_t)geo.lay.total_doubles * sizeof(double);
-  const dim3 grid(n_regular + (with_goal_terms ? 8 * ((nb + 31) / 32) : 0));  // goal-term jobs: four to a workgroup, in front, a multiple of eight workgroups
-  const bool deep_v = h->np == GTO_NB && deep;
-  if (timed) {
+  const dim3 grid(n_regular + (o.goal_terms ? 8 * ((nb + 31) / 32) : 0));  // goal-term jobs: four to a workgroup, in front, a multiple of eight workgroups
+  const bool deep_v = h->np == GTO_NB && o.deep;
+  if (o.timed) {
     int rc_ = prof_begin(h, st, deep_v ? GTO_PROF_OBSTACLE_FEW : GTO_PROF_OBSTACLE, (long long)grid.x);
     if (rc_) return rc_;
   }
   BatchPtrs bpl = bp;  // the work counters of this variant (64 cells each)
   if (bpl.work) bpl.work += 64 * (deep_v ? GTO_PROF_OBSTACLE_FEW : GTO_PROF_OBSTACLE);
   // this round's job list and its length (the kernel's first, preloaded, arguments); null outside the solve loop
-  const bool listed = bp.live != nullptr && !fixed_mode;
+  const bool listed = bp.live != nullptr && !o.fixed_mode;
   const int32_t* jobs_par = listed ? bp.jobs + (size_t)sp.parity * bp.cap * sp.kcap : nullptr;
   const int32_t* njobs_par = listed ? bp.nlive + GTO_NJOBS(sp.parity) : nullptr;
   // rounds behind a step kernel that ran the broad phase itself: the regular workgroups are laid out over its list of (job, group) pairs
   const size_t items_cap = (size_t)bp.cap * sp.kcap * (sp.T - 2) + GTO_ITEM_SLACK;
-  const int2* items_par = listed && itemized ? bp.items + (size_t)sp.parity * items_cap : nullptr;
-  const int32_t* nitems_par = listed && itemized ? bp.nlive + 8 + sp.parity : nullptr;
-  const bool hot = !fixed_mode && sp.grad_mode == GTO_GRAD_CENTRAL_DIFF && h->hot_variants;
-  if (hot && h->np == GTO_NB && deep)
-    hipLaunchKernelGGL((k_obstacle_gram<GTO_NB, GTO_OBS_DEEP_PD, false, true>), grid, dim3(256), lds, st, jobs_par, njobs_par, items_par, nitems_par, geo.nG, geo.m_nG, n_regular, B, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes,
-                       bpl, sp, t_begin, nT, fixed_mode, geo, 0);
-  else if (hot && h->np == GTO_NB)
-    hipLaunchKernelGGL((k_obstacle_gram<GTO_NB, GTO_OBS_MAIN_PD, false, true>), grid, dim3(256), lds, st, jobs_par, njobs_par, items_par, nitems_par, geo.nG, geo.m_nG, n_regular, B, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes, bpl, sp,
-                       t_begin, nT, fixed_mode, geo, 0);
-  else if (hot)
-    hipLaunchKernelGGL((k_obstacle_gram<16, GTO_OBS_MAIN_PD, false, true>), grid, dim3(256), lds, st, jobs_par, njobs_par, items_par, nitems_par, geo.nG, geo.m_nG, n_regular, B, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes, bpl, sp,
-                       t_begin, nT, fixed_mode, geo, 0);
-  else if (h->np == GTO_NB && deep)  // few instances in flight: the variant that keeps a wave's record gathers in flight together
-    hipLaunchKernelGGL((k_obstacle_gram<GTO_NB, GTO_OBS_DEEP_PD>), grid, dim3(256), lds, st, jobs_par, njobs_par, items_par, nitems_par, geo.nG, geo.m_nG, n_regular, B, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes,
-                       bpl, sp, t_begin, nT, fixed_mode, geo, 0);
-  else if (h->np == GTO_NB)
-    hipLaunchKernelGGL(k_obstacle_gram<GTO_NB>, grid, dim3(256), lds, st, jobs_par, njobs_par, items_par, nitems_par, geo.nG, geo.m_nG, n_regular, B, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes, bpl, sp,
-                       t_begin, nT, fixed_mode, geo, 0);
-  else
-    hipLaunchKernelGGL(k_obstacle_gram<16>, grid, dim3(256), lds, st, jobs_par, njobs_par, items_par, nitems_par, geo.nG, geo.m_nG, n_regular, B, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes, bpl, sp,
-                       t_begin, nT, fixed_mode, geo, 0);
-  if (sweep) {  // the crew: items n_regular, n_regular + 1, ... of the list, if there are any
-    hipLaunchKernelGGL((k_obstacle_gram<GTO_NB, GTO_OBS_MAIN_PD, true>), dim3(GTO_SWEEP_WGS), dim3(256), lds, st, jobs_par, njobs_par, items_par, nitems_par, geo.nG, geo.m_nG, GTO_SWEEP_WGS, B, h->d_rb, h->d_px, h->d_py, h->d_pz,
-                       h->d_chunks, h->d_scenes, bpl, sp, t_begin, nT, fixed_mode, geo, n_regular);
-  }
-  if (timed) return prof_end(h, st);
+  const int2* items_par = listed && o.itemized ? bp.items + (size_t)sp.parity * items_cap : nullptr;
+  const int32_t* nitems_par = listed && o.itemized ? bp.nlive + 8 + sp.parity : nullptr;
+  const bool hot = !o.fixed_mode && sp.grad_mode == GTO_GRAD_CENTRAL_DIFF;
+  hipLaunchKernelGGL(obstacle_kernel(h->np, o.deep, false, hot), grid, dim3(256), lds, st, jobs_par, njobs_par, items_par, nitems_par, geo.nG, geo.m_nG, n_regular, B,
+                     h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes, bpl, sp, o.t_begin, o.nT, o.fixed_mode, geo, 0);
+  if (sweep)  // the crew: items n_regular, n_regular + 1, ... of the list, if there are any
+    hipLaunchKernelGGL(obstacle_kernel(h->np, false, true, false), dim3(GTO_SWEEP_WGS), dim3(256), lds, st, jobs_par, njobs_par, items_par, nitems_par, geo.nG, geo.m_nG, GTO_SWEEP_WGS, B,
+                       h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes, bpl, sp, o.t_begin, o.nT, o.fixed_mode, geo, n_regular);
+  if (o.timed) return prof_end(h, st);
   return GTO_OK;
 }
 
@@ -1211,78 +1279,80 @@ static int check_scene_ids_host(gto_handle* h, const int32_t* ids, int B) {
 
 }  // extern "C"
 
-extern "C" {
+// ------------------------------------------------------------------------------------------------- the solve loop
+// At most W instances per lane are in flight; the step kernel of an instance that finishes puts the next one of its lane
+// that has not started into the next round's live list, so every round works on a full house until the lane runs out,
+// instead of dragging the tail of its slowest instances through ever emptier rounds.
+//
+// LANES.  A call's instances are dealt to up to lanes_max lanes (contiguous ranges of at least lane_min), each with a
+// stream and lists of its own over the ONE workspace of the call (everything about an instance is indexed by its id in
+// the batch): one lane's obstacle launch overlaps another's step launch while the GPU is full.  Each lane has a host
+// thread of its own (lane 0: the caller's): a round of a lane with few instances in flight lasts 25-50 us and takes two
+// launches to enqueue, which one thread cannot do for four lanes.  Towards the end of the call every lane is down to a
+// handful of stragglers whose iterations are one dependent round each; four such chains sharing the command processor
+// advance at 35-55 us a round where one alone takes 21-27, so a lane whose remaining instances are all in flight and at
+// most adopt_below hands them to lane 0 (k_adopt), which then runs ONE chain for everybody.
+struct LaneCtx {
+  hipStream_t st = nullptr;
+  BatchPtrs bp;
+  SolveParams sp;
+  int lo = 0, n = 0, W = 0, cap = 0;  // first instance, instances, in flight at the start, list capacity
+  int room = 0;                       // positions its lists can have in use: W + what it adopted
+  int span_prev = 0;                  // static positions: positions the current lists span (the last one-candidate launch's grid), 0: compact lists
+  int n_resp = 0;                     // instances whose end this lane's finished-counter counts (own + adopted)
+  int k = 0, known_done = 0, seen_round = -1, k_prev = 1;
+  bool items_ready = false, pb_off = false, handed = false;
+  double ratio_max = 0.0;  // items per job, the largest the lane's rounds published
+  long end_us = 0, few_us = 0;  // (GTO_LANE_DEBUG) when the lane's thread returned / enqueued its first few-instance round, from the start of the threads
+  unsigned long long* h_prog = nullptr;
+};
 
-int gto_solve_batch_device(gto_handle* h, int32_t B, int32_t n_max, const int32_t* scene_id, const double* qc,
-                           const double* goals, const int32_t* n_goals, const double* standoff, const double* base_pos,
-                           const double* Q0, double* Q_out, double* dQ_out, double* cost_out, int32_t* iters_out,
-                           int32_t* status_out, void* stream) {
-  if (!h) return GTO_ERR_INVALID_ARG;
-  if (B < 0 || n_max < 1) return fail(h, GTO_ERR_INVALID_ARG, "B must be >= 0 and n_max >= 1");
-  if (B == 0) return GTO_OK;
-  if (B > GTO_JOB_MASK) return fail(h, GTO_ERR_UNSUPPORTED, "more than 16.7 million instances in one call");
-  if (!scene_id || !qc || !goals || !n_goals || !base_pos || !Q0) return fail(h, GTO_ERR_INVALID_ARG, "null input array");
-  if (h->scenes.empty()) return fail(h, GTO_ERR_NO_SCENE, "no scene has been set");
-  HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-  int rc = ensure_workspace(h, B);
-  if (rc) return rc;
-  SolveParams sp = make_params(h, n_max, standoff != nullptr);
-  BatchPtrs bp = make_ptrs(h, scene_id, qc, goals, n_goals, standoff, base_pos, Q0);
-  const int T = sp.T;
-  h->last_launches = 0;
-  h->last_ms = 0.0;
-  if (h->dbg) HIPCHK(h, hipMemsetAsync(h->dbg + 40, 0, 216 * sizeof(long long), st));
+// A lane that hands what it has left to lane 0: behind the lane's last launch (its event)
+struct Handover { int lane, parity, count, k_prev; };
 
-  // At most W instances per lane are in flight; the step kernel of an instance that finishes puts the next one of its lane
-  // that has not started into the next round's live list, so every round works on a full house until the lane runs out,
-  // instead of dragging the tail of its slowest instances through ever emptier rounds.
-  //
-  // LANES.  A call's instances are dealt to up to h->lanes_max lanes (contiguous ranges of at least h->lane_min), each
-  // with a stream and lists of its own over the ONE workspace of the call (everything about an instance is indexed by its
-  // id in the batch): one lane's obstacle launch overlaps another's step launch while the GPU is full.  One host thread
-  // feeds all of them round-robin.  Towards the end of the call every lane is down to a handful of stragglers whose
-  // iterations are one dependent round each; four such chains sharing the command processor advance at 35-55 us a round
-  // where one alone takes 21-27, so a lane whose remaining instances are all in flight and at most h->adopt_below hands
-  // them to lane 0 (k_adopt), which then runs ONE chain for everybody.
-  const int L = std::max(1, std::min(std::min(h->lanes_max, GTO_MAX_LANES), B / std::max(1, h->lane_min)));
-  const int kcap = sp.kcap, nF = h->rb.n_frames;
-  struct LaneCtx {
-    hipStream_t st = nullptr;
-    BatchPtrs bp;
-    SolveParams sp;
-    int lo = 0, n = 0, W = 0, cap = 0;  // first instance, instances, in flight at the start, list capacity
-    int room = 0;                       // positions its lists can have in use: W + what it adopted
-    int span_prev = 0;                  // static positions: positions the current lists span (the last one-candidate launch's grid), 0: compact lists
-    int n_resp = 0;                     // instances whose end this lane's finished-counter counts (own + adopted)
-    int k = 0, known_done = 0, seen_round = -1, k_prev = 1;
-    bool items_ready = false, pb_off = false, handed = false;
-    double ratio_max = 0.0;  // items per job, the largest the lane's rounds published
-    long end_us = 0, few_us = 0;  // (GTO_LANE_DEBUG) when the lane's thread returned / enqueued its first few-instance round, from the start of the threads
-    unsigned long long* h_prog = nullptr;
-  };
-  std::vector<LaneCtx> lanes(L);
-  const int adopt_room = L > 1 ? (L - 1) * std::max(0, h->adopt_below) : 0;
-  size_t off_live[GTO_MAX_LANES + 1] = {0}, off_qfs[GTO_MAX_LANES + 1] = {0}, off_items[GTO_MAX_LANES + 1] = {0}, lane_zws[GTO_MAX_LANES + 1] = {0};
+// What the lanes of one solve call share: the call's shape, and the hand-over between lanes
+struct SolveCall {
+  gto_handle* h = nullptr;
+  int B = 0, L = 1, T = 0, kcap = 1, nF = 0, max_iter = 0;
+  int pb_ng = 1;         // waypoint groups of the step kernel's broad phase
+  bool pb_able = false;  // that broad phase can run for this robot and call
+  size_t lane_zws[GTO_MAX_LANES + 1] = {0};  // first block-inverse slot of each lane (wide robots)
+  LaneCtx lanes[GTO_MAX_LANES];
+  std::chrono::steady_clock::time_point tp_start;
+  std::mutex mu;                     // hand-over requests, the error string, the profiling records
+  std::vector<Handover> requests;
+  int reserved = 0;                  // instances granted to lane 0 whose k_adopt it has not enqueued yet
+  int adopt_limit = 0;
+  std::atomic<int> rem0_pub{0}, others_open{0}, failed{0};
+};
+
+// (a) the lanes of a call: partition, lists in the call's buffers, streams and events, progress words, the broad phase's
+// layout.  sp and bp are the call's; bp.work is set here when the call is profiled.
+static int setup_lanes(gto_handle* h, hipStream_t st, SolveParams& sp, BatchPtrs& bp, SolveCall& c) {
+  const int B = c.B, T = c.T, kcap = c.kcap, nF = c.nF;
+  const int L = c.L = std::max(1, std::min(std::min(h->tu.lanes_max, GTO_MAX_LANES), B / std::max(1, h->tu.lane_min)));
+  const int adopt_room = L > 1 ? (L - 1) * std::max(0, h->tu.adopt_below) : 0;
+  size_t off_live[GTO_MAX_LANES + 1] = {0}, off_qfs[GTO_MAX_LANES + 1] = {0}, off_items[GTO_MAX_LANES + 1] = {0};
   for (int l = 0; l < L; ++l) {
-    LaneCtx& ln = lanes[l];
+    LaneCtx& ln = c.lanes[l];
     ln.lo = (int)((long long)B * l / L);
     ln.n = (int)((long long)B * (l + 1) / L) - ln.lo;
-    ln.W = std::min(ln.n, h->slots);
+    ln.W = std::min(ln.n, h->tu.slots);
     ln.cap = ln.W + (l == 0 ? adopt_room : 0);
     ln.n_resp = ln.n;
     ln.room = ln.W;
     off_live[l + 1] = off_live[l] + 2 * (size_t)(1 + kcap) * ln.cap + 32;
     off_qfs[l + 1] = off_qfs[l] + 2 * (size_t)ln.cap * kcap * T * nF;
     off_items[l + 1] = off_items[l] + 2 * ((size_t)ln.cap * kcap * (T - 2) + GTO_ITEM_SLACK);
-    lane_zws[l + 1] = lane_zws[l] + (size_t)ln.cap;
+    c.lane_zws[l + 1] = c.lane_zws[l] + (size_t)ln.cap;
   }
+  int rc;
   if ((rc = ensure(h, h->livebuf, off_live[L] * sizeof(int32_t)))) return rc;
   if ((rc = ensure(h, h->qfs, off_qfs[L] * sizeof(double)))) return rc;
   if ((rc = ensure(h, h->itembuf, off_items[L] * sizeof(int2)))) return rc;
-  if (h->np != GTO_NB && (rc = ensure(h, h->zws, lane_zws[L] * (size_t)(T - 2) * h->np * h->np * sizeof(double)))) return rc;
+  if (h->np != GTO_NB && (rc = ensure(h, h->zws, c.lane_zws[L] * (size_t)(T - 2) * h->np * h->np * sizeof(double)))) return rc;
   for (int l = 0; l < L; ++l) {
-    LaneCtx& ln = lanes[l];
+    LaneCtx& ln = c.lanes[l];
     ln.sp = sp;
     ln.bp = bp;
     ln.bp.live = (int32_t*)h->livebuf.p + off_live[l];
@@ -1306,18 +1376,15 @@ int gto_solve_batch_device(gto_handle* h, int32_t B, int32_t n_max, const int32_
     else if (l < h->n_user_lane_streams) ln.st = h->user_lane_stream[l];  // gto_set_lane_streams
     else {
       if (!h->lane_stream[l]) {
-        // Streams of the greatest priority by default: the runtime gives them hardware queues of their own, one per stream
-        // in the order of creation, so four lanes sit behind four dispatcher pipes.  Streams of the default priority share
-        // the process's four queues with every other stream it has created, and two lanes whose queues sit behind one pipe
+        // Streams of the greatest priority: the runtime gives them hardware queues of their own, one per stream in the
+        // order of creation, so four lanes sit behind four dispatcher pipes.  Streams of the default priority share the
+        // process's four queues with every other stream it has created, and two lanes whose queues sit behind one pipe
         // split its workgroup dispatch rate (the evaluation launch, five thousand mostly empty workgroups, 75 us instead
-        // of 48; rocprofv3 queue ids 1 and 5 in gpurun_out traces of round 5): 118 k instead of 196 k trajectories/s for
-        // one call of 1280 instances.  GTO_LANE_PRIO=0 default priority, 2 least.
-        static const int prio_mode = getenv("GTO_LANE_PRIO") ? atoi(getenv("GTO_LANE_PRIO")) : 1;
+        // of 48; rocprofv3 queue ids 1 and 5 in traces of round 5): 118 k instead of 196 k trajectories/s for one call of
+        // 1280 instances.
         int lo_p = 0, hi_p = 0;
         HIPCHK(h, hipDeviceGetStreamPriorityRange(&lo_p, &hi_p));  // (least, greatest): greatest is the smaller number
-        if (prio_mode == 1) HIPCHK(h, hipStreamCreateWithPriority(&h->lane_stream[l], hipStreamNonBlocking, hi_p));
-        else if (prio_mode == 2) HIPCHK(h, hipStreamCreateWithPriority(&h->lane_stream[l], hipStreamNonBlocking, lo_p));
-        else HIPCHK(h, hipStreamCreateWithFlags(&h->lane_stream[l], hipStreamNonBlocking));
+        HIPCHK(h, hipStreamCreateWithPriority(&h->lane_stream[l], hipStreamNonBlocking, hi_p));
       }
       ln.st = h->lane_stream[l];
     }
@@ -1327,331 +1394,401 @@ int gto_solve_batch_device(gto_handle* h, int32_t B, int32_t n_max, const int32_
   // the finished-counter and the round counter reach the host through words in pinned memory that the step kernel
   // writes; the tag tells this call's values from what the last launches of the previous call may still be writing
   h->progress_tag = h->progress_tag + 1 ? h->progress_tag + 1 : 1;
-  for (int l = 0; l < L; ++l) lanes[l].bp.progress_tag = (unsigned long long)h->progress_tag << 32;
+  for (int l = 0; l < L; ++l) c.lanes[l].bp.progress_tag = (unsigned long long)h->progress_tag << 32;
   if (h->profiling) {
     if ((rc = ensure(h, h->counters, GTO_PROF_VARIANTS * 64 * sizeof(unsigned long long)))) return rc;
     HIPCHK(h, hipMemsetAsync(h->counters.p, 0, GTO_PROF_VARIANTS * 64 * sizeof(unsigned long long), st));
     bp.work = (unsigned long long*)h->counters.p;  // 64 cells per kernel variant (launch_obstacle picks the variant's)
-    for (int l = 0; l < L; ++l) lanes[l].bp.work = bp.work;
+    for (int l = 0; l < L; ++l) c.lanes[l].bp.work = bp.work;
   }
   // The broad phase ahead of the obstacle launch, in the rounds that fill the GPU: the step kernel settles the waypoint
   // groups none of whose bounding spheres can reach a non-zero voxel record and lists the others (prebroad_tail); the
   // launch is laid out over that list.  Needs: the groups of the launch it feeds (consecutive waypoints), room for one
   // pass in the step kernel's dead LDS, at most GTO_PB_PARK parked frames in its serial walk over the kinematic tree.
-  const int pb_tg = std::max(1, std::min(h->obs_tg, T - 2)), pb_ng = (T - 2 + pb_tg - 1) / pb_tg;
+  const int pb_tg = std::max(1, std::min(h->tu.obs_tg, T - 2));
+  c.pb_ng = (T - 2 + pb_tg - 1) / pb_tg;
   const PbLayout pbl(T, h->rb.n_frames, h->pb_C, h->rb.pb_npar);
-  const bool pb_able = h->prebroad && h->np == GTO_NB && pb_ng <= 64 && h->obs_interleave != 1 && h->rb.n_xst <= GTO_PB_PARK && pbl.pw >= 1 && h->pb_C >= 1;
+  c.pb_able = h->tu.prebroad && h->np == GTO_NB && c.pb_ng <= 64 && h->tu.obs_interleave != 1 && h->rb.n_xst <= GTO_PB_PARK && pbl.pw >= 1 && h->pb_C >= 1;
   for (int l = 0; l < L; ++l) {
-    SolveParams& lsp = lanes[l].sp;
-    lsp.pb_tg = pb_tg, lsp.pb_ng = pb_ng, lsp.pb_pw = std::max(1, pbl.pw), lsp.pb_tab0 = pbl.tab0;
-    lsp.pb_verify = h->dbg_cut == 10;
+    SolveParams& lsp = c.lanes[l].sp;
+    lsp.pb_tg = pb_tg, lsp.pb_ng = c.pb_ng, lsp.pb_pw = std::max(1, pbl.pw), lsp.pb_tab0 = pbl.tab0;
+    lsp.pb_verify = h->tu.dbg_cut == 10;
   }
-  sp.pb_tg = pb_tg, sp.pb_ng = pb_ng, sp.pb_pw = std::max(1, pbl.pw), sp.pb_tab0 = pbl.tab0;
-  for (int l = 0; l < L; ++l) {  // seeds, goal terms of the seeds, the lane's lists of round 0
-    if (h->np == GTO_NB) hipLaunchKernelGGL(k_lm_init<GTO_NB>, dim3(lanes[l].n), dim3(256), 0, st, h->d_rb, lanes[l].bp, lanes[l].sp, B, 0);
-    else hipLaunchKernelGGL(k_lm_init<16>, dim3(lanes[l].n), dim3(256), 0, st, h->d_rb, lanes[l].bp, lanes[l].sp, B, 0);
+  sp.pb_tg = pb_tg, sp.pb_ng = c.pb_ng, sp.pb_pw = std::max(1, pbl.pw), sp.pb_tab0 = pbl.tab0;
+  return GTO_OK;
+}
+
+// A round of a lane: one obstacle launch that evaluates the candidate trial trajectories of the instances in flight, one
+// step launch that accepts, solves and makes new candidates.
+enum StepVariant { STEP_FULL, STEP_FEW, STEP_WIDE };  // k_lm_step<4, 1>, k_lm_step<8, GTO_KSPEC>, k_lm_step_wide<16>
+struct RoundPlan {
+  int in_flight = 0;
+  int span = 0;            // positions this round's lists span: the step launch's grid
+  bool few = false;        // at most few_instances in flight
+  bool interleave = false;  // SolveParams::interleave
+  ObsLaunch obs;           // the obstacle launch
+  StepVariant step = STEP_FULL;
+  int k_acc = 1, k_rej = 1, spec_streak = 0;  // STEP_FEW: candidates after an accept / a rejection, SolveParams::spec_streak
+  bool pb_next = false, static_pos = false;   // STEP_FULL: the broad phase of the next round, static list positions
+  int k_next = 1;          // candidates per instance the step launch generates (the next round's k_prev)
+  bool pb_off = false;     // the lane's broad phase stays off from now on
+  double ratio_max = 0.0;  // the lane's largest items per job so far
+};
+
+// (b) what the next round of lane ln launches, from the tunables and the lane's state.  No HIP call, no allocation, no
+// lock: rounds with few instances in flight last 25-60 us and are bound by how fast the host enqueues them.
+static RoundPlan plan_round(const gto_handle* h, const SolveCall& c, const LaneCtx& ln) {
+  const Tunables& tu = h->tu;
+  RoundPlan p;
+  p.in_flight = std::min(ln.room, ln.n_resp - ln.known_done);
+  p.few = p.in_flight <= tu.few_instances;
+  // compact lists hold the instances in flight; lists of a launch with static positions keep that launch's span
+  // (instances that finished without a successor left void positions behind)
+  p.span = ln.span_prev ? ln.span_prev : p.in_flight;
+  p.interleave = tu.obs_interleave == 1 || (tu.obs_interleave == 2 && p.few);
+  p.pb_off = ln.pb_off;
+  p.ratio_max = ln.ratio_max;
+  p.k_next = ln.k_prev;
+  const bool large_call = ln.n_resp > tu.spec_deep;  // (its tail: the other lanes' launches are on the GPU, too)
+  ObsLaunch& o = p.obs;
+  o.nT = c.T - 2;
+  o.timed = h->profiling;
+  o.goal_terms = true;
+  o.n_jobs = p.span * ln.k_prev;
+  o.tg = p.few ? (large_call ? tu.obs_tg_few_tail : tu.obs_tg_few) : tu.obs_tg;
+  o.deep = p.few && tu.obs_deep && p.in_flight <= GTO_OBS_DEEP_MAX;
+  o.itemized = ln.items_ready && !p.few;
+  // length of this round's item list, estimated: what the lane's step launches published last (a few rounds old; the
+  // list changes by a few per cent a round), or, until then, the previous call's ratio of items to jobs
+  if (o.itemized && tu.item_grid) {
+    const unsigned long long p2 = __atomic_load_n(ln.h_prog + 2, __ATOMIC_RELAXED);
+    const int jobs_bound = p.in_flight * ln.k_prev;
+    if ((unsigned)(p2 >> 32) == h->progress_tag && (p2 & 0xfffffull) > 0 && (p2 & 0xfffffull) < 0xfffffull) {
+      const double items_seen = (double)(p2 & 0xfffffull), jobs_seen = (double)((p2 >> 20) & 0xfffull);
+      o.items_hint = (int)(1.5 * items_seen) + 256;
+      if (jobs_seen > 0 && jobs_seen < 4095) p.ratio_max = std::max(p.ratio_max, items_seen / jobs_seen);
+    } else if (h->items_per_job_prior > 0.0) {
+      o.items_hint = (int)(1.25 * h->items_per_job_prior * jobs_bound) + 256;
+    }
+    if (tu.item_hint_forced > 0) o.items_hint = tu.item_hint_forced;  // (tests: a launch of a few workgroups, the crew does the rest)
   }
-  {
-    BatchPtrs bpi = bp;  // the init pass indexes the batch directly
-    if ((rc = launch_obstacle(h, st, bpi, sp, B, 0, 4, 1, false))) return rc;
-  }
-  if (L > 1) {
-    HIPCHK(h, hipEventRecord(h->lane_event[0], st));
-    for (int l = 0; l < L; ++l) HIPCHK(h, hipStreamWaitEvent(lanes[l].st, h->lane_event[0], 0));
-  }
-  // one round = evaluate the candidate trial trajectories of the instances in flight (obstacle kernel) +
-  // accept/solve/new candidates (step kernel).  An instance may start late: enough rounds for every position to serve its
-  // share one after the other.
-  auto read_progress = [&](LaneCtx& ln) {
-    const unsigned long long p0 = __atomic_load_n(ln.h_prog, __ATOMIC_RELAXED), p1 = __atomic_load_n(ln.h_prog + 1, __ATOMIC_RELAXED);
-    if ((unsigned)(p0 >> 32) == h->progress_tag) ln.known_done = std::max(ln.known_done, (int)(p0 & 0xffffffffull));
-    if ((unsigned)(p1 >> 32) == h->progress_tag) ln.seen_round = std::max(ln.seen_round, (int)(p1 & 0xffffffffull));
-  };
-  // naps of the throttle below: tens of microseconds, which the default timer slack of a thread (50 us) would double
-  const int old_slack = prctl(PR_GET_TIMERSLACK);
-  if (old_slack > 1000) (void)prctl(PR_SET_TIMERSLACK, 1000UL);
-  int rc_loop = GTO_OK;
-  const auto tp_start = std::chrono::steady_clock::now();
-  // one round of lane ln: returns GTO_OK or an error
-  auto enqueue_round = [&](LaneCtx& ln, int lane_index) -> int {
-    const int k = ln.k;
-    const int in_flight = std::min(ln.room, ln.n_resp - ln.known_done);
-    const bool few = in_flight <= h->few_instances;
-    // positions this round's lists span: compact lists hold the instances in flight; lists of a launch with static positions
-    // keep that launch's span (instances that finished without a successor left void positions behind)
-    const int span = ln.span_prev ? ln.span_prev : in_flight;
-    ln.span_prev = 0;
-    if (few && !ln.few_us) ln.few_us = (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - tp_start).count();
-    const bool large_call = ln.n_resp > h->spec_deep;  // (its tail: the other lanes' launches are on the GPU, too)
-    const int tg = few ? (large_call ? h->obs_tg_few_tail : h->obs_tg_few) : h->obs_tg;
-    SolveParams& lsp = ln.sp;
-    lsp.interleave = h->obs_interleave == 1 || (h->obs_interleave == 2 && few);
-    const bool itemized = ln.items_ready && !few;
-    ln.items_ready = false;
-    lsp.round = k;
-    lsp.parity = k & 1;
-    // the goal workgroups skip fresh instances themselves: k_lm_init already produced the seed's goal terms
-    lsp.k_eval = ln.k_prev;
-    int rc_;
-    // length of this round's item list, estimated: what the lane's step launches published last (a few rounds old; the
-    // list changes by a few per cent a round), or, until then, the previous call's ratio of items to jobs
-    int items_hint = 0;
-    if (itemized && h->item_grid) {
+  if (h->np != GTO_NB) {
+    p.step = STEP_WIDE;
+  } else if (p.few && tu.step_nw_few == 8) {
+    // few instances in flight: eight waves per instance and candidate trial points ahead of their evaluation
+    p.step = STEP_FEW;
+    const int k_budget = std::max(1, tu.spec_jobs / std::max(1, p.in_flight));
+    p.k_acc = p.in_flight <= std::min(tu.spec_deep, tu.spec_few) ? std::min(std::min(large_call ? tu.spec_acc_tail : tu.spec_acc, k_budget), h->spec_kmax) : 1;
+    p.spec_streak = large_call ? tu.spec_streak_tail : tu.spec_streak;
+    p.k_rej = p.in_flight <= tu.spec_few ? std::min(std::max(std::min(tu.spec_rej, k_budget), tu.spec_rej_few), h->spec_kmax) : 1;
+    p.k_next = std::max(p.k_acc, p.k_rej);
+  } else {
+    p.step = STEP_FULL;
+    const bool pb_ok = c.pb_able && std::min(ln.W, ln.n) > tu.few_instances;
+    // a call in which the broad phase settles next to nothing (a robot inside a shelf) stops running it: the last
+    // itemized round the host has seen listed more than 1 - GTO_PB_MIN_GAIN of its (job, group) pairs
+    if (pb_ok && !p.pb_off && !ln.sp.pb_verify) {
       const unsigned long long p2 = __atomic_load_n(ln.h_prog + 2, __ATOMIC_RELAXED);
-      const int jobs_bound = in_flight * ln.k_prev;
-      if ((unsigned)(p2 >> 32) == h->progress_tag && (p2 & 0xfffffull) > 0 && (p2 & 0xfffffull) < 0xfffffull) {
-        const double items_seen = (double)(p2 & 0xfffffull), jobs_seen = (double)((p2 >> 20) & 0xfffull);
-        items_hint = (int)(1.5 * items_seen) + 256;
-        if (jobs_seen > 0 && jobs_seen < 4095) ln.ratio_max = std::max(ln.ratio_max, items_seen / jobs_seen);
-      } else if (h->items_per_job_prior > 0.0) {
-        items_hint = (int)(1.25 * h->items_per_job_prior * jobs_bound) + 256;
+      if ((unsigned)(p2 >> 32) == h->progress_tag) {
+        const double jobs_seen = (double)((p2 >> 20) & 0xfffull), items_seen = (double)(p2 & 0xfffffull);
+        if (jobs_seen > 0 && items_seen > 0 && jobs_seen < 4095 && ln.k >= 12 && items_seen > (1.0 - tu.pb_min_gain) * jobs_seen * c.pb_ng) p.pb_off = true;
       }
-      if (h->item_hint_forced > 0) items_hint = h->item_hint_forced;  // (tests: a launch of a few workgroups, the crew does the rest)
     }
-    if ((rc_ = launch_obstacle(h, ln.st, ln.bp, lsp, B, 2, T - 2, 0, h->profiling, true, span * ln.k_prev, tg, few && h->obs_deep && in_flight <= h->obs_deep_max, itemized, items_hint))) return rc_;
-    if (h->np == GTO_NB) {
-      if (few && h->step_nw_few == 8) {
-        // few instances in flight: eight waves per instance and candidate trial points ahead of their evaluation
-        const int k_budget = std::max(1, h->spec_jobs / std::max(1, in_flight));
-        lsp.k_acc = in_flight <= std::min(h->spec_deep, h->spec_few) ? std::min(std::min(large_call ? h->spec_acc_tail : h->spec_acc, k_budget), h->spec_kmax) : 1;
-        lsp.spec_streak = large_call ? h->spec_streak_tail : h->spec_streak;
-        lsp.k_rej = in_flight <= h->spec_few ? std::min(std::max(std::min(h->spec_rej, k_budget), h->spec_rej_few), h->spec_kmax) : 1;
-        const int kl = std::max(lsp.k_acc, lsp.k_rej);
-        lsp.pb_next = 0;
-        if (h->profiling && (rc_ = prof_begin(h, ln.st, GTO_PROF_STEP_FEW, in_flight))) return rc_;
-        lsp.static_pos = 0;
-        hipLaunchKernelGGL((k_lm_step<8, GTO_KSPEC>), dim3(span), dim3(512), lm_lds_bytes(T, kl), ln.st, h->d_rb, h->d_pbchunks, ln.bp, lsp, B);
-        if (h->profiling && (rc_ = prof_end(h, ln.st))) return rc_;
-        ln.k_prev = kl;
-      } else {
-        lsp.k_acc = lsp.k_rej = 1;
-        const bool pb_ok = pb_able && std::min(ln.W, ln.n) > h->few_instances;
-        // a call in which the broad phase settles next to nothing (a robot inside a shelf) stops running it: the last
-        // itemized round the host has seen listed more than 1 - GTO_PB_MIN_GAIN of its (job, group) pairs
-        if (pb_ok && !ln.pb_off && !lsp.pb_verify) {
-          const unsigned long long p2 = __atomic_load_n(ln.h_prog + 2, __ATOMIC_RELAXED);
-          if ((unsigned)(p2 >> 32) == h->progress_tag) {
-            const double jobs_seen = (double)((p2 >> 20) & 0xfffull), items_seen = (double)(p2 & 0xfffffull);
-            if (jobs_seen > 0 && items_seen > 0 && jobs_seen < 4095 && k >= 12 && items_seen > (1.0 - h->pb_min_gain) * jobs_seen * pb_ng) ln.pb_off = true;
-          }
-        }
-        lsp.pb_next = pb_ok && !ln.pb_off && !few;
-        if (h->profiling && (rc_ = prof_begin(h, ln.st, GTO_PROF_STEP, in_flight))) return rc_;
-        lsp.static_pos = h->static_pos && L == 1 && !few;
-        hipLaunchKernelGGL((k_lm_step<4, 1>), dim3(span), dim3(256), h->lm_lds, ln.st, h->d_rb, h->d_pbchunks, ln.bp, lsp, B);
-        if (lsp.static_pos) ln.span_prev = span;
-        if (h->profiling && (rc_ = prof_end(h, ln.st))) return rc_;
-        ln.k_prev = 1;
-        ln.items_ready = lsp.pb_next != 0;
-      }
-    } else {
-      if (h->profiling && (rc_ = prof_begin(h, ln.st, GTO_PROF_STEP, in_flight))) return rc_;
-      hipLaunchKernelGGL(k_lm_step_wide<16>, dim3(in_flight), dim3(GTO_WIDE_NT), h->lm_lds, ln.st, h->d_rb, ln.bp, lsp, B,
-                         (double*)h->zws.p + (size_t)lane_zws[lane_index] * (T - 2) * h->np * h->np);
-      if (h->profiling && (rc_ = prof_end(h, ln.st))) return rc_;
-    }
-    ln.k++;
-    return GTO_OK;
-  };
-  // One host thread per lane (lane 0: the caller's), as many as the call has lanes: a round of a lane with few instances
-  // in flight lasts 25-50 us and takes two launches to enqueue, which one thread cannot do for four lanes.
-  struct Handover { int lane, parity, count, k_prev; };
-  std::mutex mu;                     // hand-over requests, the error string, the profiling records
-  std::vector<Handover> requests;
-  int reserved = 0;                  // instances granted to lane 0 whose k_adopt it has not enqueued yet
-  std::atomic<int> rem0_pub{lanes[0].n}, others_open{L - 1}, failed{0};
-  const int adopt_limit = std::min(h->few_instances, lanes[0].cap);
-  h->prof_mu = L > 1 ? &mu : nullptr;
-  // waits until lane ln may enqueue its next round (throttle: never more than `ahead` rounds in front of the last step
-  // launch seen running, so that the launches stay sized to what is left and the empty rounds after the last instance
-  // finishes stay few; sleep-poll, not a blocking wait: the runtime spins in those, one host core per lane)
-  auto throttle = [&](LaneCtx& ln) -> int {
-    for (long naps = 0;; ++naps) {
-      read_progress(ln);
-      const bool few = std::min(ln.room, ln.n_resp - ln.known_done) <= h->few_instances;
-      if (ln.k - ln.seen_round <= (few ? h->ahead_few : h->ahead) + 1 || failed.load(std::memory_order_relaxed)) return GTO_OK;
-      std::this_thread::sleep_for(std::chrono::microseconds(few ? h->nap_few_us : h->nap_us));
-      if ((naps & 1023) == 1023) {  // a stream that went idle or failed without reaching the round: do not wait for ever
-        const hipError_t qe = hipStreamQuery(ln.st);
-        if (qe != hipErrorNotReady) {
-          read_progress(ln);
-          if (ln.k - ln.seen_round > (few ? h->ahead_few : h->ahead) + 1) {
-            std::lock_guard<std::mutex> g(mu);
-            h->err = qe == hipSuccess ? "solve loop: the stream went idle before the rounds it was given ran" : std::string("solve loop: ") + hipGetErrorString(qe);
-            return GTO_ERR_HIP;
-          }
+    p.pb_next = pb_ok && !p.pb_off && !p.few;
+    p.static_pos = tu.static_pos && c.L == 1 && !p.few;
+    p.k_next = 1;
+  }
+  return p;
+}
+
+// (c) enqueues the round the plan describes on the lane's stream, and moves the lane to the next round
+static int enqueue_round(gto_handle* h, const SolveCall& c, LaneCtx& ln, int lane_index, const RoundPlan& p) {
+  const int B = c.B, T = c.T;
+  SolveParams& lsp = ln.sp;
+  lsp.interleave = p.interleave;
+  lsp.round = ln.k;
+  lsp.parity = ln.k & 1;
+  lsp.k_eval = ln.k_prev;  // the goal workgroups skip fresh instances themselves: k_lm_init already produced the seed's goal terms
+  int rc;
+  if ((rc = launch_obstacle(h, ln.st, ln.bp, lsp, B, p.obs))) return rc;
+  if (h->profiling && (rc = prof_begin(h, ln.st, p.step == STEP_FEW ? GTO_PROF_STEP_FEW : GTO_PROF_STEP, p.in_flight))) return rc;
+  if (p.step == STEP_FEW) {
+    lsp.k_acc = p.k_acc, lsp.k_rej = p.k_rej, lsp.spec_streak = p.spec_streak;
+    lsp.pb_next = 0, lsp.static_pos = 0;
+    hipLaunchKernelGGL((k_lm_step<8, GTO_KSPEC>), dim3(p.span), dim3(512), lm_lds_bytes(T, p.k_next), ln.st, h->d_rb, h->d_pbchunks, ln.bp, lsp, B);
+  } else if (p.step == STEP_FULL) {
+    lsp.k_acc = lsp.k_rej = 1;
+    lsp.pb_next = p.pb_next, lsp.static_pos = p.static_pos;
+    hipLaunchKernelGGL((k_lm_step<4, 1>), dim3(p.span), dim3(256), h->lm_lds, ln.st, h->d_rb, h->d_pbchunks, ln.bp, lsp, B);
+  } else {
+    hipLaunchKernelGGL(k_lm_step_wide<16>, dim3(p.in_flight), dim3(GTO_WIDE_NT), h->lm_lds, ln.st, h->d_rb, ln.bp, lsp, B,
+                       (double*)h->zws.p + (size_t)c.lane_zws[lane_index] * (T - 2) * h->np * h->np);
+  }
+  if (h->profiling && (rc = prof_end(h, ln.st))) return rc;
+  ln.span_prev = p.static_pos ? p.span : 0;
+  ln.items_ready = p.pb_next;
+  ln.k_prev = p.k_next;
+  ln.pb_off = p.pb_off;
+  ln.ratio_max = p.ratio_max;
+  ln.k++;
+  return GTO_OK;
+}
+
+static void read_progress(unsigned tag, LaneCtx& ln) {
+  const unsigned long long p0 = __atomic_load_n(ln.h_prog, __ATOMIC_RELAXED), p1 = __atomic_load_n(ln.h_prog + 1, __ATOMIC_RELAXED);
+  if ((unsigned)(p0 >> 32) == tag) ln.known_done = std::max(ln.known_done, (int)(p0 & 0xffffffffull));
+  if ((unsigned)(p1 >> 32) == tag) ln.seen_round = std::max(ln.seen_round, (int)(p1 & 0xffffffffull));
+}
+
+// (d) waits until lane ln may enqueue its next round (throttle: never more than `ahead` rounds in front of the last step
+// launch seen running, so that the launches stay sized to what is left and the empty rounds after the last instance
+// finishes stay few; sleep-poll, not a blocking wait: the runtime spins in those, one host core per lane)
+static int throttle(SolveCall& c, LaneCtx& ln) {
+  gto_handle* h = c.h;
+  for (long naps = 0;; ++naps) {
+    read_progress(h->progress_tag, ln);
+    const bool few = std::min(ln.room, ln.n_resp - ln.known_done) <= h->tu.few_instances;
+    if (ln.k - ln.seen_round <= (few ? h->tu.ahead_few : h->tu.ahead) + 1 || c.failed.load(std::memory_order_relaxed)) return GTO_OK;
+    std::this_thread::sleep_for(std::chrono::microseconds(few ? GTO_NAP_FEW_US : GTO_NAP_US));
+    if ((naps & 1023) == 1023) {  // a stream that went idle or failed without reaching the round: do not wait for ever
+      const hipError_t qe = hipStreamQuery(ln.st);
+      if (qe != hipErrorNotReady) {
+        read_progress(h->progress_tag, ln);
+        if (ln.k - ln.seen_round > (few ? h->tu.ahead_few : h->tu.ahead) + 1) {
+          std::lock_guard<std::mutex> g(c.mu);
+          h->err = qe == hipSuccess ? "solve loop: the stream went idle before the rounds it was given ran" : std::string("solve loop: ") + hipGetErrorString(qe);
+          return GTO_ERR_HIP;
         }
       }
     }
-  };
-  auto lane_main = [&](int l) {
-    LaneCtx& ln = lanes[l];
-    (void)hipSetDevice(h->device);
-    const int old_slack_ = prctl(PR_GET_TIMERSLACK);
-    if (l > 0 && old_slack_ > 1000) (void)prctl(PR_SET_TIMERSLACK, 1000UL);
-    int rc_ = GTO_OK;
-    for (;;) {
-      if (failed.load(std::memory_order_relaxed)) break;
-      if ((rc_ = throttle(ln))) break;
-      int remaining = ln.n_resp - ln.known_done;
-      if (l == 0) {
-        // hand-overs granted since the last round: behind the lane's last launch (its event) and behind this lane's
-        {
-          std::lock_guard<std::mutex> g(mu);
-          for (const Handover& r : requests) {
-            LaneCtx& src = lanes[r.lane];
-            if (hipStreamWaitEvent(ln.st, h->lane_event[r.lane], 0) != hipSuccess) { h->err = "solve loop: hand-over between lanes failed"; rc_ = GTO_ERR_HIP; break; }
-            hipLaunchKernelGGL(k_adopt, dim3(1), dim3(256), 0, ln.st, src.bp, r.parity, ln.bp, ln.k & 1, kcap, T * nF, src.n_resp, r.count);
-            ln.n_resp += r.count;
-            ln.room = std::min(ln.cap, ln.room + r.count);
-            ln.k_prev = std::max(ln.k_prev, r.k_prev);
-            ln.items_ready = false;
-            reserved -= r.count;
-          }
-          requests.clear();
-          remaining = ln.n_resp - ln.known_done;
-          rem0_pub.store(std::max(0, remaining), std::memory_order_relaxed);
+  }
+}
+
+// (d) the host thread of lane l: throttle, hand-overs, rounds until the lane is done
+static void lane_main(SolveCall& c, int l) {
+  gto_handle* h = c.h;
+  LaneCtx& ln = c.lanes[l];
+  (void)hipSetDevice(h->device);
+  const int old_slack_ = prctl(PR_GET_TIMERSLACK);
+  if (l > 0 && old_slack_ > 1000) (void)prctl(PR_SET_TIMERSLACK, 1000UL);
+  int rc_ = GTO_OK;
+  for (;;) {
+    if (c.failed.load(std::memory_order_relaxed)) break;
+    if ((rc_ = throttle(c, ln))) break;
+    int remaining = ln.n_resp - ln.known_done;
+    if (l == 0) {
+      // hand-overs granted since the last round: behind the lane's last launch (its event) and behind this lane's
+      {
+        std::lock_guard<std::mutex> g(c.mu);
+        for (const Handover& r : c.requests) {
+          LaneCtx& src = c.lanes[r.lane];
+          if (hipStreamWaitEvent(ln.st, h->lane_event[r.lane], 0) != hipSuccess) { h->err = "solve loop: hand-over between lanes failed"; rc_ = GTO_ERR_HIP; break; }
+          hipLaunchKernelGGL(k_adopt, dim3(1), dim3(256), 0, ln.st, src.bp, r.parity, ln.bp, ln.k & 1, c.kcap, c.T * c.nF, src.n_resp, r.count);
+          ln.n_resp += r.count;
+          ln.room = std::min(ln.cap, ln.room + r.count);
+          ln.k_prev = std::max(ln.k_prev, r.k_prev);
+          ln.items_ready = false;
+          c.reserved -= r.count;
         }
-        if (rc_) break;
-        if (remaining <= 0) {
-          if (others_open.load(std::memory_order_acquire) == 0) {
-            std::lock_guard<std::mutex> g(mu);
-            if (requests.empty()) break;
-            continue;
-          }
-          std::this_thread::sleep_for(std::chrono::microseconds(10));
+        c.requests.clear();
+        remaining = ln.n_resp - ln.known_done;
+        c.rem0_pub.store(std::max(0, remaining), std::memory_order_relaxed);
+      }
+      if (rc_) break;
+      if (remaining <= 0) {
+        if (c.others_open.load(std::memory_order_acquire) == 0) {
+          std::lock_guard<std::mutex> g(c.mu);
+          if (c.requests.empty()) break;
           continue;
         }
-      } else {
-        if (remaining <= 0) break;
-        // hand-over: everything this lane has left is in flight (remaining <= W) and few, and lane 0 has room
-        if (h->adopt_below > 0 && remaining <= h->adopt_below && remaining <= ln.W && ln.k > 0) {
-          std::lock_guard<std::mutex> g(mu);
-          const int rem0 = rem0_pub.load(std::memory_order_relaxed);
-          if (rem0 <= lanes[0].W && rem0 + reserved + remaining <= adopt_limit) {
-            if (hipEventRecord(h->lane_event[l], ln.st) != hipSuccess) { h->err = "solve loop: hand-over between lanes failed"; rc_ = GTO_ERR_HIP; break; }
-            reserved += remaining;
-            requests.push_back({l, ln.k & 1, remaining, ln.k_prev});
-            ln.handed = true;
-            break;
-          }
+        std::this_thread::sleep_for(std::chrono::microseconds(10));
+        continue;
+      }
+    } else {
+      if (remaining <= 0) break;
+      // hand-over: everything this lane has left is in flight (remaining <= W) and few, and lane 0 has room
+      if (h->tu.adopt_below > 0 && remaining <= h->tu.adopt_below && remaining <= ln.W && ln.k > 0) {
+        std::lock_guard<std::mutex> g(c.mu);
+        const int rem0 = c.rem0_pub.load(std::memory_order_relaxed);
+        if (rem0 <= c.lanes[0].W && rem0 + c.reserved + remaining <= c.adopt_limit) {
+          if (hipEventRecord(h->lane_event[l], ln.st) != hipSuccess) { h->err = "solve loop: hand-over between lanes failed"; rc_ = GTO_ERR_HIP; break; }
+          c.reserved += remaining;
+          c.requests.push_back({l, ln.k & 1, remaining, ln.k_prev});
+          ln.handed = true;
+          break;
         }
       }
-      const int max_rounds = ((ln.n_resp + ln.W - 1) / std::max(1, ln.W) + 1) * (sp.max_iter + 2) + 8;
-      if (ln.k > max_rounds) {
-        std::lock_guard<std::mutex> g(mu);
-        h->err = "solve loop: a lane ran out of rounds";
-        rc_ = GTO_ERR_HIP;
-        break;
-      }
-      if ((rc_ = enqueue_round(ln, l))) break;
     }
-    if (rc_) failed.store(rc_, std::memory_order_relaxed);
-    ln.end_us = (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - tp_start).count();
-    if (l > 0) {
-      others_open.fetch_sub(1, std::memory_order_release);
-      if (old_slack_ > 1000) (void)prctl(PR_SET_TIMERSLACK, (unsigned long)old_slack_);
+    const int max_rounds = ((ln.n_resp + ln.W - 1) / std::max(1, ln.W) + 1) * (c.max_iter + 2) + 8;
+    if (ln.k > max_rounds) {
+      std::lock_guard<std::mutex> g(c.mu);
+      h->err = "solve loop: a lane ran out of rounds";
+      rc_ = GTO_ERR_HIP;
+      break;
     }
-  };
-  {
-    static const bool lane_dbg = getenv("GTO_LANE_DEBUG") != nullptr;
-    const auto tp0 = std::chrono::steady_clock::now();
-    std::vector<std::thread> workers;
-    for (int l = 1; l < L; ++l) workers.emplace_back(lane_main, l);
-    const auto tp1 = std::chrono::steady_clock::now();
-    lane_main(0);
-    const auto tp2 = std::chrono::steady_clock::now();
-    for (auto& w : workers) w.join();
-    const auto tp3 = std::chrono::steady_clock::now();
-    if (lane_dbg) {
-      auto us = [](auto a, auto b) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
-      fprintf(stderr, "[gto lanes] B %d L %d: threads started %ld us | lane 0 returned %ld us | joined %ld us | rounds", B, L, us(tp0, tp1), us(tp0, tp2), us(tp0, tp3));
-      for (int l = 0; l < L; ++l) fprintf(stderr, " %d%s@%ld(few@%ld)", lanes[l].k, lanes[l].handed ? "h" : "", lanes[l].end_us, lanes[l].few_us);
-      fprintf(stderr, "\n");
-    }
+    const RoundPlan plan = plan_round(h, c, ln);
+    if (plan.few && !ln.few_us) ln.few_us = (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - c.tp_start).count();
+    if ((rc_ = enqueue_round(h, c, ln, l, plan))) break;
   }
+  if (rc_) c.failed.store(rc_, std::memory_order_relaxed);
+  ln.end_us = (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - c.tp_start).count();
+  if (l > 0) {
+    c.others_open.fetch_sub(1, std::memory_order_release);
+    if (old_slack_ > 1000) (void)prctl(PR_SET_TIMERSLACK, (unsigned long)old_slack_);
+  }
+}
+
+// (d) runs the lanes (lane 0 on the calling thread) and returns the first error of any of them
+static int run_lanes(SolveCall& c) {
+  gto_handle* h = c.h;
+  const int L = c.L;
+  c.rem0_pub.store(c.lanes[0].n), c.others_open.store(L - 1), c.failed.store(0);
+  c.adopt_limit = std::min(h->tu.few_instances, c.lanes[0].cap);
+  h->prof_mu = L > 1 ? &c.mu : nullptr;
+  const auto tp0 = std::chrono::steady_clock::now();
+  std::vector<std::thread> workers;
+  for (int l = 1; l < L; ++l) workers.emplace_back(lane_main, std::ref(c), l);
+  const auto tp1 = std::chrono::steady_clock::now();
+  lane_main(c, 0);
+  const auto tp2 = std::chrono::steady_clock::now();
+  for (auto& w : workers) w.join();
+  const auto tp3 = std::chrono::steady_clock::now();
   h->prof_mu = nullptr;
-  rc_loop = failed.load();
+  if (h->tu.lane_debug) {
+    auto us = [](auto a, auto b) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
+    fprintf(stderr, "[gto lanes] B %d L %d: threads started %ld us | lane 0 returned %ld us | joined %ld us | rounds", c.B, L, us(tp0, tp1), us(tp0, tp2), us(tp0, tp3));
+    for (int l = 0; l < L; ++l) fprintf(stderr, " %d%s@%ld(few@%ld)", c.lanes[l].k, c.lanes[l].handed ? "h" : "", c.lanes[l].end_us, c.lanes[l].few_us);
+    fprintf(stderr, "\n");
+  }
+  return c.failed.load();
+}
+
+// (e) gto_last_kernel_profile / _time / _work of a profiled call: the events and work counters of its launches
+static int harvest_profile(gto_handle* h, hipStream_t st, const unsigned long long* work) {
+  HIPCHK(h, hipStreamSynchronize(st));
+  for (int v = 0; v < GTO_PROF_VARIANTS; ++v) h->prof_ms[v] = 0.0, h->prof_launches[v] = h->prof_wgs[v] = 0, h->prof_points[v] = 0;
+  int n_obs = 0;
+  for (int i = 0; i < h->last_launches; ++i) {
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2 * i], h->ev[2 * i + 1]));
+    const int v = h->ev_variant[i];
+    h->prof_ms[v] += ms, h->prof_launches[v] += 1, h->prof_wgs[v] += h->ev_wgs[i];
+    n_obs += v == GTO_PROF_OBSTACLE || v == GTO_PROF_OBSTACLE_FEW;
+  }
+  unsigned long long cells[GTO_PROF_VARIANTS * 64];
+  HIPCHK(h, hipMemcpy(cells, work, sizeof cells, hipMemcpyDeviceToHost));
+  for (int v = 0; v < GTO_PROF_VARIANTS; ++v)
+    for (int c = 0; c < 64; ++c) h->prof_points[v] += cells[64 * v + c];
+  // gto_last_kernel_time / _work: the obstacle kernel, both variants together (what they always reported)
+  h->last_ms = h->prof_ms[GTO_PROF_OBSTACLE] + h->prof_ms[GTO_PROF_OBSTACLE_FEW];
+  h->last_launches = n_obs;
+  h->last_counters[0] = h->prof_points[GTO_PROF_OBSTACLE] + h->prof_points[GTO_PROF_OBSTACLE_FEW];
+  h->last_counters[1] = 0;
+  return GTO_OK;
+}
+
+// (f) GTO_DEBUG_TIMING: the phase stamps the kernels of the call left in h->dbg
+static int print_debug_stamps(gto_handle* h, hipStream_t st) {
+  HIPCHK(h, hipStreamSynchronize(st));
+  long long t[256];
+  HIPCHK(h, hipMemcpy(t, h->dbg, sizeof t, hipMemcpyDeviceToHost));
+  fprintf(stderr, "[gto dbg] step-kernel phases (cycles) P0+P1 %lld | P2 %lld | diag %lld | dense %lld | back %lld | P4 %lld | P5 %lld | s_dense %lld\n",
+          t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4], t[6] - t[5], t[7] - t[6], t[9]);
+  if (h->np != GTO_NB)
+    fprintf(stderr, "[gto dbg] wide step kernel, sweeps (cycles): downward: %lld in %lld dense inversions, sweep %lld | upward: %lld in %lld dense inversions, sweep %lld\n",
+            t[56], t[57], t[58], t[59], t[60], t[61]);
+  fprintf(stderr, "[gto dbg] solve by wave (cycles from the start of P3): downward sweep: diagonal stretch %lld, its dense blocks %lld | upward sweep %lld | meeting block %lld | back substitution from its start: downward wave dense %lld, diagonal stretch %lld | upward wave %lld\n",
+          t[3] - t[2], t[41] - t[2], t[17] - t[2], t[42] - t[4], t[18] - t[42], t[19] - t[42], t[26] - t[42]);
+  fprintf(stderr, "[gto dbg] sweeps of the other candidates' waves (2..6) done at (cycles from the start of P3, 0 = no candidate): %lld %lld %lld %lld %lld | barrier passed at %lld\n",
+          t[43] ? t[43] - t[2] : 0, t[44] ? t[44] - t[2] : 0, t[45] ? t[45] - t[2] : 0, t[46] ? t[46] - t[2] : 0, t[47] ? t[47] - t[2] : 0, t[4] - t[2]);
+  fprintf(stderr, "[gto dbg] broad phase in the step kernel's tail (cycles): entry+tables %lld | barrier %lld | A (local transforms, pass 0) %lld | B (chain) %lld | C (sphere tests) %lld | other passes %lld | outputs %lld\n",
+          t[33] - t[6], t[34] - t[33], t[35] - t[34], t[36] - t[35], t[37] - t[36], t[38] - t[37], t[39] - t[38]);
+  fprintf(stderr, "[gto dbg] P2 split (cycles): loads+barrier %lld | b-vector+masks %lld | blocks %lld | e,y+barrier %lld\n", t[28] - t[1], t[29] - t[28], t[30] - t[29], t[2] - t[30]);
+  fprintf(stderr, "[gto dbg] fk_mfma_tree (cycles): local %lld | rounds %lld %lld %lld %lld | outputs %lld\n", t[21] - t[20], t[22] - t[21], t[23] - t[22], t[24] - t[23], t[25] - t[24], t[27] - t[25]);
+  // (only with -DGTO_DEBUG_LONGEST_WG: the extra clocks cost the tuned obstacle kernel registers)
+  fprintf(stderr, "[gto dbg] longest regular obstacle workgroup of the call: %lld cycles with %lld surviving chunks | goal-term wavefront of instance 0: %lld cycles\n",
+          t[40] >> 16, t[40] & 0xffff, t[32] - t[31]);
+  if (t[64] || t[65]) {  // -DGTO_DEBUG_LONGEST_WG
+    long long tot_ = 0;
+    for (int i = 64; i < 128; ++i) tot_ += t[i];
+    fprintf(stderr, "[gto dbg] regular obstacle workgroups of the call: %lld, none of whose keys got a contribution: %lld | surviving chunks per workgroup (0,1,2,...,63+):", tot_, t[48]);
+    for (int i = 64; i < 128; ++i) fprintf(stderr, " %lld", t[i]);
+    fprintf(stderr, "\n");
+    fprintf(stderr, "[gto dbg] ticks those workgroups ran, summed by surviving chunks (0,1,2,...,63+):");
+    for (int i = 192; i < 256; ++i) fprintf(stderr, " %lld", t[i]);
+    fprintf(stderr, "\n");
+  }
+  fprintf(stderr, "[gto dbg] broad phase of the step kernel (GTO_DEBUG_CUT=10, -DGTO_DEBUG_LONGEST_WG: settled groups are looked at anyway): %lld groups settled, %lld of them with a surviving chunk, %lld with a CONTRIBUTION (must be 0)\n", t[49], t[50], t[55]);
+  {
+    fprintf(stderr, "[gto dbg] workgroups without a surviving chunk by the index shift their closest chunk tolerates (0,1,2,...,63+):");
+    for (int i = 128; i < 192; ++i) fprintf(stderr, " %lld", t[i]);
+    fprintf(stderr, "\n");
+  }
+  fprintf(stderr, "[gto dbg] obstacle WG (b=0,t=T-1) cycles: prologue %lld | broad %lld | loop %lld | epilogue %lld | active chunks %lld | prologue up to the chain %lld\n",
+          t[11] - t[10], t[12] - t[11], t[13] - t[12], t[14] - t[13], t[15], t[16] - t[10]);
+  return GTO_OK;
+}
+
+extern "C" {
+
+int gto_solve_batch_device(gto_handle* h, int32_t B, int32_t n_max, const int32_t* scene_id, const double* qc,
+                           const double* goals, const int32_t* n_goals, const double* standoff, const double* base_pos,
+                           const double* Q0, double* Q_out, double* dQ_out, double* cost_out, int32_t* iters_out,
+                           int32_t* status_out, void* stream) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (B < 0 || n_max < 1) return fail(h, GTO_ERR_INVALID_ARG, "B must be >= 0 and n_max >= 1");
+  if (B == 0) return GTO_OK;
+  if (B > GTO_JOB_MASK) return fail(h, GTO_ERR_UNSUPPORTED, "more than 16.7 million instances in one call");
+  if (!scene_id || !qc || !goals || !n_goals || !base_pos || !Q0) return fail(h, GTO_ERR_INVALID_ARG, "null input array");
+  if (h->scenes.empty()) return fail(h, GTO_ERR_NO_SCENE, "no scene has been set");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  int rc = ensure_workspace(h, B);
+  if (rc) return rc;
+  SolveParams sp = make_params(h, n_max, standoff != nullptr);
+  BatchPtrs bp = make_ptrs(h, scene_id, qc, goals, n_goals, standoff, base_pos, Q0);
+  h->last_launches = 0;
+  h->last_ms = 0.0;
+  if (h->dbg) HIPCHK(h, hipMemsetAsync(h->dbg + 40, 0, 216 * sizeof(long long), st));
+
+  SolveCall c;
+  c.h = h, c.B = B, c.T = sp.T, c.kcap = sp.kcap, c.nF = h->rb.n_frames, c.max_iter = sp.max_iter;
+  if ((rc = setup_lanes(h, st, sp, bp, c))) return rc;
+  const int L = c.L;
+  for (int l = 0; l < L; ++l)  // seeds, goal terms of the seeds, the lane's lists of round 0
+    hipLaunchKernelGGL(lm_init_kernel(h->np), dim3(c.lanes[l].n), dim3(256), 0, st, h->d_rb, c.lanes[l].bp, c.lanes[l].sp, B, 0);
+  if ((rc = launch_obstacle(h, st, bp, sp, B, init_pass()))) return rc;  // (the init pass indexes the batch directly)
+  if (L > 1) {
+    HIPCHK(h, hipEventRecord(h->lane_event[0], st));
+    for (int l = 0; l < L; ++l) HIPCHK(h, hipStreamWaitEvent(c.lanes[l].st, h->lane_event[0], 0));
+  }
+  // naps of the throttle: tens of microseconds, which the default timer slack of a thread (50 us) would double
+  const int old_slack = prctl(PR_GET_TIMERSLACK);
+  if (old_slack > 1000) (void)prctl(PR_SET_TIMERSLACK, 1000UL);
+  c.tp_start = std::chrono::steady_clock::now();
+  int rc_loop = run_lanes(c);
   {
     double r_ = 0.0;
-    for (int l = 0; l < L; ++l) r_ = std::max(r_, lanes[l].ratio_max);
+    for (int l = 0; l < L; ++l) r_ = std::max(r_, c.lanes[l].ratio_max);
     if (r_ > 0.0) h->items_per_job_prior = r_;
   }
   // the other lanes' work is behind the finalisation on the caller's stream
   for (int l = 0; l < L && L > 1 && !rc_loop; ++l)
-    if (!lanes[l].handed) {
-      if (hipEventRecord(h->lane_event[l], lanes[l].st) != hipSuccess || hipStreamWaitEvent(st, h->lane_event[l], 0) != hipSuccess) {
+    if (!c.lanes[l].handed) {
+      if (hipEventRecord(h->lane_event[l], c.lanes[l].st) != hipSuccess || hipStreamWaitEvent(st, h->lane_event[l], 0) != hipSuccess) {
         h->err = "solve loop: joining the lanes failed";
         rc_loop = GTO_ERR_HIP;
       }
     }
   if (rc_loop)  // leave nothing of this call running on streams the caller does not know about
-    for (int l = 0; l < L && L > 1; ++l) (void)hipStreamSynchronize(lanes[l].st);
-  bp.live = lanes[0].bp.live, bp.cap = lanes[0].bp.cap;  // (what the debug print below and k_lm_finalize see: lists are not read there)
+    for (int l = 0; l < L && L > 1; ++l) (void)hipStreamSynchronize(c.lanes[l].st);
+  bp.live = c.lanes[0].bp.live, bp.cap = c.lanes[0].bp.cap;  // (what k_lm_finalize sees: lists are not read there)
   if (old_slack > 1000) (void)prctl(PR_SET_TIMERSLACK, (unsigned long)old_slack);
   if (rc_loop) return rc_loop;
   hipLaunchKernelGGL(k_lm_finalize, dim3(B), dim3(64), 0, st, h->d_rb, bp, sp, B, Q_out, dQ_out, cost_out, iters_out, status_out);
   HIPCHK(h, hipGetLastError());
-  if (h->dbg) {
-    HIPCHK(h, hipStreamSynchronize(st));
-    long long t[256];
-    HIPCHK(h, hipMemcpy(t, h->dbg, sizeof t, hipMemcpyDeviceToHost));
-    fprintf(stderr, "[gto dbg] step-kernel phases (cycles) P0+P1 %lld | P2 %lld | diag %lld | dense %lld | back %lld | P4 %lld | P5 %lld | s_dense %lld\n",
-            t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4], t[6] - t[5], t[7] - t[6], t[9]);
-    if (h->np != GTO_NB)
-      fprintf(stderr, "[gto dbg] wide step kernel, sweeps (cycles): downward: %lld in %lld dense inversions, sweep %lld | upward: %lld in %lld dense inversions, sweep %lld\n",
-              t[56], t[57], t[58], t[59], t[60], t[61]);
-    fprintf(stderr, "[gto dbg] solve by wave (cycles from the start of P3): downward sweep: diagonal stretch %lld, its dense blocks %lld | upward sweep %lld | meeting block %lld | back substitution from its start: downward wave dense %lld, diagonal stretch %lld | upward wave %lld\n",
-            t[3] - t[2], t[41] - t[2], t[17] - t[2], t[42] - t[4], t[18] - t[42], t[19] - t[42], t[26] - t[42]);
-    fprintf(stderr, "[gto dbg] sweeps of the other candidates' waves (2..6) done at (cycles from the start of P3, 0 = no candidate): %lld %lld %lld %lld %lld | barrier passed at %lld\n",
-            t[43] ? t[43] - t[2] : 0, t[44] ? t[44] - t[2] : 0, t[45] ? t[45] - t[2] : 0, t[46] ? t[46] - t[2] : 0, t[47] ? t[47] - t[2] : 0, t[4] - t[2]);
-    fprintf(stderr, "[gto dbg] broad phase in the step kernel's tail (cycles): entry+tables %lld | barrier %lld | A (local transforms, pass 0) %lld | B (chain) %lld | C (sphere tests) %lld | other passes %lld | outputs %lld\n",
-            t[33] - t[6], t[34] - t[33], t[35] - t[34], t[36] - t[35], t[37] - t[36], t[38] - t[37], t[39] - t[38]);
-    fprintf(stderr, "[gto dbg] P2 split (cycles): loads+barrier %lld | b-vector+masks %lld | blocks %lld | e,y+barrier %lld\n", t[28] - t[1], t[29] - t[28], t[30] - t[29], t[2] - t[30]);
-    fprintf(stderr, "[gto dbg] fk_mfma_tree (cycles): local %lld | rounds %lld %lld %lld %lld | outputs %lld\n", t[21] - t[20], t[22] - t[21], t[23] - t[22], t[24] - t[23], t[25] - t[24], t[27] - t[25]);
-    // (only with -DGTO_DEBUG_LONGEST_WG: the extra clocks cost the tuned obstacle kernel registers)
-    fprintf(stderr, "[gto dbg] longest regular obstacle workgroup of the call: %lld cycles with %lld surviving chunks | goal-term wavefront of instance 0: %lld cycles\n",
-            t[40] >> 16, t[40] & 0xffff, t[32] - t[31]);
-    if (t[64] || t[65]) {  // -DGTO_DEBUG_LONGEST_WG
-      long long tot_ = 0;
-      for (int i = 64; i < 128; ++i) tot_ += t[i];
-      fprintf(stderr, "[gto dbg] regular obstacle workgroups of the call: %lld, none of whose keys got a contribution: %lld | surviving chunks per workgroup (0,1,2,...,63+):", tot_, t[48]);
-      for (int i = 64; i < 128; ++i) fprintf(stderr, " %lld", t[i]);
-      fprintf(stderr, "\n");
-      fprintf(stderr, "[gto dbg] ticks those workgroups ran, summed by surviving chunks (0,1,2,...,63+):");
-      for (int i = 192; i < 256; ++i) fprintf(stderr, " %lld", t[i]);
-      fprintf(stderr, "\n");
-    }
-    fprintf(stderr, "[gto dbg] broad phase of the step kernel (GTO_DEBUG_CUT=10, -DGTO_DEBUG_LONGEST_WG: settled groups are looked at anyway): %lld groups settled, %lld of them with a surviving chunk, %lld with a CONTRIBUTION (must be 0)\n", t[49], t[50], t[55]);
-    {
-      fprintf(stderr, "[gto dbg] workgroups without a surviving chunk by the index shift their closest chunk tolerates (0,1,2,...,63+):");
-      for (int i = 128; i < 192; ++i) fprintf(stderr, " %lld", t[i]);
-      fprintf(stderr, "\n");
-    }
-    fprintf(stderr, "[gto dbg] obstacle WG (b=0,t=T-1) cycles: prologue %lld | broad %lld | loop %lld | epilogue %lld | active chunks %lld | prologue up to the chain %lld\n",
-            t[11] - t[10], t[12] - t[11], t[13] - t[12], t[14] - t[13], t[15], t[16] - t[10]);
-  }
-  if (h->profiling) {
-    HIPCHK(h, hipStreamSynchronize(st));
-    for (int v = 0; v < GTO_PROF_VARIANTS; ++v) h->prof_ms[v] = 0.0, h->prof_launches[v] = h->prof_wgs[v] = 0, h->prof_points[v] = 0;
-    int n_obs = 0;
-    for (int i = 0; i < h->last_launches; ++i) {
-      float ms = 0.f;
-      HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2 * i], h->ev[2 * i + 1]));
-      const int v = h->ev_variant[i];
-      h->prof_ms[v] += ms, h->prof_launches[v] += 1, h->prof_wgs[v] += h->ev_wgs[i];
-      n_obs += v == GTO_PROF_OBSTACLE || v == GTO_PROF_OBSTACLE_FEW;
-    }
-    unsigned long long cells[GTO_PROF_VARIANTS * 64];
-    HIPCHK(h, hipMemcpy(cells, bp.work, sizeof cells, hipMemcpyDeviceToHost));
-    for (int v = 0; v < GTO_PROF_VARIANTS; ++v)
-      for (int c = 0; c < 64; ++c) h->prof_points[v] += cells[64 * v + c];
-    // gto_last_kernel_time / _work: the obstacle kernel, both variants together (what they always reported)
-    h->last_ms = h->prof_ms[GTO_PROF_OBSTACLE] + h->prof_ms[GTO_PROF_OBSTACLE_FEW];
-    h->last_launches = n_obs;
-    h->last_counters[0] = h->prof_points[GTO_PROF_OBSTACLE] + h->prof_points[GTO_PROF_OBSTACLE_FEW];
-    h->last_counters[1] = 0;
-  }
+  if (h->dbg && (rc = print_debug_stamps(h, st))) return rc;
+  if (h->profiling && (rc = harvest_profile(h, st, bp.work))) return rc;
   return GTO_OK;
 }
 
@@ -2004,11 +2141,12 @@ static int eval_common(gto_handle* h, int B, int n_max, const int32_t* scene_id,
   BatchPtrs bp = make_ptrs(h, (const int32_t*)d_sid, (const double*)d_qc, (const double*)d_goals, (const int32_t*)d_ng,
                            (const double*)d_so, (const double*)d_base, (const double*)d_Q0);
   HIPCHK(h, hipMemsetAsync(bp.n_done, 0, sizeof(int32_t), h->stream));
-  if (h->np == GTO_NB) hipLaunchKernelGGL(k_lm_init<GTO_NB>, dim3(B), dim3(256), 0, h->stream, h->d_rb, bp, sp, B, 1 /* raw: evaluate Q as given */);
-  else hipLaunchKernelGGL(k_lm_init<16>, dim3(B), dim3(256), 0, h->stream, h->d_rb, bp, sp, B, 1);
-  if ((rc = launch_obstacle(h, h->stream, bp, sp, B, 0, 4, 1, false))) return rc;
+  hipLaunchKernelGGL(lm_init_kernel(h->np), dim3(B), dim3(256), 0, h->stream, h->d_rb, bp, sp, B, 1 /* raw: evaluate Q as given */);
+  if ((rc = launch_obstacle(h, h->stream, bp, sp, B, init_pass()))) return rc;
   h->last_launches = 0;
-  if ((rc = launch_obstacle(h, h->stream, bp, sp, B, 2, (int)T - 2, 0, h->profiling))) return rc;
+  ObsLaunch ev;
+  ev.nT = (int)T - 2, ev.timed = h->profiling;
+  if ((rc = launch_obstacle(h, h->stream, bp, sp, B, ev))) return rc;
   if (h->profiling) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     float ms = 0.f;

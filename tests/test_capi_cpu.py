@@ -51,9 +51,24 @@ def test_library_of_another_abi_is_refused(capi, tmp_path):
 
 
 def test_create_validates_and_has_no_cpu_fallback(capi):
+    import copy
     import torch
     from grasptrajopt_amd.robot_desc import load_builtin
     d = load_builtin("panda")
+    # descriptor validation happens before any device work, so these run with or without a GPU
+    def malformed(edit):
+        bad_d = copy.deepcopy(d)
+        edit(bad_d)
+        return bad_d
+    cases = [
+        (lambda x: x.parent.__setitem__(1, 2), "frames must list parents before children"),
+        (lambda x: x.link_frame.__setitem__(1, x.link_frame[0]), "two collision links on one frame"),
+        (lambda x: x.point_link.__setitem__(0, x.n_links), "point_link out of range"),
+        (lambda x: x.lower.__setitem__(x.opt_index[0], x.upper[x.opt_index[0]] + 1.0), "lower > upper"),
+    ]
+    for edit, why in cases:  # GTO_ERR_INVALID_ARG (-1) with the message of each
+        with pytest.raises(capi.GTOError, match=rf"failed \(-1\): {re.escape(why)}$"):
+            capi.SolverHandle(malformed(edit), "panda_hand", "panda_hand")
     if torch.cuda.is_available():
         pytest.skip("GPU present: the no-device path cannot be exercised")
     with pytest.raises(capi.GTOError, match="no HIP device|fallback"):
