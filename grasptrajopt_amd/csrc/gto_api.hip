@@ -155,8 +155,10 @@ struct gto_handle {
   double *d_px = nullptr, *d_py = nullptr, *d_pz = nullptr;
   int32_t *d_plink = nullptr, *d_perm = nullptr;
   Chunk* d_chunks = nullptr;
-  PbChunk* d_pbchunks = nullptr;  // bounding spheres of the chunks of moving links, with their frames (prebroad_tail)
+  std::vector<PbChunk> pbchunks;  // bounding spheres of the chunks of moving links, with their frames (prebroad_tail)
   int pb_C = 0;
+  float* d_pbimg = nullptr;  // their table for each valid scene (SceneDev::pb_img; sync_pb_images)
+  size_t d_pbimg_cap = 0;    // floats
   std::vector<SceneDev> scenes;  // host mirror, index = scene id
   SceneDev* d_scenes = nullptr;
   size_t d_scenes_cap = 0;
@@ -422,6 +424,12 @@ static int build_robot(const gto_robot_desc* d, int pb_merge, RobotTables& t, st
       rb.pb_ctl[i] = (src & 7) | (((rb.xst_slot[i] + 1) & 7) << 4) | ((moving_link ? 1 : 0) << 8);
       rb.pb_par[i] = -1;
       if (rb.joint_type[i] != GTO_JOINT_FIXED && rb.opt_of_frame[i] < 0) rb.pb_par[i] = rb.pb_npar, rb.pb_parf[rb.pb_npar++] = i;
+    }
+    for (int i = 0; i < d->n_frames; ++i) {  // the frame table the tail copies into its LDS as it is
+      for (int e = 0; e < 12; ++e) rb.pb_ft[i][e] = (float)rb.origin[i][e];
+      for (int e = 0; e < 3; ++e) rb.pb_ft[i][12 + e] = (float)rb.axis_unit[i][e];
+      const int32_t w = rb.joint_type[i] | ((rb.opt_of_frame[i] + 1) << 4) | ((rb.pb_par[i] + 1) << 9);
+      std::memcpy(&rb.pb_ft[i][15], &w, sizeof w);
     }
     double D = 0.0, maxp = 0.0;  // no frame origin or surface point is further than D from any other
     for (int i = 0; i < d->n_frames; ++i) {
@@ -730,6 +738,7 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
   h->tu = tu;
   std::memcpy(&h->rb, &rb, sizeof rb);
   h->pb_C = t->pb_C;
+  h->pbchunks = t->pbchunks;
   h->np = np;
   h->lm_lds = lm_lds;
   h->spec_kmax = spec_kmax;
@@ -743,8 +752,7 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
   const bool ok = up((void**)&h->d_rb, &h->rb, sizeof h->rb) && up((void**)&h->d_px, t->px.data(), P * sizeof(double)) &&
                   up((void**)&h->d_py, t->py.data(), P * sizeof(double)) && up((void**)&h->d_pz, t->pz.data(), P * sizeof(double)) &&
                   up((void**)&h->d_plink, t->plink.data(), P * sizeof(int32_t)) && up((void**)&h->d_perm, t->perm.data(), P * sizeof(int32_t)) &&
-                  up((void**)&h->d_chunks, t->chunks.data(), t->chunks.size() * sizeof(Chunk)) &&
-                  up((void**)&h->d_pbchunks, t->pbchunks.data(), t->pbchunks.size() * sizeof(PbChunk));
+                  up((void**)&h->d_chunks, t->chunks.data(), t->chunks.size() * sizeof(Chunk));
   if (!ok) { gto_destroy(h); return fail(nullptr, GTO_ERR_ALLOC, "device allocation failed in gto_create"); }
   // dynamic LDS of every kernel variant the handle can launch (obstacle_kernel, the step kernels)
   const size_t lds = std::min<size_t>((size_t)lay.total_doubles * sizeof(double), 160 * 1024);
@@ -779,7 +787,7 @@ void gto_destroy(gto_handle* h) {
   (void)hipFree(h->d_plink);
   (void)hipFree(h->d_perm);
   (void)hipFree(h->d_chunks);
-  (void)hipFree(h->d_pbchunks);
+  (void)hipFree(h->d_pbimg);
   DevBuf* bufs[] = {&h->zws, &h->counters, &h->state, &h->Qcur, &h->Qtry, &h->vis, &h->screw, &h->blocks, &h->goalblk, &h->ssfixed, &h->ndone, &h->qf, &h->livebuf, &h->qfs, &h->wrecbuf, &h->itembuf};
   if (h->h_ndone) (void)hipHostFree(h->h_ndone);
   if (h->h_progress) (void)hipHostFree(h->h_progress);
@@ -807,8 +815,44 @@ int gto_set_opts(gto_handle* h, const gto_solver_opts* o) {
   return GTO_OK;
 }
 
+// The step kernel's tail copies its sphere table into LDS as it is (prebroad_tail): per valid scene, the spheres' centres
+// and their culling radii in that scene's voxels, then the spheres' frames, rows of four floats.  The radius is the
+// expression the tail evaluated per workgroup before, with the fused multiply-add the GPU compiles it to.
+static int sync_pb_images(gto_handle* h) {
+  const int C = h->pb_C;
+  const size_t rows = (size_t)pb_img_rows(C);
+  size_t nv = 0;
+  for (const SceneDev& s : h->scenes) nv += s.valid ? 1 : 0;
+  if (nv * rows * 4 > h->d_pbimg_cap) {
+    if (h->d_pbimg) HIPCHK(h, hipFree(h->d_pbimg));
+    h->d_pbimg = nullptr;
+    const size_t cap = std::max<size_t>(16, nv * 2) * rows * 4;
+    HIPCHK(h, hipMalloc((void**)&h->d_pbimg, cap * sizeof(float)));
+    h->d_pbimg_cap = cap;
+  }
+  std::vector<float> img(nv * rows * 4, 0.f);
+  const double eps = h->rb.pb_eps;
+  size_t k = 0;
+  for (SceneDev& s : h->scenes) {
+    s.pb_img = nullptr;
+    if (!s.valid || rows == 0) continue;
+    float* v = img.data() + k * rows * 4;
+    for (int c = 0; c < C; ++c) {
+      const PbChunk& cc = h->pbchunks[c];
+      v[4 * c] = (float)cc.cx, v[4 * c + 1] = (float)cc.cy, v[4 * c + 2] = (float)cc.cz;
+      v[4 * c + 3] = (float)((int)std::ceil(std::fma(cc.r + eps, s.rinv, 1e-6)) + GTO_BROAD_MARGIN);
+      std::memcpy(v + 4 * C + c, &cc.frame, sizeof(int32_t));
+    }
+    s.pb_img = h->d_pbimg + k * rows * 4;
+    ++k;
+  }
+  if (!img.empty()) HIPCHK(h, hipMemcpy(h->d_pbimg, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
+  return GTO_OK;
+}
+
 static int sync_scene_table(gto_handle* h) {
   size_t n = h->scenes.size();
+  if (int rc = sync_pb_images(h)) return rc;
   if (n > h->d_scenes_cap) {
     if (h->d_scenes) HIPCHK(h, hipFree(h->d_scenes));
     h->d_scenes = nullptr;
@@ -1515,11 +1559,11 @@ static int enqueue_round(gto_handle* h, const SolveCall& c, LaneCtx& ln, int lan
   if (p.step == STEP_FEW) {
     lsp.k_acc = p.k_acc, lsp.k_rej = p.k_rej, lsp.spec_streak = p.spec_streak;
     lsp.pb_next = 0, lsp.static_pos = 0;
-    hipLaunchKernelGGL((k_lm_step<8, GTO_KSPEC>), dim3(p.span), dim3(512), lm_lds_bytes(T, p.k_next), ln.st, h->d_rb, h->d_pbchunks, ln.bp, lsp, B);
+    hipLaunchKernelGGL((k_lm_step<8, GTO_KSPEC>), dim3(p.span), dim3(512), lm_lds_bytes(T, p.k_next), ln.st, h->d_rb, ln.bp, lsp, B);
   } else if (p.step == STEP_FULL) {
     lsp.k_acc = lsp.k_rej = 1;
     lsp.pb_next = p.pb_next, lsp.static_pos = p.static_pos;
-    hipLaunchKernelGGL((k_lm_step<4, 1>), dim3(p.span), dim3(256), h->lm_lds, ln.st, h->d_rb, h->d_pbchunks, ln.bp, lsp, B);
+    hipLaunchKernelGGL((k_lm_step<4, 1>), dim3(p.span), dim3(256), h->lm_lds, ln.st, h->d_rb, ln.bp, lsp, B);
   } else {
     hipLaunchKernelGGL(k_lm_step_wide<16>, dim3(p.in_flight), dim3(GTO_WIDE_NT), h->lm_lds, ln.st, h->d_rb, ln.bp, lsp, B,
                        (double*)h->zws.p + (size_t)c.lane_zws[lane_index] * (T - 2) * h->np * h->np);
@@ -1701,6 +1745,8 @@ static int print_debug_stamps(gto_handle* h, hipStream_t st) {
           t[3] - t[2], t[41] - t[2], t[17] - t[2], t[42] - t[4], t[18] - t[42], t[19] - t[42], t[26] - t[42]);
   fprintf(stderr, "[gto dbg] sweeps of the other candidates' waves (2..6) done at (cycles from the start of P3, 0 = no candidate): %lld %lld %lld %lld %lld | barrier passed at %lld\n",
           t[43] ? t[43] - t[2] : 0, t[44] ? t[44] - t[2] : 0, t[45] ? t[45] - t[2] : 0, t[46] ? t[46] - t[2] : 0, t[47] ? t[47] - t[2] : 0, t[4] - t[2]);
+  fprintf(stderr, "[gto dbg] tail tables fetched by waves 2-3 during the back substitution (cycles from its start): in at %lld %lld | its barrier passed at %lld\n",
+          t[51] ? t[51] - t[42] : 0, t[52] ? t[52] - t[42] : 0, t[5] - t[42]);
   fprintf(stderr, "[gto dbg] broad phase in the step kernel's tail (cycles): entry+tables %lld | barrier %lld | A (local transforms, pass 0) %lld | B (chain) %lld | C (sphere tests) %lld | other passes %lld | outputs %lld\n",
           t[33] - t[6], t[34] - t[33], t[35] - t[34], t[36] - t[35], t[37] - t[36], t[38] - t[37], t[39] - t[38]);
   fprintf(stderr, "[gto dbg] P2 split (cycles): loads+barrier %lld | b-vector+masks %lld | blocks %lld | e,y+barrier %lld\n", t[28] - t[1], t[29] - t[28], t[30] - t[29], t[2] - t[30]);

@@ -58,6 +58,9 @@ struct RobotDev {
   int32_t pb_par[GTO_MAX_FRAMES];    // slot of the frame's joint among the actuated joints that are not optimised, or -1
   int32_t pb_parf[GTO_MAX_FRAMES];   // frame of such a slot
   int32_t pb_npar;
+  // the walk's frame table as the step kernel's tail keeps it in LDS (prebroad_tail): per frame its origin (3x4) and unit
+  // axis in floats, then joint type | optimised joint + 1 << 4 | parameter slot + 1 << 9 (an int's bits); rows of 16 bytes
+  alignas(16) float pb_ft[GTO_MAX_FRAMES][16];
   int32_t cf_orig[GTO_MAX_FRAMES];  // frame whose joint value a compact frame takes (-1: the world frame)
   int32_t cf_type[GTO_MAX_FRAMES];  // its joint type
   int32_t parent[GTO_MAX_FRAMES];
@@ -111,6 +114,9 @@ struct SceneDev {
   const uint8_t* d_obs;
   int32_t nx, ny, nz, valid;
   double ox, oy, oz, res, rinv, inv2r;
+  // the step kernel's sphere table for this scene (gto_api.hip, sync_scene_table; rows of 16 bytes): per sphere its centre
+  // and its culling radius in voxels of this scene (floats), then the spheres' frames (ints)
+  const float* pb_img;
 };
 
 struct Chunk {

@@ -39,6 +39,8 @@ def run(B, max_iter):
     lines = [l for l in r.stderr.splitlines() if l.startswith("[gto dbg]")]
     ph = [l for l in lines if "step-kernel phases" in l][-1]
     tl = [l for l in lines if "broad phase in the step kernel's tail" in l][-1]
+    pre = [l for l in lines if "tail tables fetched by waves 2-3" in l]
+    run.prefetch = pre[-1] if pre else None
     nums = lambda l: [int(x) for x in re.findall(r"(?<= )(-?\d+)(?= \||$)", l.split("(cycles)", 1)[1])]
     return ph, tl, nums(ph), nums(tl), r.stderr[-400:] if r.returncode else ""
 
@@ -50,6 +52,8 @@ ph, tl, a, b, err = run(320, 6)
 steps, tail = sum(a[:7]), sum(x for x in b if x > 0)  # (the P5 stamp is taken behind the tail: steps includes it)
 out["variants"]["k_lm_step<4,1>"] = {"critical_path_cycles": steps, "ticks_per_us": 2400, "step_phases": ph, "tail_phases": tl,
                                      "cycles_tail_broad_phase": tail, "cycles_without_tail": steps - tail}
+if run.prefetch:
+    out["variants"]["k_lm_step<4,1>"]["tail_tables_prefetch"] = run.prefetch
 ph, tl, a, b, err2 = run(1, 100)
 out["variants"]["k_lm_step<8,4>"] = {"critical_path_cycles": sum(a[:7]), "ticks_per_us": 2400, "step_phases": ph}
 json.dump(out, open(os.path.join(ROOT, "profiles", f"{tag}_step_stamps.json"), "w"), indent=1)
