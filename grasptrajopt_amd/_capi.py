@@ -106,7 +106,7 @@ def pack_robot_desc(desc: RobotDesc, link_ee: str, link_gripper: str,
 # include/gto_solver.h
 GTO_GRAD_CENTRAL_DIFF, GTO_GRAD_ZERO = 0, 1
 GTO_STATUS_CONVERGED, GTO_STATUS_MAX_ITER, GTO_STATUS_NUMERICAL = 0, 1, 2
-ABI_VERSION = 1007  # include/gto_solver.h GTO_ABI_VERSION (checked against gto_version() when the library is loaded)
+ABI_VERSION = 1008  # include/gto_solver.h GTO_ABI_VERSION (checked against gto_version() when the library is loaded)
 
 _lib = None
 
@@ -218,13 +218,15 @@ def load_library(path: Optional[str] = None):
     lib.gto_solve_ik_batch.argtypes = [H, C.c_int32, _pi, _pd, _pd, _pd, C.c_int32, _pd, _pd, _pi, _pi]
     lib.gto_solve_base_batch.argtypes = [H, C.c_int32, C.c_int32, _pi, _pd, _pd, C.c_double, C.c_int32, _pd, _pd, _pd, _pi, _pi]
     lib.gto_eval_base_objective.argtypes = [H, C.c_int32, C.c_int32, _pi, _pd, _pd, _pd, C.c_double, _pd]
+    lib.gto_retime_batch.argtypes = [H, C.c_int32, _pd, _pd, _pd, C.c_int32, C.c_int32, _pd, _pd, _pd, _pd, _pd, _pd, _pi]
+    lib.gto_retime_batch_device.argtypes = [H, C.c_int32, C.c_void_p, _pd, _pd, C.c_int32, C.c_int32] + [C.c_void_p] * 8
     _pu8 = C.POINTER(C.c_uint8)
     lib.gto_depth_sdf_cost.argtypes = [C.c_int, _pf, C.c_int32, C.c_int32, _pd, _pd, _pd, _pd, _pu8, C.c_double, _pd, C.c_int64,
                                        C.c_float, C.c_float, _pf, _pu8, _pf, _pd, _pu8]
     for fn in ("gto_create", "gto_set_opts", "gto_set_scene", "gto_set_scene_values", "gto_drop_scene", "gto_solve_batch",
                "gto_solve_batch_device", "gto_last_kernel_time", "gto_last_kernel_work", "gto_set_profiling", "gto_set_stream", "gto_set_mode", "gto_set_lanes", "gto_set_lane_streams", "gto_share_scene",
                "gto_eval_fk", "gto_eval_points", "gto_eval_points_hessian", "gto_eval_objective", "gto_eval_obstacle_normal_eq", "gto_plan_cost", "gto_solve_ik_batch",
-               "gto_solve_base_batch", "gto_eval_base_objective", "gto_depth_sdf_cost"):
+               "gto_solve_base_batch", "gto_eval_base_objective", "gto_depth_sdf_cost", "gto_retime_batch", "gto_retime_batch_device"):
         getattr(lib, fn).restype = C.c_int
     if path is None:
         _lib = lib
@@ -238,6 +240,7 @@ EXPORTED_SYMBOLS = (
     "gto_eval_fk", "gto_eval_points", "gto_eval_points_hessian",
     "gto_eval_objective", "gto_eval_obstacle_normal_eq", "gto_plan_cost", "gto_solve_ik_batch", "gto_solve_base_batch",
     "gto_eval_base_objective", "gto_depth_sdf_cost", "gto_scene_from_depth", "gto_get_scene_fields",
+    "gto_retime_batch", "gto_retime_batch_device",
 )
 
 
@@ -591,3 +594,37 @@ class SolverHandle:
         self._check(self.lib.gto_plan_cost(self._h, scene_id, n, _p(plans, _pd), _p(base, _pd),
                                            _p(cost, _pd), _p(dist, _pd)), "gto_plan_cost")
         return cost, dist
+
+    # -------------------------------------------------------------- retiming
+    def _retime_limits(self, vmax, amax):
+        nd = self.desc.ndof
+        return (_f64(np.broadcast_to(np.asarray(vmax, dtype=np.float64), (nd,))),
+                _f64(np.broadcast_to(np.asarray(amax, dtype=np.float64), (nd,))))
+
+    def retime_batch(self, plans, vmax, amax, subdiv: int = 2, n_samples: int = 100):
+        """gto_retime_batch: time-optimal retiming of plans (B, ndof, T) under joint velocity limits vmax and acceleration
+        limits amax (each (ndof,) or a scalar; vmax may hold +inf).  Returns a dict of duration (B,), t_grid (B, N),
+        sd_grid (B, N), q / qd / qdd (B, n_samples, ndof) and status (B,), N = subdiv (T-1) + 1."""
+        d, T = self.desc, self.T
+        plans = _f64(plans).reshape(-1, d.ndof, T)
+        B, N, M = plans.shape[0], int(subdiv) * (T - 1) + 1, int(n_samples)
+        vm, am = self._retime_limits(vmax, amax)
+        out = dict(duration=np.empty(B), t_grid=np.empty((B, max(N, 0))), sd_grid=np.empty((B, max(N, 0))),
+                   q=np.empty((B, max(M, 0), d.ndof)), qd=np.empty((B, max(M, 0), d.ndof)), qdd=np.empty((B, max(M, 0), d.ndof)),
+                   status=np.empty(B, dtype=np.int32))
+        self._check(self.lib.gto_retime_batch(self._h, B, _p(plans, _pd), _p(vm, _pd), _p(am, _pd), int(subdiv), M,
+                                              _p(out["duration"], _pd), _p(out["t_grid"], _pd), _p(out["sd_grid"], _pd),
+                                              _p(out["q"], _pd), _p(out["qd"], _pd), _p(out["qdd"], _pd),
+                                              _p(out["status"], _pi)), "gto_retime_batch")
+        return out
+
+    def retime_batch_device(self, B, plans, vmax, amax, subdiv, n_samples, duration_out=None, t_grid_out=None,
+                            sd_grid_out=None, q_out=None, qd_out=None, qdd_out=None, status_out=None, stream=None):
+        """gto_retime_batch_device: plans and outputs are device pointers (ints, e.g. torch.Tensor.data_ptr()) or None;
+        vmax / amax are host values."""
+        vm, am = self._retime_limits(vmax, amax)
+        vp = lambda a: None if a is None else C.c_void_p(int(a))
+        self._check(self.lib.gto_retime_batch_device(self._h, int(B), vp(plans), _p(vm, _pd), _p(am, _pd), int(subdiv),
+                                                     int(n_samples), vp(duration_out), vp(t_grid_out), vp(sd_grid_out),
+                                                     vp(q_out), vp(qd_out), vp(qdd_out), vp(status_out), vp(stream)),
+                    "gto_retime_batch_device")

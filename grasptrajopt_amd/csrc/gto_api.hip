@@ -21,6 +21,7 @@
 #include <sys/prctl.h>
 
 #include "gto_kernels.h"
+#include "gto_retime.h"
 
 #define GTO_VERSION GTO_ABI_VERSION  // include/gto_solver.h
 #ifndef GTO_OBS_DEEP_PD
@@ -209,6 +210,9 @@ struct gto_handle {
   // published (the prior of the next call's launches until its own counts arrive)
   double items_per_job_prior = 0.0;
   std::mutex* prof_mu = nullptr;  // set while a call with several lanes (host threads) runs: guards the profiling records
+  // retiming (gto_retime_batch_device): Thomas factors of the not-a-knot system for this T, workspace grown on demand
+  DevBuf rt_fac, rt_S, rt_flag, rt_P1, rt_P2, rt_cap, rt_X, rt_T, rt_stat;
+  bool rt_fac_ready = false;
 };
 
 #define HIPCHK(h, call)                                                                              \
@@ -788,7 +792,8 @@ void gto_destroy(gto_handle* h) {
   (void)hipFree(h->d_perm);
   (void)hipFree(h->d_chunks);
   (void)hipFree(h->d_pbimg);
-  DevBuf* bufs[] = {&h->zws, &h->counters, &h->state, &h->Qcur, &h->Qtry, &h->vis, &h->screw, &h->blocks, &h->goalblk, &h->ssfixed, &h->ndone, &h->qf, &h->livebuf, &h->qfs, &h->wrecbuf, &h->itembuf};
+  DevBuf* bufs[] = {&h->zws, &h->counters, &h->state, &h->Qcur, &h->Qtry, &h->vis, &h->screw, &h->blocks, &h->goalblk, &h->ssfixed, &h->ndone, &h->qf, &h->livebuf, &h->qfs, &h->wrecbuf, &h->itembuf,
+                   &h->rt_fac, &h->rt_S, &h->rt_flag, &h->rt_P1, &h->rt_P2, &h->rt_cap, &h->rt_X, &h->rt_T, &h->rt_stat};
   if (h->h_ndone) (void)hipHostFree(h->h_ndone);
   if (h->h_progress) (void)hipHostFree(h->h_progress);
   for (DevBuf* b : bufs) (void)hipFree(b->p);
@@ -2672,6 +2677,131 @@ int gto_get_scene_fields(gto_handle* h, int32_t scene_id, float* c_all_out, floa
   if (c_all_out) HIPCHK(h, hipMemcpy(c_all_out, s.c_all, nvox * sizeof(float), hipMemcpyDeviceToHost));
   if (c_obs_out) HIPCHK(h, hipMemcpy(c_obs_out, s.c_obs, nvox * sizeof(float), hipMemcpyDeviceToHost));
   return GTO_OK;
+}
+
+// ------------------------------------------------------------------ retiming under joint velocity / acceleration limits
+// (convert_plan_to_trajectory_toppra, gto/utils.py:283-323; kernels: gto_retime.h)
+
+// Thomas factors of the not-a-knot system of T uniform knots, scaled by 1/h: rows [1 2], [1 4 1] ... [1 4 1], [2 1]
+// (scipy.interpolate.CubicSpline's banded system for n >= 4; gto_create guarantees T >= 4).  [3][T]: multiplier, reciprocal
+// pivot and upper entry of every row.
+static std::vector<double> retime_factors(int T) {
+  std::vector<double> f(3 * (size_t)T, 0.0);
+  double* lo = f.data();
+  double* inv = lo + T;
+  double* up = lo + 2 * T;
+  double piv = 1.0;
+  up[0] = 2.0;
+  inv[0] = 1.0 / piv;
+  for (int i = 1; i < T; ++i) {
+    const double sub = i == T - 1 ? 2.0 : 1.0, diag = i == T - 1 ? 1.0 : 4.0;
+    up[i] = i == T - 1 ? 0.0 : 1.0;
+    lo[i] = sub / piv;
+    piv = diag - lo[i] * up[i - 1];
+    inv[i] = 1.0 / piv;
+  }
+  return f;
+}
+
+static int retime_check(gto_handle* h, int32_t B, const double* vmax, const double* amax, int32_t subdiv, int32_t M,
+                        RetimeLimits& lim, RetimeDims& d) {
+  const int ndof = h->rb.ndof, T = h->opts.T;
+  if (B < 0) return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: B must be >= 0");
+  if (!vmax || !amax) return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: null limit array");
+  for (int j = 0; j < ndof; ++j) {
+    if (!(vmax[j] > 0.0)) return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: vmax must be > 0 (+inf: no limit)");
+    if (!(amax[j] > 0.0) || !std::isfinite(amax[j]))
+      return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: amax must be finite and > 0");
+    lim.vmax[j] = vmax[j], lim.amax[j] = amax[j];
+  }
+  if (subdiv < 1 || M < 2) return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: subdiv must be >= 1 and M >= 2");
+  const long long N = (long long)subdiv * (T - 1) + 1;
+  if (N > GTO_RETIME_MAX_N) return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: subdiv (T-1) + 1 must be <= 1024");
+  if ((long long)B * std::max<long long>(N, M) * std::max(ndof, 1) > (long long)INT32_MAX * 64)
+    return fail(h, GTO_ERR_UNSUPPORTED, "gto_retime_batch: batch too large for one call");
+  d.B = B, d.ndof = ndof, d.T = T, d.N = (int)N, d.subdiv = subdiv, d.M = M;
+  return GTO_OK;
+}
+
+static unsigned retime_blocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
+
+int gto_retime_batch_device(gto_handle* h, int32_t B, const double* plans, const double* vmax, const double* amax,
+                            int32_t subdiv, int32_t M, double* duration_out, double* t_grid_out, double* sd_grid_out,
+                            double* q_out, double* qd_out, double* qdd_out, int32_t* status_out, void* stream) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  RetimeLimits lim = {};
+  RetimeDims d = {};
+  int rc = retime_check(h, B, vmax, amax, subdiv, M, lim, d);
+  if (rc) return rc;
+  if (B == 0) return GTO_OK;
+  if (!plans) return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: null plans");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  const size_t T = d.T, N = d.N, nd = d.ndof, nB = (size_t)B;
+  if (!h->rt_fac_ready) {  // once per handle (T is fixed for its lifetime)
+    const std::vector<double> f = retime_factors(d.T);
+    if ((rc = ensure(h, h->rt_fac, f.size() * sizeof(double)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->rt_fac.p, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    h->rt_fac_ready = true;
+  }
+  if ((rc = ensure(h, h->rt_S, nB * nd * T * sizeof(double)))) return rc;
+  if ((rc = ensure(h, h->rt_flag, nB * nd * sizeof(int32_t)))) return rc;
+  if ((rc = ensure(h, h->rt_P1, nB * N * nd * sizeof(double)))) return rc;
+  if ((rc = ensure(h, h->rt_P2, nB * N * nd * sizeof(double)))) return rc;
+  if ((rc = ensure(h, h->rt_cap, nB * N * sizeof(double)))) return rc;
+  if ((rc = ensure(h, h->rt_X, nB * N * sizeof(double)))) return rc;
+  if ((rc = ensure(h, h->rt_T, nB * N * sizeof(double)))) return rc;
+  if ((rc = ensure(h, h->rt_stat, nB * sizeof(int32_t)))) return rc;
+  double *S = (double*)h->rt_S.p, *P1 = (double*)h->rt_P1.p, *P2 = (double*)h->rt_P2.p, *cap = (double*)h->rt_cap.p;
+  double *X = (double*)h->rt_X.p, *Tg = (double*)h->rt_T.p;
+  int32_t *flag = (int32_t*)h->rt_flag.p, *stat = (int32_t*)h->rt_stat.p;
+  hipLaunchKernelGGL(k_retime_spline, dim3(retime_blocks((long long)B * nd, 256)), dim3(256), 0, st, plans,
+                     (const double*)h->rt_fac.p, d, S, flag);
+  hipLaunchKernelGGL(k_retime_grid, dim3(retime_blocks((long long)B * N, 256)), dim3(256), 0, st, plans, S, flag, lim, d,
+                     P1, P2, cap);
+  hipLaunchKernelGGL(k_retime_pass, dim3(B), dim3(64), 0, st, P1, P2, cap, flag, lim, d, X, Tg, stat, duration_out,
+                     t_grid_out, sd_grid_out, status_out);
+  if (q_out || qd_out || qdd_out)
+    hipLaunchKernelGGL(k_retime_sample, dim3(retime_blocks((long long)B * M, 256)), dim3(256), 0, st, plans, S, X, Tg, stat,
+                       d, q_out, qd_out, qdd_out);
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
+}
+
+int gto_retime_batch(gto_handle* h, int32_t B, const double* plans, const double* vmax, const double* amax, int32_t subdiv,
+                     int32_t M, double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out, double* qd_out,
+                     double* qdd_out, int32_t* status_out) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  RetimeLimits lim = {};
+  RetimeDims d = {};
+  int rc = retime_check(h, B, vmax, amax, subdiv, M, lim, d);
+  if (rc) return rc;
+  if (B == 0) return GTO_OK;
+  if (!plans) return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: null plans");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t nB = (size_t)B, nd = d.ndof, T = d.T, N = d.N, nM = (size_t)M;
+  const void* d_plans;
+  void *d_dur, *d_t, *d_sd, *d_q, *d_qd, *d_qdd, *d_st;
+  if ((rc = stage_in(h, 0, plans, nB * nd * T * sizeof(double), &d_plans))) return rc;
+  if ((rc = stage_out(h, 0, duration_out, nB * sizeof(double), &d_dur))) return rc;
+  if ((rc = stage_out(h, 1, t_grid_out, nB * N * sizeof(double), &d_t))) return rc;
+  if ((rc = stage_out(h, 2, sd_grid_out, nB * N * sizeof(double), &d_sd))) return rc;
+  if ((rc = stage_out(h, 3, q_out, nB * nM * nd * sizeof(double), &d_q))) return rc;
+  if ((rc = stage_out(h, 4, qd_out, nB * nM * nd * sizeof(double), &d_qd))) return rc;
+  if ((rc = stage_out(h, 5, qdd_out, nB * nM * nd * sizeof(double), &d_qdd))) return rc;
+  if ((rc = stage_out(h, 6, status_out, nB * sizeof(int32_t), &d_st))) return rc;
+  rc = gto_retime_batch_device(h, B, (const double*)d_plans, vmax, amax, subdiv, M, (double*)d_dur, (double*)d_t,
+                               (double*)d_sd, (double*)d_q, (double*)d_qd, (double*)d_qdd, (int32_t*)d_st, nullptr);
+  if (rc) return rc;
+  if ((rc = fetch_out(h, 0, duration_out, nB * sizeof(double)))) return rc;
+  if ((rc = fetch_out(h, 1, t_grid_out, nB * N * sizeof(double)))) return rc;
+  if ((rc = fetch_out(h, 2, sd_grid_out, nB * N * sizeof(double)))) return rc;
+  if ((rc = fetch_out(h, 3, q_out, nB * nM * nd * sizeof(double)))) return rc;
+  if ((rc = fetch_out(h, 4, qd_out, nB * nM * nd * sizeof(double)))) return rc;
+  if ((rc = fetch_out(h, 5, qdd_out, nB * nM * nd * sizeof(double)))) return rc;
+  if ((rc = fetch_out(h, 6, status_out, nB * sizeof(int32_t)))) return rc;
+  return sync_and_finish_out(h);
 }
 
 }  // extern "C"

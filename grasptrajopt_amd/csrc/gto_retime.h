@@ -1,0 +1,297 @@
+// gto_retime.h — time-optimal retiming of plans under joint velocity and acceleration limits (gto_retime_batch[_device],
+// include/gto_solver.h).  The reference's convert_plan_to_trajectory_toppra (gto/utils.py:283-323): a not-a-knot cubic
+// spline through the T waypoints on s in [0, 1], TOPP-RA's discretisation on a grid of N = subdiv (T-1) + 1 points
+// (x = sdot^2, u = sddot, x_{i+1} = x_i + 2 Delta u_i, constraints at the gridpoints), the controllable sets by a backward
+// pass, the greedy forward pass, constant acceleration between gridpoints, M samples of q, qdot, qddot.  FP64 throughout.
+//
+//   k_retime_spline   one lane per (plan, joint): slopes of the spline at the knots (the two substitutions of the
+//                     not-a-knot system, factored once per handle on the host), finite / moving flags
+//   k_retime_grid     one lane per (plan, gridpoint): p1 = q'(s), p2 = q''(s) of every joint, the bound on x that does
+//                     not involve u (velocity limits; acceleration limits of joints with p1 = 0)
+//   k_retime_pass     one wave per plan: backward pass (controllable sets) and forward pass (greedy profile), times.
+//                     Each stage is a two-variable LP solved exactly: every upper bound on u (a line in x) is paired with
+//                     every lower bound, and the pairs are spread over the lanes and reduced by a cross-lane min.  One
+//                     lane per plan (every pair in one lane) measured 0.6-0.1x of this rate and was dropped.
+//   k_retime_sample   one lane per (plan, sample): binary search over the gridpoint times, evaluation on the spline
+#pragma once
+#include "gto_device.h"
+
+#define GTO_RETIME_MAX_N 1024             // gridpoints per plan (the pass kernel keeps the controllable sets in LDS)
+#define GTO_RETIME_LINES (GTO_MAX_DOF + 1)  // bounds on u of each side: one per moving joint, one from the next set
+// A profile that rests over a whole segment (x at both of its ends <= GTO_RETIME_STALL * the largest x, i.e. sdot below
+// 1e-3 of its largest) spends a time on it that round-off of x alone decides: status GTO_STATUS_NUMERICAL
+#define GTO_RETIME_STALL 1e-6
+
+// per-joint limits, passed by value (a kernel argument of 512 B): no upload, no validation on the device
+struct RetimeLimits {
+  double vmax[GTO_MAX_DOF];  // > 0, +inf = no limit
+  double amax[GTO_MAX_DOF];  // finite, > 0
+};
+
+struct RetimeDims {
+  int B, ndof, T, N, subdiv, M;
+};
+
+// flags of a (plan, joint) row
+#define GTO_RT_CONST 0
+#define GTO_RT_MOVING 1
+#define GTO_RT_NONFINITE 2
+
+// Cubic piece of knot interval k at offset r in [0, h]: scipy.interpolate.CubicSpline's coefficients from the values and
+// slopes at both ends (c0 r^3 + c1 r^2 + c2 r + c3).  Returns q, q' and q''.
+__device__ __forceinline__ void rt_piece(const double* y, const double* s, int k, double r, double invh, double& q,
+                                         double& p1, double& p2) {
+  const double y0 = y[k], y1 = y[k + 1], s0 = s[k], s1 = s[k + 1];
+  const double m = (y1 - y0) * invh;
+  const double t = (s0 + s1 - 2.0 * m) * invh;
+  const double c0 = t * invh, c1 = (m - s0) * invh - t, c2 = s0;
+  q = y0 + r * (c2 + r * (c1 + r * c0));
+  p1 = c2 + r * (2.0 * c1 + 3.0 * c0 * r);
+  p2 = 2.0 * c1 + 6.0 * c0 * r;
+}
+
+// Spline slopes.  fac [3][T]: the Thomas factors of the not-a-knot system scaled by 1/h (rows [1 2], [1 4 1] ..., [2 1]):
+// multiplier of row i, reciprocal pivot of row i, upper entry of row i.
+__global__ __launch_bounds__(256) void k_retime_spline(const double* __restrict__ Q, const double* __restrict__ fac,
+                                                       RetimeDims d, double* __restrict__ S, int32_t* __restrict__ flag) {
+  const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= (long long)d.B * d.ndof) return;
+  const int T = d.T;
+  const double* y = Q + id * T;
+  double* s = S + id * T;
+  const double invh = (double)(T - 1);
+  bool finite = true, moving = false;
+  const double y0 = y[0];
+  for (int k = 0; k < T; ++k) {
+    finite = finite && isfinite(y[k]);
+    moving = moving || y[k] != y0;
+  }
+  flag[id] = !finite ? GTO_RT_NONFINITE : moving ? GTO_RT_MOVING : GTO_RT_CONST;
+  if (!finite) return;
+  const double* lo = fac;
+  const double* inv = fac + T;
+  const double* up = fac + 2 * T;
+  // forward substitution into s; right-hand sides from the chord slopes m_k
+  double mprev = (y[1] - y[0]) * invh, mcur = (y[2] - y[1]) * invh;
+  double w = 0.5 * (5.0 * mprev + mcur);
+  s[0] = w;
+  for (int i = 1; i < T - 1; ++i) {
+    if (i > 1) mprev = mcur, mcur = (y[i + 1] - y[i]) * invh;
+    w = 3.0 * (mprev + mcur) - lo[i] * w;
+    s[i] = w;
+  }
+  w = 0.5 * (mprev + 5.0 * mcur) - lo[T - 1] * w;
+  // back substitution
+  double sn = w * inv[T - 1];
+  s[T - 1] = sn;
+  for (int i = T - 2; i >= 0; --i) {
+    sn = (s[i] - up[i] * sn) * inv[i];
+    s[i] = sn;
+  }
+}
+
+// Bound on u of moving joint j at gridpoint i: upper u <= alpha + beta x, lower u >= -alpha + beta x.  A joint with p1 = 0,
+// or with |p1| so small that alpha or beta overflows, has no line (its bound on x alone, |p2 x| <= amax, is in xcap):
+// alpha = inf, beta = 0 makes every pair with it void.  Returns whether the joint has a line.
+__device__ __forceinline__ bool rt_line(double a, double b, double A, double& alpha, double& beta) {
+  alpha = A / fabs(a);
+  beta = -b / a;
+  if (isfinite(alpha) && isfinite(beta)) return true;
+  alpha = INFINITY, beta = 0.0;
+  return false;
+}
+
+// p1, p2 per (plan, gridpoint, joint) [B][N][ndof] and the x cap per (plan, gridpoint) [B][N]
+__global__ __launch_bounds__(256) void k_retime_grid(const double* __restrict__ Q, const double* __restrict__ S,
+                                                     const int32_t* __restrict__ flag, RetimeLimits lim, RetimeDims d,
+                                                     double* __restrict__ P1, double* __restrict__ P2,
+                                                     double* __restrict__ xcap) {
+  const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= (long long)d.B * d.N) return;
+  const long long b = id / d.N;
+  const int g = (int)(id - b * d.N), T = d.T, ndof = d.ndof;
+  const int k = min(g / d.subdiv, T - 2);
+  const double r = (double)(g - k * d.subdiv) / (double)(d.N - 1);
+  const double invh = (double)(T - 1);
+  double cap = INFINITY;
+  for (int j = 0; j < ndof; ++j) {
+    const long long row = b * ndof + j;
+    double p1 = 0.0, p2 = 0.0;
+    if (flag[row] == GTO_RT_NONFINITE) {
+      cap = NAN;
+    } else if (flag[row] == GTO_RT_MOVING) {
+      double q;
+      rt_piece(Q + row * T, S + row * T, k, r, invh, q, p1, p2);
+      if (p1 != 0.0 && isfinite(lim.vmax[j])) {
+        const double v = lim.vmax[j] / fabs(p1);
+        cap = fmin(cap, v * v);
+      }
+      double al, bl;
+      if (!rt_line(p1, p2, lim.amax[j], al, bl) && p2 != 0.0 && g < d.N - 1)  // |p2 x| <= amax: a bound on x alone
+        cap = fmin(cap, lim.amax[j] / fabs(p2));
+    }
+    P1[id * ndof + j] = p1;
+    P2[id * ndof + j] = p2;
+  }
+  xcap[id] = cap;
+}
+
+__device__ __forceinline__ double rt_wave_min(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// x at which upper line (au, bu) falls below lower line (al, bl); inf if it never does for x >= 0
+__device__ __forceinline__ double rt_pair(double au, double bu, double al, double bl) {
+  const double db = bl - bu;
+  return db > 0.0 ? (au - al) / db : INFINITY;
+}
+
+// One wave per plan.  Lines 0..nm-1: the moving joints (mj); line nm: the link to the next gridpoint,
+// upper u <= (X_{i+1} - x) / (2 Delta), lower u >= -x / (2 Delta).
+__global__ __launch_bounds__(64) void k_retime_pass(const double* __restrict__ P1, const double* __restrict__ P2,
+                                                    const double* __restrict__ xcap, const int32_t* __restrict__ flag,
+                                                    RetimeLimits lim, RetimeDims d, double* __restrict__ X,
+                                                    double* __restrict__ Tg, int32_t* __restrict__ stat,
+                                                    double* __restrict__ duration_out, double* __restrict__ t_out,
+                                                    double* __restrict__ sd_out, int32_t* __restrict__ status_out) {
+  __shared__ double xmax[GTO_RETIME_MAX_N];
+  __shared__ double la[GTO_RETIME_LINES], lb[GTO_RETIME_LINES];
+  __shared__ int mj[GTO_MAX_DOF];
+  const long long b = blockIdx.x;
+  const int lane = threadIdx.x, N = d.N, ndof = d.ndof;
+  const int f = lane < ndof ? flag[b * ndof + lane] : GTO_RT_CONST;
+  const unsigned long long bad = __ballot(f == GTO_RT_NONFINITE), mov = __ballot(f == GTO_RT_MOVING);
+  const long long o = b * N;
+  if (bad) {
+    for (int i = lane; i < N; i += 64) {
+      X[o + i] = NAN, Tg[o + i] = NAN;
+      if (t_out) t_out[o + i] = NAN;
+      if (sd_out) sd_out[o + i] = NAN;
+    }
+    if (lane == 0) {
+      stat[b] = GTO_STATUS_NUMERICAL;
+      if (duration_out) duration_out[b] = NAN;
+      if (status_out) status_out[b] = GTO_STATUS_NUMERICAL;
+    }
+    return;
+  }
+  const int nm = __popcll(mov), nl = nm + 1;
+  if (f == GTO_RT_MOVING) mj[__popcll(mov & ((1ull << lane) - 1ull))] = lane;
+  const double c2d = 0.5 * (double)(N - 1), twoD = 2.0 / (double)(N - 1);
+  const double* p1 = P1 + o * ndof;
+  const double* p2 = P2 + o * ndof;
+  __syncthreads();
+  // backward pass: K_{N-1} = {0}, K_i = [0, xmax_i]
+  double Xn = 0.0;
+  if (lane == 0) xmax[N - 1] = 0.0;
+  if (nm > 0)
+    for (int i = N - 2; i >= 0; --i) {
+      if (lane < nm) {
+        const int j = mj[lane];
+        double al, bl;
+        rt_line(p1[(long long)i * ndof + j], p2[(long long)i * ndof + j], lim.amax[j], al, bl);
+        la[lane] = al, lb[lane] = bl;
+      } else if (lane == nm) {
+        la[lane] = Xn * c2d, lb[lane] = -c2d;
+      }
+      __syncthreads();
+      double best = INFINITY;
+      int k = lane / nl, m = lane - k * nl;
+      for (int p = lane; p < nl * nl; p += 64) {
+        best = fmin(best, rt_pair(la[k], lb[k], m == nm ? 0.0 : -la[m], lb[m]));
+        for (m += 64; m >= nl; m -= nl) ++k;
+      }
+      best = rt_wave_min(best);
+      Xn = fmax(0.0, fmin(xcap[o + i], best));
+      if (lane == 0) xmax[i] = Xn;
+      __syncthreads();
+    }
+  // forward pass: x_0 = 0, u_i = the smallest upper bound at x_i, x_{i+1} clamped into K_{i+1}; times on the way
+  double x = 0.0, t = 0.0, xtop = 0.0, rest = INFINITY;  // largest x; smallest max(x_i, x_{i+1}) over the segments
+  if (lane == 0) {
+    X[o] = 0.0, Tg[o] = 0.0;
+    if (t_out) t_out[o] = 0.0;
+    if (sd_out) sd_out[o] = 0.0;
+  }
+  for (int i = 0; i < N - 1; ++i) {
+    double xn = 0.0;
+    if (nm > 0) {
+      const double Xi1 = xmax[i + 1];
+      double cand = INFINITY;
+      if (lane < nm) {
+        const int j = mj[lane];
+        double al, bl;
+        rt_line(p1[(long long)i * ndof + j], p2[(long long)i * ndof + j], lim.amax[j], al, bl);
+        cand = fma(bl, x, al);
+      } else if (lane == nm) {
+        cand = fma(-c2d, x, Xi1 * c2d);
+      }
+      const double u = rt_wave_min(cand);
+      xn = fmin(fmax(fma(u, twoD, x), 0.0), Xi1);
+      t += twoD / (sqrt(x) + sqrt(xn));
+      xtop = fmax(xtop, xn);
+      rest = fmin(rest, fmax(x, xn));
+    }
+    x = xn;
+    if (lane == 0) {
+      X[o + i + 1] = x, Tg[o + i + 1] = t;
+      if (t_out) t_out[o + i + 1] = t;
+      if (sd_out) sd_out[o + i + 1] = sqrt(x);
+    }
+  }
+  if (lane == 0) {
+    const bool stall = nm > 0 && rest <= GTO_RETIME_STALL * xtop;
+    const int32_t s = isfinite(t) && !stall ? GTO_STATUS_CONVERGED : GTO_STATUS_NUMERICAL;
+    stat[b] = s;
+    if (duration_out) duration_out[b] = t;
+    if (status_out) status_out[b] = s;
+  }
+}
+
+// Samples at linspace(0, duration, M) (numpy's values): the segment i with t_i <= t < t_{i+1}, s and sdot under the
+// segment's constant acceleration, q = spline(s), qdot = p1 sdot, qddot = p1 sddot + p2 sdot^2.  [B][M][ndof]
+__global__ __launch_bounds__(256) void k_retime_sample(const double* __restrict__ Q, const double* __restrict__ S,
+                                                       const double* __restrict__ X, const double* __restrict__ Tg,
+                                                       const int32_t* __restrict__ stat, RetimeDims d,
+                                                       double* __restrict__ q_out, double* __restrict__ qd_out,
+                                                       double* __restrict__ qdd_out) {
+  const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= (long long)d.B * d.M) return;
+  const long long b = id / d.M;
+  const int m = (int)(id - b * d.M), N = d.N, T = d.T, ndof = d.ndof;
+  if (stat[b] != GTO_STATUS_CONVERGED) {
+    for (int j = 0; j < ndof; ++j) {
+      if (q_out) q_out[id * ndof + j] = NAN;
+      if (qd_out) qd_out[id * ndof + j] = NAN;
+      if (qdd_out) qdd_out[id * ndof + j] = NAN;
+    }
+    return;
+  }
+  const double* t = Tg + b * N;
+  const double dur = t[N - 1];
+  const double tt = m == d.M - 1 ? dur : (double)m * (dur / (double)(d.M - 1));
+  int lo = 0, hi = N - 2;  // the largest i in [0, N-2] with t_i <= tt
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (t[mid] <= tt) lo = mid;
+    else hi = mid - 1;
+  }
+  const double x0 = X[b * N + lo], x1 = X[b * N + lo + 1];
+  const double v0 = sqrt(x0), u = (x1 - x0) * (0.5 * (double)(N - 1)), tau = tt - t[lo];
+  const double sd = v0 + u * tau;
+  double s = (double)lo / (double)(N - 1) + tau * (v0 + 0.5 * u * tau);
+  s = fmin(fmax(s, 0.0), 1.0);
+  const int k = min(max((int)(s * (double)(T - 1)), 0), T - 2);
+  const double r = s - (double)k / (double)(T - 1);
+  const double invh = (double)(T - 1);
+  for (int j = 0; j < ndof; ++j) {
+    const long long row = b * ndof + j;
+    double q, p1, p2;
+    rt_piece(Q + row * T, S + row * T, k, r, invh, q, p1, p2);
+    if (q_out) q_out[id * ndof + j] = q;
+    if (qd_out) qd_out[id * ndof + j] = p1 * sd;
+    if (qdd_out) qdd_out[id * ndof + j] = p1 * u + p2 * sd * sd;
+  }
+}

@@ -107,6 +107,17 @@ class GTORobotModel:
     def upper_optimized_joint_limits(self) -> DM:
         return DM(self.desc.upper[self.desc.opt_index])
 
+    @property
+    def velocity_actuated_joint_limits(self) -> DM:
+        """URDF <limit velocity> of every actuated joint (optas/models.py:497-506); +inf where the URDF gives none."""
+        v = self.desc.velocity
+        return DM(np.full(self.desc.ndof, np.inf) if v is None else v)
+
+    @property
+    def velocity_optimized_joint_limits(self) -> DM:
+        """The same for the optimised joints (optas/models.py:539-548)."""
+        return DM(np.asarray(self.velocity_actuated_joint_limits.toarray()).ravel()[self.desc.opt_index])
+
     def extract_parameter_dimensions(self, values):
         return np.asarray(values)[self.parameter_joint_indexes, :]
 

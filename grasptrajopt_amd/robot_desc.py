@@ -23,6 +23,11 @@ _JTYPE = {"fixed": JOINT_FIXED, "revolute": JOINT_REVOLUTE, "continuous": JOINT_
           "prismatic": JOINT_PRISMATIC}
 
 
+def _velocity_limit(v: float) -> float:
+    """A URDF velocity limit; 0 (no velocity attribute), >= 1e9 (no <limit> element, urdf.py) -> +inf, no limit."""
+    return np.inf if v <= 0.0 or v >= 1e9 else float(v)
+
+
 @dataclass
 class RobotDesc:
     name: str
@@ -48,6 +53,8 @@ class RobotDesc:
     points: np.ndarray = None       # (P,3) float64, visual-mesh frame
     normals: np.ndarray = None      # (P,3)
     point_link: np.ndarray = None   # (P,) int32
+    # joint velocity limits (ndof,) from <limit velocity>, +inf = no limit (optas/models.py:497-506); None = not recorded
+    velocity: Optional[np.ndarray] = None
 
     # ------------------------------------------------------------------ properties
     @property
@@ -103,6 +110,7 @@ class RobotDesc:
                 raise NotImplementedError(f"{j.type} joints are not supported (optas/models.py:865-866)")
         lower = np.array([urdf.joint_map[j].lower for j in actuated], dtype=np.float64)
         upper = np.array([urdf.joint_map[j].upper for j in actuated], dtype=np.float64)
+        velocity = np.array([_velocity_limit(urdf.joint_map[j].velocity) for j in actuated], dtype=np.float64)
         params = [j for j in actuated if j in set(param_joints)]
         opt_index = np.array([i for i, j in enumerate(actuated) if j not in params], dtype=np.int32)
         param_index = np.array([i for i, j in enumerate(actuated) if j in params], dtype=np.int32)
@@ -158,7 +166,7 @@ class RobotDesc:
 
         desc = cls(name=urdf.name, frame_names=order, parent=parent, joint_type=jtype, q_index=qidx,
                    origin_xyz=oxyz, origin_rpy=orpy, axis=axis, actuated_joint_names=actuated,
-                   lower=lower, upper=upper, opt_index=opt_index, param_index=param_index)
+                   lower=lower, upper=upper, opt_index=opt_index, param_index=param_index, velocity=velocity)
         desc.link_names = [l.name for l in links]
         desc.link_frame = np.array([fidx[l.name] for l in links], dtype=np.int32)
         desc.visual_xyz = np.array([l.visual_xyz for l in links], dtype=np.float64).reshape(-1, 3)
@@ -181,6 +189,8 @@ class RobotDesc:
     def save(self, prefix: str) -> None:
         meta = dict(name=self.name, frame_names=self.frame_names,
                     actuated_joint_names=self.actuated_joint_names, link_names=self.link_names)
+        if self.velocity is not None:  # JSON null = no limit
+            meta["velocity_limits"] = [float(v) if np.isfinite(v) else None for v in self.velocity]
         with open(prefix + ".json", "w") as fh:
             json.dump(meta, fh, indent=1)
         np.savez_compressed(
@@ -195,13 +205,16 @@ class RobotDesc:
         with open(prefix + ".json") as fh:
             meta = json.load(fh)
         z = np.load(prefix + ".npz")
+        vel = meta.get("velocity_limits")  # absent in descriptions written before velocity limits were recorded
+        if vel is not None:
+            vel = np.array([np.inf if v is None else v for v in vel], dtype=np.float64)
         return cls(name=meta["name"], frame_names=meta["frame_names"], parent=z["parent"],
                    joint_type=z["joint_type"], q_index=z["q_index"], origin_xyz=z["origin_xyz"],
                    origin_rpy=z["origin_rpy"], axis=z["axis"],
                    actuated_joint_names=meta["actuated_joint_names"], lower=z["lower"], upper=z["upper"],
                    opt_index=z["opt_index"], param_index=z["param_index"], link_names=meta["link_names"],
                    link_frame=z["link_frame"], visual_xyz=z["visual_xyz"], visual_rpy=z["visual_rpy"],
-                   points=z["points"], normals=z["normals"].astype(np.float64), point_link=z["point_link"])
+                   points=z["points"], normals=z["normals"].astype(np.float64), point_link=z["point_link"], velocity=vel)
 
 
 def with_planar_base(desc: RobotDesc, xy_limit: float = 1.0, name: Optional[str] = None) -> RobotDesc:
@@ -223,7 +236,8 @@ def with_planar_base(desc: RobotDesc, xy_limit: float = 1.0, name: Optional[str]
         lower=np.concatenate([[-xy_limit, -xy_limit, -np.pi], desc.lower]), upper=np.concatenate([[xy_limit, xy_limit, np.pi], desc.upper]),
         opt_index=np.concatenate([[0, 1, 2], desc.opt_index + 3]).astype(np.int32), param_index=(desc.param_index + 3).astype(np.int32),
         link_names=list(desc.link_names), link_frame=(desc.link_frame + 4).astype(np.int32), visual_xyz=desc.visual_xyz.copy(),
-        visual_rpy=desc.visual_rpy.copy(), points=desc.points.copy(), normals=desc.normals.copy(), point_link=desc.point_link.copy())
+        visual_rpy=desc.visual_rpy.copy(), points=desc.points.copy(), normals=desc.normals.copy(), point_link=desc.point_link.copy(),
+        velocity=None if desc.velocity is None else np.concatenate([[np.inf, np.inf, np.inf], desc.velocity]))
     assert out.n_frames == F0 + 4
     return out
 

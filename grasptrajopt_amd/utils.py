@@ -82,3 +82,40 @@ def grasp_collision_ratio(gripper_model, depth_pc, RT_grasps, q_gripper, RT_offs
 def filter_grasps(gripper_model, depth_pc, RT_grasps, q_gripper, RT_offset=None, threshold: float = 0.01):
     """in_collision (n,) int32 exactly as the driver builds it: ratio > threshold."""
     return (grasp_collision_ratio(gripper_model, depth_pc, RT_grasps, q_gripper, RT_offset) > threshold).astype(np.int32)
+
+
+def _retime_handle(robot, T: int):
+    """The robot's utility handle for horizon T (retiming only reads the handle's T and ndof)."""
+    from . import _capi
+    o = _capi.default_opts()
+    o.T = int(T)
+    o.standoff_offset = max(int(o.standoff_offset), 2 - int(T))  # any valid standoff waypoint: retiming does not use it
+    ln = robot.desc.link_names[-1]
+    return robot.solver_handle(ln, ln, o, role="util")
+
+
+def retime_plans(robot, plans, vlim=None, alim=0.5, subdiv: int = 2, n_samples: int = 100):
+    """Time-optimal retiming of plans (B, ndof, T) or one plan (ndof, T) on the GPU (gto_retime_batch, include/gto_solver.h):
+    not-a-knot cubic spline through the waypoints on linspace(0, 1, T), joint velocity limits ``vlim`` (default: the URDF's,
+    ``robot.velocity_actuated_joint_limits``) and acceleration limits ``alim`` (default 0.5 rad/s^2, gto/utils.py:295),
+    TOPP-RA's discretisation on subdiv (T-1) + 1 gridpoints, constant acceleration between them.  Returns a dict of
+    duration (B,), t_grid (B, N), sd_grid (B, N), q / qd / qdd (B, n_samples, ndof) at linspace(0, duration, n_samples)
+    and status (B,)."""
+    plans = np.asarray(plans, dtype=np.float64)
+    if plans.ndim == 2:
+        plans = plans[None]
+    if vlim is None:
+        vlim = np.asarray(robot.velocity_actuated_joint_limits.toarray()).ravel()
+    return _retime_handle(robot, plans.shape[2]).retime_batch(plans, vlim, alim, subdiv=subdiv, n_samples=n_samples)
+
+
+def convert_plan_to_trajectory_toppra(robot, plan, is_show: bool = False):
+    """gto/utils.py:283-323 on the GPU: plan (ndof, T) -> (qs_sample, qds_sample, qdds_sample, ts_sample), 100 samples of
+    each, in the reference's order.  Velocity limits from the URDF for all ndof joints (the reference passes the n_opt
+    optimised ones for an ndof path; parameter rows of a solved plan are constant, so their limits have no effect),
+    acceleration limits 0.5.  The gridpoints are fixed (retime_plans, subdiv=2) where toppra picks them adaptively."""
+    if is_show:
+        raise NotImplementedError("convert_plan_to_trajectory_toppra(is_show=True): plotting is not ported")
+    r = retime_plans(robot, np.asarray(plan, dtype=np.float64)[None], n_samples=100)
+    ts = np.linspace(0.0, r["duration"][0], 100)
+    return r["q"][0], r["qd"][0], r["qdd"][0], ts

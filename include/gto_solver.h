@@ -116,7 +116,7 @@ void gto_default_opts(gto_solver_opts* opts);
 /* Library/ABI version (major*1000 + minor): GTO_ABI_VERSION of the header the library was built from.  A binding checks it
  * when it loads the library and refuses another number (grasptrajopt_amd/_capi.py load_library): every change of a
  * signature or of a struct in this header bumps the minor. */
-#define GTO_ABI_VERSION 1007
+#define GTO_ABI_VERSION 1008
 int32_t gto_version(void);
 
 /*
@@ -393,6 +393,45 @@ int gto_scene_from_depth(gto_handle* h, int32_t scene_id, const float* depth, in
                          float w_inside, int32_t* shape_out, double* origin_out, double* bounds_out);
 /* The two float32 cost fields of a resident scene, device to host (either pointer may be NULL). */
 int gto_get_scene_fields(gto_handle* h, int32_t scene_id, float* c_all_out, float* c_obs_out);
+
+/*
+ * Retiming: B plans [B, ndof, T] (T = the handle's horizon; e.g. the Q_out of gto_solve_batch_device) turned into
+ * time-optimal trajectories under per-joint velocity and acceleration limits.
+ *   1. path: the not-a-knot cubic spline through the T waypoints on s_k = k/(T-1), every joint
+ *      (scipy.interpolate.CubicSpline(ss, Q.T, bc_type="not-a-knot")); p1 = q'(s), p2 = q''(s) on a grid of
+ *      N = subdiv (T-1) + 1 points (the knots and subdiv-1 even points inside each interval), N <= 1024;
+ *   2. TOPP-RA's discretisation, x = sdot^2, u = sddot, Delta = 1/(N-1): x_i <= min_j (vmax_j/|p1_j|)^2 at every gridpoint
+ *      (joints with p1_j = 0 or vmax_j = +inf skipped), -amax_j <= p1_j u_i + p2_j x_i <= amax_j at gridpoints 0..N-2
+ *      (where |p1_j| is 0 or so small that amax_j/|p1_j| or p2_j/p1_j overflows: |p2_j x_i| <= amax_j),
+ *      x_0 = x_{N-1} = 0, x_{i+1} = x_i + 2 Delta u_i;
+ *   3. the controllable sets by a backward pass of exact two-variable LPs, 4. the greedy forward pass (TOPP-RA's:
+ *      u_i the largest that keeps x_{i+1} in its controllable set), 5. t_{i+1} = t_i + 2 Delta / (sqrt x_i + sqrt x_{i+1}), constant
+ *      acceleration between gridpoints, 6. q, qdot = p1 sdot, qddot = p1 sddot + p2 sdot^2 at linspace(0, duration, M).
+ *   vmax [ndof]  > 0, +inf = no limit;  amax [ndof]  finite, > 0.  HOST arrays in both variants (they travel as a kernel
+ *                argument): invalid limits, subdiv < 1, M < 2 or N > 1024 fail the whole call with GTO_ERR_INVALID_ARG.
+ * Outputs (any may be NULL): duration_out [B], t_grid_out [B, N], sd_grid_out [B, N] (sdot at the gridpoints),
+ * q_out / qd_out / qdd_out [B, M, ndof], status_out [B]: GTO_STATUS_CONVERGED, or GTO_STATUS_NUMERICAL for a plan with a
+ * non-finite entry (its outputs are NaN; no other plan's output changes), or for a plan whose profile rests over a whole
+ * segment: x at both of its ends <= 1e-6 x the plan's largest x (sdot below 1e-3 of its largest), where the segment's
+ * time, and so the duration, is decided by round-off (infinite when both are exactly 0).  Such a plan's duration, t_grid
+ * and sd_grid are returned as computed, its samples are NaN.  The greedy forward pass is not pointwise maximal where a
+ * larger x_i lowers the u_i its segment can take, and that is how a profile can come to rest: at gridpoint N-2 after
+ * x_{N-3} reached the edge of its controllable set (19 of 16384 random Panda plans).  A plan whose waypoints are all equal has
+ * duration 0 and samples at the waypoint with zero derivatives.  Constant joints (parameter rows of a solved plan) have
+ * p1 = p2 = 0, so their limits have no effect.  B = 0 returns GTO_OK without a launch.  Every plan's result is bit for bit
+ * the same in any batch.
+ * Replaces: convert_plan_to_trajectory_toppra (gto/utils.py:283-323): toppra.SplineInterpolator, JointVelocityConstraint,
+ *           JointAccelerationConstraint, TOPPRA(..., parametrizer="ParametrizeConstAccel").compute_trajectory() and the
+ *           100 samples of q, qd, qdd (the reference's gridpoints are toppra's adaptive ones; here they are fixed).
+ */
+int gto_retime_batch(gto_handle* h, int32_t B, const double* plans, const double* vmax, const double* amax, int32_t subdiv,
+                     int32_t M, double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out, double* qd_out,
+                     double* qdd_out, int32_t* status_out);
+/* The same with plans and outputs in device memory, enqueued on `stream` (NULL = the handle's stream; asynchronous except
+ * for the first call of a handle, which uploads the spline factors and synchronises).  vmax / amax stay host arrays. */
+int gto_retime_batch_device(gto_handle* h, int32_t B, const double* plans, const double* vmax, const double* amax,
+                            int32_t subdiv, int32_t M, double* duration_out, double* t_grid_out, double* sd_grid_out,
+                            double* q_out, double* qd_out, double* qdd_out, int32_t* status_out, void* stream);
 
 #ifdef __cplusplus
 }

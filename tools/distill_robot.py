@@ -24,6 +24,8 @@ def main():
     ap.add_argument("--ref", default="/root/reference")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..",
                                                    "grasptrajopt_amd", "data"))
+    ap.add_argument("--json-only", action="store_true",
+                    help="rewrite <name>.json only (names, velocity limits) and keep the committed .npz (surface points)")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     for robot, variants in (("panda", (("panda", 100), ("panda_5k", 417))), ("fetch", (("fetch", 100),))):
@@ -35,7 +37,13 @@ def main():
                                        collision_link_names=cfg["collision_link_names"],
                                        extra_links=[cfg["link_ee"], cfg["link_gripper"]],
                                        model_dir=model_dir, points_per_link=ppl, seed=0)
-            desc.save(os.path.join(args.out, name))
+            if args.json_only:  # same JSON as a full run: save() into a scratch prefix, keep only its JSON
+                import tempfile
+                with tempfile.TemporaryDirectory() as tmp:
+                    desc.save(os.path.join(tmp, name))
+                    os.replace(os.path.join(tmp, name + ".json"), os.path.join(args.out, name + ".json"))
+            else:
+                desc.save(os.path.join(args.out, name))
             print(name, "frames", desc.n_frames, "links", desc.n_links, "points", desc.n_points,
                   "ndof", desc.ndof, "opt", desc.opt_index.tolist())
         keep = {k: cfg[k] for k in ("robot_name", "link_ee", "link_gripper", "axis_standoff", "default_pose",
