@@ -678,7 +678,7 @@ static int build_robot(const gto_robot_desc* d, int pb_merge, RobotTables& t, st
   }
   t.pb_C = (int)pbchunks.size();
   if (pbchunks.empty()) pbchunks.push_back(PbChunk{0, 0, 0, 0, 0, 0});  // (a robot none of whose links moves: the table is never read)
-  if (rb.n_chunks > GTO_MAX_ACTIVE) return bad(GTO_ERR_UNSUPPORTED, "too many surface points (max 16384)");
+  if (rb.n_chunks > GTO_MAX_ACTIVE) return bad(GTO_ERR_UNSUPPORTED, "too many surface points (max 16384, in at most 256 runs of up to 64 points of one link)");
   t.perm = std::move(perm);
   t.px = std::move(px), t.py = std::move(py), t.pz = std::move(pz);
   t.plink = std::move(plink);
@@ -714,15 +714,19 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
   // matrix-core prefix, projection onto sixteen screws) is larger than an 8-wide one's, and since round 6 the epilogue
   // projects one waypoint at a time (ObsLds: its scratch no longer grows with the group): configs[4] with 2 / 3 / 4 / 5 /
   // 6 / 8 waypoints per workgroup 29.0 / 33.1 / 35.4 / 36.6 / 34.8 / 28.7 k trajectories/s (until round 6: two, 28.2 k)
-  int tg_w = tu.obs_tg_wide;
+  // The 8-wide robots keep room for GTO_MAX_TG waypoints (any GTO_OBS_TG*), and the same shrinking when theirs would not
+  // fit: with 26 or more links of 64 points each at 32 frames, eight waypoints' Grams and chunk lists overflow the LDS.
+  int tg_w = wide ? tu.obs_tg_wide : GTO_MAX_TG;
   if (wide && tu.obs_tg_given) tg_w = std::max(tg_w, tu.obs_tg);
-  while (wide && tg_w > 1 && (size_t)ObsLds(tg_w, rb.n_frames, rb.n_links, tg_w * rb.n_chunks, np).total_doubles * sizeof(double) > 150 * 1024) --tg_w;
-  const int tg_lds = wide ? tg_w : GTO_MAX_TG;
-  const ObsLds lay(tg_lds, rb.n_frames, rb.n_links, tg_lds * rb.n_chunks, np);
+  while (tg_w > 1 && (size_t)ObsLds(tg_w, rb.n_frames, rb.n_links, tg_w * rb.n_chunks, np).total_doubles * sizeof(double) > 150 * 1024) --tg_w;
+  const ObsLds lay(tg_w, rb.n_frames, rb.n_links, tg_w * rb.n_chunks, np);
   if ((size_t)lay.total_doubles * sizeof(double) > 150 * 1024) return fail(nullptr, GTO_ERR_UNSUPPORTED, "robot too large for the obstacle kernel's LDS");
   if (wide) {
     tu.obs_tg = tu.obs_tg_given ? std::min(tu.obs_tg, tg_w) : tg_w;
     tu.obs_tg_few = std::min(tu.obs_tg_few, tu.obs_tg), tu.obs_tg_few_tail = std::min(tu.obs_tg_few_tail, tu.obs_tg);
+  } else if (tg_w < GTO_MAX_TG) {
+    tu.obs_tg = std::min(tu.obs_tg, tg_w);
+    tu.obs_tg_few = std::min(tu.obs_tg_few, tg_w), tu.obs_tg_few_tail = std::min(tu.obs_tg_few_tail, tg_w);
   }
   // candidates per step the eight-wave step kernel's LDS has room for at this T
   int spec_kmax = 1;

@@ -40,6 +40,9 @@ extern "C" {
 #define GTO_MAX_LINKS 32  /* collision links carrying surface points   */
 #define GTO_MAX_OPT 16    /* optimised joints (Panda/Fetch arm: 7, mobile Fetch: 10); IK / base placement: up to 8 */
 #define GTO_MAX_DOF 32    /* actuated joints (Panda 9, Fetch 15)        */
+/* Surface points: at most 16384, taken link by link in runs of up to 64 points, at most 256 runs in all (a link of 65 points
+ * takes two).  Every robot within these limits is created, at every T from 4 to 96: where a robot's tables
+ * leave no room for the obstacle kernel's usual waypoints per workgroup, it runs fewer (same results). */
 
 /* joint types (optas/models.py:850-866) */
 #define GTO_JOINT_FIXED 0

@@ -84,9 +84,10 @@ def _close(a, b, rtol=RTOL):
     assert np.all(np.abs(a - b) <= rtol * scale), f"max |diff| {np.abs(a - b).max():.3e}, scale {scale:.3e}"
 
 
-def _check_against_ref(desc, h, plans, subdiv=2, M=100, vmax=None):
-    vm, am = _limits(desc)
+def _check_against_ref(desc, h, plans, subdiv=2, M=100, vmax=None, amax=None):
+    vm, am = _limits(desc) if desc.velocity is not None else (None, None)
     vm = vm if vmax is None else vmax
+    am = am if amax is None else amax
     g = h.retime_batch(plans, vm, am, subdiv=subdiv, n_samples=M)
     r = rr.retime(plans, vm, am, subdiv, M)
     assert np.array_equal(g["status"], r["status"])
@@ -360,3 +361,123 @@ def test_python_surface(panda):
     fp = rr.random_plans(fetch_robot.desc, 2, 80, seed=14)
     assert utils.retime_plans(fetch_robot, fp)["t_grid"].shape == (2, 159)
     assert g is not None
+
+
+# ------------------------------------------------------------------------------------------ width and length
+def _limit_handle(T):
+    from helpers import limit_robot
+    desc, ee = limit_robot("chain", n_opt=16)
+    o = _capi.default_opts()
+    o.T, o.standoff_offset = T, -2
+    return desc, _capi.SolverHandle(desc, ee, ee, o, device=0)
+
+
+def _moving_plans(desc, B, T, mask, seed):
+    """random_plans with exactly the joints of `mask` moving (the others constant, parameter joints included)."""
+    rng = np.random.default_rng(seed)
+    lo, hi = np.maximum(desc.lower, -3.0), np.minimum(desc.upper, 3.0)
+    s = np.linspace(0.0, 1.0, T)
+    a = lo + (hi - lo) * rng.uniform(0.2, 0.8, (B, desc.ndof))
+    b = lo + (hi - lo) * rng.uniform(0.2, 0.8, (B, desc.ndof))
+    P = a[..., None] + (b - a)[..., None] * (3 * s ** 2 - 2 * s ** 3)
+    P += 0.05 * np.sin(2 * np.pi * rng.uniform(0.5, 2.0, (B, desc.ndof, 1)) * s + rng.uniform(0, 6, (B, desc.ndof, 1)))
+    still = np.setdiff1d(np.arange(desc.ndof), mask)
+    P[:, still] = P[:, still, :1]
+    return P
+
+
+def _wide_limits(desc):
+    rng = np.random.default_rng(3)
+    vm = rng.uniform(0.5, 2.5, desc.ndof)
+    vm[::7] = np.inf
+    return vm, rng.uniform(0.3, 1.5, desc.ndof)
+
+
+@pytest.mark.parametrize("T", [50, 96])
+@pytest.mark.parametrize("mask", ["all", "0,13,30", "15", "all but 7", "0,1,2,3,4,5,6,7,8,9,10"])
+def test_limit_robot_moving_masks(T, mask):
+    """The 31-joint chain of tests/helpers.limit_robot: every joint moving (31 acceleration lines and the link to the next
+    gridpoint: 32 lines, 1024 pairs, 16 sweeps of the pass kernel's pair loop), the moving joints packed by a ballot prefix
+    count from masks that are not contiguous ({0, 13, 30}, one joint alone, all but one) and the contiguous run tests had."""
+    desc, h = _limit_handle(T)
+    assert desc.ndof == 31
+    m = {"all": np.arange(31), "all but 7": np.setdiff1d(np.arange(31), [7])}.get(mask)
+    m = np.array([int(v) for v in mask.split(",")]) if m is None else m
+    plans = _moving_plans(desc, 6, T, m, seed=len(m) + T)
+    moving = np.any(plans != plans[:, :, :1], axis=2)
+    assert (moving == np.isin(np.arange(31), m)[None]).all()
+    vm, am = _wide_limits(desc)
+    g = _check_against_ref(desc, h, plans, vmax=vm, amax=am)
+    ok = _converged(g)
+    assert len(ok) >= 4, g["status"]
+    _derived_checks(desc, plans[ok], {k: v[ok] for k, v in g.items()}, vm, am)
+    h.close()
+
+
+@pytest.mark.parametrize("T,subdiv", [(94, 11), (4, 341), (50, 2)])
+def test_limit_robot_longest_grid(T, subdiv):
+    """N = subdiv (T - 1) + 1 = 1024 gridpoints, the most the pass kernel keeps in LDS, on the 31-joint chain with every joint
+    moving; one gridpoint more is refused."""
+    desc, h = _limit_handle(T)
+    N = subdiv * (T - 1) + 1
+    assert N in (1024, 99)
+    plans = _moving_plans(desc, 3, T, np.arange(31), seed=T)
+    vm, am = _wide_limits(desc)
+    g = _check_against_ref(desc, h, plans, subdiv=subdiv, M=257, vmax=vm, amax=am)
+    assert g["sd_grid"].shape == (3, N)
+    ok = _converged(g)
+    assert len(ok) >= 2, g["status"]
+    _derived_checks(desc, plans[ok], {k: v[ok] for k, v in g.items()}, vm, am, subdiv=subdiv)
+    h.close()
+    if N == 1024:
+        for T2, sd2 in ((5, 256), (33, 32)):   # N = 1025
+            desc, h = _limit_handle(T2)
+            with pytest.raises(_capi.GTOError, match=r"\(-1\): gto_retime_batch: subdiv \(T-1\) \+ 1 must be <= 1024"):
+                h.retime_batch(_moving_plans(desc, 1, T2, np.arange(31), seed=1), vm, am, subdiv=sd2)
+            h.close()
+
+
+def test_joint_moving_by_1e_300_takes_the_overflow_path():
+    """A joint that moves by ~1e-300 under a large acceleration limit: amax / |p1| overflows at every gridpoint, the joint
+    bounds x through |p2 x| <= amax alone (rt_line's overflow path on the GPU, retime_ref._has_line in the restatement),
+    and the plan is retimed by the other joints as if it stood still."""
+    desc, h = _limit_handle(50)
+    plans = _moving_plans(desc, 4, 50, np.arange(31), seed=9)
+    s = np.linspace(0.0, 1.0, 50)
+    plans[:, 12] = 1e-300 * (3 * s ** 2 - 2 * s ** 3)[None] * np.array([1.0, -2.0, 0.5, 3.0])[:, None]
+    vm, am = _wide_limits(desc)
+    am[12] = 1e12
+    for b in range(4):
+        _, _, p1, p2 = rr.path_derivatives(plans[b], 2)
+        assert np.any(p1[:, 12] != 0) and not rr._has_line(p1[:, 12], p2[:, 12], np.full(len(p1), am[12])).any()
+    g = _check_against_ref(desc, h, plans, vmax=vm, amax=am)
+    ok = _converged(g)
+    assert len(ok) >= 3, g["status"]
+    _derived_checks(desc, plans[ok], {k: v[ok] for k, v in g.items()}, vm, am)
+    # the same plans with joint 12 standing still: the same profile up to round-off
+    still = plans.copy()
+    still[:, 12] = 0.0
+    g0 = h.retime_batch(still, vm, am)
+    np.testing.assert_array_equal(g0["status"], g["status"])
+    _close(g["sd_grid"][ok] ** 2, g0["sd_grid"][ok] ** 2)
+    h.close()
+
+
+def test_lp_every_gridpoint(panda):
+    """The controllable set and the forward step of independent LPs at every interior gridpoint of N = 99 (not four)."""
+    desc, cfg, h = panda
+    plans = rr.random_plans(desc, 3, 50, seed=12)
+    vm, am = _limits(desc)
+    g = h.retime_batch(plans, vm, am)
+    N = plans.shape[2] * 2 - 1
+    for b in _converged(g):
+        moving = np.any(plans[b] != plans[b][:, :1], axis=1)
+        _, _, p1, p2 = rr.path_derivatives(plans[b], 2)
+        p1[:, ~moving] = 0.0
+        p2[:, ~moving] = 0.0
+        x = g["sd_grid"][b] ** 2
+        for i in range(1, N - 1):
+            xl = rr.controllable_lp(p1, p2, vm, am, i)
+            assert x[i] <= xl * (1 + LP_RTOL) + 1e-15, i
+            xs = rr.step_lp(p1, p2, vm, am, i - 1, x[i - 1], xl)
+            assert x[i] == pytest.approx(xs, rel=LP_RTOL, abs=1e-12), i
