@@ -4,6 +4,8 @@ Only the hot path of IRVLUTD/GraspTrajOpt lives here: the trajectory solve behin
 GTOPlanner.plan()/plan_goalset().  Public surface:
     GTORobotModel, GTOPlanner            drop-in for the reference's gto.gto_models / gto.gto_planner
     IKSolver                             drop-in for gto.ik_solver (batched on the GPU)
+    ik_solver_quaternion.IKSolver        drop-in for gto.ik_solver_quaternion (position + quaternion goals, on the GPU)
+    ik_solver_rpy.IKSolver               drop-in for gto.ik_solver_rpy (position + roll-pitch-yaw goals, on the GPU)
     DepthPointCloud                      drop-in for mesh_to_sdf.depth_point_cloud (cost fields on the GPU)
     BasePlanner                          drop-in for gto.base_planner (mobile base placement on the GPU)
     optas_facade                         OptimizationBuilder / CasADiSolver-shaped recorder + solver

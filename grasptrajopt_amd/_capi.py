@@ -106,7 +106,7 @@ def pack_robot_desc(desc: RobotDesc, link_ee: str, link_gripper: str,
 # include/gto_solver.h
 GTO_GRAD_CENTRAL_DIFF, GTO_GRAD_ZERO = 0, 1
 GTO_STATUS_CONVERGED, GTO_STATUS_MAX_ITER, GTO_STATUS_NUMERICAL = 0, 1, 2
-ABI_VERSION = 1008  # include/gto_solver.h GTO_ABI_VERSION (checked against gto_version() when the library is loaded)
+ABI_VERSION = 1009  # include/gto_solver.h GTO_ABI_VERSION (checked against gto_version() when the library is loaded)
 
 _lib = None
 
@@ -216,6 +216,7 @@ def load_library(path: Optional[str] = None):
     lib.gto_eval_obstacle_normal_eq.argtypes = [H, C.c_int32, _pi, _pd, _pd, _pd, _pd, _pd]
     lib.gto_plan_cost.argtypes = [H, C.c_int32, C.c_int32, _pd, _pd, _pd, _pd]
     lib.gto_solve_ik_batch.argtypes = [H, C.c_int32, _pi, _pd, _pd, _pd, C.c_int32, _pd, _pd, _pi, _pi]
+    lib.gto_solve_ik_pose_batch.argtypes = [H, C.c_int32, C.c_int32, _pi, _pd, _pd, _pd, C.c_int32, _pd, _pd, _pi, _pi]
     lib.gto_solve_base_batch.argtypes = [H, C.c_int32, C.c_int32, _pi, _pd, _pd, C.c_double, C.c_int32, _pd, _pd, _pd, _pi, _pi]
     lib.gto_eval_base_objective.argtypes = [H, C.c_int32, C.c_int32, _pi, _pd, _pd, _pd, C.c_double, _pd]
     lib.gto_retime_batch.argtypes = [H, C.c_int32, _pd, _pd, _pd, C.c_int32, C.c_int32, _pd, _pd, _pd, _pd, _pd, _pd, _pi]
@@ -226,7 +227,7 @@ def load_library(path: Optional[str] = None):
     for fn in ("gto_create", "gto_set_opts", "gto_set_scene", "gto_set_scene_values", "gto_drop_scene", "gto_solve_batch",
                "gto_solve_batch_device", "gto_last_kernel_time", "gto_last_kernel_work", "gto_set_profiling", "gto_set_stream", "gto_set_mode", "gto_set_lanes", "gto_set_lane_streams", "gto_share_scene",
                "gto_eval_fk", "gto_eval_points", "gto_eval_points_hessian", "gto_eval_objective", "gto_eval_obstacle_normal_eq", "gto_plan_cost", "gto_solve_ik_batch",
-               "gto_solve_base_batch", "gto_eval_base_objective", "gto_depth_sdf_cost", "gto_retime_batch", "gto_retime_batch_device"):
+               "gto_solve_ik_pose_batch", "gto_solve_base_batch", "gto_eval_base_objective", "gto_depth_sdf_cost", "gto_retime_batch", "gto_retime_batch_device"):
         getattr(lib, fn).restype = C.c_int
     if path is None:
         _lib = lib
@@ -238,8 +239,8 @@ EXPORTED_SYMBOLS = (
     "gto_set_scene", "gto_set_scene_values", "gto_drop_scene", "gto_solve_batch", "gto_solve_batch_device",
     "gto_last_kernel_time", "gto_last_kernel_work", "gto_last_kernel_profile", "gto_set_profiling", "gto_set_stream", "gto_set_mode", "gto_set_lanes", "gto_set_lane_streams", "gto_share_scene", "gto_share_scene_halves",
     "gto_eval_fk", "gto_eval_points", "gto_eval_points_hessian",
-    "gto_eval_objective", "gto_eval_obstacle_normal_eq", "gto_plan_cost", "gto_solve_ik_batch", "gto_solve_base_batch",
-    "gto_eval_base_objective", "gto_depth_sdf_cost", "gto_scene_from_depth", "gto_get_scene_fields",
+    "gto_eval_objective", "gto_eval_obstacle_normal_eq", "gto_plan_cost", "gto_solve_ik_batch", "gto_solve_ik_pose_batch",
+    "gto_solve_base_batch", "gto_eval_base_objective", "gto_depth_sdf_cost", "gto_scene_from_depth", "gto_get_scene_fields",
     "gto_retime_batch", "gto_retime_batch_device",
 )
 
@@ -550,6 +551,28 @@ class SolverHandle:
             self._check(self.lib.gto_solve_ik_batch(self._h, B, _p(sid, _pi), _p(q0, _pd), _p(goals, _pd), _p(base, _pd),
                                                     int(max_iter), _p(q, _pd), _p(cost, _pd), _p(iters, _pi), _p(status, _pi)),
                         "gto_solve_ik_batch")
+        return q, cost, iters, status
+
+    IK_GOAL_WIDTH = {0: 16, 1: 7, 2: 6}  # GTO_IK_GOAL_POINTS / _QUATERNION / _RPY: doubles per goal
+
+    def solve_ik_pose_batch(self, kind, scene_id, q0, goals, base_pos=None, max_iter=50):
+        """IK for B goals of link_ee of one kind (include/gto_solver.h GTO_IK_GOAL_*): 0 = RT (B,16) as solve_ik_batch,
+        1 = x y z qx qy qz qw (B,7) (gto/ik_solver_quaternion.py), 2 = x y z roll pitch yaw (B,6) (gto/ik_solver_rpy.py).
+        Returns (q (B,ndof), cost (B,), iters (B,), status (B,))."""
+        d = self.desc
+        q0 = _f64(q0).reshape(-1, d.ndof)
+        B = q0.shape[0]
+        goals = _f64(goals).reshape(B, -1)
+        if int(kind) in self.IK_GOAL_WIDTH and goals.shape[1] != self.IK_GOAL_WIDTH[int(kind)]:
+            raise ValueError(f"goal kind {kind} takes {self.IK_GOAL_WIDTH[int(kind)]} numbers per goal, not {goals.shape[1]}")
+        sid = None if scene_id is None else _i32(np.broadcast_to(np.asarray(scene_id), (B,)))
+        base = None if base_pos is None else _f64(np.broadcast_to(_f64(base_pos).reshape(-1, 3), (B, 3)))
+        q, cost = np.empty((B, d.ndof)), np.empty(B)
+        iters, status = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
+        self._check(self.lib.gto_solve_ik_pose_batch(self._h, int(kind), B, _p(sid, _pi), _p(q0, _pd), _p(goals, _pd),
+                                                     _p(base, _pd), int(max_iter), _p(q, _pd), _p(cost, _pd), _p(iters, _pi),
+                                                     _p(status, _pi)),
+                    "gto_solve_ik_pose_batch")
         return q, cost, iters, status
 
     def solve_base_batch(self, qc, goals, n_goals=None, effort_weight=0.01, max_iter=100):

@@ -1928,10 +1928,65 @@ int gto_solve_ik_batch(gto_handle* h, int32_t B, const int32_t* scene_id, const 
   sp.max_iter = max_iter;
   const size_t lds = (size_t)ik_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt) * sizeof(double);
   if (lds > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the IK kernel's LDS");
-  HIPCHK(h, raise_dynamic_lds((const void*)k_ik_solve, lds));
-  hipLaunchKernelGGL(k_ik_solve, dim3(B), dim3(256), lds, h->stream, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks,
+  HIPCHK(h, raise_dynamic_lds((const void*)k_ik_solve<GTO_IK_GOAL_POINTS>, lds));
+  hipLaunchKernelGGL(k_ik_solve<GTO_IK_GOAL_POINTS>, dim3(B), dim3(256), lds, h->stream, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks,
                      h->d_scenes, (const int32_t*)d_sid, (const double*)d_q0, (const double*)d_goals, (const double*)d_base, sp,
                      B, (double*)d_q, (double*)d_cost, (int32_t*)d_it, (int32_t*)d_stat);
+  HIPCHK(h, hipGetLastError());
+  if ((rc = fetch_out(h, 0, q_out, B * ndof * sizeof(double)))) return rc;
+  if ((rc = fetch_out(h, 2, cost_out, B * sizeof(double)))) return rc;
+  if ((rc = fetch_out(h, 3, iters_out, B * sizeof(int32_t)))) return rc;
+  if ((rc = fetch_out(h, 4, status_out, B * sizeof(int32_t)))) return rc;
+  if ((rc = sync_and_finish_out(h))) return rc;
+  return GTO_OK;
+}
+
+int gto_solve_ik_pose_batch(gto_handle* h, int32_t goal_kind, int32_t B, const int32_t* scene_id, const double* q0,
+                            const double* goals, const double* base_pos, int32_t max_iter, double* q_out, double* cost_out,
+                            int32_t* iters_out, int32_t* status_out) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (goal_kind != GTO_IK_GOAL_POINTS && goal_kind != GTO_IK_GOAL_QUATERNION && goal_kind != GTO_IK_GOAL_RPY)
+    return fail(h, GTO_ERR_INVALID_ARG, "unknown IK goal kind");
+  if (goal_kind == GTO_IK_GOAL_POINTS)  // the same call, launch and results
+    return gto_solve_ik_batch(h, B, scene_id, q0, goals, base_pos, max_iter, q_out, cost_out, iters_out, status_out);
+  if (B < 0 || max_iter < 0) return fail(h, GTO_ERR_INVALID_ARG, "B and max_iter must be >= 0");
+  if (B == 0) return GTO_OK;
+  if (!q0 || !goals || !q_out) return fail(h, GTO_ERR_INVALID_ARG, "null input array");
+  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, "gto_solve_ik_pose_batch handles up to eight optimised joints");
+  int rc;
+  if (scene_id && (rc = check_scene_ids_host(h, scene_id, B))) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t ndof = h->rb.ndof, gw = goal_kind == GTO_IK_GOAL_QUATERNION ? 7 : 6;
+  std::vector<double> zeros;
+  if (scene_id && !base_pos) {
+    zeros.assign((size_t)B * 3, 0.0);
+    base_pos = zeros.data();
+  }
+  const void *d_sid = nullptr, *d_q0, *d_goals, *d_base = nullptr;
+  void *d_q, *d_cost, *d_it, *d_stat;
+  if (scene_id && (rc = stage_in(h, 0, scene_id, B * sizeof(int32_t), &d_sid))) return rc;
+  if ((rc = stage_in(h, 1, q0, B * ndof * sizeof(double), &d_q0))) return rc;
+  if ((rc = stage_in(h, 2, goals, (size_t)B * gw * sizeof(double), &d_goals))) return rc;
+  if (scene_id && (rc = stage_in(h, 5, base_pos, (size_t)B * 3 * sizeof(double), &d_base))) return rc;
+  if ((rc = stage_out(h, 0, q_out, B * ndof * sizeof(double), &d_q))) return rc;
+  if ((rc = stage_out(h, 2, cost_out, B * sizeof(double), &d_cost))) return rc;
+  if ((rc = stage_out(h, 3, iters_out, B * sizeof(int32_t), &d_it))) return rc;
+  if ((rc = stage_out(h, 4, status_out, B * sizeof(int32_t), &d_stat))) return rc;
+  SolveParams sp = make_params(h, 1, false);
+  sp.max_iter = max_iter;
+  const size_t lds = (size_t)ik_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt) * sizeof(double);
+  if (lds > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the IK kernel's LDS");
+  const void* kern = goal_kind == GTO_IK_GOAL_QUATERNION ? (const void*)k_ik_solve<GTO_IK_GOAL_QUATERNION>
+                                                         : (const void*)k_ik_solve<GTO_IK_GOAL_RPY>;
+  HIPCHK(h, raise_dynamic_lds(kern, lds));
+  if (goal_kind == GTO_IK_GOAL_QUATERNION)
+    hipLaunchKernelGGL(k_ik_solve<GTO_IK_GOAL_QUATERNION>, dim3(B), dim3(256), lds, h->stream, h->d_rb, h->d_px, h->d_py, h->d_pz,
+                       h->d_chunks, h->d_scenes, (const int32_t*)d_sid, (const double*)d_q0, (const double*)d_goals,
+                       (const double*)d_base, sp, B, (double*)d_q, (double*)d_cost, (int32_t*)d_it, (int32_t*)d_stat);
+  else
+    hipLaunchKernelGGL(k_ik_solve<GTO_IK_GOAL_RPY>, dim3(B), dim3(256), lds, h->stream, h->d_rb, h->d_px, h->d_py, h->d_pz,
+                       h->d_chunks, h->d_scenes, (const int32_t*)d_sid, (const double*)d_q0, (const double*)d_goals,
+                       (const double*)d_base, sp, B, (double*)d_q, (double*)d_cost, (int32_t*)d_it, (int32_t*)d_stat);
   HIPCHK(h, hipGetLastError());
   if ((rc = fetch_out(h, 0, q_out, B * ndof * sizeof(double)))) return rc;
   if ((rc = fetch_out(h, 2, cost_out, B * sizeof(double)))) return rc;

@@ -39,31 +39,39 @@ class IKSolver:
         B = RTs.shape[0]
         q_0 = np.broadcast_to(np.asarray(q_0, dtype=np.float64).reshape(-1, self.robot.ndof), (B, self.robot.ndof))
         base = np.zeros(3) if base_position is None else np.asarray(base_position, dtype=np.float64).reshape(3)
-        sid = None
-        if self.collision_avoidance:
-            if sdf_cost_obstacle is None:
-                raise ValueError("collision_avoidance=True needs sdf_cost_obstacle")
-            sid = 0  # the IK solver owns its handle
-            from .depth_scene import resident_of
-            r = resident_of(sdf_cost_obstacle)
-            if r is not None:  # resident on the device (depth_scene.py): shared, not uploaded; whichever half of its scene the
-                # field is, it is what this solver reads as the obstacle field (shared again on every call: a later build of
-                # the resident scene leaves no stale pointer behind)
-                h.share_scene(sid, r.handle, r.sid, all_from=r.half, obs_from=r.half)
-            else:
-                shape, origin, res = self.robot.field_geometry()
-                h.set_scene(sid, np.asarray(sdf_cost_obstacle), None, shape, origin, res)
+        sid = self._bind_scene(sdf_cost_obstacle)
         q, f, iters, status = h.solve_ik_batch(sid, q_0, RTs.reshape(B, 16), base, self.max_iter)
         # errors as the reference reports them (gto/ik_solver.py:88-93)
         tf = h.eval_fk(q)[:, self._fe]
         err_pos = np.linalg.norm(RTs[:, :3, 3] - tf[:, :3, 3], axis=1)
         cosang = (np.einsum("bij,bij->b", RTs[:, :3, :3], tf[:, :3, :3]) - 1.0) / 2.0  # = 2 (q1.q2)^2 - 1
         err_rot = np.degrees(np.arccos(np.clip(cosang, -1.0, 1.0)))
-        cost = np.zeros(B)
-        if self.collision_avoidance:  # compute_plan_cost of a one-column plan (gto/gto_models.py:204-215)
-            _, _, val, _ = h.eval_points(sid, q, base, use_obs=True, want=("val",))
-            cost = val.sum(axis=1)
-        return q, err_pos, err_rot, cost, iters, status
+        return q, err_pos, err_rot, self._plan_cost(sid, q, base), iters, status
+
+    def _bind_scene(self, sdf_cost_obstacle):
+        """Scene id of the collision term on this solver's handle (None without collision avoidance)."""
+        if not self.collision_avoidance:
+            return None
+        if sdf_cost_obstacle is None:
+            raise ValueError("collision_avoidance=True needs sdf_cost_obstacle")
+        h, sid = self._handle, 0  # the IK solver owns its handle
+        from .depth_scene import resident_of
+        r = resident_of(sdf_cost_obstacle)
+        if r is not None:  # resident on the device (depth_scene.py): shared, not uploaded; whichever half of its scene the
+            # field is, it is what this solver reads as the obstacle field (shared again on every call: a later build of
+            # the resident scene leaves no stale pointer behind)
+            h.share_scene(sid, r.handle, r.sid, all_from=r.half, obs_from=r.half)
+        else:
+            shape, origin, res = self.robot.field_geometry()
+            h.set_scene(sid, np.asarray(sdf_cost_obstacle), None, shape, origin, res)
+        return sid
+
+    def _plan_cost(self, sid, q, base):
+        """compute_plan_cost of each one-column plan (gto/gto_models.py:204-215); 0 without collision avoidance."""
+        if sid is None:
+            return np.zeros(q.shape[0])
+        _, _, val, _ = self._handle.eval_points(sid, q, base, use_obs=True, want=("val",))
+        return val.sum(axis=1)
 
     # ------------------------------------------------------------------ reference signature
     def solve_ik(self, q_0, RT, sdf_cost_obstacle=None, base_position=None):

@@ -27,6 +27,46 @@ def rotZ(rotz: float) -> np.ndarray:
     return np.array([[c, -s, 0, 0], [s, c, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1.0]])
 
 
+def mat2quat(M) -> np.ndarray:
+    """transforms3d.quaternions.mat2quat, which the reference's IK solvers import (gto/ik_solver_quaternion.py:16):
+    (w, x, y, z) of a rotation matrix as the eigenvector of the largest eigenvalue of Bar-Itzhack's symmetric 4x4
+    matrix (robust to a not quite orthonormal input), with w >= 0."""
+    Qxx, Qyx, Qzx, Qxy, Qyy, Qzy, Qxz, Qyz, Qzz = np.asarray(M, dtype=np.float64)[:3, :3].flat
+    K = np.array([[Qxx - Qyy - Qzz, 0, 0, 0],
+                  [Qyx + Qxy, Qyy - Qxx - Qzz, 0, 0],
+                  [Qzx + Qxz, Qzy + Qyz, Qzz - Qxx - Qyy, 0],
+                  [Qyz - Qzy, Qzx - Qxz, Qxy - Qyx, Qxx + Qyy + Qzz]]) / 3.0
+    vals, vecs = np.linalg.eigh(K)  # (the lower triangle)
+    q = vecs[[3, 0, 1, 2], np.argmax(vals)]
+    if q[0] < 0:
+        q *= -1
+    return q
+
+
+def quat2rpy(x, y, z, w) -> np.ndarray:
+    """optas Quaternion(x, y, z, w).getrpy() (optas/spatialmath.py:410-430): roll, pitch, yaw; pitch is +pi/2 whenever
+    |sin(pitch)| >= 1, -1 included (the reference's rule, kept)."""
+    roll = np.arctan2(2.0 * (w * x + y * z), 1.0 - 2.0 * (x * x + y * y))
+    sinp = 2.0 * (w * y - z * x)
+    pitch = np.pi / 2.0 if abs(sinp) >= 1.0 else np.arcsin(sinp)
+    yaw = np.arctan2(2.0 * (w * z + x * y), 1.0 - 2.0 * (y * y + z * z))
+    return np.array([roll, pitch, yaw])
+
+
+def ik_goal_quaternion(RT) -> np.ndarray:
+    """tf_goal of gto/ik_solver_quaternion.py:81-84: x y z qx qy qz qw of a 4x4 goal pose."""
+    RT = np.asarray(RT, dtype=np.float64)
+    w, x, y, z = mat2quat(RT[:3, :3])
+    return np.array([RT[0, 3], RT[1, 3], RT[2, 3], x, y, z, w])
+
+
+def ik_goal_rpy(RT) -> np.ndarray:
+    """tf_goal of gto/ik_solver_rpy.py:84-89: x y z roll pitch yaw of a 4x4 goal pose."""
+    RT = np.asarray(RT, dtype=np.float64)
+    w, x, y, z = mat2quat(RT[:3, :3])
+    return np.concatenate([RT[:3, 3], quat2rpy(x, y, z, w)])
+
+
 def interpolate_waypoints(waypoints, n: int, m: int, mode: str = "cubic") -> np.ndarray:
     """gto/utils.py:63-82: clamped cubic through the waypoints sampled at linspace(0,1,n+2)[1:-1]
     (endpoints excluded).  The planner only ever passes two waypoints (gto/gto_planner.py:155,203),

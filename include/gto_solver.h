@@ -119,7 +119,7 @@ void gto_default_opts(gto_solver_opts* opts);
 /* Library/ABI version (major*1000 + minor): GTO_ABI_VERSION of the header the library was built from.  A binding checks it
  * when it loads the library and refuses another number (grasptrajopt_amd/_capi.py load_library): every change of a
  * signature or of a struct in this header bumps the minor. */
-#define GTO_ABI_VERSION 1008
+#define GTO_ABI_VERSION 1009
 int32_t gto_version(void);
 
 /*
@@ -224,6 +224,34 @@ int gto_share_scene_halves(gto_handle* dst, int32_t dst_id, gto_handle* src, int
 int gto_solve_ik_batch(gto_handle* h, int32_t B, const int32_t* scene_id, const double* q0, const double* goals,
                        const double* base_pos, int32_t max_iter, double* q_out, double* cost_out, int32_t* iters_out,
                        int32_t* status_out);
+
+/*
+ * Inverse kinematics to position + orientation goals of link_ee: the T = 1 problem of gto/ik_solver.py (collision term
+ * 10 * sum(sdf_cost_obstacle[offsets]), URDF joint limits, cap 50) with the pose term of
+ *   GTO_IK_GOAL_POINTS      gto/ik_solver.py:48-54           goals [B][16]: RT of link_ee, exactly gto_solve_ik_batch
+ *   GTO_IK_GOAL_QUATERNION  gto/ik_solver_quaternion.py:50-55 goals [B][7] = x y z qx qy qz qw (tf_goal of :81-84; the
+ *                           quaternion is not normalised):  |p - g[0:3]|^2 + 1 - (quat(link_ee) . g[3:7])^2
+ *   GTO_IK_GOAL_RPY         gto/ik_solver_rpy.py:53-58       goals [B][6] = x y z roll pitch yaw (tf_goal of :84-89):
+ *                           |p - g[0:3]|^2 + |(rpy(link_ee) - g[3:6]) / pi|^2, rpy as optas Quaternion.getrpy (pitch
+ *                           +pi/2 whenever |R20| >= 1; no angle wrapping: the term jumps where an angle crosses +-pi)
+ * p, quat, rpy: link_ee in the robot-base frame.  Arguments, outputs, max_iter = 0 (the objective at the clipped seed)
+ * and the limit of eight optimised joints (GTO_ERR_UNSUPPORTED beyond) as in gto_solve_ik_batch; an unknown goal_kind
+ * fails with GTO_ERR_INVALID_ARG.
+ * Non-finite inputs.  A seed's optimised joints are clipped to the joint limits first (NaN -> lower, +-Inf -> the limit),
+ * so only goals and parameter joints can leave the objective at the seed non-finite.  GTO_IK_GOAL_QUATERNION / RPY:
+ * such an instance ends at once with GTO_STATUS_NUMERICAL, 0 iterations, q_out = the clipped seed and its non-finite
+ * objective in cost_out (the rule of gto_solve_batch), never GTO_STATUS_CONVERGED.  GTO_IK_GOAL_POINTS returns what
+ * gto_solve_ik_batch returns, bit for bit, and that entry point keeps its own ending: its pose term takes a non-finite
+ * goal as an infinite objective, every step is rejected until the damping passes 1e15, and the instance comes back
+ * GTO_STATUS_CONVERGED after 11 iterations at the clipped seed with cost_out = +Inf (measured; check cost_out).
+ * Replaces: IKSolver.setup_optimization + solve_ik of gto/ik_solver_quaternion.py:30-115 and gto/ik_solver_rpy.py:30-121.
+ */
+#define GTO_IK_GOAL_POINTS 0     /* gto/ik_solver.py: goals [B][16], same as gto_solve_ik_batch */
+#define GTO_IK_GOAL_QUATERNION 1 /* gto/ik_solver_quaternion.py: goals [B][7] = x y z qx qy qz qw */
+#define GTO_IK_GOAL_RPY 2        /* gto/ik_solver_rpy.py: goals [B][6] = x y z roll pitch yaw */
+int gto_solve_ik_pose_batch(gto_handle* h, int32_t goal_kind, int32_t B, const int32_t* scene_id, const double* q0,
+                            const double* goals, const double* base_pos, int32_t max_iter, double* q_out, double* cost_out,
+                            int32_t* iters_out, int32_t* status_out);
 
 /*
  * Base placement of a mobile manipulator for B goal sets: where to park the base so that
