@@ -33,6 +33,7 @@ static std::string g_create_error;
 #define GTO_SWEEP_WGS 64   // workgroups of the crew behind an itemized obstacle launch laid out over an estimate (launch_obstacle)
 
 #define GTO_MAX_LANES 8  // lanes of one solve call (streams, list sets, progress words)
+#define GTO_STAGE_SLOTS 8  // host arrays of each direction that one host-pointer entry point stages (Staging)
 #define GTO_NAP_US 50      // the throttle's naps (the host thread of a lane sleep-polls two pinned words); 10-50 us change nothing
 #define GTO_NAP_FEW_US 10  // ... in launches with few instances in flight; 50-200 us change nothing either
 // the deep-gather obstacle variant only up to this many instances in flight (two workgroups per CU: beyond that the
@@ -177,17 +178,15 @@ struct gto_handle {
   Tunables tu;  // the GTO_* knobs, read at gto_create
   int spec_kmax = 1;  // candidates per step the eight-wave step kernel's LDS has room for at this T
   long long* dbg = nullptr;
-  // staging for the host-pointer entry points
   // buffers of the scene that the last gto_set_scene replaced: the next replacement of the same size takes them instead of
   // going through hipMalloc / hipFree (fourteen calls of 0.2-0.3 ms each: most of a small scene's upload time)
   std::vector<std::pair<void*, size_t>> spare;
-  DevBuf in[8], out[8];
+  // staging for the host-pointer entry points (Staging)
+  DevBuf in[GTO_STAGE_SLOTS], out[GTO_STAGE_SLOTS];
   // pinned twins of the staging buffers: host arrays are copied through them, so that the transfers are real DMA at a
   // steady rate (a hipMemcpyAsync from pageable memory stages inside the runtime: 1-6 ms of jitter per call with four
   // lanes copying at once) and never depend on what kind of memory the caller's arrays live in
-  DevBuf pin_in[8], pin_out[8];
-  struct PendingOut { void* host; const void* pin; size_t bytes; };
-  std::vector<PendingOut> pending_out;  // device -> pinned copies in flight; finish_out() delivers them after the sync
+  DevBuf pin_in[GTO_STAGE_SLOTS], pin_out[GTO_STAGE_SLOTS];
   // profiling of the dominant kernel
   bool profiling = false;
   std::vector<hipEvent_t> ev;
@@ -220,13 +219,11 @@ struct gto_handle {
     hipError_t e_ = (call);                                                                          \
     if (e_ != hipSuccess) {                                                                          \
       (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                  \
-      (h)->pending_out.clear(); /* an entry point that fails delivers nothing */                     \
       return GTO_ERR_HIP;                                                                            \
     }                                                                                                \
   } while (0)
 
 static int fail(gto_handle* h, int code, const std::string& msg) {
-  if (h) h->pending_out.clear();
   if (h) h->err = msg;
   else g_create_error = msg;
   return code;
@@ -887,6 +884,20 @@ static int free_scene(gto_handle* h, SceneDev& s) {
   return GTO_OK;
 }
 
+// a scene id that names a set scene (owned or borrowed)
+static bool scene_valid(const gto_handle* h, int32_t id) {
+  return id >= 0 && (size_t)id < h->scenes.size() && h->scenes[id].valid;
+}
+
+static int check_scene_ids_host(gto_handle* h, const int32_t* ids, int B) {
+  for (int b = 0; b < B; ++b)
+    if (!scene_valid(h, ids[b])) return fail(h, GTO_ERR_NO_SCENE, "scene_id refers to a scene that was never set");
+  for (int b = 0; b < B; ++b)
+    if (!h->scenes[ids[b]].r_all)
+      return fail(h, GTO_ERR_NO_SCENE, "scene_id refers to a values-only scene (gto_set_scene_values): it serves gto_plan_cost and gto_eval_points only");
+  return GTO_OK;
+}
+
 int gto_share_scene(gto_handle* dst, int32_t dst_id, gto_handle* src, int32_t src_id) {
   return gto_share_scene_halves(dst, dst_id, src, src_id, 0, 1);
 }
@@ -895,7 +906,7 @@ int gto_share_scene_halves(gto_handle* dst, int32_t dst_id, gto_handle* src, int
   if (!dst || !src) return GTO_ERR_INVALID_ARG;
   if ((all_from != 0 && all_from != 1) || (obs_from != 0 && obs_from != 1)) return fail(dst, GTO_ERR_INVALID_ARG, "gto_share_scene_halves: a half is 0 (c_all) or 1 (c_obs)");
   if (dst_id < 0 || dst_id >= 65536) return fail(dst, GTO_ERR_INVALID_ARG, "scene_id out of range [0,65536)");
-  if (src_id < 0 || (size_t)src_id >= src->scenes.size() || !src->scenes[src_id].valid)
+  if (!scene_valid(src, src_id))
     return fail(dst, GTO_ERR_NO_SCENE, "gto_share_scene: the source scene was never set");
   if (dst->device != src->device) return fail(dst, GTO_ERR_INVALID_ARG, "gto_share_scene: handles live on different devices");
   HIPCHK(dst, hipSetDevice(dst->device));
@@ -1059,7 +1070,7 @@ int gto_set_scene_values(gto_handle* h, int32_t id, const float* c_all, const fl
 
 int gto_drop_scene(gto_handle* h, int32_t id) {
   if (!h) return GTO_ERR_INVALID_ARG;
-  if (id < 0 || (size_t)id >= h->scenes.size() || !h->scenes[id].valid) return fail(h, GTO_ERR_NO_SCENE, "unknown scene");
+  if (!scene_valid(h, id)) return fail(h, GTO_ERR_NO_SCENE, "unknown scene");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   SceneDev& s = h->scenes[id];
@@ -1317,16 +1328,6 @@ static int launch_obstacle(gto_handle* h, hipStream_t st, const BatchPtrs& bp, c
     hipLaunchKernelGGL(obstacle_kernel(h->np, false, true, false), dim3(GTO_SWEEP_WGS), dim3(256), lds, st, jobs_par, njobs_par, items_par, nitems_par, geo.nG, geo.m_nG, GTO_SWEEP_WGS, B,
                        h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes, bpl, sp, o.t_begin, o.nT, o.fixed_mode, geo, n_regular);
   if (o.timed) return prof_end(h, st);
-  return GTO_OK;
-}
-
-static int check_scene_ids_host(gto_handle* h, const int32_t* ids, int B) {
-  for (int b = 0; b < B; ++b)
-    if (ids[b] < 0 || (size_t)ids[b] >= h->scenes.size() || !h->scenes[ids[b]].valid)
-      return fail(h, GTO_ERR_NO_SCENE, "scene_id refers to a scene that was never set");
-  for (int b = 0; b < B; ++b)
-    if (!h->scenes[ids[b]].r_all)
-      return fail(h, GTO_ERR_NO_SCENE, "scene_id refers to a values-only scene (gto_set_scene_values): it serves gto_plan_cost and gto_eval_points only");
   return GTO_OK;
 }
 
@@ -1784,6 +1785,85 @@ static int print_debug_stamps(gto_handle* h, hipStream_t st) {
   return GTO_OK;
 }
 
+// ------------------------------------------------------------------------------------------------- host-pointer staging
+static int ensure_pinned(gto_handle* h, DevBuf& b, size_t bytes) {
+  if (bytes <= b.cap) return GTO_OK;
+  if (b.p) HIPCHK(h, hipHostFree(b.p));
+  b.p = nullptr;
+  b.cap = 0;
+  const size_t want = bytes + bytes / 4 + 256;
+  HIPCHK(h, hipHostMalloc(&b.p, want));
+  b.cap = want;
+  return GTO_OK;
+}
+
+// The transfers of one call of a host-pointer entry point.  Every input and every output takes the next staging slot of
+// its direction (gto_handle::in / out and their pinned twins) in the order it is registered; a null host array takes
+// its slot too, gets a null device pointer and costs nothing.  An output states its size once, when it is registered.
+// finish() queues the device -> pinned copies in registration order, syncs the stream once and copies pinned -> the
+// caller's arrays.  What is to be delivered lives here, not on the handle: a call that returns early delivers nothing.
+class Staging {
+ public:
+  explicit Staging(gto_handle* h) : h_(h) {}
+
+  // n elements from the host, copied to the device on the handle's stream
+  template <class T>
+  int in(const T* src, size_t n, const T** dptr) {
+    *dptr = nullptr;
+    if (n_in_ == GTO_STAGE_SLOTS) return too_many();
+    const int k = n_in_++;
+    if (!src) return GTO_OK;
+    const size_t bytes = n * sizeof(T);
+    int rc = ensure(h_, h_->in[k], bytes);
+    if (rc) return rc;
+    if ((rc = ensure_pinned(h_, h_->pin_in[k], bytes))) return rc;  // free again: every entry point ends with a stream sync
+    memcpy(h_->pin_in[k].p, src, bytes);
+    HIPCHK(h_, hipMemcpyAsync(h_->in[k].p, h_->pin_in[k].p, bytes, hipMemcpyHostToDevice, h_->stream));
+    *dptr = (const T*)h_->in[k].p;
+    return GTO_OK;
+  }
+  // n elements for the host, delivered by finish()
+  template <class T>
+  int out(T* host, size_t n, T** dptr) { return take_out(host, n * sizeof(T), host != nullptr, dptr); }
+  // n elements the kernel writes and nobody fetches
+  template <class T>
+  int scratch(size_t n, T** dptr) { return take_out((T*)nullptr, n * sizeof(T), true, dptr); }
+
+  int finish() {
+    for (int k = 0; k < n_out_; ++k) {
+      if (!host_[k]) continue;
+      int rc = ensure_pinned(h_, h_->pin_out[k], bytes_[k]);
+      if (rc) return rc;
+      HIPCHK(h_, hipMemcpyAsync(h_->pin_out[k].p, h_->out[k].p, bytes_[k], hipMemcpyDeviceToHost, h_->stream));
+    }
+    HIPCHK(h_, hipStreamSynchronize(h_->stream));
+    for (int k = 0; k < n_out_; ++k)
+      if (host_[k]) memcpy(host_[k], h_->pin_out[k].p, bytes_[k]);
+    return GTO_OK;
+  }
+
+ private:
+  template <class T>
+  int take_out(T* host, size_t bytes, bool on_device, T** dptr) {
+    *dptr = nullptr;
+    if (n_out_ == GTO_STAGE_SLOTS) return too_many();
+    const int k = n_out_++;
+    host_[k] = host;
+    bytes_[k] = bytes;
+    if (!on_device) return GTO_OK;
+    const int rc = ensure(h_, h_->out[k], bytes);
+    if (rc) return rc;
+    *dptr = (T*)h_->out[k].p;
+    return GTO_OK;
+  }
+  int too_many() { return fail(h_, GTO_ERR_UNSUPPORTED, "internal: more than eight staged arrays of one direction"); }
+
+  gto_handle* h_;
+  int n_in_ = 0, n_out_ = 0;
+  void* host_[GTO_STAGE_SLOTS] = {};  // the caller's array of output slot k (null: not fetched)
+  size_t bytes_[GTO_STAGE_SLOTS] = {};
+};
+
 extern "C" {
 
 int gto_solve_batch_device(gto_handle* h, int32_t B, int32_t n_max, const int32_t* scene_id, const double* qc,
@@ -1847,64 +1927,22 @@ int gto_solve_batch_device(gto_handle* h, int32_t B, int32_t n_max, const int32_
   return GTO_OK;
 }
 
-// host-pointer staging helpers
-static int ensure_pinned(gto_handle* h, DevBuf& b, size_t bytes) {
-  if (bytes <= b.cap) return GTO_OK;
-  if (b.p) HIPCHK(h, hipHostFree(b.p));
-  b.p = nullptr;
-  b.cap = 0;
-  const size_t want = bytes + bytes / 4 + 256;
-  HIPCHK(h, hipHostMalloc(&b.p, want));
-  b.cap = want;
-  return GTO_OK;
-}
-static int stage_in(gto_handle* h, int slot, const void* src, size_t bytes, const void** dptr) {
-  *dptr = nullptr;
-  if (!src) return GTO_OK;
-  int rc = ensure(h, h->in[slot], bytes);
-  if (rc) return rc;
-  if ((rc = ensure_pinned(h, h->pin_in[slot], bytes))) return rc;  // free again: every entry point ends with a stream sync
-  memcpy(h->pin_in[slot].p, src, bytes);
-  HIPCHK(h, hipMemcpyAsync(h->in[slot].p, h->pin_in[slot].p, bytes, hipMemcpyHostToDevice, h->stream));
-  *dptr = h->in[slot].p;
-  return GTO_OK;
-}
-static int stage_out(gto_handle* h, int slot, const void* host, size_t bytes, void** dptr) {
-  *dptr = nullptr;
-  if (!host) return GTO_OK;
-  int rc = ensure(h, h->out[slot], bytes);
-  if (rc) return rc;
-  *dptr = h->out[slot].p;
-  return GTO_OK;
-}
-static int fetch_out(gto_handle* h, int slot, void* host, size_t bytes) {
-  if (!host) return GTO_OK;
-  int rc = ensure_pinned(h, h->pin_out[slot], bytes);
-  if (rc) return rc;
-  HIPCHK(h, hipMemcpyAsync(h->pin_out[slot].p, h->out[slot].p, bytes, hipMemcpyDeviceToHost, h->stream));
-  h->pending_out.push_back({host, h->pin_out[slot].p, bytes});
-  return GTO_OK;
-}
-// after the stream sync that follows the fetch_out calls of an entry point: pinned -> the caller's arrays
-static int sync_and_finish_out(gto_handle* h) {
-  const hipError_t e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) {
-    h->pending_out.clear();
-    HIPCHK(h, e);
-  }
-  for (const auto& po : h->pending_out) memcpy(po.host, po.pin, po.bytes);
-  h->pending_out.clear();
-  return GTO_OK;
+// k_ik_solve for a goal kind (GTO_IK_GOAL_* count from 0); the first reference to a variant decides where the code object
+// places it, and the table keeps the order they have always had
+using IkKernel = decltype(&k_ik_solve<GTO_IK_GOAL_POINTS>);
+static IkKernel ik_kernel(int kind) {
+  static const IkKernel k[3] = {k_ik_solve<GTO_IK_GOAL_POINTS>, k_ik_solve<GTO_IK_GOAL_QUATERNION>, k_ik_solve<GTO_IK_GOAL_RPY>};
+  return k[kind];
 }
 
-int gto_solve_ik_batch(gto_handle* h, int32_t B, const int32_t* scene_id, const double* q0, const double* goals,
-                       const double* base_pos, int32_t max_iter, double* q_out, double* cost_out, int32_t* iters_out,
-                       int32_t* status_out) {
-  if (!h) return GTO_ERR_INVALID_ARG;
+// gto_solve_ik_batch and gto_solve_ik_pose_batch: goals of one kind, gw doubles each; `name` speaks in the messages
+static int ik_batch(gto_handle* h, const char* name, int kind, size_t gw, int32_t B, const int32_t* scene_id,
+                    const double* q0, const double* goals, const double* base_pos, int32_t max_iter, double* q_out,
+                    double* cost_out, int32_t* iters_out, int32_t* status_out) {
   if (B < 0 || max_iter < 0) return fail(h, GTO_ERR_INVALID_ARG, "B and max_iter must be >= 0");
   if (B == 0) return GTO_OK;
   if (!q0 || !goals || !q_out) return fail(h, GTO_ERR_INVALID_ARG, "null input array");
-  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, "gto_solve_ik_batch handles up to eight optimised joints");
+  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, std::string(name) + " handles up to eight optimised joints");
   int rc;
   if (scene_id && (rc = check_scene_ids_host(h, scene_id, B))) return rc;
   HIPCHK(h, hipSetDevice(h->device));
@@ -1914,31 +1952,37 @@ int gto_solve_ik_batch(gto_handle* h, int32_t B, const int32_t* scene_id, const 
     zeros.assign((size_t)B * 3, 0.0);
     base_pos = zeros.data();
   }
-  const void *d_sid = nullptr, *d_q0, *d_goals, *d_base = nullptr;
-  void *d_q, *d_cost, *d_it, *d_stat;
-  if (scene_id && (rc = stage_in(h, 0, scene_id, B * sizeof(int32_t), &d_sid))) return rc;
-  if ((rc = stage_in(h, 1, q0, B * ndof * sizeof(double), &d_q0))) return rc;
-  if ((rc = stage_in(h, 2, goals, (size_t)B * 16 * sizeof(double), &d_goals))) return rc;
-  if (scene_id && (rc = stage_in(h, 5, base_pos, (size_t)B * 3 * sizeof(double), &d_base))) return rc;
-  if ((rc = stage_out(h, 0, q_out, B * ndof * sizeof(double), &d_q))) return rc;
-  if ((rc = stage_out(h, 2, cost_out, B * sizeof(double), &d_cost))) return rc;
-  if ((rc = stage_out(h, 3, iters_out, B * sizeof(int32_t), &d_it))) return rc;
-  if ((rc = stage_out(h, 4, status_out, B * sizeof(int32_t), &d_stat))) return rc;
+  Staging io(h);
+  const int32_t* d_sid;
+  const double *d_q0, *d_goals, *d_base;
+  double *d_q, *d_cost;
+  int32_t *d_it, *d_stat;
+  if ((rc = io.in(scene_id, B, &d_sid))) return rc;
+  if ((rc = io.in(q0, B * ndof, &d_q0))) return rc;
+  if ((rc = io.in(goals, B * gw, &d_goals))) return rc;
+  if ((rc = io.in(scene_id ? base_pos : nullptr, (size_t)B * 3, &d_base))) return rc;  // (no scene: no base)
+  if ((rc = io.out(q_out, B * ndof, &d_q))) return rc;
+  if ((rc = io.out(cost_out, B, &d_cost))) return rc;
+  if ((rc = io.out(iters_out, B, &d_it))) return rc;
+  if ((rc = io.out(status_out, B, &d_stat))) return rc;
   SolveParams sp = make_params(h, 1, false);
   sp.max_iter = max_iter;
   const size_t lds = (size_t)ik_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt) * sizeof(double);
   if (lds > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the IK kernel's LDS");
-  HIPCHK(h, raise_dynamic_lds((const void*)k_ik_solve<GTO_IK_GOAL_POINTS>, lds));
-  hipLaunchKernelGGL(k_ik_solve<GTO_IK_GOAL_POINTS>, dim3(B), dim3(256), lds, h->stream, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks,
-                     h->d_scenes, (const int32_t*)d_sid, (const double*)d_q0, (const double*)d_goals, (const double*)d_base, sp,
-                     B, (double*)d_q, (double*)d_cost, (int32_t*)d_it, (int32_t*)d_stat);
+  const IkKernel kern = ik_kernel(kind);
+  HIPCHK(h, raise_dynamic_lds((const void*)kern, lds));
+  hipLaunchKernelGGL(kern, dim3(B), dim3(256), lds, h->stream, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes,
+                     d_sid, d_q0, d_goals, d_base, sp, B, d_q, d_cost, d_it, d_stat);
   HIPCHK(h, hipGetLastError());
-  if ((rc = fetch_out(h, 0, q_out, B * ndof * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 2, cost_out, B * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 3, iters_out, B * sizeof(int32_t)))) return rc;
-  if ((rc = fetch_out(h, 4, status_out, B * sizeof(int32_t)))) return rc;
-  if ((rc = sync_and_finish_out(h))) return rc;
-  return GTO_OK;
+  return io.finish();
+}
+
+int gto_solve_ik_batch(gto_handle* h, int32_t B, const int32_t* scene_id, const double* q0, const double* goals,
+                       const double* base_pos, int32_t max_iter, double* q_out, double* cost_out, int32_t* iters_out,
+                       int32_t* status_out) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  return ik_batch(h, "gto_solve_ik_batch", GTO_IK_GOAL_POINTS, 16, B, scene_id, q0, goals, base_pos, max_iter, q_out,
+                  cost_out, iters_out, status_out);
 }
 
 int gto_solve_ik_pose_batch(gto_handle* h, int32_t goal_kind, int32_t B, const int32_t* scene_id, const double* q0,
@@ -1949,51 +1993,56 @@ int gto_solve_ik_pose_batch(gto_handle* h, int32_t goal_kind, int32_t B, const i
     return fail(h, GTO_ERR_INVALID_ARG, "unknown IK goal kind");
   if (goal_kind == GTO_IK_GOAL_POINTS)  // the same call, launch and results
     return gto_solve_ik_batch(h, B, scene_id, q0, goals, base_pos, max_iter, q_out, cost_out, iters_out, status_out);
-  if (B < 0 || max_iter < 0) return fail(h, GTO_ERR_INVALID_ARG, "B and max_iter must be >= 0");
+  return ik_batch(h, "gto_solve_ik_pose_batch", goal_kind, goal_kind == GTO_IK_GOAL_QUATERNION ? 7 : 6, B, scene_id, q0,
+                  goals, base_pos, max_iter, q_out, cost_out, iters_out, status_out);
+}
+
+// gto_solve_base_batch and gto_eval_base_objective after their own B check; `null_input`: one of the arrays the entry point
+// needs is null.  A solve starts from qc.  An evaluation passes the point (y0, q0) with max_iter 0 and no y_out / q_out:
+// qc is the first goal's configuration of every set in q0, and the point k_base_solve writes back stays on the device.
+static int base_batch(gto_handle* h, const char* name, int32_t B, int32_t n_max, const int32_t* n_goals, bool null_input,
+                      const double* qc, const double* goals, double effort_weight, int32_t max_iter, const double* y0,
+                      const double* q0, double* y_out, double* q_out, double* cost_out, int32_t* iters_out,
+                      int32_t* status_out) {
+  if (n_max < 1 || n_max > GTO_MAX_BASE_GOALS) return fail(h, GTO_ERR_UNSUPPORTED, "n_max must be in [1, 32]");
+  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, std::string(name) + " handles up to eight optimised joints");
   if (B == 0) return GTO_OK;
-  if (!q0 || !goals || !q_out) return fail(h, GTO_ERR_INVALID_ARG, "null input array");
-  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, "gto_solve_ik_pose_batch handles up to eight optimised joints");
-  int rc;
-  if (scene_id && (rc = check_scene_ids_host(h, scene_id, B))) return rc;
+  if (null_input) return fail(h, GTO_ERR_INVALID_ARG, "null input array");
+  for (int b = 0; b < B; ++b)
+    if (n_goals[b] < 1 || n_goals[b] > n_max) return fail(h, GTO_ERR_INVALID_ARG, "n_goals[b] must be in [1, n_max]");
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t ndof = h->rb.ndof, gw = goal_kind == GTO_IK_GOAL_QUATERNION ? 7 : 6;
-  std::vector<double> zeros;
-  if (scene_id && !base_pos) {
-    zeros.assign((size_t)B * 3, 0.0);
-    base_pos = zeros.data();
+  const size_t ndof = h->rb.ndof, nB = B;
+  std::vector<double> qc_eval;
+  if (q0) {
+    qc_eval.resize(nB * ndof);
+    for (size_t b = 0; b < nB; ++b) std::copy(q0 + b * n_max * ndof, q0 + b * n_max * ndof + ndof, qc_eval.begin() + b * ndof);
+    qc = qc_eval.data();
   }
-  const void *d_sid = nullptr, *d_q0, *d_goals, *d_base = nullptr;
-  void *d_q, *d_cost, *d_it, *d_stat;
-  if (scene_id && (rc = stage_in(h, 0, scene_id, B * sizeof(int32_t), &d_sid))) return rc;
-  if ((rc = stage_in(h, 1, q0, B * ndof * sizeof(double), &d_q0))) return rc;
-  if ((rc = stage_in(h, 2, goals, (size_t)B * gw * sizeof(double), &d_goals))) return rc;
-  if (scene_id && (rc = stage_in(h, 5, base_pos, (size_t)B * 3 * sizeof(double), &d_base))) return rc;
-  if ((rc = stage_out(h, 0, q_out, B * ndof * sizeof(double), &d_q))) return rc;
-  if ((rc = stage_out(h, 2, cost_out, B * sizeof(double), &d_cost))) return rc;
-  if ((rc = stage_out(h, 3, iters_out, B * sizeof(int32_t), &d_it))) return rc;
-  if ((rc = stage_out(h, 4, status_out, B * sizeof(int32_t), &d_stat))) return rc;
+  Staging io(h);
+  const double *d_qc, *d_goals, *d_y0, *d_q0;
+  const int32_t* d_ng;
+  double *d_q, *d_y, *d_cost;
+  int32_t *d_it, *d_stat;
+  int rc;
+  if ((rc = io.in(qc, nB * ndof, &d_qc))) return rc;
+  if ((rc = io.in(goals, nB * n_max * 16, &d_goals))) return rc;
+  if ((rc = io.in(n_goals, nB, &d_ng))) return rc;
+  if ((rc = io.in(y0, nB * 3, &d_y0))) return rc;
+  if ((rc = io.in(q0, nB * n_max * ndof, &d_q0))) return rc;
+  if ((rc = q_out ? io.out(q_out, nB * n_max * ndof, &d_q) : io.scratch(nB * n_max * ndof, &d_q))) return rc;
+  if ((rc = y_out ? io.out(y_out, nB * 3, &d_y) : io.scratch(nB * 3, &d_y))) return rc;
+  if ((rc = io.out(cost_out, nB, &d_cost))) return rc;
+  if ((rc = io.out(iters_out, nB, &d_it))) return rc;
+  if ((rc = io.out(status_out, nB, &d_stat))) return rc;
   SolveParams sp = make_params(h, 1, false);
   sp.max_iter = max_iter;
-  const size_t lds = (size_t)ik_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt) * sizeof(double);
-  if (lds > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the IK kernel's LDS");
-  const void* kern = goal_kind == GTO_IK_GOAL_QUATERNION ? (const void*)k_ik_solve<GTO_IK_GOAL_QUATERNION>
-                                                         : (const void*)k_ik_solve<GTO_IK_GOAL_RPY>;
-  HIPCHK(h, raise_dynamic_lds(kern, lds));
-  if (goal_kind == GTO_IK_GOAL_QUATERNION)
-    hipLaunchKernelGGL(k_ik_solve<GTO_IK_GOAL_QUATERNION>, dim3(B), dim3(256), lds, h->stream, h->d_rb, h->d_px, h->d_py, h->d_pz,
-                       h->d_chunks, h->d_scenes, (const int32_t*)d_sid, (const double*)d_q0, (const double*)d_goals,
-                       (const double*)d_base, sp, B, (double*)d_q, (double*)d_cost, (int32_t*)d_it, (int32_t*)d_stat);
-  else
-    hipLaunchKernelGGL(k_ik_solve<GTO_IK_GOAL_RPY>, dim3(B), dim3(256), lds, h->stream, h->d_rb, h->d_px, h->d_py, h->d_pz,
-                       h->d_chunks, h->d_scenes, (const int32_t*)d_sid, (const double*)d_q0, (const double*)d_goals,
-                       (const double*)d_base, sp, B, (double*)d_q, (double*)d_cost, (int32_t*)d_it, (int32_t*)d_stat);
+  const size_t lds = (size_t)base_lds_doubles(n_max) * sizeof(double);
+  if (lds > 160 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "goal set too large for the base kernel's LDS");
+  HIPCHK(h, raise_dynamic_lds((const void*)k_base_solve, lds));
+  hipLaunchKernelGGL(k_base_solve, dim3(B), dim3(256), lds, h->stream, h->d_rb, d_qc, d_goals, d_ng, sp, effort_weight, n_max,
+                     d_y, d_q, d_cost, d_it, d_stat, d_y0, d_q0);
   HIPCHK(h, hipGetLastError());
-  if ((rc = fetch_out(h, 0, q_out, B * ndof * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 2, cost_out, B * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 3, iters_out, B * sizeof(int32_t)))) return rc;
-  if ((rc = fetch_out(h, 4, status_out, B * sizeof(int32_t)))) return rc;
-  if ((rc = sync_and_finish_out(h))) return rc;
-  return GTO_OK;
+  return io.finish();
 }
 
 int gto_solve_base_batch(gto_handle* h, int32_t B, int32_t n_max, const int32_t* n_goals, const double* qc,
@@ -2001,41 +2050,8 @@ int gto_solve_base_batch(gto_handle* h, int32_t B, int32_t n_max, const int32_t*
                          double* cost_out, int32_t* iters_out, int32_t* status_out) {
   if (!h) return GTO_ERR_INVALID_ARG;
   if (B < 0 || max_iter < 0) return fail(h, GTO_ERR_INVALID_ARG, "B and max_iter must be >= 0");
-  if (n_max < 1 || n_max > GTO_MAX_BASE_GOALS) return fail(h, GTO_ERR_UNSUPPORTED, "n_max must be in [1, 32]");
-  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, "gto_solve_base_batch handles up to eight optimised joints");
-  if (B == 0) return GTO_OK;
-  if (!n_goals || !qc || !goals || !y_out || !q_out) return fail(h, GTO_ERR_INVALID_ARG, "null input array");
-  for (int b = 0; b < B; ++b)
-    if (n_goals[b] < 1 || n_goals[b] > n_max) return fail(h, GTO_ERR_INVALID_ARG, "n_goals[b] must be in [1, n_max]");
-  HIPCHK(h, hipSetDevice(h->device));
-  const size_t ndof = h->rb.ndof;
-  int rc;
-  const void *d_qc, *d_goals, *d_ng;
-  void *d_q, *d_y, *d_cost, *d_it, *d_stat;
-  if ((rc = stage_in(h, 1, qc, B * ndof * sizeof(double), &d_qc))) return rc;
-  if ((rc = stage_in(h, 2, goals, (size_t)B * n_max * 16 * sizeof(double), &d_goals))) return rc;
-  if ((rc = stage_in(h, 3, n_goals, B * sizeof(int32_t), &d_ng))) return rc;
-  if ((rc = stage_out(h, 0, q_out, (size_t)B * n_max * ndof * sizeof(double), &d_q))) return rc;
-  if ((rc = stage_out(h, 1, y_out, (size_t)B * 3 * sizeof(double), &d_y))) return rc;
-  if ((rc = stage_out(h, 2, cost_out, B * sizeof(double), &d_cost))) return rc;
-  if ((rc = stage_out(h, 3, iters_out, B * sizeof(int32_t), &d_it))) return rc;
-  if ((rc = stage_out(h, 4, status_out, B * sizeof(int32_t), &d_stat))) return rc;
-  SolveParams sp = make_params(h, 1, false);
-  sp.max_iter = max_iter;
-  const size_t lds = (size_t)base_lds_doubles(n_max) * sizeof(double);
-  if (lds > 160 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "goal set too large for the base kernel's LDS");
-  HIPCHK(h, raise_dynamic_lds((const void*)k_base_solve, lds));
-  hipLaunchKernelGGL(k_base_solve, dim3(B), dim3(256), lds, h->stream, h->d_rb, (const double*)d_qc, (const double*)d_goals,
-                     (const int32_t*)d_ng, sp, effort_weight, n_max, (double*)d_y, (double*)d_q, (double*)d_cost,
-                     (int32_t*)d_it, (int32_t*)d_stat, (const double*)nullptr, (const double*)nullptr);
-  HIPCHK(h, hipGetLastError());
-  if ((rc = fetch_out(h, 0, q_out, (size_t)B * n_max * ndof * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 1, y_out, (size_t)B * 3 * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 2, cost_out, B * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 3, iters_out, B * sizeof(int32_t)))) return rc;
-  if ((rc = fetch_out(h, 4, status_out, B * sizeof(int32_t)))) return rc;
-  if ((rc = sync_and_finish_out(h))) return rc;
-  return GTO_OK;
+  return base_batch(h, "gto_solve_base_batch", B, n_max, n_goals, !n_goals || !qc || !goals || !y_out || !q_out, qc, goals,
+                    effort_weight, max_iter, nullptr, nullptr, y_out, q_out, cost_out, iters_out, status_out);
 }
 
 #ifdef GTO_DEBUG_BASE_TIMING
@@ -2051,42 +2067,8 @@ int gto_eval_base_objective(gto_handle* h, int32_t B, int32_t n_max, const int32
                             const double* q, const double* goals, double effort_weight, double* cost_out) {
   if (!h) return GTO_ERR_INVALID_ARG;
   if (B < 0) return fail(h, GTO_ERR_INVALID_ARG, "B must be >= 0");
-  if (n_max < 1 || n_max > GTO_MAX_BASE_GOALS) return fail(h, GTO_ERR_UNSUPPORTED, "n_max must be in [1, 32]");
-  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, "gto_eval_base_objective handles up to eight optimised joints");
-  if (B == 0) return GTO_OK;
-  if (!n_goals || !y || !q || !goals || !cost_out) return fail(h, GTO_ERR_INVALID_ARG, "null input array");
-  for (int b = 0; b < B; ++b)
-    if (n_goals[b] < 1 || n_goals[b] > n_max) return fail(h, GTO_ERR_INVALID_ARG, "n_goals[b] must be in [1, n_max]");
-  HIPCHK(h, hipSetDevice(h->device));
-  const size_t ndof = h->rb.ndof;
-  int rc;
-  // the parameter joints come from the first goal's configuration of every set
-  std::vector<double> qc((size_t)B * ndof);
-  for (int b = 0; b < B; ++b) std::copy(q + (size_t)b * n_max * ndof, q + (size_t)b * n_max * ndof + ndof, qc.begin() + (size_t)b * ndof);
-  const void *d_qc, *d_goals, *d_ng, *d_y0, *d_q0;
-  void *d_q, *d_y, *d_cost;
-  if ((rc = stage_in(h, 1, qc.data(), B * ndof * sizeof(double), &d_qc))) return rc;
-  if ((rc = stage_in(h, 2, goals, (size_t)B * n_max * 16 * sizeof(double), &d_goals))) return rc;
-  if ((rc = stage_in(h, 3, n_goals, B * sizeof(int32_t), &d_ng))) return rc;
-  if ((rc = stage_in(h, 4, y, (size_t)B * 3 * sizeof(double), &d_y0))) return rc;
-  if ((rc = stage_in(h, 6, q, (size_t)B * n_max * ndof * sizeof(double), &d_q0))) return rc;
-  if ((rc = ensure(h, h->out[0], (size_t)B * n_max * ndof * sizeof(double)))) return rc;
-  if ((rc = ensure(h, h->out[1], (size_t)B * 3 * sizeof(double)))) return rc;
-  d_q = h->out[0].p;
-  d_y = h->out[1].p;
-  if ((rc = stage_out(h, 2, cost_out, B * sizeof(double), &d_cost))) return rc;
-  SolveParams sp = make_params(h, 1, false);
-  sp.max_iter = 0;
-  const size_t lds = (size_t)base_lds_doubles(n_max) * sizeof(double);
-  if (lds > 160 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "goal set too large for the base kernel's LDS");
-  HIPCHK(h, raise_dynamic_lds((const void*)k_base_solve, lds));
-  hipLaunchKernelGGL(k_base_solve, dim3(B), dim3(256), lds, h->stream, h->d_rb, (const double*)d_qc, (const double*)d_goals,
-                     (const int32_t*)d_ng, sp, effort_weight, n_max, (double*)d_y, (double*)d_q, (double*)d_cost,
-                     (int32_t*)nullptr, (int32_t*)nullptr, (const double*)d_y0, (const double*)d_q0);
-  HIPCHK(h, hipGetLastError());
-  if ((rc = fetch_out(h, 2, cost_out, B * sizeof(double)))) return rc;
-  if ((rc = sync_and_finish_out(h))) return rc;
-  return GTO_OK;
+  return base_batch(h, "gto_eval_base_objective", B, n_max, n_goals, !n_goals || !y || !q || !goals || !cost_out, nullptr,
+                    goals, effort_weight, 0, y, q, nullptr, nullptr, cost_out, nullptr, nullptr);
 }
 
 int gto_solve_batch(gto_handle* h, int32_t B, int32_t n_max, const int32_t* scene_id, const double* qc, const double* goals,
@@ -2102,53 +2084,52 @@ int gto_solve_batch(gto_handle* h, int32_t B, int32_t n_max, const int32_t* scen
     if (n_goals[b] < 1 || n_goals[b] > n_max) return fail(h, GTO_ERR_INVALID_ARG, "n_goals[b] must be in [1, n_max]");
   HIPCHK(h, hipSetDevice(h->device));
   const size_t ndof = h->rb.ndof, T = h->opts.T;
-  const void *d_sid, *d_qc, *d_goals, *d_ng, *d_so, *d_base, *d_Q0;
-  void *d_Q, *d_dQ, *d_cost, *d_it, *d_stat;
-  if ((rc = stage_in(h, 0, scene_id, B * sizeof(int32_t), &d_sid))) return rc;
-  if ((rc = stage_in(h, 1, qc, B * ndof * sizeof(double), &d_qc))) return rc;
-  if ((rc = stage_in(h, 2, goals, (size_t)B * n_max * 16 * sizeof(double), &d_goals))) return rc;
-  if ((rc = stage_in(h, 3, n_goals, B * sizeof(int32_t), &d_ng))) return rc;
-  if ((rc = stage_in(h, 4, standoff, (size_t)B * 16 * sizeof(double), &d_so))) return rc;
-  if ((rc = stage_in(h, 5, base_pos, (size_t)B * 3 * sizeof(double), &d_base))) return rc;
-  if ((rc = stage_in(h, 6, Q0, B * ndof * T * sizeof(double), &d_Q0))) return rc;
-  if ((rc = stage_out(h, 0, Q_out, B * ndof * T * sizeof(double), &d_Q))) return rc;
-  if ((rc = stage_out(h, 1, dQ_out, B * ndof * (T - 1) * sizeof(double), &d_dQ))) return rc;
-  if ((rc = stage_out(h, 2, cost_out, B * sizeof(double), &d_cost))) return rc;
-  if ((rc = stage_out(h, 3, iters_out, B * sizeof(int32_t), &d_it))) return rc;
-  if ((rc = stage_out(h, 4, status_out, B * sizeof(int32_t), &d_stat))) return rc;
-  rc = gto_solve_batch_device(h, B, n_max, (const int32_t*)d_sid, (const double*)d_qc, (const double*)d_goals,
-                              (const int32_t*)d_ng, (const double*)d_so, (const double*)d_base, (const double*)d_Q0,
-                              (double*)d_Q, (double*)d_dQ, (double*)d_cost, (int32_t*)d_it, (int32_t*)d_stat, nullptr);
+  Staging io(h);
+  const int32_t *d_sid, *d_ng;
+  const double *d_qc, *d_goals, *d_so, *d_base, *d_Q0;
+  double *d_Q, *d_dQ, *d_cost;
+  int32_t *d_it, *d_stat;
+  if ((rc = io.in(scene_id, B, &d_sid))) return rc;
+  if ((rc = io.in(qc, B * ndof, &d_qc))) return rc;
+  if ((rc = io.in(goals, (size_t)B * n_max * 16, &d_goals))) return rc;
+  if ((rc = io.in(n_goals, B, &d_ng))) return rc;
+  if ((rc = io.in(standoff, (size_t)B * 16, &d_so))) return rc;
+  if ((rc = io.in(base_pos, (size_t)B * 3, &d_base))) return rc;
+  if ((rc = io.in(Q0, B * ndof * T, &d_Q0))) return rc;
+  if ((rc = io.out(Q_out, B * ndof * T, &d_Q))) return rc;
+  if ((rc = io.out(dQ_out, B * ndof * (T - 1), &d_dQ))) return rc;
+  if ((rc = io.out(cost_out, B, &d_cost))) return rc;
+  if ((rc = io.out(iters_out, B, &d_it))) return rc;
+  if ((rc = io.out(status_out, B, &d_stat))) return rc;
+  rc = gto_solve_batch_device(h, B, n_max, d_sid, d_qc, d_goals, d_ng, d_so, d_base, d_Q0, d_Q, d_dQ, d_cost, d_it, d_stat,
+                              nullptr);
   if (rc) return rc;
-  if ((rc = fetch_out(h, 0, Q_out, B * ndof * T * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 1, dQ_out, B * ndof * (T - 1) * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 2, cost_out, B * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 3, iters_out, B * sizeof(int32_t)))) return rc;
-  if ((rc = fetch_out(h, 4, status_out, B * sizeof(int32_t)))) return rc;
-  if ((rc = sync_and_finish_out(h))) return rc;
-  return GTO_OK;
+  return io.finish();
 }
 
 // -------------------------------------------------------------------------------------------------
+// k_eval_kin over nq configurations on the device: the frames (frames_out) or the links' visual transforms (vis_out)
+static int launch_eval_kin(gto_handle* h, int nq, const double* dq, double* frames_out, double* vis_out) {
+  const size_t lds = sizeof(double) * eval_kin_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
+  HIPCHK(h, raise_dynamic_lds((const void*)k_eval_kin, lds));
+  hipLaunchKernelGGL(k_eval_kin, dim3((nq + GTO_EVAL_TG - 1) / GTO_EVAL_TG), dim3(256), lds, h->stream, h->d_rb, nq, dq,
+                     frames_out, vis_out);
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
+}
+
 int gto_eval_fk(gto_handle* h, int32_t nq, const double* q, double* frames_out) {
   if (!h || !q || !frames_out || nq < 0) return h ? fail(h, GTO_ERR_INVALID_ARG, "bad argument") : GTO_ERR_INVALID_ARG;
   if (nq == 0) return GTO_OK;
   HIPCHK(h, hipSetDevice(h->device));
-  const void* dq;
-  void* dout;
+  Staging io(h);
+  const double* dq;
+  double* dout;
   int rc;
-  size_t ob = (size_t)nq * h->rb.n_frames * 16 * sizeof(double);
-  if ((rc = stage_in(h, 0, q, (size_t)nq * h->rb.ndof * sizeof(double), &dq))) return rc;
-  if ((rc = stage_out(h, 0, frames_out, ob, &dout))) return rc;
-  {
-    const size_t lds = sizeof(double) * eval_kin_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
-    HIPCHK(h, raise_dynamic_lds((const void*)k_eval_kin, lds));
-    hipLaunchKernelGGL(k_eval_kin, dim3((nq + GTO_EVAL_TG - 1) / GTO_EVAL_TG), dim3(256), lds, h->stream, h->d_rb, nq, (const double*)dq,
-                       (double*)dout, (double*)nullptr);
-  }
-  if ((rc = fetch_out(h, 0, frames_out, ob))) return rc;
-  if ((rc = sync_and_finish_out(h))) return rc;
-  return GTO_OK;
+  if ((rc = io.in(q, (size_t)nq * h->rb.ndof, &dq))) return rc;
+  if ((rc = io.out(frames_out, (size_t)nq * h->rb.n_frames * 16, &dout))) return rc;
+  if ((rc = launch_eval_kin(h, nq, dq, dout, nullptr))) return rc;
+  return io.finish();
 }
 
 int gto_eval_points(gto_handle* h, int32_t scene_id, int32_t nq, const double* q, const double* base_pos, int32_t use_obs,
@@ -2156,61 +2137,49 @@ int gto_eval_points(gto_handle* h, int32_t scene_id, int32_t nq, const double* q
   if (!h || !q || !base_pos || nq < 0) return h ? fail(h, GTO_ERR_INVALID_ARG, "bad argument") : GTO_ERR_INVALID_ARG;
   if (nq == 0) return GTO_OK;
   const bool want_field = offset_out || value_out || grad_out;
-  if (want_field && (scene_id < 0 || (size_t)scene_id >= h->scenes.size() || !h->scenes[scene_id].valid))
-    return fail(h, GTO_ERR_NO_SCENE, "unknown scene");
+  if (want_field && !scene_valid(h, scene_id)) return fail(h, GTO_ERR_NO_SCENE, "unknown scene");
   HIPCHK(h, hipSetDevice(h->device));
   const int P = h->rb.n_points, L = h->rb.n_links;
-  const void *dq, *dbase;
-  void *dx, *doff, *dval, *dgrad;
+  Staging io(h);
+  const double *dq, *dbase;
+  double *dx, *dval, *dgrad;
+  int32_t* doff;
   int rc;
-  if ((rc = stage_in(h, 0, q, (size_t)nq * h->rb.ndof * sizeof(double), &dq))) return rc;
-  if ((rc = stage_in(h, 1, base_pos, (size_t)nq * 3 * sizeof(double), &dbase))) return rc;
+  if ((rc = io.in(q, (size_t)nq * h->rb.ndof, &dq))) return rc;
+  if ((rc = io.in(base_pos, (size_t)nq * 3, &dbase))) return rc;
   if ((rc = ensure(h, h->vis, (size_t)nq * L * 12 * sizeof(double)))) return rc;
-  if ((rc = stage_out(h, 0, xyz_out, (size_t)nq * P * 3 * sizeof(double), &dx))) return rc;
-  if ((rc = stage_out(h, 1, offset_out, (size_t)nq * P * sizeof(int32_t), &doff))) return rc;
-  if ((rc = stage_out(h, 2, value_out, (size_t)nq * P * sizeof(double), &dval))) return rc;
-  if ((rc = stage_out(h, 3, grad_out, (size_t)nq * P * 3 * sizeof(double), &dgrad))) return rc;
-  {
-    const size_t lds = sizeof(double) * eval_kin_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
-    HIPCHK(h, raise_dynamic_lds((const void*)k_eval_kin, lds));
-    hipLaunchKernelGGL(k_eval_kin, dim3((nq + GTO_EVAL_TG - 1) / GTO_EVAL_TG), dim3(256), lds, h->stream, h->d_rb, nq, (const double*)dq,
-                       (double*)nullptr, (double*)h->vis.p);
-  }
+  if ((rc = io.out(xyz_out, (size_t)nq * P * 3, &dx))) return rc;
+  if ((rc = io.out(offset_out, (size_t)nq * P, &doff))) return rc;
+  if ((rc = io.out(value_out, (size_t)nq * P, &dval))) return rc;
+  if ((rc = io.out(grad_out, (size_t)nq * P * 3, &dgrad))) return rc;
+  if ((rc = launch_eval_kin(h, nq, dq, nullptr, (double*)h->vis.p))) return rc;
   hipLaunchKernelGGL(k_eval_points, dim3((P + 255) / 256, nq), dim3(256), 0, h->stream, h->d_rb, h->d_px, h->d_py, h->d_pz,
                      h->d_plink, h->d_perm, want_field ? h->d_scenes + scene_id : nullptr, nq, (const double*)h->vis.p,
-                     (const double*)dbase, use_obs, (double*)dx, (int32_t*)doff, (double*)dval, (double*)dgrad);
-  if ((rc = fetch_out(h, 0, xyz_out, (size_t)nq * P * 3 * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 1, offset_out, (size_t)nq * P * sizeof(int32_t)))) return rc;
-  if ((rc = fetch_out(h, 2, value_out, (size_t)nq * P * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 3, grad_out, (size_t)nq * P * 3 * sizeof(double)))) return rc;
-  if ((rc = sync_and_finish_out(h))) return rc;
-  return GTO_OK;
+                     dbase, use_obs, dx, doff, dval, dgrad);
+  HIPCHK(h, hipGetLastError());
+  return io.finish();
 }
 
 int gto_eval_points_hessian(gto_handle* h, int32_t scene_id, int32_t nq, const double* q, const double* base_pos, int32_t use_obs,
                             double* hess_out) {
   if (!h || !q || !base_pos || !hess_out || nq < 0) return h ? fail(h, GTO_ERR_INVALID_ARG, "bad argument") : GTO_ERR_INVALID_ARG;
   if (nq == 0) return GTO_OK;
-  if (scene_id < 0 || (size_t)scene_id >= h->scenes.size() || !h->scenes[scene_id].valid) return fail(h, GTO_ERR_NO_SCENE, "unknown scene");
+  if (!scene_valid(h, scene_id)) return fail(h, GTO_ERR_NO_SCENE, "unknown scene");
   HIPCHK(h, hipSetDevice(h->device));
   const int P = h->rb.n_points, L = h->rb.n_links;
-  const void *dq, *dbase;
-  void* dh;
+  Staging io(h);
+  const double *dq, *dbase;
+  double* dh;
   int rc;
-  if ((rc = stage_in(h, 0, q, (size_t)nq * h->rb.ndof * sizeof(double), &dq))) return rc;
-  if ((rc = stage_in(h, 1, base_pos, (size_t)nq * 3 * sizeof(double), &dbase))) return rc;
+  if ((rc = io.in(q, (size_t)nq * h->rb.ndof, &dq))) return rc;
+  if ((rc = io.in(base_pos, (size_t)nq * 3, &dbase))) return rc;
   if ((rc = ensure(h, h->vis, (size_t)nq * L * 12 * sizeof(double)))) return rc;
-  if ((rc = stage_out(h, 0, hess_out, (size_t)nq * P * 9 * sizeof(double), &dh))) return rc;
-  {
-    const size_t lds = sizeof(double) * eval_kin_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
-    HIPCHK(h, raise_dynamic_lds((const void*)k_eval_kin, lds));
-    hipLaunchKernelGGL(k_eval_kin, dim3((nq + GTO_EVAL_TG - 1) / GTO_EVAL_TG), dim3(256), lds, h->stream, h->d_rb, nq, (const double*)dq,
-                       (double*)nullptr, (double*)h->vis.p);
-  }
+  if ((rc = io.out(hess_out, (size_t)nq * P * 9, &dh))) return rc;
+  if ((rc = launch_eval_kin(h, nq, dq, nullptr, (double*)h->vis.p))) return rc;
   hipLaunchKernelGGL(k_eval_points_hessian, dim3((P + 255) / 256, nq), dim3(256), 0, h->stream, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_plink,
-                     h->d_perm, h->d_scenes + scene_id, nq, (const double*)h->vis.p, (const double*)dbase, use_obs, (double*)dh);
-  if ((rc = fetch_out(h, 0, hess_out, (size_t)nq * P * 9 * sizeof(double)))) return rc;
-  return sync_and_finish_out(h);
+                     h->d_perm, h->d_scenes + scene_id, nq, (const double*)h->vis.p, dbase, use_obs, dh);
+  HIPCHK(h, hipGetLastError());
+  return io.finish();
 }
 
 // Shared by gto_eval_objective / gto_eval_obstacle_normal_eq: run init (kinematics + goal terms of Q as
@@ -2238,18 +2207,19 @@ static int eval_common(gto_handle* h, int B, int n_max, const int32_t* scene_id,
     n_goals = dummy_n.data();
     standoff = nullptr;
   }
-  const void *d_sid, *d_qc, *d_goals, *d_ng, *d_so, *d_base, *d_Q0;
-  if ((rc = stage_in(h, 0, scene_id, B * sizeof(int32_t), &d_sid))) return rc;
-  if ((rc = stage_in(h, 1, qc.data(), B * ndof * sizeof(double), &d_qc))) return rc;
-  if ((rc = stage_in(h, 2, goals, (size_t)B * n_max * 16 * sizeof(double), &d_goals))) return rc;
-  if ((rc = stage_in(h, 3, n_goals, B * sizeof(int32_t), &d_ng))) return rc;
-  if ((rc = stage_in(h, 4, standoff, (size_t)B * 16 * sizeof(double), &d_so))) return rc;
-  if ((rc = stage_in(h, 5, base_pos, (size_t)B * 3 * sizeof(double), &d_base))) return rc;
-  if ((rc = stage_in(h, 6, Q, B * ndof * T * sizeof(double), &d_Q0))) return rc;
+  Staging io(h);  // inputs only: the pieces come back below
+  const int32_t *d_sid, *d_ng;
+  const double *d_qc, *d_goals, *d_so, *d_base, *d_Q0;
+  if ((rc = io.in(scene_id, B, &d_sid))) return rc;
+  if ((rc = io.in(qc.data(), B * ndof, &d_qc))) return rc;
+  if ((rc = io.in(goals, (size_t)B * n_max * 16, &d_goals))) return rc;
+  if ((rc = io.in(n_goals, B, &d_ng))) return rc;
+  if ((rc = io.in(standoff, (size_t)B * 16, &d_so))) return rc;
+  if ((rc = io.in(base_pos, (size_t)B * 3, &d_base))) return rc;
+  if ((rc = io.in(Q, B * ndof * T, &d_Q0))) return rc;
   if ((rc = ensure_workspace(h, B))) return rc;
   SolveParams sp = make_params(h, n_max, standoff != nullptr);
-  BatchPtrs bp = make_ptrs(h, (const int32_t*)d_sid, (const double*)d_qc, (const double*)d_goals, (const int32_t*)d_ng,
-                           (const double*)d_so, (const double*)d_base, (const double*)d_Q0);
+  BatchPtrs bp = make_ptrs(h, d_sid, d_qc, d_goals, d_ng, d_so, d_base, d_Q0);
   HIPCHK(h, hipMemsetAsync(bp.n_done, 0, sizeof(int32_t), h->stream));
   hipLaunchKernelGGL(lm_init_kernel(h->np), dim3(B), dim3(256), 0, h->stream, h->d_rb, bp, sp, B, 1 /* raw: evaluate Q as given */);
   if ((rc = launch_obstacle(h, h->stream, bp, sp, B, init_pass()))) return rc;
@@ -2329,24 +2299,24 @@ int gto_plan_cost(gto_handle* h, int32_t scene_id, int32_t n, const double* plan
   if (!h) return GTO_ERR_INVALID_ARG;
   if (n < 0 || !plans || !base_pos || !cost_out) return fail(h, GTO_ERR_INVALID_ARG, "bad argument");
   if (n == 0) return GTO_OK;
-  if (scene_id < 0 || (size_t)scene_id >= h->scenes.size() || !h->scenes[scene_id].valid) return fail(h, GTO_ERR_NO_SCENE, "unknown scene");
+  if (!scene_valid(h, scene_id)) return fail(h, GTO_ERR_NO_SCENE, "unknown scene");
   HIPCHK(h, hipSetDevice(h->device));
   const size_t ndof = h->rb.ndof, T = h->opts.T;
-  const void *dplans, *dbase;
-  void* dpart;
+  Staging io(h);
+  const double *dplans, *dbase;
+  double* dpart;
   int rc;
-  if ((rc = stage_in(h, 0, plans, (size_t)n * ndof * T * sizeof(double), &dplans))) return rc;
-  if ((rc = stage_in(h, 1, base_pos, 3 * sizeof(double), &dbase))) return rc;
+  if ((rc = io.in(plans, (size_t)n * ndof * T, &dplans))) return rc;
+  if ((rc = io.in(base_pos, 3, &dbase))) return rc;
   std::vector<double> part((size_t)n * T);
-  if ((rc = stage_out(h, 0, part.data(), part.size() * sizeof(double), &dpart))) return rc;
+  if ((rc = io.out(part.data(), part.size(), &dpart))) return rc;
   const size_t pc_lds = sizeof(double) * plan_cost_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
   if (pc_lds > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the plan-cost kernel's LDS");
   HIPCHK(h, raise_dynamic_lds((const void*)k_plan_cost, pc_lds));
   hipLaunchKernelGGL(k_plan_cost, dim3((unsigned)((T + GTO_PLAN_TG - 1) / GTO_PLAN_TG), n), dim3(256), pc_lds, h->stream, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_plink,
-                     h->d_scenes + scene_id, (int)T, (const double*)dplans, (const double*)dbase, (double*)dpart);
-  if ((rc = fetch_out(h, 0, part.data(), part.size() * sizeof(double)))) return rc;
-  if ((rc = sync_and_finish_out(h))) return rc;
+                     h->d_scenes + scene_id, (int)T, dplans, dbase, dpart);
   HIPCHK(h, hipGetLastError());
+  if ((rc = io.finish())) return rc;
   for (int i = 0; i < n; ++i) {
     double c = 0.0, dd = 0.0;
     for (size_t t = 0; t < T; ++t) c += part[(size_t)i * T + t];  // waypoint order, like the reference loop
@@ -2727,8 +2697,7 @@ int gto_scene_from_depth(gto_handle* h, int32_t scene_id, const float* depth, in
 /* The two cost fields of a resident scene, device to host (float32 [nx ny nz] each; either pointer may be null). */
 int gto_get_scene_fields(gto_handle* h, int32_t scene_id, float* c_all_out, float* c_obs_out) {
   if (!h) return GTO_ERR_INVALID_ARG;
-  if (scene_id < 0 || (size_t)scene_id >= h->scenes.size() || !h->scenes[scene_id].valid)
-    return fail(h, GTO_ERR_NO_SCENE, "gto_get_scene_fields: the scene was never set");
+  if (!scene_valid(h, scene_id)) return fail(h, GTO_ERR_NO_SCENE, "gto_get_scene_fields: the scene was never set");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   const SceneDev& s = h->scenes[scene_id];
@@ -2840,27 +2809,21 @@ int gto_retime_batch(gto_handle* h, int32_t B, const double* plans, const double
   if (!plans) return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: null plans");
   HIPCHK(h, hipSetDevice(h->device));
   const size_t nB = (size_t)B, nd = d.ndof, T = d.T, N = d.N, nM = (size_t)M;
-  const void* d_plans;
-  void *d_dur, *d_t, *d_sd, *d_q, *d_qd, *d_qdd, *d_st;
-  if ((rc = stage_in(h, 0, plans, nB * nd * T * sizeof(double), &d_plans))) return rc;
-  if ((rc = stage_out(h, 0, duration_out, nB * sizeof(double), &d_dur))) return rc;
-  if ((rc = stage_out(h, 1, t_grid_out, nB * N * sizeof(double), &d_t))) return rc;
-  if ((rc = stage_out(h, 2, sd_grid_out, nB * N * sizeof(double), &d_sd))) return rc;
-  if ((rc = stage_out(h, 3, q_out, nB * nM * nd * sizeof(double), &d_q))) return rc;
-  if ((rc = stage_out(h, 4, qd_out, nB * nM * nd * sizeof(double), &d_qd))) return rc;
-  if ((rc = stage_out(h, 5, qdd_out, nB * nM * nd * sizeof(double), &d_qdd))) return rc;
-  if ((rc = stage_out(h, 6, status_out, nB * sizeof(int32_t), &d_st))) return rc;
-  rc = gto_retime_batch_device(h, B, (const double*)d_plans, vmax, amax, subdiv, M, (double*)d_dur, (double*)d_t,
-                               (double*)d_sd, (double*)d_q, (double*)d_qd, (double*)d_qdd, (int32_t*)d_st, nullptr);
+  Staging io(h);
+  const double* d_plans;
+  double *d_dur, *d_t, *d_sd, *d_q, *d_qd, *d_qdd;
+  int32_t* d_st;
+  if ((rc = io.in(plans, nB * nd * T, &d_plans))) return rc;
+  if ((rc = io.out(duration_out, nB, &d_dur))) return rc;
+  if ((rc = io.out(t_grid_out, nB * N, &d_t))) return rc;
+  if ((rc = io.out(sd_grid_out, nB * N, &d_sd))) return rc;
+  if ((rc = io.out(q_out, nB * nM * nd, &d_q))) return rc;
+  if ((rc = io.out(qd_out, nB * nM * nd, &d_qd))) return rc;
+  if ((rc = io.out(qdd_out, nB * nM * nd, &d_qdd))) return rc;
+  if ((rc = io.out(status_out, nB, &d_st))) return rc;
+  rc = gto_retime_batch_device(h, B, d_plans, vmax, amax, subdiv, M, d_dur, d_t, d_sd, d_q, d_qd, d_qdd, d_st, nullptr);
   if (rc) return rc;
-  if ((rc = fetch_out(h, 0, duration_out, nB * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 1, t_grid_out, nB * N * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 2, sd_grid_out, nB * N * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 3, q_out, nB * nM * nd * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 4, qd_out, nB * nM * nd * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 5, qdd_out, nB * nM * nd * sizeof(double)))) return rc;
-  if ((rc = fetch_out(h, 6, status_out, nB * sizeof(int32_t)))) return rc;
-  return sync_and_finish_out(h);
+  return io.finish();
 }
 
 }  // extern "C"

@@ -1386,3 +1386,61 @@ def test_non_finite_inputs_end_in_status_numerical(capi, oracle_mod, robot, T):
     np.testing.assert_array_equal(Q2, Qc)
     np.testing.assert_array_equal(it2, itc)
     h.close()
+
+
+# ------------------------------------------------------------------------------------------ staging on one handle
+def test_entry_points_interleaved_on_one_handle_equal_fresh_handles(capi, oracle_mod):
+    """The host-pointer entry points stage their arrays through the same slots and pinned buffers of a handle.  Called
+    interleaved on one handle, forwards and backwards, with a refused call in the middle, every call returns bit for
+    bit what the same call returns on a fresh handle."""
+    from grasptrajopt_amd import utils
+    prob = Problem("panda", B=6, scene_seed=3)
+    opts = oracle_mod.reference_opts(max_iter=10)
+
+    def handle():
+        h = capi.SolverHandle(prob.desc, prob.cfg["link_ee"], prob.cfg["link_gripper"], opts, device=0)
+        h.set_scene(*prob.scene_args())
+        return h
+
+    shared = handle()
+    prob.finish(shared.eval_fk)
+    d, B = prob.desc, prob.B
+    rng = np.random.default_rng(4)
+    q0 = prob.qc.copy()
+    q0[:, d.opt_index] += rng.uniform(-0.3, 0.3, size=(B, len(d.opt_index)))
+    RT = prob.goals[:, 0]
+    quat = np.stack([utils.ik_goal_quaternion(g.reshape(4, 4)) for g in RT])
+    rpy = np.stack([utils.ik_goal_rpy(g.reshape(4, 4)) for g in RT])
+    base_goals, _ = syn.make_base_goal_sets(d, shared.eval_fk, prob.cfg["link_ee"], prob.qc[0], B, 3, 0)
+    y = rng.uniform(-0.1, 0.1, size=(B, 3))
+    qb = np.repeat(prob.qc[:, None], 3, axis=1)
+    qs = np.concatenate([prob.Q0[b].T[::11] for b in range(2)])
+    calls = {
+        "retime_batch": lambda h: h.retime_batch(prob.Q0, d.velocity, 0.5, subdiv=2, n_samples=40),
+        "solve_ik_batch": lambda h: h.solve_ik_batch(0, q0, RT, prob.base, max_iter=30),
+        "solve_ik_pose_batch 1": lambda h: h.solve_ik_pose_batch(1, 0, q0, quat, prob.base, max_iter=30),
+        "solve_ik_pose_batch 2": lambda h: h.solve_ik_pose_batch(2, None, q0, rpy, max_iter=30),
+        "solve_base_batch": lambda h: h.solve_base_batch(prob.qc, base_goals, None, 0.01, max_iter=40),
+        "eval_base_objective": lambda h: h.eval_base_objective(y, qb, base_goals),
+        "eval_points": lambda h: h.eval_points(0, qs, prob.base[0]),
+        "eval_points xyz val": lambda h: h.eval_points(0, qs, prob.base[0], want=("xyz", "val")),
+        "plan_cost": lambda h: h.plan_cost(0, prob.Q0, prob.base[0]),
+        "solve_batch": lambda h: h.solve_batch(*prob.solve_args()),
+    }
+
+    def bits(r):
+        r = [r[k] for k in sorted(r)] if isinstance(r, dict) else r if isinstance(r, tuple) else (r,)
+        return [None if a is None else (a.dtype, a.shape, a.tobytes()) for a in r]
+
+    fresh = {}
+    for name, call in calls.items():
+        h = handle()
+        fresh[name] = bits(call(h))
+        h.close()
+    order = list(calls)
+    for k, name in enumerate(order + order[::-1]):
+        if k == len(order) // 2:
+            with pytest.raises(capi.GTOError, match="scene"):
+                shared.solve_ik_batch(7, q0, RT, prob.base)
+        assert bits(calls[name](shared)) == fresh[name], name
+    shared.close()
