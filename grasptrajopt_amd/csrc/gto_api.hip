@@ -21,6 +21,7 @@
 #include <sys/prctl.h>
 
 #include "gto_kernels.h"
+#include "gto_depth.h"
 #include "gto_retime.h"
 
 #define GTO_VERSION GTO_ABI_VERSION  // include/gto_solver.h
@@ -2335,6 +2336,8 @@ int gto_plan_cost(gto_handle* h, int32_t scene_id, int32_t n, const double* plan
 // Device buffers of gto_depth_sdf_cost are kept between calls (the entry point has no handle to hang them on): a call
 // allocates a dozen buffers, and hipMalloc / hipFree cost more than the kernels for the reference's 5 cm grids.  A buffer is
 // reused for a request of at most half its size up to its size; at most 1 GiB stays cached per process.
+}  // extern "C"
+
 namespace {
 struct DepthPool {
   struct Item { int device; void* p; size_t cap; };
@@ -2370,7 +2373,108 @@ struct DepthPool {
   }
 };
 DepthPool g_depth_pool;
+
+// What one call of an entry point (`who`, on handle `h` or none) holds of the pool, and how it reports its errors.  The
+// buffers go back when the call ends, however it ends.
+struct DepthLease {
+  gto_handle* h;
+  const char* who;
+  int device;
+  std::vector<std::pair<void*, size_t>> bufs;
+  DepthLease(gto_handle* h_, const char* who_, int device_) : h(h_), who(who_), device(device_) {}
+  DepthLease(const DepthLease&) = delete;
+  ~DepthLease() { release(); }
+  void release() {
+    if (bufs.empty()) return;
+    (void)hipDeviceSynchronize();  // nothing of this call may still be using them when the next call takes them
+    for (auto& b : bufs) g_depth_pool.give(device, b.first, b.second);
+    bufs.clear();
+  }
+  int no_memory() { return fail(h, GTO_ERR_ALLOC, std::string(who) + ": device allocation failed"); }
+  int hip(hipError_t e) { return e == hipSuccess ? GTO_OK : fail(h, GTO_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
+  // (the pool serves a request from the buffers of about its size that earlier calls gave back, first come first served: an
+  // entry point asks for its buffers in the same order every time, so that each finds its own predecessor again)
+  template <class T>
+  T* alloc(size_t count) {
+    size_t cap = 0;
+    void* p = g_depth_pool.take(device, count ? count * sizeof(T) : 8, &cap);
+    if (p) bufs.emplace_back(p, cap);
+    return (T*)p;
+  }
+  template <class T>
+  int upload(const T* host, size_t count, const T** dev) {  // a host array's copy on the device
+    T* d = alloc<T>(count);
+    *dev = d;
+    if (!d) return no_memory();
+    return count ? hip(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice)) : GTO_OK;
+  }
+};
+#define DEPTH_TRY(rc_expr)                     \
+  do {                                         \
+    if (const int rc_ = (rc_expr)) return rc_; \
+  } while (0)
+
+// GTO_DEPTH_BRUTE and GTO_DEPTH_STATS are read by every call (gto_depth_sdf_cost has no handle whose Tunables could hold them)
+bool depth_brute_force() {  // the exhaustive search (reference construction; the two are compared in a test)
+  const char* e = getenv("GTO_DEPTH_BRUTE");
+  return e && atoi(e) != 0;
+}
+bool depth_stats() { return getenv("GTO_DEPTH_STATS") != nullptr; }
+
+// The two non-blocking streams of a device that gto_scene_from_depth's searches run on, kept for the process
+hipError_t depth_search_streams(int device, hipStream_t* sa, hipStream_t* sb) {
+  static std::mutex mu;
+  static std::vector<std::pair<int, std::pair<hipStream_t, hipStream_t>>> streams;
+  std::lock_guard<std::mutex> lock(mu);
+  for (auto& e : streams)
+    if (e.first == device) {
+      *sa = e.second.first, *sb = e.second.second;
+      return hipSuccess;
+    }
+  hipError_t e = hipStreamCreateWithFlags(sa, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(sb, hipStreamNonBlocking);
+  if (e == hipSuccess) streams.push_back({device, {*sa, *sb}});
+  return e;
+}
+
+int upload_camera(DepthLease& c, const double* K, const double* Kinv, const double* pose, const double* inv, DepthCamera* cam) {
+  double mats[9 + 9 + 16 + 16];
+  std::memcpy(mats, K, 9 * sizeof(double));
+  std::memcpy(mats + 9, Kinv, 9 * sizeof(double));
+  std::memcpy(mats + 18, pose, 16 * sizeof(double));
+  std::memcpy(mats + 34, inv, 16 * sizeof(double));
+  const double* d;
+  DEPTH_TRY(c.upload(mats, sizeof mats / sizeof *mats, &d));
+  *cam = {d, d + 9, d + 18, d + 34};
+  return GTO_OK;
+}
+
+// Queries in Morton order of their position within the cloud's root box (coherent waves): 30-bit keys, hipCUB radix sort of
+// (key, index) on the null stream
+int sort_queries(DepthLease& c, const DepthCloud& cl, DepthQueries* qs) {
+  const long nq = qs->nq;
+  if (nq >= ((int64_t)1 << 31)) return fail(c.h, GTO_ERR_UNSUPPORTED, std::string(c.who) + ": more than 2^31 queries");
+  unsigned* d_keys = c.alloc<unsigned>((size_t)nq * 4);  // keys in / out, indices in / out
+  if (!d_keys) return c.no_memory();
+  unsigned *d_keys2 = d_keys + nq, *d_idx = d_keys + 2 * nq, *d_idx2 = d_keys + 3 * nq;
+  hipLaunchKernelGGL(k_query_keys, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, 0, qs->q, nq, cl.boxes, d_keys, d_idx);
+  size_t tmp_bytes = 0;
+  DEPTH_TRY(c.hip(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, (int)nq, 0, 30, (hipStream_t)0)));
+  void* d_tmp = c.alloc<char>(tmp_bytes);
+  if (!d_tmp) return c.no_memory();
+  qs->order = d_idx2;
+  return c.hip(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, (int)nq, 0, 30, (hipStream_t)0));
+}
+
+// The three counters k_depth_sdf_bvh adds to under GTO_DEPTH_STATS, zeroed (null without it, and when the pool has none left)
+int depth_counters(DepthLease& c, bool stats, unsigned long long** d_stats) {
+  *d_stats = stats ? c.alloc<unsigned long long>(3) : nullptr;
+  return *d_stats ? c.hip(hipMemset(*d_stats, 0, 3 * sizeof(unsigned long long))) : GTO_OK;
+}
+
 }  // namespace
+
+extern "C" {
 
 int gto_depth_sdf_cost(int device, const float* depth, int32_t H, int32_t W, const double* K, const double* Kinv,
                        const double* cam_pose, const double* cam_inv, const uint8_t* target_mask, double threshold,
@@ -2384,120 +2488,56 @@ int gto_depth_sdf_cost(int device, const float* depth, int32_t H, int32_t W, con
   const size_t N = (size_t)H * W;
   int cur_dev = 0;
   (void)hipGetDevice(&cur_dev);
-  std::vector<std::pair<void*, size_t>> bufs;
-  auto dalloc = [&](size_t bytes) -> void* {
-    size_t cap = 0;
-    void* p = g_depth_pool.take(cur_dev, bytes ? bytes : 8, &cap);
-    if (p) bufs.emplace_back(p, cap);
-    return p;
-  };
-  auto cleanup = [&]() {
-    (void)hipDeviceSynchronize();  // nothing of this call may still be using them when the next call takes them
-    for (auto& b : bufs) g_depth_pool.give(cur_dev, b.first, b.second);
-  };
-#define DCHK(expr)                                                                                     \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) {                                                                            \
-      cleanup();                                                                                       \
-      return fail(nullptr, GTO_ERR_HIP, std::string("gto_depth_sdf_cost: ") + hipGetErrorString(e_));  \
-    }                                                                                                  \
-  } while (0)
-  float* d_depth = (float*)dalloc(N * sizeof(float));
-  double* d_mats = (double*)dalloc((9 + 9 + 16 + 16) * sizeof(double));
-  uint8_t* d_mask = target_mask ? (uint8_t*)dalloc(N) : nullptr;
-  double* d_p = (double*)dalloc(3 * N * sizeof(double));
-  uint8_t* d_valid = (uint8_t*)dalloc(N);
-  double* d_q = (double*)dalloc((size_t)nq * 3 * sizeof(double));
-  float* d_sdf = (float*)dalloc((size_t)nq * sizeof(float));
-  float* d_cost = (float*)dalloc((size_t)nq * sizeof(float));
-  uint8_t* d_in = (uint8_t*)dalloc((size_t)nq);
-  if (!d_depth || !d_mats || (target_mask && !d_mask) || !d_p || !d_valid || !d_q || !d_sdf || !d_cost || !d_in) {
-    cleanup();
-    return fail(nullptr, GTO_ERR_ALLOC, "gto_depth_sdf_cost: device allocation failed");
-  }
-  double mats[50];
-  std::memcpy(mats, K, 9 * sizeof(double));
-  std::memcpy(mats + 9, Kinv, 9 * sizeof(double));
-  std::memcpy(mats + 18, cam_pose, 16 * sizeof(double));
-  std::memcpy(mats + 34, cam_inv, 16 * sizeof(double));
-  DCHK(hipMemcpy(d_depth, depth, N * sizeof(float), hipMemcpyHostToDevice));
-  DCHK(hipMemcpy(d_mats, mats, sizeof mats, hipMemcpyHostToDevice));
-  if (target_mask) DCHK(hipMemcpy(d_mask, target_mask, N, hipMemcpyHostToDevice));
-  if (nq) DCHK(hipMemcpy(d_q, query, (size_t)nq * 3 * sizeof(double), hipMemcpyHostToDevice));
-  double *d_px = d_p, *d_py = d_p + N, *d_pz = d_p + 2 * N;
-  hipLaunchKernelGGL(k_depth_backproject, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, d_depth, H, W, d_mats + 9,
-                     d_mats + 18, d_mask, threshold, d_px, d_py, d_pz, d_valid);
-  const char* brute_env = getenv("GTO_DEPTH_BRUTE");
-  const bool brute = brute_env && atoi(brute_env) != 0;  // the exhaustive search (reference construction; the two are compared in a test)
-  if (nq && brute) {
-    hipLaunchKernelGGL(k_depth_sdf, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, 0, d_px, d_py, d_pz, (int)N, d_depth, H, W,
-                       d_mats, d_mats + 34, d_q, (long)nq, epsilon, w_inside, d_sdf, d_in, d_cost);
-  } else if (nq) {
-    // bounding-box hierarchy over 8 x 4 pixel tiles of the depth image (k_depth_sdf_bvh): same distances, bit for bit
-    const int tx = (W + GTO_BVH_TILE_W - 1) / GTO_BVH_TILE_W, ty = (H + GTO_BVH_TILE_H - 1) / GTO_BVH_TILE_H;
-    int P = 1;
-    while (P < tx || P < ty) P <<= 1;
-    if (P > 1024) {  // more tiles per side than k_bvh_up's single workgroup builds: the exhaustive search serves such images
-      hipLaunchKernelGGL(k_depth_sdf, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, 0, d_px, d_py, d_pz, (int)N, d_depth, H, W,
-                         d_mats, d_mats + 34, d_q, (long)nq, epsilon, w_inside, d_sdf, d_in, d_cost);
-    } else {
-    double* d_boxes = (double*)dalloc((size_t)(2 * P * P) * 6 * sizeof(double));
-    if (!d_boxes) {
-      cleanup();
-      return fail(nullptr, GTO_ERR_ALLOC, "gto_depth_sdf_cost: device allocation failed");
-    }
-    hipLaunchKernelGGL(k_bvh_leaves, dim3((unsigned)((P * P + 255) / 256)), dim3(256), 0, 0, d_px, d_py, d_pz, H, W, P, d_boxes);
-    if (P > 1) hipLaunchKernelGGL(k_bvh_up, dim3(1), dim3(1024), 0, 0, P, d_boxes);
-    // queries in Morton order of their position (coherent waves): 30-bit keys, hipCUB radix sort of (key, index)
-    if (nq >= ((int64_t)1 << 31)) {
-      cleanup();
-      return fail(nullptr, GTO_ERR_UNSUPPORTED, "gto_depth_sdf_cost: more than 2^31 queries");
-    }
-    unsigned* d_keys = (unsigned*)dalloc((size_t)nq * 4 * sizeof(unsigned));  // keys in / out, indices in / out
-    if (!d_keys) {
-      cleanup();
-      return fail(nullptr, GTO_ERR_ALLOC, "gto_depth_sdf_cost: device allocation failed");
-    }
-    unsigned long long* d_stats = nullptr;
-    if (getenv("GTO_DEPTH_STATS")) {
-      d_stats = (unsigned long long*)dalloc(3 * sizeof(unsigned long long));
-      if (d_stats) DCHK(hipMemset(d_stats, 0, 3 * sizeof(unsigned long long)));
-    }
-    unsigned *d_keys2 = d_keys + nq, *d_idx = d_keys + 2 * nq, *d_idx2 = d_keys + 3 * nq;
-    hipLaunchKernelGGL(k_query_keys, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, 0, d_q, (long)nq, d_boxes, d_keys, d_idx);
-    size_t tmp_bytes = 0;
-    DCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, (int)nq, 0, 30, (hipStream_t)0));
-    void* d_tmp = dalloc(tmp_bytes);
-    if (!d_tmp) {
-      cleanup();
-      return fail(nullptr, GTO_ERR_ALLOC, "gto_depth_sdf_cost: device allocation failed");
-    }
-    DCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, (int)nq, 0, 30, (hipStream_t)0));
-    hipLaunchKernelGGL(k_depth_sdf_bvh, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, 0, d_px, d_py, d_pz, d_boxes, P, d_idx2, d_depth, H, W,
-                       d_mats, d_mats + 34, d_q, (long)nq, epsilon, w_inside, d_sdf, d_in, d_cost, d_stats, 0);
+  // bounding-box hierarchy over 8 x 4 pixel tiles of the depth image (k_depth_sdf_bvh): the exhaustive search's distances,
+  // bit for bit.  The exhaustive search itself on request, and for images with more tiles per side than k_bvh_up builds
+  const int P = tile_levels(H, W);
+  const bool tree = nq && !depth_brute_force() && P <= GTO_BVH_MAX_P;
+  DepthLease c(nullptr, "gto_depth_sdf_cost", cur_dev);
+  const float* d_depth;
+  const uint8_t* d_mask = nullptr;
+  DepthCamera cam;
+  DepthQueries qs = {nullptr, (long)nq, nullptr};
+  DEPTH_TRY(c.upload(depth, N, &d_depth));
+  DEPTH_TRY(upload_camera(c, K, Kinv, cam_pose, cam_inv, &cam));
+  if (target_mask) DEPTH_TRY(c.upload(target_mask, N, &d_mask));
+  double* d_p = c.alloc<double>(3 * N);
+  uint8_t* d_valid = c.alloc<uint8_t>(N);
+  if (!d_p || !d_valid) return c.no_memory();
+  DEPTH_TRY(c.upload(query, (size_t)nq * 3, &qs.q));
+  float* d_sdf = c.alloc<float>((size_t)nq);
+  float* d_cost = c.alloc<float>((size_t)nq);
+  uint8_t* d_in = c.alloc<uint8_t>((size_t)nq);
+  double* d_boxes = tree ? c.alloc<double>(bvh_box_doubles(P)) : nullptr;
+  if (!d_sdf || !d_cost || !d_in || (tree && !d_boxes)) return c.no_memory();
+  const DepthCloud cloud = {d_depth, H, W, d_p, d_p + N, d_p + 2 * N, tree ? P : 0, d_boxes};
+  const DepthFields out = {d_sdf, d_in, d_cost};
+  build_cloud(cloud, cam, d_mask, threshold, d_valid);
+  if (tree) {
+    unsigned long long* d_stats;
+    DEPTH_TRY(depth_counters(c, depth_stats(), &d_stats));
+    DEPTH_TRY(sort_queries(c, cloud, &qs));
+    search_tree(0, cloud, cam, qs, epsilon, w_inside, out, d_stats, false);
     if (d_stats) {
       unsigned long long st[3];
-      DCHK(hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost));
+      DEPTH_TRY(c.hip(hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost)));
       fprintf(stderr, "[gto] depth field search: %lld queries, nodes popped per query %.1f, leaves per query %.1f, loop iterations per wave %.1f\n",
               (long long)nq, (double)st[0] / nq, (double)st[1] / nq, (double)st[2] / ((nq + 63) / 64));
     }
-    }
+  } else if (nq) {
+    search_exhaustive(0, cloud, cam, qs, epsilon, w_inside, out);
   }
-  DCHK(hipGetLastError());
-  DCHK(hipDeviceSynchronize());
-  if (sdf_out && nq) DCHK(hipMemcpy(sdf_out, d_sdf, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost));
-  if (cost_out && nq) DCHK(hipMemcpy(cost_out, d_cost, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost));
-  if (inside_out && nq) DCHK(hipMemcpy(inside_out, d_in, (size_t)nq, hipMemcpyDeviceToHost));
-  if (valid_out) DCHK(hipMemcpy(valid_out, d_valid, N, hipMemcpyDeviceToHost));
+  DEPTH_TRY(c.hip(hipGetLastError()));
+  DEPTH_TRY(c.hip(hipDeviceSynchronize()));
+  if (sdf_out && nq) DEPTH_TRY(c.hip(hipMemcpy(sdf_out, d_sdf, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost)));
+  if (cost_out && nq) DEPTH_TRY(c.hip(hipMemcpy(cost_out, d_cost, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost)));
+  if (inside_out && nq) DEPTH_TRY(c.hip(hipMemcpy(inside_out, d_in, (size_t)nq, hipMemcpyDeviceToHost)));
+  if (valid_out) DEPTH_TRY(c.hip(hipMemcpy(valid_out, d_valid, N, hipMemcpyDeviceToHost)));
   if (points_out) {
     std::vector<double> soa(3 * N);
-    DCHK(hipMemcpy(soa.data(), d_p, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+    DEPTH_TRY(c.hip(hipMemcpy(soa.data(), d_p, 3 * N * sizeof(double), hipMemcpyDeviceToHost)));
     for (size_t i = 0; i < N; ++i)
       for (int r = 0; r < 3; ++r) points_out[3 * i + r] = soa[(size_t)r * N + i];
   }
-#undef DCHK
-  cleanup();
   return GTO_OK;
 }
 
@@ -2527,83 +2567,41 @@ int gto_scene_from_depth(gto_handle* h, int32_t scene_id, const float* depth, in
   if (!depth || !K || !Kinv || !cam_pose || !cam_inv || H < 1 || W < 1 || !(grid_res > 0) || !(margin >= 0))
     return fail(h, GTO_ERR_INVALID_ARG, "gto_scene_from_depth: null or empty input");
   HIPCHK(h, hipSetDevice(h->device));
-  const bool stats = getenv("GTO_DEPTH_STATS") != nullptr;
+  const bool stats = depth_stats();
   auto t_now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_[8] = {t_now(), 0, 0, 0, 0, 0, 0, 0};
   const size_t N = (size_t)H * W;
-  const int tx = (W + GTO_BVH_TILE_W - 1) / GTO_BVH_TILE_W, ty = (H + GTO_BVH_TILE_H - 1) / GTO_BVH_TILE_H;
-  int P = 1;
-  while (P < tx || P < ty) P <<= 1;
-  if (P > 1024) return fail(h, GTO_ERR_UNSUPPORTED, "gto_scene_from_depth: image larger than 8192 x 4096 pixels");
-  std::vector<std::pair<void*, size_t>> bufs;
-  auto dalloc = [&](size_t bytes) -> void* {
-    size_t cap = 0;
-    void* p = g_depth_pool.take(h->device, bytes ? bytes : 8, &cap);
-    if (p) bufs.emplace_back(p, cap);
-    return p;
-  };
-  auto cleanup = [&]() {
-    (void)hipDeviceSynchronize();
-    for (auto& b : bufs) g_depth_pool.give(h->device, b.first, b.second);
-  };
-#define DCHK(expr)                                                                                   \
-  do {                                                                                               \
-    hipError_t e_ = (expr);                                                                          \
-    if (e_ != hipSuccess) {                                                                          \
-      cleanup();                                                                                     \
-      return fail(h, GTO_ERR_HIP, std::string("gto_scene_from_depth: ") + hipGetErrorString(e_));    \
-    }                                                                                                \
-  } while (0)
-#define DNULL(p)                                                                                     \
-  do {                                                                                               \
-    if (!(p)) {                                                                                      \
-      cleanup();                                                                                     \
-      return fail(h, GTO_ERR_ALLOC, "gto_scene_from_depth: device allocation failed");               \
-    }                                                                                                \
-  } while (0)
+  const int P = tile_levels(H, W);
+  if (P > GTO_BVH_MAX_P) return fail(h, GTO_ERR_UNSUPPORTED, "gto_scene_from_depth: image larger than 8192 x 4096 pixels");
+  DepthLease c(h, "gto_scene_from_depth", h->device);
   // the second cloud: the obstacle image (the driver's depth_obstacle, examples/pybullet_gto_planning.py:187-189: the target's
   // pixels pushed to the threshold) without the masked pixels; its visibility test reads the obstacle image
   const bool two = target_mask != nullptr || depth_obstacle != nullptr;
-  float* d_depth = (float*)dalloc(N * sizeof(float));
-  float* d_depth_o = depth_obstacle ? (float*)dalloc(N * sizeof(float)) : d_depth;
-  double* d_mats = (double*)dalloc((9 + 9 + 16 + 16 + 8) * sizeof(double));
-  uint8_t* d_mask = target_mask ? (uint8_t*)dalloc(N) : nullptr;
-  double* d_pa = (double*)dalloc(3 * N * sizeof(double));
-  double* d_po = two ? (double*)dalloc(3 * N * sizeof(double)) : d_pa;
-  uint8_t* d_valid = (uint8_t*)dalloc(N);
-  double* d_boxa = (double*)dalloc((size_t)(2 * P * P) * 6 * sizeof(double));
-  double* d_boxo = two ? (double*)dalloc((size_t)(2 * P * P) * 6 * sizeof(double)) : d_boxa;
-  DNULL(d_depth); DNULL(d_depth_o); DNULL(d_mats); DNULL(d_pa); DNULL(d_po); DNULL(d_valid); DNULL(d_boxa); DNULL(d_boxo);
-  if (target_mask) DNULL(d_mask);
-  double mats[50];
-  std::memcpy(mats, K, 9 * sizeof(double));
-  std::memcpy(mats + 9, Kinv, 9 * sizeof(double));
-  std::memcpy(mats + 18, cam_pose, 16 * sizeof(double));
-  std::memcpy(mats + 34, cam_inv, 16 * sizeof(double));
-  DCHK(hipMemcpy(d_depth, depth, N * sizeof(float), hipMemcpyHostToDevice));
-  if (depth_obstacle) DCHK(hipMemcpy(d_depth_o, depth_obstacle, N * sizeof(float), hipMemcpyHostToDevice));
-  DCHK(hipMemcpy(d_mats, mats, sizeof mats, hipMemcpyHostToDevice));
-  if (target_mask) DCHK(hipMemcpy(d_mask, target_mask, N, hipMemcpyHostToDevice));
+  const float *d_depth, *d_depth_o;
+  const uint8_t* d_mask = nullptr;
+  DepthCamera cam;
+  DEPTH_TRY(c.upload(depth, N, &d_depth));
+  d_depth_o = d_depth;
+  if (depth_obstacle) DEPTH_TRY(c.upload(depth_obstacle, N, &d_depth_o));
+  DEPTH_TRY(upload_camera(c, K, Kinv, cam_pose, cam_inv, &cam));
+  if (target_mask) DEPTH_TRY(c.upload(target_mask, N, &d_mask));
+  double* d_pa = c.alloc<double>(3 * N);
+  double* d_po = two ? c.alloc<double>(3 * N) : d_pa;
+  uint8_t* d_valid = c.alloc<uint8_t>(N);
+  double* d_boxa = c.alloc<double>(bvh_box_doubles(P));
+  double* d_boxo = two ? c.alloc<double>(bvh_box_doubles(P)) : d_boxa;
+  if (!d_pa || !d_po || !d_valid || !d_boxa || !d_boxo) return c.no_memory();
   t_[1] = t_now();
-  const unsigned nbN = (unsigned)((N + 255) / 256);
-  hipLaunchKernelGGL(k_depth_backproject, dim3(nbN), dim3(256), 0, 0, d_depth, H, W, d_mats + 9, d_mats + 18, (const uint8_t*)nullptr, threshold,
-                     d_pa, d_pa + N, d_pa + 2 * N, d_valid);
   // the hierarchy of the first cloud: its root box is the bounding box of the valid points (gto/gto_models.py:155-157)
-  hipLaunchKernelGGL(k_bvh_leaves, dim3((unsigned)((P * P + 255) / 256)), dim3(256), 0, 0, d_pa, d_pa + N, d_pa + 2 * N, H, W, P, d_boxa);
-  if (P > 1) hipLaunchKernelGGL(k_bvh_up, dim3(1), dim3(1024), 0, 0, P, d_boxa);
-  if (two) {
-    hipLaunchKernelGGL(k_depth_backproject, dim3(nbN), dim3(256), 0, 0, d_depth_o, H, W, d_mats + 9, d_mats + 18, (const uint8_t*)d_mask, threshold,
-                       d_po, d_po + N, d_po + 2 * N, d_valid);
-    hipLaunchKernelGGL(k_bvh_leaves, dim3((unsigned)((P * P + 255) / 256)), dim3(256), 0, 0, d_po, d_po + N, d_po + 2 * N, H, W, P, d_boxo);
-    if (P > 1) hipLaunchKernelGGL(k_bvh_up, dim3(1), dim3(1024), 0, 0, P, d_boxo);
-  }
+  const DepthCloud all = {d_depth, H, W, d_pa, d_pa + N, d_pa + 2 * N, P, d_boxa};
+  const DepthCloud obs = {d_depth_o, H, W, d_po, d_po + N, d_po + 2 * N, P, d_boxo};
+  build_cloud(all, cam, nullptr, threshold, d_valid);
+  if (two) build_cloud(obs, cam, d_mask, threshold, d_valid);
   double root[6];
-  DCHK(hipMemcpy(root, d_boxa, sizeof root, hipMemcpyDeviceToHost));  // (synchronises with the null stream)
+  DEPTH_TRY(c.hip(hipMemcpy(root, all.boxes, sizeof root, hipMemcpyDeviceToHost)));  // (synchronises with the null stream)
   t_[2] = t_now();
-  if (!(root[0] <= root[3]) || !std::isfinite(root[0]) || !std::isfinite(root[3])) {
-    cleanup();
+  if (!(root[0] <= root[3]) || !std::isfinite(root[0]) || !std::isfinite(root[3]))
     return fail(h, GTO_ERR_INVALID_ARG, "gto_scene_from_depth: no valid pixel in the depth image");
-  }
   std::vector<double> ax[3];
   int32_t shape[3];
   double origin[3];
@@ -2614,74 +2612,44 @@ int gto_scene_from_depth(gto_handle* h, int32_t scene_id, const float* depth, in
     origin[a] = root[a] - margin;
     nq *= ax[a].size();
   }
-  if (nq == 0 || nq >= ((size_t)1 << 31)) {
-    cleanup();
-    return fail(h, GTO_ERR_UNSUPPORTED, "gto_scene_from_depth: empty grid or more than 2^31 voxels");
-  }
+  if (nq == 0 || nq >= ((size_t)1 << 31)) return fail(h, GTO_ERR_UNSUPPORTED, "gto_scene_from_depth: empty grid or more than 2^31 voxels");
   std::vector<double> axes(ax[0]);
   axes.insert(axes.end(), ax[1].begin(), ax[1].end());
   axes.insert(axes.end(), ax[2].begin(), ax[2].end());
-  double* d_axes = (double*)dalloc(axes.size() * sizeof(double));
-  double* d_q = (double*)dalloc(nq * 3 * sizeof(double));
-  float* d_costa = (float*)dalloc(nq * sizeof(float));
-  float* d_costo = two ? (float*)dalloc(nq * sizeof(float)) : d_costa;
-  float* d_sdf = (float*)dalloc(nq * sizeof(float));
-  uint8_t* d_in = (uint8_t*)dalloc(nq);
-  unsigned* d_keys = (unsigned*)dalloc(nq * 4 * sizeof(unsigned));
-  DNULL(d_axes); DNULL(d_q); DNULL(d_costa); DNULL(d_costo); DNULL(d_sdf); DNULL(d_in); DNULL(d_keys);
-  DCHK(hipMemcpy(d_axes, axes.data(), axes.size() * sizeof(double), hipMemcpyHostToDevice));
-  const unsigned nbq = (unsigned)((nq + 255) / 256);
-  hipLaunchKernelGGL(k_grid_queries, dim3(nbq), dim3(256), 0, 0, d_axes, shape[0], shape[1], shape[2], d_q);
-  unsigned *d_keys2 = d_keys + nq, *d_idx = d_keys + 2 * nq, *d_idx2 = d_keys + 3 * nq;
-  hipLaunchKernelGGL(k_query_keys, dim3(nbq), dim3(256), 0, 0, d_q, (long)nq, d_boxa, d_keys, d_idx);
-  size_t tmp_bytes = 0;
-  DCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, (int)nq, 0, 30, (hipStream_t)0));
-  void* d_tmp = dalloc(tmp_bytes);
-  DNULL(d_tmp);
-  DCHK(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, (int)nq, 0, 30, (hipStream_t)0));
-  unsigned long long* d_stats = nullptr;
-  if (stats) {
-    d_stats = (unsigned long long*)dalloc(3 * sizeof(unsigned long long));
-    if (d_stats) DCHK(hipMemset(d_stats, 0, 3 * sizeof(unsigned long long)));
-    DCHK(hipDeviceSynchronize());
-  }
+  const double* d_axes;
+  DEPTH_TRY(c.upload(axes.data(), axes.size(), &d_axes));
+  double* d_q = c.alloc<double>(nq * 3);
+  float* d_costa = c.alloc<float>(nq);
+  float* d_costo = two ? c.alloc<float>(nq) : d_costa;
+  uint8_t* d_in = c.alloc<uint8_t>(nq);
+  if (!d_q || !d_costa || !d_costo || !d_in) return c.no_memory();
+  hipLaunchKernelGGL(k_grid_queries, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, 0, d_axes, shape[0], shape[1], shape[2], d_q);
+  DepthQueries qs = {d_q, (long)nq, nullptr};
+  DEPTH_TRY(sort_queries(c, all, &qs));
+  unsigned long long* d_stats;
+  DEPTH_TRY(depth_counters(c, stats, &d_stats));
+  if (stats) DEPTH_TRY(c.hip(hipDeviceSynchronize()));
   t_[3] = t_now();
   // the two searches are independent and each is bound by its slowest packets (the voxels deep behind the surfaces): side
   // by side on two streams of their own, behind everything the null stream has done so far
-  static std::mutex s_mu;
-  static std::vector<std::pair<int, std::pair<hipStream_t, hipStream_t>>> s_streams;  // per device, kept for the process
   hipStream_t sa = nullptr, sb = nullptr;
-  {
-    std::lock_guard<std::mutex> lock(s_mu);
-    for (auto& e : s_streams)
-      if (e.first == h->device) sa = e.second.first, sb = e.second.second;
-    if (!sa) {
-      DCHK(hipStreamCreateWithFlags(&sa, hipStreamNonBlocking));
-      DCHK(hipStreamCreateWithFlags(&sb, hipStreamNonBlocking));
-      s_streams.push_back({h->device, {sa, sb}});
-    }
-  }
-  DCHK(hipStreamSynchronize(0));
-  uint8_t* d_in2 = two ? (uint8_t*)dalloc(nq) : d_in;
-  DNULL(d_in2);
-  hipLaunchKernelGGL(k_depth_sdf_bvh, dim3(nbq), dim3(256), 0, sa, d_pa, d_pa + N, d_pa + 2 * N, d_boxa, P, d_idx2, d_depth, H, W, d_mats, d_mats + 34,
-                     d_q, (long)nq, epsilon, w_inside, (float*)nullptr, d_in, d_costa, d_stats, 1);
-  if (two)
-    hipLaunchKernelGGL(k_depth_sdf_bvh, dim3(nbq), dim3(256), 0, sb, d_po, d_po + N, d_po + 2 * N, d_boxo, P, d_idx2, d_depth_o, H, W, d_mats, d_mats + 34,
-                       d_q, (long)nq, epsilon, w_inside, (float*)nullptr, d_in2, d_costo, (unsigned long long*)nullptr, 1);
-  DCHK(hipGetLastError());
-  DCHK(hipDeviceSynchronize());
+  DEPTH_TRY(c.hip(depth_search_streams(h->device, &sa, &sb)));
+  DEPTH_TRY(c.hip(hipStreamSynchronize(0)));
+  uint8_t* d_in2 = two ? c.alloc<uint8_t>(nq) : d_in;
+  if (!d_in2) return c.no_memory();
+  search_tree(sa, all, cam, qs, epsilon, w_inside, {nullptr, d_in, d_costa}, d_stats, true);
+  if (two) search_tree(sb, obs, cam, qs, epsilon, w_inside, {nullptr, d_in2, d_costo}, nullptr, true);
+  DEPTH_TRY(c.hip(hipGetLastError()));
+  DEPTH_TRY(c.hip(hipDeviceSynchronize()));
   t_[4] = t_now();
   if (d_stats) {
     unsigned long long stv[3];
-    DCHK(hipMemcpy(stv, d_stats, sizeof stv, hipMemcpyDeviceToHost));
+    DEPTH_TRY(c.hip(hipMemcpy(stv, d_stats, sizeof stv, hipMemcpyDeviceToHost)));
     fprintf(stderr, "[gto] depth field search (first cloud): %zu queries, nodes popped per wave %.1f, leaves per wave %.1f\n", nq, (double)stv[2] / ((nq + 63) / 64), (double)stv[1] / 64 / ((nq + 63) / 64));
   }
   const int rc = set_scene_impl(h, scene_id, d_costa, two ? d_costo : nullptr, shape, origin, grid_res, false, hipMemcpyDeviceToDevice);
   t_[5] = t_now();
-#undef DCHK
-#undef DNULL
-  cleanup();
+  c.release();
   t_[6] = t_now();
   if (stats)
     fprintf(stderr, "[gto] scene from depth (%d x %d image, %zu voxels), ms: alloc + upload %.3f | back-projection, hierarchies, bounds %.3f | queries, keys, sort %.3f | "

@@ -403,6 +403,56 @@ def test_device_resident_depth_scene_equals_the_host_path(oracle_mod, res, patte
     assert h_["pc_all"] == d_["pc_all"]
 
 
+def test_depth_entry_points_refuse_bad_input_and_serve_the_next_call():
+    """What gto_depth_sdf_cost and gto_scene_from_depth refuse (include/gto_solver.h): the code, the text of gto_last_error,
+    and that a refusal in the middle of a call (an image without a valid pixel: buffers taken, kernels launched) leaves the
+    handle and the buffer cache as a fresh handle finds them: the next build gives the same grid and the same fields."""
+    import ctypes as C
+    from grasptrajopt_amd import _capi
+    cfg = cfg_of("panda")
+    depth, K, cam, target = _depth_scene_inputs()
+    H, W = depth.shape
+    Kinv, cinv = np.ascontiguousarray(np.linalg.inv(K)), np.ascontiguousarray(np.linalg.inv(cam))
+    query = np.array([[0.5, 0.0, 0.2], [0.4, 0.1, 0.0]])
+    lib = _capi.load_library()
+    pf, pd, pu8 = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+    ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
+
+    def cost_call(depth=depth, H=H, query=query, nq=len(query)):
+        out = np.empty(max(nq, 1), np.float32)
+        rc = lib.gto_depth_sdf_cost(0, ptr(depth, pf), H, W, ptr(K, pd), ptr(Kinv, pd), ptr(cam, pd), ptr(cinv, pd), None, 2.0,
+                                    ptr(query, pd), nq, 0.02, 1.0, None, None, ptr(out, pf), None, None)
+        return rc, (lib.gto_last_error(None) or b"").decode()
+
+    for kw in (dict(depth=None), dict(H=0), dict(query=None)):
+        assert cost_call(**kw) == (-1, "gto_depth_sdf_cost: null or empty input"), kw
+    assert cost_call()[0] == 0
+
+    def new_handle():
+        return _capi.SolverHandle(g.load_builtin("panda"), cfg["link_ee"], cfg["link_gripper"], _capi.default_opts(), device=0)
+
+    def scene_call(h, depth=depth, H=H, grid_res=0.05):
+        shp, org, bnd = np.zeros(3, np.int32), np.zeros(3), np.zeros(6)
+        rc = lib.gto_scene_from_depth(h._h, 0, ptr(depth, pf), H, W, ptr(K, pd), ptr(Kinv, pd), ptr(cam, pd), ptr(cinv, pd), ptr(target, pu8),
+                                      None, 2.0, grid_res, 0.4, 0.02, 1.0, ptr(shp, C.POINTER(C.c_int32)), ptr(org, pd), ptr(bnd, pd))
+        return rc, (lib.gto_last_error(h._h) or b"").decode()
+
+    h = new_handle()
+    for kw in (dict(depth=None), dict(H=0), dict(grid_res=0.0), dict(grid_res=-0.05)):
+        assert scene_call(h, **kw) == (-1, "gto_scene_from_depth: null or empty input"), kw
+    assert scene_call(h, depth=np.zeros_like(depth)) == (-1, "gto_scene_from_depth: no valid pixel in the depth image")
+    fresh = new_handle()
+    built = [x.scene_from_depth(0, depth, K, cam, target_mask=target, threshold=2.0, grid_res=0.05) for x in (h, fresh)]
+    assert built[0][0] == built[1][0]
+    np.testing.assert_array_equal(built[0][1], built[1][1])
+    np.testing.assert_array_equal(built[0][2], built[1][2])
+    for a, b in zip(h.scene_fields(0), fresh.scene_fields(0)):
+        assert (a > 0).any()
+        np.testing.assert_array_equal(a, b)
+    h.close()
+    fresh.close()
+
+
 def test_resident_depth_scene_is_rebuilt_not_reused_across_images(oracle_mod):
     """Two objects, one robot model (the driver's loop, examples/pybullet_gto_planning.py:160-300): the second object's
     fields come from another image.  A field of the FIRST object used after the second object's scene was built (its
