@@ -106,7 +106,7 @@ def pack_robot_desc(desc: RobotDesc, link_ee: str, link_gripper: str,
 # include/gto_solver.h
 GTO_GRAD_CENTRAL_DIFF, GTO_GRAD_ZERO = 0, 1
 GTO_STATUS_CONVERGED, GTO_STATUS_MAX_ITER, GTO_STATUS_NUMERICAL = 0, 1, 2
-ABI_VERSION = 1009  # include/gto_solver.h GTO_ABI_VERSION (checked against gto_version() when the library is loaded)
+ABI_VERSION = 1010  # include/gto_solver.h GTO_ABI_VERSION (checked against gto_version() when the library is loaded)
 
 _lib = None
 
@@ -224,7 +224,11 @@ def load_library(path: Optional[str] = None):
     _pu8 = C.POINTER(C.c_uint8)
     lib.gto_depth_sdf_cost.argtypes = [C.c_int, _pf, C.c_int32, C.c_int32, _pd, _pd, _pd, _pd, _pu8, C.c_double, _pd, C.c_int64,
                                        C.c_float, C.c_float, _pf, _pu8, _pf, _pd, _pu8]
-    for fn in ("gto_create", "gto_set_opts", "gto_set_scene", "gto_set_scene_values", "gto_drop_scene", "gto_solve_batch",
+    _i64 = C.c_int64
+    lib.gto_cloud_sdf_cost.argtypes = [C.c_int, _pd, _pd, _i64, C.c_int32, _pd, _i64, C.c_float, C.c_float, _pf, _pu8, _pf, _pi]
+    lib.gto_scene_from_clouds.argtypes = [H, C.c_int32, _pd, _pd, _i64, _i64, C.c_int32, C.c_double, C.c_double, C.c_float, C.c_float,
+                                          _pi, _pd, _pd]
+    for fn in ("gto_cloud_sdf_cost", "gto_scene_from_clouds", "gto_create", "gto_set_opts", "gto_set_scene", "gto_set_scene_values", "gto_drop_scene", "gto_solve_batch",
                "gto_solve_batch_device", "gto_last_kernel_time", "gto_last_kernel_work", "gto_set_profiling", "gto_set_stream", "gto_set_mode", "gto_set_lanes", "gto_set_lane_streams", "gto_share_scene",
                "gto_eval_fk", "gto_eval_points", "gto_eval_points_hessian", "gto_eval_objective", "gto_eval_obstacle_normal_eq", "gto_plan_cost", "gto_solve_ik_batch",
                "gto_solve_ik_pose_batch", "gto_solve_base_batch", "gto_eval_base_objective", "gto_depth_sdf_cost", "gto_retime_batch", "gto_retime_batch_device"):
@@ -241,6 +245,7 @@ EXPORTED_SYMBOLS = (
     "gto_eval_fk", "gto_eval_points", "gto_eval_points_hessian",
     "gto_eval_objective", "gto_eval_obstacle_normal_eq", "gto_plan_cost", "gto_solve_ik_batch", "gto_solve_ik_pose_batch",
     "gto_solve_base_batch", "gto_eval_base_objective", "gto_depth_sdf_cost", "gto_scene_from_depth", "gto_get_scene_fields",
+    "gto_cloud_sdf_cost", "gto_scene_from_clouds",
     "gto_retime_batch", "gto_retime_batch_device",
 )
 
@@ -346,6 +351,23 @@ class SolverHandle:
         self._check(self.lib.gto_scene_from_depth(self._h, scene_id, _p(depth, _pf), Hh, Ww, _p(K, _pd), _p(Kinv, _pd), _p(cam, _pd), _p(cinv, _pd),
                                                   None if mask is None else mask.ctypes.data_as(pu8), _p(dobs, _pf), float(threshold), float(grid_res), float(margin),
                                                   float(epsilon), float(w_inside), _p(shp, _pi), _p(org, _pd), _p(bnd, _pd)), "gto_scene_from_depth")
+        self.scenes[scene_id] = (tuple(int(x) for x in shp), org.copy(), float(grid_res))
+        self._bump(scene_id)
+        return tuple(int(x) for x in shp), org, np.stack((bnd[:3], bnd[3:]), axis=1)
+
+    def scene_from_clouds(self, scene_id: int, points, normals, n_obstacle=None, k=11, grid_res=0.05, margin=0.4, epsilon=0.02,
+                          w_inside=1.0):
+        """gto_scene_from_clouds: sampled meshes -> both cost fields resident as scene `scene_id`; the first `n_obstacle`
+        samples are the scene without the target object (None: all of them, one field used twice).  Returns (shape, origin,
+        bounds (3, 2)) of the grid, nothing else leaves the device."""
+        pts, nrm = _f64(points).reshape(-1, 3), _f64(normals).reshape(-1, 3)
+        if pts.shape != nrm.shape:
+            raise ValueError("points and normals must have the same shape")
+        n_all = pts.shape[0]
+        shp, org, bnd = np.zeros(3, np.int32), np.zeros(3), np.zeros(6)
+        self._check(self.lib.gto_scene_from_clouds(self._h, scene_id, _p(pts, _pd), _p(nrm, _pd), n_all, n_all if n_obstacle is None else int(n_obstacle),
+                                                   int(k), float(grid_res), float(margin), float(epsilon), float(w_inside), _p(shp, _pi), _p(org, _pd),
+                                                   _p(bnd, _pd)), "gto_scene_from_clouds")
         self.scenes[scene_id] = (tuple(int(x) for x in shp), org.copy(), float(grid_res))
         self._bump(scene_id)
         return tuple(int(x) for x in shp), org, np.stack((bnd[:3], bnd[3:]), axis=1)

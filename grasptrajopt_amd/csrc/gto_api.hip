@@ -22,6 +22,7 @@
 
 #include "gto_kernels.h"
 #include "gto_depth.h"
+#include "gto_cloud.h"
 #include "gto_retime.h"
 
 #define GTO_VERSION GTO_ABI_VERSION  // include/gto_solver.h
@@ -2655,6 +2656,194 @@ int gto_scene_from_depth(gto_handle* h, int32_t scene_id, const float* depth, in
     fprintf(stderr, "[gto] scene from depth (%d x %d image, %zu voxels), ms: alloc + upload %.3f | back-projection, hierarchies, bounds %.3f | queries, keys, sort %.3f | "
                     "two searches %.3f | records + distance fields %.3f | release %.3f | total %.3f\n",
             H, W, nq, t_[1] - t_[0], t_[2] - t_[1], t_[3] - t_[2], t_[4] - t_[3], t_[5] - t_[4], t_[6] - t_[5], t_[6] - t_[0]);
+  if (rc) return rc;
+  if (shape_out) std::memcpy(shape_out, shape, sizeof shape);
+  if (origin_out) std::memcpy(origin_out, origin, sizeof origin);
+  if (bounds_out) std::memcpy(bounds_out, root, sizeof root);
+  return GTO_OK;
+}
+
+
+// ------------------------------------------------------------------ cost field from a sampled mesh (gto_cloud.h)
+}  // extern "C"
+
+namespace {
+bool cloud_brute_force() {  // the exhaustive search (reference construction; the two are compared in a test)
+  const char* e = getenv("GTO_CLOUD_BRUTE");
+  return e && atoi(e) != 0;
+}
+bool cloud_stats() { return getenv("GTO_CLOUD_STATS") != nullptr; }
+
+// What both entry points check before any device work.  box_out: bounding box of the n samples (lo x y z, hi x y z).
+int check_cloud(gto_handle* h, const char* who, const double* points, const double* normals, int64_t n, int32_t k, double box_out[6]) {
+  const std::string w(who);
+  if (!points || !normals) return fail(h, GTO_ERR_INVALID_ARG, w + ": null points or normals");
+  if (k < 1 || k > GTO_CLOUD_MAX_K) return fail(h, GTO_ERR_INVALID_ARG, w + ": k must be in [1, 16]");
+  if (n < k) return fail(h, GTO_ERR_INVALID_ARG, w + ": fewer samples than k");
+  if (n > ((int64_t)1 << 28)) return fail(h, GTO_ERR_UNSUPPORTED, w + ": more than 2^28 samples");
+  for (int a = 0; a < 3; ++a) box_out[a] = INFINITY, box_out[3 + a] = -INFINITY;
+  for (int64_t i = 0; i < n; ++i)
+    for (int a = 0; a < 3; ++a) {
+      const double v = points[3 * i + a];
+      if (!std::isfinite(v) || !std::isfinite(normals[3 * i + a])) return fail(h, GTO_ERR_INVALID_ARG, w + ": non-finite point or normal");
+      box_out[a] = std::min(box_out[a], v), box_out[3 + a] = std::max(box_out[3 + a], v);
+    }
+  return GTO_OK;
+}
+
+// The samples d_points / d_normals [n][3] (device) as a SampleCloud; with `tree`, in key order under their hierarchy.
+// box: their bounding box (check_cloud).
+int make_sample_cloud(DepthLease& c, const double* d_points, const double* d_normals, int64_t n, const double box[6], bool tree, SampleCloud* cl) {
+  *cl = {d_points, d_normals, (unsigned)n, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr};
+  if (!tree) return GTO_OK;
+  // k_query_keys spreads its keys over a box grown by its own extent on every side (queries lie around a cloud): the
+  // samples lie within their box, so it is handed the middle third and the keys use all their bits
+  double kbox[6];
+  for (int a = 0; a < 3; ++a) {
+    const double third = (box[3 + a] - box[a]) / 3.0;
+    kbox[a] = box[a] + third, kbox[3 + a] = box[3 + a] - third;
+  }
+  const double* d_kbox;
+  DEPTH_TRY(c.upload(kbox, 6, &d_kbox));
+  DepthCloud keyed = {};
+  keyed.boxes = const_cast<double*>(d_kbox);
+  DepthQueries ps = {d_points, (long)n, nullptr};
+  DEPTH_TRY(sort_queries(c, keyed, &ps));
+  cl->n_leaves = cloud_leaf_slots((unsigned)n);
+  cl->n_slots = (unsigned)((n + GTO_CLOUD_LEAF - 1) / GTO_CLOUD_LEAF) * GTO_CLOUD_LEAF;
+  cl->px = c.alloc<double>((size_t)cl->n_slots * 3);
+  cl->pid = c.alloc<unsigned>(cl->n_slots);
+  cl->boxes = c.alloc<double>((size_t)2 * cl->n_leaves * 6);
+  if (!cl->px || !cl->pid || !cl->boxes) return c.no_memory();
+  cl->py = cl->px + cl->n_slots, cl->pz = cl->px + 2 * (size_t)cl->n_slots;
+  build_sample_tree(*cl, ps.order);
+  return c.hip(hipGetLastError());
+}
+}  // namespace
+
+extern "C" {
+
+int gto_cloud_sdf_cost(int device, const double* points, const double* normals, int64_t n, int32_t k, const double* query,
+                       int64_t nq, float epsilon, float w_inside, float* sdf_out, uint8_t* inside_out, float* cost_out,
+                       int32_t* nearest_out) {
+  double box[6];
+  if (int rc = check_cloud(nullptr, "gto_cloud_sdf_cost", points, normals, n, k, box)) return rc;
+  if (nq < 0 || (nq > 0 && !query)) return fail(nullptr, GTO_ERR_INVALID_ARG, "gto_cloud_sdf_cost: null or negative query count");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, GTO_ERR_NO_DEVICE, "no HIP device");
+  if (device >= 0 && hipSetDevice(device) != hipSuccess) return fail(nullptr, GTO_ERR_NO_DEVICE, "hipSetDevice failed");
+  if (nq == 0) return GTO_OK;
+  int cur_dev = 0;
+  (void)hipGetDevice(&cur_dev);
+  DepthLease c(nullptr, "gto_cloud_sdf_cost", cur_dev);
+  const double *d_points, *d_normals;
+  DepthQueries qs = {nullptr, (long)nq, nullptr};
+  DEPTH_TRY(c.upload(points, (size_t)n * 3, &d_points));
+  DEPTH_TRY(c.upload(normals, (size_t)n * 3, &d_normals));
+  DEPTH_TRY(c.upload(query, (size_t)nq * 3, &qs.q));
+  const CloudFields out = {c.alloc<float>((size_t)nq), c.alloc<uint8_t>((size_t)nq), c.alloc<float>((size_t)nq), c.alloc<int32_t>((size_t)nq)};
+  if (!out.sdf || !out.inside || !out.cost || !out.nearest) return c.no_memory();
+  const bool tree = !cloud_brute_force();
+  SampleCloud cl;
+  DEPTH_TRY(make_sample_cloud(c, d_points, d_normals, n, box, tree, &cl));
+  if (tree) {
+    DepthCloud rooted = {};
+    rooted.boxes = cl.boxes;
+    DEPTH_TRY(sort_queries(c, rooted, &qs));
+    search_cloud_tree(0, cl, k, qs, epsilon, w_inside, out);
+  } else {
+    search_cloud_exhaustive(0, cl, k, qs, epsilon, w_inside, out);
+  }
+  DEPTH_TRY(c.hip(hipGetLastError()));
+  DEPTH_TRY(c.hip(hipDeviceSynchronize()));
+  if (sdf_out) DEPTH_TRY(c.hip(hipMemcpy(sdf_out, out.sdf, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost)));
+  if (inside_out) DEPTH_TRY(c.hip(hipMemcpy(inside_out, out.inside, (size_t)nq, hipMemcpyDeviceToHost)));
+  if (cost_out) DEPTH_TRY(c.hip(hipMemcpy(cost_out, out.cost, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost)));
+  if (nearest_out) DEPTH_TRY(c.hip(hipMemcpy(nearest_out, out.nearest, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost)));
+  return GTO_OK;
+}
+
+/* include/gto_solver.h: gto_scene_from_depth's counterpart for sampled meshes.  The samples go up once through the handle's
+ * staging; the first n_obstacle of them are the second cloud.  One ordering of the voxel centres serves both searches. */
+int gto_scene_from_clouds(gto_handle* h, int32_t scene_id, const double* points, const double* normals, int64_t n_all,
+                          int64_t n_obstacle, int32_t k, double grid_res, double margin, float epsilon, float w_inside,
+                          int32_t* shape_out, double* origin_out, double* bounds_out) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (!(grid_res > 0) || !(margin >= 0)) return fail(h, GTO_ERR_INVALID_ARG, "gto_scene_from_clouds: grid_res must be > 0 and margin >= 0");
+  if (n_obstacle > n_all) return fail(h, GTO_ERR_INVALID_ARG, "gto_scene_from_clouds: n_obstacle must be <= n_all");
+  double root[6], box_o[6];
+  if (int rc = check_cloud(h, "gto_scene_from_clouds", points, normals, n_all, k, root)) return rc;
+  const bool two = n_obstacle != n_all;
+  if (two)
+    if (int rc = check_cloud(h, "gto_scene_from_clouds", points, normals, n_obstacle, k, box_o)) return rc;
+  std::vector<double> ax[3];
+  int32_t shape[3];
+  double origin[3];
+  size_t nq = 1;
+  for (int a = 0; a < 3; ++a) {
+    ax[a] = np_arange(root[a] - margin, root[3 + a] + margin, grid_res);
+    shape[a] = (int32_t)ax[a].size();
+    origin[a] = root[a] - margin;
+    nq *= ax[a].size();
+  }
+  if (nq == 0 || nq >= ((size_t)1 << 31)) return fail(h, GTO_ERR_UNSUPPORTED, "gto_scene_from_clouds: empty grid or more than 2^31 voxels");
+  HIPCHK(h, hipSetDevice(h->device));
+  const bool stats = cloud_stats();
+  auto t_now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  double t_[6] = {t_now(), 0, 0, 0, 0, 0};
+  Staging io(h);  // inputs only: nothing but the geometry returns
+  const double *d_points, *d_normals;
+  int rc;
+  if ((rc = io.in(points, (size_t)n_all * 3, &d_points))) return rc;
+  if ((rc = io.in(normals, (size_t)n_all * 3, &d_normals))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // the pipeline below runs on the null stream and two search streams
+  t_[1] = t_now();
+  DepthLease c(h, "gto_scene_from_clouds", h->device);
+  const bool tree = !cloud_brute_force();
+  SampleCloud all, obs;
+  DEPTH_TRY(make_sample_cloud(c, d_points, d_normals, n_all, root, tree, &all));
+  obs = all;
+  if (two) DEPTH_TRY(make_sample_cloud(c, d_points, d_normals, n_obstacle, box_o, tree, &obs));
+  if (stats) DEPTH_TRY(c.hip(hipDeviceSynchronize()));
+  t_[2] = t_now();
+  std::vector<double> axes(ax[0]);
+  axes.insert(axes.end(), ax[1].begin(), ax[1].end());
+  axes.insert(axes.end(), ax[2].begin(), ax[2].end());
+  const double* d_axes;
+  DEPTH_TRY(c.upload(axes.data(), axes.size(), &d_axes));
+  double* d_q = c.alloc<double>(nq * 3);
+  float* d_costa = c.alloc<float>(nq);
+  float* d_costo = two ? c.alloc<float>(nq) : d_costa;
+  if (!d_q || !d_costa || !d_costo) return c.no_memory();
+  hipLaunchKernelGGL(k_grid_queries, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, 0, d_axes, shape[0], shape[1], shape[2], d_q);
+  DepthQueries qs = {d_q, (long)nq, nullptr};
+  if (tree) {  // one key pass and one sort for both fields, over the root box of all samples
+    DepthCloud rooted = {};
+    rooted.boxes = all.boxes;
+    DEPTH_TRY(sort_queries(c, rooted, &qs));
+  }
+  hipStream_t sa = nullptr, sb = nullptr;
+  DEPTH_TRY(c.hip(depth_search_streams(h->device, &sa, &sb)));
+  DEPTH_TRY(c.hip(hipStreamSynchronize(0)));
+  t_[3] = t_now();
+  if (tree) {
+    search_cloud_tree(sa, all, k, qs, epsilon, w_inside, {nullptr, nullptr, d_costa, nullptr});
+    if (two) search_cloud_tree(sb, obs, k, qs, epsilon, w_inside, {nullptr, nullptr, d_costo, nullptr});
+  } else {
+    search_cloud_exhaustive(sa, all, k, qs, epsilon, w_inside, {nullptr, nullptr, d_costa, nullptr});
+    if (two) search_cloud_exhaustive(sb, obs, k, qs, epsilon, w_inside, {nullptr, nullptr, d_costo, nullptr});
+  }
+  DEPTH_TRY(c.hip(hipGetLastError()));
+  DEPTH_TRY(c.hip(hipDeviceSynchronize()));
+  t_[4] = t_now();
+  rc = set_scene_impl(h, scene_id, d_costa, two ? d_costo : nullptr, shape, origin, grid_res, false, hipMemcpyDeviceToDevice);
+  c.release();
+  t_[5] = t_now();
+  if (stats)
+    fprintf(stderr, "[gto] scene from clouds (%lld + %lld samples, k %d, %zu voxels, %s), ms: upload %.3f | sort + build %.3f | queries, keys, sort %.3f | "
+                    "search %.3f | records + distance fields %.3f | total %.3f\n",
+            (long long)n_all, (long long)(two ? n_obstacle : 0), (int)k, nq, tree ? "tree" : "exhaustive", t_[1] - t_[0], t_[2] - t_[1], t_[3] - t_[2],
+            t_[4] - t_[3], t_[5] - t_[4], t_[5] - t_[0]);
   if (rc) return rc;
   if (shape_out) std::memcpy(shape_out, shape, sizeof shape);
   if (origin_out) std::memcpy(origin_out, origin, sizeof origin);

@@ -75,6 +75,20 @@ __device__ __forceinline__ bool depth_is_outside(double q0, double q1, double q2
   return outside;
 }
 
+// The cost map of mesh_to_sdf/depth_point_cloud.py:84-89 for a signed distance `dist` (negative: inside).  The depth path
+// (depth_sdf_finish) and the sampled-mesh path (gto_cloud.h) both end in it.
+__device__ __forceinline__ float sdf_cost_map(float dist, bool inside, float epsilon, float w_inside) {
+#pragma clang fp contract(off)
+  float c = 0.0f;
+  if (inside) {
+    c = w_inside * (-dist + epsilon / 2.0f);
+  } else if (dist > 0.0f && dist < epsilon) {
+    const float e = dist - epsilon;
+    c = (e * e) / (2.0f * epsilon);
+  }
+  return c;
+}
+
 __device__ __forceinline__ void depth_sdf_finish(bool live, long q, double q0, double q1, double q2, double best,
                                                  const float* __restrict__ depth, int H, int W, const double* __restrict__ K,
                                                  const double* __restrict__ cam_inv, float epsilon, float w_inside,
@@ -97,13 +111,7 @@ __device__ __forceinline__ void depth_sdf_finish(bool live, long q, double q0, d
   bool outside = true;
   if (ix >= 0 && iy >= 0 && ix < W && iy < H) outside = pc[2] < (double)depth[iy * W + ix];
   if (!outside) dist = -dist;
-  float c = 0.0f;
-  if (!outside) {
-    c = w_inside * (-dist + epsilon / 2.0f);
-  } else if (dist > 0.0f && dist < epsilon) {
-    const float e = dist - epsilon;
-    c = (e * e) / (2.0f * epsilon);
-  }
+  const float c = sdf_cost_map(dist, !outside, epsilon, w_inside);
   if (sdf_out) sdf_out[q] = dist;
   if (inside_out) inside_out[q] = outside ? 0 : 1;
   if (cost_out) cost_out[q] = c;
@@ -189,9 +197,10 @@ __global__ void k_bvh_leaves(const double* __restrict__ px, const double* __rest
   double* b = boxes + (size_t)(P * P - 1 + s) * 6;
   for (int k = 0; k < 3; ++k) b[k] = lo[k], b[3 + k] = hi[k];
 }
-// inner nodes, level by level from the leaves up (one workgroup: 2 P^2 nodes are a few ten thousand)
-__global__ __launch_bounds__(1024) void k_bvh_up(int P, double* __restrict__ boxes) {
-  for (int first = (P * P - 1) / 2, count = P * P / 2; count >= 1; first = (first - 1) / 2, count >>= 1) {
+// inner nodes, level by level from the leaves up (one workgroup: twice the leaf slots are a few ten thousand nodes).
+// n_leaves: the leaf slots, a power of two (P x P for an image; gto_cloud.h builds its hierarchy over sorted samples with it)
+__global__ __launch_bounds__(1024) void k_bvh_up(int n_leaves, double* __restrict__ boxes) {
+  for (int first = (n_leaves - 1) / 2, count = n_leaves / 2; count >= 1; first = (first - 1) / 2, count >>= 1) {
     for (int i = threadIdx.x; i < count; i += 1024) {
       const int n = first + i;
       const double* a = boxes + (size_t)(2 * n + 1) * 6;
@@ -360,7 +369,7 @@ inline void build_cloud(const DepthCloud& cl, const DepthCamera& cam, const uint
   hipLaunchKernelGGL(k_depth_backproject, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, cl.depth, cl.H, cl.W, cam.Kinv, cam.pose, d_mask,
                      threshold, cl.px, cl.py, cl.pz, d_valid);
   if (P) hipLaunchKernelGGL(k_bvh_leaves, dim3((unsigned)((P * P + 255) / 256)), dim3(256), 0, 0, cl.px, cl.py, cl.pz, cl.H, cl.W, P, cl.boxes);
-  if (P > 1) hipLaunchKernelGGL(k_bvh_up, dim3(1), dim3(1024), 0, 0, P, cl.boxes);
+  if (P > 1) hipLaunchKernelGGL(k_bvh_up, dim3(1), dim3(1024), 0, 0, P * P, cl.boxes);
 }
 
 inline void search_tree(hipStream_t stream, const DepthCloud& cl, const DepthCamera& cam, const DepthQueries& qs, float epsilon, float w_inside,

@@ -200,6 +200,27 @@ class GTORobotModel:
         self.workspace_bounds = np.stack((points.min(0), points.max(0)), axis=1)
         self._setup_field(self.workspace_bounds[:, 0], self.workspace_bounds[:, 1])
 
+    def setup_clouds_field(self, cloud_obstacle, cloud_target=None, sample_count=11, epsilon=0.02, w_inside=1.0):
+        """setup_points_field for a scene given as sampled meshes (surface_point_cloud.SurfacePointCloud): the grid is the
+        bounding box of all samples + field_margin at grid_resolution (:155-171), and ONE gto_scene_from_clouds call leaves
+        ``sdf_cost_all`` (obstacles and target) and ``sdf_cost_obstacle`` (``cloud_obstacle`` alone) resident in the scene the
+        lazy depth fields use (depth_scene.DEPTH_SCENE), from where the planner, the IK solver and compute_plan_cost share
+        them.  Returns (sdf_cost_all, sdf_cost_obstacle); without a target they are one field."""
+        from .depth_scene import DEPTH_SCENE, Resident
+        from .surface_point_cloud import ResidentCloudField
+        pts, nrm = cloud_obstacle.points, cloud_obstacle.normals
+        if cloud_target is not None:
+            pts, nrm = np.concatenate([pts, cloud_target.points]), np.concatenate([nrm, cloud_target.normals])
+        h = self._util_handle()
+        shape, origin, bounds = h.scene_from_clouds(DEPTH_SCENE, pts, nrm, cloud_obstacle.points.shape[0], sample_count,
+                                                    self.grid_resolution, self.field_margin, epsilon, w_inside)
+        self._setup_field(bounds[:, 0], bounds[:, 1])
+        self.workspace_bounds = bounds
+        assert tuple(self.field_shape) == tuple(shape)
+        gen = h.scene_generation(DEPTH_SCENE)
+        f_all = ResidentCloudField(self, Resident(h, DEPTH_SCENE, 0, gen))
+        return f_all, (f_all if cloud_target is None else ResidentCloudField(self, Resident(h, DEPTH_SCENE, 1, gen)))
+
     def __getattr__(self, name):
         # only reached for attributes that are not set: the grid geometry while a depth cloud is pending
         if name in GTORobotModel._FIELD_ATTRS and self.__dict__.get("_pending_depth") is not None:

@@ -28,6 +28,7 @@ class UrdfLink:
     visual_rpy: List[float] = field(default_factory=lambda: [0.0, 0.0, 0.0])
     visual_mesh: Optional[str] = None
     visual_scale: List[float] = field(default_factory=lambda: [1.0, 1.0, 1.0])
+    visual_box: Optional[List[float]] = None  # <box size="x y z"> (object URDFs: surface_point_cloud.urdf_visual_meshes)
 
 
 @dataclass
@@ -81,6 +82,9 @@ class Urdf:
                 link.visual_mesh = mesh.get("filename")
                 if mesh.get("scale"):
                     link.visual_scale = _floats(mesh.get("scale"))
+            box = vis.find("geometry/box")
+            if box is not None:
+                link.visual_box = _floats(box.get("size"))
         return link
 
     @staticmethod

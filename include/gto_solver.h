@@ -119,7 +119,7 @@ void gto_default_opts(gto_solver_opts* opts);
 /* Library/ABI version (major*1000 + minor): GTO_ABI_VERSION of the header the library was built from.  A binding checks it
  * when it loads the library and refuses another number (grasptrajopt_amd/_capi.py load_library): every change of a
  * signature or of a struct in this header bumps the minor. */
-#define GTO_ABI_VERSION 1009
+#define GTO_ABI_VERSION 1010
 int32_t gto_version(void);
 
 /*
@@ -422,6 +422,35 @@ int gto_scene_from_depth(gto_handle* h, int32_t scene_id, const float* depth, in
                          const double* Kinv, const double* cam_pose, const double* cam_inv, const uint8_t* target_mask,
                          const float* depth_obstacle, double threshold, double grid_res, double margin, float epsilon,
                          float w_inside, int32_t* shape_out, double* origin_out, double* bounds_out);
+/*
+ * Cost field from a sampled triangle mesh: what the reference's SurfacePointCloud does with a KD-tree on the CPU
+ * (mesh_to_sdf/surface_point_cloud.py:16-64, the use_depth_buffer=False branch of get_sdf that
+ * mesh_to_sdf(..., surface_point_method='sample') takes, mesh_to_sdf/__init__.py:24-42).  Stand-alone (no handle): uses
+ * HIP device `device`.
+ *   points, normals [n][3]: surface samples and the normals of their faces; k: the reference's sample_count (11), 1..16
+ *   query [nq][3] world points
+ * Outputs (host; each may be NULL): sdf_out [nq] float32 distance to the nearest sample, negative where more than half
+ * of the k nearest samples see the query behind their face (:46-52); inside_out [nq] that vote; cost_out [nq] the cost
+ * map of mesh_to_sdf/depth_point_cloud.py:84-89 of that signed distance; nearest_out [nq] index of the nearest sample.
+ * Among samples at equal distance the lower index counts as nearer (the reference leaves ties open).  Bit-identical to
+ * the reference on tests/golden/surface_cloud.npz.  GTO_ERR_INVALID_ARG for n < k, k outside 1..16, non-finite samples.
+ */
+int gto_cloud_sdf_cost(int device, const double* points, const double* normals, int64_t n, int32_t k, const double* query,
+                       int64_t nq, float epsilon, float w_inside, float* sdf_out, uint8_t* inside_out, float* cost_out,
+                       int32_t* nearest_out);
+
+/*
+ * gto_scene_from_depth for furniture whose meshes are known: sampled meshes -> grid = bounding box of all samples +
+ * margin at grid_res (gto/gto_models.py:155-171; numpy.arange's values) -> sdf_cost_all from all n_all samples and
+ * sdf_cost_obstacle from the first n_obstacle of them (the scene without the target object) at the voxel centres
+ * (surface_point_cloud.py:32-64 + depth_point_cloud.py:84-89; bit-identical to two gto_cloud_sdf_cost calls) -> scene
+ * `scene_id` of the handle with its voxel records and distance fields.  n_obstacle == n_all: one field, used as both.
+ * Nothing but the geometry returns to the host: shape_out [3], origin_out [3], bounds_out [6] = (min x, y, z, max x, y, z)
+ * of all samples.
+ */
+int gto_scene_from_clouds(gto_handle* h, int32_t scene_id, const double* points, const double* normals, int64_t n_all,
+                          int64_t n_obstacle, int32_t k, double grid_res, double margin, float epsilon, float w_inside,
+                          int32_t* shape_out, double* origin_out, double* bounds_out);
 /* The two float32 cost fields of a resident scene, device to host (either pointer may be NULL). */
 int gto_get_scene_fields(gto_handle* h, int32_t scene_id, float* c_all_out, float* c_obs_out);
 
