@@ -8,6 +8,7 @@ GTOPlanner.plan()/plan_goalset().  Public surface:
     ik_solver_rpy.IKSolver               drop-in for gto.ik_solver_rpy (position + roll-pitch-yaw goals, on the GPU)
     DepthPointCloud                      drop-in for mesh_to_sdf.depth_point_cloud (cost fields on the GPU)
     SurfacePointCloud                    drop-in for mesh_to_sdf.surface_point_cloud (cost fields of sampled meshes on the GPU)
+    observation.Observation              a DepthPointCloud / SurfacePointCloud resident on the GPU + the collision checks against it
     BasePlanner                          drop-in for gto.base_planner (mobile base placement on the GPU)
     optas_facade                         OptimizationBuilder / CasADiSolver-shaped recorder + solver
     _capi.SolverHandle                   thin ctypes binding of the C ABI (include/gto_solver.h)
@@ -17,7 +18,8 @@ from .gto_planner import GTOPlanner  # noqa: F401
 from .ik_solver import IKSolver  # noqa: F401
 from .depth_point_cloud import DepthPointCloud  # noqa: F401
 from .surface_point_cloud import SurfacePointCloud  # noqa: F401
+from .observation import Observation  # noqa: F401
 from .base_planner import BasePlanner  # noqa: F401
 from .robot_desc import RobotDesc, load_builtin  # noqa: F401
 
-__all__ = ["GTORobotModel", "GTOPlanner", "IKSolver", "DepthPointCloud", "SurfacePointCloud", "BasePlanner", "RobotDesc", "load_builtin"]
+__all__ = ["GTORobotModel", "GTOPlanner", "IKSolver", "DepthPointCloud", "SurfacePointCloud", "Observation", "BasePlanner", "RobotDesc", "load_builtin"]

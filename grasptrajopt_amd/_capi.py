@@ -106,7 +106,7 @@ def pack_robot_desc(desc: RobotDesc, link_ee: str, link_gripper: str,
 # include/gto_solver.h
 GTO_GRAD_CENTRAL_DIFF, GTO_GRAD_ZERO = 0, 1
 GTO_STATUS_CONVERGED, GTO_STATUS_MAX_ITER, GTO_STATUS_NUMERICAL = 0, 1, 2
-ABI_VERSION = 1010  # include/gto_solver.h GTO_ABI_VERSION (checked against gto_version() when the library is loaded)
+ABI_VERSION = 1011  # include/gto_solver.h GTO_ABI_VERSION (checked against gto_version() when the library is loaded)
 
 _lib = None
 
@@ -228,6 +228,18 @@ def load_library(path: Optional[str] = None):
     lib.gto_cloud_sdf_cost.argtypes = [C.c_int, _pd, _pd, _i64, C.c_int32, _pd, _i64, C.c_float, C.c_float, _pf, _pu8, _pf, _pi]
     lib.gto_scene_from_clouds.argtypes = [H, C.c_int32, _pd, _pd, _i64, _i64, C.c_int32, C.c_double, C.c_double, C.c_float, C.c_float,
                                           _pi, _pd, _pd]
+    O = C.c_void_p  # gto_observation*
+    lib.gto_observation_from_depth.argtypes = [C.c_int, _pf, C.c_int32, C.c_int32, _pd, _pd, _pd, _pd, _pu8, C.c_double, C.POINTER(O)]
+    lib.gto_observation_from_cloud.argtypes = [C.c_int, _pd, _pd, _i64, C.c_int32, C.POINTER(O)]
+    lib.gto_observation_destroy.argtypes = [O]
+    lib.gto_observation_destroy.restype = None
+    lib.gto_observation_sdf.argtypes = [O, _pd, _i64, _pf, _pu8]
+    lib.gto_observation_check_posed.argtypes = [O, _pd, C.c_int32, _pd, C.c_int32, _pi]
+    lib.gto_check_plans.argtypes = [H, O, C.c_int32, _pd, _pd, C.c_int32, _pi]
+    lib.gto_check_plans_device.argtypes = [H, O, C.c_int32, C.c_void_p, _pd, C.c_int32, C.c_void_p, C.c_void_p]
+    for fn in ("gto_observation_from_depth", "gto_observation_from_cloud", "gto_observation_sdf", "gto_observation_check_posed", "gto_check_plans",
+               "gto_check_plans_device"):
+        getattr(lib, fn).restype = C.c_int
     for fn in ("gto_cloud_sdf_cost", "gto_scene_from_clouds", "gto_create", "gto_set_opts", "gto_set_scene", "gto_set_scene_values", "gto_drop_scene", "gto_solve_batch",
                "gto_solve_batch_device", "gto_last_kernel_time", "gto_last_kernel_work", "gto_set_profiling", "gto_set_stream", "gto_set_mode", "gto_set_lanes", "gto_set_lane_streams", "gto_share_scene",
                "gto_eval_fk", "gto_eval_points", "gto_eval_points_hessian", "gto_eval_objective", "gto_eval_obstacle_normal_eq", "gto_plan_cost", "gto_solve_ik_batch",
@@ -247,6 +259,8 @@ EXPORTED_SYMBOLS = (
     "gto_solve_base_batch", "gto_eval_base_objective", "gto_depth_sdf_cost", "gto_scene_from_depth", "gto_get_scene_fields",
     "gto_cloud_sdf_cost", "gto_scene_from_clouds",
     "gto_retime_batch", "gto_retime_batch_device",
+    "gto_observation_from_depth", "gto_observation_from_cloud", "gto_observation_destroy", "gto_observation_sdf",
+    "gto_observation_check_posed", "gto_check_plans", "gto_check_plans_device",
 )
 
 
@@ -639,6 +653,40 @@ class SolverHandle:
         self._check(self.lib.gto_plan_cost(self._h, scene_id, n, _p(plans, _pd), _p(base, _pd),
                                            _p(cost, _pd), _p(dist, _pd)), "gto_plan_cost")
         return cost, dist
+
+    # -------------------------------------------------------------- collision checks against a resident observation
+    def _check_base(self, base_pos, B):
+        """(host array, per_plan flag) of a base position (3,) or per-plan bases (B, 3)."""
+        base = _f64(base_pos)
+        if base.shape == (3,):
+            return base, 0
+        if base.shape != (B, 3):
+            raise GTOError(f"check_plans: base_pos must be (3,) or ({B}, 3), one base per plan; got {base.shape}")
+        return base, 1
+
+    def check_plans(self, obs, plans, base_pos=(0.0, 0.0, 0.0)):
+        """gto_check_plans: for plans (B, ndof, T) the number of the robot's surface points inside the observation ``obs``
+        (observation.Observation) at every waypoint, int32 (B, T); -1 where a waypoint holds a non-finite entry.
+        base_pos (3,) for all plans or (B, 3)."""
+        d, T = self.desc, self.T
+        plans = _f64(plans)
+        if plans.ndim != 3 or plans.shape[1:] != (d.ndof, T):
+            raise GTOError(f"check_plans: plans must have shape (B, {d.ndof}, {T}) -- ndof joints by the handle's horizon T = {T} "
+                           f"waypoints -- got {plans.shape}")
+        B = plans.shape[0]
+        base, per_plan = self._check_base(base_pos, B)
+        count = np.empty((B, T), dtype=np.int32)
+        self._check(self.lib.gto_check_plans(self._h, obs._ptr(), B, _p(plans, _pd), _p(base, _pd), per_plan, _p(count, _pi)),
+                    "gto_check_plans")
+        return count
+
+    def check_plans_device(self, obs, B, plans, count_out, base_pos=(0.0, 0.0, 0.0), stream=None):
+        """gto_check_plans_device: plans (B, ndof, T) float64 and count_out (B, T) int32 are device pointers (ints, e.g.
+        torch.Tensor.data_ptr()); enqueued on ``stream`` (None: the handle's) without a host synchronisation."""
+        base, per_plan = self._check_base(base_pos, int(B))
+        vp = lambda a: None if a is None else C.c_void_p(int(a))
+        self._check(self.lib.gto_check_plans_device(self._h, obs._ptr(), int(B), vp(plans), _p(base, _pd), per_plan, vp(count_out),
+                                                    vp(stream)), "gto_check_plans_device")
 
     # -------------------------------------------------------------- retiming
     def _retime_limits(self, vmax, amax):

@@ -24,6 +24,7 @@
 #include "gto_depth.h"
 #include "gto_cloud.h"
 #include "gto_retime.h"
+#include "gto_observe.h"
 
 #define GTO_VERSION GTO_ABI_VERSION  // include/gto_solver.h
 #ifndef GTO_OBS_DEEP_PD
@@ -214,6 +215,8 @@ struct gto_handle {
   // retiming (gto_retime_batch_device): Thomas factors of the not-a-knot system for this T, workspace grown on demand
   DevBuf rt_fac, rt_S, rt_flag, rt_P1, rt_P2, rt_cap, rt_X, rt_T, rt_stat;
   bool rt_fac_ready = false;
+  // collision checks against a cloud observation (gto_check_plans_device): world points, votes and per-plan bases of a chunk
+  DevBuf ck_xyz, ck_flags, ck_base;
 };
 
 #define HIPCHK(h, call)                                                                              \
@@ -796,7 +799,7 @@ void gto_destroy(gto_handle* h) {
   (void)hipFree(h->d_chunks);
   (void)hipFree(h->d_pbimg);
   DevBuf* bufs[] = {&h->zws, &h->counters, &h->state, &h->Qcur, &h->Qtry, &h->vis, &h->screw, &h->blocks, &h->goalblk, &h->ssfixed, &h->ndone, &h->qf, &h->livebuf, &h->qfs, &h->wrecbuf, &h->itembuf,
-                   &h->rt_fac, &h->rt_S, &h->rt_flag, &h->rt_P1, &h->rt_P2, &h->rt_cap, &h->rt_X, &h->rt_T, &h->rt_stat};
+                   &h->rt_fac, &h->rt_S, &h->rt_flag, &h->rt_P1, &h->rt_P2, &h->rt_cap, &h->rt_X, &h->rt_T, &h->rt_stat, &h->ck_xyz, &h->ck_flags, &h->ck_base};
   if (h->h_ndone) (void)hipHostFree(h->h_ndone);
   if (h->h_progress) (void)hipHostFree(h->h_progress);
   for (DevBuf* b : bufs) (void)hipFree(b->p);
@@ -2391,6 +2394,15 @@ struct DepthLease {
     for (auto& b : bufs) g_depth_pool.give(device, b.first, b.second);
     bufs.clear();
   }
+  // a buffer of this call that outlives it (a gto_observation takes it over and frees it itself)
+  void* keep(const void* p) {
+    for (size_t k = 0; k < bufs.size(); ++k)
+      if (bufs[k].first == p) {
+        bufs.erase(bufs.begin() + k);
+        return const_cast<void*>(p);
+      }
+    return nullptr;
+  }
   int no_memory() { return fail(h, GTO_ERR_ALLOC, std::string(who) + ": device allocation failed"); }
   int hip(hipError_t e) { return e == hipSuccess ? GTO_OK : fail(h, GTO_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
   // (the pool serves a request from the buffers of about its size that earlier calls gave back, first come first served: an
@@ -2980,6 +2992,258 @@ int gto_retime_batch(gto_handle* h, int32_t B, const double* plans, const double
   if ((rc = io.out(status_out, nB, &d_st))) return rc;
   rc = gto_retime_batch_device(h, B, d_plans, vmax, amax, subdiv, M, d_dur, d_t, d_sd, d_q, d_qd, d_qdd, d_st, nullptr);
   if (rc) return rc;
+  return io.finish();
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ a resident observation and the collision checks (gto_observe.h)
+struct gto_observation {
+  int device = 0;
+  bool is_depth = true;
+  std::vector<void*> owned;  // device buffers, freed by gto_observation_destroy
+  // depth: image, camera, world points, tile hierarchy (P = 0: none, exhaustive search)
+  DepthCloud depth = {};
+  DepthCamera cam = {};
+  // cloud: samples, normals, the samples in key order under their hierarchy (n_leaves = 0: none), the vote's k
+  SampleCloud cloud = {};
+  int k = 0;
+};
+
+namespace {
+void obs_adopt(gto_observation* o, DepthLease& c, std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (p && c.keep(p)) o->owned.push_back(const_cast<void*>(p));
+}
+ObsDepthView depth_view(const gto_observation* o) { return {o->depth.depth, o->depth.H, o->depth.W, o->cam.K, o->cam.inv}; }
+
+// the vote of the observation's k nearest samples for nq queries in the caller's order (neighbours as they come), on `st`
+void obs_cloud_votes(hipStream_t st, const gto_observation* o, const double* d_q, long nq, uint8_t* d_flags) {
+  const DepthQueries qs = {d_q, nq, nullptr};
+  const CloudFields out = {nullptr, d_flags, nullptr, nullptr};
+  if (o->cloud.n_leaves && !cloud_brute_force()) search_cloud_tree(st, o->cloud, o->k, qs, 0.0f, 0.0f, out);
+  else search_cloud_exhaustive(st, o->cloud, o->k, qs, 0.0f, 0.0f, out);
+}
+// queries of a cloud observation per launch chain of a check: bounds the workspace (25 bytes per query)
+constexpr long long kCheckChunkQueries = 1ll << 24;
+// waypoints per workgroup of k_check_plans: GTO_CHECK_TG in the environment (1 .. 4, read by every call; default 4, the
+// measured choice: DESIGN.md 7g).  Results do not depend on it.
+int check_waypoints_per_group() {
+  const char* e = getenv("GTO_CHECK_TG");
+  const int v = e ? atoi(e) : GTO_CHECK_TG;
+  return v >= 1 && v <= GTO_CHECK_TG ? v : GTO_CHECK_TG;
+}
+}  // namespace
+
+extern "C" {
+
+int gto_observation_from_depth(int device, const float* depth, int32_t H, int32_t W, const double* K, const double* Kinv,
+                               const double* cam_pose, const double* cam_inv, const uint8_t* target_mask, double threshold,
+                               gto_observation** out) {
+  if (out) *out = nullptr;
+  if (!out || !depth || !K || !Kinv || !cam_pose || !cam_inv || H < 1 || W < 1)
+    return fail(nullptr, GTO_ERR_INVALID_ARG, "gto_observation_from_depth: null or empty input");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, GTO_ERR_NO_DEVICE, "no HIP device");
+  if (device >= 0 && hipSetDevice(device) != hipSuccess) return fail(nullptr, GTO_ERR_NO_DEVICE, "hipSetDevice failed");
+  const size_t N = (size_t)H * W;
+  int cur_dev = 0;
+  (void)hipGetDevice(&cur_dev);
+  const int P = tile_levels(H, W);
+  const bool tree = P <= GTO_BVH_MAX_P;  // beyond: the exhaustive search, as gto_depth_sdf_cost
+  std::unique_ptr<gto_observation> o(new gto_observation);
+  o->device = cur_dev, o->is_depth = true;
+  DepthLease c(nullptr, "gto_observation_from_depth", cur_dev);
+  const float* d_depth;
+  const uint8_t* d_mask = nullptr;
+  DEPTH_TRY(c.upload(depth, N, &d_depth));
+  DEPTH_TRY(upload_camera(c, K, Kinv, cam_pose, cam_inv, &o->cam));
+  if (target_mask) DEPTH_TRY(c.upload(target_mask, N, &d_mask));
+  double* d_p = c.alloc<double>(3 * N);
+  uint8_t* d_valid = c.alloc<uint8_t>(N);
+  double* d_boxes = tree ? c.alloc<double>(bvh_box_doubles(P)) : nullptr;
+  if (!d_p || !d_valid || (tree && !d_boxes)) return c.no_memory();
+  o->depth = {d_depth, H, W, d_p, d_p + N, d_p + 2 * N, tree ? P : 0, d_boxes};
+  build_cloud(o->depth, o->cam, d_mask, threshold, d_valid);
+  DEPTH_TRY(c.hip(hipGetLastError()));
+  DEPTH_TRY(c.hip(hipDeviceSynchronize()));
+  obs_adopt(o.get(), c, {d_depth, o->cam.K, d_p, d_boxes});
+  *out = o.release();
+  return GTO_OK;
+}
+
+int gto_observation_from_cloud(int device, const double* points, const double* normals, int64_t n, int32_t k,
+                               gto_observation** out) {
+  if (out) *out = nullptr;
+  if (!out) return fail(nullptr, GTO_ERR_INVALID_ARG, "gto_observation_from_cloud: null output");
+  double box[6];
+  if (int rc = check_cloud(nullptr, "gto_observation_from_cloud", points, normals, n, k, box)) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, GTO_ERR_NO_DEVICE, "no HIP device");
+  if (device >= 0 && hipSetDevice(device) != hipSuccess) return fail(nullptr, GTO_ERR_NO_DEVICE, "hipSetDevice failed");
+  int cur_dev = 0;
+  (void)hipGetDevice(&cur_dev);
+  std::unique_ptr<gto_observation> o(new gto_observation);
+  o->device = cur_dev, o->is_depth = false, o->k = k;
+  DepthLease c(nullptr, "gto_observation_from_cloud", cur_dev);
+  const double *d_points, *d_normals;
+  DEPTH_TRY(c.upload(points, (size_t)n * 3, &d_points));
+  DEPTH_TRY(c.upload(normals, (size_t)n * 3, &d_normals));
+  DEPTH_TRY(make_sample_cloud(c, d_points, d_normals, n, box, !cloud_brute_force(), &o->cloud));
+  DEPTH_TRY(c.hip(hipGetLastError()));
+  DEPTH_TRY(c.hip(hipDeviceSynchronize()));
+  obs_adopt(o.get(), c, {d_points, d_normals, o->cloud.px, o->cloud.pid, o->cloud.boxes});
+  *out = o.release();
+  return GTO_OK;
+}
+
+void gto_observation_destroy(gto_observation* o) {
+  if (!o) return;
+  int cur = -1;
+  (void)hipGetDevice(&cur);
+  (void)hipSetDevice(o->device);
+  (void)hipDeviceSynchronize();  // nothing may still be reading it
+  for (void* p : o->owned) (void)hipFree(p);
+  if (cur >= 0) (void)hipSetDevice(cur);  // the caller's current device is the caller's
+  delete o;
+}
+
+int gto_observation_sdf(gto_observation* o, const double* query, int64_t nq, float* sdf_out, uint8_t* inside_out) {
+  if (!o || nq < 0 || (nq > 0 && !query)) return fail(nullptr, GTO_ERR_INVALID_ARG, "gto_observation_sdf: null observation or query");
+  if (nq == 0) return GTO_OK;
+  if (hipSetDevice(o->device) != hipSuccess) return fail(nullptr, GTO_ERR_NO_DEVICE, "hipSetDevice failed");
+  DepthLease c(nullptr, "gto_observation_sdf", o->device);
+  DepthQueries qs = {nullptr, (long)nq, nullptr};
+  DEPTH_TRY(c.upload(query, (size_t)nq * 3, &qs.q));
+  float* d_sdf = c.alloc<float>((size_t)nq);
+  uint8_t* d_in = c.alloc<uint8_t>((size_t)nq);
+  if (!d_sdf || !d_in) return c.no_memory();
+  if (o->is_depth) {
+    const DepthFields out = {d_sdf, d_in, nullptr};
+    if (o->depth.P && !depth_brute_force()) {
+      DEPTH_TRY(sort_queries(c, o->depth, &qs));
+      search_tree(0, o->depth, o->cam, qs, 0.0f, 0.0f, out, nullptr, false);
+    } else {
+      search_exhaustive(0, o->depth, o->cam, qs, 0.0f, 0.0f, out);
+    }
+  } else {
+    const CloudFields out = {d_sdf, d_in, nullptr, nullptr};
+    if (o->cloud.n_leaves && !cloud_brute_force()) {
+      DepthCloud rooted = {};
+      rooted.boxes = o->cloud.boxes;
+      DEPTH_TRY(sort_queries(c, rooted, &qs));
+      search_cloud_tree(0, o->cloud, o->k, qs, 0.0f, 0.0f, out);
+    } else {
+      search_cloud_exhaustive(0, o->cloud, o->k, qs, 0.0f, 0.0f, out);
+    }
+  }
+  DEPTH_TRY(c.hip(hipGetLastError()));
+  DEPTH_TRY(c.hip(hipDeviceSynchronize()));
+  if (sdf_out) DEPTH_TRY(c.hip(hipMemcpy(sdf_out, d_sdf, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost)));
+  if (inside_out) DEPTH_TRY(c.hip(hipMemcpy(inside_out, d_in, (size_t)nq, hipMemcpyDeviceToHost)));
+  return GTO_OK;
+}
+
+int gto_observation_check_posed(gto_observation* o, const double* points, int32_t P, const double* poses, int32_t n,
+                                int32_t* count_out) {
+  if (!o || P < 0 || n < 0 || (P > 0 && !points) || (n > 0 && !poses))
+    return fail(nullptr, GTO_ERR_INVALID_ARG, "gto_observation_check_posed: null observation, points or poses");
+  if (n == 0) return GTO_OK;
+  if (hipSetDevice(o->device) != hipSuccess) return fail(nullptr, GTO_ERR_NO_DEVICE, "hipSetDevice failed");
+  DepthLease c(nullptr, "gto_observation_check_posed", o->device);
+  const double *d_points, *d_poses;
+  DEPTH_TRY(c.upload(points, (size_t)P * 3, &d_points));
+  DEPTH_TRY(c.upload(poses, (size_t)n * 16, &d_poses));
+  int32_t* d_count = c.alloc<int32_t>((size_t)n);
+  if (!d_count) return c.no_memory();
+  if (o->is_depth) {
+    hipLaunchKernelGGL(k_check_posed<true>, dim3((unsigned)n), dim3(256), 0, 0, d_points, (int)P, d_poses, depth_view(o), (double*)nullptr, d_count);
+  } else {
+    const long long per = std::max<long long>(1, kCheckChunkQueries / std::max(1, (int)P));
+    const int chunk = (int)std::min<long long>(n, per);
+    double* d_xyz = c.alloc<double>((size_t)chunk * P * 3);
+    uint8_t* d_flags = c.alloc<uint8_t>((size_t)chunk * P);
+    if (!d_xyz || !d_flags) return c.no_memory();
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+      const int m = std::min(chunk, n - i0);
+      hipLaunchKernelGGL(k_check_posed<false>, dim3((unsigned)m), dim3(256), 0, 0, d_points, (int)P, d_poses + (size_t)i0 * 16, ObsDepthView{}, d_xyz,
+                         d_count + i0);
+      if (P) obs_cloud_votes(0, o, d_xyz, (long)m * P, d_flags);
+      hipLaunchKernelGGL(k_count_flags, dim3((unsigned)m), dim3(256), 0, 0, d_flags, (int)P, d_count + i0);
+    }
+  }
+  DEPTH_TRY(c.hip(hipGetLastError()));
+  DEPTH_TRY(c.hip(hipDeviceSynchronize()));
+  if (count_out) DEPTH_TRY(c.hip(hipMemcpy(count_out, d_count, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost)));
+  return GTO_OK;
+}
+
+int gto_check_plans_device(gto_handle* h, gto_observation* o, int32_t B, const double* plans, const double* base_pos,
+                           int32_t per_plan_base, int32_t* count_out, void* stream) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (!o || B < 0 || !base_pos) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_plans: null observation or base position");
+  if (o->device != h->device) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_plans: the observation lives on another device than the handle");
+  if (B == 0) return GTO_OK;
+  if (!plans) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_plans: null plans");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  const int T = h->opts.T, P = h->rb.n_points, ndof = h->rb.ndof;
+  const size_t lds = sizeof(double) * check_plans_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
+  if (lds > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the collision-check kernel's LDS");
+  const int tg = check_waypoints_per_group();
+  const unsigned tgroups = (unsigned)((T + tg - 1) / tg);
+  int rc;
+  const double* d_base = nullptr;
+  if (per_plan_base) {
+    // hipMemcpyAsync from pageable host memory returns once the array has been copied to the runtime's staging memory (the
+    // documented behaviour of the asynchronous copies for pageable memory): the caller's array is free on return, and the
+    // copy is ordered on `st` in front of the kernel.  ck_base is one buffer per handle: see the header on streams.
+    if ((rc = ensure(h, h->ck_base, (size_t)B * 3 * sizeof(double)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->ck_base.p, base_pos, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    d_base = (const double*)h->ck_base.p;
+  }
+  const double b0 = per_plan_base ? 0.0 : base_pos[0], b1 = per_plan_base ? 0.0 : base_pos[1], b2 = per_plan_base ? 0.0 : base_pos[2];
+  if (o->is_depth) {
+    HIPCHK(h, raise_dynamic_lds((const void*)k_check_plans<true>, lds));
+    if (count_out)
+      hipLaunchKernelGGL(k_check_plans<true>, dim3((unsigned)B, tgroups), dim3(256), lds, st, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_plink, T, tg, plans,
+                         b0, b1, b2, d_base, depth_view(o), (double*)nullptr, count_out);
+  } else if (count_out) {
+    HIPCHK(h, raise_dynamic_lds((const void*)k_check_plans<false>, lds));
+    const long long per = std::max<long long>(1, kCheckChunkQueries / ((long long)T * std::max(1, P)));
+    const int chunk = (int)std::min<long long>(B, per);
+    if ((rc = ensure(h, h->ck_xyz, (size_t)chunk * T * P * 3 * sizeof(double)))) return rc;
+    if ((rc = ensure(h, h->ck_flags, (size_t)chunk * T * P))) return rc;
+    double* d_xyz = (double*)h->ck_xyz.p;
+    uint8_t* d_flags = (uint8_t*)h->ck_flags.p;
+    for (int i0 = 0; i0 < B; i0 += chunk) {
+      const int m = std::min(chunk, B - i0);
+      int32_t* cnt = count_out + (size_t)i0 * T;
+      hipLaunchKernelGGL(k_check_plans<false>, dim3((unsigned)m, tgroups), dim3(256), lds, st, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_plink, T, tg,
+                         plans + (size_t)i0 * ndof * T, b0, b1, b2, d_base ? d_base + (size_t)i0 * 3 : nullptr, ObsDepthView{}, d_xyz, cnt);
+      if (P) obs_cloud_votes(st, o, d_xyz, (long)m * T * P, d_flags);
+      hipLaunchKernelGGL(k_count_flags, dim3((unsigned)(m * T)), dim3(256), 0, st, d_flags, P, cnt);
+    }
+  }
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
+}
+
+int gto_check_plans(gto_handle* h, gto_observation* o, int32_t B, const double* plans, const double* base_pos,
+                    int32_t per_plan_base, int32_t* count_out) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (!o || B < 0 || !base_pos) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_plans: null observation or base position");
+  if (o->device != h->device) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_plans: the observation lives on another device than the handle");
+  if (B == 0) return GTO_OK;
+  if (!plans) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_plans: null plans");
+  HIPCHK(h, hipSetDevice(h->device));
+  Staging io(h);
+  const double* d_plans;
+  int32_t* d_count;
+  int rc;
+  if ((rc = io.in(plans, (size_t)B * h->rb.ndof * h->opts.T, &d_plans))) return rc;
+  if ((rc = io.out(count_out, (size_t)B * h->opts.T, &d_count))) return rc;
+  if ((rc = gto_check_plans_device(h, o, B, d_plans, base_pos, per_plan_base, d_count, nullptr))) return rc;
   return io.finish();
 }
 

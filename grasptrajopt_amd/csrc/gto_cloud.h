@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void k_cloud_knn(const double* __restrict__ px
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const long slot = (long)blockIdx.x * 256 + tid;
   const bool live = slot < nq;
-  const long q = live ? (long)order[slot] : 0;
+  const long q = live ? (order ? (long)order[slot] : slot) : 0;  // no order: the caller's (queries that are neighbours as they come)
   const double q0 = live ? query[3 * q] : 0.0, q1 = live ? query[3 * q + 1] : 0.0, q2 = live ? query[3 * q + 2] : 0.0;
   CloudBest<KCAP> best;
   best.clear();

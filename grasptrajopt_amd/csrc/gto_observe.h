@@ -1,0 +1,190 @@
+// gto_observe.h — collision checks against a resident observation (gto_observation_*, gto_check_plans: include/gto_solver.h).
+// The grasp collision filter of the planning driver (examples/pybullet_gto_planning.py:203-221,
+// examples/pybullet_gto_planning_mobile.py:307-322) and the plan collision statistic of the offline evaluator
+// (examples/pybullet_evaluate_plans.py:219-233): surface points of the gripper / the robot are placed in the world and the
+// ones with get_sdf < 0 are counted.
+//
+// Depth observation.  get_sdf is the float32 distance to the cloud, negated where the point fails the visibility test
+// (mesh_to_sdf/depth_point_cloud.py:57-62, 127-141), so "get_sdf < 0" is "!is_outside" for every point that does not
+// coincide with a cloud point: the count needs no nearest-neighbour search.
+//   k_check_plans<true>   one workgroup per (plan, four waypoints): kinematics of the four configurations into LDS
+//                         (fk_mfma_tree, as k_eval_kin and k_plan_cost), lanes over the surface points in the handle's
+//                         per-link order, depth_is_outside (gto_depth.h) per point, ballot + popcount per wave, the four
+//                         waves' counts through LDS, one store per waypoint
+//   k_check_posed<true>   one workgroup per pose: x = R p + t without contraction, the products added in the order
+//                         numpy.einsum("nij,pj->npi") adds them (x, z, y) before the translation; the same counting
+// Cloud observation (sampled mesh).  The sign is the vote of the k nearest samples' normals, so there is a search:
+//   k_check_plans<false> / k_check_posed<false>  write the world points [item][P][3] instead of counting (and mark the
+//                         items with a non-finite entry); consecutive points belong to one link at one waypoint, so the 64
+//                         queries of a wave are neighbours in space and k_cloud_knn's packet walk (gto_cloud.h) takes them
+//                         in this order, without keys and without a sort
+//   k_count_flags         one workgroup per item: the P votes of k_cloud_knn summed (ballot + popcount, LDS across waves)
+// An item (waypoint or pose) with a non-finite entry reports -1; its kinematics run on zeros, so nothing non-finite enters
+// a matrix-core product or a search.
+#pragma once
+#include "gto_cloud.h"
+
+// what depth_is_outside reads of a depth observation (all pointers: device)
+struct ObsDepthView {
+  const float* depth;
+  int H, W;
+  const double *K, *cam_inv;
+};
+
+#define GTO_CHECK_TG GTO_PLAN_TG  // most waypoints per workgroup of k_check_plans (the LDS layout is k_plan_cost's)
+__host__ __device__ inline int check_plans_lds_doubles(int F, int L, int n) { return plan_cost_lds_doubles(F, L, n); }
+
+// sum over the workgroup's four waves of a wave-uniform count per group g < TG; s_cnt: [4][TG] ints of LDS
+template <int TG>
+__device__ __forceinline__ void check_counts_to_lds(const int (&cnt)[TG], int tid, int* s_cnt) {
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int g = 0; g < TG; ++g) s_cnt[(tid >> 6) * TG + g] = cnt[g];
+  }
+}
+
+// plans [nplans][ndof][T]; tg: waypoints per workgroup, 1..GTO_CHECK_TG (grid.y = ceil(T / tg); results do not depend on
+// it: every waypoint's kinematics are a matrix-core block of their own); base: (b0, b1, b2) for every plan, or base_pp [nplans][3].  DEPTH: count_out [nplans][T].
+// !DEPTH: xyz_out [nplans][T][P][3] and count_out [nplans][T] = -1 for a waypoint with a non-finite entry, else 0.
+// The world point is k_eval_points' expression, term for term (gto_kernels.h): the same bits as gto_eval_points' xyz_out.
+template <bool DEPTH>
+__global__ __launch_bounds__(256) void k_check_plans(const RobotDev* __restrict__ rb, const double* __restrict__ px,
+                                                     const double* __restrict__ py, const double* __restrict__ pz,
+                                                     const int32_t* __restrict__ plink, int T, int tg, const double* __restrict__ plans,
+                                                     double b0, double b1, double b2, const double* __restrict__ base_pp,
+                                                     ObsDepthView dv, double* __restrict__ xyz_out,
+                                                     int32_t* __restrict__ count_out) {
+  constexpr int TG = GTO_CHECK_TG;
+  const int i = blockIdx.x, t0 = blockIdx.y * tg, tid = threadIdx.x;  // tg <= TG waypoints per workgroup (GTO_CHECK_TG)
+  const int F = rb->n_frames, L = rb->n_links, n = rb->n_opt, ndof = rb->ndof, P = rb->n_points;
+  const int ng = min(tg, T - t0);
+  extern __shared__ __attribute__((aligned(16))) double smem_ck[];
+  double* s_tab = smem_ck;
+  double* s_sc = s_tab + fk_tab_doubles(F, L, n);  // [TG][F][2]
+  double* s_X = s_sc + TG * F * 2;
+  double* s_vis = s_X + fk_scratch_doubles(F, TG);  // [TG][L][12]
+  double* s_screw = s_vis + TG * L * 12;            // (by-product of the kinematics, unused here)
+  int* s_cnt = reinterpret_cast<int*>(s_screw + TG * screw_rows(n) * 6);  // [4][TG]
+  int* s_bad = s_cnt + 4 * TG;                                             // [TG]
+  const int nt = fk_tab_doubles(F, L, n);
+  for (int k = tid; k < nt; k += 256) s_tab[k] = rb->fk_tab[k];
+  if (tid < TG) s_bad[tid] = 0;
+  __syncthreads();
+  for (int idx = tid; idx < ng * ndof; idx += 256) {
+    const int kq = idx / ndof, j = idx - kq * ndof;
+    if (!isfinite(plans[((size_t)i * ndof + j) * T + t0 + kq])) s_bad[kq] = 1;
+  }
+  __syncthreads();
+  for (int idx = tid; idx < ng * F; idx += 256) {
+    const int kq = idx / F, f = idx - kq * F;
+    const int jt = rb->joint_type[f], dq = rb->q_index[f];
+    double a = 0.0, cs = 1.0;
+    if (dq >= 0 && !s_bad[kq]) {
+      const double qv = plans[((size_t)i * ndof + dq) * T + t0 + kq];
+      if (jt == GTO_JOINT_REVOLUTE) sincos(qv, &a, &cs);
+      else if (jt == GTO_JOINT_PRISMATIC) a = qv;
+    }
+    s_sc[2 * idx] = a;
+    s_sc[2 * idx + 1] = cs;
+  }
+  __syncthreads();
+  fk_mfma_tree(rb, s_tab, ng, s_sc, s_X, reinterpret_cast<int*>(s_X + ng * 32 * F + 64), tid, s_vis, s_screw, nullptr, screw_rows(n));
+  __syncthreads();
+  if (base_pp) b0 = base_pp[3 * (size_t)i], b1 = base_pp[3 * (size_t)i + 1], b2 = base_pp[3 * (size_t)i + 2];
+  const bool base_ok = isfinite(b0) && isfinite(b1) && isfinite(b2);
+  int cnt[TG];
+#pragma unroll
+  for (int g = 0; g < TG; ++g) cnt[g] = 0;
+  for (int p0 = 0; p0 < P; p0 += 256) {  // uniform trip count: every lane takes part in the ballots
+    const int p = p0 + tid;
+    const bool live = p < P;
+    const double x0 = live ? px[p] : 0.0, x1 = live ? py[p] : 0.0, x2 = live ? pz[p] : 0.0;
+    const int l = live ? plink[p] : 0;
+#pragma unroll
+    for (int g = 0; g < TG; ++g) {
+      if (g < ng) {
+        const double* V = s_vis + (g * L + l) * 12;
+        const double X0 = V[0] * x0 + V[1] * x1 + V[2] * x2 + V[3] + b0;
+        const double X1 = V[4] * x0 + V[5] * x1 + V[6] * x2 + V[7] + b1;
+        const double X2 = V[8] * x0 + V[9] * x1 + V[10] * x2 + V[11] + b2;
+        if constexpr (DEPTH) {
+          const bool in = live && !depth_is_outside(X0, X1, X2, dv.depth, dv.H, dv.W, dv.K, dv.cam_inv);
+          cnt[g] += __popcll(__ballot(in));
+        } else if (live) {
+          double* o = xyz_out + (((size_t)i * T + t0 + g) * P + p) * 3;
+          const bool ok = base_ok && !s_bad[g];
+          o[0] = ok ? X0 : 0.0, o[1] = ok ? X1 : 0.0, o[2] = ok ? X2 : 0.0;
+        }
+      }
+    }
+  }
+  if constexpr (DEPTH) {
+    check_counts_to_lds<TG>(cnt, tid, s_cnt);
+    __syncthreads();
+    if (tid < ng)
+      count_out[(size_t)i * T + t0 + tid] =
+          (s_bad[tid] || !base_ok) ? -1 : ((s_cnt[tid] + s_cnt[TG + tid]) + s_cnt[2 * TG + tid]) + s_cnt[3 * TG + tid];
+  } else {
+    if (tid < ng) count_out[(size_t)i * T + t0 + tid] = (s_bad[tid] || !base_ok) ? -1 : 0;
+  }
+}
+
+// points [P][3] in the frame the poses place (the open gripper's surface points in the gripper frame), poses [n][16]
+// row-major 4x4.  DEPTH: count_out [n].  !DEPTH: xyz_out [n][P][3] and count_out [n] = -1 for a non-finite pose, else 0.
+template <bool DEPTH>
+__global__ __launch_bounds__(256) void k_check_posed(const double* __restrict__ points, int P, const double* __restrict__ poses,
+                                                     ObsDepthView dv, double* __restrict__ xyz_out,
+                                                     int32_t* __restrict__ count_out) {
+#pragma clang fp contract(off)  // numpy's products and sums, one rounding each
+  __shared__ int s_cnt[4];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  const double* M = poses + 16 * (size_t)i;
+  bool bad = false;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) bad = bad || !isfinite(M[e]);  // uniform: every lane reads the same sixteen values
+  if (bad) {
+    if (tid == 0) count_out[i] = -1;
+    if constexpr (DEPTH) return;
+  }
+  int cnt = 0;
+  for (int p0 = 0; p0 < P; p0 += 256) {
+    const int p = p0 + tid;
+    const bool live = p < P;
+    const double x0 = live ? points[3 * (size_t)p] : 0.0, x1 = live ? points[3 * (size_t)p + 1] : 0.0,
+                 x2 = live ? points[3 * (size_t)p + 2] : 0.0;
+    // numpy.einsum("nij,pj->npi") adds the three products of a row in the order x, z, y (numpy 2.2's unrolled inner loop):
+    // utils.grasp_collision_ratio's bits, which tests/test_gpu_observation.py compares with
+    const double X0 = ((M[0] * x0 + M[2] * x2) + M[1] * x1) + M[3];
+    const double X1 = ((M[4] * x0 + M[6] * x2) + M[5] * x1) + M[7];
+    const double X2 = ((M[8] * x0 + M[10] * x2) + M[9] * x1) + M[11];
+    if constexpr (DEPTH) {
+      const bool in = live && !depth_is_outside(X0, X1, X2, dv.depth, dv.H, dv.W, dv.K, dv.cam_inv);
+      cnt += __popcll(__ballot(in));
+    } else if (live) {
+      double* o = xyz_out + ((size_t)i * P + p) * 3;
+      o[0] = bad ? 0.0 : X0, o[1] = bad ? 0.0 : X1, o[2] = bad ? 0.0 : X2;
+    }
+  }
+  if constexpr (DEPTH) {
+    if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
+    __syncthreads();
+    if (tid == 0) count_out[i] = ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3];
+  } else {
+    if (tid == 0 && !bad) count_out[i] = 0;
+  }
+}
+
+// count[item] = number of non-zero flags among flags[item][P]; an item marked -1 keeps its mark
+__global__ __launch_bounds__(256) void k_count_flags(const uint8_t* __restrict__ flags, int P, int32_t* __restrict__ count) {
+  __shared__ int s_cnt[4];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  if (count[i] < 0) return;  // uniform
+  int cnt = 0;
+  for (int p0 = 0; p0 < P; p0 += 256) {
+    const int p = p0 + tid;
+    cnt += __popcll(__ballot(p < P && flags[(size_t)i * P + p] != 0));
+  }
+  if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
+  __syncthreads();
+  if (tid == 0) count[i] = ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3];
+}

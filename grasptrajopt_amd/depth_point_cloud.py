@@ -96,3 +96,15 @@ class DepthPointCloud:
     def is_outside(self, points):
         """:126-141."""
         return ~self._run(points)[1]
+
+    def observation(self):
+        """This cloud resident on the device (observation.Observation), built on first use and kept: image, camera,
+        back-projected points and tile hierarchy stay there for sdf / check_posed / check_plans.  It is a snapshot of the
+        arrays as they are now; build a new DepthPointCloud for a new image."""
+        from .observation import Observation
+        o = self.__dict__.get("_observation")
+        if o is None or o.closed:
+            o = Observation.from_depth(self.depth, self.intrinsic_matrix, self.camera_pose, self.target_mask, self.threshold,
+                                       self.device, Kinv=self._Kinv, cam_inv=self._cam_inv)
+            self._observation = o
+        return o

@@ -99,6 +99,16 @@ class SurfacePointCloud:
             voxels = np.pad(voxels, 1, mode="constant", constant_values=1)
         return voxels
 
+    def observation(self, sample_count=11):
+        """This cloud resident on the device (observation.Observation) for the vote of ``sample_count`` neighbours, built on
+        first use and kept: samples, normals and their hierarchy stay there for sdf / check_posed / check_plans."""
+        from .observation import Observation
+        cache = self.__dict__.setdefault("_observations", {})
+        o = cache.get(int(sample_count))
+        if o is None or o.closed:
+            o = cache[int(sample_count)] = Observation.from_cloud(self.points, self.normals, int(sample_count), self.device)
+        return o
+
     def nearest_sample(self, query_points, sample_count=11):
         """Index of the nearest sample of every query (the lower index among samples at equal distance)."""
         return self._run(query_points, sample_count)[3]

@@ -257,3 +257,54 @@ def make_base_goal_sets(desc, fk: Callable[[np.ndarray], np.ndarray], link_ee: s
         q[:, oi] = np.clip(qc[oi] + rng.uniform(-spread, spread, size=(n, len(oi))), lo, hi)
         goals[b] = Binv @ np.asarray(fk(q))[:, fe]
     return goals, ystar
+
+
+# ---------------------------------------------------------------------- inputs of the collision checks (observation.py)
+def wall_scene(H=480, W=640, cam_xyz=(-0.9, 0.0, 0.5)):
+    """The fixture's scene at the driver's image size: a camera behind the robot looking along +x at a wall 1.45 m away with
+    a box 0.2 m in front of it; a block of invalid pixels, a strip beyond the threshold, a masked target."""
+    s = H / 120.0
+    K = np.array([[150.0 * s, 0, 80.0 * s], [0, 150.0 * s, 60.0 * s], [0, 0, 1.0]])
+    cam = np.eye(4)
+    cam[:3, :3] = np.array([[0, 0, 1.0], [-1.0, 0, 0], [0, -1.0, 0]])
+    cam[:3, 3] = cam_xyz
+    depth = np.full((H, W), 1.45, dtype=np.float32)
+    depth[int(42 * s):int(78 * s), int(56 * s):int(104 * s)] = 1.25
+    depth[int(110 * s):, 0:int(20 * s)] = 0.0
+    depth[:, int(150 * s):] = 2.0
+    rng = np.random.default_rng(5)
+    depth += (rng.uniform(-0.004, 0.004, size=depth.shape) * (depth > 0)).astype(np.float32)  # no two pixels alike
+    mask = np.zeros((H, W), dtype=np.uint8)
+    mask[int(50 * s):int(60 * s), int(70 * s):int(80 * s)] = 1
+    return depth, K, cam, mask
+
+
+def start_pose(desc, cfg):
+    pose = np.array(cfg["default_pose"], dtype=np.float64)
+    return np.concatenate([np.zeros(desc.ndof - len(pose)), pose])
+
+
+def random_plans(desc, cfg, B, T=50, seed=0, reach=1.2):
+    """Default pose -> a random configuration of the optimised joints, straight in joint space (as the fixture's)."""
+    rng = np.random.default_rng(seed)
+    qc = start_pose(desc, cfg)
+    opt = np.asarray(desc.opt_index)
+    lo, hi = np.maximum(desc.lower[opt], qc[opt] - reach), np.minimum(desc.upper[opt], qc[opt] + reach)
+    plans = np.tile(qc[None, :, None], (B, 1, T))
+    for b in range(B):
+        qg = rng.uniform(lo, hi)
+        plans[b, opt, :] = qc[opt, None] + (qg - qc[opt])[:, None] * np.linspace(0.0, 1.0, T)[None, :]
+    return plans
+
+
+def grasp_poses(n, seed, x=(-0.3, 0.4)):
+    """Placements of a gripper model whose points are given in the robot's base frame at its default pose: a small turn
+    about z and a shift, from well in front of the obstacles to deep inside them."""
+    rng = np.random.default_rng(seed)
+    RT = np.tile(np.eye(4), (n, 1, 1))
+    for i in range(n):
+        a = rng.uniform(-0.2, 0.2)
+        c, s = np.cos(a), np.sin(a)
+        RT[i, :3, :3] = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1.0]])
+        RT[i, :3, 3] = [rng.uniform(*x), rng.uniform(-0.1, 0.1), rng.uniform(-0.05, 0.1)]
+    return RT

@@ -124,8 +124,37 @@ def filter_grasps(gripper_model, depth_pc, RT_grasps, q_gripper, RT_offset=None,
     return (grasp_collision_ratio(gripper_model, depth_pc, RT_grasps, q_gripper, RT_offset) > threshold).astype(np.int32)
 
 
+def plans_in_collision(robot, cloud_or_obs, plans, base_position=(0.0, 0.0, 0.0), max_points: int = 5, is_mobile: bool = False):
+    """plan_in_collision for a batch, against a resident observation (observation.Observation, or the cached one of a
+    DepthPointCloud / SurfacePointCloud): plans (B, ndof, T) or one plan (ndof, T); base_position (3,) or one per plan (B, 3),
+    ignored with is_mobile (examples/pybullet_evaluate_plans.py:224-227).  Kinematics, visibility test (or k-nearest vote)
+    and counting run on the GPU (gto_check_plans); only the counts come back.  Returns (in_collision (B,) bool,
+    first colliding waypoint (B,) or -1, points in collision (B, T) int32; -1 marks a waypoint with a non-finite entry)."""
+    from .observation import as_observation
+    plans = np.asarray(plans, dtype=np.float64)
+    if plans.ndim == 2:
+        plans = plans[None]
+    base = np.zeros(3) if is_mobile else np.asarray(base_position, dtype=np.float64)
+    counts = _retime_handle(robot, plans.shape[-1]).check_plans(as_observation(cloud_or_obs), plans, base)
+    over = counts > max_points
+    hit = over.any(axis=1)
+    return hit, np.where(hit, over.argmax(axis=1), -1), counts
+
+
+def grasp_collision_counts(gripper_model, cloud_or_obs, RT_grasps, q_gripper, RT_offset=None):
+    """grasp_collision_ratio against a resident observation: the open gripper's surface points are placed at every
+    ``RT_grasp @ RT_offset`` and tested on the GPU (gto_observation_check_posed); only the counts come back.  Returns
+    (counts (n,) int32, P): counts / P is grasp_collision_ratio's value, and the driver rejects counts / P > 0.01."""
+    from .observation import as_observation
+    RT = np.asarray(RT_grasps, dtype=np.float64).reshape(-1, 4, 4)
+    if RT_offset is not None:
+        RT = RT @ np.asarray(RT_offset, dtype=np.float64)
+    pts, _ = gripper_model.compute_fk_surface_points(q_gripper)  # gripper frame, (P, 3)
+    return as_observation(cloud_or_obs).check_posed(pts, RT), int(pts.shape[0])
+
+
 def _retime_handle(robot, T: int):
-    """The robot's utility handle for horizon T (retiming only reads the handle's T and ndof)."""
+    """The robot's utility handle for horizon T (retiming and the plan checks only read the handle's T and the robot)."""
     from . import _capi
     o = _capi.default_opts()
     o.T = int(T)

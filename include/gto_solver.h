@@ -119,7 +119,7 @@ void gto_default_opts(gto_solver_opts* opts);
 /* Library/ABI version (major*1000 + minor): GTO_ABI_VERSION of the header the library was built from.  A binding checks it
  * when it loads the library and refuses another number (grasptrajopt_amd/_capi.py load_library): every change of a
  * signature or of a struct in this header bumps the minor. */
-#define GTO_ABI_VERSION 1010
+#define GTO_ABI_VERSION 1011
 int32_t gto_version(void);
 
 /*
@@ -453,6 +453,73 @@ int gto_scene_from_clouds(gto_handle* h, int32_t scene_id, const double* points,
                           int32_t* shape_out, double* origin_out, double* bounds_out);
 /* The two float32 cost fields of a resident scene, device to host (either pointer may be NULL). */
 int gto_get_scene_fields(gto_handle* h, int32_t scene_id, float* c_all_out, float* c_obs_out);
+
+/*
+ * ---- a resident observation and the collision checks against it -----------------------------------
+ * The reference keeps what it observed alive as an object: DepthPointCloud owns its KD-tree
+ * (mesh_to_sdf/depth_point_cloud.py:25) and is asked many times -- by the grasp collision filter
+ * (examples/pybullet_gto_planning.py:203-221, examples/pybullet_gto_planning_mobile.py:307-322) and by the plan collision
+ * statistic (examples/pybullet_evaluate_plans.py:219-233).  A gto_observation is that object on the device: it owns its
+ * device memory until gto_observation_destroy, is bound to one HIP device and is independent of any handle or scene.
+ * Errors of the calls below that take no handle are read with gto_last_error(NULL).
+ *
+ * gto_observation_from_depth: arguments and meaning of gto_depth_sdf_cost.  Keeps the image, the camera matrices, the
+ * back-projected points and the hierarchy over their 8 x 4 pixel tiles.
+ * gto_observation_from_cloud: arguments and meaning of gto_cloud_sdf_cost (k: the sample_count of the vote, 1..16).  Keeps
+ * the samples, their normals and the hierarchy over the Morton-sorted samples.
+ * Both validate in the order of those entry points (GTO_ERR_INVALID_ARG before GTO_ERR_NO_DEVICE).
+ */
+typedef struct gto_observation gto_observation;
+int gto_observation_from_depth(int device, const float* depth, int32_t height, int32_t width, const double* K,
+                               const double* Kinv, const double* cam_pose, const double* cam_inv, const uint8_t* target_mask,
+                               double threshold, gto_observation** out);
+int gto_observation_from_cloud(int device, const double* points, const double* normals, int64_t n, int32_t k,
+                               gto_observation** out);
+void gto_observation_destroy(gto_observation* obs);
+
+/*
+ * Queries.  Pointer outputs may be NULL; a count of zero items returns GTO_OK without a launch; every item's result is bit
+ * for bit the same in any batch and at any position in it.
+ *
+ * "Inside", the property the checks count, per kind of observation:
+ *   depth   !is_outside (mesh_to_sdf/depth_point_cloud.py:127-141): the point projects into the image and is not in front
+ *           of the surface seen at its pixel.  No nearest-neighbour search is made.
+ *   cloud   more than half of the k nearest samples see the point behind their face (mesh_to_sdf/surface_point_cloud.py:46-52).
+ * This equals the reference's `get_sdf < 0` (depth_point_cloud.py:57-62) except for a query that coincides with a cloud
+ * point: there the reference yields -0, which is not below zero, and the checks here still count the point.
+ *
+ * gto_observation_sdf: get_sdf (sdf_out [nq] float32) and !is_outside / the vote (inside_out [nq]) at world points
+ * query [nq][3]: the bits of gto_depth_sdf_cost / gto_cloud_sdf_cost on the same inputs (ties to the lower index), with the
+ * upload and the build already paid.
+ */
+int gto_observation_sdf(gto_observation* obs, const double* query, int64_t nq, float* sdf_out, uint8_t* inside_out);
+/*
+ * The grasp collision filter (pybullet_gto_planning.py:203-221): points [P][3] (the open gripper's surface points in the
+ * frame the poses place) at poses [n][16] (row-major 4x4), x = R_i p + t_i in FP64 without contraction, the products of
+ * a row added in the order numpy.einsum("nij,pj->npi") adds them ((R_i0 p_0 + R_i2 p_2) + R_i1 p_1, numpy 2.2) before the
+ * translation: the bits of utils.grasp_collision_ratio's placed points.  count_out [n]: how many of the P
+ * points are inside (the driver rejects count / P > 0.01); -1 for a pose with a non-finite entry, which changes no other
+ * count.
+ */
+int gto_observation_check_posed(gto_observation* obs, const double* points, int32_t P, const double* poses, int32_t n,
+                                int32_t* count_out);
+/*
+ * The plan collision statistic (pybullet_evaluate_plans.py:219-233): plans [B][ndof][T] (T: the handle's horizon).  The
+ * world surface points x = visual_tf(q_t) p + base come from the device kinematics behind gto_eval_points and are bit-equal
+ * to its xyz_out.  count_out [B][T]: how many of the handle's P surface points are inside at waypoint t of plan b (the
+ * evaluator calls a plan colliding when some waypoint has more than 5); -1 for a waypoint (or a base) with a non-finite
+ * entry, which changes no other count.  base_pos: HOST array in both variants, [3] (per_plan_base == 0) or [B][3]; zeros
+ * reproduce the evaluator's is_mobile branch.  `obs` on another device than the handle's: GTO_ERR_INVALID_ARG.
+ * gto_check_plans_device: plans and count_out in device memory, enqueued on `stream` (NULL = the handle's stream) without a
+ * host synchronisation: it takes the Q_out of gto_solve_batch_device on the same stream as it is.  The per-plan bases and
+ * (cloud observation) the world points and votes of a call live in one workspace per handle: calls on one handle go to one
+ * stream, or the caller orders them (a handle is not thread-safe, and its calls are not stream-safe against each other).
+ * GTO_CLOUD_BRUTE (the exhaustive search of gto_cloud_sdf_cost) holds for the votes of every query above as well.
+ */
+int gto_check_plans(gto_handle* h, gto_observation* obs, int32_t B, const double* plans, const double* base_pos,
+                    int32_t per_plan_base, int32_t* count_out);
+int gto_check_plans_device(gto_handle* h, gto_observation* obs, int32_t B, const double* plans, const double* base_pos,
+                           int32_t per_plan_base, int32_t* count_out, void* stream);
 
 /*
  * Retiming: B plans [B, ndof, T] (T = the handle's horizon; e.g. the Q_out of gto_solve_batch_device) turned into
