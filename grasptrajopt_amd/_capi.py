@@ -106,7 +106,7 @@ def pack_robot_desc(desc: RobotDesc, link_ee: str, link_gripper: str,
 # include/gto_solver.h
 GTO_GRAD_CENTRAL_DIFF, GTO_GRAD_ZERO = 0, 1
 GTO_STATUS_CONVERGED, GTO_STATUS_MAX_ITER, GTO_STATUS_NUMERICAL = 0, 1, 2
-ABI_VERSION = 1011  # include/gto_solver.h GTO_ABI_VERSION (checked against gto_version() when the library is loaded)
+ABI_VERSION = 1012  # include/gto_solver.h GTO_ABI_VERSION (checked against gto_version() when the library is loaded)
 
 _lib = None
 
@@ -237,6 +237,11 @@ def load_library(path: Optional[str] = None):
     lib.gto_observation_check_posed.argtypes = [O, _pd, C.c_int32, _pd, C.c_int32, _pi]
     lib.gto_check_plans.argtypes = [H, O, C.c_int32, _pd, _pd, C.c_int32, _pi]
     lib.gto_check_plans_device.argtypes = [H, O, C.c_int32, C.c_void_p, _pd, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.gto_solve_ik_pose_batch_device.argtypes = [H, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 5
+    lib.gto_ik_report_device.argtypes = [H, C.c_int32] + [C.c_void_p] * 4 + [C.c_double] * 3 + [C.c_void_p] * 5
+    lib.gto_seed_goalsets_device.argtypes = [H, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32, C.c_int32] + [C.c_void_p] * 8
+    for fn in ("gto_solve_ik_pose_batch_device", "gto_ik_report_device", "gto_seed_goalsets_device"):
+        getattr(lib, fn).restype = C.c_int
     for fn in ("gto_observation_from_depth", "gto_observation_from_cloud", "gto_observation_sdf", "gto_observation_check_posed", "gto_check_plans",
                "gto_check_plans_device"):
         getattr(lib, fn).restype = C.c_int
@@ -261,6 +266,7 @@ EXPORTED_SYMBOLS = (
     "gto_retime_batch", "gto_retime_batch_device",
     "gto_observation_from_depth", "gto_observation_from_cloud", "gto_observation_destroy", "gto_observation_sdf",
     "gto_observation_check_posed", "gto_check_plans", "gto_check_plans_device",
+    "gto_solve_ik_pose_batch_device", "gto_ik_report_device", "gto_seed_goalsets_device",
 )
 
 
@@ -610,6 +616,36 @@ class SolverHandle:
                                                      _p(status, _pi)),
                     "gto_solve_ik_pose_batch")
         return q, cost, iters, status
+
+    # -------------------------------------------------------------- the stream-ordered chain (grasp_chain.GraspChain)
+    def solve_ik_pose_batch_device(self, kind, B, scene_id, q0, goals, base_pos, max_iter, q_out, cost_out=None,
+                                   iters_out=None, status_out=None, stream=None):
+        """gto_solve_ik_pose_batch_device: all arrays are device pointers (ints, e.g. torch.Tensor.data_ptr()) or None;
+        scene_id None = no collision term (base_pos may then be None)."""
+        vp = lambda a: None if a is None else C.c_void_p(int(a))
+        self._check(self.lib.gto_solve_ik_pose_batch_device(self._h, int(kind), int(B), vp(scene_id), vp(q0), vp(goals),
+                                                            vp(base_pos), int(max_iter), vp(q_out), vp(cost_out), vp(iters_out),
+                                                            vp(status_out), vp(stream)), "gto_solve_ik_pose_batch_device")
+
+    def ik_report_device(self, B, scene_id, q, goals, base_pos, pos_tol, rot_tol_deg, cost_tol, err_pos_out=None,
+                         err_rot_out=None, cost_out=None, accept_out=None, stream=None):
+        """gto_ik_report_device: err_pos, err_rot (degrees), collision cost and the acceptance flag (uint8) of B IK solutions;
+        device pointers or None."""
+        vp = lambda a: None if a is None else C.c_void_p(int(a))
+        self._check(self.lib.gto_ik_report_device(self._h, int(B), vp(scene_id), vp(q), vp(goals), vp(base_pos), float(pos_tol),
+                                                  float(rot_tol_deg), float(cost_tol), vp(err_pos_out), vp(err_rot_out),
+                                                  vp(cost_out), vp(accept_out), vp(stream)), "gto_ik_report_device")
+
+    def seed_goalsets_device(self, B, n_max, scene_id, qc, goals, n_goals, q_solutions, accept, base_pos, interpolate,
+                             solutions_f32, goals_out=None, n_goals_out=None, n_accepted_out=None, Q0_out=None,
+                             seed_index_out=None, seed_cost_out=None, seed_dist_out=None, stream=None):
+        """gto_seed_goalsets_device: accepted goal sets, seed scores, the chosen seed; device pointers or None."""
+        vp = lambda a: None if a is None else C.c_void_p(int(a))
+        self._check(self.lib.gto_seed_goalsets_device(self._h, int(B), int(n_max), vp(scene_id), vp(qc), vp(goals), vp(n_goals),
+                                                      vp(q_solutions), vp(accept), vp(base_pos), int(bool(interpolate)),
+                                                      int(bool(solutions_f32)), vp(goals_out), vp(n_goals_out),
+                                                      vp(n_accepted_out), vp(Q0_out), vp(seed_index_out), vp(seed_cost_out),
+                                                      vp(seed_dist_out), vp(stream)), "gto_seed_goalsets_device")
 
     def solve_base_batch(self, qc, goals, n_goals=None, effort_weight=0.01, max_iter=100):
         """Base placement for B goal sets (gto/base_planner.py:35-123): qc (B,ndof), goals (B,n_max,4,4).

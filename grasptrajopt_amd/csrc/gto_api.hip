@@ -25,6 +25,7 @@
 #include "gto_cloud.h"
 #include "gto_retime.h"
 #include "gto_observe.h"
+#include "gto_seed.h"
 
 #define GTO_VERSION GTO_ABI_VERSION  // include/gto_solver.h
 #ifndef GTO_OBS_DEEP_PD
@@ -217,6 +218,8 @@ struct gto_handle {
   bool rt_fac_ready = false;
   // collision checks against a cloud observation (gto_check_plans_device): world points, votes and per-plan bases of a chunk
   DevBuf ck_xyz, ck_flags, ck_base;
+  // seed choice (gto_seed_goalsets_device): per-waypoint cost sums of the candidates [B][n_max][T]
+  DevBuf sd_part;
 };
 
 #define HIPCHK(h, call)                                                                              \
@@ -799,7 +802,7 @@ void gto_destroy(gto_handle* h) {
   (void)hipFree(h->d_chunks);
   (void)hipFree(h->d_pbimg);
   DevBuf* bufs[] = {&h->zws, &h->counters, &h->state, &h->Qcur, &h->Qtry, &h->vis, &h->screw, &h->blocks, &h->goalblk, &h->ssfixed, &h->ndone, &h->qf, &h->livebuf, &h->qfs, &h->wrecbuf, &h->itembuf,
-                   &h->rt_fac, &h->rt_S, &h->rt_flag, &h->rt_P1, &h->rt_P2, &h->rt_cap, &h->rt_X, &h->rt_T, &h->rt_stat, &h->ck_xyz, &h->ck_flags, &h->ck_base};
+                   &h->rt_fac, &h->rt_S, &h->rt_flag, &h->rt_P1, &h->rt_P2, &h->rt_cap, &h->rt_X, &h->rt_T, &h->rt_stat, &h->ck_xyz, &h->ck_flags, &h->ck_base, &h->sd_part};
   if (h->h_ndone) (void)hipHostFree(h->h_ndone);
   if (h->h_progress) (void)hipHostFree(h->h_progress);
   for (DevBuf* b : bufs) (void)hipFree(b->p);
@@ -1940,15 +1943,43 @@ static IkKernel ik_kernel(int kind) {
   return k[kind];
 }
 
+// The launch of k_ik_solve<kind> over B instances whose arrays are on the device, on stream st: what the host-pointer and
+// the device-pointer entry points share
+static int ik_launch(gto_handle* h, int kind, int32_t B, const int32_t* d_sid, const double* d_q0, const double* d_goals,
+                     const double* d_base, int32_t max_iter, double* d_q, double* d_cost, int32_t* d_it, int32_t* d_stat,
+                     hipStream_t st) {
+  SolveParams sp = make_params(h, 1, false);
+  sp.max_iter = max_iter;
+  const size_t lds = (size_t)ik_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt) * sizeof(double);
+  if (lds > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the IK kernel's LDS");
+  const IkKernel kern = ik_kernel(kind);
+  HIPCHK(h, raise_dynamic_lds((const void*)kern, lds));
+  hipLaunchKernelGGL(kern, dim3(B), dim3(256), lds, st, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes,
+                     d_sid, d_q0, d_goals, d_base, sp, B, d_q, d_cost, d_it, d_stat, (int)h->scenes.size());
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
+}
+
+// the checks of every IK entry point that need no array's contents; GTO_OK with *empty set for B == 0
+static int ik_check(gto_handle* h, const char* name, int32_t B, int32_t max_iter, bool null_input, bool* empty) {
+  *empty = false;
+  if (B < 0 || max_iter < 0) return fail(h, GTO_ERR_INVALID_ARG, "B and max_iter must be >= 0");
+  if (B == 0) {
+    *empty = true;
+    return GTO_OK;
+  }
+  if (null_input) return fail(h, GTO_ERR_INVALID_ARG, "null input array");
+  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, std::string(name) + " handles up to eight optimised joints");
+  return GTO_OK;
+}
+
 // gto_solve_ik_batch and gto_solve_ik_pose_batch: goals of one kind, gw doubles each; `name` speaks in the messages
 static int ik_batch(gto_handle* h, const char* name, int kind, size_t gw, int32_t B, const int32_t* scene_id,
                     const double* q0, const double* goals, const double* base_pos, int32_t max_iter, double* q_out,
                     double* cost_out, int32_t* iters_out, int32_t* status_out) {
-  if (B < 0 || max_iter < 0) return fail(h, GTO_ERR_INVALID_ARG, "B and max_iter must be >= 0");
-  if (B == 0) return GTO_OK;
-  if (!q0 || !goals || !q_out) return fail(h, GTO_ERR_INVALID_ARG, "null input array");
-  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, std::string(name) + " handles up to eight optimised joints");
-  int rc;
+  bool empty;
+  int rc = ik_check(h, name, B, max_iter, !q0 || !goals || !q_out, &empty);
+  if (rc || empty) return rc;
   if (scene_id && (rc = check_scene_ids_host(h, scene_id, B))) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   const size_t ndof = h->rb.ndof;
@@ -1970,15 +2001,7 @@ static int ik_batch(gto_handle* h, const char* name, int kind, size_t gw, int32_
   if ((rc = io.out(cost_out, B, &d_cost))) return rc;
   if ((rc = io.out(iters_out, B, &d_it))) return rc;
   if ((rc = io.out(status_out, B, &d_stat))) return rc;
-  SolveParams sp = make_params(h, 1, false);
-  sp.max_iter = max_iter;
-  const size_t lds = (size_t)ik_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt) * sizeof(double);
-  if (lds > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the IK kernel's LDS");
-  const IkKernel kern = ik_kernel(kind);
-  HIPCHK(h, raise_dynamic_lds((const void*)kern, lds));
-  hipLaunchKernelGGL(kern, dim3(B), dim3(256), lds, h->stream, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes,
-                     d_sid, d_q0, d_goals, d_base, sp, B, d_q, d_cost, d_it, d_stat);
-  HIPCHK(h, hipGetLastError());
+  if ((rc = ik_launch(h, kind, B, d_sid, d_q0, d_goals, d_base, max_iter, d_q, d_cost, d_it, d_stat, h->stream))) return rc;
   return io.finish();
 }
 
@@ -2000,6 +2023,72 @@ int gto_solve_ik_pose_batch(gto_handle* h, int32_t goal_kind, int32_t B, const i
     return gto_solve_ik_batch(h, B, scene_id, q0, goals, base_pos, max_iter, q_out, cost_out, iters_out, status_out);
   return ik_batch(h, "gto_solve_ik_pose_batch", goal_kind, goal_kind == GTO_IK_GOAL_QUATERNION ? 7 : 6, B, scene_id, q0,
                   goals, base_pos, max_iter, q_out, cost_out, iters_out, status_out);
+}
+
+int gto_solve_ik_pose_batch_device(gto_handle* h, int32_t goal_kind, int32_t B, const int32_t* scene_id, const double* q0,
+                                   const double* goals, const double* base_pos, int32_t max_iter, double* q_out,
+                                   double* cost_out, int32_t* iters_out, int32_t* status_out, void* stream) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (goal_kind != GTO_IK_GOAL_POINTS && goal_kind != GTO_IK_GOAL_QUATERNION && goal_kind != GTO_IK_GOAL_RPY)
+    return fail(h, GTO_ERR_INVALID_ARG, "unknown IK goal kind");
+  bool empty;
+  const int rc = ik_check(h, "gto_solve_ik_pose_batch_device", B, max_iter, !q0 || !goals || !q_out, &empty);
+  if (rc || empty) return rc;
+  if (scene_id && !base_pos) return fail(h, GTO_ERR_INVALID_ARG, "gto_solve_ik_pose_batch_device: scene_id needs base_pos");
+  HIPCHK(h, hipSetDevice(h->device));
+  return ik_launch(h, goal_kind, B, scene_id, q0, goals, scene_id ? base_pos : nullptr, max_iter, q_out, cost_out, iters_out,
+                   status_out, stream ? (hipStream_t)stream : h->stream);
+}
+
+int gto_ik_report_device(gto_handle* h, int32_t B, const int32_t* scene_id, const double* q, const double* goals,
+                         const double* base_pos, double pos_tol, double rot_tol_deg, double cost_tol, double* err_pos_out,
+                         double* err_rot_out, double* cost_out, uint8_t* accept_out, void* stream) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (B < 0) return fail(h, GTO_ERR_INVALID_ARG, "gto_ik_report_device: B must be >= 0");
+  if (B == 0) return GTO_OK;
+  if (!q || !goals) return fail(h, GTO_ERR_INVALID_ARG, "gto_ik_report_device: null input array");
+  if (scene_id && !base_pos) return fail(h, GTO_ERR_INVALID_ARG, "gto_ik_report_device: scene_id needs base_pos");
+  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, "gto_ik_report_device handles up to eight optimised joints");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t lds = sizeof(double) * plan_cost_lds_doubles_tg(1, h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
+  if (lds > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the report kernel's LDS");
+  HIPCHK(h, raise_dynamic_lds((const void*)k_ik_report, lds));
+  hipLaunchKernelGGL(k_ik_report, dim3(B), dim3(256), lds, stream ? (hipStream_t)stream : h->stream, h->d_rb, h->d_px, h->d_py,
+                     h->d_pz, h->d_plink, h->d_scenes, (int)h->scenes.size(), scene_id, q, goals, base_pos, pos_tol, rot_tol_deg,
+                     cost_tol, err_pos_out, err_rot_out, cost_out, accept_out);
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
+}
+
+int gto_seed_goalsets_device(gto_handle* h, int32_t B, int32_t n_max, const int32_t* scene_id, const double* qc,
+                             const double* goals, const int32_t* n_goals, const double* q_solutions, const uint8_t* accept,
+                             const double* base_pos, int32_t interpolate, int32_t solutions_f32, double* goals_out,
+                             int32_t* n_goals_out, int32_t* n_accepted_out, double* Q0_out, int32_t* seed_index_out,
+                             double* seed_cost_out, double* seed_dist_out, void* stream) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (B < 0 || n_max < 1) return fail(h, GTO_ERR_INVALID_ARG, "gto_seed_goalsets_device: B must be >= 0 and n_max >= 1");
+  if (B == 0) return GTO_OK;
+  if (!scene_id || !qc || !goals || !n_goals || !q_solutions || !base_pos)
+    return fail(h, GTO_ERR_INVALID_ARG, "gto_seed_goalsets_device: null input array");
+  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, "gto_seed_goalsets_device handles up to eight optimised joints");
+  if (n_max > 65535 || B > 65535) return fail(h, GTO_ERR_UNSUPPORTED, "gto_seed_goalsets_device: at most 65535 instances of at most 65535 goals in one call");
+  if (h->scenes.empty()) return fail(h, GTO_ERR_NO_SCENE, "no scene has been set");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  const int T = h->opts.T;
+  int rc;
+  if ((rc = ensure(h, h->sd_part, (size_t)B * n_max * T * sizeof(double)))) return rc;
+  const size_t lds = sizeof(double) * plan_cost_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
+  if (lds > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the seed-score kernel's LDS");
+  HIPCHK(h, raise_dynamic_lds((const void*)k_seed_score, lds));
+  hipLaunchKernelGGL(k_seed_score, dim3((unsigned)((T + GTO_PLAN_TG - 1) / GTO_PLAN_TG), n_max, B), dim3(256), lds, st, h->d_rb,
+                     h->d_px, h->d_py, h->d_pz, h->d_plink, h->d_scenes, (int)h->scenes.size(), scene_id, qc, n_goals,
+                     q_solutions, accept, base_pos, T, n_max, solutions_f32 != 0, (double*)h->sd_part.p);
+  hipLaunchKernelGGL(k_seed_select, dim3(B), dim3(64), 0, st, h->d_rb, qc, goals, n_goals, q_solutions, accept,
+                     (const double*)h->sd_part.p, T, T + h->opts.standoff_offset, n_max, interpolate != 0, solutions_f32 != 0,
+                     goals_out, n_goals_out, n_accepted_out, Q0_out, seed_index_out, seed_cost_out, seed_dist_out);
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
 }
 
 // gto_solve_base_batch and gto_eval_base_objective after their own B check; `null_input`: one of the arrays the entry point

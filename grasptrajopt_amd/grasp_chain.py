@@ -1,0 +1,209 @@
+"""GraspChain — the per-object loop of the reference's driver (examples/pybullet_gto_planning.py:242-294) on one stream:
+
+    grasp poses -> IK (gto_solve_ik_pose_batch_device) -> err_pos / err_rot / collision cost and the acceptance test of :262
+    (gto_ik_report_device) -> accepted goal sets and seeds (gto_seed_goalsets_device) -> gto_solve_batch_device ->
+    optionally gto_check_plans_device and gto_retime_batch_device
+
+for many objects at once, with ONE host synchronisation at the end.  ``IKSolver.solve_ik_batch`` + the filter on the host +
+``GTOPlanner.plan_goalset`` compute the same thing object by object with a host round trip between the steps; the plans
+are bit-equal (the same seed and goals go into the same solve).
+"""
+from __future__ import annotations
+
+from types import SimpleNamespace
+
+import numpy as np
+
+from . import _capi
+from .synthetic import standoff_pose
+
+
+class GraspChain:
+    def __init__(self, robot, link_ee, link_gripper, standoff_distance=-0.1, standoff_offset=-10, device=0):
+        import torch
+        self.robot, self.link_ee, self.link_gripper = robot, link_ee, link_gripper
+        self.standoff_distance, self.standoff_offset = standoff_distance, standoff_offset
+        self.T = 50            # gto/gto_planner.py:25
+        self.Tmax = 10.0       # :26
+        self.max_iter = 100    # :141
+        self.ik_max_iter = 50  # gto/ik_solver.py:76
+        opts = _capi.default_opts()
+        dt = self.Tmax / (self.T - 1)
+        opts.T, opts.Tmax, opts.standoff_offset = self.T, dt * (self.T - 1), standoff_offset  # (GTOPlanner's horizon, bit for bit)
+        opts.w_obstacle, opts.w_vel, opts.max_iter = 10.0, 0.01, self.max_iter  # :114,:130 and gto/ik_solver.py:70
+        self._handle = _capi.SolverHandle(robot.desc, link_ee, link_gripper, opts, device=device)
+        self._torch = torch
+        self.device = torch.device("cuda", device)
+        self.stream = torch.cuda.Stream(device=self.device)
+        self._handle.set_stream(self.stream.cuda_stream)
+        self._buf = {}
+
+    def close(self):
+        if self._handle is not None:
+            self._torch.cuda.synchronize(self.device)
+            self._handle.close()
+            self._handle = None
+            self._buf = {}
+
+    # ------------------------------------------------------------------ scenes
+    def bind_scene(self, sid, sdf_cost_all, sdf_cost_obstacle):
+        """Scene ``sid`` of the chain's handle from a pair of cost fields: two fields of one resident scene
+        (depth_scene.LazyCostField) are shared in as ``IKSolver._bind_scene`` shares them, arrays are uploaded.  A scene
+        that is bound stays: ``plan_objects`` takes its id in place of a pair of fields."""
+        from .depth_scene import resident_of
+        h = self._handle
+        ro, ra = resident_of(sdf_cost_obstacle), resident_of(sdf_cost_all)  # the obstacle field first: its build holds both fields
+        if ro is not None and ra is not None and ra.handle is ro.handle and (ra.sid, ra.gen) == (ro.sid, ro.gen):
+            # (shared again on every call: a later build of the resident scene leaves no stale pointer behind)
+            h.share_scene(sid, ro.handle, ro.sid, all_from=ra.half, obs_from=ro.half)
+        else:
+            shape, origin, res = self.robot.field_geometry()
+            h.set_scene(sid, np.asarray(sdf_cost_all), np.asarray(sdf_cost_obstacle), shape, origin, res)
+        return sid
+
+    def _scene_ids(self, fields, B):
+        """Scene id of every object: ``fields`` is one entry for all objects or one per object; an entry is the id of a bound
+        scene or a pair (sdf_cost_all, sdf_cost_obstacle); objects that name the same pair share one scene."""
+        one = isinstance(fields, (int, np.integer)) or (isinstance(fields, tuple) and len(fields) == 2 and not isinstance(fields[0], tuple))
+        entries = [fields] * B if one else list(fields)
+        if len(entries) != B:
+            raise ValueError(f"fields: one entry for all objects or one per object ({B}), got {len(entries)}")
+        taken = {int(e) for e in entries if isinstance(e, (int, np.integer))}
+        ids, seen, nxt = [], {}, 0
+        for e in entries:
+            if isinstance(e, (int, np.integer)):
+                ids.append(int(e))
+                continue
+            key = (id(e[0]), id(e[1]))
+            if key not in seen:
+                while nxt in taken:
+                    nxt += 1
+                seen[key] = self.bind_scene(nxt, e[0], e[1])
+                taken.add(nxt)
+            ids.append(seen[key])
+        return np.asarray(ids, dtype=np.int32)
+
+    # ------------------------------------------------------------------ buffers
+    def _dev(self, name, shape, dtype):
+        """A device buffer of the chain, kept between calls while the shape stays."""
+        t = self._buf.get(name)
+        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+            t = self._torch.empty(tuple(shape), dtype=dtype, device=self.device)
+            self._buf[name] = t
+        return t
+
+    def _pin(self, name, shape, dtype):
+        """A pinned host buffer of the chain (a call ends with a synchronisation: nothing is in flight when it is reused)."""
+        t = self._buf.get("pin/" + name)
+        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+            t = self._torch.empty(tuple(shape), dtype=dtype, pin_memory=True)
+            self._buf["pin/" + name] = t
+        return t
+
+    def _up(self, name, array, dtype):
+        """Host array -> the chain's device buffer of that name, through pinned memory, enqueued on the current stream."""
+        src = self._torch.from_numpy(np.require(array, dtype=dtype, requirements=["C", "W"]))  # (a read-only view is copied)
+        pin = self._pin(name, src.shape, src.dtype)
+        pin.copy_(src)
+        dst = self._dev(name, src.shape, src.dtype)
+        dst.copy_(pin, non_blocking=True)
+        return dst
+
+    # ------------------------------------------------------------------ the chain
+    def plan_objects(self, qc, ik_goals, plan_goals, n_grasps, fields, base_position, axis_standoff="x", use_standoff=True,
+                     interpolate=True, pos_tol=0.01, rot_tol_deg=5.0, ik_collision_threshold=5.0, float32_solutions=True,
+                     observation=None, retime=None):
+        """B objects with up to n_max candidate grasps each.
+
+        qc (B, ndof) or (ndof,); ik_goals, plan_goals (B, n_max, 4, 4): the poses IK is solved to and the poses the plan
+        goes to (the shelf driver solves IK to ``RT @ standoff`` and plans to ``RT``, :256-259); n_grasps (B,) how many rows
+        of an object count; fields: see ``_scene_ids``; base_position (3,) or (B, 3).  observation: an
+        ``observation.Observation`` to count the solved plans' surface points inside (gto_check_plans_device).  retime: a
+        dict ``vmax, amax[, subdiv, n_samples]`` to retime the solved plans (gto_retime_batch_device).
+
+        Returns a namespace: plans (B, ndof, T), dQ (B, ndof, T-1), cost, iters, status (B,), n_accepted (B,) (0: no
+        feasible grasp, the driver's ``continue``; the plan is then the solve from the constant seed to all goals),
+        seed_index (B,) (position among the accepted, -1 without one), seed_cost, seed_dist (B, n_max), q_solutions
+        (B, n_max, ndof) (float32 with float32_solutions), err_pos, err_rot, ik_cost, ik_iters, ik_status, accept
+        (B, n_max), and counts (B, T) / durations, retime_status (B,) when asked for."""
+        torch, h, d = self._torch, self._handle, self.robot.desc
+        ndof, T = d.ndof, self.T
+        ik_goals = np.asarray(ik_goals, dtype=np.float64)
+        B, n_max = ik_goals.shape[0], ik_goals.shape[1]
+        ik_goals = ik_goals.reshape(B, n_max, 16)
+        plan_goals = np.asarray(plan_goals, dtype=np.float64).reshape(B, n_max, 16)
+        n_grasps = np.ascontiguousarray(np.broadcast_to(np.asarray(n_grasps, dtype=np.int32), (B,)))
+        if B and (n_grasps.min() < 1 or n_grasps.max() > n_max):
+            raise ValueError("n_grasps must be in [1, n_max]")
+        qc = np.ascontiguousarray(np.broadcast_to(np.asarray(qc, dtype=np.float64).reshape(-1, ndof), (B, ndof)))
+        base = np.ascontiguousarray(np.broadcast_to(np.asarray(base_position, dtype=np.float64).reshape(-1, 3), (B, 3)))
+        sid = self._scene_ids(fields, B)
+        if int(h.opts.max_iter) != int(self.max_iter):
+            h.set_opts(max_iter=int(self.max_iter))
+        N = B * n_max
+        f64, i32, u8 = torch.float64, torch.int32, torch.uint8
+        res = SimpleNamespace()
+        with torch.cuda.stream(self.stream):
+            st = self.stream.cuda_stream
+            d_sid, d_qc, d_base = self._up("sid", sid, np.int32), self._up("qc", qc, np.float64), self._up("base", base, np.float64)
+            d_ikg, d_pg = self._up("ik_goals", ik_goals, np.float64), self._up("plan_goals", plan_goals, np.float64)
+            d_ng = self._up("n_grasps", n_grasps, np.int32)
+            # per candidate grasp: its object's scene, seed and base
+            d_sid_ik = self._up("sid_ik", np.repeat(sid, n_max), np.int32)
+            d_q0_ik = self._up("q0_ik", np.repeat(qc, n_max, axis=0), np.float64)
+            d_base_ik = self._up("base_ik", np.repeat(base, n_max, axis=0), np.float64)
+            d_q = self._dev("q_sol", (B, n_max, ndof), f64)
+            d_ikf, d_ikit, d_ikst = self._dev("ik_f", (B, n_max), f64), self._dev("ik_it", (B, n_max), i32), self._dev("ik_st", (B, n_max), i32)
+            d_ep, d_er, d_ic = self._dev("err_pos", (B, n_max), f64), self._dev("err_rot", (B, n_max), f64), self._dev("ik_cost", (B, n_max), f64)
+            d_acc = self._dev("accept", (B, n_max), u8)
+            d_gc, d_ngc, d_nacc = self._dev("goals_c", (B, n_max, 16), f64), self._dev("n_goals_c", (B,), i32), self._dev("n_acc", (B,), i32)
+            d_Q0, d_si = self._dev("Q0", (B, ndof, T), f64), self._dev("seed_index", (B,), i32)
+            d_sc, d_sd = self._dev("seed_cost", (B, n_max), f64), self._dev("seed_dist", (B, n_max), f64)
+            d_Q, d_dQ = self._dev("Q", (B, ndof, T), f64), self._dev("dQ", (B, ndof, T - 1), f64)
+            d_f, d_it, d_stat = self._dev("f", (B,), f64), self._dev("it", (B,), i32), self._dev("stat", (B,), i32)
+            d_so = None
+            if use_standoff:
+                S = standoff_pose(self.standoff_distance, axis_standoff)
+                d_so = self._up("standoff", np.broadcast_to(np.asarray(S, dtype=np.float64).reshape(1, 16), (B, 16)), np.float64)
+            d_gc.zero_()  # rows behind an object's accepted goals are never read; they are defined all the same
+            d_sc.fill_(float("nan"))
+            d_sd.fill_(float("nan"))
+            if N:
+                h.solve_ik_pose_batch_device(0, N, d_sid_ik.data_ptr(), d_q0_ik.data_ptr(), d_ikg.data_ptr(), d_base_ik.data_ptr(),
+                                             self.ik_max_iter, d_q.data_ptr(), d_ikf.data_ptr(), d_ikit.data_ptr(),
+                                             d_ikst.data_ptr(), st)
+                h.ik_report_device(N, d_sid_ik.data_ptr(), d_q.data_ptr(), d_ikg.data_ptr(), d_base_ik.data_ptr(), pos_tol,
+                                   rot_tol_deg, ik_collision_threshold, d_ep.data_ptr(), d_er.data_ptr(), d_ic.data_ptr(),
+                                   d_acc.data_ptr(), st)
+                h.seed_goalsets_device(B, n_max, d_sid.data_ptr(), d_qc.data_ptr(), d_pg.data_ptr(), d_ng.data_ptr(), d_q.data_ptr(),
+                                       d_acc.data_ptr(), d_base.data_ptr(), interpolate, float32_solutions, d_gc.data_ptr(),
+                                       d_ngc.data_ptr(), d_nacc.data_ptr(), d_Q0.data_ptr(), d_si.data_ptr(), d_sc.data_ptr(),
+                                       d_sd.data_ptr(), st)
+                h.solve_batch_device(B, n_max, d_sid.data_ptr(), d_qc.data_ptr(), d_gc.data_ptr(), d_ngc.data_ptr(),
+                                     None if d_so is None else d_so.data_ptr(), d_base.data_ptr(), d_Q0.data_ptr(), d_Q.data_ptr(),
+                                     d_dQ.data_ptr(), d_f.data_ptr(), d_it.data_ptr(), d_stat.data_ptr(), st)
+                if observation is not None:
+                    d_cnt = self._dev("counts", (B, T), i32)
+                    h.check_plans_device(observation, B, d_Q.data_ptr(), d_cnt.data_ptr(), base_pos=base, stream=st)
+                if retime is not None:
+                    d_dur, d_rst = self._dev("durations", (B,), f64), self._dev("retime_status", (B,), i32)
+                    h.retime_batch_device(B, d_Q.data_ptr(), retime["vmax"], retime["amax"], int(retime.get("subdiv", 2)),
+                                          int(retime.get("n_samples", 100)), duration_out=d_dur.data_ptr(),
+                                          status_out=d_rst.data_ptr(), stream=st)
+            out = dict(plans=d_Q, dQ=d_dQ, cost=d_f, iters=d_it, status=d_stat, n_accepted=d_nacc, seed_index=d_si, seed_cost=d_sc,
+                       seed_dist=d_sd, q_solutions=d_q, err_pos=d_ep, err_rot=d_er, ik_cost=d_ic, ik_iters=d_ikit, ik_status=d_ikst,
+                       accept=d_acc)
+            if N and observation is not None:
+                out["counts"] = d_cnt
+            if N and retime is not None:
+                out["durations"], out["retime_status"] = d_dur, d_rst
+            host = {k: self._pin("out/" + k, v.shape, v.dtype) for k, v in out.items()}
+            for k, v in out.items():
+                host[k].copy_(v, non_blocking=True)
+        self.stream.synchronize()  # the one host synchronisation of the call
+        for k, v in host.items():
+            setattr(res, k, v.numpy().copy())
+        res.accept = res.accept.astype(bool)
+        if float32_solutions:
+            res.q_solutions = res.q_solutions.astype(np.float32)
+        return res

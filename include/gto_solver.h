@@ -119,7 +119,7 @@ void gto_default_opts(gto_solver_opts* opts);
 /* Library/ABI version (major*1000 + minor): GTO_ABI_VERSION of the header the library was built from.  A binding checks it
  * when it loads the library and refuses another number (grasptrajopt_amd/_capi.py load_library): every change of a
  * signature or of a struct in this header bumps the minor. */
-#define GTO_ABI_VERSION 1011
+#define GTO_ABI_VERSION 1012
 int32_t gto_version(void);
 
 /*
@@ -559,6 +559,73 @@ int gto_retime_batch(gto_handle* h, int32_t B, const double* plans, const double
 int gto_retime_batch_device(gto_handle* h, int32_t B, const double* plans, const double* vmax, const double* amax,
                             int32_t subdiv, int32_t M, double* duration_out, double* t_grid_out, double* sd_grid_out,
                             double* q_out, double* qd_out, double* qdd_out, int32_t* status_out, void* stream);
+
+/*
+ * The stream-ordered chain from grasp poses to a solved plan (the per-object loop of examples/pybullet_gto_planning.py:
+ * 242-294 without a host round trip): gto_solve_ik_pose_batch_device -> gto_ik_report_device -> gto_seed_goalsets_device ->
+ * gto_solve_batch_device -> gto_check_plans_device -> gto_retime_batch_device on one stream.  The three entry points below
+ * take device pointers and `stream` (NULL = the handle's stream), enqueue and return without a host synchronisation; what
+ * they validate are host-side facts only (counts, null pointers, n_max, flags).  Handles with more than eight optimised
+ * joints: GTO_ERR_UNSUPPORTED.  B = 0 returns GTO_OK without a launch.  Every instance's result is bit for bit the same in
+ * any batch and at any position in it.  Their workspace lives on the handle: calls on one handle go to one stream, or the
+ * caller orders them (the rule of gto_check_plans_device).
+ *
+ * gto_solve_ik_pose_batch_device: the contract of gto_solve_ik_pose_batch with resident arrays (q_out required, the other
+ * outputs may be NULL); the same kernel and launch, results bit-equal to the host-pointer call.  base_pos may be NULL only
+ * when scene_id is NULL.  Scene ids live on the device and are NOT checked on the host: the kernel takes an id that names
+ * no scene of the handle (or a values-only scene) as GTO_STATUS_NUMERICAL with 0 iterations, q_out = the clipped seed and
+ * cost_out = NaN.
+ */
+int gto_solve_ik_pose_batch_device(gto_handle* h, int32_t goal_kind, int32_t B, const int32_t* scene_id, const double* q0,
+                                   const double* goals, const double* base_pos, int32_t max_iter, double* q_out,
+                                   double* cost_out, int32_t* iters_out, int32_t* status_out, void* stream);
+/*
+ * What the reference reports of an IK solution (gto/ik_solver.py:88-97) and the driver's acceptance test (:262), for B
+ * configurations q [B][ndof] against goal poses goals [B][16] (RT of link_ee, row-major 4x4):
+ *   err_pos = |RT[:3,3] - T_ee(q)[:3,3]|
+ *   err_rot = degrees(arccos(clip((trace(R_RT^T R_ee) - 1) / 2, -1, 1)))   (= the reference's 2 (q1.q2)^2 - 1)
+ *   cost    = plain sum of c_obs at the robot's surface points at q (compute_plan_cost of a one-column plan) with the
+ *             instance's scene and base_pos [B][3]; 0 when scene_id is NULL (base_pos may then be NULL).  Order of the sum:
+ *             thread i of 256 adds points i, i + 256, ... (the handle's link-sorted order), the 64 partial sums of a wave are
+ *             added by its lane-swap tree, then the four waves' sums in wave order ((w0 + w1) + w2) + w3: the order of
+ *             gto_plan_cost for one waypoint.  A scene id that names no scene: cost = NaN.
+ *   accept  = err_pos < pos_tol && err_rot < rot_tol_deg && cost < cost_tol (uint8 0 / 1); false whenever one of the three
+ *             is NaN.
+ * T_ee comes from the device kinematics behind gto_eval_fk.  Any output pointer may be NULL.
+ */
+int gto_ik_report_device(gto_handle* h, int32_t B, const int32_t* scene_id, const double* q, const double* goals,
+                         const double* base_pos, double pos_tol, double rot_tol_deg, double cost_tol, double* err_pos_out,
+                         double* err_rot_out, double* cost_out, uint8_t* accept_out, void* stream);
+/*
+ * Accepted goal sets and seeds of B goal-set problems (the driver's :267-269 and GTOPlanner.plan_goalset's seed choice,
+ * gto/gto_planner.py:193-219), per instance b:
+ *   inputs   scene_id [B], qc [B][ndof], goals [B][n_max][16], n_goals [B] (a value < 1 or > n_max is read as clamped to
+ *            [1, n_max]: it lives on the device), q_solutions [B][n_max][ndof] (the IK solution of every goal row),
+ *            accept [B][n_max] uint8 or NULL (= every row accepted), base_pos [B][3]
+ *   compaction  the accepted goals among rows 0..n_goals[b]-1, in their order, to goals_out [b][0..]; n_goals_out [b] =
+ *            n_accepted_out [b] = their count; seed_cost_out / seed_dist_out [b][.] are indexed by compacted position; rows
+ *            beyond the count are left untouched.  goals_out must not overlap goals.
+ *   candidates  for accepted solution j and waypoint t: Q[:, t] = qc + (q_j - qc) h_t, h_t = s s (3 - 2 s), s = (t + 1) /
+ *            (T + 1), in FP64 without fused multiply-adds (gto/utils.py:63-82 for two waypoints); rows of parameter joints
+ *            are qc's.  solutions_f32 != 0 rounds q_j to float32 and back first (the driver keeps q_solutions in float32).
+ *            They are generated in the scoring kernel: no [B][n][ndof][T] array exists.
+ *   score    seed_cost = sum of c_obs over all waypoints and surface points with the instance's scene and base (per waypoint
+ *            in the order given at gto_ik_report_device, then the waypoints in order), seed_dist = |Q[:, 0] - Q[:, T-1]|:
+ *            bit-equal to gto_plan_cost of the same candidates.  A scene id that names no scene: seed_cost = NaN.
+ *   choice   seed_index_out [b] = np.lexsort((dist, cost))[0] over the compacted positions: lowest cost, then lowest
+ *            distance, then lowest position; a NaN ranks after every number.  Q0_out [b][ndof][T]: the chosen candidate
+ *            (interpolate != 0), or qc for t < T + standoff_offset and the candidate's last column from there on (== 0).
+ *   no accepted solution (the q_solutions=None branch)  goals_out [b] = the first n_goals[b] goals unchanged, n_goals_out [b]
+ *            = n_goals[b], n_accepted_out [b] = 0, seed_index_out [b] = -1, Q0_out [b] = qc in every column: the instance
+ *            stays solvable by gto_solve_batch_device, and n_accepted_out tells the caller that it has no feasible grasp.
+ * Any output pointer may be NULL.  goals_out, n_goals_out and Q0_out are what gto_solve_batch_device takes as goals, n_goals
+ * and Q0.  n_max and B: at most 65535 each.  GTO_ERR_NO_SCENE when the handle has no scene at all.
+ */
+int gto_seed_goalsets_device(gto_handle* h, int32_t B, int32_t n_max, const int32_t* scene_id, const double* qc,
+                             const double* goals, const int32_t* n_goals, const double* q_solutions, const uint8_t* accept,
+                             const double* base_pos, int32_t interpolate, int32_t solutions_f32, double* goals_out,
+                             int32_t* n_goals_out, int32_t* n_accepted_out, double* Q0_out, int32_t* seed_index_out,
+                             double* seed_cost_out, double* seed_dist_out, void* stream);
 
 #ifdef __cplusplus
 }
