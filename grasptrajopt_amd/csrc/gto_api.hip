@@ -2467,14 +2467,24 @@ struct DepthPool {
 };
 DepthPool g_depth_pool;
 
+// GTO_DEPTH_BRUTE / GTO_CLOUD_BRUTE ask for the exhaustive search (the reference construction; the two searches are compared
+// in tests), GTO_DEPTH_STATS / GTO_CLOUD_STATS for the [gto] lines on stderr.  An entry-point call reads them once (the
+// entry points without a handle have no Tunables that could hold them): with its lease, or by itself where it takes none.
+struct SearchEnv { bool depth_brute, depth_stats, cloud_brute, cloud_stats; };
+SearchEnv search_env() {
+  auto set = [](const char* e) { return e && atoi(e) != 0; };
+  return {set(getenv("GTO_DEPTH_BRUTE")), getenv("GTO_DEPTH_STATS") != nullptr, set(getenv("GTO_CLOUD_BRUTE")), getenv("GTO_CLOUD_STATS") != nullptr};
+}
+
 // What one call of an entry point (`who`, on handle `h` or none) holds of the pool, and how it reports its errors.  The
 // buffers go back when the call ends, however it ends.
 struct DepthLease {
   gto_handle* h;
   const char* who;
   int device;
+  const SearchEnv env;
   std::vector<std::pair<void*, size_t>> bufs;
-  DepthLease(gto_handle* h_, const char* who_, int device_) : h(h_), who(who_), device(device_) {}
+  DepthLease(gto_handle* h_, const char* who_, int device_) : h(h_), who(who_), device(device_), env(search_env()) {}
   DepthLease(const DepthLease&) = delete;
   ~DepthLease() { release(); }
   void release() {
@@ -2510,20 +2520,42 @@ struct DepthLease {
     if (!d) return no_memory();
     return count ? hip(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice)) : GTO_OK;
   }
+  template <class T>
+  int download(T* host, const T* dev, size_t count) {  // an output the caller may not have asked for (null), or an empty one
+    return host && count ? hip(hipMemcpy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost)) : GTO_OK;
+  }
+  int sync() {  // everything enqueued so far has run, and without an error
+    const int rc = hip(hipGetLastError());
+    return rc ? rc : hip(hipDeviceSynchronize());
+  }
 };
 #define DEPTH_TRY(rc_expr)                     \
   do {                                         \
     if (const int rc_ = (rc_expr)) return rc_; \
   } while (0)
 
-// GTO_DEPTH_BRUTE and GTO_DEPTH_STATS are read by every call (gto_depth_sdf_cost has no handle whose Tunables could hold them)
-bool depth_brute_force() {  // the exhaustive search (reference construction; the two are compared in a test)
-  const char* e = getenv("GTO_DEPTH_BRUTE");
-  return e && atoi(e) != 0;
+// The device of an entry point without a handle: `device`, made current, or the current one for a negative `device`
+int select_device(int device, int* cur) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, GTO_ERR_NO_DEVICE, "no HIP device");
+  if (device >= 0 && hipSetDevice(device) != hipSuccess) return fail(nullptr, GTO_ERR_NO_DEVICE, "hipSetDevice failed");
+  *cur = 0;
+  (void)hipGetDevice(cur);
+  return GTO_OK;
 }
-bool depth_stats() { return getenv("GTO_DEPTH_STATS") != nullptr; }
 
-// The two non-blocking streams of a device that gto_scene_from_depth's searches run on, kept for the process
+// Wall-clock marks between the phases of a scene builder, for its line under GTO_DEPTH_STATS / GTO_CLOUD_STATS: one at
+// the start, two of the builder's own, four of finish_scene
+struct PhaseClock {
+  double t[7];
+  int n = 0;
+  PhaseClock() { mark(); }
+  void mark() { t[n++] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+  bool full() const { return n == 7; }
+  double ms(int from, int to) const { return t[to] - t[from]; }
+};
+
+// The two non-blocking streams of a device that the scene builders' searches run on, kept for the process
 hipError_t depth_search_streams(int device, hipStream_t* sa, hipStream_t* sb) {
   static std::mutex mu;
   static std::vector<std::pair<int, std::pair<hipStream_t, hipStream_t>>> streams;
@@ -2551,15 +2583,44 @@ int upload_camera(DepthLease& c, const double* K, const double* Kinv, const doub
   return GTO_OK;
 }
 
-// Queries in Morton order of their position within the cloud's root box (coherent waves): 30-bit keys, hipCUB radix sort of
-// (key, index) on the null stream
-int sort_queries(DepthLease& c, const DepthCloud& cl, DepthQueries* qs) {
+// Depth image (device) + camera + mask -> the back-projected cloud, with its tile hierarchy when `want_tree` (the caller has
+// checked that the image is within GTO_BVH_MAX_P), on the null stream.  d_valid [H * W]: the pixels' flags.
+int make_depth_cloud(DepthLease& c, const float* d_depth, int H, int W, const DepthCamera& cam, const uint8_t* d_mask, double threshold,
+                     bool want_tree, uint8_t* d_valid, DepthCloud* cl) {
+  const size_t N = (size_t)H * W;
+  const int P = want_tree ? tile_levels(H, W) : 0;
+  double* d_p = c.alloc<double>(3 * N);
+  double* d_boxes = P ? c.alloc<double>(bvh_box_doubles(P)) : nullptr;
+  if (!d_p || (P && !d_boxes)) return c.no_memory();
+  *cl = {d_depth, H, W, d_p, d_p + N, d_p + 2 * N, P, d_boxes};
+  build_cloud(*cl, cam, d_mask, threshold, d_valid);
+  return GTO_OK;
+}
+
+// The same from the host's image, camera matrices and mask (null: none), for the entry points that take one image
+int upload_depth_cloud(DepthLease& c, const float* depth, int H, int W, const double* K, const double* Kinv, const double* pose,
+                       const double* inv, const uint8_t* mask, double threshold, bool want_tree, DepthCamera* cam, uint8_t** d_valid,
+                       DepthCloud* cl) {
+  const size_t N = (size_t)H * W;
+  const float* d_depth;
+  const uint8_t* d_mask = nullptr;
+  DEPTH_TRY(c.upload(depth, N, &d_depth));
+  DEPTH_TRY(upload_camera(c, K, Kinv, pose, inv, cam));
+  if (mask) DEPTH_TRY(c.upload(mask, N, &d_mask));
+  *d_valid = c.alloc<uint8_t>(N);
+  if (!*d_valid) return c.no_memory();
+  return make_depth_cloud(c, d_depth, H, W, *cam, d_mask, threshold, want_tree, *d_valid, cl);
+}
+
+// Queries in Morton order of their position within a cloud's root box d_root_box (device; lo x y z, hi x y z): coherent
+// waves.  30-bit keys, hipCUB radix sort of (key, index) on the null stream
+int sort_queries(DepthLease& c, const double* d_root_box, DepthQueries* qs) {
   const long nq = qs->nq;
   if (nq >= ((int64_t)1 << 31)) return fail(c.h, GTO_ERR_UNSUPPORTED, std::string(c.who) + ": more than 2^31 queries");
   unsigned* d_keys = c.alloc<unsigned>((size_t)nq * 4);  // keys in / out, indices in / out
   if (!d_keys) return c.no_memory();
   unsigned *d_keys2 = d_keys + nq, *d_idx = d_keys + 2 * nq, *d_idx2 = d_keys + 3 * nq;
-  hipLaunchKernelGGL(k_query_keys, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, 0, qs->q, nq, cl.boxes, d_keys, d_idx);
+  hipLaunchKernelGGL(k_query_keys, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, 0, qs->q, nq, d_root_box, d_keys, d_idx);
   size_t tmp_bytes = 0;
   DEPTH_TRY(c.hip(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, (int)nq, 0, 30, (hipStream_t)0)));
   void* d_tmp = c.alloc<char>(tmp_bytes);
@@ -2568,85 +2629,31 @@ int sort_queries(DepthLease& c, const DepthCloud& cl, DepthQueries* qs) {
   return c.hip(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, (int)nq, 0, 30, (hipStream_t)0));
 }
 
+// Which search a cloud gets: the tree if it was built with one, unless the call runs under the exhaustive switch.  The tree
+// search wants its queries sorted (sort_queries) and the exhaustive one ignores their order; sorting is the caller's step,
+// since one order may serve two searches and the collision checks keep the caller's.
+bool use_tree(const DepthCloud& cl, const SearchEnv& env) { return cl.P != 0 && !env.depth_brute; }
+bool use_tree(const SampleCloud& cl, const SearchEnv& env) { return cl.n_leaves != 0 && !env.cloud_brute; }
+void search_depth(const SearchEnv& env, hipStream_t stream, const DepthCloud& cl, const DepthCamera& cam, const DepthQueries& qs, float epsilon,
+                  float w_inside, const DepthFields& out, unsigned long long* d_stats, bool cost_only) {
+  if (use_tree(cl, env)) search_tree(stream, cl, cam, qs, epsilon, w_inside, out, d_stats, cost_only);
+  else search_exhaustive(stream, cl, cam, qs, epsilon, w_inside, out);
+}
+void search_samples(const SearchEnv& env, hipStream_t stream, const SampleCloud& cl, int k, const DepthQueries& qs, float epsilon, float w_inside,
+                    const CloudFields& out) {
+  if (use_tree(cl, env)) search_cloud_tree(stream, cl, k, qs, epsilon, w_inside, out);
+  else search_cloud_exhaustive(stream, cl, k, qs, epsilon, w_inside, out);
+}
+
 // The three counters k_depth_sdf_bvh adds to under GTO_DEPTH_STATS, zeroed (null without it, and when the pool has none left)
-int depth_counters(DepthLease& c, bool stats, unsigned long long** d_stats) {
-  *d_stats = stats ? c.alloc<unsigned long long>(3) : nullptr;
+int depth_counters(DepthLease& c, unsigned long long** d_stats) {
+  *d_stats = c.env.depth_stats ? c.alloc<unsigned long long>(3) : nullptr;
   return *d_stats ? c.hip(hipMemset(*d_stats, 0, 3 * sizeof(unsigned long long))) : GTO_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int gto_depth_sdf_cost(int device, const float* depth, int32_t H, int32_t W, const double* K, const double* Kinv,
-                       const double* cam_pose, const double* cam_inv, const uint8_t* target_mask, double threshold,
-                       const double* query, int64_t nq, float epsilon, float w_inside, float* sdf_out,
-                       uint8_t* inside_out, float* cost_out, double* points_out, uint8_t* valid_out) {
-  if (!depth || !K || !Kinv || !cam_pose || !cam_inv || H < 1 || W < 1 || nq < 0 || (nq > 0 && !query))
-    return fail(nullptr, GTO_ERR_INVALID_ARG, "gto_depth_sdf_cost: null or empty input");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, GTO_ERR_NO_DEVICE, "no HIP device");
-  if (device >= 0 && hipSetDevice(device) != hipSuccess) return fail(nullptr, GTO_ERR_NO_DEVICE, "hipSetDevice failed");
-  const size_t N = (size_t)H * W;
-  int cur_dev = 0;
-  (void)hipGetDevice(&cur_dev);
-  // bounding-box hierarchy over 8 x 4 pixel tiles of the depth image (k_depth_sdf_bvh): the exhaustive search's distances,
-  // bit for bit.  The exhaustive search itself on request, and for images with more tiles per side than k_bvh_up builds
-  const int P = tile_levels(H, W);
-  const bool tree = nq && !depth_brute_force() && P <= GTO_BVH_MAX_P;
-  DepthLease c(nullptr, "gto_depth_sdf_cost", cur_dev);
-  const float* d_depth;
-  const uint8_t* d_mask = nullptr;
-  DepthCamera cam;
-  DepthQueries qs = {nullptr, (long)nq, nullptr};
-  DEPTH_TRY(c.upload(depth, N, &d_depth));
-  DEPTH_TRY(upload_camera(c, K, Kinv, cam_pose, cam_inv, &cam));
-  if (target_mask) DEPTH_TRY(c.upload(target_mask, N, &d_mask));
-  double* d_p = c.alloc<double>(3 * N);
-  uint8_t* d_valid = c.alloc<uint8_t>(N);
-  if (!d_p || !d_valid) return c.no_memory();
-  DEPTH_TRY(c.upload(query, (size_t)nq * 3, &qs.q));
-  float* d_sdf = c.alloc<float>((size_t)nq);
-  float* d_cost = c.alloc<float>((size_t)nq);
-  uint8_t* d_in = c.alloc<uint8_t>((size_t)nq);
-  double* d_boxes = tree ? c.alloc<double>(bvh_box_doubles(P)) : nullptr;
-  if (!d_sdf || !d_cost || !d_in || (tree && !d_boxes)) return c.no_memory();
-  const DepthCloud cloud = {d_depth, H, W, d_p, d_p + N, d_p + 2 * N, tree ? P : 0, d_boxes};
-  const DepthFields out = {d_sdf, d_in, d_cost};
-  build_cloud(cloud, cam, d_mask, threshold, d_valid);
-  if (tree) {
-    unsigned long long* d_stats;
-    DEPTH_TRY(depth_counters(c, depth_stats(), &d_stats));
-    DEPTH_TRY(sort_queries(c, cloud, &qs));
-    search_tree(0, cloud, cam, qs, epsilon, w_inside, out, d_stats, false);
-    if (d_stats) {
-      unsigned long long st[3];
-      DEPTH_TRY(c.hip(hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost)));
-      fprintf(stderr, "[gto] depth field search: %lld queries, nodes popped per query %.1f, leaves per query %.1f, loop iterations per wave %.1f\n",
-              (long long)nq, (double)st[0] / nq, (double)st[1] / nq, (double)st[2] / ((nq + 63) / 64));
-    }
-  } else if (nq) {
-    search_exhaustive(0, cloud, cam, qs, epsilon, w_inside, out);
-  }
-  DEPTH_TRY(c.hip(hipGetLastError()));
-  DEPTH_TRY(c.hip(hipDeviceSynchronize()));
-  if (sdf_out && nq) DEPTH_TRY(c.hip(hipMemcpy(sdf_out, d_sdf, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost)));
-  if (cost_out && nq) DEPTH_TRY(c.hip(hipMemcpy(cost_out, d_cost, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost)));
-  if (inside_out && nq) DEPTH_TRY(c.hip(hipMemcpy(inside_out, d_in, (size_t)nq, hipMemcpyDeviceToHost)));
-  if (valid_out) DEPTH_TRY(c.hip(hipMemcpy(valid_out, d_valid, N, hipMemcpyDeviceToHost)));
-  if (points_out) {
-    std::vector<double> soa(3 * N);
-    DEPTH_TRY(c.hip(hipMemcpy(soa.data(), d_p, 3 * N * sizeof(double), hipMemcpyDeviceToHost)));
-    for (size_t i = 0; i < N; ++i)
-      for (int r = 0; r < 3; ++r) points_out[3 * i + r] = soa[(size_t)r * N + i];
-  }
-  return GTO_OK;
-}
-
-
 // numpy.arange(start, stop, step) for doubles, value for value: the length is ceil((stop - start) / step), the fill is
 // a[i] = start + i * ((start + step) - start) (numpy's DOUBLE_fill takes the increment from the first two elements)
-static std::vector<double> np_arange(double start, double stop, double step) {
+std::vector<double> np_arange(double start, double stop, double step) {
   const double len = std::ceil((stop - start) / step);
   const long n = len > 0 ? (long)len : 0;
   std::vector<double> a((size_t)n);
@@ -2655,127 +2662,64 @@ static std::vector<double> np_arange(double start, double stop, double step) {
   return a;
 }
 
-/* include/gto_solver.h: the per-object perception steps of examples/pybullet_gto_planning.py:176-190 in one call, with
- * nothing but the grid geometry coming back to the host.  The depth image goes up once; the cloud of all pixels and the
- * cloud without the target's pixels are back-projected from it; the grid is the bounding box of the first cloud plus
- * `margin` at `grid_res` (gto/gto_models.py:155-171, numpy.arange's values); both cost fields are searched with ONE
- * ordering of the voxel centres (one key pass, one radix sort) against the two tile hierarchies, and installed as scene
- * `scene_id` with their voxel records and distance fields, device to device. */
-int gto_scene_from_depth(gto_handle* h, int32_t scene_id, const float* depth, int32_t H, int32_t W, const double* K,
-                         const double* Kinv, const double* cam_pose, const double* cam_inv, const uint8_t* target_mask,
-                         const float* depth_obstacle, double threshold, double grid_res, double margin, float epsilon,
-                         float w_inside, int32_t* shape_out, double* origin_out, double* bounds_out) {
-  if (!h) return GTO_ERR_INVALID_ARG;
-  if (!depth || !K || !Kinv || !cam_pose || !cam_inv || H < 1 || W < 1 || !(grid_res > 0) || !(margin >= 0))
-    return fail(h, GTO_ERR_INVALID_ARG, "gto_scene_from_depth: null or empty input");
-  HIPCHK(h, hipSetDevice(h->device));
-  const bool stats = depth_stats();
-  auto t_now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t_[8] = {t_now(), 0, 0, 0, 0, 0, 0, 0};
-  const size_t N = (size_t)H * W;
-  const int P = tile_levels(H, W);
-  if (P > GTO_BVH_MAX_P) return fail(h, GTO_ERR_UNSUPPORTED, "gto_scene_from_depth: image larger than 8192 x 4096 pixels");
-  DepthLease c(h, "gto_scene_from_depth", h->device);
-  // the second cloud: the obstacle image (the driver's depth_obstacle, examples/pybullet_gto_planning.py:187-189: the target's
-  // pixels pushed to the threshold) without the masked pixels; its visibility test reads the obstacle image
-  const bool two = target_mask != nullptr || depth_obstacle != nullptr;
-  const float *d_depth, *d_depth_o;
-  const uint8_t* d_mask = nullptr;
-  DepthCamera cam;
-  DEPTH_TRY(c.upload(depth, N, &d_depth));
-  d_depth_o = d_depth;
-  if (depth_obstacle) DEPTH_TRY(c.upload(depth_obstacle, N, &d_depth_o));
-  DEPTH_TRY(upload_camera(c, K, Kinv, cam_pose, cam_inv, &cam));
-  if (target_mask) DEPTH_TRY(c.upload(target_mask, N, &d_mask));
-  double* d_pa = c.alloc<double>(3 * N);
-  double* d_po = two ? c.alloc<double>(3 * N) : d_pa;
-  uint8_t* d_valid = c.alloc<uint8_t>(N);
-  double* d_boxa = c.alloc<double>(bvh_box_doubles(P));
-  double* d_boxo = two ? c.alloc<double>(bvh_box_doubles(P)) : d_boxa;
-  if (!d_pa || !d_po || !d_valid || !d_boxa || !d_boxo) return c.no_memory();
-  t_[1] = t_now();
-  // the hierarchy of the first cloud: its root box is the bounding box of the valid points (gto/gto_models.py:155-157)
-  const DepthCloud all = {d_depth, H, W, d_pa, d_pa + N, d_pa + 2 * N, P, d_boxa};
-  const DepthCloud obs = {d_depth_o, H, W, d_po, d_po + N, d_po + 2 * N, P, d_boxo};
-  build_cloud(all, cam, nullptr, threshold, d_valid);
-  if (two) build_cloud(obs, cam, d_mask, threshold, d_valid);
-  double root[6];
-  DEPTH_TRY(c.hip(hipMemcpy(root, all.boxes, sizeof root, hipMemcpyDeviceToHost)));  // (synchronises with the null stream)
-  t_[2] = t_now();
-  if (!(root[0] <= root[3]) || !std::isfinite(root[0]) || !std::isfinite(root[3]))
-    return fail(h, GTO_ERR_INVALID_ARG, "gto_scene_from_depth: no valid pixel in the depth image");
-  std::vector<double> ax[3];
-  int32_t shape[3];
-  double origin[3];
-  size_t nq = 1;
+// The voxel grid of a scene: the bounding box `bounds` of a cloud plus `margin` at `res` (gto/gto_models.py:155-171,
+// numpy.arange's values).  axes: the centres along x, then y, then z.
+struct VoxelGrid { double bounds[6]; std::vector<double> axes; int32_t shape[3]; double origin[3]; size_t nq; };
+int plan_grid(gto_handle* h, const char* who, const double bounds[6], double margin, double res, VoxelGrid* g) {
+  std::memcpy(g->bounds, bounds, sizeof g->bounds);
+  g->axes.clear();
+  g->nq = 1;
   for (int a = 0; a < 3; ++a) {
-    ax[a] = np_arange(root[a] - margin, root[3 + a] + margin, grid_res);
-    shape[a] = (int32_t)ax[a].size();
-    origin[a] = root[a] - margin;
-    nq *= ax[a].size();
+    const std::vector<double> ax = np_arange(bounds[a] - margin, bounds[3 + a] + margin, res);
+    g->axes.insert(g->axes.end(), ax.begin(), ax.end());
+    g->shape[a] = (int32_t)ax.size();
+    g->origin[a] = bounds[a] - margin;
+    g->nq *= ax.size();
   }
-  if (nq == 0 || nq >= ((size_t)1 << 31)) return fail(h, GTO_ERR_UNSUPPORTED, "gto_scene_from_depth: empty grid or more than 2^31 voxels");
-  std::vector<double> axes(ax[0]);
-  axes.insert(axes.end(), ax[1].begin(), ax[1].end());
-  axes.insert(axes.end(), ax[2].begin(), ax[2].end());
+  if (g->nq == 0 || g->nq >= ((size_t)1 << 31)) return fail(h, GTO_ERR_UNSUPPORTED, std::string(who) + ": empty grid or more than 2^31 voxels");
+  return GTO_OK;
+}
+// its voxel centres on the device, x slowest (null stream)
+int make_grid_queries(DepthLease& c, const VoxelGrid& g, DepthQueries* qs) {
   const double* d_axes;
-  DEPTH_TRY(c.upload(axes.data(), axes.size(), &d_axes));
-  double* d_q = c.alloc<double>(nq * 3);
-  float* d_costa = c.alloc<float>(nq);
-  float* d_costo = two ? c.alloc<float>(nq) : d_costa;
-  uint8_t* d_in = c.alloc<uint8_t>(nq);
-  if (!d_q || !d_costa || !d_costo || !d_in) return c.no_memory();
-  hipLaunchKernelGGL(k_grid_queries, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, 0, d_axes, shape[0], shape[1], shape[2], d_q);
-  DepthQueries qs = {d_q, (long)nq, nullptr};
-  DEPTH_TRY(sort_queries(c, all, &qs));
-  unsigned long long* d_stats;
-  DEPTH_TRY(depth_counters(c, stats, &d_stats));
-  if (stats) DEPTH_TRY(c.hip(hipDeviceSynchronize()));
-  t_[3] = t_now();
-  // the two searches are independent and each is bound by its slowest packets (the voxels deep behind the surfaces): side
-  // by side on two streams of their own, behind everything the null stream has done so far
-  hipStream_t sa = nullptr, sb = nullptr;
-  DEPTH_TRY(c.hip(depth_search_streams(h->device, &sa, &sb)));
-  DEPTH_TRY(c.hip(hipStreamSynchronize(0)));
-  uint8_t* d_in2 = two ? c.alloc<uint8_t>(nq) : d_in;
-  if (!d_in2) return c.no_memory();
-  search_tree(sa, all, cam, qs, epsilon, w_inside, {nullptr, d_in, d_costa}, d_stats, true);
-  if (two) search_tree(sb, obs, cam, qs, epsilon, w_inside, {nullptr, d_in2, d_costo}, nullptr, true);
-  DEPTH_TRY(c.hip(hipGetLastError()));
-  DEPTH_TRY(c.hip(hipDeviceSynchronize()));
-  t_[4] = t_now();
-  if (d_stats) {
-    unsigned long long stv[3];
-    DEPTH_TRY(c.hip(hipMemcpy(stv, d_stats, sizeof stv, hipMemcpyDeviceToHost)));
-    fprintf(stderr, "[gto] depth field search (first cloud): %zu queries, nodes popped per wave %.1f, leaves per wave %.1f\n", nq, (double)stv[2] / ((nq + 63) / 64), (double)stv[1] / 64 / ((nq + 63) / 64));
-  }
-  const int rc = set_scene_impl(h, scene_id, d_costa, two ? d_costo : nullptr, shape, origin, grid_res, false, hipMemcpyDeviceToDevice);
-  t_[5] = t_now();
-  c.release();
-  t_[6] = t_now();
-  if (stats)
-    fprintf(stderr, "[gto] scene from depth (%d x %d image, %zu voxels), ms: alloc + upload %.3f | back-projection, hierarchies, bounds %.3f | queries, keys, sort %.3f | "
-                    "two searches %.3f | records + distance fields %.3f | release %.3f | total %.3f\n",
-            H, W, nq, t_[1] - t_[0], t_[2] - t_[1], t_[3] - t_[2], t_[4] - t_[3], t_[5] - t_[4], t_[6] - t_[5], t_[6] - t_[0]);
-  if (rc) return rc;
-  if (shape_out) std::memcpy(shape_out, shape, sizeof shape);
-  if (origin_out) std::memcpy(origin_out, origin, sizeof origin);
-  if (bounds_out) std::memcpy(bounds_out, root, sizeof root);
+  DEPTH_TRY(c.upload(g.axes.data(), g.axes.size(), &d_axes));
+  double* d_q = c.alloc<double>(g.nq * 3);
+  if (!d_q) return c.no_memory();
+  hipLaunchKernelGGL(k_grid_queries, dim3((unsigned)((g.nq + 255) / 256)), dim3(256), 0, 0, d_axes, g.shape[0], g.shape[1], g.shape[2], d_q);
+  *qs = {d_q, (long)g.nq, nullptr};
   return GTO_OK;
 }
 
-
-// ------------------------------------------------------------------ cost field from a sampled mesh (gto_cloud.h)
-}  // extern "C"
-
-namespace {
-bool cloud_brute_force() {  // the exhaustive search (reference construction; the two are compared in a test)
-  const char* e = getenv("GTO_CLOUD_BRUTE");
-  return e && atoi(e) != 0;
+// What both scene builders do once their clouds are built and the voxel centres laid out.  `search(sa, sb)` enqueues the one
+// or two searches on the device's two search streams, behind everything the null stream has done so far: they are
+// independent and each is bound by its slowest packets (the voxels deep behind the surfaces), so they run side by side.
+// `searched()` follows when they are done.  Then the fields d_all / d_obs (null: one field) become scene `scene_id`, with
+// their voxel records and distance fields, device to device; the lease goes back; the geometry goes out.  Marks of `clk`:
+// searches enqueued from here, searches done, scene installed, lease released.
+struct SceneGeometryOut { int32_t* shape; double *origin, *bounds; };  // of the caller; each may be null
+template <class Search, class Searched>
+int finish_scene(DepthLease& c, PhaseClock& clk, int32_t scene_id, const VoxelGrid& g, double res, const float* d_all, const float* d_obs,
+                 const SceneGeometryOut& out, Search search, Searched searched) {
+  hipStream_t sa = nullptr, sb = nullptr;
+  DEPTH_TRY(c.hip(depth_search_streams(c.device, &sa, &sb)));
+  DEPTH_TRY(c.hip(hipStreamSynchronize(0)));
+  clk.mark();
+  search(sa, sb);
+  DEPTH_TRY(c.sync());
+  clk.mark();
+  DEPTH_TRY(searched());
+  const int rc = set_scene_impl(c.h, scene_id, d_all, d_obs, g.shape, g.origin, res, false, hipMemcpyDeviceToDevice);
+  clk.mark();
+  c.release();
+  clk.mark();
+  if (rc) return rc;
+  if (out.shape) std::memcpy(out.shape, g.shape, sizeof g.shape);
+  if (out.origin) std::memcpy(out.origin, g.origin, sizeof g.origin);
+  if (out.bounds) std::memcpy(out.bounds, g.bounds, sizeof g.bounds);
+  return GTO_OK;
 }
-bool cloud_stats() { return getenv("GTO_CLOUD_STATS") != nullptr; }
 
-// What both entry points check before any device work.  box_out: bounding box of the n samples (lo x y z, hi x y z).
+// What the sampled-mesh entry points check before any device work.  box_out: bounding box of the n samples (lo x y z, hi x y z).
 int check_cloud(gto_handle* h, const char* who, const double* points, const double* normals, int64_t n, int32_t k, double box_out[6]) {
   const std::string w(who);
   if (!points || !normals) return fail(h, GTO_ERR_INVALID_ARG, w + ": null points or normals");
@@ -2792,11 +2736,11 @@ int check_cloud(gto_handle* h, const char* who, const double* points, const doub
   return GTO_OK;
 }
 
-// The samples d_points / d_normals [n][3] (device) as a SampleCloud; with `tree`, in key order under their hierarchy.
-// box: their bounding box (check_cloud).
-int make_sample_cloud(DepthLease& c, const double* d_points, const double* d_normals, int64_t n, const double box[6], bool tree, SampleCloud* cl) {
+// The samples d_points / d_normals [n][3] (device) as a SampleCloud; under their hierarchy, in key order, unless the call
+// runs under the exhaustive switch.  box: their bounding box (check_cloud).
+int make_sample_cloud(DepthLease& c, const double* d_points, const double* d_normals, int64_t n, const double box[6], SampleCloud* cl) {
   *cl = {d_points, d_normals, (unsigned)n, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr};
-  if (!tree) return GTO_OK;
+  if (c.env.cloud_brute) return GTO_OK;
   // k_query_keys spreads its keys over a box grown by its own extent on every side (queries lie around a cloud): the
   // samples lie within their box, so it is handed the middle third and the keys use all their bits
   double kbox[6];
@@ -2806,10 +2750,8 @@ int make_sample_cloud(DepthLease& c, const double* d_points, const double* d_nor
   }
   const double* d_kbox;
   DEPTH_TRY(c.upload(kbox, 6, &d_kbox));
-  DepthCloud keyed = {};
-  keyed.boxes = const_cast<double*>(d_kbox);
   DepthQueries ps = {d_points, (long)n, nullptr};
-  DEPTH_TRY(sort_queries(c, keyed, &ps));
+  DEPTH_TRY(sort_queries(c, d_kbox, &ps));
   cl->n_leaves = cloud_leaf_slots((unsigned)n);
   cl->n_slots = (unsigned)((n + GTO_CLOUD_LEAF - 1) / GTO_CLOUD_LEAF) * GTO_CLOUD_LEAF;
   cl->px = c.alloc<double>((size_t)cl->n_slots * 3);
@@ -2820,22 +2762,146 @@ int make_sample_cloud(DepthLease& c, const double* d_points, const double* d_nor
   build_sample_tree(*cl, ps.order);
   return c.hip(hipGetLastError());
 }
+
 }  // namespace
 
 extern "C" {
 
+int gto_depth_sdf_cost(int device, const float* depth, int32_t H, int32_t W, const double* K, const double* Kinv,
+                       const double* cam_pose, const double* cam_inv, const uint8_t* target_mask, double threshold,
+                       const double* query, int64_t nq, float epsilon, float w_inside, float* sdf_out,
+                       uint8_t* inside_out, float* cost_out, double* points_out, uint8_t* valid_out) {
+  if (!depth || !K || !Kinv || !cam_pose || !cam_inv || H < 1 || W < 1 || nq < 0 || (nq > 0 && !query))
+    return fail(nullptr, GTO_ERR_INVALID_ARG, "gto_depth_sdf_cost: null or empty input");
+  int cur_dev;
+  DEPTH_TRY(select_device(device, &cur_dev));
+  DepthLease c(nullptr, "gto_depth_sdf_cost", cur_dev);
+  // bounding-box hierarchy over 8 x 4 pixel tiles of the depth image (k_depth_sdf_bvh): the exhaustive search's distances,
+  // bit for bit.  No hierarchy, and the exhaustive search itself, on request, and for images with more tiles per side
+  // than k_bvh_up builds; none without queries either
+  const bool tree = nq && !c.env.depth_brute && tile_levels(H, W) <= GTO_BVH_MAX_P;
+  const size_t N = (size_t)H * W;
+  DepthQueries qs = {nullptr, (long)nq, nullptr};
+  DEPTH_TRY(c.upload(query, (size_t)nq * 3, &qs.q));
+  const DepthFields out = {c.alloc<float>((size_t)nq), c.alloc<uint8_t>((size_t)nq), c.alloc<float>((size_t)nq)};
+  if (!out.sdf || !out.inside || !out.cost) return c.no_memory();
+  DepthCamera cam;
+  DepthCloud cloud;
+  uint8_t* d_valid;
+  DEPTH_TRY(upload_depth_cloud(c, depth, H, W, K, Kinv, cam_pose, cam_inv, target_mask, threshold, tree, &cam, &d_valid, &cloud));
+  unsigned long long* d_stats = nullptr;
+  if (tree) {
+    DEPTH_TRY(depth_counters(c, &d_stats));
+    DEPTH_TRY(sort_queries(c, cloud.boxes, &qs));
+  }
+  if (nq) search_depth(c.env, 0, cloud, cam, qs, epsilon, w_inside, out, d_stats, false);
+  if (d_stats) {
+    unsigned long long st[3];
+    DEPTH_TRY(c.download(st, d_stats, 3));
+    fprintf(stderr, "[gto] depth field search: %lld queries, nodes popped per query %.1f, leaves per query %.1f, loop iterations per wave %.1f\n",
+            (long long)nq, (double)st[0] / nq, (double)st[1] / nq, (double)st[2] / ((nq + 63) / 64));
+  }
+  DEPTH_TRY(c.sync());
+  DEPTH_TRY(c.download(sdf_out, out.sdf, (size_t)nq));
+  DEPTH_TRY(c.download(cost_out, out.cost, (size_t)nq));
+  DEPTH_TRY(c.download(inside_out, out.inside, (size_t)nq));
+  DEPTH_TRY(c.download(valid_out, d_valid, N));
+  if (points_out) {
+    std::vector<double> soa(3 * N);
+    DEPTH_TRY(c.download(soa.data(), cloud.px, 3 * N));
+    for (size_t i = 0; i < N; ++i)
+      for (int r = 0; r < 3; ++r) points_out[3 * i + r] = soa[(size_t)r * N + i];
+  }
+  return GTO_OK;
+}
+
+/* include/gto_solver.h: the per-object perception steps of examples/pybullet_gto_planning.py:176-190 in one call, with
+ * nothing but the grid geometry coming back to the host.  The depth image goes up once; the cloud of all pixels and the
+ * cloud without the target's pixels are back-projected from it; the grid is the bounding box of the first cloud plus
+ * `margin` at `grid_res`; both cost fields are searched with ONE ordering of the voxel centres (one key pass, one radix
+ * sort) against the two tile hierarchies, and installed as scene `scene_id`. */
+int gto_scene_from_depth(gto_handle* h, int32_t scene_id, const float* depth, int32_t H, int32_t W, const double* K,
+                         const double* Kinv, const double* cam_pose, const double* cam_inv, const uint8_t* target_mask,
+                         const float* depth_obstacle, double threshold, double grid_res, double margin, float epsilon,
+                         float w_inside, int32_t* shape_out, double* origin_out, double* bounds_out) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (!depth || !K || !Kinv || !cam_pose || !cam_inv || H < 1 || W < 1 || !(grid_res > 0) || !(margin >= 0))
+    return fail(h, GTO_ERR_INVALID_ARG, "gto_scene_from_depth: null or empty input");
+  HIPCHK(h, hipSetDevice(h->device));
+  PhaseClock clk;
+  const size_t N = (size_t)H * W;
+  if (tile_levels(H, W) > GTO_BVH_MAX_P) return fail(h, GTO_ERR_UNSUPPORTED, "gto_scene_from_depth: image larger than 8192 x 4096 pixels");
+  DepthLease c(h, "gto_scene_from_depth", h->device);
+  // the second cloud: the obstacle image (the driver's depth_obstacle, examples/pybullet_gto_planning.py:187-189: the target's
+  // pixels pushed to the threshold) without the masked pixels; its visibility test reads the obstacle image
+  const bool two = target_mask != nullptr || depth_obstacle != nullptr;
+  const float *d_depth, *d_depth_o;
+  const uint8_t* d_mask = nullptr;
+  DepthCamera cam;
+  DEPTH_TRY(c.upload(depth, N, &d_depth));
+  d_depth_o = d_depth;
+  if (depth_obstacle) DEPTH_TRY(c.upload(depth_obstacle, N, &d_depth_o));
+  DEPTH_TRY(upload_camera(c, K, Kinv, cam_pose, cam_inv, &cam));
+  if (target_mask) DEPTH_TRY(c.upload(target_mask, N, &d_mask));
+  uint8_t* d_valid = c.alloc<uint8_t>(N);
+  if (!d_valid) return c.no_memory();
+  clk.mark();
+  // the hierarchy of the first cloud: its root box is the bounding box of the valid points (gto/gto_models.py:155-157)
+  DepthCloud all, obs;
+  DEPTH_TRY(make_depth_cloud(c, d_depth, H, W, cam, nullptr, threshold, true, d_valid, &all));
+  obs = all;
+  if (two) DEPTH_TRY(make_depth_cloud(c, d_depth_o, H, W, cam, d_mask, threshold, true, d_valid, &obs));
+  double root[6];
+  DEPTH_TRY(c.download(root, all.boxes, 6));  // (synchronises with the null stream)
+  clk.mark();
+  if (!(root[0] <= root[3]) || !std::isfinite(root[0]) || !std::isfinite(root[3]))
+    return fail(h, GTO_ERR_INVALID_ARG, "gto_scene_from_depth: no valid pixel in the depth image");
+  VoxelGrid grid;
+  DEPTH_TRY(plan_grid(h, c.who, root, margin, grid_res, &grid));
+  DepthQueries qs;
+  DEPTH_TRY(make_grid_queries(c, grid, &qs));
+  const size_t nq = grid.nq;
+  float* d_costa = c.alloc<float>(nq);
+  float* d_costo = two ? c.alloc<float>(nq) : nullptr;
+  uint8_t* d_in = c.alloc<uint8_t>(nq);
+  uint8_t* d_in2 = two ? c.alloc<uint8_t>(nq) : nullptr;
+  if (!d_costa || !d_in || (two && (!d_costo || !d_in2))) return c.no_memory();
+  DEPTH_TRY(sort_queries(c, all.boxes, &qs));
+  unsigned long long* d_stats;
+  DEPTH_TRY(depth_counters(c, &d_stats));
+  if (c.env.depth_stats) DEPTH_TRY(c.hip(hipDeviceSynchronize()));
+  const int rc = finish_scene(
+      c, clk, scene_id, grid, grid_res, d_costa, d_costo, {shape_out, origin_out, bounds_out},
+      [&](hipStream_t sa, hipStream_t sb) {  // (always the tree: the image is within its limit, and a scene is not a reference construction)
+        search_tree(sa, all, cam, qs, epsilon, w_inside, {nullptr, d_in, d_costa}, d_stats, true);
+        if (two) search_tree(sb, obs, cam, qs, epsilon, w_inside, {nullptr, d_in2, d_costo}, nullptr, true);
+      },
+      [&]() {
+        unsigned long long stv[3];
+        const int rc = c.download(stv, d_stats, d_stats ? 3 : 0);
+        if (d_stats && !rc)
+          fprintf(stderr, "[gto] depth field search (first cloud): %zu queries, nodes popped per wave %.1f, leaves per wave %.1f\n", nq,
+                  (double)stv[2] / ((nq + 63) / 64), (double)stv[1] / 64 / ((nq + 63) / 64));
+        return rc;
+      });
+  if (c.env.depth_stats && clk.full())
+    fprintf(stderr, "[gto] scene from depth (%d x %d image, %zu voxels), ms: alloc + upload %.3f | back-projection, hierarchies, bounds %.3f | queries, keys, sort %.3f | "
+                    "two searches %.3f | records + distance fields %.3f | release %.3f | total %.3f\n",
+            H, W, nq, clk.ms(0, 1), clk.ms(1, 2), clk.ms(2, 3), clk.ms(3, 4), clk.ms(4, 5), clk.ms(5, 6), clk.ms(0, 6));
+  return rc;
+}
+
+
+// ------------------------------------------------------------------ cost field from a sampled mesh (gto_cloud.h)
 int gto_cloud_sdf_cost(int device, const double* points, const double* normals, int64_t n, int32_t k, const double* query,
                        int64_t nq, float epsilon, float w_inside, float* sdf_out, uint8_t* inside_out, float* cost_out,
                        int32_t* nearest_out) {
   double box[6];
   if (int rc = check_cloud(nullptr, "gto_cloud_sdf_cost", points, normals, n, k, box)) return rc;
   if (nq < 0 || (nq > 0 && !query)) return fail(nullptr, GTO_ERR_INVALID_ARG, "gto_cloud_sdf_cost: null or negative query count");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, GTO_ERR_NO_DEVICE, "no HIP device");
-  if (device >= 0 && hipSetDevice(device) != hipSuccess) return fail(nullptr, GTO_ERR_NO_DEVICE, "hipSetDevice failed");
+  int cur_dev;
+  DEPTH_TRY(select_device(device, &cur_dev));
   if (nq == 0) return GTO_OK;
-  int cur_dev = 0;
-  (void)hipGetDevice(&cur_dev);
   DepthLease c(nullptr, "gto_cloud_sdf_cost", cur_dev);
   const double *d_points, *d_normals;
   DepthQueries qs = {nullptr, (long)nq, nullptr};
@@ -2844,23 +2910,15 @@ int gto_cloud_sdf_cost(int device, const double* points, const double* normals, 
   DEPTH_TRY(c.upload(query, (size_t)nq * 3, &qs.q));
   const CloudFields out = {c.alloc<float>((size_t)nq), c.alloc<uint8_t>((size_t)nq), c.alloc<float>((size_t)nq), c.alloc<int32_t>((size_t)nq)};
   if (!out.sdf || !out.inside || !out.cost || !out.nearest) return c.no_memory();
-  const bool tree = !cloud_brute_force();
   SampleCloud cl;
-  DEPTH_TRY(make_sample_cloud(c, d_points, d_normals, n, box, tree, &cl));
-  if (tree) {
-    DepthCloud rooted = {};
-    rooted.boxes = cl.boxes;
-    DEPTH_TRY(sort_queries(c, rooted, &qs));
-    search_cloud_tree(0, cl, k, qs, epsilon, w_inside, out);
-  } else {
-    search_cloud_exhaustive(0, cl, k, qs, epsilon, w_inside, out);
-  }
-  DEPTH_TRY(c.hip(hipGetLastError()));
-  DEPTH_TRY(c.hip(hipDeviceSynchronize()));
-  if (sdf_out) DEPTH_TRY(c.hip(hipMemcpy(sdf_out, out.sdf, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost)));
-  if (inside_out) DEPTH_TRY(c.hip(hipMemcpy(inside_out, out.inside, (size_t)nq, hipMemcpyDeviceToHost)));
-  if (cost_out) DEPTH_TRY(c.hip(hipMemcpy(cost_out, out.cost, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost)));
-  if (nearest_out) DEPTH_TRY(c.hip(hipMemcpy(nearest_out, out.nearest, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost)));
+  DEPTH_TRY(make_sample_cloud(c, d_points, d_normals, n, box, &cl));
+  if (use_tree(cl, c.env)) DEPTH_TRY(sort_queries(c, cl.boxes, &qs));
+  search_samples(c.env, 0, cl, k, qs, epsilon, w_inside, out);
+  DEPTH_TRY(c.sync());
+  DEPTH_TRY(c.download(sdf_out, out.sdf, (size_t)nq));
+  DEPTH_TRY(c.download(inside_out, out.inside, (size_t)nq));
+  DEPTH_TRY(c.download(cost_out, out.cost, (size_t)nq));
+  DEPTH_TRY(c.download(nearest_out, out.nearest, (size_t)nq));
   return GTO_OK;
 }
 
@@ -2877,79 +2935,43 @@ int gto_scene_from_clouds(gto_handle* h, int32_t scene_id, const double* points,
   const bool two = n_obstacle != n_all;
   if (two)
     if (int rc = check_cloud(h, "gto_scene_from_clouds", points, normals, n_obstacle, k, box_o)) return rc;
-  std::vector<double> ax[3];
-  int32_t shape[3];
-  double origin[3];
-  size_t nq = 1;
-  for (int a = 0; a < 3; ++a) {
-    ax[a] = np_arange(root[a] - margin, root[3 + a] + margin, grid_res);
-    shape[a] = (int32_t)ax[a].size();
-    origin[a] = root[a] - margin;
-    nq *= ax[a].size();
-  }
-  if (nq == 0 || nq >= ((size_t)1 << 31)) return fail(h, GTO_ERR_UNSUPPORTED, "gto_scene_from_clouds: empty grid or more than 2^31 voxels");
+  VoxelGrid grid;
+  DEPTH_TRY(plan_grid(h, "gto_scene_from_clouds", root, margin, grid_res, &grid));
   HIPCHK(h, hipSetDevice(h->device));
-  const bool stats = cloud_stats();
-  auto t_now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t_[6] = {t_now(), 0, 0, 0, 0, 0};
+  PhaseClock clk;
   Staging io(h);  // inputs only: nothing but the geometry returns
   const double *d_points, *d_normals;
-  int rc;
-  if ((rc = io.in(points, (size_t)n_all * 3, &d_points))) return rc;
-  if ((rc = io.in(normals, (size_t)n_all * 3, &d_normals))) return rc;
+  DEPTH_TRY(io.in(points, (size_t)n_all * 3, &d_points));
+  DEPTH_TRY(io.in(normals, (size_t)n_all * 3, &d_normals));
   HIPCHK(h, hipStreamSynchronize(h->stream));  // the pipeline below runs on the null stream and two search streams
-  t_[1] = t_now();
+  clk.mark();
   DepthLease c(h, "gto_scene_from_clouds", h->device);
-  const bool tree = !cloud_brute_force();
   SampleCloud all, obs;
-  DEPTH_TRY(make_sample_cloud(c, d_points, d_normals, n_all, root, tree, &all));
+  DEPTH_TRY(make_sample_cloud(c, d_points, d_normals, n_all, root, &all));
   obs = all;
-  if (two) DEPTH_TRY(make_sample_cloud(c, d_points, d_normals, n_obstacle, box_o, tree, &obs));
-  if (stats) DEPTH_TRY(c.hip(hipDeviceSynchronize()));
-  t_[2] = t_now();
-  std::vector<double> axes(ax[0]);
-  axes.insert(axes.end(), ax[1].begin(), ax[1].end());
-  axes.insert(axes.end(), ax[2].begin(), ax[2].end());
-  const double* d_axes;
-  DEPTH_TRY(c.upload(axes.data(), axes.size(), &d_axes));
-  double* d_q = c.alloc<double>(nq * 3);
-  float* d_costa = c.alloc<float>(nq);
-  float* d_costo = two ? c.alloc<float>(nq) : d_costa;
-  if (!d_q || !d_costa || !d_costo) return c.no_memory();
-  hipLaunchKernelGGL(k_grid_queries, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, 0, d_axes, shape[0], shape[1], shape[2], d_q);
-  DepthQueries qs = {d_q, (long)nq, nullptr};
-  if (tree) {  // one key pass and one sort for both fields, over the root box of all samples
-    DepthCloud rooted = {};
-    rooted.boxes = all.boxes;
-    DEPTH_TRY(sort_queries(c, rooted, &qs));
-  }
-  hipStream_t sa = nullptr, sb = nullptr;
-  DEPTH_TRY(c.hip(depth_search_streams(h->device, &sa, &sb)));
-  DEPTH_TRY(c.hip(hipStreamSynchronize(0)));
-  t_[3] = t_now();
-  if (tree) {
-    search_cloud_tree(sa, all, k, qs, epsilon, w_inside, {nullptr, nullptr, d_costa, nullptr});
-    if (two) search_cloud_tree(sb, obs, k, qs, epsilon, w_inside, {nullptr, nullptr, d_costo, nullptr});
-  } else {
-    search_cloud_exhaustive(sa, all, k, qs, epsilon, w_inside, {nullptr, nullptr, d_costa, nullptr});
-    if (two) search_cloud_exhaustive(sb, obs, k, qs, epsilon, w_inside, {nullptr, nullptr, d_costo, nullptr});
-  }
-  DEPTH_TRY(c.hip(hipGetLastError()));
-  DEPTH_TRY(c.hip(hipDeviceSynchronize()));
-  t_[4] = t_now();
-  rc = set_scene_impl(h, scene_id, d_costa, two ? d_costo : nullptr, shape, origin, grid_res, false, hipMemcpyDeviceToDevice);
-  c.release();
-  t_[5] = t_now();
-  if (stats)
+  if (two) DEPTH_TRY(make_sample_cloud(c, d_points, d_normals, n_obstacle, box_o, &obs));
+  if (c.env.cloud_stats) DEPTH_TRY(c.hip(hipDeviceSynchronize()));
+  clk.mark();
+  DepthQueries qs;
+  DEPTH_TRY(make_grid_queries(c, grid, &qs));
+  float* d_costa = c.alloc<float>(grid.nq);
+  float* d_costo = two ? c.alloc<float>(grid.nq) : nullptr;
+  if (!d_costa || (two && !d_costo)) return c.no_memory();
+  const bool tree = use_tree(all, c.env);
+  if (tree) DEPTH_TRY(sort_queries(c, all.boxes, &qs));  // one key pass and one sort for both fields, over the root box of all samples
+  const int rc = finish_scene(
+      c, clk, scene_id, grid, grid_res, d_costa, d_costo, {shape_out, origin_out, bounds_out},
+      [&](hipStream_t sa, hipStream_t sb) {
+        search_samples(c.env, sa, all, k, qs, epsilon, w_inside, {nullptr, nullptr, d_costa, nullptr});
+        if (two) search_samples(c.env, sb, obs, k, qs, epsilon, w_inside, {nullptr, nullptr, d_costo, nullptr});
+      },
+      []() { return (int)GTO_OK; });
+  if (c.env.cloud_stats && clk.full())
     fprintf(stderr, "[gto] scene from clouds (%lld + %lld samples, k %d, %zu voxels, %s), ms: upload %.3f | sort + build %.3f | queries, keys, sort %.3f | "
                     "search %.3f | records + distance fields %.3f | total %.3f\n",
-            (long long)n_all, (long long)(two ? n_obstacle : 0), (int)k, nq, tree ? "tree" : "exhaustive", t_[1] - t_[0], t_[2] - t_[1], t_[3] - t_[2],
-            t_[4] - t_[3], t_[5] - t_[4], t_[5] - t_[0]);
-  if (rc) return rc;
-  if (shape_out) std::memcpy(shape_out, shape, sizeof shape);
-  if (origin_out) std::memcpy(origin_out, origin, sizeof origin);
-  if (bounds_out) std::memcpy(bounds_out, root, sizeof root);
-  return GTO_OK;
+            (long long)n_all, (long long)(two ? n_obstacle : 0), (int)k, grid.nq, tree ? "tree" : "exhaustive", clk.ms(0, 1), clk.ms(1, 2), clk.ms(2, 3),
+            clk.ms(3, 4), clk.ms(4, 6), clk.ms(0, 6));
+  return rc;
 }
 
 /* The two cost fields of a resident scene, device to host (float32 [nx ny nz] each; either pointer may be null). */
@@ -3107,14 +3129,22 @@ void obs_adopt(gto_observation* o, DepthLease& c, std::initializer_list<const vo
 ObsDepthView depth_view(const gto_observation* o) { return {o->depth.depth, o->depth.H, o->depth.W, o->cam.K, o->cam.inv}; }
 
 // the vote of the observation's k nearest samples for nq queries in the caller's order (neighbours as they come), on `st`
-void obs_cloud_votes(hipStream_t st, const gto_observation* o, const double* d_q, long nq, uint8_t* d_flags) {
-  const DepthQueries qs = {d_q, nq, nullptr};
-  const CloudFields out = {nullptr, d_flags, nullptr, nullptr};
-  if (o->cloud.n_leaves && !cloud_brute_force()) search_cloud_tree(st, o->cloud, o->k, qs, 0.0f, 0.0f, out);
-  else search_cloud_exhaustive(st, o->cloud, o->k, qs, 0.0f, 0.0f, out);
+void obs_cloud_votes(const SearchEnv& env, hipStream_t st, const gto_observation* o, const double* d_q, long nq, uint8_t* d_flags) {
+  search_samples(env, st, o->cloud, o->k, {d_q, nq, nullptr}, 0.0f, 0.0f, {nullptr, d_flags, nullptr, nullptr});
 }
 // queries of a cloud observation per launch chain of a check: bounds the workspace (25 bytes per query)
 constexpr long long kCheckChunkQueries = 1ll << 24;
+// how many of n items (grasps, plans) of per_item >= 1 queries each go into one launch chain: at least one
+int chunk_items(int n, long long per_item) { return (int)std::min<long long>(n, std::max<long long>(1, kCheckChunkQueries / per_item)); }
+// What gto_check_plans and its device variant check before any device work.  *empty: nothing to do (B = 0).
+int check_plans_args(gto_handle* h, const gto_observation* o, int32_t B, const double* plans, const double* base_pos, bool* empty) {
+  *empty = B == 0;
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (!o || B < 0 || !base_pos) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_plans: null observation or base position");
+  if (o->device != h->device) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_plans: the observation lives on another device than the handle");
+  if (B > 0 && !plans) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_plans: null plans");
+  return GTO_OK;
+}
 // waypoints per workgroup of k_check_plans: GTO_CHECK_TG in the environment (1 .. 4, read by every call; default 4, the
 // measured choice: DESIGN.md 7g).  Results do not depend on it.
 int check_waypoints_per_group() {
@@ -3132,31 +3162,16 @@ int gto_observation_from_depth(int device, const float* depth, int32_t H, int32_
   if (out) *out = nullptr;
   if (!out || !depth || !K || !Kinv || !cam_pose || !cam_inv || H < 1 || W < 1)
     return fail(nullptr, GTO_ERR_INVALID_ARG, "gto_observation_from_depth: null or empty input");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, GTO_ERR_NO_DEVICE, "no HIP device");
-  if (device >= 0 && hipSetDevice(device) != hipSuccess) return fail(nullptr, GTO_ERR_NO_DEVICE, "hipSetDevice failed");
-  const size_t N = (size_t)H * W;
-  int cur_dev = 0;
-  (void)hipGetDevice(&cur_dev);
-  const int P = tile_levels(H, W);
-  const bool tree = P <= GTO_BVH_MAX_P;  // beyond: the exhaustive search, as gto_depth_sdf_cost
+  int cur_dev;
+  DEPTH_TRY(select_device(device, &cur_dev));
   std::unique_ptr<gto_observation> o(new gto_observation);
   o->device = cur_dev, o->is_depth = true;
   DepthLease c(nullptr, "gto_observation_from_depth", cur_dev);
-  const float* d_depth;
-  const uint8_t* d_mask = nullptr;
-  DEPTH_TRY(c.upload(depth, N, &d_depth));
-  DEPTH_TRY(upload_camera(c, K, Kinv, cam_pose, cam_inv, &o->cam));
-  if (target_mask) DEPTH_TRY(c.upload(target_mask, N, &d_mask));
-  double* d_p = c.alloc<double>(3 * N);
-  uint8_t* d_valid = c.alloc<uint8_t>(N);
-  double* d_boxes = tree ? c.alloc<double>(bvh_box_doubles(P)) : nullptr;
-  if (!d_p || !d_valid || (tree && !d_boxes)) return c.no_memory();
-  o->depth = {d_depth, H, W, d_p, d_p + N, d_p + 2 * N, tree ? P : 0, d_boxes};
-  build_cloud(o->depth, o->cam, d_mask, threshold, d_valid);
-  DEPTH_TRY(c.hip(hipGetLastError()));
-  DEPTH_TRY(c.hip(hipDeviceSynchronize()));
-  obs_adopt(o.get(), c, {d_depth, o->cam.K, d_p, d_boxes});
+  const bool tree = tile_levels(H, W) <= GTO_BVH_MAX_P;  // beyond: the exhaustive search, as gto_depth_sdf_cost
+  uint8_t* d_valid;
+  DEPTH_TRY(upload_depth_cloud(c, depth, H, W, K, Kinv, cam_pose, cam_inv, target_mask, threshold, tree, &o->cam, &d_valid, &o->depth));
+  DEPTH_TRY(c.sync());
+  obs_adopt(o.get(), c, {o->depth.depth, o->cam.K, o->depth.px, o->depth.boxes});
   *out = o.release();
   return GTO_OK;
 }
@@ -3167,20 +3182,16 @@ int gto_observation_from_cloud(int device, const double* points, const double* n
   if (!out) return fail(nullptr, GTO_ERR_INVALID_ARG, "gto_observation_from_cloud: null output");
   double box[6];
   if (int rc = check_cloud(nullptr, "gto_observation_from_cloud", points, normals, n, k, box)) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(nullptr, GTO_ERR_NO_DEVICE, "no HIP device");
-  if (device >= 0 && hipSetDevice(device) != hipSuccess) return fail(nullptr, GTO_ERR_NO_DEVICE, "hipSetDevice failed");
-  int cur_dev = 0;
-  (void)hipGetDevice(&cur_dev);
+  int cur_dev;
+  DEPTH_TRY(select_device(device, &cur_dev));
   std::unique_ptr<gto_observation> o(new gto_observation);
   o->device = cur_dev, o->is_depth = false, o->k = k;
   DepthLease c(nullptr, "gto_observation_from_cloud", cur_dev);
   const double *d_points, *d_normals;
   DEPTH_TRY(c.upload(points, (size_t)n * 3, &d_points));
   DEPTH_TRY(c.upload(normals, (size_t)n * 3, &d_normals));
-  DEPTH_TRY(make_sample_cloud(c, d_points, d_normals, n, box, !cloud_brute_force(), &o->cloud));
-  DEPTH_TRY(c.hip(hipGetLastError()));
-  DEPTH_TRY(c.hip(hipDeviceSynchronize()));
+  DEPTH_TRY(make_sample_cloud(c, d_points, d_normals, n, box, &o->cloud));
+  DEPTH_TRY(c.sync());
   obs_adopt(o.get(), c, {d_points, d_normals, o->cloud.px, o->cloud.pid, o->cloud.boxes});
   *out = o.release();
   return GTO_OK;
@@ -3208,28 +3219,15 @@ int gto_observation_sdf(gto_observation* o, const double* query, int64_t nq, flo
   uint8_t* d_in = c.alloc<uint8_t>((size_t)nq);
   if (!d_sdf || !d_in) return c.no_memory();
   if (o->is_depth) {
-    const DepthFields out = {d_sdf, d_in, nullptr};
-    if (o->depth.P && !depth_brute_force()) {
-      DEPTH_TRY(sort_queries(c, o->depth, &qs));
-      search_tree(0, o->depth, o->cam, qs, 0.0f, 0.0f, out, nullptr, false);
-    } else {
-      search_exhaustive(0, o->depth, o->cam, qs, 0.0f, 0.0f, out);
-    }
+    if (use_tree(o->depth, c.env)) DEPTH_TRY(sort_queries(c, o->depth.boxes, &qs));
+    search_depth(c.env, 0, o->depth, o->cam, qs, 0.0f, 0.0f, {d_sdf, d_in, nullptr}, nullptr, false);
   } else {
-    const CloudFields out = {d_sdf, d_in, nullptr, nullptr};
-    if (o->cloud.n_leaves && !cloud_brute_force()) {
-      DepthCloud rooted = {};
-      rooted.boxes = o->cloud.boxes;
-      DEPTH_TRY(sort_queries(c, rooted, &qs));
-      search_cloud_tree(0, o->cloud, o->k, qs, 0.0f, 0.0f, out);
-    } else {
-      search_cloud_exhaustive(0, o->cloud, o->k, qs, 0.0f, 0.0f, out);
-    }
+    if (use_tree(o->cloud, c.env)) DEPTH_TRY(sort_queries(c, o->cloud.boxes, &qs));
+    search_samples(c.env, 0, o->cloud, o->k, qs, 0.0f, 0.0f, {d_sdf, d_in, nullptr, nullptr});
   }
-  DEPTH_TRY(c.hip(hipGetLastError()));
-  DEPTH_TRY(c.hip(hipDeviceSynchronize()));
-  if (sdf_out) DEPTH_TRY(c.hip(hipMemcpy(sdf_out, d_sdf, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost)));
-  if (inside_out) DEPTH_TRY(c.hip(hipMemcpy(inside_out, d_in, (size_t)nq, hipMemcpyDeviceToHost)));
+  DEPTH_TRY(c.sync());
+  DEPTH_TRY(c.download(sdf_out, d_sdf, (size_t)nq));
+  DEPTH_TRY(c.download(inside_out, d_in, (size_t)nq));
   return GTO_OK;
 }
 
@@ -3248,8 +3246,7 @@ int gto_observation_check_posed(gto_observation* o, const double* points, int32_
   if (o->is_depth) {
     hipLaunchKernelGGL(k_check_posed<true>, dim3((unsigned)n), dim3(256), 0, 0, d_points, (int)P, d_poses, depth_view(o), (double*)nullptr, d_count);
   } else {
-    const long long per = std::max<long long>(1, kCheckChunkQueries / std::max(1, (int)P));
-    const int chunk = (int)std::min<long long>(n, per);
+    const int chunk = chunk_items(n, std::max(1, (int)P));
     double* d_xyz = c.alloc<double>((size_t)chunk * P * 3);
     uint8_t* d_flags = c.alloc<uint8_t>((size_t)chunk * P);
     if (!d_xyz || !d_flags) return c.no_memory();
@@ -3257,29 +3254,27 @@ int gto_observation_check_posed(gto_observation* o, const double* points, int32_
       const int m = std::min(chunk, n - i0);
       hipLaunchKernelGGL(k_check_posed<false>, dim3((unsigned)m), dim3(256), 0, 0, d_points, (int)P, d_poses + (size_t)i0 * 16, ObsDepthView{}, d_xyz,
                          d_count + i0);
-      if (P) obs_cloud_votes(0, o, d_xyz, (long)m * P, d_flags);
+      if (P) obs_cloud_votes(c.env, 0, o, d_xyz, (long)m * P, d_flags);
       hipLaunchKernelGGL(k_count_flags, dim3((unsigned)m), dim3(256), 0, 0, d_flags, (int)P, d_count + i0);
     }
   }
-  DEPTH_TRY(c.hip(hipGetLastError()));
-  DEPTH_TRY(c.hip(hipDeviceSynchronize()));
-  if (count_out) DEPTH_TRY(c.hip(hipMemcpy(count_out, d_count, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost)));
+  DEPTH_TRY(c.sync());
+  DEPTH_TRY(c.download(count_out, d_count, (size_t)n));
   return GTO_OK;
 }
 
 int gto_check_plans_device(gto_handle* h, gto_observation* o, int32_t B, const double* plans, const double* base_pos,
                            int32_t per_plan_base, int32_t* count_out, void* stream) {
-  if (!h) return GTO_ERR_INVALID_ARG;
-  if (!o || B < 0 || !base_pos) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_plans: null observation or base position");
-  if (o->device != h->device) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_plans: the observation lives on another device than the handle");
-  if (B == 0) return GTO_OK;
-  if (!plans) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_plans: null plans");
+  bool empty;
+  if (int rc = check_plans_args(h, o, B, plans, base_pos, &empty)) return rc;
+  if (empty) return GTO_OK;
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t st = stream ? (hipStream_t)stream : h->stream;
   const int T = h->opts.T, P = h->rb.n_points, ndof = h->rb.ndof;
   const size_t lds = sizeof(double) * check_plans_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
   if (lds > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the collision-check kernel's LDS");
   const int tg = check_waypoints_per_group();
+  const SearchEnv env = search_env();
   const unsigned tgroups = (unsigned)((T + tg - 1) / tg);
   int rc;
   const double* d_base = nullptr;
@@ -3299,8 +3294,7 @@ int gto_check_plans_device(gto_handle* h, gto_observation* o, int32_t B, const d
                          b0, b1, b2, d_base, depth_view(o), (double*)nullptr, count_out);
   } else if (count_out) {
     HIPCHK(h, raise_dynamic_lds((const void*)k_check_plans<false>, lds));
-    const long long per = std::max<long long>(1, kCheckChunkQueries / ((long long)T * std::max(1, P)));
-    const int chunk = (int)std::min<long long>(B, per);
+    const int chunk = chunk_items(B, (long long)T * std::max(1, P));
     if ((rc = ensure(h, h->ck_xyz, (size_t)chunk * T * P * 3 * sizeof(double)))) return rc;
     if ((rc = ensure(h, h->ck_flags, (size_t)chunk * T * P))) return rc;
     double* d_xyz = (double*)h->ck_xyz.p;
@@ -3310,7 +3304,7 @@ int gto_check_plans_device(gto_handle* h, gto_observation* o, int32_t B, const d
       int32_t* cnt = count_out + (size_t)i0 * T;
       hipLaunchKernelGGL(k_check_plans<false>, dim3((unsigned)m, tgroups), dim3(256), lds, st, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_plink, T, tg,
                          plans + (size_t)i0 * ndof * T, b0, b1, b2, d_base ? d_base + (size_t)i0 * 3 : nullptr, ObsDepthView{}, d_xyz, cnt);
-      if (P) obs_cloud_votes(st, o, d_xyz, (long)m * T * P, d_flags);
+      if (P) obs_cloud_votes(env, st, o, d_xyz, (long)m * T * P, d_flags);
       hipLaunchKernelGGL(k_count_flags, dim3((unsigned)(m * T)), dim3(256), 0, st, d_flags, P, cnt);
     }
   }
@@ -3320,11 +3314,9 @@ int gto_check_plans_device(gto_handle* h, gto_observation* o, int32_t B, const d
 
 int gto_check_plans(gto_handle* h, gto_observation* o, int32_t B, const double* plans, const double* base_pos,
                     int32_t per_plan_base, int32_t* count_out) {
-  if (!h) return GTO_ERR_INVALID_ARG;
-  if (!o || B < 0 || !base_pos) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_plans: null observation or base position");
-  if (o->device != h->device) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_plans: the observation lives on another device than the handle");
-  if (B == 0) return GTO_OK;
-  if (!plans) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_plans: null plans");
+  bool empty;
+  if (int rc = check_plans_args(h, o, B, plans, base_pos, &empty)) return rc;
+  if (empty) return GTO_OK;
   HIPCHK(h, hipSetDevice(h->device));
   Staging io(h);
   const double* d_plans;

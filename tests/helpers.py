@@ -15,6 +15,20 @@ def cfg_of(robot):
         return json.load(fh)
 
 
+class exhaustive:
+    """GTO_CLOUD_BRUTE=1 for the calls inside (the library reads it on every call)."""
+
+    def __enter__(self):
+        self.old = os.environ.get("GTO_CLOUD_BRUTE")
+        os.environ["GTO_CLOUD_BRUTE"] = "1"
+
+    def __exit__(self, *exc):
+        if self.old is None:
+            del os.environ["GTO_CLOUD_BRUTE"]
+        else:
+            os.environ["GTO_CLOUD_BRUTE"] = self.old
+
+
 class Problem:
     """A seeded batch of (scene, goal) instances for one robot."""
 

@@ -2,6 +2,8 @@
 replaces -- DepthPointCloud / SurfacePointCloud.get_sdf, utils.plan_in_collision, utils.grasp_collision_ratio -- and against
 the reference's own counts (tests/golden/collision_checks.npz).  Every comparison is exact.  Run the file under a time limit
 (timeout -k 10 900 pytest ...) and stop at the first fault."""
+from contextlib import nullcontext
+
 import numpy as np
 import pytest
 
@@ -14,7 +16,7 @@ from grasptrajopt_amd.observation import Observation
 from grasptrajopt_amd.utils import (filter_grasps, grasp_collision_counts, grasp_collision_ratio, plan_in_collision,
                                     plans_in_collision)
 from grasptrajopt_amd.synthetic import grasp_poses, random_plans, start_pose, wall_scene
-from helpers import cfg_of
+from helpers import cfg_of, exhaustive
 
 pytestmark = pytest.mark.gpu
 
@@ -289,3 +291,36 @@ def test_cloud_observation_checks(shelf_cloud):
     want[2, 49] = -1
     np.testing.assert_array_equal(h.check_plans(obs, few, base), want)
     robot.close()
+
+
+# ---------------------------------------------------------------------------------------------- 9. cloud observation, both searches
+@pytest.mark.parametrize("k", [1, 11])
+@pytest.mark.parametrize("n", [11, 33, 65])
+def test_cloud_observation_by_tree_and_by_exhaustive_search(n, k, monkeypatch):
+    """One leaf that is not full, two leaves, three leaves.  Whether the observation was built with its hierarchy or under
+    GTO_CLOUD_BRUTE=1 without one, and whether it is asked with the variable set or not: sdf gives the restatement's bits,
+    and check_posed the restatement's counts (poses of identity rotation: the kernel's position is q + t in float64, one
+    rounding, as numpy's).  257 points cross the 256-thread stride of the check."""
+    monkeypatch.delenv("GTO_CLOUD_BRUTE", raising=False)
+    rng = np.random.default_rng(n)
+    pts, nrm = rng.normal(size=(n, 3)), rng.normal(size=(n, 3))
+    q = np.concatenate([rng.normal(size=(300, 3)), pts[:5], 50.0 + rng.normal(size=(10, 3))])
+    want = ref.cloud_sdf(pts, nrm, q, k=k)
+    poses = np.tile(np.eye(4), (8, 1, 1))
+    poses[:, :3, 3] = rng.normal(size=(8, 3))
+    want_counts = np.array([ref.cloud_sdf(pts, nrm, q[:257] + t, k=k)["inside"].sum() for t in poses[:, :3, 3]], dtype=np.int32)
+    assert (want_counts > 0).any() and (want_counts < 257).any()
+    poses[6, 2, 3] = np.nan
+    want_counts[6] = -1
+    for built_brute in (False, True):
+        with exhaustive() if built_brute else nullcontext():
+            obs = Observation.from_cloud(pts, nrm, k)
+        for asked_brute in (False, True):
+            with exhaustive() if asked_brute else nullcontext():
+                sdf, inside = obs.sdf(q)
+                counts = obs.check_posed(q[:257], poses)
+            mode = f"built exhaustive={built_brute}, asked exhaustive={asked_brute}"
+            np.testing.assert_array_equal(bits(sdf), bits(want["sdf"]), err_msg=mode)
+            np.testing.assert_array_equal(inside, want["inside"], err_msg=mode)
+            np.testing.assert_array_equal(counts, want_counts, err_msg=mode)
+        obs.close()

@@ -2,8 +2,6 @@
 reference's own results (tests/golden/surface_cloud.npz, made by tests/golden/make_surface_cloud_golden.py) and the numpy
 restatement (cloud_sdf_ref.py), and through the planner.  Run the file under a time limit (timeout -k 10 600 pytest ...)
 and stop at the first fault."""
-import os
-
 import numpy as np
 import pytest
 
@@ -12,27 +10,13 @@ import cloud_sdf_ref as ref
 import grasptrajopt_amd as g
 from grasptrajopt_amd import surface_point_cloud as spc
 from grasptrajopt_amd import synthetic as syn
-from helpers import cfg_of
+from helpers import cfg_of, exhaustive
 
 pytestmark = pytest.mark.gpu
 
 
 def bits(a):
     return np.asarray(a, dtype=np.float32).view(np.uint32)
-
-
-class exhaustive:
-    """GTO_CLOUD_BRUTE=1 for the calls inside (the library reads it on every call)."""
-
-    def __enter__(self):
-        self.old = os.environ.get("GTO_CLOUD_BRUTE")
-        os.environ["GTO_CLOUD_BRUTE"] = "1"
-
-    def __exit__(self, *exc):
-        if self.old is None:
-            del os.environ["GTO_CLOUD_BRUTE"]
-        else:
-            os.environ["GTO_CLOUD_BRUTE"] = self.old
 
 
 def shelf_parts(z, base_pose=None):

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """depth_field_rate.py — time of one cost-field construction (gto_depth_sdf_cost) at the reference's sizes:
-a 480x640 depth image and the voxel centres of the Panda workspace grid at 5 cm, then at 128^3."""
+a 480x640 depth image and the voxel centres of the Panda workspace grid at 5 cm, then at 128^3.  Median of five timed
+calls [min .. max] after one warm-up call."""
 import os
+import statistics
 import sys
 import time
 
@@ -31,9 +33,12 @@ dpc = g.DepthPointCloud(depth, K, cam)
 for n in (48, 128):
     ax = np.linspace(-0.4, 1.84, n)
     q = np.stack(np.meshgrid(ax, ax - 0.72, ax, indexing="ij"), -1).reshape(-1, 3)
-    dpc.get_sdf_cost(q[:1000])
-    t0 = time.perf_counter()
-    c = dpc.get_sdf_cost(q)
-    dt = time.perf_counter() - t0
-    print(f"{H}x{W} depth ({(depth > 0).sum()} points), {n}^3 = {q.shape[0]} voxels: {1e3 * dt:8.1f} ms  "
+    dpc.get_sdf_cost(q)  # warm-up
+    ts = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        c = dpc.get_sdf_cost(q)
+        ts.append(time.perf_counter() - t0)
+    dt = statistics.median(ts)
+    print(f"{H}x{W} depth ({(depth > 0).sum()} points), {n}^3 = {q.shape[0]} voxels: {1e3 * dt:8.2f} ms [{1e3 * min(ts):.2f} .. {1e3 * max(ts):.2f}]  "
           f"({q.shape[0] * H * W / dt / 1e9:.1f} G point-pairs/s), non-zero cost voxels {int((c > 0).sum())}")
