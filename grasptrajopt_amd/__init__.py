@@ -10,6 +10,7 @@ GTOPlanner.plan()/plan_goalset().  Public surface:
     SurfacePointCloud                    drop-in for mesh_to_sdf.surface_point_cloud (cost fields of sampled meshes on the GPU)
     observation.Observation              a DepthPointCloud / SurfacePointCloud resident on the GPU + the collision checks against it
     BasePlanner                          drop-in for gto.base_planner (mobile base placement on the GPU)
+    occupancy.OccupancyGrid              the x-y occupancy grid of the mobile pipeline resident on the GPU
     optas_facade                         OptimizationBuilder / CasADiSolver-shaped recorder + solver
     _capi.SolverHandle                   thin ctypes binding of the C ABI (include/gto_solver.h)
 """

@@ -176,6 +176,11 @@ def load_library(path: Optional[str] = None):
     if v != ABI_VERSION:
         raise RuntimeError(f"{p}: ABI version {v}, this wrapper speaks {ABI_VERSION} (include/gto_solver.h GTO_ABI_VERSION): "
                            "rebuild the library from this tree (__graft_entry__.build())")
+    # entry points that were added without a new ABI number (include/gto_solver.h): a build from before them is refused by name
+    missing = [sym for sym in EXPORTED_SYMBOLS if not hasattr(lib, sym)]
+    if missing:
+        raise RuntimeError(f"{p}: ABI version {v} but no {', '.join(missing)}: an older build of this interface; "
+                           "rebuild the library from this tree (__graft_entry__.build())")
     H = C.c_void_p
     lib.gto_default_opts.argtypes = [C.POINTER(CSolverOpts)]
     lib.gto_default_opts.restype = None
@@ -242,6 +247,18 @@ def load_library(path: Optional[str] = None):
     lib.gto_seed_goalsets_device.argtypes = [H, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32, C.c_int32] + [C.c_void_p] * 8
     for fn in ("gto_solve_ik_pose_batch_device", "gto_ik_report_device", "gto_seed_goalsets_device"):
         getattr(lib, fn).restype = C.c_int
+    G = C.c_void_p  # gto_occupancy*
+    lib.gto_occupancy_from_observation.argtypes = [O, C.c_double, C.c_double, C.c_double, C.POINTER(G)]
+    lib.gto_occupancy_from_points.argtypes = [C.c_int, _pd, _i64, C.c_double, C.c_double, C.c_double, C.POINTER(G)]
+    lib.gto_occupancy_geometry.argtypes = [G, _pd, _pi, _pd, _pd]
+    lib.gto_occupancy_grid.argtypes = [G, _pu8]
+    lib.gto_occupancy_destroy.argtypes = [G]
+    lib.gto_occupancy_destroy.restype = None
+    lib.gto_solve_base_batch_device.argtypes = [H, C.c_int32, C.c_int32, _pi, C.c_void_p, C.c_void_p, C.c_double, C.c_int32] + [C.c_void_p] * 6
+    lib.gto_base_report_device.argtypes = [H, G, C.c_int32, C.c_int32, _pi] + [C.c_void_p] * 9
+    for fn in ("gto_occupancy_from_observation", "gto_occupancy_from_points", "gto_occupancy_geometry", "gto_occupancy_grid",
+               "gto_solve_base_batch_device", "gto_base_report_device"):
+        getattr(lib, fn).restype = C.c_int
     for fn in ("gto_observation_from_depth", "gto_observation_from_cloud", "gto_observation_sdf", "gto_observation_check_posed", "gto_check_plans",
                "gto_check_plans_device"):
         getattr(lib, fn).restype = C.c_int
@@ -267,6 +284,8 @@ EXPORTED_SYMBOLS = (
     "gto_observation_from_depth", "gto_observation_from_cloud", "gto_observation_destroy", "gto_observation_sdf",
     "gto_observation_check_posed", "gto_check_plans", "gto_check_plans_device",
     "gto_solve_ik_pose_batch_device", "gto_ik_report_device", "gto_seed_goalsets_device",
+    "gto_occupancy_from_observation", "gto_occupancy_from_points", "gto_occupancy_geometry", "gto_occupancy_grid",
+    "gto_occupancy_destroy", "gto_solve_base_batch_device", "gto_base_report_device",
 )
 
 
@@ -664,6 +683,28 @@ class SolverHandle:
                                                       _p(cost, _pd), _p(iters, _pi), _p(status, _pi)),
                         "gto_solve_base_batch")
         return y, q, cost, iters, status
+
+    # -------------------------------------------------------------- the stream-ordered base placement (BasePlanner.place_base)
+    def solve_base_batch_device(self, B, n_max, n_goals, qc, goals, effort_weight, max_iter, y_out, q_out, cost_out=None,
+                                iters_out=None, status_out=None, stream=None):
+        """gto_solve_base_batch_device: n_goals is a HOST int32 array (B,); every other array is a device pointer (an int,
+        e.g. torch.Tensor.data_ptr()) or None."""
+        ng = _i32(np.broadcast_to(np.asarray(n_goals), (int(B),)))
+        vp = lambda a: None if a is None else C.c_void_p(int(a))
+        self._check(self.lib.gto_solve_base_batch_device(self._h, int(B), int(n_max), _p(ng, _pi), vp(qc), vp(goals),
+                                                         float(effort_weight), int(max_iter), vp(y_out), vp(q_out), vp(cost_out),
+                                                         vp(iters_out), vp(status_out), vp(stream)), "gto_solve_base_batch_device")
+
+    def base_report_device(self, occ, B, n_max, n_goals, qc, goals, y, q, err_pos_out=None, err_rot_out=None,
+                           collision_out=None, first_free_out=None, stream=None):
+        """gto_base_report_device: err_pos / err_rot (degrees) of every goal, the footprint count of every set on the
+        occupancy grid ``occ`` (occupancy.OccupancyGrid or None) and the first free set; n_goals is a HOST array, the others
+        device pointers or None."""
+        ng = _i32(np.broadcast_to(np.asarray(n_goals), (int(B),)))
+        vp = lambda a: None if a is None else C.c_void_p(int(a))
+        self._check(self.lib.gto_base_report_device(self._h, None if occ is None else occ._ptr(), int(B), int(n_max), _p(ng, _pi),
+                                                    vp(qc), vp(goals), vp(y), vp(q), vp(err_pos_out), vp(err_rot_out),
+                                                    vp(collision_out), vp(first_free_out), vp(stream)), "gto_base_report_device")
 
     def eval_base_objective(self, y, q, goals, n_goals=None, effort_weight=0.01):
         """Base-placement objective (gto/base_planner.py:57-87) at y (B,3), q (B,n_max,ndof), goals (B,n_max,4,4)."""

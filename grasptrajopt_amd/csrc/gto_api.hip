@@ -26,6 +26,7 @@
 #include "gto_retime.h"
 #include "gto_observe.h"
 #include "gto_seed.h"
+#include "gto_occupancy.h"
 
 #define GTO_VERSION GTO_ABI_VERSION  // include/gto_solver.h
 #ifndef GTO_OBS_DEEP_PD
@@ -37,6 +38,7 @@ static std::string g_create_error;
 #define GTO_SWEEP_WGS 64   // workgroups of the crew behind an itemized obstacle launch laid out over an estimate (launch_obstacle)
 
 #define GTO_MAX_LANES 8  // lanes of one solve call (streams, list sets, progress words)
+#define GTO_BASE_PIN_SLOTS 4  // calls of the base placement chain whose n_goals may be in flight at once without the host waiting
 #define GTO_STAGE_SLOTS 8  // host arrays of each direction that one host-pointer entry point stages (Staging)
 #define GTO_NAP_US 50      // the throttle's naps (the host thread of a lane sleep-polls two pinned words); 10-50 us change nothing
 #define GTO_NAP_FEW_US 10  // ... in launches with few instances in flight; 50-200 us change nothing either
@@ -220,6 +222,12 @@ struct gto_handle {
   DevBuf ck_xyz, ck_flags, ck_base;
   // seed choice (gto_seed_goalsets_device): per-waypoint cost sums of the candidates [B][n_max][T]
   DevBuf sd_part;
+  // base placement with resident arrays (gto_solve_base_batch_device, gto_base_report_device): the device copy of the
+  // caller's n_goals, and the per-set counts when the caller asks for the choice alone
+  DevBuf bs_ng, bs_coll;
+  DevBuf bs_pin[GTO_BASE_PIN_SLOTS];           // pinned copies of n_goals, one per call in flight (base_counts_to_device)
+  hipEvent_t bs_pin_ev[GTO_BASE_PIN_SLOTS] = {};  // recorded behind the copy that reads slot k
+  int bs_pin_next = 0;
 };
 
 #define HIPCHK(h, call)                                                                              \
@@ -802,7 +810,7 @@ void gto_destroy(gto_handle* h) {
   (void)hipFree(h->d_chunks);
   (void)hipFree(h->d_pbimg);
   DevBuf* bufs[] = {&h->zws, &h->counters, &h->state, &h->Qcur, &h->Qtry, &h->vis, &h->screw, &h->blocks, &h->goalblk, &h->ssfixed, &h->ndone, &h->qf, &h->livebuf, &h->qfs, &h->wrecbuf, &h->itembuf,
-                   &h->rt_fac, &h->rt_S, &h->rt_flag, &h->rt_P1, &h->rt_P2, &h->rt_cap, &h->rt_X, &h->rt_T, &h->rt_stat, &h->ck_xyz, &h->ck_flags, &h->ck_base, &h->sd_part};
+                   &h->rt_fac, &h->rt_S, &h->rt_flag, &h->rt_P1, &h->rt_P2, &h->rt_cap, &h->rt_X, &h->rt_T, &h->rt_stat, &h->ck_xyz, &h->ck_flags, &h->ck_base, &h->sd_part, &h->bs_ng, &h->bs_coll};
   if (h->h_ndone) (void)hipHostFree(h->h_ndone);
   if (h->h_progress) (void)hipHostFree(h->h_progress);
   for (DevBuf* b : bufs) (void)hipFree(b->p);
@@ -811,6 +819,8 @@ void gto_destroy(gto_handle* h) {
   for (auto& b : h->out) (void)hipFree(b.p);
   for (auto& b : h->pin_in) if (b.p) (void)hipHostFree(b.p);
   for (auto& b : h->pin_out) if (b.p) (void)hipHostFree(b.p);
+  for (auto& b : h->bs_pin) if (b.p) (void)hipHostFree(b.p);
+  for (auto e : h->bs_pin_ev) if (e) (void)hipEventDestroy(e);
   for (auto e : h->ev) (void)hipEventDestroy(e);
   if (h->stream && h->own_stream) (void)hipStreamDestroy(h->stream);
   for (int l = 0; l < GTO_MAX_LANES; ++l) {
@@ -2091,19 +2101,69 @@ int gto_seed_goalsets_device(gto_handle* h, int32_t B, int32_t n_max, const int3
   return GTO_OK;
 }
 
-// gto_solve_base_batch and gto_eval_base_objective after their own B check; `null_input`: one of the arrays the entry point
-// needs is null.  A solve starts from qc.  An evaluation passes the point (y0, q0) with max_iter 0 and no y_out / q_out:
-// qc is the first goal's configuration of every set in q0, and the point k_base_solve writes back stays on the device.
+// What every base-placement entry point checks once its own B check is done; `null_input`: one of the arrays the entry
+// point needs is null.  GTO_OK with *empty set for B == 0.
+static int base_check(gto_handle* h, const char* name, int32_t B, int32_t n_max, const int32_t* n_goals, bool null_input, bool* empty) {
+  *empty = false;
+  if (n_max < 1 || n_max > GTO_MAX_BASE_GOALS) return fail(h, GTO_ERR_UNSUPPORTED, "n_max must be in [1, 32]");
+  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, std::string(name) + " handles up to eight optimised joints");
+  if (B == 0) {
+    *empty = true;
+    return GTO_OK;
+  }
+  if (null_input) return fail(h, GTO_ERR_INVALID_ARG, "null input array");
+  for (int b = 0; b < B; ++b)
+    if (n_goals[b] < 1 || n_goals[b] > n_max) return fail(h, GTO_ERR_INVALID_ARG, "n_goals[b] must be in [1, n_max]");
+  return GTO_OK;
+}
+
+// The launch of k_base_solve over B goal sets whose arrays are on the device, on stream st: what the host-pointer and the
+// device-pointer entry points share
+static int base_launch(gto_handle* h, int32_t B, int32_t n_max, const double* d_qc, const double* d_goals, const int32_t* d_ng,
+                       double effort_weight, int32_t max_iter, const double* d_y0, const double* d_q0, double* d_y, double* d_q,
+                       double* d_cost, int32_t* d_it, int32_t* d_stat, hipStream_t st) {
+  SolveParams sp = make_params(h, 1, false);
+  sp.max_iter = max_iter;
+  const size_t lds = (size_t)base_lds_doubles(n_max) * sizeof(double);
+  if (lds > 160 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "goal set too large for the base kernel's LDS");
+  HIPCHK(h, raise_dynamic_lds((const void*)k_base_solve, lds));
+  hipLaunchKernelGGL(k_base_solve, dim3(B), dim3(256), lds, st, h->d_rb, d_qc, d_goals, d_ng, sp, effort_weight, n_max,
+                     d_y, d_q, d_cost, d_it, d_stat, d_y0, d_q0);
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
+}
+
+// The caller's n_goals [B] (host, checked) on the device, ordered on `st` in front of the kernel that reads it.  The array is
+// copied into a pinned slot of the handle first, so the caller's array is free on return whatever memory it lives in, and
+// the transfer is a real asynchronous DMA.  A slot is reused once the copy that read it has run (its event; with
+// GTO_BASE_PIN_SLOTS calls in flight the host waits for the oldest).  bs_ng is one device buffer per handle: calls on one
+// handle go to one stream, or the caller orders them.
+static int base_counts_to_device(gto_handle* h, int32_t B, const int32_t* n_goals, hipStream_t st, const int32_t** d_ng) {
+  const size_t bytes = (size_t)B * sizeof(int32_t);
+  int rc = ensure(h, h->bs_ng, bytes);
+  if (rc) return rc;
+  const int k = h->bs_pin_next;
+  h->bs_pin_next = (k + 1) % GTO_BASE_PIN_SLOTS;
+  if (!h->bs_pin_ev[k]) HIPCHK(h, hipEventCreateWithFlags(&h->bs_pin_ev[k], hipEventDisableTiming));
+  else HIPCHK(h, hipEventSynchronize(h->bs_pin_ev[k]));
+  if ((rc = ensure_pinned(h, h->bs_pin[k], bytes))) return rc;
+  memcpy(h->bs_pin[k].p, n_goals, bytes);
+  HIPCHK(h, hipMemcpyAsync(h->bs_ng.p, h->bs_pin[k].p, bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipEventRecord(h->bs_pin_ev[k], st));
+  *d_ng = (const int32_t*)h->bs_ng.p;
+  return GTO_OK;
+}
+
+// gto_solve_base_batch and gto_eval_base_objective after their own B check.  A solve starts from qc.  An evaluation passes
+// the point (y0, q0) with max_iter 0 and no y_out / q_out: qc is the first goal's configuration of every set in q0, and the
+// point k_base_solve writes back stays on the device.
 static int base_batch(gto_handle* h, const char* name, int32_t B, int32_t n_max, const int32_t* n_goals, bool null_input,
                       const double* qc, const double* goals, double effort_weight, int32_t max_iter, const double* y0,
                       const double* q0, double* y_out, double* q_out, double* cost_out, int32_t* iters_out,
                       int32_t* status_out) {
-  if (n_max < 1 || n_max > GTO_MAX_BASE_GOALS) return fail(h, GTO_ERR_UNSUPPORTED, "n_max must be in [1, 32]");
-  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, std::string(name) + " handles up to eight optimised joints");
-  if (B == 0) return GTO_OK;
-  if (null_input) return fail(h, GTO_ERR_INVALID_ARG, "null input array");
-  for (int b = 0; b < B; ++b)
-    if (n_goals[b] < 1 || n_goals[b] > n_max) return fail(h, GTO_ERR_INVALID_ARG, "n_goals[b] must be in [1, n_max]");
+  bool empty;
+  int rc = base_check(h, name, B, n_max, n_goals, null_input, &empty);
+  if (rc || empty) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   const size_t ndof = h->rb.ndof, nB = B;
   std::vector<double> qc_eval;
@@ -2117,7 +2177,6 @@ static int base_batch(gto_handle* h, const char* name, int32_t B, int32_t n_max,
   const int32_t* d_ng;
   double *d_q, *d_y, *d_cost;
   int32_t *d_it, *d_stat;
-  int rc;
   if ((rc = io.in(qc, nB * ndof, &d_qc))) return rc;
   if ((rc = io.in(goals, nB * n_max * 16, &d_goals))) return rc;
   if ((rc = io.in(n_goals, nB, &d_ng))) return rc;
@@ -2128,14 +2187,8 @@ static int base_batch(gto_handle* h, const char* name, int32_t B, int32_t n_max,
   if ((rc = io.out(cost_out, nB, &d_cost))) return rc;
   if ((rc = io.out(iters_out, nB, &d_it))) return rc;
   if ((rc = io.out(status_out, nB, &d_stat))) return rc;
-  SolveParams sp = make_params(h, 1, false);
-  sp.max_iter = max_iter;
-  const size_t lds = (size_t)base_lds_doubles(n_max) * sizeof(double);
-  if (lds > 160 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "goal set too large for the base kernel's LDS");
-  HIPCHK(h, raise_dynamic_lds((const void*)k_base_solve, lds));
-  hipLaunchKernelGGL(k_base_solve, dim3(B), dim3(256), lds, h->stream, h->d_rb, d_qc, d_goals, d_ng, sp, effort_weight, n_max,
-                     d_y, d_q, d_cost, d_it, d_stat, d_y0, d_q0);
-  HIPCHK(h, hipGetLastError());
+  if ((rc = base_launch(h, B, n_max, d_qc, d_goals, d_ng, effort_weight, max_iter, d_y0, d_q0, d_y, d_q, d_cost, d_it, d_stat, h->stream)))
+    return rc;
   return io.finish();
 }
 
@@ -2146,6 +2199,22 @@ int gto_solve_base_batch(gto_handle* h, int32_t B, int32_t n_max, const int32_t*
   if (B < 0 || max_iter < 0) return fail(h, GTO_ERR_INVALID_ARG, "B and max_iter must be >= 0");
   return base_batch(h, "gto_solve_base_batch", B, n_max, n_goals, !n_goals || !qc || !goals || !y_out || !q_out, qc, goals,
                     effort_weight, max_iter, nullptr, nullptr, y_out, q_out, cost_out, iters_out, status_out);
+}
+
+int gto_solve_base_batch_device(gto_handle* h, int32_t B, int32_t n_max, const int32_t* n_goals, const double* qc,
+                                const double* goals, double effort_weight, int32_t max_iter, double* y_out, double* q_out,
+                                double* cost_out, int32_t* iters_out, int32_t* status_out, void* stream) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (B < 0 || max_iter < 0) return fail(h, GTO_ERR_INVALID_ARG, "B and max_iter must be >= 0");
+  bool empty;
+  int rc = base_check(h, "gto_solve_base_batch_device", B, n_max, n_goals, !n_goals || !qc || !goals || !y_out || !q_out, &empty);
+  if (rc || empty) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  const int32_t* d_ng;
+  if ((rc = base_counts_to_device(h, B, n_goals, st, &d_ng))) return rc;
+  return base_launch(h, B, n_max, qc, goals, d_ng, effort_weight, max_iter, nullptr, nullptr, y_out, q_out, cost_out, iters_out,
+                     status_out, st);
 }
 
 #ifdef GTO_DEBUG_BASE_TIMING
@@ -3326,6 +3395,166 @@ int gto_check_plans(gto_handle* h, gto_observation* o, int32_t B, const double* 
   if ((rc = io.out(count_out, (size_t)B * h->opts.T, &d_count))) return rc;
   if ((rc = gto_check_plans_device(h, o, B, d_plans, base_pos, per_plan_base, d_count, nullptr))) return rc;
   return io.finish();
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ a resident occupancy grid and the placement report (gto_occupancy.h)
+struct gto_occupancy {
+  int device = 0;
+  double origin[2] = {0, 0}, xlim[2] = {0, 0}, ylim[2] = {0, 0}, res = 0;
+  int32_t shape[2] = {0, 0};
+  uint8_t* grid = nullptr;  // device, [nx][ny], 0 / 1; freed by gto_occupancy_destroy
+};
+
+namespace {
+// what both builders check of their numbers before any device work
+int check_occupancy_params(const char* who, double margin, double res, double epsilon) {
+  const std::string w(who);
+  if (!(res > 0.0) || !std::isfinite(res) || !std::isfinite(margin) || !(epsilon >= 0.0) || !std::isfinite(epsilon))
+    return fail(nullptr, GTO_ERR_INVALID_ARG, w + ": margin, resolution > 0 and epsilon >= 0 must be finite");
+  if (std::ceil(epsilon / res) > GTO_OCC_MAX_K) return fail(nullptr, GTO_ERR_UNSUPPORTED, w + ": epsilon beyond eight grid steps");
+  return GTO_OK;
+}
+// The grid of GTORobotModel.setup_occupancy_grid (gto/gto_models.py:218-244) from points on the device, on the null stream,
+// synchronous.  The lease is the caller's: everything but the grid goes back to the pool with it.
+int build_occupancy(DepthLease& c, const OccPoints& pts, double margin, double res, double epsilon, gto_occupancy** out) {
+  const std::string w(c.who);
+  const int k = (int)std::ceil(epsilon / res);
+  const unsigned blocks = (unsigned)std::min<long>(1024, std::max<long>(1, (pts.n + 255) / 256));
+  double* d_part = c.alloc<double>((size_t)blocks * GTO_OCC_PART);
+  if (!d_part) return c.no_memory();
+  hipLaunchKernelGGL(k_occ_bounds, dim3(blocks), dim3(256), 0, 0, pts, d_part);
+  DEPTH_TRY(c.sync());
+  std::vector<double> part((size_t)blocks * GTO_OCC_PART);
+  DEPTH_TRY(c.download(part.data(), d_part, part.size()));
+  double xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
+  bool bad = false;
+  for (unsigned i = 0; i < blocks; ++i) {
+    const double* p = &part[(size_t)i * GTO_OCC_PART];
+    xmax = std::max(xmax, p[0]), ymin = std::min(ymin, p[1]), ymax = std::max(ymax, p[2]), bad = bad || p[3] != 0.0;
+  }
+  if (!bad && ymin == INFINITY) return fail(nullptr, GTO_ERR_INVALID_ARG, w + ": no point with z > 0.01");
+  if (bad || !std::isfinite(xmax)) return fail(nullptr, GTO_ERR_UNSUPPORTED, w + ": the points' bounds are not finite");
+  std::unique_ptr<gto_occupancy> o(new gto_occupancy);
+  o->device = c.device, o->res = res;
+  o->xlim[0] = 0.0, o->xlim[1] = xmax, o->ylim[0] = ymin, o->ylim[1] = ymax;
+  o->origin[0] = o->xlim[0] - margin, o->origin[1] = o->ylim[0] - margin;
+  // the axes' lengths as numpy.arange counts them, as doubles: a finite but enormous coordinate is refused before anything
+  // of that size is allocated
+  const double lx = std::ceil(((o->xlim[1] + margin) - (o->xlim[0] - margin)) / res), ly = std::ceil(((o->ylim[1] + margin) - (o->ylim[0] - margin)) / res);
+  const double most = (double)((size_t)1 << 26);
+  if (!(lx >= 1.0 && ly >= 1.0 && lx <= most && ly <= most && lx * ly <= most))
+    return fail(nullptr, GTO_ERR_UNSUPPORTED, w + ": empty grid or more than 2^26 nodes");
+  const std::vector<double> xg = np_arange(o->xlim[0] - margin, o->xlim[1] + margin, res);
+  const std::vector<double> yg = np_arange(o->ylim[0] - margin, o->ylim[1] + margin, res);
+  if (xg.empty() || yg.empty() || xg.size() > ((size_t)1 << 26) || yg.size() > ((size_t)1 << 26) || xg.size() * yg.size() > ((size_t)1 << 26))
+    return fail(nullptr, GTO_ERR_UNSUPPORTED, w + ": empty grid or more than 2^26 nodes");
+  o->shape[0] = (int32_t)xg.size(), o->shape[1] = (int32_t)yg.size();
+  const size_t nodes = xg.size() * yg.size();
+  const double *d_xg, *d_yg;
+  DEPTH_TRY(c.upload(xg.data(), xg.size(), &d_xg));
+  DEPTH_TRY(c.upload(yg.data(), yg.size(), &d_yg));
+  uint8_t* d_grid = c.alloc<uint8_t>(nodes);
+  if (!d_grid) return c.no_memory();
+  DEPTH_TRY(c.hip(hipMemset(d_grid, 0, nodes)));
+  hipLaunchKernelGGL(k_occ_mark, dim3((unsigned)((pts.n + 255) / 256)), dim3(256), 0, 0, pts, d_xg, d_yg, o->shape[0], o->shape[1], res,
+                     epsilon, k, d_grid);
+  DEPTH_TRY(c.sync());
+  o->grid = (uint8_t*)c.keep(d_grid);
+  *out = o.release();
+  return GTO_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int gto_occupancy_from_observation(gto_observation* obs, double margin, double resolution, double epsilon, gto_occupancy** out) {
+  if (out) *out = nullptr;
+  if (!out || !obs) return fail(nullptr, GTO_ERR_INVALID_ARG, "gto_occupancy_from_observation: null observation or output");
+  DEPTH_TRY(check_occupancy_params("gto_occupancy_from_observation", margin, resolution, epsilon));
+  if (hipSetDevice(obs->device) != hipSuccess) return fail(nullptr, GTO_ERR_NO_DEVICE, "hipSetDevice failed");
+  DepthLease c(nullptr, "gto_occupancy_from_observation", obs->device);
+  OccPoints pts;
+  if (obs->is_depth) pts = {obs->depth.px, obs->depth.py, obs->depth.pz, (long)obs->depth.H * obs->depth.W, 1, 1};
+  else pts = {obs->cloud.points, obs->cloud.points + 1, obs->cloud.points + 2, (long)obs->cloud.n, 3, 0};
+  return build_occupancy(c, pts, margin, resolution, epsilon, out);
+}
+
+int gto_occupancy_from_points(int device, const double* points, int64_t n, double margin, double resolution, double epsilon,
+                              gto_occupancy** out) {
+  if (out) *out = nullptr;
+  if (!out || !points || n < 1) return fail(nullptr, GTO_ERR_INVALID_ARG, "gto_occupancy_from_points: null or empty input");
+  if (n > ((int64_t)1 << 28)) return fail(nullptr, GTO_ERR_UNSUPPORTED, "gto_occupancy_from_points: more than 2^28 points");
+  DEPTH_TRY(check_occupancy_params("gto_occupancy_from_points", margin, resolution, epsilon));
+  int cur_dev;
+  DEPTH_TRY(select_device(device, &cur_dev));
+  DepthLease c(nullptr, "gto_occupancy_from_points", cur_dev);
+  const double* d_p;
+  DEPTH_TRY(c.upload(points, (size_t)n * 3, &d_p));
+  return build_occupancy(c, {d_p, d_p + 1, d_p + 2, (long)n, 3, 0}, margin, resolution, epsilon, out);
+}
+
+int gto_occupancy_geometry(const gto_occupancy* occ, double* origin, int32_t* shape, double* xlim, double* ylim) {
+  if (!occ) return fail(nullptr, GTO_ERR_INVALID_ARG, "gto_occupancy_geometry: null occupancy grid");
+  if (origin) std::memcpy(origin, occ->origin, sizeof occ->origin);
+  if (shape) std::memcpy(shape, occ->shape, sizeof occ->shape);
+  if (xlim) std::memcpy(xlim, occ->xlim, sizeof occ->xlim);
+  if (ylim) std::memcpy(ylim, occ->ylim, sizeof occ->ylim);
+  return GTO_OK;
+}
+
+int gto_occupancy_grid(gto_occupancy* occ, uint8_t* out) {
+  if (!occ || !out) return fail(nullptr, GTO_ERR_INVALID_ARG, "gto_occupancy_grid: null occupancy grid or output");
+  if (hipSetDevice(occ->device) != hipSuccess) return fail(nullptr, GTO_ERR_NO_DEVICE, "hipSetDevice failed");
+  const hipError_t e = hipMemcpy(out, occ->grid, (size_t)occ->shape[0] * occ->shape[1], hipMemcpyDeviceToHost);
+  return e == hipSuccess ? GTO_OK : fail(nullptr, GTO_ERR_HIP, std::string("gto_occupancy_grid: ") + hipGetErrorString(e));
+}
+
+void gto_occupancy_destroy(gto_occupancy* occ) {
+  if (!occ) return;
+  int cur = -1;
+  (void)hipGetDevice(&cur);
+  (void)hipSetDevice(occ->device);
+  (void)hipDeviceSynchronize();  // nothing may still be reading it
+  (void)hipFree(occ->grid);
+  if (cur >= 0) (void)hipSetDevice(cur);  // the caller's current device is the caller's
+  delete occ;
+}
+
+int gto_base_report_device(gto_handle* h, gto_occupancy* occ, int32_t B, int32_t n_max, const int32_t* n_goals, const double* qc,
+                           const double* goals, const double* y, const double* q, double* err_pos_out, double* err_rot_out,
+                           int32_t* collision_out, int32_t* first_free_out, void* stream) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (B < 0) return fail(h, GTO_ERR_INVALID_ARG, "gto_base_report_device: B must be >= 0");
+  if (!occ && (collision_out || first_free_out))
+    return fail(h, GTO_ERR_INVALID_ARG, "gto_base_report_device: collision_out and first_free_out need an occupancy grid");
+  if (occ && occ->device != h->device)
+    return fail(h, GTO_ERR_INVALID_ARG, "gto_base_report_device: the occupancy grid lives on another device than the handle");
+  bool empty;
+  int rc = base_check(h, "gto_base_report_device", B, n_max, n_goals, !n_goals || !qc || !goals || !y || !q, &empty);
+  if (rc || empty) return rc;
+  if (B > 65535) return fail(h, GTO_ERR_UNSUPPORTED, "gto_base_report_device: at most 65535 goal sets in one call");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  const bool count = occ && (collision_out || first_free_out);
+  if (!count && !err_pos_out && !err_rot_out) return GTO_OK;
+  const size_t lds = sizeof(double) * plan_cost_lds_doubles_tg(1, h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
+  if (lds > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the report kernel's LDS");
+  const int32_t* d_ng;
+  if ((rc = base_counts_to_device(h, B, n_goals, st, &d_ng))) return rc;
+  if (count && !collision_out) {  // the choice alone: the counts stay in the handle's workspace
+    if ((rc = ensure(h, h->bs_coll, (size_t)B * sizeof(int32_t)))) return rc;
+    collision_out = (int32_t*)h->bs_coll.p;
+  }
+  OccGridView og = {};
+  if (count) og = {occ->grid, occ->shape[0], occ->shape[1], occ->origin[0], occ->origin[1], occ->res};
+  HIPCHK(h, raise_dynamic_lds((const void*)k_base_report, lds));
+  hipLaunchKernelGGL(k_base_report, dim3((unsigned)(n_max + (count ? 1 : 0)), (unsigned)B), dim3(256), lds, st, h->d_rb, h->d_px, h->d_py,
+                     h->d_pz, h->d_plink, d_ng, qc, goals, y, q, n_max, og, err_pos_out, err_rot_out, count ? collision_out : nullptr);
+  if (first_free_out) hipLaunchKernelGGL(k_base_first_free, dim3(1), dim3(64), 0, st, collision_out, B, first_free_out);
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
 }
 
 }  // extern "C"

@@ -308,7 +308,31 @@ class GTORobotModel:
     def setup_occupancy_grid(self, points, epsilon=0.02):
         """gto/gto_models.py:218-244: grid nodes of the x-y plane that have an observed point (z > 0.01)
         within `epsilon`.  The reference asks a KD-tree for every node's nearest point; equivalently every
-        point marks the nodes within `epsilon` of it (one scatter pass, no tree)."""
+        point marks the nodes within `epsilon` of it (one scatter pass, no tree).
+
+        Given the lazy device-resident points of a DepthPointCloud (depth_scene.LazyCloudPoints) the grid is built on the
+        device from the cloud's resident observation (occupancy.OccupancyGrid), without bringing the cloud to the host: the
+        same attributes, bit for bit, and the resident grid stays on the robot (``occupancy``) for BasePlanner.place_base.
+        Given an array, the numpy pass below."""
+        from .depth_scene import LazyCloudPoints
+        old = self.__dict__.pop("occupancy", None)
+        if old is not None:
+            old.close()
+        if isinstance(points, LazyCloudPoints) and points._value is None:
+            from .occupancy import OccupancyGrid
+            m, r = self.field_margin, self.grid_resolution
+            occ = OccupancyGrid.from_observation(points.dpc.observation(), m, r, epsilon)
+            self.occupancy = occ
+            self.xlim_2d = [0, np.float64(occ.xlim[1])]
+            self.ylim_2d = [np.float64(occ.ylim[0]), np.float64(occ.ylim[1])]
+            self.occupancy_grid_origin = np.array([self.xlim_2d[0] - m, self.ylim_2d[0] - m]).reshape((1, 2))
+            self.xgrid = np.arange(self.xlim_2d[0] - m, self.xlim_2d[1] + m, r)
+            self.ygrid = np.arange(self.ylim_2d[0] - m, self.ylim_2d[1] + m, r)
+            self.occupancy_grid_shape = (len(self.xgrid), len(self.ygrid))
+            assert self.occupancy_grid_shape == occ.shape
+            self.occupancy_grid_size = occ.size
+            self.occupancy_grid = occ.grid.astype(np.float64).reshape(-1, 1)
+            return
         points = np.asarray(points, dtype=np.float64)
         xys = points[points[:, 2] > 0.01, :2]
         m, r = self.field_margin, self.grid_resolution
@@ -362,6 +386,9 @@ class GTORobotModel:
         return float(cost[0]), float(dist[0])
 
     def close(self):
+        occ = self.__dict__.pop("occupancy", None)
+        if occ is not None:
+            occ.close()
         for h in self._handles.values():
             h.close()
         self._handles.clear()

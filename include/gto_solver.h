@@ -118,7 +118,9 @@ void gto_default_opts(gto_solver_opts* opts);
 
 /* Library/ABI version (major*1000 + minor): GTO_ABI_VERSION of the header the library was built from.  A binding checks it
  * when it loads the library and refuses another number (grasptrajopt_amd/_capi.py load_library): every change of a
- * signature or of a struct in this header bumps the minor. */
+ * signature or of a struct in this header bumps the minor.  Entry points that are only ADDED leave it alone (the occupancy
+ * grid and the base placement chain at the end of this header came that way): no existing call changes its meaning, and a
+ * binding that needs them refuses a library that lacks them by name (grasptrajopt_amd/_capi.py load_library). */
 #define GTO_ABI_VERSION 1012
 int32_t gto_version(void);
 
@@ -269,8 +271,8 @@ int gto_solve_ik_pose_batch(gto_handle* h, int32_t goal_kind, int32_t B, const i
  *   max_iter  iteration cap (reference IPOPT cap: 100, :95)
  * Outputs (host): y_out [B][3] = (x, y, theta), the old base in the new base frame (:52);
  * q_out [B][n_max][ndof] arm configuration per goal (rows >= n_goals[b]: qc); cost_out, iters_out,
- * status_out as in gto_solve_batch (may be NULL).  err_pos / err_rot (:127-143) follow from gto_eval_fk,
- * the occupancy statistic (:146-158) from gto_eval_points' transformed points.
+ * status_out as in gto_solve_batch (may be NULL).  err_pos / err_rot (:127-143) and the occupancy statistic (:146-158)
+ * of the solution: gto_base_report_device below (on the host: gto_eval_fk and gto_eval_points' transformed points).
  * Replaces: BasePlanner.setup_optimization + the solve inside plan_goalset (gto/base_planner.py:35-123).
  */
 int gto_solve_base_batch(gto_handle* h, int32_t B, int32_t n_max, const int32_t* n_goals, const double* qc,
@@ -626,6 +628,70 @@ int gto_seed_goalsets_device(gto_handle* h, int32_t B, int32_t n_max, const int3
                              const double* base_pos, int32_t interpolate, int32_t solutions_f32, double* goals_out,
                              int32_t* n_goals_out, int32_t* n_accepted_out, double* Q0_out, int32_t* seed_index_out,
                              double* seed_cost_out, double* seed_dist_out, void* stream);
+
+/*
+ * ---- the stream-ordered base placement loop (examples/pybullet_gto_planning_mobile.py:157-202, gto/base_planner.py:96-168) ---
+ * The driver draws grasps, places the base for them, and draws again until the robot's footprint at the new base is free:
+ * one host round trip per draw.  Here many draws go in and the first free one comes out: gto_solve_base_batch_device ->
+ * gto_base_report_device on one stream, against a resident occupancy grid, with one synchronisation at the end.
+ *
+ * A gto_occupancy is the x-y occupancy grid of GTORobotModel.setup_occupancy_grid (gto/gto_models.py:218-244) on the device:
+ * bound to one HIP device, independent of any handle, owner of its device memory until gto_occupancy_destroy.  Of the points
+ * with z > 0.01: xlim = [0, max x], ylim = [min y, max y], axes numpy.arange(lim_lo - margin, lim_hi + margin, resolution); a
+ * node is 1 when a point lies within epsilon of it (the reference asks a KD-tree per node), FP64 in numpy's order without
+ * contraction: the grid is bit-equal to the reference's (tests/golden/occupancy.npz).  Creation is synchronous.
+ * gto_occupancy_from_observation: the back-projected points of a depth observation (invalid and masked pixels left out) or
+ * the samples of a cloud observation, without a copy through the host.  gto_occupancy_from_points: host points [n][3].
+ * GTO_ERR_INVALID_ARG: null or empty input, non-finite margin / resolution / epsilon, resolution <= 0, epsilon < 0, no point
+ * with z > 0.01 (numpy raises there).  GTO_ERR_UNSUPPORTED: a non-finite bound, ceil(epsilon / resolution) > 8, more than
+ * 2^26 nodes.  Both validate before any device work (GTO_ERR_INVALID_ARG before GTO_ERR_NO_DEVICE); errors are read with
+ * gto_last_error(NULL).
+ * gto_occupancy_geometry: origin [2], shape [2] = (nx, ny), xlim [2], ylim [2] (each may be NULL).  gto_occupancy_grid: the
+ * grid row-major [nx][ny], 0 or 1, device to host.
+ */
+typedef struct gto_occupancy gto_occupancy;
+int gto_occupancy_from_observation(gto_observation* obs, double margin, double resolution, double epsilon, gto_occupancy** out);
+int gto_occupancy_from_points(int device, const double* points, int64_t n, double margin, double resolution, double epsilon,
+                              gto_occupancy** out);
+int gto_occupancy_geometry(const gto_occupancy* occ, double* origin, int32_t* shape, double* xlim, double* ylim);
+int gto_occupancy_grid(gto_occupancy* occ, uint8_t* out);
+void gto_occupancy_destroy(gto_occupancy* occ);
+
+/*
+ * gto_solve_base_batch with qc, goals and the outputs resident in device memory, enqueued on `stream` (NULL = the handle's
+ * stream) without a host synchronisation: the same kernel, grid and LDS, results bit-equal to the host-pointer call.  n_goals
+ * [B] stays a HOST array (the rule of base_pos / vmax elsewhere): it is checked as in gto_solve_base_batch and copied in front
+ * of the launch on `stream` through pinned memory of the handle; the caller's array is free on return (with four such
+ * calls of a handle still in flight the host waits for the oldest copy).  y_out and q_out are required; cost_out, iters_out and
+ * status_out may be NULL.  The copy of n_goals lives on the handle: calls on one handle go to one stream, or the caller
+ * orders them (the rule of gto_check_plans_device).
+ */
+int gto_solve_base_batch_device(gto_handle* h, int32_t B, int32_t n_max, const int32_t* n_goals, const double* qc,
+                                const double* goals, double effort_weight, int32_t max_iter, double* y_out, double* q_out,
+                                double* cost_out, int32_t* iters_out, int32_t* status_out, void* stream);
+/*
+ * What the reference reports of a base placement (gto/base_planner.py:127-162) and the driver's choice among draws, for B
+ * goal sets: qc [B][ndof], goals [B][n_max][16], y [B][3] and q [B][n_max][ndof] as gto_solve_base_batch_device wrote them,
+ * all in device memory; n_goals [B] a HOST array as there; enqueued on `stream` without a host synchronisation.
+ *   per goal i < n_goals[b]   RT = B(y_b) RT_i G(q_i), B = rt2tr(rotz(theta), [x, y, 0]), G = T_ee(q_i)^-1 T_g(q_i) (the
+ *       rigid inverse in closed form):  err_pos_out [b][i] = |RT[:3,3] - T_g(q_i)[:3,3]|,  err_rot_out [b][i] =
+ *       degrees(arccos(clip((trace(R_RT^T R_g) - 1) / 2, -1, 1))); kinematics behind gto_eval_fk; rows >= n_goals[b] are left
+ *       untouched.
+ *   per set   the handle's P surface points at qc_b (gto_eval_points' expression with a zero base) in the new
+ *       base frame, x' = c (x - y0) + s (yy - y1), y' = -s (x - y0) + c (yy - y1), c, s = cos, sin theta, FP64 without
+ *       contraction; their nodes floor((. - origin) / resolution) clipped per axis (points_to_offsets_occupancy_numpy,
+ *       gto/gto_models.py:262-273); collision_out [b] = how many of them are marked = the reference's `cost` (the grid is
+ *       0 / 1); -1 when y_b or qc_b has a non-finite entry, which changes no other set's result.
+ *   the choice   first_free_out [0] = the lowest b with collision_out [b] == 0, or -1: the driver's `if cost == 0: break`
+ *       over the draws in order.
+ * Any output may be NULL.  occ may be NULL: then collision_out and first_free_out must be NULL too.  `occ` on another device
+ * than the handle's: GTO_ERR_INVALID_ARG.  More than eight optimised joints, n_max outside [1, 32], B > 65535:
+ * GTO_ERR_UNSUPPORTED.  B = 0: GTO_OK without a launch.  Every set's result is bit for bit the same in any batch and at any
+ * position in it.
+ */
+int gto_base_report_device(gto_handle* h, gto_occupancy* occ, int32_t B, int32_t n_max, const int32_t* n_goals, const double* qc,
+                           const double* goals, const double* y, const double* q, double* err_pos_out, double* err_rot_out,
+                           int32_t* collision_out, int32_t* first_free_out, void* stream);
 
 #ifdef __cplusplus
 }
