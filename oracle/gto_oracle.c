@@ -1151,7 +1151,7 @@ static void solve_ik_instance(const gto_robot_desc* d, const gto_solver_opts* o,
       for (int j = 0; j < n; ++j) {
         double v = cur.A[i * n + j];
         if (act[i] || act[j]) v = (i == j) ? 1.0 : 0.0;
-        else if (i == j) v *= (1.0 + lambda);
+        else if (i == j) v = v == 0.0 ? lambda : v * (1.0 + lambda); /* a joint no residual depends on */
         D[i * n + j] = v;
       }
       rhs[i] = act[i] ? 0.0 : -cur.b[i];

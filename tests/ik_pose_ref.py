@@ -36,6 +36,34 @@ def quat_of(R):
     return np.array([(R02 + R20) * s, (R12 + R21) * s, z, (R10 - R01) * s])
 
 
+def shepperd_branch(R):
+    """The pivot quat_of takes: 0 for w, 1, 2, 3 for x, y, z."""
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr >= R[0, 0] and tr >= R[1, 1] and tr >= R[2, 2]:
+        return 0
+    if R[0, 0] >= R[1, 1] and R[0, 0] >= R[2, 2]:
+        return 1
+    return 2 if R[1, 1] >= R[2, 2] else 3
+
+
+def shepperd_margin(R):
+    """How far the pivot's quantity (the largest of tr, R00, R11, R22) lies above the runner-up."""
+    v = np.sort([R[0, 0] + R[1, 1] + R[2, 2], R[0, 0], R[1, 1], R[2, 2]])
+    return float(v[3] - v[2])
+
+
+def small_rotations(eta):
+    """The six rotations by +-eta about the world axes."""
+    out = []
+    for a in range(3):
+        for s in (eta, -eta):
+            K = np.zeros((3, 3))
+            i, j = (a + 1) % 3, (a + 2) % 3
+            K[j, i], K[i, j] = 1.0, -1.0
+            out.append(np.eye(3) + np.sin(s) * K + (1.0 - np.cos(s)) * K @ K)  # Rodrigues
+    return out
+
+
 def rpy_of(R):
     """optas Quaternion.getrpy in matrix entries: pitch +pi/2 whenever |R20| >= 1 (-1 included)."""
     pitch = np.pi / 2.0 if abs(R[2, 0]) >= 1.0 else np.arcsin(-R[2, 0])
@@ -125,8 +153,8 @@ def jacobian(kind, T, g, S):
 class PoseProblem:
     """f(x), b(x), A(x) of one instance (no collision term) as functions of the optimised joints."""
 
-    def __init__(self, oracle_obj, desc, link_ee, kind, q_full, g):
-        self.o, self.d, self.kind = oracle_obj, desc, kind
+    def __init__(self, oracle_obj, desc, link_ee, kind, q_full, g, rot=None):
+        self.o, self.d, self.kind, self.rot = oracle_obj, desc, kind, rot  # rot: a 3x3 turned onto link_ee's rotation
         self.fe = desc.frame_index(link_ee)
         self.q_full = np.array(q_full, dtype=np.float64)
         self.g = np.asarray(g, dtype=np.float64)
@@ -140,7 +168,10 @@ class PoseProblem:
     def frames(self, X):
         Q = np.repeat(self.q_full[None], len(X), 0)
         Q[:, self.oi] = X
-        return self.o.eval_fk(Q)
+        fr = self.o.eval_fk(Q)
+        if self.rot is not None:
+            fr[:, self.fe, :3, :3] = self.rot @ fr[:, self.fe, :3, :3]
+        return fr
 
     def f(self, X):
         fr = self.frames(np.atleast_2d(X))
@@ -194,6 +225,7 @@ def solve(prob, q0_full, opts, max_iter):
             break
         act = (x <= lo) & (b > 0.0) | (x >= hi) & (b < 0.0)
         S = A * (1.0 + lam * np.eye(n))
+        S[np.diag(A) == 0.0, np.diag(A) == 0.0] = lam  # a joint no residual depends on: lambda itself damps it
         S[act, :] = 0.0
         S[:, act] = 0.0
         S[act, act] = 1.0
