@@ -436,6 +436,12 @@ int gto_scene_from_depth(gto_handle* h, int32_t scene_id, const float* depth, in
  * map of mesh_to_sdf/depth_point_cloud.py:84-89 of that signed distance; nearest_out [nq] index of the nearest sample.
  * Among samples at equal distance the lower index counts as nearer (the reference leaves ties open).  Bit-identical to
  * the reference on tests/golden/surface_cloud.npz.  GTO_ERR_INVALID_ARG for n < k, k outside 1..16, non-finite samples.
+ * Non-finite queries are answered, not refused, and change no other query's result.  A query with a NaN coordinate has
+ * no nearest sample: sdf = +inf, inside = 0, cost = 0, nearest = -1.  A query with an infinite coordinate and no NaN is
+ * infinitely far from every sample, so (distance, index) order makes samples 0 .. k-1 its k nearest: nearest = 0,
+ * |sdf| = inf with the sign of their vote (a dot product that is NaN counts as "in front"), cost = the cost map of that
+ * value (+inf inside for w_inside > 0, else 0).  The tree search and the
+ * exhaustive search (GTO_CLOUD_BRUTE) agree on both, bit for bit.
  */
 int gto_cloud_sdf_cost(int device, const double* points, const double* normals, int64_t n, int32_t k, const double* query,
                        int64_t nq, float epsilon, float w_inside, float* sdf_out, uint8_t* inside_out, float* cost_out,

@@ -61,6 +61,53 @@ def cloud_sdf(points, normals, query, k=11, chunk=128):
     return out
 
 
+def cloud_sdf_pruned(points, normals, query, k=11, extra=5):
+    """cloud_sdf's dict, value for value, for many queries against a cloud of a few hundred samples: a KD-tree (scipy) names
+    k + 1 + extra candidates per query, and the restatement's own arithmetic and (squared distance, index) order run on the
+    candidates alone.  Why nothing is lost: a sample the tree left out is no nearer, by the tree's arithmetic, than its
+    farthest candidate at distance D; the two arithmetics agree to a few 1e-16 relative, so the restatement's squared
+    distance of such a sample is at least D^2 (1 - 1e-12).  A query is settled by its candidates when their (k+1)-th
+    squared distance is below D^2 (1 - 1e-9): every sample left out is then strictly farther than all k + 1.  The other
+    queries go through cloud_sdf.  tests/test_cloud_cases_cpu.py compares the two on a whole instance."""
+    from scipy.spatial import cKDTree
+    points = np.asarray(points, dtype=np.float64)
+    normals = np.asarray(normals, dtype=np.float64)
+    query = np.asarray(query, dtype=np.float64).reshape(-1, 3)
+    m = k + 1 + extra
+    if points.shape[0] <= m:
+        return cloud_sdf(points, normals, query, k)
+    tree = cKDTree(points)
+    parts = []
+    for s in range(0, max(1, query.shape[0]), 1 << 16):
+        q = query[s:s + (1 << 16)]
+        D, cand = tree.query(q, k=m, workers=4)
+        cand = np.sort(cand, axis=1)  # by index, then a stable sort by value: (value, index) order
+        dx, dy, dz = (q[:, None, a] - points[cand, a] for a in range(3))
+        r = dx * dx
+        r = r + dy * dy
+        r = r + dz * dz
+        o = np.argsort(r, axis=1, kind="stable")[:, :k + 1]
+        idx = np.take_along_axis(cand, o, 1)
+        d2 = np.take_along_axis(r, o, 1)
+        near = idx[:, :k]
+        ddx, ddy, ddz = (np.take_along_axis(a, o[:, :k], 1) for a in (dx, dy, dz))
+        nn = normals[near]
+        dot = ddx * nn[..., 0]
+        dot = dot + ddy * nn[..., 1]
+        dot = dot + ddz * nn[..., 2]
+        inside = (dot < 0).sum(axis=1) > k * 0.5
+        dist = np.sqrt(d2[:, 0]).astype(np.float32)
+        dist[inside] *= -1
+        part = {"sdf": dist, "inside": inside, "nearest": near[:, 0].astype(np.int32), "d2": d2, "dot": dot}
+        open_rows = np.flatnonzero(~(d2[:, k] < D[:, -1] * D[:, -1] * (1.0 - 1e-9)))
+        if len(open_rows):
+            full = cloud_sdf(points, normals, q[open_rows], k)
+            for name in part:
+                part[name][open_rows] = full[name]
+        parts.append(part)
+    return {name: np.concatenate([p[name] for p in parts]) for name in parts[0]}
+
+
 def cost_map(sdf, inside, epsilon=0.02, w_inside=1.0):
     """depth_point_cloud.py:84-89 in float32, the arithmetic of the device function sdf_cost_map (csrc/gto_depth.h)."""
     sdf = np.asarray(sdf, dtype=np.float32)
