@@ -311,18 +311,20 @@ static hipError_t raise_dynamic_lds(const void* kernel, size_t bytes) {
 }
 
 // The obstacle kernel variant of a launch: np-wide blocks; deep gather batches (launches with few instances in flight);
-// the crew behind an itemized launch laid out over an estimate; the hot variants of the solve loop's evaluations (central
-// differences: the value-only gather, the init pass's virtual waypoints and the static-link bookkeeping compiled out).
-// The wide robots have two variants, the crew has one.  gto_create raises the dynamic LDS of every variant this returns.
+// an itemized launch laid out over an estimate, with the crew for the rest at the end of its grid; the hot variants of the
+// solve loop's evaluations (central differences: the value-only gather, the init pass's virtual waypoints and the
+// static-link bookkeeping compiled out).  The wide robots have two variants, the launches with a crew have two.  gto_create
+// raises the dynamic LDS of every variant this returns.
 using ObsKernel = decltype(&k_obstacle_gram<GTO_NB>);
 static ObsKernel obstacle_kernel(int np, bool deep, bool sweep, bool hot) {
   // [wide, 8-wide, 8-wide deep]; the first reference to a variant decides where the code object places it, so they keep
-  // the order they have always had
+  // the order they have always had (the launch with a crew where the crew's own kernel was, its hot variant last)
   static const ObsKernel cold[3] = {k_obstacle_gram<16>, k_obstacle_gram<GTO_NB>, k_obstacle_gram<GTO_NB, GTO_OBS_DEEP_PD>};
   static const ObsKernel crew = k_obstacle_gram<GTO_NB, GTO_OBS_MAIN_PD, true>;
   static const ObsKernel warm[3] = {k_obstacle_gram<16, GTO_OBS_MAIN_PD, false, true>, k_obstacle_gram<GTO_NB, GTO_OBS_MAIN_PD, false, true>,
                                     k_obstacle_gram<GTO_NB, GTO_OBS_DEEP_PD, false, true>};
-  if (sweep && np == GTO_NB) return crew;
+  static const ObsKernel warm_crew = k_obstacle_gram<GTO_NB, GTO_OBS_MAIN_PD, true, true>;
+  if (sweep && !deep && np == GTO_NB) return hot ? warm_crew : crew;
   const int i = np != GTO_NB ? 0 : deep ? 2 : 1;
   return hot ? warm[i] : cold[i];
 }
@@ -1318,12 +1320,13 @@ static int launch_obstacle(gto_handle* h, hipStream_t st, const BatchPtrs& bp, c
   int n_regular = obstacle_grid(nb, nG);
   // Itemized launches: laid out over the caller's estimate of the item list's length instead of its upper bound (nine
   // tenths of the workgroups of the upper bound find no item and leave; they cost the other lanes' launches dispatch
-  // slots: +7 % trajectories/s without them); a crew of GTO_SWEEP_WGS workgroups behind the launch walks whatever the
-  // estimate missed (the kernel's SWEEP variant), so the result does not depend on it.
+  // slots: +7 % trajectories/s without them); a crew of GTO_SWEEP_WGS workgroups at the end of the launch's grid walks
+  // whatever the estimate missed (the kernel's SWEEP variant), so the result does not depend on it.
   const bool sweep = o.itemized && o.items_hint > 0 && o.items_hint + GTO_SWEEP_WGS < n_regular && bp.live != nullptr && !o.fixed_mode && !o.deep && h->np == GTO_NB;  // (the wide robots' launches are never itemized)
   if (sweep) n_regular = 8 * ((o.items_hint + 7) / 8);
   const size_t lds = (size_t)geo.lay.total_doubles * sizeof(double);
-  const dim3 grid(n_regular + (o.goal_terms ? 8 * ((nb + 31) / 32) : 0));  // goal-term jobs: four to a workgroup, in front, a multiple of eight workgroups
+  const int n_crew = sweep ? GTO_SWEEP_WGS : 0;  // behind the regular workgroups: items n_regular, n_regular + 1, ... of the list, if there are any
+  const dim3 grid(n_regular + n_crew + (o.goal_terms ? 8 * ((nb + 31) / 32) : 0));  // goal-term jobs: four to a workgroup, in front, a multiple of eight workgroups
   const bool deep_v = h->np == GTO_NB && o.deep;
   if (o.timed) {
     int rc_ = prof_begin(h, st, deep_v ? GTO_PROF_OBSTACLE_FEW : GTO_PROF_OBSTACLE, (long long)grid.x);
@@ -1340,11 +1343,8 @@ static int launch_obstacle(gto_handle* h, hipStream_t st, const BatchPtrs& bp, c
   const int2* items_par = listed && o.itemized ? bp.items + (size_t)sp.parity * items_cap : nullptr;
   const int32_t* nitems_par = listed && o.itemized ? bp.nlive + 8 + sp.parity : nullptr;
   const bool hot = !o.fixed_mode && sp.grad_mode == GTO_GRAD_CENTRAL_DIFF;
-  hipLaunchKernelGGL(obstacle_kernel(h->np, o.deep, false, hot), grid, dim3(256), lds, st, jobs_par, njobs_par, items_par, nitems_par, geo.nG, geo.m_nG, n_regular, B,
-                     h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes, bpl, sp, o.t_begin, o.nT, o.fixed_mode, geo, 0);
-  if (sweep)  // the crew: items n_regular, n_regular + 1, ... of the list, if there are any
-    hipLaunchKernelGGL(obstacle_kernel(h->np, false, true, false), dim3(GTO_SWEEP_WGS), dim3(256), lds, st, jobs_par, njobs_par, items_par, nitems_par, geo.nG, geo.m_nG, GTO_SWEEP_WGS, B,
-                       h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes, bpl, sp, o.t_begin, o.nT, o.fixed_mode, geo, n_regular);
+  hipLaunchKernelGGL(obstacle_kernel(h->np, o.deep, sweep, hot), grid, dim3(256), lds, st, jobs_par, njobs_par, items_par, nitems_par, geo.nG, geo.m_nG, n_regular, B,
+                     h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes, bpl, sp, o.t_begin, o.nT, o.fixed_mode, geo, n_crew);
   if (o.timed) return prof_end(h, st);
   return GTO_OK;
 }
