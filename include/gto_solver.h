@@ -70,6 +70,9 @@ extern "C" {
  * (optas/models.py:236-321, 826-868) and GTORobotModel (gto/gto_models.py:62-101).
  * Frames are listed parents-before-children; frame i is reached from parent[i] by the fixed
  * origin transform rt2tr(rpy2r(rpy), xyz) followed by the joint motion about/along `axis`.
+ * The small end: every count may be 1 (one frame, whose joint then sits on the root itself, one optimised joint, one
+ * link, one surface point, one gripper point), frame_ee and frame_gripper may be any two frames, above every optimised
+ * joint included, and no link need hang below an optimised joint (tests/small_robots.py).
  */
 typedef struct gto_robot_desc {
   int32_t n_frames;
@@ -271,7 +274,9 @@ int gto_solve_ik_pose_batch(gto_handle* h, int32_t goal_kind, int32_t B, const i
  *   max_iter  iteration cap (reference IPOPT cap: 100, :95)
  * Outputs (host): y_out [B][3] = (x, y, theta), the old base in the new base frame (:52);
  * q_out [B][n_max][ndof] arm configuration per goal (rows >= n_goals[b]: qc); cost_out, iters_out,
- * status_out as in gto_solve_batch (may be NULL).  err_pos / err_rot (:127-143) and the occupancy statistic (:146-158)
+ * status_out as in gto_solve_batch (may be NULL).  An optimised joint that moves none of the gripper's frame has a zero
+ * diagonal entry in every goal block; it is damped by lambda itself, as in gto_solve_ik_batch, and keeps its value of qc.
+ * err_pos / err_rot (:127-143) and the occupancy statistic (:146-158)
  * of the solution: gto_base_report_device below (on the host: gto_eval_fk and gto_eval_points' transformed points).
  * Replaces: BasePlanner.setup_optimization + the solve inside plan_goalset (gto/base_planner.py:35-123).
  */
@@ -670,7 +675,8 @@ void gto_occupancy_destroy(gto_occupancy* occ);
  * of the launch on `stream` through pinned memory of the handle; the caller's array is free on return (with four such
  * calls of a handle still in flight the host waits for the oldest copy).  y_out and q_out are required; cost_out, iters_out and
  * status_out may be NULL.  The copy of n_goals lives on the handle: calls on one handle go to one stream, or the caller
- * orders them (the rule of gto_check_plans_device).
+ * orders them (the rule of gto_check_plans_device).  An optimised joint that moves none of the gripper's frame is damped by
+ * lambda itself and keeps its value of qc, as in gto_solve_base_batch.
  */
 int gto_solve_base_batch_device(gto_handle* h, int32_t B, int32_t n_max, const int32_t* n_goals, const double* qc,
                                 const double* goals, double effort_weight, int32_t max_iter, double* y_out, double* q_out,

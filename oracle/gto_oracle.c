@@ -1355,7 +1355,7 @@ static void solve_base_instance(const gto_robot_desc* d, const gto_solver_opts* 
       for (int j = 0; j < N; ++j) {
         double v = Acur[(size_t)i * N + j];
         if (act[i] || act[j]) v = (i == j) ? 1.0 : 0.0;
-        else if (i == j) v *= (1.0 + lambda);
+        else if (i == j) v = v == 0.0 ? lambda : v * (1.0 + lambda); /* a joint that moves no goal frame (solve_ik_instance) */
         M[(size_t)i * N + j] = v;
       }
       rhs[i] = act[i] ? 0.0 : -bcur[i];

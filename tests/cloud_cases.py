@@ -452,7 +452,7 @@ def box_samples(lo, hi, rng):
     return np.concatenate(pts), np.concatenate(nrm)
 
 
-def plan_cloud(name, desc, T, world_points, seed=None):
+def plan_cloud(name, desc, T, world_points, seed=None, key=None):
     """The plans of depth_cases.plan_instance (B = 3 straight joint-space plans, a shared base, per-plan bases, a NaN to plant)
     and an obstacle for them: a closed axis-aligned box around where the second half of plan 0 puts the robot's far links
     (the tenth of its surface points farthest from the base at the last waypoint), under the shared base and under plan 0's
@@ -461,8 +461,8 @@ def plan_cloud(name, desc, T, world_points, seed=None):
     normals, lo, hi added."""
     if seed is None:
         seed = PLAN_SEED.get((name, T), 0)
-    inst = dc.plan_instance(name, desc, T, world_points)
-    rng = np.random.default_rng(8000 + 100 * dc.PLAN_ROBOTS.index(name) + T + 1000 * seed)
+    inst = dc.plan_instance(name, desc, T, world_points, key=key)
+    rng = np.random.default_rng(8000 + 100 * (dc.PLAN_ROBOTS.index(name) if key is None else key) + T + 1000 * seed)
     ts = np.arange((T - 1) // 2 + 1, T)
     q = inst.plans[0][:, ts].T
     xa = world_points(q, np.tile(inst.base, (len(ts), 1)))

@@ -340,15 +340,16 @@ def plan_robot(name):
     return desc, ee, ee, 40
 
 
-def plan_instance(name, desc, T, world_points, seed=0):
+def plan_instance(name, desc, T, world_points, seed=0, key=None):
     """B = 3 straight joint-space plans of `desc` over T waypoints and a depth image they reach through.
     world_points(q (n, ndof), base (n, 3)) -> (n, P, 3): the robot's surface points in the world (the oracle's).
     The camera stands behind the robot and looks along +x.  The image hugs the first half of the motion from behind: a
     pixel's depth is that of the farthest point the waypoints t <= (T - 1) / 2 put there (with the shared base and with
     the per-plan bases) plus 1 to 1.4 cm, so these waypoints count 0; a pixel none of them reaches lies in front of the
     whole robot, so what the second half of the motion moves there counts.  No two pixels are alike.  Returns plans
-    (B, ndof, T), base (3,), bases (B, 3), nan_at (plan, joint, waypoint), depth, K, cam."""
-    rng = np.random.default_rng(7000 + 100 * PLAN_ROBOTS.index(name) + T + 1000 * seed)
+    (B, ndof, T), base (3,), bases (B, 3), nan_at (plan, joint, waypoint), depth, K, cam.  A robot outside PLAN_ROBOTS
+    (tests/small_robots.py) gives the `key` that stands for its place in that list."""
+    rng = np.random.default_rng(7000 + 100 * (PLAN_ROBOTS.index(name) if key is None else key) + T + 1000 * seed)
     B = PLAN_B
     if name == "panda":
         from helpers import cfg_of

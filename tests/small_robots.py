@@ -1,0 +1,417 @@
+"""The smallest robots include/gto_solver.h accepts, as seeded cases for the CPU and the GPU suite (no GPU here).
+
+gto_create takes n_frames, n_links, n_opt, n_points and n_gripper_points from 1 on and the end-effector and gripper
+frames anywhere; the kernels were written for 32 frames and 8 or 16 optimised joints and pad down.  Kinds (all required):
+  chain_1 .. chain_7   a serial chain of n + 1 frames, ndof = n_opt = n, a collision link on every frame, 3 gripper points:
+                       every padding of the 8-wide kernels (GTO_NB = 8 rows for n of them) and of fk_mfma_tree's 4 x 4 tiles
+  chain_9_short        10 frames, n_opt = 9: the narrowest robot of the 16-wide kernels on the shortest tree that holds it
+  one_point            the 1-joint chain with one collision link on the moving frame, one surface point, one gripper
+                       point: one chunk of count 1, one PbChunk, a gripper cloud whose orientation cannot be observed
+  static_links_only    2 frames, 1 joint, the only collision link on the root: no optimised joint moves a chunk, the
+                       PbChunk table is empty, f_obs > 0 is constant and every obstacle block is zero
+  prismatic_only       3 frames, two prismatic optimised joints, no revolute joint: the goal's orientation is out of reach
+  ee_above_joints      a 3-joint chain with link_ee = link_gripper = the root: no goal residual depends on a joint
+  ee_not_gripper       4 frames, 2 joints, the fixed tip frame is the gripper and its parent the end effector
+  root_joint           n_frames = 1: the actuated joint sits on the root frame itself (parent = -1)
+Horizons: T = 4 with standoff_offset = -1 and T = 5 with -2 on every kind, T = 50 (-10) on chain_1, one_point and
+static_links_only.  Scenes: a random 5 x 5 x 5 field around the robot; one_point and chain_2 also get 1 x 1 x 1 and
+1 x 4 x 1 fields with voxels large enough to hold the robot.
+
+A case is usable only if the oracle's three solves are robust (robust_runs below): the same iteration counts and statuses
+and results within 1e-9 after every seed entry and goal translation moved by a relative 1e-12.  Then no accept / reject
+decision sits on round-off and the GPU's iteration counts can be compared for equality.  SEEDS holds, per case, the first
+seed (of at most 20 tried) for which that holds; a kind may change its seed, it may not leave KINDS."""
+import numpy as np
+
+from grasptrajopt_amd import synthetic as syn
+from grasptrajopt_amd.robot_desc import RobotDesc
+
+KINDS = [f"chain_{n}" for n in range(1, 8)] + ["chain_9_short", "one_point", "static_links_only", "prismatic_only",
+                                                "ee_above_joints", "ee_not_gripper", "root_joint"]
+LONG_KINDS = ("chain_1", "one_point", "static_links_only")     # also at T = 50
+FLAT_KINDS = ("one_point", "chain_2")                          # also on 1 x 1 x 1 and 1 x 4 x 1 fields
+HORIZONS = {4: -1, 5: -2, 50: -10}                             # T -> standoff_offset
+B = 4
+N_MAX = 3                                                      # goals per set of the ragged variants
+RAGGED_KINDS = ("chain_1", "chain_4", "one_point")
+MAX_ITER, IK_MAX_ITER, BASE_MAX_ITER = 40, 30, 25
+
+# (kind, T, scene shape) -> seed, where seed 0 does not pass the robustness condition or a field misses the robot
+# (static_links_only: misses an instance)
+SEEDS = {("one_point", 4, (5, 5, 5)): 1, ("static_links_only", 5, (5, 5, 5)): 2, ("static_links_only", 50, (5, 5, 5)): 3,
+         ("root_joint", 4, (5, 5, 5)): 1}
+
+
+# ------------------------------------------------------------------------------------------------------------ robots
+def _tree(name, seed, parent, jt, link_frames, counts, root_origin=False):
+    """A RobotDesc as helpers.random_robot builds one: seeded origins, axes and limits; every actuated joint is optimised."""
+    rng = np.random.default_rng(seed)
+    parent, jt = np.asarray(parent, dtype=np.int32), np.asarray(jt, dtype=np.int32)
+    F = len(parent)
+    act = [f for f in range(F) if jt[f] != 0]
+    q_index = np.full(F, -1, dtype=np.int32)
+    q_index[act] = np.arange(len(act))
+    ndof = len(act)
+    origin_xyz = rng.uniform(-0.05, 0.05, size=(F, 3))
+    origin_xyz[:, 2] = rng.uniform(0.06, 0.14, size=F)
+    origin_rpy = rng.uniform(-1.2, 1.2, size=(F, 3))
+    if not root_origin:
+        origin_xyz[0] = origin_rpy[0] = 0.0
+    axis = rng.standard_normal((F, 3))
+    axis /= np.linalg.norm(axis, axis=1, keepdims=True)
+    prism = np.array([jt[f] == 2 for f in act], dtype=bool)
+    lower = np.where(prism, -0.15, -2.0) * rng.uniform(0.6, 1.0, ndof)
+    upper = np.where(prism, 0.15, 2.0) * rng.uniform(0.6, 1.0, ndof)
+    L = len(link_frames)
+    pts, plink = [], []
+    for l in range(L):
+        m = int(counts[l])
+        pts.append(rng.uniform(-0.02, 0.02, 3) + rng.standard_normal((m, 3)) * rng.uniform(0.01, 0.03, 3))
+        plink.append(np.full(m, l, dtype=np.int32))
+    names = [f"f{i}" for i in range(F)]
+    P = int(sum(counts))
+    return RobotDesc(
+        name=name, frame_names=names, parent=parent, joint_type=jt, q_index=q_index, origin_xyz=origin_xyz,
+        origin_rpy=origin_rpy, axis=axis, actuated_joint_names=[f"j{k}" for k in range(ndof)], lower=lower, upper=upper,
+        opt_index=np.arange(ndof, dtype=np.int32), param_index=np.array([], dtype=np.int32),
+        link_names=[names[f] for f in link_frames], link_frame=np.array(link_frames, dtype=np.int32),
+        visual_xyz=rng.uniform(-0.02, 0.02, (L, 3)), visual_rpy=rng.uniform(-0.5, 0.5, (L, 3)), points=np.concatenate(pts),
+        normals=np.zeros((P, 3)), point_link=np.concatenate(plink))
+
+
+def _chain(name, seed, n, prismatic=()):
+    """n + 1 frames, frame i on frame i - 1, joints 1 .. n actuated (every third prismatic from n = 3 on), a link on every
+    frame with 3 to 9 points."""
+    jt = [0] + [2 if (k in prismatic or (n >= 3 and k % 3 == 2)) else 1 for k in range(1, n + 1)]
+    counts = 3 + np.random.default_rng(seed + 77).integers(0, 7, size=n + 1)
+    return _tree(name, seed, np.arange(-1, n), jt, list(range(n + 1)), counts)
+
+
+class Robot:
+    """A kind's robot with the frames and the number of gripper points it is solved with, and the counts its name promises."""
+
+    def __init__(self, kind, seed=0):
+        self.kind = kind
+        exp = None
+        if kind.startswith("chain_"):
+            n = int(kind.split("_")[1])
+            d = _chain(kind, seed, n)
+            ee = gr = f"f{n}"
+            ngp = 3
+            exp = dict(frames=n + 1, ndof=n, n_opt=n, links=n + 1, moving=n)
+        elif kind == "one_point":
+            d = _tree(kind, seed, [-1, 0], [0, 1], [1], [1])
+            ee = gr = "f1"
+            ngp = 1
+            exp = dict(frames=2, ndof=1, n_opt=1, links=1, moving=1, points=1)
+        elif kind == "static_links_only":
+            d = _tree(kind, seed, [-1, 0], [0, 1], [0], [5])
+            ee, gr, ngp = "f1", "f0", 3     # (the gripper's points are a collision link's: the root's is the only one)
+            exp = dict(frames=2, ndof=1, n_opt=1, links=1, moving=0, points=5)
+        elif kind == "prismatic_only":
+            d = _tree(kind, seed, [-1, 0, 1], [0, 2, 2], [0, 1, 2], [4, 3, 5])
+            ee = gr = "f2"
+            ngp = 3
+            exp = dict(frames=3, ndof=2, n_opt=2, links=3, moving=2)
+        elif kind == "ee_above_joints":
+            d = _tree(kind, seed, [-1, 0, 1, 2], [0, 1, 1, 1], [0, 1, 2, 3], [4, 3, 5, 3])
+            ee = gr = "f0"
+            ngp = 3
+            exp = dict(frames=4, ndof=3, n_opt=3, links=4, moving=3)
+        elif kind == "ee_not_gripper":
+            d = _tree(kind, seed, [-1, 0, 1, 2], [0, 1, 1, 0], [0, 1, 2, 3], [3, 4, 3, 5])
+            ee, gr, ngp = "f2", "f3", 3
+            exp = dict(frames=4, ndof=2, n_opt=2, links=4, moving=3)
+        elif kind == "root_joint":
+            d = _tree(kind, seed, [-1], [1], [0], [5], root_origin=True)
+            ee = gr = "f0"
+            ngp = 3
+            exp = dict(frames=1, ndof=1, n_opt=1, links=1, moving=1, points=5)
+        else:
+            raise KeyError(kind)
+        self.desc, self.ee, self.gripper, self.n_gripper_points, self.expected = d, ee, gr, ngp, exp
+
+    def counts(self):
+        """What gto_create sees: frames, joints, links, points, gripper points, and chunks an optimised joint moves (every
+        link here has at most 64 points: one chunk per link, and one PbChunk per moving link)."""
+        d = self.desc
+        assert np.bincount(d.point_link, minlength=d.n_links).max() <= 64
+        return dict(frames=d.n_frames, ndof=d.ndof, n_opt=d.n_opt, links=d.n_links, points=d.n_points,
+                    gripper_points=min(self.n_gripper_points, len(d.link_points(self.gripper))),
+                    moving=int(d.link_is_moving().sum()))
+
+    def extent(self):
+        """No surface point is further than this from the root (origins, prismatic travel, visual origins, points)."""
+        d = self.desc
+        r = np.linalg.norm(d.origin_xyz, axis=1).sum()
+        r += sum(max(abs(d.lower[d.q_index[f]]), abs(d.upper[d.q_index[f]])) for f in range(d.n_frames) if d.joint_type[f] == 2)
+        return float(r + np.linalg.norm(d.visual_xyz, axis=1).max() + np.linalg.norm(d.points, axis=1).max())
+
+
+# ------------------------------------------------------------------------------------------------------------ scenes
+def field(rng, shape, extent):
+    """A random field as test_gpu_limits._field makes one, centred on the robot's root.  A 5 x 5 x 5 grid spans the robot's
+    reach; these robots stand in two or three of its voxels, so 60 % / 50 % of them cost something (there: 35 % / 25 %) and
+    the cases' tests assert that both fields are met.  A flat grid's voxel holds the whole robot (base included), and costs
+    something."""
+    n = int(np.prod(shape))
+    c_all = (0.03 * rng.random(n) * (rng.random(n) < 0.6)).astype(np.float32)
+    c_obs = (0.03 * rng.random(n) * (rng.random(n) < 0.5)).astype(np.float32)
+    if max(shape) < 5:
+        res = 2.0 * extent + 0.4
+        origin = [-0.5 * res * s for s in shape]
+        home = int(np.ravel_multi_index([s // 2 for s in shape], shape))   # (even axes: the root is on a voxel face)
+        for s in range(n):
+            c_all[s] = max(c_all[s], np.float32(0.01 + 0.001 * s))
+        c_obs[home] = max(c_obs[home], np.float32(0.02))
+    else:
+        res = (2.0 * extent + 0.2) / shape[0]
+        origin = [-0.5 * res * s for s in shape]
+    return c_all, c_obs, tuple(int(s) for s in shape), tuple(origin), float(res)
+
+
+def _rigid(t, axis, angle):
+    w = np.asarray(axis, dtype=np.float64) / np.linalg.norm(axis)
+    Wx = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    M = np.eye(4)
+    M[:3, :3] = np.eye(3) + np.sin(angle) * Wx + (1 - np.cos(angle)) * Wx @ Wx
+    M[:3, 3] = t
+    return M
+
+
+# ------------------------------------------------------------------------------------------------------------- cases
+def case_ids():
+    """(kind, T, scene shape) of every case."""
+    out = []
+    for kind in KINDS:
+        for T in (4, 5):
+            out.append((kind, T, (5, 5, 5)))
+        if kind in LONG_KINDS:
+            out.append((kind, 50, (5, 5, 5)))
+        if kind in FLAT_KINDS:
+            for T in (4, 5):
+                out += [(kind, T, (1, 1, 1)), (kind, T, (1, 4, 1))]
+    return out
+
+
+def case_name(cid):
+    kind, T, shape = cid
+    return f"{kind}-T{T}-{'x'.join(map(str, shape))}"
+
+
+class Case:
+    """One kind at one horizon in one scene: B instances with qc, ragged goal sets of up to N_MAX goals (the oracle's FK of
+    in-limit configurations; column 0 alone is the single-goal problem), seeds from syn.make_seed towards goal 0, and a
+    non-zero base."""
+
+    def __init__(self, oracle_mod, kind, T, shape=(5, 5, 5), seed=None):
+        self.id = (kind, T, tuple(shape))
+        self.seed = SEEDS.get(self.id, 0) if seed is None else seed
+        self.robot = Robot(kind, seed=self.seed)
+        d = self.desc = self.robot.desc
+        self.kind, self.T, self.B = kind, T, B
+        self.ee, self.gripper, self.ngp = self.robot.ee, self.robot.gripper, self.robot.n_gripper_points
+        self.opts = oracle_mod.reference_opts(T=T, standoff_offset=HORIZONS[T], max_iter=MAX_ITER)
+        rng = np.random.default_rng(31 * self.seed + 7 * T + 1000 * KINDS.index(kind) + int(np.prod(shape)) + sum(shape))
+        self.scene = field(rng, shape, self.robot.extent() + 0.1)
+        lo, hi = d.lower, d.upper
+        self.qc = rng.uniform(0.3 * lo, 0.3 * hi, size=(B, d.ndof))
+        self.qg = rng.uniform(0.8 * lo, 0.8 * hi, size=(B, N_MAX, d.ndof))
+        o = self.oracle(oracle_mod)
+        fk = o.eval_fk(self.qg.reshape(-1, d.ndof))[:, d.frame_index(self.ee)]
+        if kind == "ee_above_joints":  # (the root's pose is the same at every configuration: goals beside it, or no term is ever non-zero)
+            fk = fk @ np.stack([_rigid(rng.uniform(-0.1, 0.1, 3), rng.standard_normal(3), 0.3) for _ in range(len(fk))])
+        self.goals_all = np.ascontiguousarray(fk.reshape(B, N_MAX, 16))
+        self.goals = np.ascontiguousarray(self.goals_all[:, :1])
+        self.n_goals = np.ones(B, dtype=np.int32)
+        self.n_goals_ragged = np.array([N_MAX, 1, 2, N_MAX][:B], dtype=np.int32)
+        self.S = syn.standoff_pose(-0.05, "z")
+        self.base = rng.uniform(-0.05, 0.05, size=(B, 3))
+        self.Q0 = np.stack([syn.make_seed(self.qc[b], self.qg[b, 0], T, d.param_index) for b in range(B)])
+        self.rng = rng
+
+    def oracle(self, oracle_mod):
+        o = oracle_mod.Oracle(self.desc, self.ee, self.gripper, self.opts, n_gripper_points=self.ngp)
+        o.set_scene(0, *self.scene)
+        return o
+
+    def handle(self, capi):
+        h = capi.SolverHandle(self.desc, self.ee, self.gripper, self.opts, device=0, n_gripper_points=self.ngp)
+        h.set_scene(0, *self.scene)
+        return h
+
+    def solve_args(self, ragged=False, goals=None, Q0=None):
+        g = self.goals_all if ragged else self.goals
+        return (0, self.qc, g if goals is None else goals, self.n_goals_ragged if ragged else self.n_goals, self.S, self.base,
+                self.Q0 if Q0 is None else Q0)
+
+    def nudged(self, ragged=False, rel=1e-12):
+        """(goals, Q0, qc) with every goal translation and every seed entry moved by a relative `rel`, seeded signs."""
+        rng = np.random.default_rng(99 + self.seed)
+        g = (self.goals_all if ragged else self.goals).copy().reshape(self.B, -1, 4, 4)
+        g[..., :3, 3] *= 1.0 + rel * rng.choice([-1.0, 1.0], size=g[..., :3, 3].shape)
+        Q0 = self.Q0 * (1.0 + rel * rng.choice([-1.0, 1.0], size=self.Q0.shape))
+        qc = self.qc * (1.0 + rel * rng.choice([-1.0, 1.0], size=self.qc.shape))
+        return g.reshape(self.B, -1, 16), Q0, qc
+
+
+def robust_runs(case, o, ragged=False):
+    """The oracle's trajectory, IK (with the scene) and base solves of a case, clean and nudged.  Returns a list of
+    (name, clean, nudged) with each run as (x, cost, iterations, status)."""
+    g, Q0, qc = case.nudged(ragged)
+    nt = o.usable_cores()
+    out = []
+    a = o.solve_batch(*case.solve_args(ragged), n_threads=nt)
+    b = o.solve_batch(*case.solve_args(ragged, goals=g, Q0=Q0), n_threads=nt)
+    out.append(("solve_batch", (a[0], a[2], a[3], a[4]), (b[0], b[2], b[3], b[4])))
+    if not ragged:
+        for sid in (None, 0):
+            a = o.solve_ik_batch(sid, case.qc, case.goals[:, 0], case.base, max_iter=IK_MAX_ITER, n_threads=nt)
+            b = o.solve_ik_batch(sid, qc, g[:, 0], case.base, max_iter=IK_MAX_ITER, n_threads=nt)
+            out.append((f"solve_ik_batch(scene={sid})", a, b))
+    gs, ng = (case.goals_all, case.n_goals_ragged) if ragged else (case.goals, case.n_goals)
+    a = o.solve_base_batch(case.qc, gs, ng, 0.01, max_iter=BASE_MAX_ITER, n_threads=nt)
+    b = o.solve_base_batch(qc, g, ng, 0.01, max_iter=BASE_MAX_ITER, n_threads=nt)
+    out.append(("solve_base_batch", (np.concatenate([a[0].ravel(), a[1].ravel()]), a[2], a[3], a[4]),
+                (np.concatenate([b[0].ravel(), b[1].ravel()]), b[2], b[3], b[4])))
+    return out
+
+
+def robust_failures(case, o, ragged=False):
+    """What of the robustness condition a case misses ([] = usable)."""
+    bad = []
+    for name, a, b in robust_runs(case, o, ragged):
+        if not (np.isfinite(a[1]).all() and np.isin(a[3], (0, 1)).all()):
+            bad.append(f"{name}: cost {a[1]} status {a[3]}")
+        if not (np.array_equal(a[2], b[2]) and np.array_equal(a[3], b[3])):
+            bad.append(f"{name}: iterations {a[2]} / {b[2]}, status {a[3]} / {b[3]}")
+        elif not np.abs(a[0] - b[0]).max() <= 1e-9:
+            bad.append(f"{name}: results move by {np.abs(a[0] - b[0]).max():.2e}")
+    return bad
+
+
+# ------------------------------------------------------------------------------------ inputs of the other entry points
+IK_KINDS = [k for k in KINDS if k != "chain_9_short"]          # the IK and base kernels take up to eight optimised joints
+POSE_MAX_ITER = 50
+
+
+def pose_goals(case, goal_kind):
+    """The case's first goals as quaternion (1) or roll-pitch-yaw (2) goals of gto_solve_ik_pose_batch."""
+    from grasptrajopt_amd import utils
+    f = {1: utils.ik_goal_quaternion, 2: utils.ik_goal_rpy}[goal_kind]
+    return np.stack([f(g.reshape(4, 4)) for g in case.goals[:, 0]])
+
+
+def pose_restatement(case, o, goal_kind, rot=None, max_iter=POSE_MAX_ITER):
+    """tests/ik_pose_ref.py's solve of every instance without a scene: (q (B, ndof), cost (B,), iterations, status).
+    rot: a 3 x 3 turned onto the end effector's rotation (ik_pose_cases.unstable)."""
+    import ik_pose_ref as ref
+    goals = pose_goals(case, goal_kind)
+    out = [ref.solve(ref.PoseProblem(o, case.desc, case.ee, goal_kind, case.qc[b], goals[b], rot=rot), case.qc[b], case.opts, max_iter)
+           for b in range(case.B)]
+    return (np.stack([r[0] for r in out]), np.array([r[1] for r in out]), np.array([r[2] for r in out], dtype=np.int32),
+            np.array([r[3] for r in out], dtype=np.int32))
+
+
+RETIME_KINDS = ("chain_1", "chain_2", "one_point")
+RETIME_SUBDIVS = (1, 2, 5)
+RETIME_B = 5
+# (kind, T) -> seed of retime_ref.random_plans: the first for which the restatement's profile converges at every subdivision
+# (on grids this short a wiggling plan often comes to rest inside the path: status NUMERICAL, nothing to compare)
+RETIME_SEEDS = {("chain_1", 4): 5, ("chain_1", 5): 0, ("chain_2", 4): 7, ("chain_2", 5): 5, ("one_point", 4): 5, ("one_point", 5): 0}
+
+
+def retime_inputs(kind, T, seed=None):
+    """(desc, plans (5, ndof, T), vmax, amax): smooth random plans (retime_ref.random_plans) inside the limits.  In plan 1
+    joint 0 stands still (a 1-joint plan then has no moving joint: duration 0, status 0); plan 3 is plan 2 backwards."""
+    import retime_ref as rr
+    d = Robot(kind, seed=SEEDS.get((kind, T, (5, 5, 5)), 0)).desc   # (the robot of the kind's case at this horizon)
+    plans = rr.random_plans(d, RETIME_B, T, seed=RETIME_SEEDS[kind, T] if seed is None else seed)
+    plans[1, 0] = plans[1, 0, 0]
+    plans[3] = plans[2][:, ::-1]
+    rng = np.random.default_rng(T)
+    return d, plans, rng.uniform(0.8, 1.6, d.ndof), np.full(d.ndof, 0.5)
+
+
+def seed_goalset_case(case, n_max=5):
+    """Inputs of gto_seed_goalsets_device on a case's robot and scene, in the order of tests/seed_cases.seed_case_wide:
+    (qc, q_solutions, goals, n_goals, accept, scene ids, bases) for B instances: every row accepted, an empty mask, two
+    copies of one solution (ties in cost and distance), a NaN solution, ragged counts."""
+    d = case.desc
+    rng = np.random.default_rng(500 + case.seed + case.T)
+    qc = case.qc + rng.uniform(-0.02, 0.02, case.qc.shape)
+    qs = rng.uniform(0.9 * d.lower, 0.9 * d.upper, (case.B, n_max, d.ndof))
+    goals = rng.standard_normal((case.B, n_max, 16))
+    n_goals = np.array([n_max, n_max, n_max, 2][:case.B], dtype=np.int32)
+    accept = (rng.random((case.B, n_max)) < 0.7).astype(np.uint8)
+    accept[0] = 1
+    accept[1] = 0
+    qs[2, 1] = qs[2, 0]
+    qs[2, 3] = qs[2, 0]
+    accept[2] = 1
+    qs[3, 0, d.ndof - 1] = np.nan
+    accept[3, :2] = 1
+    return qc, qs, goals, n_goals, accept, np.zeros(case.B, dtype=np.int32), case.base.copy()
+
+
+# (kind, T, scene shape) -> instances of seed_goalset_case whose two cheapest different candidates cost the oracle the same
+# non-zero sum, bit for bit (a few points that stand in the same voxels at every waypoint: only their distances tell them
+# apart, which test_gpu_seed_waves.clearly_first does not accept as a clear choice); the cases not listed have none
+SEED_TIES = {("chain_1", 5, (5, 5, 5)): 1, ("chain_2", 5, (5, 5, 5)): 1, ("chain_2", 4, (1, 1, 1)): 3, ("chain_2", 5, (1, 1, 1)): 3,
+             ("chain_7", 4, (5, 5, 5)): 1, ("one_point", 4, (5, 5, 5)): 1, ("one_point", 5, (5, 5, 5)): 2, ("one_point", 50, (5, 5, 5)): 1,
+             ("one_point", 4, (1, 1, 1)): 3, ("one_point", 4, (1, 4, 1)): 2, ("one_point", 5, (1, 1, 1)): 3, ("one_point", 5, (1, 4, 1)): 2,
+             ("static_links_only", 4, (5, 5, 5)): 3, ("static_links_only", 5, (5, 5, 5)): 3, ("static_links_only", 50, (5, 5, 5)): 3,
+             ("prismatic_only", 5, (5, 5, 5)): 1, ("root_joint", 4, (5, 5, 5)): 2, ("root_joint", 5, (5, 5, 5)): 2}
+
+
+def seed_cost_ties(want):
+    """How many instances of tests/test_gpu_seed_waves.oracle_seeds' result have such a tie."""
+    def tied(w):
+        cost, dist = w["seed_cost"], w["oracle_dist"]
+        order = np.lexsort((dist, cost))
+        c0, d0 = cost[order[0]], dist[order[0]]
+        same = lambda a, b: a == b or (a != a and b != b)
+        rest = [k for k in order[1:] if not (same(cost[k], c0) and same(dist[k], d0))]
+        return bool(rest) and cost[rest[0]] == c0 != 0.0
+    return sum(tied(w) for w in want if w["n_accepted"])
+
+
+REPORT_B, REPORT_N_MAX = 5, 3
+# (kind, T) -> seed of base_chain_ref.report_case where 100 + T gives footprints that all collide or are all free
+REPORT_SEEDS = {("chain_3", 5): 106, ("chain_4", 4): 105, ("ee_above_joints", 5): 106}
+
+
+def base_report_case(case, o):
+    """base_chain_ref.report_case on a case's robot: five sets of up to three goals, random base poses, an observed cloud and
+    its occupancy grid; the builder asserts that no placed point lies within 1e-9 m of a cell edge."""
+    import base_chain_ref as bref
+    return bref.report_case(o, case.desc, REPORT_B, REPORT_N_MAX, REPORT_SEEDS.get((case.kind, case.T), 100 + case.T))
+
+
+PLAN_KINDS = tuple(KINDS)   # check_plans runs on every kind, at every horizon of the kind, on the robot of its 5 x 5 x 5 case
+# (kind, T) -> seed of cloud_cases.plan_cloud's samples, where seed 0 leaves an undecided point
+PLAN_CLOUD_SEEDS = {}
+
+
+def plan_case_ids():
+    return [cid for cid in case_ids() if cid[2] == (5, 5, 5)]
+
+
+def plan_key(kind):
+    import depth_cases as dc
+    return len(dc.PLAN_ROBOTS) + KINDS.index(kind)
+
+
+def plan_depth_instance(case, o):
+    """depth_cases.plan_instance on a case's robot: three straight plans, a shared base, per-plan bases and a 60 x 80 image."""
+    import depth_cases as dc
+    world_points = lambda q, base: o.eval_points(0, q, base, want_field=False)[0]
+    return dc.plan_instance(case.kind, case.desc, case.T, world_points, key=plan_key(case.kind)), world_points
+
+
+def plan_cloud_instance(case, o):
+    """cloud_cases.plan_cloud on a case's robot: the same plans and a sampled box where plan 0 ends."""
+    import cloud_cases as cc
+    world_points = lambda q, base: o.eval_points(0, q, base, want_field=False)[0]
+    return cc.plan_cloud(case.kind, case.desc, case.T, world_points, seed=PLAN_CLOUD_SEEDS.get((case.kind, case.T), 0),
+                         key=plan_key(case.kind)), world_points
