@@ -245,7 +245,11 @@ def load_library(path: Optional[str] = None):
     lib.gto_solve_ik_pose_batch_device.argtypes = [H, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 5
     lib.gto_ik_report_device.argtypes = [H, C.c_int32] + [C.c_void_p] * 4 + [C.c_double] * 3 + [C.c_void_p] * 5
     lib.gto_seed_goalsets_device.argtypes = [H, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32, C.c_int32] + [C.c_void_p] * 8
-    for fn in ("gto_solve_ik_pose_batch_device", "gto_ik_report_device", "gto_seed_goalsets_device"):
+    lib.gto_seed_goalsets_multi_device.argtypes = [H, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32, C.c_int32] + [C.c_void_p] * 9
+    lib.gto_plan_report_device.argtypes = [H, C.c_int32, C.c_int32] + [C.c_void_p] * 9
+    lib.gto_select_plans_device.argtypes = [H, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_double, C.c_double, C.c_int32] + [C.c_void_p] * 7
+    for fn in ("gto_solve_ik_pose_batch_device", "gto_ik_report_device", "gto_seed_goalsets_device", "gto_seed_goalsets_multi_device",
+               "gto_plan_report_device", "gto_select_plans_device"):
         getattr(lib, fn).restype = C.c_int
     G = C.c_void_p  # gto_occupancy*
     lib.gto_occupancy_from_observation.argtypes = [O, C.c_double, C.c_double, C.c_double, C.POINTER(G)]
@@ -286,6 +290,7 @@ EXPORTED_SYMBOLS = (
     "gto_solve_ik_pose_batch_device", "gto_ik_report_device", "gto_seed_goalsets_device",
     "gto_occupancy_from_observation", "gto_occupancy_from_points", "gto_occupancy_geometry", "gto_occupancy_grid",
     "gto_occupancy_destroy", "gto_solve_base_batch_device", "gto_base_report_device",
+    "gto_seed_goalsets_multi_device", "gto_plan_report_device", "gto_select_plans_device",
 )
 
 
@@ -665,6 +670,39 @@ class SolverHandle:
                                                       int(bool(solutions_f32)), vp(goals_out), vp(n_goals_out),
                                                       vp(n_accepted_out), vp(Q0_out), vp(seed_index_out), vp(seed_cost_out),
                                                       vp(seed_dist_out), vp(stream)), "gto_seed_goalsets_device")
+
+    # -------------------------------------------------------------- several seeds per goal set (GraspChain.plan_objects(n_seeds=k))
+    def seed_goalsets_multi_device(self, B, n_max, n_seeds, scene_id, qc, goals, n_goals, q_solutions, accept, base_pos, interpolate,
+                                   solutions_f32, goals_out=None, n_goals_out=None, n_accepted_out=None, accepted_rows_out=None,
+                                   Q0_out=None, seed_index_out=None, seed_cost_out=None, seed_dist_out=None, stream=None):
+        """gto_seed_goalsets_multi_device: the n_seeds best seeds of every goal set, one slot of goals_out / n_goals_out /
+        Q0_out / seed_index_out (leading shape (B, n_seeds)) each; device pointers or None."""
+        vp = lambda a: None if a is None else C.c_void_p(int(a))
+        self._check(self.lib.gto_seed_goalsets_multi_device(self._h, int(B), int(n_max), int(n_seeds), vp(scene_id), vp(qc), vp(goals),
+                                                            vp(n_goals), vp(q_solutions), vp(accept), vp(base_pos),
+                                                            int(bool(interpolate)), int(bool(solutions_f32)), vp(goals_out),
+                                                            vp(n_goals_out), vp(n_accepted_out), vp(accepted_rows_out), vp(Q0_out),
+                                                            vp(seed_index_out), vp(seed_cost_out), vp(seed_dist_out), vp(stream)),
+                    "gto_seed_goalsets_multi_device")
+
+    def plan_report_device(self, B, n_max, goals, n_goals, standoff, Q, goal_index_out=None, goal_cost_out=None, err_pos_out=None,
+                           err_rot_out=None, stream=None):
+        """gto_plan_report_device: the goal every plan reached (the objective's arg-min goal), that goal's term and err_pos /
+        err_rot (degrees) of the last waypoint against it; device pointers or None."""
+        vp = lambda a: None if a is None else C.c_void_p(int(a))
+        self._check(self.lib.gto_plan_report_device(self._h, int(B), int(n_max), vp(goals), vp(n_goals), vp(standoff), vp(Q),
+                                                    vp(goal_index_out), vp(goal_cost_out), vp(err_pos_out), vp(err_rot_out),
+                                                    vp(stream)), "gto_plan_report_device")
+
+    def select_plans_device(self, B, n_seeds, status, cost, err_pos, err_rot, counts, pos_tol, rot_tol_deg, max_points, Q=None,
+                            dQ=None, best_slot_out=None, class_out=None, Q_out=None, dQ_out=None, stream=None):
+        """gto_select_plans_device: the class of every slot's plan and the best slot of every object, with copies of its
+        rows; device pointers or None."""
+        vp = lambda a: None if a is None else C.c_void_p(int(a))
+        self._check(self.lib.gto_select_plans_device(self._h, int(B), int(n_seeds), vp(status), vp(cost), vp(err_pos), vp(err_rot),
+                                                     vp(counts), float(pos_tol), float(rot_tol_deg), int(max_points), vp(Q), vp(dQ),
+                                                     vp(best_slot_out), vp(class_out), vp(Q_out), vp(dQ_out), vp(stream)),
+                    "gto_select_plans_device")
 
     def solve_base_batch(self, qc, goals, n_goals=None, effort_weight=0.01, max_iter=100):
         """Base placement for B goal sets (gto/base_planner.py:35-123): qc (B,ndof), goals (B,n_max,4,4).

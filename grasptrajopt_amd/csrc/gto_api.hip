@@ -2070,18 +2070,20 @@ int gto_ik_report_device(gto_handle* h, int32_t B, const int32_t* scene_id, cons
   return GTO_OK;
 }
 
-int gto_seed_goalsets_device(gto_handle* h, int32_t B, int32_t n_max, const int32_t* scene_id, const double* qc,
-                             const double* goals, const int32_t* n_goals, const double* q_solutions, const uint8_t* accept,
-                             const double* base_pos, int32_t interpolate, int32_t solutions_f32, double* goals_out,
-                             int32_t* n_goals_out, int32_t* n_accepted_out, double* Q0_out, int32_t* seed_index_out,
-                             double* seed_cost_out, double* seed_dist_out, void* stream) {
-  if (!h) return GTO_ERR_INVALID_ARG;
-  if (B < 0 || n_max < 1) return fail(h, GTO_ERR_INVALID_ARG, "gto_seed_goalsets_device: B must be >= 0 and n_max >= 1");
+// Both seed entry points behind their handle check: the checks, k_seed_score and the choice.  n_seeds = 0: the plain
+// choice (k_seed_select); otherwise the ranked one into n_seeds slots per instance.
+static int seed_goalsets(gto_handle* h, const std::string& name, int32_t B, int32_t n_max, int32_t n_seeds, const int32_t* scene_id,
+                         const double* qc, const double* goals, const int32_t* n_goals, const double* q_solutions,
+                         const uint8_t* accept, const double* base_pos, int32_t interpolate, int32_t solutions_f32,
+                         double* goals_out, int32_t* n_goals_out, int32_t* n_accepted_out, int32_t* accepted_rows_out,
+                         double* Q0_out, int32_t* seed_index_out, double* seed_cost_out, double* seed_dist_out, void* stream) {
+  if (B < 0 || n_max < 1) return fail(h, GTO_ERR_INVALID_ARG, name + ": B must be >= 0 and n_max >= 1");
   if (B == 0) return GTO_OK;
   if (!scene_id || !qc || !goals || !n_goals || !q_solutions || !base_pos)
-    return fail(h, GTO_ERR_INVALID_ARG, "gto_seed_goalsets_device: null input array");
-  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, "gto_seed_goalsets_device handles up to eight optimised joints");
-  if (n_max > 65535 || B > 65535) return fail(h, GTO_ERR_UNSUPPORTED, "gto_seed_goalsets_device: at most 65535 instances of at most 65535 goals in one call");
+    return fail(h, GTO_ERR_INVALID_ARG, name + ": null input array");
+  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, name + " handles up to eight optimised joints");
+  if (n_max > 65535 || B > 65535) return fail(h, GTO_ERR_UNSUPPORTED, name + ": at most 65535 instances of at most 65535 goals in one call");
+  if (n_seeds && (long long)B * n_seeds > 65535) return fail(h, GTO_ERR_UNSUPPORTED, name + ": B * n_seeds must be at most 65535");
   if (h->scenes.empty()) return fail(h, GTO_ERR_NO_SCENE, "no scene has been set");
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t st = stream ? (hipStream_t)stream : h->stream;
@@ -2094,9 +2096,78 @@ int gto_seed_goalsets_device(gto_handle* h, int32_t B, int32_t n_max, const int3
   hipLaunchKernelGGL(k_seed_score, dim3((unsigned)((T + GTO_PLAN_TG - 1) / GTO_PLAN_TG), n_max, B), dim3(256), lds, st, h->d_rb,
                      h->d_px, h->d_py, h->d_pz, h->d_plink, h->d_scenes, (int)h->scenes.size(), scene_id, qc, n_goals,
                      q_solutions, accept, base_pos, T, n_max, solutions_f32 != 0, (double*)h->sd_part.p);
-  hipLaunchKernelGGL(k_seed_select, dim3(B), dim3(64), 0, st, h->d_rb, qc, goals, n_goals, q_solutions, accept,
-                     (const double*)h->sd_part.p, T, T + h->opts.standoff_offset, n_max, interpolate != 0, solutions_f32 != 0,
-                     goals_out, n_goals_out, n_accepted_out, Q0_out, seed_index_out, seed_cost_out, seed_dist_out);
+  if (n_seeds)
+    hipLaunchKernelGGL(k_seed_select_ranked, dim3(B), dim3(64), 0, st, h->d_rb, qc, goals, n_goals, q_solutions, accept,
+                       (const double*)h->sd_part.p, T, T + h->opts.standoff_offset, n_max, interpolate != 0, solutions_f32 != 0,
+                       (int)n_seeds, goals_out, n_goals_out, n_accepted_out, accepted_rows_out, Q0_out, seed_index_out,
+                       seed_cost_out, seed_dist_out);
+  else
+    hipLaunchKernelGGL(k_seed_select, dim3(B), dim3(64), 0, st, h->d_rb, qc, goals, n_goals, q_solutions, accept,
+                       (const double*)h->sd_part.p, T, T + h->opts.standoff_offset, n_max, interpolate != 0, solutions_f32 != 0,
+                       goals_out, n_goals_out, n_accepted_out, Q0_out, seed_index_out, seed_cost_out, seed_dist_out);
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
+}
+
+int gto_seed_goalsets_device(gto_handle* h, int32_t B, int32_t n_max, const int32_t* scene_id, const double* qc,
+                             const double* goals, const int32_t* n_goals, const double* q_solutions, const uint8_t* accept,
+                             const double* base_pos, int32_t interpolate, int32_t solutions_f32, double* goals_out,
+                             int32_t* n_goals_out, int32_t* n_accepted_out, double* Q0_out, int32_t* seed_index_out,
+                             double* seed_cost_out, double* seed_dist_out, void* stream) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  return seed_goalsets(h, "gto_seed_goalsets_device", B, n_max, 0, scene_id, qc, goals, n_goals, q_solutions, accept, base_pos,
+                       interpolate, solutions_f32, goals_out, n_goals_out, n_accepted_out, nullptr, Q0_out, seed_index_out,
+                       seed_cost_out, seed_dist_out, stream);
+}
+
+int gto_seed_goalsets_multi_device(gto_handle* h, int32_t B, int32_t n_max, int32_t n_seeds, const int32_t* scene_id,
+                                   const double* qc, const double* goals, const int32_t* n_goals, const double* q_solutions,
+                                   const uint8_t* accept, const double* base_pos, int32_t interpolate, int32_t solutions_f32,
+                                   double* goals_out, int32_t* n_goals_out, int32_t* n_accepted_out, int32_t* accepted_rows_out,
+                                   double* Q0_out, int32_t* seed_index_out, double* seed_cost_out, double* seed_dist_out,
+                                   void* stream) {
+  // a plain number, looked at before anything else: no handle is needed to refuse it
+  if (n_seeds < 1 || n_seeds > GTO_MAX_SEEDS) return fail(h, GTO_ERR_UNSUPPORTED, "gto_seed_goalsets_multi_device: n_seeds must be in [1, 16]");
+  if (!h) return GTO_ERR_INVALID_ARG;
+  return seed_goalsets(h, "gto_seed_goalsets_multi_device", B, n_max, n_seeds, scene_id, qc, goals, n_goals, q_solutions, accept,
+                       base_pos, interpolate, solutions_f32, goals_out, n_goals_out, n_accepted_out, accepted_rows_out, Q0_out,
+                       seed_index_out, seed_cost_out, seed_dist_out, stream);
+}
+
+int gto_plan_report_device(gto_handle* h, int32_t B, int32_t n_max, const double* goals, const int32_t* n_goals,
+                           const double* standoff, const double* Q, int32_t* goal_index_out, double* goal_cost_out,
+                           double* err_pos_out, double* err_rot_out, void* stream) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (B < 0 || n_max < 1) return fail(h, GTO_ERR_INVALID_ARG, "gto_plan_report_device: B must be >= 0 and n_max >= 1");
+  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, "gto_plan_report_device handles up to eight optimised joints");
+  if (B == 0) return GTO_OK;
+  if (!goals || !n_goals || !Q) return fail(h, GTO_ERR_INVALID_ARG, "gto_plan_report_device: null input array");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t lds = sizeof(double) * plan_cost_lds_doubles_tg(1, h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
+  if (lds > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the report kernel's LDS");
+  HIPCHK(h, raise_dynamic_lds((const void*)k_plan_report, lds));
+  const int T = h->opts.T;
+  hipLaunchKernelGGL(k_plan_report, dim3(B), dim3(256), lds, stream ? (hipStream_t)stream : h->stream, h->d_rb, goals, n_goals,
+                     standoff, Q, T, T + h->opts.standoff_offset, (int)n_max, goal_index_out, goal_cost_out, err_pos_out, err_rot_out);
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
+}
+
+int gto_select_plans_device(gto_handle* h, int32_t B, int32_t n_seeds, const int32_t* status, const double* cost,
+                            const double* err_pos, const double* err_rot, const int32_t* counts, double pos_tol,
+                            double rot_tol_deg, int32_t max_points, const double* Q, const double* dQ, int32_t* best_slot_out,
+                            int32_t* class_out, double* Q_out, double* dQ_out, void* stream) {
+  if (n_seeds < 1 || n_seeds > GTO_MAX_SEEDS) return fail(h, GTO_ERR_UNSUPPORTED, "gto_select_plans_device: n_seeds must be in [1, 16]");
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (B < 0) return fail(h, GTO_ERR_INVALID_ARG, "gto_select_plans_device: B must be >= 0");
+  if (h->np != GTO_NB) return fail(h, GTO_ERR_UNSUPPORTED, "gto_select_plans_device handles up to eight optimised joints");
+  if (B == 0) return GTO_OK;
+  if (!status || !cost || !err_pos || !err_rot || (Q_out && !Q) || (dQ_out && !dQ))
+    return fail(h, GTO_ERR_INVALID_ARG, "gto_select_plans_device: null input array");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_select_plans, dim3(B), dim3(256), 0, stream ? (hipStream_t)stream : h->stream, (int)n_seeds, h->opts.T,
+                     h->rb.ndof, status, cost, err_pos, err_rot, counts, pos_tol, rot_tol_deg, (int)max_points, Q, dQ,
+                     best_slot_out, class_out, Q_out, dQ_out);
   HIPCHK(h, hipGetLastError());
   return GTO_OK;
 }

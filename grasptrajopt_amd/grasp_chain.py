@@ -4,6 +4,9 @@
     (gto_ik_report_device) -> accepted goal sets and seeds (gto_seed_goalsets_device) -> gto_solve_batch_device ->
     optionally gto_check_plans_device and gto_retime_batch_device
 
+(with ``n_seeds`` > 1: gto_seed_goalsets_multi_device -> one gto_solve_batch_device over every object's n_seeds best seeds ->
+gto_plan_report_device -> gto_check_plans_device -> gto_select_plans_device, and the best plan of every object goes on)
+
 for many objects at once, with ONE host synchronisation at the end.  ``IKSolver.solve_ik_batch`` + the filter on the host +
 ``GTOPlanner.plan_goalset`` compute the same thing object by object with a host round trip between the steps; the plans
 are bit-equal (the same seed and goals go into the same solve).
@@ -112,7 +115,7 @@ class GraspChain:
     # ------------------------------------------------------------------ the chain
     def plan_objects(self, qc, ik_goals, plan_goals, n_grasps, fields, base_position, axis_standoff="x", use_standoff=True,
                      interpolate=True, pos_tol=0.01, rot_tol_deg=5.0, ik_collision_threshold=5.0, float32_solutions=True,
-                     observation=None, retime=None):
+                     observation=None, retime=None, n_seeds=1, max_points=5):
         """B objects with up to n_max candidate grasps each.
 
         qc (B, ndof) or (ndof,); ik_goals, plan_goals (B, n_max, 4, 4): the poses IK is solved to and the poses the plan
@@ -125,11 +128,24 @@ class GraspChain:
         feasible grasp, the driver's ``continue``; the plan is then the solve from the constant seed to all goals),
         seed_index (B,) (position among the accepted, -1 without one), seed_cost, seed_dist (B, n_max), q_solutions
         (B, n_max, ndof) (float32 with float32_solutions), err_pos, err_rot, ik_cost, ik_iters, ik_status, accept
-        (B, n_max), and counts (B, T) / durations, retime_status (B,) when asked for."""
+        (B, n_max), and counts (B, T) / durations, retime_status (B,) when asked for.
+
+        n_seeds > 1 solves every object from its n_seeds best seeds (np.lexsort((dist, cost))[:n_seeds]) in one solve of
+        B * n_seeds instances and keeps the best plan: the lowest class (0 reached within pos_tol / rot_tol_deg and no
+        waypoint with more than max_points surface points inside the observation, 1 free, 2 reached, 3 neither, 4 a solve
+        that ended numerically), then the lowest cost, then the lowest slot.  plans, dQ, cost, iters, status, counts are the
+        chosen slot's; seed_index becomes (B, n_seeds) (-1: a slot behind the accepted grasps, which solves slot 0 again);
+        added: best_slot, plan_class (B,), goal_index (B,) (the compacted position of the grasp the plan reached), goal_row
+        (B,) (its row among the object's grasps: where to close the gripper; -1 without an accepted grasp), plan_err_pos,
+        plan_err_rot (B,), slot_cost, slot_class (B, n_seeds), slot_plans (B, n_seeds, ndof, T).  n_seeds = 1 is the chain above, launch for launch."""
+        K = int(n_seeds)
+        multi = K != 1  # K slots per object, a slot being one instance of the solve
         torch, h, d = self._torch, self._handle, self.robot.desc
         ndof, T = d.ndof, self.T
         ik_goals = np.asarray(ik_goals, dtype=np.float64)
         B, n_max = ik_goals.shape[0], ik_goals.shape[1]
+        if not 1 <= K <= 16 or B * K > 65535:
+            raise ValueError("n_seeds must be in [1, 16] and B * n_seeds at most 65535")
         ik_goals = ik_goals.reshape(B, n_max, 16)
         plan_goals = np.asarray(plan_goals, dtype=np.float64).reshape(B, n_max, 16)
         n_grasps = np.ascontiguousarray(np.broadcast_to(np.asarray(n_grasps, dtype=np.int32), (B,)))
@@ -140,7 +156,8 @@ class GraspChain:
         sid = self._scene_ids(fields, B)
         if int(h.opts.max_iter) != int(self.max_iter):
             h.set_opts(max_iter=int(self.max_iter))
-        N = B * n_max
+        N, M = B * n_max, B * K
+        slots = (B, K) if multi else (B,)  # leading shape of what exists once per solve instance
         f64, i32, u8 = torch.float64, torch.int32, torch.uint8
         res = SimpleNamespace()
         with torch.cuda.stream(self.stream):
@@ -156,18 +173,31 @@ class GraspChain:
             d_ikf, d_ikit, d_ikst = self._dev("ik_f", (B, n_max), f64), self._dev("ik_it", (B, n_max), i32), self._dev("ik_st", (B, n_max), i32)
             d_ep, d_er, d_ic = self._dev("err_pos", (B, n_max), f64), self._dev("err_rot", (B, n_max), f64), self._dev("ik_cost", (B, n_max), f64)
             d_acc = self._dev("accept", (B, n_max), u8)
-            d_gc, d_ngc, d_nacc = self._dev("goals_c", (B, n_max, 16), f64), self._dev("n_goals_c", (B,), i32), self._dev("n_acc", (B,), i32)
-            d_Q0, d_si = self._dev("Q0", (B, ndof, T), f64), self._dev("seed_index", (B,), i32)
+            d_gc, d_ngc, d_nacc = self._dev("goals_c", slots + (n_max, 16), f64), self._dev("n_goals_c", slots, i32), self._dev("n_acc", (B,), i32)
+            d_Q0, d_si = self._dev("Q0", slots + (ndof, T), f64), self._dev("seed_index", slots, i32)
             d_sc, d_sd = self._dev("seed_cost", (B, n_max), f64), self._dev("seed_dist", (B, n_max), f64)
             d_Q, d_dQ = self._dev("Q", (B, ndof, T), f64), self._dev("dQ", (B, ndof, T - 1), f64)
-            d_f, d_it, d_stat = self._dev("f", (B,), f64), self._dev("it", (B,), i32), self._dev("stat", (B,), i32)
+            d_f, d_it, d_stat = self._dev("f", slots, f64), self._dev("it", slots, i32), self._dev("stat", slots, i32)
             d_so = None
             if use_standoff:
                 S = standoff_pose(self.standoff_distance, axis_standoff)
-                d_so = self._up("standoff", np.broadcast_to(np.asarray(S, dtype=np.float64).reshape(1, 16), (B, 16)), np.float64)
+                d_so = self._up("standoff", np.broadcast_to(np.asarray(S, dtype=np.float64).reshape(1, 16), (M, 16)), np.float64)
+            so_ptr = None if d_so is None else d_so.data_ptr()
             d_gc.zero_()  # rows behind an object's accepted goals are never read; they are defined all the same
             d_sc.fill_(float("nan"))
             d_sd.fill_(float("nan"))
+            if multi:
+                # per slot: its object's scene, current configuration and base; the slots' plans, of which d_Q gets the best
+                base_s = np.repeat(base, K, axis=0)
+                d_sid_s, d_qc_s = self._up("sid_slot", np.repeat(sid, K), np.int32), self._up("qc_slot", np.repeat(qc, K, axis=0), np.float64)
+                d_base_s = self._up("base_slot", base_s, np.float64)
+                d_Qs, d_dQs = self._dev("slot_Q", (B, K, ndof, T), f64), self._dev("slot_dQ", (B, K, ndof, T - 1), f64)
+                d_rows = self._dev("accepted_rows", (B, n_max), i32)
+                d_gi, d_gcost = self._dev("slot_goal_index", (B, K), i32), self._dev("slot_goal_cost", (B, K), f64)
+                d_pep, d_per = self._dev("slot_err_pos", (B, K), f64), self._dev("slot_err_rot", (B, K), f64)
+                d_scls, d_best, d_cls = self._dev("slot_class", (B, K), i32), self._dev("best_slot", (B,), i32), self._dev("plan_class", (B,), i32)
+                d_rows.fill_(-1)
+            d_cnt = None
             if N:
                 h.solve_ik_pose_batch_device(0, N, d_sid_ik.data_ptr(), d_q0_ik.data_ptr(), d_ikg.data_ptr(), d_base_ik.data_ptr(),
                                              self.ik_max_iter, d_q.data_ptr(), d_ikf.data_ptr(), d_ikit.data_ptr(),
@@ -175,16 +205,32 @@ class GraspChain:
                 h.ik_report_device(N, d_sid_ik.data_ptr(), d_q.data_ptr(), d_ikg.data_ptr(), d_base_ik.data_ptr(), pos_tol,
                                    rot_tol_deg, ik_collision_threshold, d_ep.data_ptr(), d_er.data_ptr(), d_ic.data_ptr(),
                                    d_acc.data_ptr(), st)
-                h.seed_goalsets_device(B, n_max, d_sid.data_ptr(), d_qc.data_ptr(), d_pg.data_ptr(), d_ng.data_ptr(), d_q.data_ptr(),
-                                       d_acc.data_ptr(), d_base.data_ptr(), interpolate, float32_solutions, d_gc.data_ptr(),
-                                       d_ngc.data_ptr(), d_nacc.data_ptr(), d_Q0.data_ptr(), d_si.data_ptr(), d_sc.data_ptr(),
-                                       d_sd.data_ptr(), st)
-                h.solve_batch_device(B, n_max, d_sid.data_ptr(), d_qc.data_ptr(), d_gc.data_ptr(), d_ngc.data_ptr(),
-                                     None if d_so is None else d_so.data_ptr(), d_base.data_ptr(), d_Q0.data_ptr(), d_Q.data_ptr(),
-                                     d_dQ.data_ptr(), d_f.data_ptr(), d_it.data_ptr(), d_stat.data_ptr(), st)
-                if observation is not None:
-                    d_cnt = self._dev("counts", (B, T), i32)
-                    h.check_plans_device(observation, B, d_Q.data_ptr(), d_cnt.data_ptr(), base_pos=base, stream=st)
+                seed_in = (d_sid.data_ptr(), d_qc.data_ptr(), d_pg.data_ptr(), d_ng.data_ptr(), d_q.data_ptr(), d_acc.data_ptr(),
+                           d_base.data_ptr(), interpolate, float32_solutions, d_gc.data_ptr(), d_ngc.data_ptr(), d_nacc.data_ptr())
+                seed_out = (d_Q0.data_ptr(), d_si.data_ptr(), d_sc.data_ptr(), d_sd.data_ptr(), st)
+                if not multi:
+                    h.seed_goalsets_device(B, n_max, *seed_in, *seed_out)
+                    h.solve_batch_device(B, n_max, d_sid.data_ptr(), d_qc.data_ptr(), d_gc.data_ptr(), d_ngc.data_ptr(), so_ptr,
+                                         d_base.data_ptr(), d_Q0.data_ptr(), d_Q.data_ptr(), d_dQ.data_ptr(), d_f.data_ptr(),
+                                         d_it.data_ptr(), d_stat.data_ptr(), st)
+                    if observation is not None:
+                        d_cnt = self._dev("counts", (B, T), i32)
+                        h.check_plans_device(observation, B, d_Q.data_ptr(), d_cnt.data_ptr(), base_pos=base, stream=st)
+                else:
+                    h.seed_goalsets_multi_device(B, n_max, K, *seed_in, d_rows.data_ptr(), *seed_out)
+                    h.solve_batch_device(M, n_max, d_sid_s.data_ptr(), d_qc_s.data_ptr(), d_gc.data_ptr(), d_ngc.data_ptr(), so_ptr,
+                                         d_base_s.data_ptr(), d_Q0.data_ptr(), d_Qs.data_ptr(), d_dQs.data_ptr(), d_f.data_ptr(),
+                                         d_it.data_ptr(), d_stat.data_ptr(), st)
+                    h.plan_report_device(M, n_max, d_gc.data_ptr(), d_ngc.data_ptr(), so_ptr, d_Qs.data_ptr(), d_gi.data_ptr(),
+                                         d_gcost.data_ptr(), d_pep.data_ptr(), d_per.data_ptr(), st)
+                    if observation is not None:
+                        d_cnt = self._dev("counts", (B, K, T), i32)
+                        h.check_plans_device(observation, M, d_Qs.data_ptr(), d_cnt.data_ptr(), base_pos=base_s, stream=st)
+                    sel = (d_stat.data_ptr(), d_f.data_ptr(), d_pep.data_ptr(), d_per.data_ptr(),
+                           None if d_cnt is None else d_cnt.data_ptr(), pos_tol, rot_tol_deg, int(max_points))
+                    h.select_plans_device(M, 1, *sel, class_out=d_scls.data_ptr(), stream=st)  # every slot on its own: its class
+                    h.select_plans_device(B, K, *sel, Q=d_Qs.data_ptr(), dQ=d_dQs.data_ptr(), best_slot_out=d_best.data_ptr(),
+                                          class_out=d_cls.data_ptr(), Q_out=d_Q.data_ptr(), dQ_out=d_dQ.data_ptr(), stream=st)
                 if retime is not None:
                     d_dur, d_rst = self._dev("durations", (B,), f64), self._dev("retime_status", (B,), i32)
                     h.retime_batch_device(B, d_Q.data_ptr(), retime["vmax"], retime["amax"], int(retime.get("subdiv", 2)),
@@ -193,10 +239,13 @@ class GraspChain:
             out = dict(plans=d_Q, dQ=d_dQ, cost=d_f, iters=d_it, status=d_stat, n_accepted=d_nacc, seed_index=d_si, seed_cost=d_sc,
                        seed_dist=d_sd, q_solutions=d_q, err_pos=d_ep, err_rot=d_er, ik_cost=d_ic, ik_iters=d_ikit, ik_status=d_ikst,
                        accept=d_acc)
-            if N and observation is not None:
+            if d_cnt is not None:
                 out["counts"] = d_cnt
             if N and retime is not None:
                 out["durations"], out["retime_status"] = d_dur, d_rst
+            if multi:  # (cost, iters, status and counts hold every slot's until the chosen slot's are picked below)
+                out.update(best_slot=d_best, plan_class=d_cls, slot_class=d_scls, slot_goal_index=d_gi, slot_err_pos=d_pep,
+                           slot_err_rot=d_per, accepted_rows=d_rows, slot_plans=d_Qs)
             host = {k: self._pin("out/" + k, v.shape, v.dtype) for k, v in out.items()}
             for k, v in out.items():
                 host[k].copy_(v, non_blocking=True)
@@ -206,4 +255,15 @@ class GraspChain:
         res.accept = res.accept.astype(bool)
         if float32_solutions:
             res.q_solutions = res.q_solutions.astype(np.float32)
+        if multi:  # the chosen slot's entries of the small per-slot arrays, picked on the host
+            rows, best = np.arange(B), res.best_slot
+            res.slot_cost, res.slot_iters, res.slot_status = res.cost, res.iters, res.status
+            res.cost, res.iters, res.status = res.slot_cost[rows, best], res.slot_iters[rows, best], res.slot_status[rows, best]
+            res.goal_index = res.slot_goal_index[rows, best]
+            res.plan_err_pos, res.plan_err_rot = res.slot_err_pos[rows, best], res.slot_err_rot[rows, best]
+            if hasattr(res, "counts"):
+                res.slot_counts = res.counts
+                res.counts = res.slot_counts[rows, best]
+            known = (res.n_accepted > 0) & (res.goal_index >= 0)
+            res.goal_row = np.where(known, res.accepted_rows[rows, np.maximum(res.goal_index, 0)], -1).astype(np.int32)
         return res

@@ -705,6 +705,73 @@ int gto_base_report_device(gto_handle* h, gto_occupancy* occ, int32_t B, int32_t
                            const double* goals, const double* y, const double* q, double* err_pos_out, double* err_rot_out,
                            int32_t* collision_out, int32_t* first_free_out, void* stream);
 
+/*
+ * ---- several seeds per goal set, and the best of their plans --------------------------------------------------------------
+ * GTOPlanner.plan_goalset solves from the one seed np.lexsort((dist, cost))[0] names (gto/gto_planner.py:193-219): a local
+ * solver started there finds that seed's optimum.  The three entry points below solve a goal set from its n_seeds best
+ * seeds and keep the best plan: gto_seed_goalsets_multi_device -> ONE gto_solve_batch_device over B * n_seeds instances ->
+ * gto_plan_report_device -> gto_check_plans_device -> gto_select_plans_device, on one stream.  They are additions (the ABI
+ * number stays); they take device pointers and `stream` (NULL = the handle's stream), enqueue without a host
+ * synchronisation and validate host-side facts only; their workspace lives on the handle (the rule of
+ * gto_check_plans_device); B = 0 returns GTO_OK without a launch; handles with more than eight optimised joints:
+ * GTO_ERR_UNSUPPORTED; every object's result is bit for bit the same in any batch and at any position in it.
+ *
+ * gto_seed_goalsets_multi_device: the inputs, compaction, candidates, scores and order of gto_seed_goalsets_device; the first
+ * n_seeds entries of np.lexsort((dist, cost)) over the compacted positions come out (cost, then distance, then position, a
+ * NaN after every number), one SLOT each.  n_seeds outside [1, GTO_MAX_SEEDS] or B * n_seeds > 65535: GTO_ERR_UNSUPPORTED
+ * (n_seeds is looked at first, before the handle).
+ *   goals_out [B][n_seeds][n_max][16], n_goals_out [B][n_seeds]   the instance's compacted goals and their count, written once
+ *            per slot: with Q0_out the B * n_seeds slots are goals, n_goals and Q0 of B * n_seeds instances of
+ *            gto_solve_batch_device
+ *   n_accepted_out [B]; accepted_rows_out [B][n_max] int32: the original row of compacted position j (positions at or
+ *            beyond the count are left untouched); seed_cost_out, seed_dist_out [B][n_max] as in gto_seed_goalsets_device
+ *   Q0_out [B][n_seeds][ndof][T], seed_index_out [B][n_seeds]
+ *       slot r < min(n_seeds, n_accepted)   the r-th ranked candidate, built as gto_seed_goalsets_device builds its chosen one
+ *       slot r >= n_accepted >= 1           seed_index_out = -1 and Q0 = slot 0's: the solve is a duplicate, which
+ *                                           gto_select_plans_device never prefers (ties go to the lower slot)
+ *       no accepted solution                the branch of gto_seed_goalsets_device in every slot
+ * Any output may be NULL.  With n_seeds = 1 every output is bit-equal to gto_seed_goalsets_device.
+ */
+#define GTO_MAX_SEEDS 16
+int gto_seed_goalsets_multi_device(gto_handle* h, int32_t B, int32_t n_max, int32_t n_seeds, const int32_t* scene_id,
+                                   const double* qc, const double* goals, const int32_t* n_goals, const double* q_solutions,
+                                   const uint8_t* accept, const double* base_pos, int32_t interpolate, int32_t solutions_f32,
+                                   double* goals_out, int32_t* n_goals_out, int32_t* n_accepted_out, int32_t* accepted_rows_out,
+                                   double* Q0_out, int32_t* seed_index_out, double* seed_cost_out, double* seed_dist_out,
+                                   void* stream);
+/*
+ * Which goal a plan reached and how closely: B plans Q [B][ndof][T] against goals [B][n_max][16], n_goals [B] (read as at
+ * most n_max) and standoff [B][16] or NULL, in the layout of gto_solve_batch_device.
+ *   goal_index_out [b]  the goal whose term of the objective is lowest: the point-matching sum at waypoint T - 1, plus the
+ *                       standoff term at waypoint T + standoff_offset when standoff is given (gto/gto_planner.py:86-105);
+ *                       the lowest index wins ties: goal_argmin of gto_eval_objective (the same device code)
+ *   goal_cost_out [b]   that term's value (f_goal of gto_eval_objective)
+ *   err_pos_out, err_rot_out [b]   T_ee(q_{T-1}) against that goal's RT, as gto_ik_report_device reports q_{T-1} against it
+ *                       (the same device code: the same bits)
+ * A plan with a non-finite entry: goal_index = -1, cost and errors NaN; nobody else's result changes.  Any output may be
+ * NULL.
+ */
+int gto_plan_report_device(gto_handle* h, int32_t B, int32_t n_max, const double* goals, const int32_t* n_goals,
+                           const double* standoff, const double* Q, int32_t* goal_index_out, double* goal_cost_out,
+                           double* err_pos_out, double* err_rot_out, void* stream);
+/*
+ * The best of every object's n_seeds plans.  status, cost, err_pos, err_rot [B][n_seeds], counts [B][n_seeds][T] or NULL,
+ * Q [B][n_seeds][ndof][T] and dQ [B][n_seeds][ndof][T-1] are what gto_solve_batch_device, gto_plan_report_device and
+ * gto_check_plans_device wrote for the B * n_seeds instances.  Per slot:
+ *   valid    status != GTO_STATUS_NUMERICAL and cost finite
+ *   free     counts is NULL, or every waypoint's count is in [0, max_points] (a count of -1 is not free)
+ *   reached  err_pos < pos_tol && err_rot < rot_tol_deg (false on NaN)
+ *   class    0 valid, free, reached | 1 valid, free | 2 valid, reached | 3 valid | 4 not valid
+ * best_slot_out [B]: the lowest class, then the lowest cost (a NaN after every number), then the lowest slot.  class_out [B]:
+ * that slot's class; 0 is a plan the evaluator counts as usable.  Q_out [B][ndof][T], dQ_out [B][ndof][T-1]: copies of the
+ * chosen slot's rows.  Any output may be NULL (Q / dQ may then be NULL too).  n_seeds outside [1, GTO_MAX_SEEDS]:
+ * GTO_ERR_UNSUPPORTED (looked at first, before the handle).
+ */
+int gto_select_plans_device(gto_handle* h, int32_t B, int32_t n_seeds, const int32_t* status, const double* cost,
+                            const double* err_pos, const double* err_rot, const int32_t* counts, double pos_tol,
+                            double rot_tol_deg, int32_t max_points, const double* Q, const double* dQ, int32_t* best_slot_out,
+                            int32_t* class_out, double* Q_out, double* dQ_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
