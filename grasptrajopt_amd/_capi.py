@@ -16,9 +16,11 @@ from .robot_desc import RobotDesc
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GTO_HIP_LIB", os.path.join(_HERE, "csrc", "libgto_hip.so"))  # override: A/B builds
 
+# include/gto_solver.h
 GTO_MAX_FRAMES, GTO_MAX_LINKS, GTO_MAX_OPT, GTO_MAX_DOF = 32, 32, 16, 32
-GRAD_CENTRAL_DIFF, GRAD_ZERO = 0, 1
-STATUS_CONVERGED, STATUS_MAX_ITER, STATUS_NUMERICAL = 0, 1, 2
+GTO_GRAD_CENTRAL_DIFF, GTO_GRAD_ZERO = 0, 1
+GTO_STATUS_CONVERGED, GTO_STATUS_MAX_ITER, GTO_STATUS_NUMERICAL = 0, 1, 2
+ABI_VERSION = 1012  # GTO_ABI_VERSION (checked against gto_version() when the library is loaded)
 
 _pd = C.POINTER(C.c_double)
 _pi = C.POINTER(C.c_int32)
@@ -63,6 +65,99 @@ def _p(a: Optional[np.ndarray], typ):
     return None if a is None else a.ctypes.data_as(typ)
 
 
+def _vp(a):
+    """A device pointer or a stream (an int such as torch.Tensor.data_ptr()) or None."""
+    return None if a is None else C.c_void_p(int(a))
+
+
+def _per_instance(x, B) -> np.ndarray:
+    """One int32 per instance from a scalar or an array (B,)."""
+    return _i32(np.broadcast_to(np.asarray(x), (B,)))
+
+
+def _bases(base_pos, B) -> np.ndarray:
+    """One base position per instance, (B, 3), from (3,) or (B, 3)."""
+    return _f64(np.broadcast_to(_f64(base_pos).reshape(-1, 3), (B, 3)))
+
+
+def _prototypes():
+    """Every entry point of include/gto_solver.h, in its order: name -> (restype, argtypes).  The only place where this
+    binding states a signature; tests/test_capi_cpu.py compares it with the header argument by argument."""
+    I, I32, I64, D, F = C.c_int, C.c_int32, C.c_int64, C.c_double, C.c_float
+    V = C.c_void_p  # gto_handle*, gto_observation*, gto_occupancy*, device pointers and streams
+    PV = C.POINTER(V)  # out-handles, void* const*
+    pu8, pu64 = C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)
+    desc, opts = C.POINTER(CRobotDesc), C.POINTER(CSolverOpts)
+    solve = [V, I32, I32] + [V] * 12
+    scene = [V, I32, _pf, _pf, _pi, _pd, D]
+    depth = [I, _pf, I32, I32, _pd, _pd, _pd, _pd, pu8, D]  # device, image, camera, mask, threshold
+    seeds = [V] * 7 + [I32, I32]
+    return {
+        "gto_default_opts": (None, [opts]),
+        "gto_version": (I32, []),
+        "gto_create": (I, [desc, opts, I, PV]),
+        "gto_destroy": (None, [V]),
+        "gto_last_error": (C.c_char_p, [V]),
+        "gto_set_opts": (I, [V, opts]),
+        "gto_set_scene": (I, scene),
+        "gto_set_scene_values": (I, scene),
+        "gto_drop_scene": (I, [V, I32]),
+        "gto_solve_batch": (I, solve),
+        "gto_solve_batch_device": (I, solve + [V]),
+        "gto_share_scene": (I, [V, I32, V, I32]),
+        "gto_share_scene_halves": (I, [V, I32, V, I32, I32, I32]),
+        "gto_solve_ik_batch": (I, [V, I32, _pi, _pd, _pd, _pd, I32, _pd, _pd, _pi, _pi]),
+        "gto_solve_ik_pose_batch": (I, [V, I32, I32, _pi, _pd, _pd, _pd, I32, _pd, _pd, _pi, _pi]),
+        "gto_solve_base_batch": (I, [V, I32, I32, _pi, _pd, _pd, D, I32, _pd, _pd, _pd, _pi, _pi]),
+        "gto_set_mode": (I, [V, I32]),
+        "gto_set_lanes": (I, [V, I32, I32, I32]),
+        "gto_set_lane_streams": (I, [V, I32, PV]),
+        "gto_set_stream": (I, [V, V]),
+        "gto_last_kernel_time": (I, [V, _pd, _pi]),
+        "gto_last_kernel_work": (I, [V, pu64, pu64]),
+        "gto_last_kernel_profile": (I, [V, I32, _pd, _pi, pu64, pu64]),
+        "gto_set_profiling": (I, [V, I32]),
+        "gto_eval_fk": (I, [V, I32, _pd, _pd]),
+        "gto_eval_points": (I, [V, I32, I32, _pd, _pd, I32, _pd, _pi, _pd, _pd]),
+        "gto_eval_points_hessian": (I, [V, I32, I32, _pd, _pd, I32, _pd]),
+        "gto_eval_objective": (I, [V, I32, I32, _pi, _pd, _pi, _pd, _pd, _pd, _pd, _pd, _pd, _pi]),
+        "gto_eval_obstacle_normal_eq": (I, [V, I32, _pi, _pd, _pd, _pd, _pd, _pd]),
+        "gto_eval_base_objective": (I, [V, I32, I32, _pi, _pd, _pd, _pd, D, _pd]),
+        "gto_plan_cost": (I, [V, I32, I32, _pd, _pd, _pd, _pd]),
+        "gto_depth_sdf_cost": (I, depth + [_pd, I64, F, F, _pf, pu8, _pf, _pd, pu8]),
+        "gto_scene_from_depth": (I, [V, I32, _pf, I32, I32, _pd, _pd, _pd, _pd, pu8, _pf, D, D, D, F, F, _pi, _pd, _pd]),
+        "gto_cloud_sdf_cost": (I, [I, _pd, _pd, I64, I32, _pd, I64, F, F, _pf, pu8, _pf, _pi]),
+        "gto_scene_from_clouds": (I, [V, I32, _pd, _pd, I64, I64, I32, D, D, F, F, _pi, _pd, _pd]),
+        "gto_get_scene_fields": (I, [V, I32, _pf, _pf]),
+        "gto_observation_from_depth": (I, depth + [PV]),
+        "gto_observation_from_cloud": (I, [I, _pd, _pd, I64, I32, PV]),
+        "gto_observation_destroy": (None, [V]),
+        "gto_observation_sdf": (I, [V, _pd, I64, _pf, pu8]),
+        "gto_observation_check_posed": (I, [V, _pd, I32, _pd, I32, _pi]),
+        "gto_check_plans": (I, [V, V, I32, _pd, _pd, I32, _pi]),
+        "gto_check_plans_device": (I, [V, V, I32, V, _pd, I32, V, V]),
+        "gto_retime_batch": (I, [V, I32, _pd, _pd, _pd, I32, I32, _pd, _pd, _pd, _pd, _pd, _pd, _pi]),
+        "gto_retime_batch_device": (I, [V, I32, V, _pd, _pd, I32, I32] + [V] * 8),
+        "gto_solve_ik_pose_batch_device": (I, [V, I32, I32] + [V] * 4 + [I32] + [V] * 5),
+        "gto_ik_report_device": (I, [V, I32] + [V] * 4 + [D] * 3 + [V] * 5),
+        "gto_seed_goalsets_device": (I, [V, I32, I32] + seeds + [V] * 8),
+        "gto_occupancy_from_observation": (I, [V, D, D, D, PV]),
+        "gto_occupancy_from_points": (I, [I, _pd, I64, D, D, D, PV]),
+        "gto_occupancy_geometry": (I, [V, _pd, _pi, _pd, _pd]),
+        "gto_occupancy_grid": (I, [V, pu8]),
+        "gto_occupancy_destroy": (None, [V]),
+        "gto_solve_base_batch_device": (I, [V, I32, I32, _pi, V, V, D, I32] + [V] * 6),
+        "gto_base_report_device": (I, [V, V, I32, I32, _pi] + [V] * 9),
+        "gto_seed_goalsets_multi_device": (I, [V, I32, I32, I32] + seeds + [V] * 9),
+        "gto_plan_report_device": (I, [V, I32, I32] + [V] * 9),
+        "gto_select_plans_device": (I, [V, I32, I32] + [V] * 5 + [D, D, I32] + [V] * 7),
+    }
+
+
+PROTOTYPES = _prototypes()
+EXPORTED_SYMBOLS = tuple(PROTOTYPES)
+
+
 def pack_robot_desc(desc: RobotDesc, link_ee: str, link_gripper: str,
                     n_gripper_points: Optional[int] = None) -> Tuple[CRobotDesc, list]:
     """Build the C struct; the returned list keeps the backing arrays alive."""
@@ -102,11 +197,6 @@ def pack_robot_desc(desc: RobotDesc, link_ee: str, link_gripper: str,
     c.gripper_points = _p(k(_f64(gp)), _pd)
     return c, keep
 
-
-# include/gto_solver.h
-GTO_GRAD_CENTRAL_DIFF, GTO_GRAD_ZERO = 0, 1
-GTO_STATUS_CONVERGED, GTO_STATUS_MAX_ITER, GTO_STATUS_NUMERICAL = 0, 1, 2
-ABI_VERSION = 1012  # include/gto_solver.h GTO_ABI_VERSION (checked against gto_version() when the library is loaded)
 
 _lib = None
 
@@ -168,7 +258,7 @@ def load_library(path: Optional[str] = None):
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the GTO solve path.")
     _preload_hip_runtime()
     lib = C.CDLL(p)
-    lib.gto_version.restype = C.c_int32
+    lib.gto_version.restype = PROTOTYPES["gto_version"][0]
     # one ABI number for wrapper and library: a library named by GTO_HIP_LIB for an A/B run has to be a build of THIS
     # interface -- an older one that lacks a symbol, or has it with other arguments (gto_scene_from_depth once got a pointer
     # in the middle of its signature), is refused here instead of being called with shifted arguments
@@ -181,117 +271,12 @@ def load_library(path: Optional[str] = None):
     if missing:
         raise RuntimeError(f"{p}: ABI version {v} but no {', '.join(missing)}: an older build of this interface; "
                            "rebuild the library from this tree (__graft_entry__.build())")
-    H = C.c_void_p
-    lib.gto_default_opts.argtypes = [C.POINTER(CSolverOpts)]
-    lib.gto_default_opts.restype = None
-    lib.gto_create.argtypes = [C.POINTER(CRobotDesc), C.POINTER(CSolverOpts), C.c_int, C.POINTER(H)]
-    lib.gto_destroy.argtypes = [H]
-    lib.gto_destroy.restype = None
-    lib.gto_last_error.argtypes = [H]
-    lib.gto_last_error.restype = C.c_char_p
-    lib.gto_set_opts.argtypes = [H, C.POINTER(CSolverOpts)]
-    lib.gto_set_scene.argtypes = [H, C.c_int32, _pf, _pf, _pi, _pd, C.c_double]
-    lib.gto_set_scene_values.argtypes = [H, C.c_int32, _pf, _pf, _pi, _pd, C.c_double]
-    lib.gto_drop_scene.argtypes = [H, C.c_int32]
-    solve_args = [H, C.c_int32, C.c_int32] + [C.c_void_p] * 12
-    lib.gto_solve_batch.argtypes = solve_args
-    lib.gto_solve_batch_device.argtypes = solve_args + [C.c_void_p]
-    lib.gto_last_kernel_time.argtypes = [H, _pd, _pi]
-    lib.gto_set_profiling.argtypes = [H, C.c_int32]
-    lib.gto_last_kernel_work.argtypes = [H, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.gto_last_kernel_profile.argtypes = [H, C.c_int32, _pd, _pi, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.gto_last_kernel_profile.restype = C.c_int
-    lib.gto_set_stream.argtypes = [H, C.c_void_p]
-    lib.gto_set_mode.argtypes = [H, C.c_int32]
-    lib.gto_set_lanes.argtypes = [H, C.c_int32, C.c_int32, C.c_int32]
-    lib.gto_set_lane_streams.argtypes = [H, C.c_int32, C.POINTER(C.c_void_p)]
-    lib.gto_share_scene.argtypes = [H, C.c_int32, H, C.c_int32]
-    lib.gto_share_scene_halves.argtypes = [H, C.c_int32, H, C.c_int32, C.c_int32, C.c_int32]
-    lib.gto_share_scene_halves.restype = C.c_int
-    lib.gto_scene_from_depth.argtypes = [H, C.c_int32, _pf, C.c_int32, C.c_int32, _pd, _pd, _pd, _pd, C.POINTER(C.c_uint8), _pf, C.c_double,
-                                         C.c_double, C.c_double, C.c_float, C.c_float, _pi, _pd, _pd]
-    lib.gto_scene_from_depth.restype = C.c_int
-    lib.gto_get_scene_fields.argtypes = [H, C.c_int32, _pf, _pf]
-    lib.gto_get_scene_fields.restype = C.c_int
-    lib.gto_eval_fk.argtypes = [H, C.c_int32, _pd, _pd]
-    lib.gto_eval_points.argtypes = [H, C.c_int32, C.c_int32, _pd, _pd, C.c_int32, _pd, _pi, _pd, _pd]
-    lib.gto_eval_points_hessian.argtypes = [H, C.c_int32, C.c_int32, _pd, _pd, C.c_int32, _pd]
-    lib.gto_eval_points_hessian.restype = C.c_int
-    lib.gto_eval_objective.argtypes = [H, C.c_int32, C.c_int32, _pi, _pd, _pi, _pd, _pd, _pd, _pd, _pd, _pd, _pi]
-    lib.gto_eval_obstacle_normal_eq.argtypes = [H, C.c_int32, _pi, _pd, _pd, _pd, _pd, _pd]
-    lib.gto_plan_cost.argtypes = [H, C.c_int32, C.c_int32, _pd, _pd, _pd, _pd]
-    lib.gto_solve_ik_batch.argtypes = [H, C.c_int32, _pi, _pd, _pd, _pd, C.c_int32, _pd, _pd, _pi, _pi]
-    lib.gto_solve_ik_pose_batch.argtypes = [H, C.c_int32, C.c_int32, _pi, _pd, _pd, _pd, C.c_int32, _pd, _pd, _pi, _pi]
-    lib.gto_solve_base_batch.argtypes = [H, C.c_int32, C.c_int32, _pi, _pd, _pd, C.c_double, C.c_int32, _pd, _pd, _pd, _pi, _pi]
-    lib.gto_eval_base_objective.argtypes = [H, C.c_int32, C.c_int32, _pi, _pd, _pd, _pd, C.c_double, _pd]
-    lib.gto_retime_batch.argtypes = [H, C.c_int32, _pd, _pd, _pd, C.c_int32, C.c_int32, _pd, _pd, _pd, _pd, _pd, _pd, _pi]
-    lib.gto_retime_batch_device.argtypes = [H, C.c_int32, C.c_void_p, _pd, _pd, C.c_int32, C.c_int32] + [C.c_void_p] * 8
-    _pu8 = C.POINTER(C.c_uint8)
-    lib.gto_depth_sdf_cost.argtypes = [C.c_int, _pf, C.c_int32, C.c_int32, _pd, _pd, _pd, _pd, _pu8, C.c_double, _pd, C.c_int64,
-                                       C.c_float, C.c_float, _pf, _pu8, _pf, _pd, _pu8]
-    _i64 = C.c_int64
-    lib.gto_cloud_sdf_cost.argtypes = [C.c_int, _pd, _pd, _i64, C.c_int32, _pd, _i64, C.c_float, C.c_float, _pf, _pu8, _pf, _pi]
-    lib.gto_scene_from_clouds.argtypes = [H, C.c_int32, _pd, _pd, _i64, _i64, C.c_int32, C.c_double, C.c_double, C.c_float, C.c_float,
-                                          _pi, _pd, _pd]
-    O = C.c_void_p  # gto_observation*
-    lib.gto_observation_from_depth.argtypes = [C.c_int, _pf, C.c_int32, C.c_int32, _pd, _pd, _pd, _pd, _pu8, C.c_double, C.POINTER(O)]
-    lib.gto_observation_from_cloud.argtypes = [C.c_int, _pd, _pd, _i64, C.c_int32, C.POINTER(O)]
-    lib.gto_observation_destroy.argtypes = [O]
-    lib.gto_observation_destroy.restype = None
-    lib.gto_observation_sdf.argtypes = [O, _pd, _i64, _pf, _pu8]
-    lib.gto_observation_check_posed.argtypes = [O, _pd, C.c_int32, _pd, C.c_int32, _pi]
-    lib.gto_check_plans.argtypes = [H, O, C.c_int32, _pd, _pd, C.c_int32, _pi]
-    lib.gto_check_plans_device.argtypes = [H, O, C.c_int32, C.c_void_p, _pd, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.gto_solve_ik_pose_batch_device.argtypes = [H, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 5
-    lib.gto_ik_report_device.argtypes = [H, C.c_int32] + [C.c_void_p] * 4 + [C.c_double] * 3 + [C.c_void_p] * 5
-    lib.gto_seed_goalsets_device.argtypes = [H, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32, C.c_int32] + [C.c_void_p] * 8
-    lib.gto_seed_goalsets_multi_device.argtypes = [H, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32, C.c_int32] + [C.c_void_p] * 9
-    lib.gto_plan_report_device.argtypes = [H, C.c_int32, C.c_int32] + [C.c_void_p] * 9
-    lib.gto_select_plans_device.argtypes = [H, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_double, C.c_double, C.c_int32] + [C.c_void_p] * 7
-    for fn in ("gto_solve_ik_pose_batch_device", "gto_ik_report_device", "gto_seed_goalsets_device", "gto_seed_goalsets_multi_device",
-               "gto_plan_report_device", "gto_select_plans_device"):
-        getattr(lib, fn).restype = C.c_int
-    G = C.c_void_p  # gto_occupancy*
-    lib.gto_occupancy_from_observation.argtypes = [O, C.c_double, C.c_double, C.c_double, C.POINTER(G)]
-    lib.gto_occupancy_from_points.argtypes = [C.c_int, _pd, _i64, C.c_double, C.c_double, C.c_double, C.POINTER(G)]
-    lib.gto_occupancy_geometry.argtypes = [G, _pd, _pi, _pd, _pd]
-    lib.gto_occupancy_grid.argtypes = [G, _pu8]
-    lib.gto_occupancy_destroy.argtypes = [G]
-    lib.gto_occupancy_destroy.restype = None
-    lib.gto_solve_base_batch_device.argtypes = [H, C.c_int32, C.c_int32, _pi, C.c_void_p, C.c_void_p, C.c_double, C.c_int32] + [C.c_void_p] * 6
-    lib.gto_base_report_device.argtypes = [H, G, C.c_int32, C.c_int32, _pi] + [C.c_void_p] * 9
-    for fn in ("gto_occupancy_from_observation", "gto_occupancy_from_points", "gto_occupancy_geometry", "gto_occupancy_grid",
-               "gto_solve_base_batch_device", "gto_base_report_device"):
-        getattr(lib, fn).restype = C.c_int
-    for fn in ("gto_observation_from_depth", "gto_observation_from_cloud", "gto_observation_sdf", "gto_observation_check_posed", "gto_check_plans",
-               "gto_check_plans_device"):
-        getattr(lib, fn).restype = C.c_int
-    for fn in ("gto_cloud_sdf_cost", "gto_scene_from_clouds", "gto_create", "gto_set_opts", "gto_set_scene", "gto_set_scene_values", "gto_drop_scene", "gto_solve_batch",
-               "gto_solve_batch_device", "gto_last_kernel_time", "gto_last_kernel_work", "gto_set_profiling", "gto_set_stream", "gto_set_mode", "gto_set_lanes", "gto_set_lane_streams", "gto_share_scene",
-               "gto_eval_fk", "gto_eval_points", "gto_eval_points_hessian", "gto_eval_objective", "gto_eval_obstacle_normal_eq", "gto_plan_cost", "gto_solve_ik_batch",
-               "gto_solve_ik_pose_batch", "gto_solve_base_batch", "gto_eval_base_objective", "gto_depth_sdf_cost", "gto_retime_batch", "gto_retime_batch_device"):
-        getattr(lib, fn).restype = C.c_int
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if path is None:
         _lib = lib
     return lib
-
-
-EXPORTED_SYMBOLS = (
-    "gto_default_opts", "gto_version", "gto_create", "gto_destroy", "gto_last_error", "gto_set_opts",
-    "gto_set_scene", "gto_set_scene_values", "gto_drop_scene", "gto_solve_batch", "gto_solve_batch_device",
-    "gto_last_kernel_time", "gto_last_kernel_work", "gto_last_kernel_profile", "gto_set_profiling", "gto_set_stream", "gto_set_mode", "gto_set_lanes", "gto_set_lane_streams", "gto_share_scene", "gto_share_scene_halves",
-    "gto_eval_fk", "gto_eval_points", "gto_eval_points_hessian",
-    "gto_eval_objective", "gto_eval_obstacle_normal_eq", "gto_plan_cost", "gto_solve_ik_batch", "gto_solve_ik_pose_batch",
-    "gto_solve_base_batch", "gto_eval_base_objective", "gto_depth_sdf_cost", "gto_scene_from_depth", "gto_get_scene_fields",
-    "gto_cloud_sdf_cost", "gto_scene_from_clouds",
-    "gto_retime_batch", "gto_retime_batch_device",
-    "gto_observation_from_depth", "gto_observation_from_cloud", "gto_observation_destroy", "gto_observation_sdf",
-    "gto_observation_check_posed", "gto_check_plans", "gto_check_plans_device",
-    "gto_solve_ik_pose_batch_device", "gto_ik_report_device", "gto_seed_goalsets_device",
-    "gto_occupancy_from_observation", "gto_occupancy_from_points", "gto_occupancy_geometry", "gto_occupancy_grid",
-    "gto_occupancy_destroy", "gto_solve_base_batch_device", "gto_base_report_device",
-    "gto_seed_goalsets_multi_device", "gto_plan_report_device", "gto_select_plans_device",
-)
 
 
 def default_opts() -> CSolverOpts:
@@ -442,10 +427,10 @@ class SolverHandle:
                     np.empty(0, dtype=np.int32), np.empty(0, dtype=np.int32))
         goals = _f64(goals).reshape(B, -1, 16)
         n_max = goals.shape[1]
-        n_goals = _i32(np.broadcast_to(np.asarray(n_goals), (B,)))
-        scene_id = _i32(np.broadcast_to(np.asarray(scene_id), (B,)))
+        n_goals = _per_instance(n_goals, B)
+        scene_id = _per_instance(scene_id, B)
         so = None if standoff is None else _f64(np.broadcast_to(_f64(standoff).reshape(-1, 16), (B, 16)))
-        base = _f64(np.broadcast_to(_f64(base_pos).reshape(-1, 3), (B, 3)))
+        base = _bases(base_pos, B)
         Q0 = _f64(Q0).reshape(B, d.ndof, T)
         if out is not None:
             Q, dQ, cost, iters, status = out
@@ -459,19 +444,17 @@ class SolverHandle:
             cost = np.empty(B)
             iters = np.empty(B, dtype=np.int32)
             status = np.empty(B, dtype=np.int32)
-        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        rc = self.lib.gto_solve_batch(self._h, B, n_max, vp(scene_id), vp(qc), vp(goals), vp(n_goals),
-                                      vp(so), vp(base), vp(Q0), vp(Q), vp(dQ), vp(cost), vp(iters), vp(status))
+        arrays = (scene_id, qc, goals, n_goals, so, base, Q0, Q, dQ, cost, iters, status)
+        rc = self.lib.gto_solve_batch(self._h, B, n_max, *(_p(a, C.c_void_p) for a in arrays))
         self._check(rc, "gto_solve_batch")
         return Q, dQ, cost, iters, status
 
     def solve_batch_device(self, B, n_max, scene_id, qc, goals, n_goals, standoff, base_pos, Q0,
                            Q_out, dQ_out, cost_out, iters_out, status_out, stream=None):
         """All arguments are device pointers (ints, e.g. torch.Tensor.data_ptr()) or None."""
-        vp = lambda a: None if a is None else C.c_void_p(int(a))
-        rc = self.lib.gto_solve_batch_device(self._h, B, n_max, vp(scene_id), vp(qc), vp(goals), vp(n_goals),
-                                             vp(standoff), vp(base_pos), vp(Q0), vp(Q_out), vp(dQ_out),
-                                             vp(cost_out), vp(iters_out), vp(status_out), vp(stream))
+        rc = self.lib.gto_solve_batch_device(self._h, B, n_max, _vp(scene_id), _vp(qc), _vp(goals), _vp(n_goals),
+                                             _vp(standoff), _vp(base_pos), _vp(Q0), _vp(Q_out), _vp(dQ_out),
+                                             _vp(cost_out), _vp(iters_out), _vp(status_out), _vp(stream))
         self._check(rc, "gto_solve_batch_device")
 
     def share_scene(self, scene_id, src: "SolverHandle", src_scene_id=None, all_from: int = 0, obs_from: int = 1):
@@ -490,7 +473,7 @@ class SolverHandle:
     def set_stream(self, stream):
         """Bind every launch/copy of this handle to the caller's HIP stream (an int such as
         torch.cuda.Stream.cuda_stream); None restores a private stream."""
-        self._check(self.lib.gto_set_stream(self._h, None if stream is None else C.c_void_p(int(stream))), "gto_set_stream")
+        self._check(self.lib.gto_set_stream(self._h, _vp(stream)), "gto_set_stream")
 
     MODE_ROUNDS, MODE_SINGLE_LAUNCH = 0, 1
 
@@ -551,7 +534,7 @@ class SolverHandle:
         want_field=False); the others are None and cost neither device memory nor a transfer."""
         q = _f64(q).reshape(-1, self.desc.ndof)
         nq, P = q.shape[0], self.desc.n_points
-        base = _f64(np.broadcast_to(_f64(base_pos).reshape(-1, 3), (nq, 3)))
+        base = _bases(base_pos, nq)
         if want is None:
             want = ("xyz", "off", "val", "grad") if want_field else ("xyz",)
         xyz = np.empty((nq, P, 3)) if "xyz" in want else None
@@ -567,7 +550,7 @@ class SolverHandle:
         """Hessian of the selected cost field at the surface points of configurations q: (nq, P, 3, 3), gto/sdf_callback.py:165-183."""
         q = _f64(q).reshape(-1, self.desc.ndof)
         nq, P = q.shape[0], self.desc.n_points
-        base = _f64(np.broadcast_to(_f64(base_pos).reshape(-1, 3), (nq, 3)))
+        base = _bases(base_pos, nq)
         out = np.empty((nq, P, 3, 3))
         self._check(self.lib.gto_eval_points_hessian(self._h, scene_id, nq, _p(q, _pd), _p(base, _pd), int(use_obs), _p(out, _pd)), "gto_eval_points_hessian")
         return out
@@ -578,10 +561,10 @@ class SolverHandle:
         B = Q.shape[0]
         goals = _f64(goals).reshape(B, -1, 16)
         n_max = goals.shape[1]
-        n_goals = _i32(np.broadcast_to(np.asarray(n_goals), (B,)))
-        scene_id = _i32(np.broadcast_to(np.asarray(scene_id), (B,)))
+        n_goals = _per_instance(n_goals, B)
+        scene_id = _per_instance(scene_id, B)
         so = None if standoff is None else _f64(np.broadcast_to(_f64(standoff).reshape(-1, 16), (B, 16)))
-        base = _f64(np.broadcast_to(_f64(base_pos).reshape(-1, 3), (B, 3)))
+        base = _bases(base_pos, B)
         fg, fo, fv = np.empty(B), np.empty(B), np.empty(B)
         am = np.empty(B, dtype=np.int32)
         self._check(self.lib.gto_eval_objective(self._h, B, n_max, _p(scene_id, _pi), _p(goals, _pd),
@@ -594,8 +577,8 @@ class SolverHandle:
         d, T, n = self.desc, self.T, self.desc.n_opt
         Q = _f64(Q).reshape(-1, d.ndof, T)
         B = Q.shape[0]
-        scene_id = _i32(np.broadcast_to(np.asarray(scene_id), (B,)))
-        base = _f64(np.broadcast_to(_f64(base_pos).reshape(-1, 3), (B, 3)))
+        scene_id = _per_instance(scene_id, B)
+        base = _bases(base_pos, B)
         JtJ, Jtr, ss = np.empty((B, T, n, n)), np.empty((B, T, n)), np.empty((B, T))
         self._check(self.lib.gto_eval_obstacle_normal_eq(self._h, B, _p(scene_id, _pi), _p(base, _pd),
                                                          _p(Q, _pd), _p(JtJ, _pd), _p(Jtr, _pd), _p(ss, _pd)),
@@ -609,8 +592,8 @@ class SolverHandle:
         q0 = _f64(q0).reshape(-1, d.ndof)
         B = q0.shape[0]
         goals = _f64(goals).reshape(B, 16)
-        sid = None if scene_id is None else _i32(np.broadcast_to(np.asarray(scene_id), (B,)))
-        base = None if base_pos is None else _f64(np.broadcast_to(_f64(base_pos).reshape(-1, 3), (B, 3)))
+        sid = None if scene_id is None else _per_instance(scene_id, B)
+        base = None if base_pos is None else _bases(base_pos, B)
         q, cost = np.empty((B, d.ndof)), np.empty(B)
         iters, status = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
         if B:
@@ -631,8 +614,8 @@ class SolverHandle:
         goals = _f64(goals).reshape(B, -1)
         if int(kind) in self.IK_GOAL_WIDTH and goals.shape[1] != self.IK_GOAL_WIDTH[int(kind)]:
             raise ValueError(f"goal kind {kind} takes {self.IK_GOAL_WIDTH[int(kind)]} numbers per goal, not {goals.shape[1]}")
-        sid = None if scene_id is None else _i32(np.broadcast_to(np.asarray(scene_id), (B,)))
-        base = None if base_pos is None else _f64(np.broadcast_to(_f64(base_pos).reshape(-1, 3), (B, 3)))
+        sid = None if scene_id is None else _per_instance(scene_id, B)
+        base = None if base_pos is None else _bases(base_pos, B)
         q, cost = np.empty((B, d.ndof)), np.empty(B)
         iters, status = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
         self._check(self.lib.gto_solve_ik_pose_batch(self._h, int(kind), B, _p(sid, _pi), _p(q0, _pd), _p(goals, _pd),
@@ -646,30 +629,27 @@ class SolverHandle:
                                    iters_out=None, status_out=None, stream=None):
         """gto_solve_ik_pose_batch_device: all arrays are device pointers (ints, e.g. torch.Tensor.data_ptr()) or None;
         scene_id None = no collision term (base_pos may then be None)."""
-        vp = lambda a: None if a is None else C.c_void_p(int(a))
-        self._check(self.lib.gto_solve_ik_pose_batch_device(self._h, int(kind), int(B), vp(scene_id), vp(q0), vp(goals),
-                                                            vp(base_pos), int(max_iter), vp(q_out), vp(cost_out), vp(iters_out),
-                                                            vp(status_out), vp(stream)), "gto_solve_ik_pose_batch_device")
+        self._check(self.lib.gto_solve_ik_pose_batch_device(self._h, int(kind), int(B), _vp(scene_id), _vp(q0), _vp(goals),
+                                                            _vp(base_pos), int(max_iter), _vp(q_out), _vp(cost_out), _vp(iters_out),
+                                                            _vp(status_out), _vp(stream)), "gto_solve_ik_pose_batch_device")
 
     def ik_report_device(self, B, scene_id, q, goals, base_pos, pos_tol, rot_tol_deg, cost_tol, err_pos_out=None,
                          err_rot_out=None, cost_out=None, accept_out=None, stream=None):
         """gto_ik_report_device: err_pos, err_rot (degrees), collision cost and the acceptance flag (uint8) of B IK solutions;
         device pointers or None."""
-        vp = lambda a: None if a is None else C.c_void_p(int(a))
-        self._check(self.lib.gto_ik_report_device(self._h, int(B), vp(scene_id), vp(q), vp(goals), vp(base_pos), float(pos_tol),
-                                                  float(rot_tol_deg), float(cost_tol), vp(err_pos_out), vp(err_rot_out),
-                                                  vp(cost_out), vp(accept_out), vp(stream)), "gto_ik_report_device")
+        self._check(self.lib.gto_ik_report_device(self._h, int(B), _vp(scene_id), _vp(q), _vp(goals), _vp(base_pos), float(pos_tol),
+                                                  float(rot_tol_deg), float(cost_tol), _vp(err_pos_out), _vp(err_rot_out),
+                                                  _vp(cost_out), _vp(accept_out), _vp(stream)), "gto_ik_report_device")
 
     def seed_goalsets_device(self, B, n_max, scene_id, qc, goals, n_goals, q_solutions, accept, base_pos, interpolate,
                              solutions_f32, goals_out=None, n_goals_out=None, n_accepted_out=None, Q0_out=None,
                              seed_index_out=None, seed_cost_out=None, seed_dist_out=None, stream=None):
         """gto_seed_goalsets_device: accepted goal sets, seed scores, the chosen seed; device pointers or None."""
-        vp = lambda a: None if a is None else C.c_void_p(int(a))
-        self._check(self.lib.gto_seed_goalsets_device(self._h, int(B), int(n_max), vp(scene_id), vp(qc), vp(goals), vp(n_goals),
-                                                      vp(q_solutions), vp(accept), vp(base_pos), int(bool(interpolate)),
-                                                      int(bool(solutions_f32)), vp(goals_out), vp(n_goals_out),
-                                                      vp(n_accepted_out), vp(Q0_out), vp(seed_index_out), vp(seed_cost_out),
-                                                      vp(seed_dist_out), vp(stream)), "gto_seed_goalsets_device")
+        self._check(self.lib.gto_seed_goalsets_device(self._h, int(B), int(n_max), _vp(scene_id), _vp(qc), _vp(goals), _vp(n_goals),
+                                                      _vp(q_solutions), _vp(accept), _vp(base_pos), int(bool(interpolate)),
+                                                      int(bool(solutions_f32)), _vp(goals_out), _vp(n_goals_out),
+                                                      _vp(n_accepted_out), _vp(Q0_out), _vp(seed_index_out), _vp(seed_cost_out),
+                                                      _vp(seed_dist_out), _vp(stream)), "gto_seed_goalsets_device")
 
     # -------------------------------------------------------------- several seeds per goal set (GraspChain.plan_objects(n_seeds=k))
     def seed_goalsets_multi_device(self, B, n_max, n_seeds, scene_id, qc, goals, n_goals, q_solutions, accept, base_pos, interpolate,
@@ -677,31 +657,28 @@ class SolverHandle:
                                    Q0_out=None, seed_index_out=None, seed_cost_out=None, seed_dist_out=None, stream=None):
         """gto_seed_goalsets_multi_device: the n_seeds best seeds of every goal set, one slot of goals_out / n_goals_out /
         Q0_out / seed_index_out (leading shape (B, n_seeds)) each; device pointers or None."""
-        vp = lambda a: None if a is None else C.c_void_p(int(a))
-        self._check(self.lib.gto_seed_goalsets_multi_device(self._h, int(B), int(n_max), int(n_seeds), vp(scene_id), vp(qc), vp(goals),
-                                                            vp(n_goals), vp(q_solutions), vp(accept), vp(base_pos),
-                                                            int(bool(interpolate)), int(bool(solutions_f32)), vp(goals_out),
-                                                            vp(n_goals_out), vp(n_accepted_out), vp(accepted_rows_out), vp(Q0_out),
-                                                            vp(seed_index_out), vp(seed_cost_out), vp(seed_dist_out), vp(stream)),
+        self._check(self.lib.gto_seed_goalsets_multi_device(self._h, int(B), int(n_max), int(n_seeds), _vp(scene_id), _vp(qc), _vp(goals),
+                                                            _vp(n_goals), _vp(q_solutions), _vp(accept), _vp(base_pos),
+                                                            int(bool(interpolate)), int(bool(solutions_f32)), _vp(goals_out),
+                                                            _vp(n_goals_out), _vp(n_accepted_out), _vp(accepted_rows_out), _vp(Q0_out),
+                                                            _vp(seed_index_out), _vp(seed_cost_out), _vp(seed_dist_out), _vp(stream)),
                     "gto_seed_goalsets_multi_device")
 
     def plan_report_device(self, B, n_max, goals, n_goals, standoff, Q, goal_index_out=None, goal_cost_out=None, err_pos_out=None,
                            err_rot_out=None, stream=None):
         """gto_plan_report_device: the goal every plan reached (the objective's arg-min goal), that goal's term and err_pos /
         err_rot (degrees) of the last waypoint against it; device pointers or None."""
-        vp = lambda a: None if a is None else C.c_void_p(int(a))
-        self._check(self.lib.gto_plan_report_device(self._h, int(B), int(n_max), vp(goals), vp(n_goals), vp(standoff), vp(Q),
-                                                    vp(goal_index_out), vp(goal_cost_out), vp(err_pos_out), vp(err_rot_out),
-                                                    vp(stream)), "gto_plan_report_device")
+        self._check(self.lib.gto_plan_report_device(self._h, int(B), int(n_max), _vp(goals), _vp(n_goals), _vp(standoff), _vp(Q),
+                                                    _vp(goal_index_out), _vp(goal_cost_out), _vp(err_pos_out), _vp(err_rot_out),
+                                                    _vp(stream)), "gto_plan_report_device")
 
     def select_plans_device(self, B, n_seeds, status, cost, err_pos, err_rot, counts, pos_tol, rot_tol_deg, max_points, Q=None,
                             dQ=None, best_slot_out=None, class_out=None, Q_out=None, dQ_out=None, stream=None):
         """gto_select_plans_device: the class of every slot's plan and the best slot of every object, with copies of its
         rows; device pointers or None."""
-        vp = lambda a: None if a is None else C.c_void_p(int(a))
-        self._check(self.lib.gto_select_plans_device(self._h, int(B), int(n_seeds), vp(status), vp(cost), vp(err_pos), vp(err_rot),
-                                                     vp(counts), float(pos_tol), float(rot_tol_deg), int(max_points), vp(Q), vp(dQ),
-                                                     vp(best_slot_out), vp(class_out), vp(Q_out), vp(dQ_out), vp(stream)),
+        self._check(self.lib.gto_select_plans_device(self._h, int(B), int(n_seeds), _vp(status), _vp(cost), _vp(err_pos), _vp(err_rot),
+                                                     _vp(counts), float(pos_tol), float(rot_tol_deg), int(max_points), _vp(Q), _vp(dQ),
+                                                     _vp(best_slot_out), _vp(class_out), _vp(Q_out), _vp(dQ_out), _vp(stream)),
                     "gto_select_plans_device")
 
     def solve_base_batch(self, qc, goals, n_goals=None, effort_weight=0.01, max_iter=100):
@@ -712,7 +689,7 @@ class SolverHandle:
         B = qc.shape[0]
         goals = _f64(goals).reshape(B, -1, 16)
         n_max = goals.shape[1]
-        ng = _i32(np.broadcast_to(np.asarray(n_max if n_goals is None else n_goals), (B,)))
+        ng = _per_instance(n_max if n_goals is None else n_goals, B)
         y, q, cost = np.empty((B, 3)), np.empty((B, n_max, d.ndof)), np.empty(B)
         iters, status = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
         if B:
@@ -727,22 +704,20 @@ class SolverHandle:
                                 iters_out=None, status_out=None, stream=None):
         """gto_solve_base_batch_device: n_goals is a HOST int32 array (B,); every other array is a device pointer (an int,
         e.g. torch.Tensor.data_ptr()) or None."""
-        ng = _i32(np.broadcast_to(np.asarray(n_goals), (int(B),)))
-        vp = lambda a: None if a is None else C.c_void_p(int(a))
-        self._check(self.lib.gto_solve_base_batch_device(self._h, int(B), int(n_max), _p(ng, _pi), vp(qc), vp(goals),
-                                                         float(effort_weight), int(max_iter), vp(y_out), vp(q_out), vp(cost_out),
-                                                         vp(iters_out), vp(status_out), vp(stream)), "gto_solve_base_batch_device")
+        ng = _per_instance(n_goals, int(B))
+        self._check(self.lib.gto_solve_base_batch_device(self._h, int(B), int(n_max), _p(ng, _pi), _vp(qc), _vp(goals),
+                                                         float(effort_weight), int(max_iter), _vp(y_out), _vp(q_out), _vp(cost_out),
+                                                         _vp(iters_out), _vp(status_out), _vp(stream)), "gto_solve_base_batch_device")
 
     def base_report_device(self, occ, B, n_max, n_goals, qc, goals, y, q, err_pos_out=None, err_rot_out=None,
                            collision_out=None, first_free_out=None, stream=None):
         """gto_base_report_device: err_pos / err_rot (degrees) of every goal, the footprint count of every set on the
         occupancy grid ``occ`` (occupancy.OccupancyGrid or None) and the first free set; n_goals is a HOST array, the others
         device pointers or None."""
-        ng = _i32(np.broadcast_to(np.asarray(n_goals), (int(B),)))
-        vp = lambda a: None if a is None else C.c_void_p(int(a))
+        ng = _per_instance(n_goals, int(B))
         self._check(self.lib.gto_base_report_device(self._h, None if occ is None else occ._ptr(), int(B), int(n_max), _p(ng, _pi),
-                                                    vp(qc), vp(goals), vp(y), vp(q), vp(err_pos_out), vp(err_rot_out),
-                                                    vp(collision_out), vp(first_free_out), vp(stream)), "gto_base_report_device")
+                                                    _vp(qc), _vp(goals), _vp(y), _vp(q), _vp(err_pos_out), _vp(err_rot_out),
+                                                    _vp(collision_out), _vp(first_free_out), _vp(stream)), "gto_base_report_device")
 
     def eval_base_objective(self, y, q, goals, n_goals=None, effort_weight=0.01):
         """Base-placement objective (gto/base_planner.py:57-87) at y (B,3), q (B,n_max,ndof), goals (B,n_max,4,4)."""
@@ -752,7 +727,7 @@ class SolverHandle:
         goals = _f64(goals).reshape(B, -1, 16)
         n_max = goals.shape[1]
         q = _f64(q).reshape(B, n_max, d.ndof)
-        ng = _i32(np.broadcast_to(np.asarray(n_max if n_goals is None else n_goals), (B,)))
+        ng = _per_instance(n_max if n_goals is None else n_goals, B)
         cost = np.empty(B)
         if B:
             self._check(self.lib.gto_eval_base_objective(self._h, B, n_max, _p(ng, _pi), _p(y, _pd), _p(q, _pd), _p(goals, _pd),
@@ -799,9 +774,8 @@ class SolverHandle:
         """gto_check_plans_device: plans (B, ndof, T) float64 and count_out (B, T) int32 are device pointers (ints, e.g.
         torch.Tensor.data_ptr()); enqueued on ``stream`` (None: the handle's) without a host synchronisation."""
         base, per_plan = self._check_base(base_pos, int(B))
-        vp = lambda a: None if a is None else C.c_void_p(int(a))
-        self._check(self.lib.gto_check_plans_device(self._h, obs._ptr(), int(B), vp(plans), _p(base, _pd), per_plan, vp(count_out),
-                                                    vp(stream)), "gto_check_plans_device")
+        self._check(self.lib.gto_check_plans_device(self._h, obs._ptr(), int(B), _vp(plans), _p(base, _pd), per_plan, _vp(count_out),
+                                                    _vp(stream)), "gto_check_plans_device")
 
     # -------------------------------------------------------------- retiming
     def _retime_limits(self, vmax, amax):
@@ -831,8 +805,7 @@ class SolverHandle:
         """gto_retime_batch_device: plans and outputs are device pointers (ints, e.g. torch.Tensor.data_ptr()) or None;
         vmax / amax are host values."""
         vm, am = self._retime_limits(vmax, amax)
-        vp = lambda a: None if a is None else C.c_void_p(int(a))
-        self._check(self.lib.gto_retime_batch_device(self._h, int(B), vp(plans), _p(vm, _pd), _p(am, _pd), int(subdiv),
-                                                     int(n_samples), vp(duration_out), vp(t_grid_out), vp(sd_grid_out),
-                                                     vp(q_out), vp(qd_out), vp(qdd_out), vp(status_out), vp(stream)),
+        self._check(self.lib.gto_retime_batch_device(self._h, int(B), _vp(plans), _p(vm, _pd), _p(am, _pd), int(subdiv),
+                                                     int(n_samples), _vp(duration_out), _vp(t_grid_out), _vp(sd_grid_out),
+                                                     _vp(q_out), _vp(qd_out), _vp(qdd_out), _vp(status_out), _vp(stream)),
                     "gto_retime_batch_device")

@@ -27,6 +27,7 @@
 #include "gto_observe.h"
 #include "gto_seed.h"
 #include "gto_occupancy.h"
+#include "gto_owned.h"
 
 #define GTO_VERSION GTO_ABI_VERSION  // include/gto_solver.h
 #ifndef GTO_OBS_DEEP_PD
@@ -147,10 +148,10 @@ static void read_tunables(Tunables& t) {
   if (t.dbg_cut) fprintf(stderr, "[gto] WARNING: GTO_DEBUG_CUT=%d cuts the obstacle kernel short: timing experiments only, RESULTS ARE GARBAGE\n", t.dbg_cut);
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-};
+// Every device and pinned allocation behind the ABI lives in one of these and goes with the object that holds it: a
+// handle, a scene's entry, an observation, an occupancy grid, a call's locals (gto_owned.h; DepthPool is the exception)
+using DevBuf = Owned<hipFree>;
+using PinBuf = Owned<hipHostFree>;
 
 struct gto_handle {
   int device = 0;
@@ -159,40 +160,43 @@ struct gto_handle {
   std::string err;
   gto_solver_opts opts;
   RobotDev rb;  // host copy
+  // the robot's tables on the device, uploaded once by gto_create: the buffers, and what the launches take
+  DevBuf rb_buf, px_buf, py_buf, pz_buf, plink_buf, perm_buf, chunks_buf;
   RobotDev* d_rb = nullptr;
   double *d_px = nullptr, *d_py = nullptr, *d_pz = nullptr;
   int32_t *d_plink = nullptr, *d_perm = nullptr;
   Chunk* d_chunks = nullptr;
   std::vector<PbChunk> pbchunks;  // bounding spheres of the chunks of moving links, with their frames (prebroad_tail)
   int pb_C = 0;
-  float* d_pbimg = nullptr;  // their table for each valid scene (SceneDev::pb_img; sync_pb_images)
-  size_t d_pbimg_cap = 0;    // floats
+  DevBuf d_pbimg;  // their table (floats) for each valid scene (SceneDev::pb_img; sync_pb_images)
   std::vector<SceneDev> scenes;  // host mirror, index = scene id
-  SceneDev* d_scenes = nullptr;
-  size_t d_scenes_cap = 0;
+  // per scene id, the one to six allocations the scene owns; none for a borrowed scene (valid == 2) and an empty slot
+  std::vector<std::vector<DevBuf>> scene_bufs;
+  DevBuf scenes_buf;  // the table on the device
+  SceneDev* d_scenes = nullptr;  // ... as the launches take it (sync_scene_table)
   // solve workspace (grown on demand)
   DevBuf state, Qcur, Qtry, vis, screw, blocks, goalblk, ssfixed, ndone, qf, livebuf, qfs, wrecbuf, itembuf;
   DevBuf counters;  // work counters of a profiled solve
   unsigned long long last_counters[4] = {0, 0, 0, 0};
-  int32_t* h_ndone = nullptr;  // pinned
+  PinBuf h_ndone;
   // pinned, device-visible, written by the first workgroup of every step launch: word 0 = call tag << 32 | instances
   // finished, word 1 = call tag << 32 | round of that launch.  The host sizes its launches by the first and stays at most
   // `ahead` rounds in front of the second: no event, no copy, nothing in the stream between the kernels
-  unsigned long long* h_progress = nullptr;
+  PinBuf h_progress;
   unsigned long long* d_progress = nullptr;  // its device address
   unsigned progress_tag = 0;
   Tunables tu;  // the GTO_* knobs, read at gto_create
   int spec_kmax = 1;  // candidates per step the eight-wave step kernel's LDS has room for at this T
-  long long* dbg = nullptr;
+  DevBuf dbg;  // GTO_DEBUG_TIMING: the kernels' phase stamps (long long[256])
   // buffers of the scene that the last gto_set_scene replaced: the next replacement of the same size takes them instead of
   // going through hipMalloc / hipFree (fourteen calls of 0.2-0.3 ms each: most of a small scene's upload time)
-  std::vector<std::pair<void*, size_t>> spare;
+  std::vector<DevBuf> spare;
   // staging for the host-pointer entry points (Staging)
   DevBuf in[GTO_STAGE_SLOTS], out[GTO_STAGE_SLOTS];
   // pinned twins of the staging buffers: host arrays are copied through them, so that the transfers are real DMA at a
   // steady rate (a hipMemcpyAsync from pageable memory stages inside the runtime: 1-6 ms of jitter per call with four
   // lanes copying at once) and never depend on what kind of memory the caller's arrays live in
-  DevBuf pin_in[GTO_STAGE_SLOTS], pin_out[GTO_STAGE_SLOTS];
+  PinBuf pin_in[GTO_STAGE_SLOTS], pin_out[GTO_STAGE_SLOTS];
   // profiling of the dominant kernel
   bool profiling = false;
   std::vector<hipEvent_t> ev;
@@ -225,9 +229,20 @@ struct gto_handle {
   // base placement with resident arrays (gto_solve_base_batch_device, gto_base_report_device): the device copy of the
   // caller's n_goals, and the per-set counts when the caller asks for the choice alone
   DevBuf bs_ng, bs_coll;
-  DevBuf bs_pin[GTO_BASE_PIN_SLOTS];           // pinned copies of n_goals, one per call in flight (base_counts_to_device)
+  PinBuf bs_pin[GTO_BASE_PIN_SLOTS];           // pinned copies of n_goals, one per call in flight (base_counts_to_device)
   hipEvent_t bs_pin_ev[GTO_BASE_PIN_SLOTS] = {};  // recorded behind the copy that reads slot k
   int bs_pin_next = 0;
+
+  // the streams and events the handle created; the buffers above free themselves after this (gto_destroy has set the device)
+  ~gto_handle() {
+    for (auto e : bs_pin_ev) if (e) (void)hipEventDestroy(e);
+    for (auto e : ev) (void)hipEventDestroy(e);
+    if (stream && own_stream) (void)hipStreamDestroy(stream);
+    for (int l = 0; l < GTO_MAX_LANES; ++l) {
+      if (lane_stream[l]) (void)hipStreamDestroy(lane_stream[l]);
+      if (lane_event[l]) (void)hipEventDestroy(lane_event[l]);
+    }
+  }
 };
 
 #define HIPCHK(h, call)                                                                              \
@@ -245,15 +260,31 @@ static int fail(gto_handle* h, int code, const std::string& msg) {
   return code;
 }
 
-static int ensure(gto_handle* h, DevBuf& b, size_t bytes) {
-  if (bytes <= b.cap) return GTO_OK;
-  if (b.p) HIPCHK(h, hipFree(b.p));
-  b.p = nullptr;
-  b.cap = 0;
-  size_t want = bytes + bytes / 4 + 256;
-  HIPCHK(h, hipMalloc(&b.p, want));
-  b.cap = want;
+// exactly `bytes` bytes: scenes, whose spares are matched by byte count, and the tables that never grow
+static hipError_t dev_alloc(DevBuf& b, size_t bytes) {
+  void* p = nullptr;
+  const hipError_t e = hipMalloc(&p, bytes);
+  if (e == hipSuccess) b = DevBuf(p, bytes);
+  return e;
+}
+static hipError_t pinned_alloc(PinBuf& b, size_t bytes, unsigned flags = hipHostMallocDefault) {
+  void* p = nullptr;
+  const hipError_t e = hipHostMalloc(&p, bytes, flags);
+  if (e == hipSuccess) b = PinBuf(p, bytes);
+  return e;
+}
+
+// a buffer of at least `bytes` bytes, device or pinned: grown with 25 % + 256 B to spare, contents not kept
+template <class Buf, class Alloc>
+static int ensure_with(gto_handle* h, Buf& b, size_t bytes, Alloc alloc) {
+  if (bytes <= b.bytes()) return GTO_OK;
+  HIPCHK(h, b.reset());
+  HIPCHK(h, alloc(b, bytes + bytes / 4 + 256));
   return GTO_OK;
+}
+static int ensure(gto_handle* h, DevBuf& b, size_t bytes) { return ensure_with(h, b, bytes, dev_alloc); }
+static int ensure(gto_handle* h, PinBuf& b, size_t bytes) {
+  return ensure_with(h, b, bytes, [](PinBuf& x, size_t n) { return pinned_alloc(x, n); });
 }
 
 extern "C" {
@@ -765,18 +796,20 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
   h->np = np;
   h->lm_lds = lm_lds;
   h->spec_kmax = spec_kmax;
-  if (tu.debug_timing) { (void)hipMalloc((void**)&h->dbg, 256 * sizeof(long long)); (void)hipMemset(h->dbg, 0, 256 * sizeof(long long)); }
-  auto up = [&](void** dst, const void* src, size_t bytes) -> bool {
-    if (hipMalloc(dst, bytes) != hipSuccess) return false;
-    return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+  if (tu.debug_timing && dev_alloc(h->dbg, 256 * sizeof(long long)) == hipSuccess) (void)hipMemset(h->dbg.get(), 0, h->dbg.bytes());
+  auto up = [&](DevBuf& b, const void* src, size_t bytes) -> bool {
+    return dev_alloc(b, bytes) == hipSuccess && hipMemcpy(b.get(), src, bytes, hipMemcpyHostToDevice) == hipSuccess;
   };
   const size_t P = t->px.size();
   if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { gto_destroy(h); return fail(nullptr, GTO_ERR_HIP, "hipStreamCreate failed"); }
-  const bool ok = up((void**)&h->d_rb, &h->rb, sizeof h->rb) && up((void**)&h->d_px, t->px.data(), P * sizeof(double)) &&
-                  up((void**)&h->d_py, t->py.data(), P * sizeof(double)) && up((void**)&h->d_pz, t->pz.data(), P * sizeof(double)) &&
-                  up((void**)&h->d_plink, t->plink.data(), P * sizeof(int32_t)) && up((void**)&h->d_perm, t->perm.data(), P * sizeof(int32_t)) &&
-                  up((void**)&h->d_chunks, t->chunks.data(), t->chunks.size() * sizeof(Chunk));
+  const bool ok = up(h->rb_buf, &h->rb, sizeof h->rb) && up(h->px_buf, t->px.data(), P * sizeof(double)) &&
+                  up(h->py_buf, t->py.data(), P * sizeof(double)) && up(h->pz_buf, t->pz.data(), P * sizeof(double)) &&
+                  up(h->plink_buf, t->plink.data(), P * sizeof(int32_t)) && up(h->perm_buf, t->perm.data(), P * sizeof(int32_t)) &&
+                  up(h->chunks_buf, t->chunks.data(), t->chunks.size() * sizeof(Chunk));
   if (!ok) { gto_destroy(h); return fail(nullptr, GTO_ERR_ALLOC, "device allocation failed in gto_create"); }
+  h->d_rb = h->rb_buf.as<RobotDev>(), h->d_chunks = h->chunks_buf.as<Chunk>();
+  h->d_px = h->px_buf.as<double>(), h->d_py = h->py_buf.as<double>(), h->d_pz = h->pz_buf.as<double>();
+  h->d_plink = h->plink_buf.as<int32_t>(), h->d_perm = h->perm_buf.as<int32_t>();
   // dynamic LDS of every kernel variant the handle can launch (obstacle_kernel, the step kernels)
   const size_t lds = std::min<size_t>((size_t)lay.total_doubles * sizeof(double), 160 * 1024);
   hipError_t e = hipSuccess;
@@ -792,44 +825,7 @@ void gto_destroy(gto_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (auto& s : h->scenes) {
-    if (s.valid == 1) {
-      if (s.c_obs != s.c_all) (void)hipFree((void*)s.c_obs);
-      (void)hipFree((void*)s.c_all);
-      if (s.r_obs != s.r_all) (void)hipFree((void*)s.r_obs);
-      (void)hipFree((void*)s.r_all);
-      if (s.d_obs != s.d_all) (void)hipFree((void*)s.d_obs);
-      (void)hipFree((void*)s.d_all);
-    }
-  }
-  (void)hipFree(h->d_scenes);
-  (void)hipFree(h->d_rb);
-  (void)hipFree(h->d_px);
-  (void)hipFree(h->d_py);
-  (void)hipFree(h->d_pz);
-  (void)hipFree(h->d_plink);
-  (void)hipFree(h->d_perm);
-  (void)hipFree(h->d_chunks);
-  (void)hipFree(h->d_pbimg);
-  DevBuf* bufs[] = {&h->zws, &h->counters, &h->state, &h->Qcur, &h->Qtry, &h->vis, &h->screw, &h->blocks, &h->goalblk, &h->ssfixed, &h->ndone, &h->qf, &h->livebuf, &h->qfs, &h->wrecbuf, &h->itembuf,
-                   &h->rt_fac, &h->rt_S, &h->rt_flag, &h->rt_P1, &h->rt_P2, &h->rt_cap, &h->rt_X, &h->rt_T, &h->rt_stat, &h->ck_xyz, &h->ck_flags, &h->ck_base, &h->sd_part, &h->bs_ng, &h->bs_coll};
-  if (h->h_ndone) (void)hipHostFree(h->h_ndone);
-  if (h->h_progress) (void)hipHostFree(h->h_progress);
-  for (DevBuf* b : bufs) (void)hipFree(b->p);
-  for (auto& sp_ : h->spare) (void)hipFree(sp_.first);
-  for (auto& b : h->in) (void)hipFree(b.p);
-  for (auto& b : h->out) (void)hipFree(b.p);
-  for (auto& b : h->pin_in) if (b.p) (void)hipHostFree(b.p);
-  for (auto& b : h->pin_out) if (b.p) (void)hipHostFree(b.p);
-  for (auto& b : h->bs_pin) if (b.p) (void)hipHostFree(b.p);
-  for (auto e : h->bs_pin_ev) if (e) (void)hipEventDestroy(e);
-  for (auto e : h->ev) (void)hipEventDestroy(e);
-  if (h->stream && h->own_stream) (void)hipStreamDestroy(h->stream);
-  for (int l = 0; l < GTO_MAX_LANES; ++l) {
-    if (h->lane_stream[l]) (void)hipStreamDestroy(h->lane_stream[l]);
-    if (h->lane_event[l]) (void)hipEventDestroy(h->lane_event[l]);
-  }
-  delete h;
+  delete h;  // ~gto_handle: its streams and events, then every buffer by its owner
 }
 
 int gto_set_opts(gto_handle* h, const gto_solver_opts* o) {
@@ -849,12 +845,9 @@ static int sync_pb_images(gto_handle* h) {
   const size_t rows = (size_t)pb_img_rows(C);
   size_t nv = 0;
   for (const SceneDev& s : h->scenes) nv += s.valid ? 1 : 0;
-  if (nv * rows * 4 > h->d_pbimg_cap) {
-    if (h->d_pbimg) HIPCHK(h, hipFree(h->d_pbimg));
-    h->d_pbimg = nullptr;
-    const size_t cap = std::max<size_t>(16, nv * 2) * rows * 4;
-    HIPCHK(h, hipMalloc((void**)&h->d_pbimg, cap * sizeof(float)));
-    h->d_pbimg_cap = cap;
+  if (nv * rows * 4 * sizeof(float) > h->d_pbimg.bytes()) {
+    HIPCHK(h, h->d_pbimg.reset());
+    HIPCHK(h, dev_alloc(h->d_pbimg, std::max<size_t>(16, nv * 2) * rows * 4 * sizeof(float)));
   }
   std::vector<float> img(nv * rows * 4, 0.f);
   const double eps = h->rb.pb_eps;
@@ -869,39 +862,42 @@ static int sync_pb_images(gto_handle* h) {
       v[4 * c + 3] = (float)((int)std::ceil(std::fma(cc.r + eps, s.rinv, 1e-6)) + GTO_BROAD_MARGIN);
       std::memcpy(v + 4 * C + c, &cc.frame, sizeof(int32_t));
     }
-    s.pb_img = h->d_pbimg + k * rows * 4;
+    s.pb_img = h->d_pbimg.as<float>() + k * rows * 4;
     ++k;
   }
-  if (!img.empty()) HIPCHK(h, hipMemcpy(h->d_pbimg, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (!img.empty()) HIPCHK(h, hipMemcpy(h->d_pbimg.get(), img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
   return GTO_OK;
 }
 
 static int sync_scene_table(gto_handle* h) {
   size_t n = h->scenes.size();
   if (int rc = sync_pb_images(h)) return rc;
-  if (n > h->d_scenes_cap) {
-    if (h->d_scenes) HIPCHK(h, hipFree(h->d_scenes));
+  if (n * sizeof(SceneDev) > h->scenes_buf.bytes()) {
     h->d_scenes = nullptr;
-    size_t cap = std::max<size_t>(16, n * 2);
-    HIPCHK(h, hipMalloc((void**)&h->d_scenes, cap * sizeof(SceneDev)));
-    h->d_scenes_cap = cap;
+    HIPCHK(h, h->scenes_buf.reset());
+    HIPCHK(h, dev_alloc(h->scenes_buf, std::max<size_t>(16, n * 2) * sizeof(SceneDev)));
+    h->d_scenes = h->scenes_buf.as<SceneDev>();
   }
   HIPCHK(h, hipMemcpy(h->d_scenes, h->scenes.data(), n * sizeof(SceneDev), hipMemcpyHostToDevice));
   return GTO_OK;
 }
 
 // valid: 0 empty, 1 owned by this handle, 2 borrowed from another handle (gto_share_scene)
-static int free_scene(gto_handle* h, SceneDev& s) {
-  if (s.valid == 1) {
-    if (s.c_obs != s.c_all) HIPCHK(h, hipFree((void*)s.c_obs));
-    HIPCHK(h, hipFree((void*)s.c_all));
-    if (s.r_obs != s.r_all) HIPCHK(h, hipFree((void*)s.r_obs));
-    HIPCHK(h, hipFree((void*)s.r_all));
-    if (s.d_obs != s.d_all) HIPCHK(h, hipFree((void*)s.d_obs));
-    HIPCHK(h, hipFree((void*)s.d_all));
-  }
-  s.valid = 0;
+static int free_scene(gto_handle* h, int32_t id) {
+  h->scenes[id].valid = 0;
+  std::vector<DevBuf> bufs;
+  bufs.swap(h->scene_bufs[id]);  // the entry owns nothing from here on; what a failed free leaves goes with `bufs`
+  for (DevBuf& b : bufs) HIPCHK(h, b.reset());
   return GTO_OK;
+}
+
+// room for scene `id` in the table and in the list of what the scenes own
+static void grow_scene_table(gto_handle* h, int32_t id) {
+  if ((size_t)id < h->scenes.size()) return;
+  SceneDev z;
+  memset(&z, 0, sizeof z);
+  h->scenes.resize(id + 1, z);
+  h->scene_bufs.resize(id + 1);
 }
 
 // a scene id that names a set scene (owned or borrowed)
@@ -931,12 +927,8 @@ int gto_share_scene_halves(gto_handle* dst, int32_t dst_id, gto_handle* src, int
   if (dst->device != src->device) return fail(dst, GTO_ERR_INVALID_ARG, "gto_share_scene: handles live on different devices");
   HIPCHK(dst, hipSetDevice(dst->device));
   HIPCHK(dst, hipStreamSynchronize(dst->stream));
-  if ((size_t)dst_id >= dst->scenes.size()) {
-    SceneDev z;
-    memset(&z, 0, sizeof z);
-    dst->scenes.resize(dst_id + 1, z);
-  }
-  int rcf = free_scene(dst, dst->scenes[dst_id]);
+  grow_scene_table(dst, dst_id);
+  int rcf = free_scene(dst, dst_id);
   if (rcf) return rcf;
   const SceneDev& ss = src->scenes[src_id];
   SceneDev& ds = dst->scenes[dst_id];
@@ -962,35 +954,28 @@ static int set_scene_impl(gto_handle* h, int32_t id, const float* c_all, const f
   HIPCHK(h, hipStreamSynchronize(h->stream));
   // Build the new scene completely first (fields, voxel records, distance fields), then swap it in and free the old one:
   // a failure half-way leaves the table and the previous scene of this id untouched and frees what was allocated.
-  std::vector<void*> owned;
-  auto fail_free = [&](hipError_t e, const char* what) {
-    for (void* p : owned) (void)hipFree(p);
-    h->err = std::string(what) + ": " + hipGetErrorString(e);
-    return GTO_ERR_HIP;
-  };
-#define SCN(call)                                      \
-  do {                                                 \
-    hipError_t e_ = (call);                            \
-    if (e_ != hipSuccess) return fail_free(e_, #call); \
-  } while (0)
-  auto dalloc = [&](void** p, size_t bytes) {
-    for (size_t k = 0; k < h->spare.size(); ++k)
-      if (h->spare[k].second == bytes) {  // a buffer of the scene replaced last time
-        *p = h->spare[k].first;
-        h->spare.erase(h->spare.begin() + k);
-        owned.push_back(*p);
-        return hipSuccess;
-      }
-    hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) owned.push_back(*p);
+  std::vector<DevBuf> built, aside;  // the new scene's buffers; the scratch half of the distance fields
+  auto dalloc_in = [&](std::vector<DevBuf>& into, void** p, size_t bytes) {
+    into.emplace_back();
+    DevBuf& b = into.back();
+    hipError_t e = hipSuccess;
+    auto fit = std::find_if(h->spare.begin(), h->spare.end(), [&](const DevBuf& sp_) { return sp_.bytes() == bytes; });
+    if (fit != h->spare.end()) {  // a buffer of the scene replaced last time
+      b = std::move(*fit);
+      h->spare.erase(fit);
+    } else {
+      e = dev_alloc(b, bytes);
+    }
+    *p = b.get();
     return e;
   };
+  auto dalloc = [&](void** p, size_t bytes) { return dalloc_in(built, p, bytes); };
   float *da = nullptr, *dob = nullptr;
-  SCN(dalloc((void**)&da, nvox * sizeof(float)));
-  SCN(hipMemcpy(da, c_all, nvox * sizeof(float), kind));
+  HIPCHK(h, dalloc((void**)&da, nvox * sizeof(float)));
+  HIPCHK(h, hipMemcpy(da, c_all, nvox * sizeof(float), kind));
   if (c_obs && c_obs != c_all) {
-    SCN(dalloc((void**)&dob, nvox * sizeof(float)));
-    SCN(hipMemcpy(dob, c_obs, nvox * sizeof(float), kind));
+    HIPCHK(h, dalloc((void**)&dob, nvox * sizeof(float)));
+    HIPCHK(h, hipMemcpy(dob, c_obs, nvox * sizeof(float), kind));
   } else {
     dob = da;
   }
@@ -999,20 +984,20 @@ static int set_scene_impl(gto_handle* h, int32_t id, const float* c_all, const f
   VoxelRec *ra = nullptr, *rob = nullptr;
   uint8_t *dista = nullptr, *distb = nullptr, *scratch = nullptr;
   if (!values_only) {
-  SCN(dalloc((void**)&ra, nvox * sizeof(VoxelRec)));
+  HIPCHK(h, dalloc((void**)&ra, nvox * sizeof(VoxelRec)));
   const unsigned nblk = (unsigned)((nvox + 255) / 256);
   hipLaunchKernelGGL(k_build_records, dim3(nblk), dim3(256), 0, h->stream, da, ra, shape[0], shape[1], shape[2]);
   if (dob != da) {
-    SCN(dalloc((void**)&rob, nvox * sizeof(VoxelRec)));
+    HIPCHK(h, dalloc((void**)&rob, nvox * sizeof(VoxelRec)));
     hipLaunchKernelGGL(k_build_records, dim3(nblk), dim3(256), 0, h->stream, dob, rob, shape[0], shape[1], shape[2]);
   } else {
     rob = ra;
   }
   // broad-phase distance fields: ping-pong relaxation, the scratch half is freed again
-  SCN(dalloc((void**)&scratch, nvox));
+  HIPCHK(h, dalloc_in(aside, (void**)&scratch, nvox));
   for (int which = 0; which < (rob != ra ? 2 : 1); ++which) {
     uint8_t* d0 = nullptr;
-    SCN(dalloc((void**)&d0, nvox));
+    HIPCHK(h, dalloc((void**)&d0, nvox));
     if (h->tu.dist_relax) {  // GTO_DIST_RELAX=1: the reference construction, GTO_DIST_CAP sweeps of 3x3x3 min-plus-one (A/B and tests)
       uint8_t* d1 = scratch;
       hipLaunchKernelGGL(k_dist_init, dim3(nblk), dim3(256), 0, h->stream, which ? rob : ra, d0, (long)nvox);
@@ -1031,34 +1016,15 @@ static int set_scene_impl(gto_handle* h, int32_t id, const float* c_all, const f
   }
   if (rob == ra) distb = dista;
   }
-  SCN(hipStreamSynchronize(h->stream));
-  SCN(hipGetLastError());
-#undef SCN
-  if ((size_t)id >= h->scenes.size()) {
-    SceneDev z;
-    memset(&z, 0, sizeof z);
-    h->scenes.resize(id + 1, z);
-  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipGetLastError());
+  grow_scene_table(h, id);
   SceneDev& s = h->scenes[id];
-  // what is left of the previous spares did not fit this scene: free it; the replaced scene's buffers become the spares
-  for (auto& sp_ : h->spare) (void)hipFree(sp_.first);
-  h->spare.clear();
-  if (scratch) h->spare.emplace_back((void*)scratch, nvox);
-  if (s.valid == 1) {
-    const size_t ov = (size_t)s.nx * s.ny * s.nz;
-    auto keep = [&](const void* p_, size_t bytes) {
-      if (p_) h->spare.emplace_back(const_cast<void*>(p_), bytes);
-    };
-    if (s.c_obs != s.c_all) keep(s.c_obs, ov * sizeof(float));
-    keep(s.c_all, ov * sizeof(float));
-    if (s.r_obs != s.r_all) keep(s.r_obs, ov * sizeof(VoxelRec));
-    keep(s.r_all, ov * sizeof(VoxelRec));
-    if (s.d_obs != s.d_all) keep(s.d_obs, ov);
-    keep(s.d_all, ov);
-    s.valid = 0;
-  }
-  int rcf = free_scene(h, s);
-  if (rcf) return rcf;
+  // what is left of the previous spares did not fit this scene: free it; the scratch half and the replaced scene's buffers
+  // become the spares
+  h->spare = std::move(aside);
+  for (DevBuf& b : h->scene_bufs[id]) h->spare.push_back(std::move(b));
+  h->scene_bufs[id] = std::move(built);
   s.c_all = da;
   s.c_obs = dob;
   s.r_all = ra;
@@ -1093,10 +1059,9 @@ int gto_drop_scene(gto_handle* h, int32_t id) {
   if (!scene_valid(h, id)) return fail(h, GTO_ERR_NO_SCENE, "unknown scene");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  SceneDev& s = h->scenes[id];
-  int rcf = free_scene(h, s);
+  int rcf = free_scene(h, id);
   if (rcf) return rcf;
-  memset(&s, 0, sizeof s);
+  memset(&h->scenes[id], 0, sizeof(SceneDev));
   return sync_scene_table(h);
 }
 
@@ -1219,11 +1184,11 @@ static int ensure_workspace(gto_handle* h, int B) {
   if ((rc = ensure(h, h->ndone, 64 * GTO_MAX_LANES))) return rc;  // a finished-counter per lane, a cache line apart
   if ((rc = ensure(h, h->qf, (size_t)B * T * rb.n_frames * sizeof(double)))) return rc;
   if ((rc = ensure(h, h->wrecbuf, (size_t)(kcap + 1) * B * T * 8 * sizeof(double)))) return rc;
-  if (!h->h_ndone) HIPCHK(h, hipHostMalloc((void**)&h->h_ndone, 64));
+  if (!h->h_ndone) HIPCHK(h, pinned_alloc(h->h_ndone, 64));
   if (!h->h_progress) {
-    HIPCHK(h, hipHostMalloc((void**)&h->h_progress, 64 * GTO_MAX_LANES, hipHostMallocMapped));  // eight words per lane
-    std::memset(h->h_progress, 0, 64 * GTO_MAX_LANES);  // every word the solve loop reads carries a call tag (never 0)
-    HIPCHK(h, hipHostGetDevicePointer((void**)&h->d_progress, h->h_progress, 0));
+    HIPCHK(h, pinned_alloc(h->h_progress, 64 * GTO_MAX_LANES, hipHostMallocMapped));  // eight words per lane
+    std::memset(h->h_progress.get(), 0, 64 * GTO_MAX_LANES);  // every word the solve loop reads carries a call tag (never 0)
+    HIPCHK(h, hipHostGetDevicePointer((void**)&h->d_progress, h->h_progress.get(), 0));
   }
   return GTO_OK;
 }
@@ -1238,25 +1203,25 @@ static BatchPtrs make_ptrs(gto_handle* h, const int32_t* scene_id, const double*
   bp.standoff = standoff;
   bp.base_pos = base_pos;
   bp.Q0 = Q0;
-  bp.state = (InstState*)h->state.p;
-  bp.Qcur = (double*)h->Qcur.p;
-  bp.Qtry = (double*)h->Qtry.p;
-  bp.blocks = (double*)h->blocks.p;
-  bp.goalblk = (double*)h->goalblk.p;
-  bp.ss_fixed = (double*)h->ssfixed.p;
-  bp.n_done = (int32_t*)h->ndone.p;
-  bp.qf = (double*)h->qf.p;
+  bp.state = h->state.as<InstState>();
+  bp.Qcur = h->Qcur.as<double>();
+  bp.Qtry = h->Qtry.as<double>();
+  bp.blocks = h->blocks.as<double>();
+  bp.goalblk = h->goalblk.as<double>();
+  bp.ss_fixed = h->ssfixed.as<double>();
+  bp.n_done = h->ndone.as<int32_t>();
+  bp.qf = h->qf.as<double>();
   bp.live = nullptr;  // the live lists only exist inside the solve loop
   bp.jobs = nullptr;
   bp.nlive = nullptr;
   bp.next = nullptr;
   bp.qfs = nullptr;
-  bp.wrec = (double*)h->wrecbuf.p;
+  bp.wrec = h->wrecbuf.as<double>();
   bp.items = nullptr;
   bp.scenes = h->d_scenes;
   bp.cap = 0;
   bp.n_total = 0;
-  bp.dbg = h->dbg;
+  bp.dbg = h->dbg.as<long long>();
   bp.work = nullptr;
   return bp;
 }
@@ -1427,18 +1392,18 @@ static int setup_lanes(gto_handle* h, hipStream_t st, SolveParams& sp, BatchPtrs
     LaneCtx& ln = c.lanes[l];
     ln.sp = sp;
     ln.bp = bp;
-    ln.bp.live = (int32_t*)h->livebuf.p + off_live[l];
+    ln.bp.live = h->livebuf.as<int32_t>() + off_live[l];
     ln.bp.jobs = ln.bp.live + 2 * ln.cap;
     ln.bp.nlive = ln.bp.jobs + 2 * ln.cap * kcap;
     ln.bp.next = ln.bp.nlive + 4;
-    ln.bp.qfs = (double*)h->qfs.p + off_qfs[l];
-    ln.bp.items = h->np == GTO_NB ? (int2*)h->itembuf.p + off_items[l] : nullptr;
-    ln.bp.n_done = (int32_t*)h->ndone.p + 16 * l;
+    ln.bp.qfs = h->qfs.as<double>() + off_qfs[l];
+    ln.bp.items = h->np == GTO_NB ? h->itembuf.as<int2>() + off_items[l] : nullptr;
+    ln.bp.n_done = h->ndone.as<int32_t>() + 16 * l;
     ln.bp.cap = ln.cap;
     ln.bp.b0 = ln.lo;
     ln.bp.w0 = ln.W;
     ln.bp.n_total = ln.lo + ln.n;
-    ln.h_prog = h->h_progress + 8 * l;
+    ln.h_prog = h->h_progress.as<unsigned long long>() + 8 * l;
     ln.bp.progress = h->d_progress + 8 * l;
     // One lane: the caller's stream.  Several: streams of the handle's own, created one after the other -- the runtime deals
     // streams to its few hardware queues (GPU_MAX_HW_QUEUES, default 4) in the order of their creation, and two lanes on
@@ -1462,15 +1427,15 @@ static int setup_lanes(gto_handle* h, hipStream_t st, SolveParams& sp, BatchPtrs
     }
     if (!h->lane_event[l]) HIPCHK(h, hipEventCreateWithFlags(&h->lane_event[l], hipEventDisableTiming));
   }
-  HIPCHK(h, hipMemsetAsync(h->ndone.p, 0, 16 * sizeof(int32_t) * L, st));
+  HIPCHK(h, hipMemsetAsync(h->ndone.get(), 0, 16 * sizeof(int32_t) * L, st));
   // the finished-counter and the round counter reach the host through words in pinned memory that the step kernel
   // writes; the tag tells this call's values from what the last launches of the previous call may still be writing
   h->progress_tag = h->progress_tag + 1 ? h->progress_tag + 1 : 1;
   for (int l = 0; l < L; ++l) c.lanes[l].bp.progress_tag = (unsigned long long)h->progress_tag << 32;
   if (h->profiling) {
     if ((rc = ensure(h, h->counters, GTO_PROF_VARIANTS * 64 * sizeof(unsigned long long)))) return rc;
-    HIPCHK(h, hipMemsetAsync(h->counters.p, 0, GTO_PROF_VARIANTS * 64 * sizeof(unsigned long long), st));
-    bp.work = (unsigned long long*)h->counters.p;  // 64 cells per kernel variant (launch_obstacle picks the variant's)
+    HIPCHK(h, hipMemsetAsync(h->counters.get(), 0, GTO_PROF_VARIANTS * 64 * sizeof(unsigned long long), st));
+    bp.work = h->counters.as<unsigned long long>();  // 64 cells per kernel variant (launch_obstacle picks the variant's)
     for (int l = 0; l < L; ++l) c.lanes[l].bp.work = bp.work;
   }
   // The broad phase ahead of the obstacle launch, in the rounds that fill the GPU: the step kernel settles the waypoint
@@ -1594,7 +1559,7 @@ static int enqueue_round(gto_handle* h, const SolveCall& c, LaneCtx& ln, int lan
     hipLaunchKernelGGL((k_lm_step<4, 1>), dim3(p.span), dim3(256), h->lm_lds, ln.st, h->d_rb, ln.bp, lsp, B);
   } else {
     hipLaunchKernelGGL(k_lm_step_wide<16>, dim3(p.in_flight), dim3(GTO_WIDE_NT), h->lm_lds, ln.st, h->d_rb, ln.bp, lsp, B,
-                       (double*)h->zws.p + (size_t)c.lane_zws[lane_index] * (T - 2) * h->np * h->np);
+                       h->zws.as<double>() + (size_t)c.lane_zws[lane_index] * (T - 2) * h->np * h->np);
   }
   if (h->profiling && (rc = prof_end(h, ln.st))) return rc;
   ln.span_prev = p.static_pos ? p.span : 0;
@@ -1763,7 +1728,7 @@ static int harvest_profile(gto_handle* h, hipStream_t st, const unsigned long lo
 static int print_debug_stamps(gto_handle* h, hipStream_t st) {
   HIPCHK(h, hipStreamSynchronize(st));
   long long t[256];
-  HIPCHK(h, hipMemcpy(t, h->dbg, sizeof t, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(t, h->dbg.get(), sizeof t, hipMemcpyDeviceToHost));
   fprintf(stderr, "[gto dbg] step-kernel phases (cycles) P0+P1 %lld | P2 %lld | diag %lld | dense %lld | back %lld | P4 %lld | P5 %lld | s_dense %lld\n",
           t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4], t[6] - t[5], t[7] - t[6], t[9]);
   if (h->np != GTO_NB)
@@ -1804,17 +1769,6 @@ static int print_debug_stamps(gto_handle* h, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------- host-pointer staging
-static int ensure_pinned(gto_handle* h, DevBuf& b, size_t bytes) {
-  if (bytes <= b.cap) return GTO_OK;
-  if (b.p) HIPCHK(h, hipHostFree(b.p));
-  b.p = nullptr;
-  b.cap = 0;
-  const size_t want = bytes + bytes / 4 + 256;
-  HIPCHK(h, hipHostMalloc(&b.p, want));
-  b.cap = want;
-  return GTO_OK;
-}
-
 // The transfers of one call of a host-pointer entry point.  Every input and every output takes the next staging slot of
 // its direction (gto_handle::in / out and their pinned twins) in the order it is registered; a null host array takes
 // its slot too, gets a null device pointer and costs nothing.  An output states its size once, when it is registered.
@@ -1834,10 +1788,10 @@ class Staging {
     const size_t bytes = n * sizeof(T);
     int rc = ensure(h_, h_->in[k], bytes);
     if (rc) return rc;
-    if ((rc = ensure_pinned(h_, h_->pin_in[k], bytes))) return rc;  // free again: every entry point ends with a stream sync
-    memcpy(h_->pin_in[k].p, src, bytes);
-    HIPCHK(h_, hipMemcpyAsync(h_->in[k].p, h_->pin_in[k].p, bytes, hipMemcpyHostToDevice, h_->stream));
-    *dptr = (const T*)h_->in[k].p;
+    if ((rc = ensure(h_, h_->pin_in[k], bytes))) return rc;  // free again: every entry point ends with a stream sync
+    memcpy(h_->pin_in[k].get(), src, bytes);
+    HIPCHK(h_, hipMemcpyAsync(h_->in[k].get(), h_->pin_in[k].get(), bytes, hipMemcpyHostToDevice, h_->stream));
+    *dptr = h_->in[k].as<const T>();
     return GTO_OK;
   }
   // n elements for the host, delivered by finish()
@@ -1850,13 +1804,13 @@ class Staging {
   int finish() {
     for (int k = 0; k < n_out_; ++k) {
       if (!host_[k]) continue;
-      int rc = ensure_pinned(h_, h_->pin_out[k], bytes_[k]);
+      int rc = ensure(h_, h_->pin_out[k], bytes_[k]);
       if (rc) return rc;
-      HIPCHK(h_, hipMemcpyAsync(h_->pin_out[k].p, h_->out[k].p, bytes_[k], hipMemcpyDeviceToHost, h_->stream));
+      HIPCHK(h_, hipMemcpyAsync(h_->pin_out[k].get(), h_->out[k].get(), bytes_[k], hipMemcpyDeviceToHost, h_->stream));
     }
     HIPCHK(h_, hipStreamSynchronize(h_->stream));
     for (int k = 0; k < n_out_; ++k)
-      if (host_[k]) memcpy(host_[k], h_->pin_out[k].p, bytes_[k]);
+      if (host_[k]) memcpy(host_[k], h_->pin_out[k].get(), bytes_[k]);
     return GTO_OK;
   }
 
@@ -1871,7 +1825,7 @@ class Staging {
     if (!on_device) return GTO_OK;
     const int rc = ensure(h_, h_->out[k], bytes);
     if (rc) return rc;
-    *dptr = (T*)h_->out[k].p;
+    *dptr = h_->out[k].as<T>();
     return GTO_OK;
   }
   int too_many() { return fail(h_, GTO_ERR_UNSUPPORTED, "internal: more than eight staged arrays of one direction"); }
@@ -1902,7 +1856,7 @@ int gto_solve_batch_device(gto_handle* h, int32_t B, int32_t n_max, const int32_
   BatchPtrs bp = make_ptrs(h, scene_id, qc, goals, n_goals, standoff, base_pos, Q0);
   h->last_launches = 0;
   h->last_ms = 0.0;
-  if (h->dbg) HIPCHK(h, hipMemsetAsync(h->dbg + 40, 0, 216 * sizeof(long long), st));
+  if (h->dbg) HIPCHK(h, hipMemsetAsync(h->dbg.as<long long>() + 40, 0, 216 * sizeof(long long), st));
 
   SolveCall c;
   c.h = h, c.B = B, c.T = sp.T, c.kcap = sp.kcap, c.nF = h->rb.n_frames, c.max_iter = sp.max_iter;
@@ -2095,15 +2049,15 @@ static int seed_goalsets(gto_handle* h, const std::string& name, int32_t B, int3
   HIPCHK(h, raise_dynamic_lds((const void*)k_seed_score, lds));
   hipLaunchKernelGGL(k_seed_score, dim3((unsigned)((T + GTO_PLAN_TG - 1) / GTO_PLAN_TG), n_max, B), dim3(256), lds, st, h->d_rb,
                      h->d_px, h->d_py, h->d_pz, h->d_plink, h->d_scenes, (int)h->scenes.size(), scene_id, qc, n_goals,
-                     q_solutions, accept, base_pos, T, n_max, solutions_f32 != 0, (double*)h->sd_part.p);
+                     q_solutions, accept, base_pos, T, n_max, solutions_f32 != 0, h->sd_part.as<double>());
   if (n_seeds)
     hipLaunchKernelGGL(k_seed_select_ranked, dim3(B), dim3(64), 0, st, h->d_rb, qc, goals, n_goals, q_solutions, accept,
-                       (const double*)h->sd_part.p, T, T + h->opts.standoff_offset, n_max, interpolate != 0, solutions_f32 != 0,
+                       h->sd_part.as<const double>(), T, T + h->opts.standoff_offset, n_max, interpolate != 0, solutions_f32 != 0,
                        (int)n_seeds, goals_out, n_goals_out, n_accepted_out, accepted_rows_out, Q0_out, seed_index_out,
                        seed_cost_out, seed_dist_out);
   else
     hipLaunchKernelGGL(k_seed_select, dim3(B), dim3(64), 0, st, h->d_rb, qc, goals, n_goals, q_solutions, accept,
-                       (const double*)h->sd_part.p, T, T + h->opts.standoff_offset, n_max, interpolate != 0, solutions_f32 != 0,
+                       h->sd_part.as<const double>(), T, T + h->opts.standoff_offset, n_max, interpolate != 0, solutions_f32 != 0,
                        goals_out, n_goals_out, n_accepted_out, Q0_out, seed_index_out, seed_cost_out, seed_dist_out);
   HIPCHK(h, hipGetLastError());
   return GTO_OK;
@@ -2217,11 +2171,11 @@ static int base_counts_to_device(gto_handle* h, int32_t B, const int32_t* n_goal
   h->bs_pin_next = (k + 1) % GTO_BASE_PIN_SLOTS;
   if (!h->bs_pin_ev[k]) HIPCHK(h, hipEventCreateWithFlags(&h->bs_pin_ev[k], hipEventDisableTiming));
   else HIPCHK(h, hipEventSynchronize(h->bs_pin_ev[k]));
-  if ((rc = ensure_pinned(h, h->bs_pin[k], bytes))) return rc;
-  memcpy(h->bs_pin[k].p, n_goals, bytes);
-  HIPCHK(h, hipMemcpyAsync(h->bs_ng.p, h->bs_pin[k].p, bytes, hipMemcpyHostToDevice, st));
+  if ((rc = ensure(h, h->bs_pin[k], bytes))) return rc;
+  memcpy(h->bs_pin[k].get(), n_goals, bytes);
+  HIPCHK(h, hipMemcpyAsync(h->bs_ng.get(), h->bs_pin[k].get(), bytes, hipMemcpyHostToDevice, st));
   HIPCHK(h, hipEventRecord(h->bs_pin_ev[k], st));
-  *d_ng = (const int32_t*)h->bs_ng.p;
+  *d_ng = h->bs_ng.as<const int32_t>();
   return GTO_OK;
 }
 
@@ -2386,9 +2340,9 @@ int gto_eval_points(gto_handle* h, int32_t scene_id, int32_t nq, const double* q
   if ((rc = io.out(offset_out, (size_t)nq * P, &doff))) return rc;
   if ((rc = io.out(value_out, (size_t)nq * P, &dval))) return rc;
   if ((rc = io.out(grad_out, (size_t)nq * P * 3, &dgrad))) return rc;
-  if ((rc = launch_eval_kin(h, nq, dq, nullptr, (double*)h->vis.p))) return rc;
+  if ((rc = launch_eval_kin(h, nq, dq, nullptr, h->vis.as<double>()))) return rc;
   hipLaunchKernelGGL(k_eval_points, dim3((P + 255) / 256, nq), dim3(256), 0, h->stream, h->d_rb, h->d_px, h->d_py, h->d_pz,
-                     h->d_plink, h->d_perm, want_field ? h->d_scenes + scene_id : nullptr, nq, (const double*)h->vis.p,
+                     h->d_plink, h->d_perm, want_field ? h->d_scenes + scene_id : nullptr, nq, h->vis.as<const double>(),
                      dbase, use_obs, dx, doff, dval, dgrad);
   HIPCHK(h, hipGetLastError());
   return io.finish();
@@ -2409,9 +2363,9 @@ int gto_eval_points_hessian(gto_handle* h, int32_t scene_id, int32_t nq, const d
   if ((rc = io.in(base_pos, (size_t)nq * 3, &dbase))) return rc;
   if ((rc = ensure(h, h->vis, (size_t)nq * L * 12 * sizeof(double)))) return rc;
   if ((rc = io.out(hess_out, (size_t)nq * P * 9, &dh))) return rc;
-  if ((rc = launch_eval_kin(h, nq, dq, nullptr, (double*)h->vis.p))) return rc;
+  if ((rc = launch_eval_kin(h, nq, dq, nullptr, h->vis.as<double>()))) return rc;
   hipLaunchKernelGGL(k_eval_points_hessian, dim3((P + 255) / 256, nq), dim3(256), 0, h->stream, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_plink,
-                     h->d_perm, h->d_scenes + scene_id, nq, (const double*)h->vis.p, dbase, use_obs, dh);
+                     h->d_perm, h->d_scenes + scene_id, nq, h->vis.as<const double>(), dbase, use_obs, dh);
   HIPCHK(h, hipGetLastError());
   return io.finish();
 }
@@ -2471,11 +2425,11 @@ static int eval_common(gto_handle* h, int B, int n_max, const int32_t* scene_id,
   const size_t bstride = (size_t)h->np * h->np + h->np + 8;
   blocks.resize((size_t)B * T * bstride);
   ssfixed.resize((size_t)B * 4);
-  HIPCHK(h, hipMemcpyAsync(states.data(), h->state.p, B * sizeof(InstState), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(states.data(), h->state.get(), B * sizeof(InstState), hipMemcpyDeviceToHost, h->stream));
   // trial slot is 1 right after init (slot = 0)
-  HIPCHK(h, hipMemcpyAsync(blocks.data(), (double*)h->blocks.p + (size_t)1 * B * T * bstride,
+  HIPCHK(h, hipMemcpyAsync(blocks.data(), h->blocks.as<double>() + (size_t)1 * B * T * bstride,
                            blocks.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(ssfixed.data(), h->ssfixed.p, ssfixed.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(ssfixed.data(), h->ssfixed.get(), ssfixed.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipGetLastError());
   return GTO_OK;
@@ -2572,6 +2526,8 @@ int gto_plan_cost(gto_handle* h, int32_t scene_id, int32_t n, const double* plan
 }  // extern "C"
 
 namespace {
+// On raw pointers, not owners: the pool has static storage duration, and an owner in it would call hipFree while the
+// process exits, when the runtime may be gone already.  What is cached at exit is left to the process's end.
 struct DepthPool {
   struct Item { int device; void* p; size_t cap; };
   std::mutex mu;
@@ -2633,14 +2589,15 @@ struct DepthLease {
     for (auto& b : bufs) g_depth_pool.give(device, b.first, b.second);
     bufs.clear();
   }
-  // a buffer of this call that outlives it (a gto_observation takes it over and frees it itself)
-  void* keep(const void* p) {
-    for (size_t k = 0; k < bufs.size(); ++k)
+  // a buffer of this call that outlives it: it leaves the lease with an owner (a gto_observation, a gto_occupancy)
+  DevBuf keep(const void* p) {
+    for (size_t k = 0; p && k < bufs.size(); ++k)
       if (bufs[k].first == p) {
+        DevBuf b(bufs[k].first, bufs[k].second);
         bufs.erase(bufs.begin() + k);
-        return const_cast<void*>(p);
+        return b;
       }
-    return nullptr;
+    return DevBuf();
   }
   int no_memory() { return fail(h, GTO_ERR_ALLOC, std::string(who) + ": device allocation failed"); }
   int hip(hipError_t e) { return e == hipSuccess ? GTO_OK : fail(h, GTO_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
@@ -3189,7 +3146,7 @@ int gto_retime_batch_device(gto_handle* h, int32_t B, const double* plans, const
   if (!h->rt_fac_ready) {  // once per handle (T is fixed for its lifetime)
     const std::vector<double> f = retime_factors(d.T);
     if ((rc = ensure(h, h->rt_fac, f.size() * sizeof(double)))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->rt_fac.p, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->rt_fac.get(), f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(h, hipStreamSynchronize(st));
     h->rt_fac_ready = true;
   }
@@ -3201,11 +3158,11 @@ int gto_retime_batch_device(gto_handle* h, int32_t B, const double* plans, const
   if ((rc = ensure(h, h->rt_X, nB * N * sizeof(double)))) return rc;
   if ((rc = ensure(h, h->rt_T, nB * N * sizeof(double)))) return rc;
   if ((rc = ensure(h, h->rt_stat, nB * sizeof(int32_t)))) return rc;
-  double *S = (double*)h->rt_S.p, *P1 = (double*)h->rt_P1.p, *P2 = (double*)h->rt_P2.p, *cap = (double*)h->rt_cap.p;
-  double *X = (double*)h->rt_X.p, *Tg = (double*)h->rt_T.p;
-  int32_t *flag = (int32_t*)h->rt_flag.p, *stat = (int32_t*)h->rt_stat.p;
+  double *S = h->rt_S.as<double>(), *P1 = h->rt_P1.as<double>(), *P2 = h->rt_P2.as<double>(), *cap = h->rt_cap.as<double>();
+  double *X = h->rt_X.as<double>(), *Tg = h->rt_T.as<double>();
+  int32_t *flag = h->rt_flag.as<int32_t>(), *stat = h->rt_stat.as<int32_t>();
   hipLaunchKernelGGL(k_retime_spline, dim3(retime_blocks((long long)B * nd, 256)), dim3(256), 0, st, plans,
-                     (const double*)h->rt_fac.p, d, S, flag);
+                     h->rt_fac.as<const double>(), d, S, flag);
   hipLaunchKernelGGL(k_retime_grid, dim3(retime_blocks((long long)B * N, 256)), dim3(256), 0, st, plans, S, flag, lim, d,
                      P1, P2, cap);
   hipLaunchKernelGGL(k_retime_pass, dim3(B), dim3(64), 0, st, P1, P2, cap, flag, lim, d, X, Tg, stat, duration_out,
@@ -3252,7 +3209,7 @@ int gto_retime_batch(gto_handle* h, int32_t B, const double* plans, const double
 struct gto_observation {
   int device = 0;
   bool is_depth = true;
-  std::vector<void*> owned;  // device buffers, freed by gto_observation_destroy
+  std::vector<DevBuf> owned;  // its device buffers
   // depth: image, camera, world points, tile hierarchy (P = 0: none, exhaustive search)
   DepthCloud depth = {};
   DepthCamera cam = {};
@@ -3264,7 +3221,7 @@ struct gto_observation {
 namespace {
 void obs_adopt(gto_observation* o, DepthLease& c, std::initializer_list<const void*> ps) {
   for (const void* p : ps)
-    if (p && c.keep(p)) o->owned.push_back(const_cast<void*>(p));
+    if (DevBuf b = c.keep(p)) o->owned.push_back(std::move(b));
 }
 ObsDepthView depth_view(const gto_observation* o) { return {o->depth.depth, o->depth.H, o->depth.W, o->cam.K, o->cam.inv}; }
 
@@ -3343,9 +3300,8 @@ void gto_observation_destroy(gto_observation* o) {
   (void)hipGetDevice(&cur);
   (void)hipSetDevice(o->device);
   (void)hipDeviceSynchronize();  // nothing may still be reading it
-  for (void* p : o->owned) (void)hipFree(p);
+  delete o;  // frees its buffers
   if (cur >= 0) (void)hipSetDevice(cur);  // the caller's current device is the caller's
-  delete o;
 }
 
 int gto_observation_sdf(gto_observation* o, const double* query, int64_t nq, float* sdf_out, uint8_t* inside_out) {
@@ -3423,8 +3379,8 @@ int gto_check_plans_device(gto_handle* h, gto_observation* o, int32_t B, const d
     // documented behaviour of the asynchronous copies for pageable memory): the caller's array is free on return, and the
     // copy is ordered on `st` in front of the kernel.  ck_base is one buffer per handle: see the header on streams.
     if ((rc = ensure(h, h->ck_base, (size_t)B * 3 * sizeof(double)))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->ck_base.p, base_pos, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-    d_base = (const double*)h->ck_base.p;
+    HIPCHK(h, hipMemcpyAsync(h->ck_base.get(), base_pos, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    d_base = h->ck_base.as<const double>();
   }
   const double b0 = per_plan_base ? 0.0 : base_pos[0], b1 = per_plan_base ? 0.0 : base_pos[1], b2 = per_plan_base ? 0.0 : base_pos[2];
   if (o->is_depth) {
@@ -3437,8 +3393,8 @@ int gto_check_plans_device(gto_handle* h, gto_observation* o, int32_t B, const d
     const int chunk = chunk_items(B, (long long)T * std::max(1, P));
     if ((rc = ensure(h, h->ck_xyz, (size_t)chunk * T * P * 3 * sizeof(double)))) return rc;
     if ((rc = ensure(h, h->ck_flags, (size_t)chunk * T * P))) return rc;
-    double* d_xyz = (double*)h->ck_xyz.p;
-    uint8_t* d_flags = (uint8_t*)h->ck_flags.p;
+    double* d_xyz = h->ck_xyz.as<double>();
+    uint8_t* d_flags = h->ck_flags.as<uint8_t>();
     for (int i0 = 0; i0 < B; i0 += chunk) {
       const int m = std::min(chunk, B - i0);
       int32_t* cnt = count_out + (size_t)i0 * T;
@@ -3475,7 +3431,7 @@ struct gto_occupancy {
   int device = 0;
   double origin[2] = {0, 0}, xlim[2] = {0, 0}, ylim[2] = {0, 0}, res = 0;
   int32_t shape[2] = {0, 0};
-  uint8_t* grid = nullptr;  // device, [nx][ny], 0 / 1; freed by gto_occupancy_destroy
+  DevBuf grid;  // device, uint8 [nx][ny], 0 / 1
 };
 
 namespace {
@@ -3532,7 +3488,7 @@ int build_occupancy(DepthLease& c, const OccPoints& pts, double margin, double r
   hipLaunchKernelGGL(k_occ_mark, dim3((unsigned)((pts.n + 255) / 256)), dim3(256), 0, 0, pts, d_xg, d_yg, o->shape[0], o->shape[1], res,
                      epsilon, k, d_grid);
   DEPTH_TRY(c.sync());
-  o->grid = (uint8_t*)c.keep(d_grid);
+  o->grid = c.keep(d_grid);
   *out = o.release();
   return GTO_OK;
 }
@@ -3578,7 +3534,7 @@ int gto_occupancy_geometry(const gto_occupancy* occ, double* origin, int32_t* sh
 int gto_occupancy_grid(gto_occupancy* occ, uint8_t* out) {
   if (!occ || !out) return fail(nullptr, GTO_ERR_INVALID_ARG, "gto_occupancy_grid: null occupancy grid or output");
   if (hipSetDevice(occ->device) != hipSuccess) return fail(nullptr, GTO_ERR_NO_DEVICE, "hipSetDevice failed");
-  const hipError_t e = hipMemcpy(out, occ->grid, (size_t)occ->shape[0] * occ->shape[1], hipMemcpyDeviceToHost);
+  const hipError_t e = hipMemcpy(out, occ->grid.get(), (size_t)occ->shape[0] * occ->shape[1], hipMemcpyDeviceToHost);
   return e == hipSuccess ? GTO_OK : fail(nullptr, GTO_ERR_HIP, std::string("gto_occupancy_grid: ") + hipGetErrorString(e));
 }
 
@@ -3588,9 +3544,8 @@ void gto_occupancy_destroy(gto_occupancy* occ) {
   (void)hipGetDevice(&cur);
   (void)hipSetDevice(occ->device);
   (void)hipDeviceSynchronize();  // nothing may still be reading it
-  (void)hipFree(occ->grid);
+  delete occ;  // frees the grid
   if (cur >= 0) (void)hipSetDevice(cur);  // the caller's current device is the caller's
-  delete occ;
 }
 
 int gto_base_report_device(gto_handle* h, gto_occupancy* occ, int32_t B, int32_t n_max, const int32_t* n_goals, const double* qc,
@@ -3616,10 +3571,10 @@ int gto_base_report_device(gto_handle* h, gto_occupancy* occ, int32_t B, int32_t
   if ((rc = base_counts_to_device(h, B, n_goals, st, &d_ng))) return rc;
   if (count && !collision_out) {  // the choice alone: the counts stay in the handle's workspace
     if ((rc = ensure(h, h->bs_coll, (size_t)B * sizeof(int32_t)))) return rc;
-    collision_out = (int32_t*)h->bs_coll.p;
+    collision_out = h->bs_coll.as<int32_t>();
   }
   OccGridView og = {};
-  if (count) og = {occ->grid, occ->shape[0], occ->shape[1], occ->origin[0], occ->origin[1], occ->res};
+  if (count) og = {occ->grid.as<uint8_t>(), occ->shape[0], occ->shape[1], occ->origin[0], occ->origin[1], occ->res};
   HIPCHK(h, raise_dynamic_lds((const void*)k_base_report, lds));
   hipLaunchKernelGGL(k_base_report, dim3((unsigned)(n_max + (count ? 1 : 0)), (unsigned)B), dim3(256), lds, st, h->d_rb, h->d_px, h->d_py,
                      h->d_pz, h->d_plink, d_ng, qc, goals, y, q, n_max, og, err_pos_out, err_rot_out, count ? collision_out : nullptr);
