@@ -151,6 +151,7 @@ def _prototypes():
         "gto_seed_goalsets_multi_device": (I, [V, I32, I32, I32] + seeds + [V] * 9),
         "gto_plan_report_device": (I, [V, I32, I32] + [V] * 9),
         "gto_select_plans_device": (I, [V, I32, I32] + [V] * 5 + [D, D, I32] + [V] * 7),
+        "gto_filter_grasps_device": (I, [V, I32, I32, PV, V, I32] + [V] * 5 + [_pd, _pd, D] + [V] * 8),
     }
 
 
@@ -680,6 +681,23 @@ class SolverHandle:
                                                      _vp(counts), float(pos_tol), float(rot_tol_deg), int(max_points), _vp(Q), _vp(dQ),
                                                      _vp(best_slot_out), _vp(class_out), _vp(Q_out), _vp(dQ_out), _vp(stream)),
                     "gto_select_plans_device")
+
+    # -------------------------------------------------------------- the grasp collision filter (GraspChain.plan_grasps)
+    def filter_grasps_device(self, observations, n_max, points, P, object_pose, grasps, n_grasps, check_offset, ik_offset=None,
+                             world_to_base=None, base_pos=None, max_ratio=0.01, count_out=None, keep_out=None, kept_rows_out=None,
+                             n_kept_out=None, n_grasps_out=None, plan_goals_out=None, ik_goals_out=None, stream=None):
+        """gto_filter_grasps_device: observations is a HOST sequence of observation.Observation, one per object (B = its
+        length; entries may repeat); check_offset and ik_offset are HOST 4x4 matrices; every other array is a device
+        pointer (an int, e.g. torch.Tensor.data_ptr()) or None."""
+        B = len(observations)
+        obs = (C.c_void_p * max(1, B))(*[o._ptr() for o in observations])
+        co = _f64(check_offset).reshape(16)
+        io = None if ik_offset is None else _f64(ik_offset).reshape(16)
+        self._check(self.lib.gto_filter_grasps_device(self._h, B, int(n_max), obs, _vp(points), int(P), _vp(object_pose), _vp(grasps),
+                                                      _vp(n_grasps), _vp(world_to_base), _vp(base_pos), _p(co, _pd), _p(io, _pd),
+                                                      float(max_ratio), _vp(count_out), _vp(keep_out), _vp(kept_rows_out),
+                                                      _vp(n_kept_out), _vp(n_grasps_out), _vp(plan_goals_out), _vp(ik_goals_out),
+                                                      _vp(stream)), "gto_filter_grasps_device")
 
     def solve_base_batch(self, qc, goals, n_goals=None, effort_weight=0.01, max_iter=100):
         """Base placement for B goal sets (gto/base_planner.py:35-123): qc (B,ndof), goals (B,n_max,4,4).

@@ -39,7 +39,7 @@ static std::string g_create_error;
 #define GTO_SWEEP_WGS 64   // workgroups of the crew behind an itemized obstacle launch laid out over an estimate (launch_obstacle)
 
 #define GTO_MAX_LANES 8  // lanes of one solve call (streams, list sets, progress words)
-#define GTO_BASE_PIN_SLOTS 4  // calls of the base placement chain whose n_goals may be in flight at once without the host waiting
+#define GTO_BASE_PIN_SLOTS 4  // calls whose small host arrays (n_goals, the filter's view table) may be in flight at once without the host waiting
 #define GTO_STAGE_SLOTS 8  // host arrays of each direction that one host-pointer entry point stages (Staging)
 #define GTO_NAP_US 50      // the throttle's naps (the host thread of a lane sleep-polls two pinned words); 10-50 us change nothing
 #define GTO_NAP_FEW_US 10  // ... in launches with few instances in flight; 50-200 us change nothing either
@@ -229,9 +229,12 @@ struct gto_handle {
   // base placement with resident arrays (gto_solve_base_batch_device, gto_base_report_device): the device copy of the
   // caller's n_goals, and the per-set counts when the caller asks for the choice alone
   DevBuf bs_ng, bs_coll;
-  PinBuf bs_pin[GTO_BASE_PIN_SLOTS];           // pinned copies of n_goals, one per call in flight (base_counts_to_device)
+  PinBuf bs_pin[GTO_BASE_PIN_SLOTS];           // pinned copies of n_goals, one per call in flight (pinned_to_device)
   hipEvent_t bs_pin_ev[GTO_BASE_PIN_SLOTS] = {};  // recorded behind the copy that reads slot k
   int bs_pin_next = 0;
+  // the grasp filter (gto_filter_grasps_device): the depth objects' views, the uncompacted goals [B][n_max][16], the poses
+  // of the cloud objects' rows [B][n_max][16], the counts [B][n_max]
+  DevBuf fg_tab, fg_plan, fg_ik, fg_pose, fg_count;
 
   // the streams and events the handle created; the buffers above free themselves after this (gto_destroy has set the device)
   ~gto_handle() {
@@ -2158,23 +2161,28 @@ static int base_launch(gto_handle* h, int32_t B, int32_t n_max, const double* d_
   return GTO_OK;
 }
 
-// The caller's n_goals [B] (host, checked) on the device, ordered on `st` in front of the kernel that reads it.  The array is
-// copied into a pinned slot of the handle first, so the caller's array is free on return whatever memory it lives in, and
-// the transfer is a real asynchronous DMA.  A slot is reused once the copy that read it has run (its event; with
-// GTO_BASE_PIN_SLOTS calls in flight the host waits for the oldest).  bs_ng is one device buffer per handle: calls on one
-// handle go to one stream, or the caller orders them.
-static int base_counts_to_device(gto_handle* h, int32_t B, const int32_t* n_goals, hipStream_t st, const int32_t** d_ng) {
-  const size_t bytes = (size_t)B * sizeof(int32_t);
-  int rc = ensure(h, h->bs_ng, bytes);
+// `bytes` bytes of a host array of the caller on the device in `dst` (grown on demand), ordered on `st` in front of the kernel
+// that reads them.  The array is copied into a pinned slot of the handle first, so the caller's array is free on return
+// whatever memory it lives in, and the transfer is a real asynchronous DMA.  A slot is reused once the copy that read it has
+// run (its event; with GTO_BASE_PIN_SLOTS calls in flight the host waits for the oldest).  dst is one device buffer per
+// handle: calls on one handle go to one stream, or the caller orders them.
+static int pinned_to_device(gto_handle* h, DevBuf& dst, const void* src, size_t bytes, hipStream_t st) {
+  int rc = ensure(h, dst, bytes);
   if (rc) return rc;
   const int k = h->bs_pin_next;
   h->bs_pin_next = (k + 1) % GTO_BASE_PIN_SLOTS;
   if (!h->bs_pin_ev[k]) HIPCHK(h, hipEventCreateWithFlags(&h->bs_pin_ev[k], hipEventDisableTiming));
   else HIPCHK(h, hipEventSynchronize(h->bs_pin_ev[k]));
   if ((rc = ensure(h, h->bs_pin[k], bytes))) return rc;
-  memcpy(h->bs_pin[k].get(), n_goals, bytes);
-  HIPCHK(h, hipMemcpyAsync(h->bs_ng.get(), h->bs_pin[k].get(), bytes, hipMemcpyHostToDevice, st));
+  memcpy(h->bs_pin[k].get(), src, bytes);
+  HIPCHK(h, hipMemcpyAsync(dst.get(), h->bs_pin[k].get(), bytes, hipMemcpyHostToDevice, st));
   HIPCHK(h, hipEventRecord(h->bs_pin_ev[k], st));
+  return GTO_OK;
+}
+
+// The caller's n_goals [B] (host, checked) on the device in bs_ng: pinned_to_device
+static int base_counts_to_device(gto_handle* h, int32_t B, const int32_t* n_goals, hipStream_t st, const int32_t** d_ng) {
+  if (int rc = pinned_to_device(h, h->bs_ng, n_goals, (size_t)B * sizeof(int32_t), st)) return rc;
   *d_ng = h->bs_ng.as<const int32_t>();
   return GTO_OK;
 }
@@ -3404,6 +3412,86 @@ int gto_check_plans_device(gto_handle* h, gto_observation* o, int32_t B, const d
       hipLaunchKernelGGL(k_count_flags, dim3((unsigned)(m * T)), dim3(256), 0, st, d_flags, P, cnt);
     }
   }
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
+}
+
+// The grasp collision filter on the stream (include/gto_solver.h; kernels: gto_observe.h).  The observations are host facts of
+// the call: which of them are depth images decides the launches.
+int gto_filter_grasps_device(gto_handle* h, int32_t B, int32_t n_max, gto_observation* const* obs, const double* points, int32_t P,
+                             const double* object_pose, const double* grasps, const int32_t* n_grasps, const double* world_to_base,
+                             const double* base_pos, const double* check_offset, const double* ik_offset, double max_ratio,
+                             int32_t* count_out, uint8_t* keep_out, int32_t* kept_rows_out, int32_t* n_kept_out,
+                             int32_t* n_grasps_out, double* plan_goals_out, double* ik_goals_out, void* stream) {
+  const char* who = "gto_filter_grasps_device";
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (B < 0 || n_max < 1 || P < 1 || !(max_ratio >= 0.0) || !std::isfinite(max_ratio))
+    return fail(h, GTO_ERR_INVALID_ARG, std::string(who) + ": B >= 0, n_max >= 1, P >= 1 and a finite max_ratio >= 0 are required");
+  if (B == 0) return GTO_OK;
+  if (B > 65535 || n_max > 65535) return fail(h, GTO_ERR_UNSUPPORTED, std::string(who) + ": at most 65535 objects of at most 65535 grasps in one call");
+  if (!obs || !points || !object_pose || !grasps || !n_grasps || !check_offset) return fail(h, GTO_ERR_INVALID_ARG, std::string(who) + ": null input array");
+  for (int b = 0; b < B; ++b) {
+    if (!obs[b]) return fail(h, GTO_ERR_INVALID_ARG, std::string(who) + ": null observation");
+    if (obs[b]->device != h->device) return fail(h, GTO_ERR_INVALID_ARG, std::string(who) + ": an observation lives on another device than the handle");
+  }
+  PoseArg coff, ioff = {};
+  for (int e = 0; e < 16; ++e) {
+    coff.m[e] = check_offset[e];
+    if (ik_offset) ioff.m[e] = ik_offset[e];
+    if (!std::isfinite(coff.m[e]) || !std::isfinite(ioff.m[e])) return fail(h, GTO_ERR_INVALID_ARG, std::string(who) + ": non-finite entry in check_offset or ik_offset");
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  const size_t rows = (size_t)B * n_max;
+  int rc;
+  if ((rc = ensure(h, h->fg_plan, rows * 16 * sizeof(double)))) return rc;
+  if ((rc = ensure(h, h->fg_ik, rows * 16 * sizeof(double)))) return rc;
+  if ((rc = ensure(h, h->fg_count, rows * sizeof(int32_t)))) return rc;
+  double *ws_plan = h->fg_plan.as<double>(), *ws_ik = h->fg_ik.as<double>();
+  int32_t* ws_count = h->fg_count.as<int32_t>();
+  const int has_ik = ik_offset != nullptr;
+  // the depth objects: one launch over all of them, each against its own image
+  std::vector<FilterDepthItem> items;
+  for (int b = 0; b < B; ++b)
+    if (obs[b]->is_depth) items.push_back({depth_view(obs[b]), b});
+  if (!items.empty()) {
+    if ((rc = pinned_to_device(h, h->fg_tab, items.data(), items.size() * sizeof(FilterDepthItem), st))) return rc;
+    hipLaunchKernelGGL(k_filter_depth, dim3((unsigned)n_max, (unsigned)items.size()), dim3(256), 0, st, h->fg_tab.as<const FilterDepthItem>(),
+                       points, (int)P, (int)n_max, object_pose, grasps, n_grasps, world_to_base, base_pos, coff, ioff, has_ik, ws_plan, ws_ik,
+                       ws_count);
+  }
+  // the cloud objects: every run of consecutive objects that name one observation takes gto_observation_check_posed's chain
+  if (items.size() < (size_t)B) {
+    if ((rc = ensure(h, h->fg_pose, rows * 16 * sizeof(double)))) return rc;
+    double* ws_pose = h->fg_pose.as<double>();
+    const SearchEnv env = search_env();
+    for (int b0 = 0; b0 < B;) {
+      int b1 = b0 + 1;
+      if (obs[b0]->is_depth) {
+        b0 = b1;
+        continue;
+      }
+      while (b1 < B && obs[b1] == obs[b0]) ++b1;
+      const long long n = (long long)(b1 - b0) * n_max;  // the run's poses: at most 65535 * 65535
+      hipLaunchKernelGGL(k_filter_pose, dim3((unsigned)((n_max + 63) / 64), (unsigned)(b1 - b0)), dim3(64), 0, st, b0, (int)n_max, object_pose, grasps,
+                         n_grasps, world_to_base, base_pos, coff, ioff, has_ik, ws_plan, ws_ik, ws_pose);
+      const long long chunk = std::min<long long>(n, std::max<long long>(1, kCheckChunkQueries / P));
+      if ((rc = ensure(h, h->ck_xyz, (size_t)chunk * P * 3 * sizeof(double)))) return rc;
+      if ((rc = ensure(h, h->ck_flags, (size_t)chunk * P))) return rc;
+      for (long long i0 = 0; i0 < n; i0 += chunk) {
+        const long long m = std::min(chunk, n - i0);
+        const size_t at = (size_t)b0 * n_max + (size_t)i0;
+        hipLaunchKernelGGL(k_check_posed<false>, dim3((unsigned)m), dim3(256), 0, st, points, (int)P, ws_pose + at * 16, ObsDepthView{},
+                           h->ck_xyz.as<double>(), ws_count + at);
+        obs_cloud_votes(env, st, obs[b0], h->ck_xyz.as<const double>(), (long)(m * P), h->ck_flags.as<uint8_t>());
+        hipLaunchKernelGGL(k_count_flags, dim3((unsigned)m), dim3(256), 0, st, h->ck_flags.as<const uint8_t>(), (int)P, ws_count + at);
+      }
+      b0 = b1;
+    }
+  }
+  hipLaunchKernelGGL(k_filter_compact, dim3((unsigned)B), dim3(64), 0, st, (int)n_max, (int)P, max_ratio, n_grasps, (const int32_t*)ws_count,
+                     (const double*)ws_plan, (const double*)ws_ik, count_out, keep_out, kept_rows_out, n_kept_out, n_grasps_out, plan_goals_out,
+                     ik_goals_out);
   HIPCHK(h, hipGetLastError());
   return GTO_OK;
 }

@@ -1,7 +1,10 @@
-"""GraspChain — the per-object loop of the reference's driver (examples/pybullet_gto_planning.py:242-294) on one stream:
+"""GraspChain — the per-object loop of the reference's driver after perception (examples/pybullet_gto_planning.py:192-294)
+on one stream:
 
-    grasp poses -> IK (gto_solve_ik_pose_batch_device) -> err_pos / err_rot / collision cost and the acceptance test of :262
-    (gto_ik_report_device) -> accepted goal sets and seeds (gto_seed_goalsets_device) -> gto_solve_batch_device ->
+    object poses and object-frame grasps -> the grasp collision filter against each object's observation, the base-frame
+    goal sets compacted (gto_filter_grasps_device; ``plan_grasps``, :192-236) ->
+    grasp poses (``plan_objects`` starts here, :242) -> IK (gto_solve_ik_pose_batch_device) -> err_pos / err_rot /
+    collision cost and the acceptance test of :262 (gto_ik_report_device) -> accepted goal sets and seeds (gto_seed_goalsets_device) -> gto_solve_batch_device ->
     optionally gto_check_plans_device and gto_retime_batch_device
 
 (with ``n_seeds`` > 1: gto_seed_goalsets_multi_device -> one gto_solve_batch_device over every object's n_seeds best seeds ->
@@ -13,6 +16,7 @@ are bit-equal (the same seed and goals go into the same solve).
 """
 from __future__ import annotations
 
+import inspect
 from types import SimpleNamespace
 
 import numpy as np
@@ -138,19 +142,112 @@ class GraspChain:
         added: best_slot, plan_class (B,), goal_index (B,) (the compacted position of the grasp the plan reached), goal_row
         (B,) (its row among the object's grasps: where to close the gripper; -1 without an accepted grasp), plan_err_pos,
         plan_err_rot (B,), slot_cost, slot_class (B, n_seeds), slot_plans (B, n_seeds, ndof, T).  n_seeds = 1 is the chain above, launch for launch."""
+        ik_goals = np.asarray(ik_goals, dtype=np.float64)
+        B, n_max = ik_goals.shape[0], ik_goals.shape[1]
+        ik_goals = ik_goals.reshape(B, n_max, 16)
+        plan_goals = np.asarray(plan_goals, dtype=np.float64).reshape(B, n_max, 16)
+        n_grasps = self._grasp_counts(n_grasps, B, n_max)
+
+        def feed(st, d_base):
+            return (self._up("ik_goals", ik_goals, np.float64), self._up("plan_goals", plan_goals, np.float64),
+                    self._up("n_grasps", n_grasps, np.int32), {})
+
+        return self._plan(B, n_max, feed, qc, fields, base_position, axis_standoff, use_standoff, interpolate, pos_tol, rot_tol_deg,
+                          ik_collision_threshold, float32_solutions, observation, retime, n_seeds, max_points)
+
+    def plan_grasps(self, qc, object_poses, grasps, n_grasps, observations, fields, base_position, gripper_points, check_offset,
+                    ik_offset=None, world_to_base=None, max_ratio=0.01, **plan_objects_keywords):
+        """The driver's whole per-object loop after perception (:192-294): the grasp collision filter, then ``plan_objects``,
+        with the one synchronisation at the end.
+
+        object_poses (B, 4, 4); grasps (B, n_max, 4, 4) in the object's frame; n_grasps (B,); observations: one entry for all
+        objects or one per object, an ``observation.Observation`` or a DepthPointCloud / SurfacePointCloud (its cached
+        observation); gripper_points (P, 3): the open gripper's surface points in the frame the poses place; check_offset
+        (4, 4): the pose the points are placed at relative to the grasp (the driver's get_standoff_pose(offset, axis));
+        ik_offset (4, 4) or None: the shelf driver solves IK to ``RT @ standoff`` (:256-259); world_to_base (B, 4, 4) or None:
+        the mobile driver's inv(RT_base); a grasp is kept when count / P <= max_ratio.  base_position is subtracted from the
+        goals (:254) and serves the chain as in ``plan_objects``, whose other keywords pass through.
+
+        gto_filter_grasps_device writes the goal sets ``plan_objects`` would be given (``utils.filter_grasp_sets`` computes
+        them on the host), and exactly its launches follow.  Added to its result: grasp_counts (B, n_max) (-1: a non-finite
+        row; rows beyond n_grasps are -1 too), grasp_keep (B, n_max), kept_rows (B, n_max) (the original row of a compacted
+        position, -1 beyond the kept ones), n_kept (B,) (0: no collision-free grasp, the driver's ``continue`` at :236; the
+        object is then solved to its row 0), grasp_row (B,): the ORIGINAL row of the grasp the plan was seeded from -- with
+        n_seeds > 1 of the grasp it reached --, -1 without a kept or an accepted grasp.  accept, q_solutions, err_pos and the
+        other per-candidate arrays are indexed by compacted position."""
+        from .observation import as_observation
+        torch = self._torch
+        object_poses = np.asarray(object_poses, dtype=np.float64).reshape(-1, 16)
+        B = object_poses.shape[0]
+        grasps = np.asarray(grasps, dtype=np.float64)
+        n_max = grasps.shape[1]
+        grasps = grasps.reshape(B, n_max, 16)
+        n_grasps = self._grasp_counts(n_grasps, B, n_max)
+        points = np.asarray(gripper_points, dtype=np.float64).reshape(-1, 3)
+        one = not isinstance(observations, (list, tuple))
+        obs = [as_observation(o) for o in ([observations] * B if one else observations)]
+        if len(obs) != B:
+            raise ValueError(f"observations: one entry for all objects or one per object ({B}), got {len(obs)}")
+        w2b = None if world_to_base is None else np.asarray(world_to_base, dtype=np.float64).reshape(B, 16)
+        f64, i32, u8 = torch.float64, torch.int32, torch.uint8
+
+        def feed(st, d_base):
+            d_op, d_gr = self._up("object_poses", object_poses, np.float64), self._up("grasps", grasps, np.float64)
+            d_n, d_pts = self._up("n_grasps_in", n_grasps, np.int32), self._up("gripper_points", points, np.float64)
+            d_w = None if w2b is None else self._up("world_to_base", w2b, np.float64)
+            d_ikg, d_pg = self._dev("ik_goals", (B, n_max, 16), f64), self._dev("plan_goals", (B, n_max, 16), f64)
+            d_ng, d_nk = self._dev("n_grasps", (B,), i32), self._dev("n_kept", (B,), i32)
+            d_fc, d_keep = self._dev("grasp_counts", (B, n_max), i32), self._dev("grasp_keep", (B, n_max), u8)
+            d_rows = self._dev("kept_rows", (B, n_max), i32)
+            d_ikg.zero_()  # positions behind an object's kept grasps are solved by IK and read by nobody: defined all the same
+            d_pg.zero_()
+            d_keep.zero_()
+            d_fc.fill_(-1)
+            d_rows.fill_(-1)
+            if B:
+                self._handle.filter_grasps_device(obs, n_max, d_pts.data_ptr(), points.shape[0], d_op.data_ptr(), d_gr.data_ptr(),
+                                                  d_n.data_ptr(), check_offset, ik_offset, None if d_w is None else d_w.data_ptr(),
+                                                  d_base.data_ptr(), max_ratio, d_fc.data_ptr(), d_keep.data_ptr(), d_rows.data_ptr(),
+                                                  d_nk.data_ptr(), d_ng.data_ptr(), d_pg.data_ptr(), d_ikg.data_ptr(), st)
+            return d_ikg, d_pg, d_ng, dict(grasp_counts=d_fc, grasp_keep=d_keep, kept_rows=d_rows, n_kept=d_nk)
+
+        kw = {k: p.default for k, p in inspect.signature(self.plan_objects).parameters.items() if p.default is not p.empty}
+        unknown = set(plan_objects_keywords) - set(kw)
+        if unknown:
+            raise TypeError(f"plan_grasps: unexpected keyword(s) {sorted(unknown)}")
+        kw.update(plan_objects_keywords)
+        res = self._plan(B, n_max, feed, qc, fields, base_position, **kw)
+        res.grasp_keep = res.grasp_keep.astype(bool)
+        rows = np.arange(B)
+        if int(kw["n_seeds"]) != 1:
+            pos = res.goal_row  # the compacted position of the grasp the plan reached
+        else:  # the seed's position among the accepted -> its compacted position
+            counted = res.accept & (np.arange(n_max)[None, :] < np.maximum(res.n_kept, 1)[:, None])
+            order = np.argsort(~counted, axis=1, kind="stable")  # the accepted positions first, in their order
+            pos = np.where(res.seed_index >= 0, order[rows, np.maximum(res.seed_index, 0)], -1)
+        known = (res.n_kept > 0) & (res.n_accepted > 0) & (pos >= 0)
+        res.grasp_row = np.where(known, res.kept_rows[rows, np.maximum(pos, 0)], -1).astype(np.int32)
+        return res
+
+    @staticmethod
+    def _grasp_counts(n_grasps, B, n_max):
+        n_grasps = np.ascontiguousarray(np.broadcast_to(np.asarray(n_grasps, dtype=np.int32), (B,)))
+        if B and (n_grasps.min() < 1 or n_grasps.max() > n_max):
+            raise ValueError("n_grasps must be in [1, n_max]")
+        return n_grasps
+
+    def _plan(self, B, n_max, feed, qc, fields, base_position, axis_standoff, use_standoff, interpolate, pos_tol, rot_tol_deg,
+              ik_collision_threshold, float32_solutions, observation, retime, n_seeds, max_points):
+        """What ``plan_objects`` and ``plan_grasps`` share: the chain from the goal sets on.  ``feed(stream, d_base)`` is called
+        on the chain's stream behind the uploads of scene ids, qc and base; it returns the device arrays ik_goals, plan_goals
+        (B, n_max, 16), n_grasps (B,) -- uploaded, or written by launches it enqueued -- and a dict of further device arrays
+        to bring back with the result."""
         K = int(n_seeds)
         multi = K != 1  # K slots per object, a slot being one instance of the solve
         torch, h, d = self._torch, self._handle, self.robot.desc
         ndof, T = d.ndof, self.T
-        ik_goals = np.asarray(ik_goals, dtype=np.float64)
-        B, n_max = ik_goals.shape[0], ik_goals.shape[1]
         if not 1 <= K <= 16 or B * K > 65535:
             raise ValueError("n_seeds must be in [1, 16] and B * n_seeds at most 65535")
-        ik_goals = ik_goals.reshape(B, n_max, 16)
-        plan_goals = np.asarray(plan_goals, dtype=np.float64).reshape(B, n_max, 16)
-        n_grasps = np.ascontiguousarray(np.broadcast_to(np.asarray(n_grasps, dtype=np.int32), (B,)))
-        if B and (n_grasps.min() < 1 or n_grasps.max() > n_max):
-            raise ValueError("n_grasps must be in [1, n_max]")
         qc = np.ascontiguousarray(np.broadcast_to(np.asarray(qc, dtype=np.float64).reshape(-1, ndof), (B, ndof)))
         base = np.ascontiguousarray(np.broadcast_to(np.asarray(base_position, dtype=np.float64).reshape(-1, 3), (B, 3)))
         sid = self._scene_ids(fields, B)
@@ -163,8 +260,7 @@ class GraspChain:
         with torch.cuda.stream(self.stream):
             st = self.stream.cuda_stream
             d_sid, d_qc, d_base = self._up("sid", sid, np.int32), self._up("qc", qc, np.float64), self._up("base", base, np.float64)
-            d_ikg, d_pg = self._up("ik_goals", ik_goals, np.float64), self._up("plan_goals", plan_goals, np.float64)
-            d_ng = self._up("n_grasps", n_grasps, np.int32)
+            d_ikg, d_pg, d_ng, extra = feed(st, d_base)
             # per candidate grasp: its object's scene, seed and base
             d_sid_ik = self._up("sid_ik", np.repeat(sid, n_max), np.int32)
             d_q0_ik = self._up("q0_ik", np.repeat(qc, n_max, axis=0), np.float64)
@@ -239,6 +335,7 @@ class GraspChain:
             out = dict(plans=d_Q, dQ=d_dQ, cost=d_f, iters=d_it, status=d_stat, n_accepted=d_nacc, seed_index=d_si, seed_cost=d_sc,
                        seed_dist=d_sd, q_solutions=d_q, err_pos=d_ep, err_rot=d_er, ik_cost=d_ic, ik_iters=d_ikit, ik_status=d_ikst,
                        accept=d_acc)
+            out.update(extra)
             if d_cnt is not None:
                 out["counts"] = d_cnt
             if N and retime is not None:

@@ -153,6 +153,72 @@ def grasp_collision_counts(gripper_model, cloud_or_obs, RT_grasps, q_gripper, RT
     return as_observation(cloud_or_obs).check_posed(pts, RT), int(pts.shape[0])
 
 
+def pose_product(A, B) -> np.ndarray:
+    """A @ B for 4x4 matrices (leading axes broadcast) as gto_filter_grasps_device forms it: the full product, entry (r, c) =
+    ((A_r0 B_0c + A_r1 B_1c) + A_r2 B_2c) + A_r3 B_3c, written with elementwise operations, which numpy does not fuse
+    (numpy.matmul goes through BLAS and promises no bits)."""
+    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+    a = lambda k: A[..., :, k, None]
+    b = lambda k: B[..., None, k, :]
+    return ((a(0) * b(0) + a(1) * b(1)) + a(2) * b(2)) + a(3) * b(3)
+
+
+def filter_grasp_sets(observations, gripper_points, object_poses, grasps, n_grasps, check_offset, ik_offset=None,
+                      world_to_base=None, base_position=None, max_ratio: float = 0.01):
+    """The driver's checking stage (examples/pybullet_gto_planning.py:203-236, examples/pybullet_gto_planning_mobile.py:
+    313-343) for B objects on the host, object by object: what gto_filter_grasps_device computes on the stream
+    (include/gto_solver.h), in numpy on top of ``Observation.check_posed``.
+
+    observations: one entry for all objects or one per object (an Observation, a DepthPointCloud or a SurfacePointCloud);
+    gripper_points (P, 3); object_poses (B, 4, 4); grasps (B, n_max, 4, 4) in the object frame; n_grasps (B,), read as
+    clamped to [1, n_max]; check_offset (4, 4); ik_offset (4, 4) or None; world_to_base (B, 4, 4) or None; base_position
+    (3,), (B, 3) or None.  Returns a dict: counts (B, n_max) int32 (-1: a non-finite row, and the rows beyond n_grasps),
+    keep (B, n_max) bool, kept_rows (B, n_max) int32 (-1 beyond the kept ones), n_kept (B,), n_grasps (B,) = max(n_kept, 1),
+    plan_goals and ik_goals (B, n_max, 4, 4): the kept rows' goals in their order, zeros behind them; an object without a
+    kept row holds row 0's goals at position 0."""
+    from .observation import as_observation
+    O = np.asarray(object_poses, dtype=np.float64).reshape(-1, 4, 4)
+    B = O.shape[0]
+    R = np.asarray(grasps, dtype=np.float64)
+    n_max = R.shape[1]
+    R = R.reshape(B, n_max, 4, 4)
+    pts = np.asarray(gripper_points, dtype=np.float64).reshape(-1, 3)
+    P = pts.shape[0]
+    one = not isinstance(observations, (list, tuple))
+    obs = [as_observation(o) for o in ([observations] * B if one else observations)]
+    n_in = np.clip(np.broadcast_to(np.asarray(n_grasps, dtype=np.int64), (B,)), 1, n_max)
+    W = None if world_to_base is None else np.asarray(world_to_base, dtype=np.float64).reshape(B, 4, 4)
+    base = None if base_position is None else np.broadcast_to(np.asarray(base_position, dtype=np.float64).reshape(-1, 3), (B, 3))
+    Sc = np.asarray(check_offset, dtype=np.float64).reshape(4, 4)
+    Si = None if ik_offset is None else np.asarray(ik_offset, dtype=np.float64).reshape(4, 4)
+    out = dict(counts=np.full((B, n_max), -1, np.int32), keep=np.zeros((B, n_max), bool), kept_rows=np.full((B, n_max), -1, np.int32),
+               n_kept=np.zeros(B, np.int32), n_grasps=np.ones(B, np.int32), plan_goals=np.zeros((B, n_max, 4, 4)),
+               ik_goals=np.zeros((B, n_max, 4, 4)))
+    for b in range(B):
+        n = int(n_in[b])
+        with np.errstate(all="ignore"):
+            G = pose_product(O[b], R[b, :n])
+            if W is not None:
+                G = pose_product(W[b], G)
+            Cm = pose_product(G, Sc)
+            A = G.copy()
+            if base is not None:
+                A[:, :3, 3] = G[:, :3, 3] - base[b]
+            ik = A if Si is None else pose_product(A, Si)
+        bad = ~(np.isfinite(O[b]).all() & np.isfinite(R[b, :n]).all(axis=(1, 2)) & np.isfinite(Cm).all(axis=(1, 2)))
+        if W is not None:
+            bad |= ~np.isfinite(W[b]).all()
+        counts = np.where(bad, -1, obs[b].check_posed(pts, Cm)).astype(np.int32)
+        keep = (counts >= 0) & (counts.astype(np.float64) / float(P) <= max_ratio)
+        rows = np.flatnonzero(keep)
+        out["counts"][b, :n], out["keep"][b, :n] = counts, keep
+        out["n_kept"][b], out["n_grasps"][b] = len(rows), max(len(rows), 1)
+        out["kept_rows"][b, :len(rows)] = rows
+        take = rows if len(rows) else np.array([0])
+        out["plan_goals"][b, :len(take)], out["ik_goals"][b, :len(take)] = A[take], ik[take]
+    return out
+
+
 def _retime_handle(robot, T: int):
     """The robot's utility handle for horizon T (retiming and the plan checks only read the handle's T and the robot)."""
     from . import _capi

@@ -772,6 +772,60 @@ int gto_select_plans_device(gto_handle* h, int32_t B, int32_t n_seeds, const int
                             double rot_tol_deg, int32_t max_points, const double* Q, const double* dQ, int32_t* best_slot_out,
                             int32_t* class_out, double* Q_out, double* dQ_out, void* stream);
 
+/*
+ * ---- the grasp collision filter on the stream (the driver's checking stage, examples/pybullet_gto_planning.py:203-236) -------
+ * Object poses and object-frame grasps go in; the compacted, base-frame goal sets come out in the layout
+ * gto_solve_ik_pose_batch_device (ik_goals_out) and gto_seed_goalsets_device (plan_goals_out as goals, n_grasps_out as n_goals)
+ * take; every object is tested against its own observation.  An addition (the ABI number stays).  Enqueued on `stream` (NULL =
+ * the handle's stream) without a host synchronisation; what is validated are host-side facts only.  It reads no kinematics and
+ * works on every handle, whatever its number of optimised joints.
+ *   host arguments (read during the call, free on return)
+ *     obs [B]            the observation object b is tested against; entries may repeat, depth and cloud observations may be
+ *                        mixed; they must outlive the enqueued work
+ *     check_offset [16]  the pose the gripper's points are placed at, relative to the grasp (get_standoff_pose(offset, axis))
+ *     ik_offset [16] or NULL   the shelf driver's RT @ standoff for IK (:256-259)
+ *   device arguments
+ *     points [P][3]      the open gripper's surface points in the frame the poses place
+ *     object_pose [B][16], grasps [B][n_max][16] (object frame), n_grasps [B] (a value < 1 or > n_max is read as clamped to
+ *     [1, n_max]: it lives on the device), world_to_base [B][16] or NULL (the mobile driver's inv(RT_base)), base_pos [B][3]
+ *     or NULL, and every output; any output may be NULL; outputs must not overlap inputs
+ *   per object b and row i < n_grasps[b]
+ *     G = object_pose_b grasp_bi; with world_to_base G = W_b G (the association order of the mobile driver, :313-343)
+ *     C = G check_offset; the P points are placed as x = R p + t of C with gto_observation_check_posed's expression, term for
+ *     term (the products added in the order x, z, y, then the translation, without contraction)
+ *     count_out [b][i]   how many of the placed points are inside obs[b] ("inside" as for gto_observation_check_posed); -1 when
+ *                        object_pose_b, grasp_bi or W_b holds a non-finite entry (or C overflows to one), which changes no
+ *                        other row
+ *     keep_out [b][i]    count >= 0 && (double)count / (double)P <= max_ratio, the division in FP64: the driver's
+ *                        "ratio > 0.01 -> in collision"; with P = 100 and max_ratio = 0.01 one point inside is kept, as in numpy
+ *     plan goal          A = G with A[r][3] = G[r][3] - base_pos[b][r], r < 3 (:254); unchanged with base_pos NULL
+ *     IK goal            A ik_offset; A with ik_offset NULL
+ *     rows >= n_grasps[b] are left untouched in count_out and keep_out
+ *   products   every product is the full 4x4 product in FP64 without contraction, entry (r, c) =
+ *              ((A_r0 B_0c + A_r1 B_1c) + A_r2 B_2c) + A_r3 B_3c (utils.pose_product restates it; numpy.matmul goes through
+ *              BLAS and promises no bits)
+ *   compaction the kept rows, in their order, to plan_goals_out [b][0..n_kept) and ik_goals_out [b][0..n_kept), both
+ *              [B][n_max][16]; kept_rows_out [b][j] = the original row of position j; positions >= n_kept are left untouched;
+ *              n_kept_out [b] = the true count (may be 0), n_grasps_out [b] = max(n_kept, 1).  No row kept: position 0 gets
+ *              row 0's two goals and kept_rows_out [b][0] = -1: the object stays solvable by the chain and n_kept_out tells
+ *              the caller that it had no collision-free grasp (the driver's `continue`, :236), as n_accepted_out does.
+ * Depth observations take one launch over all their objects (each workgroup reads its object's image from a table copied in
+ * front of the launch through pinned memory of the handle); every run of consecutive objects that name one cloud observation
+ * takes the launch chain of gto_observation_check_posed, at most 2^24 queries at a time.  Every row's and every object's
+ * result is bit for bit the same in any batch and at any position in it.
+ * GTO_ERR_INVALID_ARG: null handle; B < 0, n_max < 1, P < 1, a non-finite or negative max_ratio; null obs, entry of obs,
+ * points, object_pose, grasps, n_grasps or check_offset; a non-finite entry of check_offset / ik_offset; an observation on
+ * another device than the handle's.  GTO_ERR_UNSUPPORTED: B or n_max above 65535.  B = 0: GTO_OK without a launch.  The
+ * workspace lives on the handle: calls on one handle go to one stream, or the caller orders them (the rule of
+ * gto_check_plans_device).
+ */
+int gto_filter_grasps_device(gto_handle* h, int32_t B, int32_t n_max, gto_observation* const* obs, const double* points,
+                             int32_t P, const double* object_pose, const double* grasps, const int32_t* n_grasps,
+                             const double* world_to_base, const double* base_pos, const double* check_offset,
+                             const double* ik_offset, double max_ratio, int32_t* count_out, uint8_t* keep_out,
+                             int32_t* kept_rows_out, int32_t* n_kept_out, int32_t* n_grasps_out, double* plan_goals_out,
+                             double* ik_goals_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
