@@ -522,6 +522,13 @@ class SolverHandle:
             out[name] = (ms.value, n.value, wg.value, pts.value)
         return out
 
+    def last_seed_test_profile(self):
+        """(ms, launches, workgroups) of k_seed_broad in the last profiled solve: the seeds of the instances that waited for a
+        slot, tested against the distance field once per call (no launch: the call had no such instance, or no broad phase)."""
+        ms, n, wg, pts = C.c_double(), C.c_int32(), C.c_uint64(), C.c_uint64()
+        self._check(self.lib.gto_last_kernel_profile(self._h, 4, C.byref(ms), C.byref(n), C.byref(wg), C.byref(pts)), "gto_last_kernel_profile")
+        return ms.value, n.value, wg.value
+
     # -------------------------------------------------------------- evaluation entry points
     def eval_fk(self, q):
         q = _f64(q).reshape(-1, self.desc.ndof)

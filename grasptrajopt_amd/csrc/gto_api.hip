@@ -78,6 +78,7 @@ struct Tunables {
   int static_pos = 1;  // GTO_STATIC_POS=0: every instance draws its list positions from the counters in every round
   int pb_merge = 4;  // GTO_PB_MERGE: chunks of a link under one sphere of the step kernel's broad phase
   int prebroad = 1;  // GTO_PREBROAD=0: every (job, group) gets a workgroup of the obstacle kernel in every round
+  int seed_pb = 1;   // GTO_SEED_PB=0: nothing is known about the seed of an instance that takes over a slot, and every group of it is listed (k_seed_broad)
   double pb_min_gain = 0.10;  // GTO_PB_MIN_GAIN: a call whose step-kernel broad phase settles less than this share of the groups stops running it
   int obs_tg = 3;  // GTO_OBS_TG: waypoints per workgroup of the obstacle kernel: they share the table staging, the FK barriers and the launch overhead
   int obs_tg_few = 2;  // GTO_OBS_TG_FEW: ... when few instances are in flight (one small batch, the tail of a call): lower latency per round; results do not depend on the group size
@@ -115,6 +116,7 @@ static void read_tunables(Tunables& t) {
       {"GTO_SPEC_FEW", &Tunables::spec_few, nullptr, nullptr, 0, BIG},
       {"GTO_OBS_DEEP", &Tunables::obs_deep, nullptr, nullptr, 0, 1},
       {"GTO_PREBROAD", &Tunables::prebroad, nullptr, nullptr, 0, 1},
+      {"GTO_SEED_PB", &Tunables::seed_pb, nullptr, nullptr, 0, 1},
       {"GTO_PB_MERGE", &Tunables::pb_merge, nullptr, nullptr, 1, BIG},
       {"GTO_STATIC_POS", &Tunables::static_pos, nullptr, nullptr, 0, 1},
       {"GTO_OBS_INTERLEAVE", &Tunables::obs_interleave, nullptr, nullptr, 0, 2},
@@ -175,7 +177,7 @@ struct gto_handle {
   DevBuf scenes_buf;  // the table on the device
   SceneDev* d_scenes = nullptr;  // ... as the launches take it (sync_scene_table)
   // solve workspace (grown on demand)
-  DevBuf state, Qcur, Qtry, vis, screw, blocks, goalblk, ssfixed, ndone, qf, livebuf, qfs, wrecbuf, itembuf;
+  DevBuf state, Qcur, Qtry, vis, screw, blocks, goalblk, ssfixed, ndone, qf, livebuf, qfs, wrecbuf, itembuf, seedmask;
   DevBuf counters;  // work counters of a profiled solve
   unsigned long long last_counters[4] = {0, 0, 0, 0};
   PinBuf h_ndone;
@@ -205,9 +207,9 @@ struct gto_handle {
   double last_ms = 0.0;
   int last_launches = 0;
   // per kernel variant of the last profiled solve: milliseconds, launches, workgroups launched, surface points gathered
-  double prof_ms[GTO_PROF_VARIANTS] = {0, 0, 0, 0};
-  long long prof_launches[GTO_PROF_VARIANTS] = {0, 0, 0, 0}, prof_wgs[GTO_PROF_VARIANTS] = {0, 0, 0, 0};
-  unsigned long long prof_points[GTO_PROF_VARIANTS] = {0, 0, 0, 0};
+  double prof_ms[GTO_PROF_VARIANTS] = {};
+  long long prof_launches[GTO_PROF_VARIANTS] = {}, prof_wgs[GTO_PROF_VARIANTS] = {};
+  unsigned long long prof_points[GTO_PROF_VARIANTS] = {};
   size_t lm_lds = 0;
   int np = GTO_NB;     // block width of the normal equations: 8 (up to eight optimised joints) or 16
   DevBuf zws;          // k_lm_step_wide: block inverses [slots][T-2][np*np]
@@ -819,6 +821,7 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
   for (int v = 0; v < 8 && e == hipSuccess; ++v) e = raise_dynamic_lds((const void*)obstacle_kernel(np, v & 1, v & 2, v & 4), lds);
   if (e == hipSuccess) e = wide ? raise_dynamic_lds((const void*)k_lm_step_wide<16>, lm_lds) : raise_dynamic_lds((const void*)k_lm_step<4, 1>, lm_lds);
   if (e == hipSuccess && !wide) e = raise_dynamic_lds((const void*)k_lm_step<8, GTO_KSPEC>, lm_lds_bytes(opts->T, spec_kmax));
+  if (e == hipSuccess && !wide) e = raise_dynamic_lds((const void*)k_seed_broad, lm_lds);
   if (e != hipSuccess) { gto_destroy(h); return fail(nullptr, GTO_ERR_HIP, "hipFuncSetAttribute failed"); }
   *out = h;
   return GTO_OK;
@@ -1187,6 +1190,7 @@ static int ensure_workspace(gto_handle* h, int B) {
   if ((rc = ensure(h, h->ndone, 64 * GTO_MAX_LANES))) return rc;  // a finished-counter per lane, a cache line apart
   if ((rc = ensure(h, h->qf, (size_t)B * T * rb.n_frames * sizeof(double)))) return rc;
   if ((rc = ensure(h, h->wrecbuf, (size_t)(kcap + 1) * B * T * 8 * sizeof(double)))) return rc;
+  if ((rc = ensure(h, h->seedmask, (size_t)B * sizeof(unsigned long long)))) return rc;
   if (!h->h_ndone) HIPCHK(h, pinned_alloc(h->h_ndone, 64));
   if (!h->h_progress) {
     HIPCHK(h, pinned_alloc(h->h_progress, 64 * GTO_MAX_LANES, hipHostMallocMapped));  // eight words per lane
@@ -1341,6 +1345,7 @@ struct LaneCtx {
   int span_prev = 0;                  // static positions: positions the current lists span (the last one-candidate launch's grid), 0: compact lists
   int n_resp = 0;                     // instances whose end this lane's finished-counter counts (own + adopted)
   int k = 0, known_done = 0, seen_round = -1, k_prev = 1;
+  int last_plain = -1;                // the last round whose obstacle launch was not itemized (the length it published is no list's: 0)
   bool items_ready = false, pb_off = false, handed = false;
   double ratio_max = 0.0;  // items per job, the largest the lane's rounds published
   long end_us = 0, few_us = 0;  // (GTO_LANE_DEBUG) when the lane's thread returned / enqueued its first few-instance round, from the start of the threads
@@ -1458,6 +1463,23 @@ static int setup_lanes(gto_handle* h, hipStream_t st, SolveParams& sp, BatchPtrs
   return GTO_OK;
 }
 
+// The seeds of the instances that wait for a slot, tested against the distance field once, behind the init pass (k_seed_broad
+// needs ss_fixed and qf): lanes with more instances than slots whose full rounds run the step kernel's broad phase
+// (plan_round's pb_ok).  A call without such a lane launches nothing and keeps null masks: every group of a seed is listed.
+static int test_waiting_seeds(gto_handle* h, hipStream_t st, SolveCall& c) {
+  if (!c.pb_able || !h->tu.seed_pb) return GTO_OK;
+  for (int l = 0; l < c.L; ++l) {
+    LaneCtx& ln = c.lanes[l];
+    if (ln.n <= ln.W || ln.W <= h->tu.few_instances) continue;
+    int rc;
+    if (h->profiling && (rc = prof_begin(h, st, GTO_PROF_SEED_TEST, ln.n - ln.W))) return rc;
+    hipLaunchKernelGGL(k_seed_broad, dim3(ln.n - ln.W), dim3(256), h->lm_lds, st, h->d_rb, ln.bp, ln.sp, c.B, h->seedmask.as<unsigned long long>());
+    if (h->profiling && (rc = prof_end(h, st))) return rc;
+    ln.bp.seed_mask = h->seedmask.as<unsigned long long>();
+  }
+  return GTO_OK;
+}
+
 // A round of a lane: one obstacle launch that evaluates the candidate trial trajectories of the instances in flight, one
 // step launch that accepts, solves and makes new candidates.
 enum StepVariant { STEP_FULL, STEP_FEW, STEP_WIDE };  // k_lm_step<4, 1>, k_lm_step<8, GTO_KSPEC>, k_lm_step_wide<16>
@@ -1503,7 +1525,11 @@ static RoundPlan plan_round(const gto_handle* h, const SolveCall& c, const LaneC
   if (o.itemized && tu.item_grid) {
     const unsigned long long p2 = __atomic_load_n(ln.h_prog + 2, __ATOMIC_RELAXED);
     const int jobs_bound = p.in_flight * ln.k_prev;
-    if ((unsigned)(p2 >> 32) == h->progress_tag && (p2 & 0xfffffull) > 0 && (p2 & 0xfffffull) < 0xfffffull) {
+    // (a published 0 is a list's length only if the launch that published it was itemized: the word is that of round
+    // seen_round - 1 at the earliest.  A call whose seeds k_seed_broad settled whole and whose instances stay clear of
+    // the field has empty lists round after round, and its launches are laid out over the estimate's floor, not the bound)
+    const bool zero_ok = ln.last_plain < ln.seen_round - 1;
+    if ((unsigned)(p2 >> 32) == h->progress_tag && ((p2 & 0xfffffull) > 0 || zero_ok) && (p2 & 0xfffffull) < 0xfffffull) {
       const double items_seen = (double)(p2 & 0xfffffull), jobs_seen = (double)((p2 >> 20) & 0xfffull);
       o.items_hint = (int)(1.5 * items_seen) + 256;
       if (jobs_seen > 0 && jobs_seen < 4095) p.ratio_max = std::max(p.ratio_max, items_seen / jobs_seen);
@@ -1566,6 +1592,7 @@ static int enqueue_round(gto_handle* h, const SolveCall& c, LaneCtx& ln, int lan
   }
   if (h->profiling && (rc = prof_end(h, ln.st))) return rc;
   ln.span_prev = p.static_pos ? p.span : 0;
+  if (!p.obs.itemized) ln.last_plain = ln.k;
   ln.items_ready = p.pb_next;
   ln.k_prev = p.k_next;
   ln.pb_off = p.pb_off;
@@ -1868,6 +1895,7 @@ int gto_solve_batch_device(gto_handle* h, int32_t B, int32_t n_max, const int32_
   for (int l = 0; l < L; ++l)  // seeds, goal terms of the seeds, the lane's lists of round 0
     hipLaunchKernelGGL(lm_init_kernel(h->np), dim3(c.lanes[l].n), dim3(256), 0, st, h->d_rb, c.lanes[l].bp, c.lanes[l].sp, B, 0);
   if ((rc = launch_obstacle(h, st, bp, sp, B, init_pass()))) return rc;  // (the init pass indexes the batch directly)
+  if ((rc = test_waiting_seeds(h, st, c))) return rc;
   if (L > 1) {
     HIPCHK(h, hipEventRecord(h->lane_event[0], st));
     for (int l = 0; l < L; ++l) HIPCHK(h, hipStreamWaitEvent(c.lanes[l].st, h->lane_event[0], 0));

@@ -336,7 +336,8 @@ int gto_last_kernel_work(gto_handle* h, uint64_t* points_gathered, uint64_t* chu
 #define GTO_PROF_OBSTACLE_FEW 1  /* k_obstacle_gram<8,8>: launches with few instances in flight */
 #define GTO_PROF_STEP 2          /* k_lm_step<4,1> (k_lm_step_wide for nine to sixteen optimised joints) */
 #define GTO_PROF_STEP_FEW 3      /* k_lm_step<8,4>: few instances in flight, candidate trial points */
-#define GTO_PROF_VARIANTS 4
+#define GTO_PROF_SEED_TEST 4     /* k_seed_broad: the seeds of the instances that wait for a slot, once per call (none: 0 launches) */
+#define GTO_PROF_VARIANTS 5
 int gto_last_kernel_profile(gto_handle* h, int32_t variant, double* total_ms, int32_t* launches, uint64_t* workgroups,
                             uint64_t* points_gathered);
 /* Enable/disable per-launch event timing of the solve loop's kernels (off by default). */
