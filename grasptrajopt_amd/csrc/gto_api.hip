@@ -79,6 +79,11 @@ struct Tunables {
   int pb_merge = 4;  // GTO_PB_MERGE: chunks of a link under one sphere of the step kernel's broad phase
   int prebroad = 1;  // GTO_PREBROAD=0: every (job, group) gets a workgroup of the obstacle kernel in every round
   int seed_pb = 1;   // GTO_SEED_PB=0: nothing is known about the seed of an instance that takes over a slot, and every group of it is listed (k_seed_broad)
+  int seed_pb_all = 1;  // GTO_SEED_PB_ALL=0: the seeds that start in a slot are not tested, and round 0's obstacle launch looks at every group of them
+  // GTO_INIT_DEDUP=0: every instance of a solve call runs the init pass itself.  Otherwise the init pass of a call runs once per
+  // run of equal start states (k_init_heads, k_ss_fixed_spread) when it is more than init_dedup_min workgroups
+  // (GTO_INIT_DEDUP_MIN; four per instance): up to one wave of workgroups, 1280, the two small launches cost more than they save
+  int init_dedup = 1, init_dedup_min = 1280;
   double pb_min_gain = 0.10;  // GTO_PB_MIN_GAIN: a call whose step-kernel broad phase settles less than this share of the groups stops running it
   int obs_tg = 3;  // GTO_OBS_TG: waypoints per workgroup of the obstacle kernel: they share the table staging, the FK barriers and the launch overhead
   int obs_tg_few = 2;  // GTO_OBS_TG_FEW: ... when few instances are in flight (one small batch, the tail of a call): lower latency per round; results do not depend on the group size
@@ -117,6 +122,9 @@ static void read_tunables(Tunables& t) {
       {"GTO_OBS_DEEP", &Tunables::obs_deep, nullptr, nullptr, 0, 1},
       {"GTO_PREBROAD", &Tunables::prebroad, nullptr, nullptr, 0, 1},
       {"GTO_SEED_PB", &Tunables::seed_pb, nullptr, nullptr, 0, 1},
+      {"GTO_SEED_PB_ALL", &Tunables::seed_pb_all, nullptr, nullptr, 0, 1},
+      {"GTO_INIT_DEDUP", &Tunables::init_dedup, nullptr, nullptr, 0, 1},
+      {"GTO_INIT_DEDUP_MIN", &Tunables::init_dedup_min, nullptr, nullptr, 0, BIG},
       {"GTO_PB_MERGE", &Tunables::pb_merge, nullptr, nullptr, 1, BIG},
       {"GTO_STATIC_POS", &Tunables::static_pos, nullptr, nullptr, 0, 1},
       {"GTO_OBS_INTERLEAVE", &Tunables::obs_interleave, nullptr, nullptr, 0, 2},
@@ -177,7 +185,7 @@ struct gto_handle {
   DevBuf scenes_buf;  // the table on the device
   SceneDev* d_scenes = nullptr;  // ... as the launches take it (sync_scene_table)
   // solve workspace (grown on demand)
-  DevBuf state, Qcur, Qtry, vis, screw, blocks, goalblk, ssfixed, ndone, qf, livebuf, qfs, wrecbuf, itembuf, seedmask;
+  DevBuf state, Qcur, Qtry, vis, screw, blocks, goalblk, ssfixed, ndone, qf, livebuf, qfs, wrecbuf, itembuf, seedmask, inithead;
   DevBuf counters;  // work counters of a profiled solve
   unsigned long long last_counters[4] = {0, 0, 0, 0};
   PinBuf h_ndone;
@@ -1191,6 +1199,7 @@ static int ensure_workspace(gto_handle* h, int B) {
   if ((rc = ensure(h, h->qf, (size_t)B * T * rb.n_frames * sizeof(double)))) return rc;
   if ((rc = ensure(h, h->wrecbuf, (size_t)(kcap + 1) * B * T * 8 * sizeof(double)))) return rc;
   if ((rc = ensure(h, h->seedmask, (size_t)B * sizeof(unsigned long long)))) return rc;
+  if ((rc = ensure(h, h->inithead, (size_t)B * sizeof(int32_t)))) return rc;
   if (!h->h_ndone) HIPCHK(h, pinned_alloc(h->h_ndone, 64));
   if (!h->h_progress) {
     HIPCHK(h, pinned_alloc(h->h_progress, 64 * GTO_MAX_LANES, hipHostMallocMapped));  // eight words per lane
@@ -1276,10 +1285,11 @@ struct ObsLaunch {
   bool deep = false;        // the variant with deep gather batches (few instances in flight)
   bool itemized = false;    // the regular workgroups walk the step kernel's list of (job, group) pairs
   int items_hint = 0;       // estimate of that list's length (0: its upper bound)
+  const int32_t* rep = nullptr;  // the init pass: the instance whose start state instance b shares (k_init_heads; null: every instance computes)
 };
-static ObsLaunch init_pass() {
+static ObsLaunch init_pass(const int32_t* rep = nullptr) {
   ObsLaunch o;
-  o.t_begin = 0, o.nT = 4, o.fixed_mode = 1;
+  o.t_begin = 0, o.nT = 4, o.fixed_mode = 1, o.rep = rep;
   return o;
 }
 
@@ -1313,7 +1323,7 @@ static int launch_obstacle(gto_handle* h, hipStream_t st, const BatchPtrs& bp, c
   // rounds behind a step kernel that ran the broad phase itself: the regular workgroups are laid out over its list of (job, group) pairs
   const size_t items_cap = (size_t)bp.cap * sp.kcap * (sp.T - 2) + GTO_ITEM_SLACK;
   const int2* items_par = listed && o.itemized ? bp.items + (size_t)sp.parity * items_cap : nullptr;
-  const int32_t* nitems_par = listed && o.itemized ? bp.nlive + 8 + sp.parity : nullptr;
+  const int32_t* nitems_par = listed && o.itemized ? bp.nlive + 8 + sp.parity : (o.fixed_mode ? o.rep : nullptr);  // (the init pass has no list: rep[] rides here)
   const bool hot = !o.fixed_mode && sp.grad_mode == GTO_GRAD_CENTRAL_DIFF;
   hipLaunchKernelGGL(obstacle_kernel(h->np, o.deep, sweep, hot), grid, dim3(256), lds, st, jobs_par, njobs_par, items_par, nitems_par, geo.nG, geo.m_nG, n_regular, B,
                      h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes, bpl, sp, o.t_begin, o.nT, o.fixed_mode, geo, n_crew);
@@ -1347,6 +1357,7 @@ struct LaneCtx {
   int k = 0, known_done = 0, seen_round = -1, k_prev = 1;
   int last_plain = -1;                // the last round whose obstacle launch was not itemized (the length it published is no list's: 0)
   bool items_ready = false, pb_off = false, handed = false;
+  bool seed_round0 = false;           // round 0 is itemized from the seed test: the length it publishes is a list's, but of seeds
   double ratio_max = 0.0;  // items per job, the largest the lane's rounds published
   long end_us = 0, few_us = 0;  // (GTO_LANE_DEBUG) when the lane's thread returned / enqueued its first few-instance round, from the start of the threads
   unsigned long long* h_prog = nullptr;
@@ -1463,6 +1474,19 @@ static int setup_lanes(gto_handle* h, hipStream_t st, SolveParams& sp, BatchPtrs
   return GTO_OK;
 }
 
+// The init pass of a solve call, behind k_lm_init (it indexes the batch directly): ss_fixed of every instance.  A call whose
+// init pass is more than init_dedup_min workgroups runs it once per run of equal start states: k_init_heads names every
+// instance's representative, the workgroups of the others leave at once, k_ss_fixed_spread hands them the four numbers.
+static int run_init_pass(gto_handle* h, hipStream_t st, const BatchPtrs& bp, const SolveParams& sp, int B) {
+  if (!h->tu.init_dedup || 4 * (long long)B <= h->tu.init_dedup_min) return launch_obstacle(h, st, bp, sp, B, init_pass());
+  int32_t* rep = h->inithead.as<int32_t>();
+  hipLaunchKernelGGL(k_init_heads, dim3((B + 255) / 256), dim3(256), 0, st, h->d_rb, bp, sp.T, B, rep);
+  const int rc = launch_obstacle(h, st, bp, sp, B, init_pass(rep));
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_ss_fixed_spread, dim3((B + 255) / 256), dim3(256), 0, st, bp, B, rep);
+  return GTO_OK;
+}
+
 // The seeds of the instances that wait for a slot, tested against the distance field once, behind the init pass (k_seed_broad
 // needs ss_fixed and qf): lanes with more instances than slots whose full rounds run the step kernel's broad phase
 // (plan_round's pb_ok).  A call without such a lane launches nothing and keeps null masks: every group of a seed is listed.
@@ -1473,9 +1497,19 @@ static int test_waiting_seeds(gto_handle* h, hipStream_t st, SolveCall& c) {
     if (ln.n <= ln.W || ln.W <= h->tu.few_instances) continue;
     int rc;
     if (h->profiling && (rc = prof_begin(h, st, GTO_PROF_SEED_TEST, ln.n - ln.W))) return rc;
-    hipLaunchKernelGGL(k_seed_broad, dim3(ln.n - ln.W), dim3(256), h->lm_lds, st, h->d_rb, ln.bp, ln.sp, c.B, h->seedmask.as<unsigned long long>());
+    hipLaunchKernelGGL(k_seed_broad, dim3(ln.n - ln.W), dim3(256), h->lm_lds, st, h->d_rb, ln.bp, ln.sp, c.B, h->seedmask.as<unsigned long long>(), 0);
     if (h->profiling && (rc = prof_end(h, st))) return rc;
     ln.bp.seed_mask = h->seedmask.as<unsigned long long>();
+    // ... and the seeds that start in a slot, which lists what is left of them for round 0: that round is then planned as
+    // an itemized launch like every full round behind it (plan_round: the estimate is the previous call's items per job,
+    // or the upper bound).  The length round 0 publishes is a list of SEEDS: it says nothing about the lists of trial
+    // points behind it (a Fetch whose seed rests in front of the shelf lists a fifth of what it lists eight rounds later,
+    // and a crew of 64 walked the rest of a launch laid out over 1.5 x that: 3.1 ms for one round), so no estimate is taken
+    // from it (seed_round0), as none was taken from the 0 a plain round 0 publishes
+    if (h->tu.seed_pb_all) {
+      hipLaunchKernelGGL(k_seed_broad, dim3(ln.W), dim3(256), h->lm_lds, st, h->d_rb, ln.bp, ln.sp, c.B, h->seedmask.as<unsigned long long>(), 1);
+      ln.items_ready = ln.seed_round0 = true;
+    }
   }
   return GTO_OK;
 }
@@ -1529,7 +1563,8 @@ static RoundPlan plan_round(const gto_handle* h, const SolveCall& c, const LaneC
     // seen_round - 1 at the earliest.  A call whose seeds k_seed_broad settled whole and whose instances stay clear of
     // the field has empty lists round after round, and its launches are laid out over the estimate's floor, not the bound)
     const bool zero_ok = ln.last_plain < ln.seen_round - 1;
-    if ((unsigned)(p2 >> 32) == h->progress_tag && ((p2 & 0xfffffull) > 0 || zero_ok) && (p2 & 0xfffffull) < 0xfffffull) {
+    const bool of_seeds = ln.seed_round0 && ln.seen_round < 2;  // (the word may still be round 0's)
+    if ((unsigned)(p2 >> 32) == h->progress_tag && ((p2 & 0xfffffull) > 0 || zero_ok) && !of_seeds && (p2 & 0xfffffull) < 0xfffffull) {
       const double items_seen = (double)(p2 & 0xfffffull), jobs_seen = (double)((p2 >> 20) & 0xfffull);
       o.items_hint = (int)(1.5 * items_seen) + 256;
       if (jobs_seen > 0 && jobs_seen < 4095) p.ratio_max = std::max(p.ratio_max, items_seen / jobs_seen);
@@ -1894,7 +1929,7 @@ int gto_solve_batch_device(gto_handle* h, int32_t B, int32_t n_max, const int32_
   const int L = c.L;
   for (int l = 0; l < L; ++l)  // seeds, goal terms of the seeds, the lane's lists of round 0
     hipLaunchKernelGGL(lm_init_kernel(h->np), dim3(c.lanes[l].n), dim3(256), 0, st, h->d_rb, c.lanes[l].bp, c.lanes[l].sp, B, 0);
-  if ((rc = launch_obstacle(h, st, bp, sp, B, init_pass()))) return rc;  // (the init pass indexes the batch directly)
+  if ((rc = run_init_pass(h, st, bp, sp, B))) return rc;
   if ((rc = test_waiting_seeds(h, st, c))) return rc;
   if (L > 1) {
     HIPCHK(h, hipEventRecord(h->lane_event[0], st));
@@ -2446,7 +2481,7 @@ static int eval_common(gto_handle* h, int B, int n_max, const int32_t* scene_id,
   BatchPtrs bp = make_ptrs(h, d_sid, d_qc, d_goals, d_ng, d_so, d_base, d_Q0);
   HIPCHK(h, hipMemsetAsync(bp.n_done, 0, sizeof(int32_t), h->stream));
   hipLaunchKernelGGL(lm_init_kernel(h->np), dim3(B), dim3(256), 0, h->stream, h->d_rb, bp, sp, B, 1 /* raw: evaluate Q as given */);
-  if ((rc = launch_obstacle(h, h->stream, bp, sp, B, init_pass()))) return rc;
+  if ((rc = run_init_pass(h, h->stream, bp, sp, B))) return rc;
   h->last_launches = 0;
   ObsLaunch ev;
   ev.nT = (int)T - 2, ev.timed = h->profiling;
