@@ -152,6 +152,12 @@ def _prototypes():
         "gto_plan_report_device": (I, [V, I32, I32] + [V] * 9),
         "gto_select_plans_device": (I, [V, I32, I32] + [V] * 5 + [D, D, I32] + [V] * 7),
         "gto_filter_grasps_device": (I, [V, I32, I32, PV, V, I32] + [V] * 5 + [_pd, _pd, D] + [V] * 8),
+        "gto_retrieve_lift_device": (I, [V, I32, V, V, V, _pd, D, I32, _pi, _pd, I32, I32, D, D] + [V] * 8),
+        "gto_retrieve_lift": (I, [V, I32, _pd, _pi, _pd, _pd, D, I32, _pi, _pd, I32, I32, D, D, _pd, _pd, _pd, _pd, _pi, _pi, _pi]),
+        "gto_retrieve_reverse_device": (I, [V, I32, V, _pi, _pd, I32, V, _pi, V]),
+        "gto_retrieve_path_columns": (I, [V]),
+        "gto_check_paths": (I, [V, V, I32, I32, _pd, _pd, I32, _pi]),
+        "gto_check_paths_device": (I, [V, V, I32, I32, V, _pd, I32, V, V]),
     }
 
 
@@ -801,6 +807,81 @@ class SolverHandle:
         base, per_plan = self._check_base(base_pos, int(B))
         self._check(self.lib.gto_check_plans_device(self._h, obs._ptr(), int(B), _vp(plans), _p(base, _pd), per_plan, _vp(count_out),
                                                     _vp(stream)), "gto_check_plans_device")
+
+    def check_paths(self, obs, paths, base_pos=(0.0, 0.0, 0.0)):
+        """gto_check_paths: check_plans for paths (B, ndof, Tp) of any length Tp >= 1; int32 (B, Tp)."""
+        paths = _f64(paths)
+        if paths.ndim != 3 or paths.shape[1] != self.desc.ndof or paths.shape[2] < 1:
+            raise GTOError(f"check_paths: paths must have shape (B, {self.desc.ndof}, Tp >= 1); got {paths.shape}")
+        B, Tp = paths.shape[0], paths.shape[2]
+        base, per_plan = self._check_base(base_pos, B)
+        count = np.empty((B, Tp), dtype=np.int32)
+        self._check(self.lib.gto_check_paths(self._h, obs._ptr(), B, Tp, _p(paths, _pd), _p(base, _pd), per_plan, _p(count, _pi)),
+                    "gto_check_paths")
+        return count
+
+    def check_paths_device(self, obs, B, Tp, paths, count_out, base_pos=(0.0, 0.0, 0.0), stream=None):
+        """gto_check_paths_device: check_plans_device with the number of columns Tp given: paths (B, ndof, Tp) float64 and
+        count_out (B, Tp) int32 are device pointers."""
+        base, per_plan = self._check_base(base_pos, int(B))
+        self._check(self.lib.gto_check_paths_device(self._h, obs._ptr(), int(B), int(Tp), _vp(paths), _p(base, _pd), per_plan,
+                                                    _vp(count_out), _vp(stream)), "gto_check_paths_device")
+
+    # -------------------------------------------------------------- the motion after the grasp
+    @staticmethod
+    def _closed(closed_joints, closed_values):
+        """(indices int32, values float64, count) of the joints a retrieve path holds closed; values may be one scalar."""
+        cj = _i32([] if closed_joints is None else closed_joints).reshape(-1)
+        cv = _f64(np.broadcast_to(np.asarray(closed_values, dtype=np.float64), cj.shape))
+        return cj, cv, int(cj.size)
+
+    def retrieve_lift(self, plans, distance, steps=10, direction=(0.0, 0.0, 1.0), closed_joints=None, closed_values=0.0,
+                      scene_id=None, base_pos=None, max_iter=50, pos_tol=0.01, rot_tol_deg=5.0):
+        """gto_retrieve_lift: after plans (B, ndof, T), ``steps`` IK steps of link_ee along ``direction`` over ``distance``
+        with the gripper's pose held and the joints ``closed_joints`` at ``closed_values``.  Returns a dict of path
+        (B, ndof, steps + 1), goals (B, steps, 4, 4), err_pos / err_rot (degrees) / iters / status (B, steps) and reached (B,)."""
+        d, T, K = self.desc, self.T, int(steps)
+        plans = _f64(plans).reshape(-1, d.ndof, T)
+        B = plans.shape[0]
+        sid = None if scene_id is None else _per_instance(scene_id, B)
+        base = None if base_pos is None else _bases(base_pos, B)
+        cj, cv, nc = self._closed(closed_joints, closed_values)
+        dirv = _f64(direction).reshape(3)
+        Kc = max(K, 0)
+        out = dict(path=np.empty((B, d.ndof, Kc + 1)), goals=np.empty((B, Kc, 4, 4)), err_pos=np.empty((B, Kc)),
+                   err_rot=np.empty((B, Kc)), iters=np.empty((B, Kc), dtype=np.int32), status=np.empty((B, Kc), dtype=np.int32),
+                   reached=np.empty(B, dtype=np.int32))
+        self._check(self.lib.gto_retrieve_lift(self._h, B, _p(plans, _pd), _p(sid, _pi), _p(base, _pd), _p(dirv, _pd), float(distance), K,
+                                               _p(cj, _pi), _p(cv, _pd), nc, int(max_iter), float(pos_tol), float(rot_tol_deg),
+                                               _p(out["path"], _pd), _p(out["goals"], _pd), _p(out["err_pos"], _pd),
+                                               _p(out["err_rot"], _pd), _p(out["iters"], _pi), _p(out["status"], _pi),
+                                               _p(out["reached"], _pi)), "gto_retrieve_lift")
+        return out
+
+    def retrieve_lift_device(self, B, plans, scene_id, base_pos, direction, distance, steps, closed_joints, closed_values, max_iter,
+                             pos_tol, rot_tol_deg, path_out, goals_out=None, err_pos_out=None, err_rot_out=None, iters_out=None,
+                             status_out=None, reached_out=None, stream=None):
+        """gto_retrieve_lift_device: direction, closed_joints and closed_values are HOST values; every other array is a device
+        pointer (an int, e.g. torch.Tensor.data_ptr()) or None."""
+        cj, cv, nc = self._closed(closed_joints, closed_values)
+        dirv = _f64(direction).reshape(3)
+        self._check(self.lib.gto_retrieve_lift_device(self._h, int(B), _vp(plans), _vp(scene_id), _vp(base_pos), _p(dirv, _pd),
+                                                      float(distance), int(steps), _p(cj, _pi), _p(cv, _pd), nc, int(max_iter),
+                                                      float(pos_tol), float(rot_tol_deg), _vp(path_out), _vp(goals_out),
+                                                      _vp(err_pos_out), _vp(err_rot_out), _vp(iters_out), _vp(status_out),
+                                                      _vp(reached_out), _vp(stream)), "gto_retrieve_lift_device")
+
+    def retrieve_path_columns(self):
+        """gto_retrieve_path_columns: columns of the reversed path (19 at the defaults); -1 when the horizon is too short."""
+        return int(self.lib.gto_retrieve_path_columns(self._h))
+
+    def retrieve_reverse(self, B, plans, closed_joints, closed_values, path_out, stream=None):
+        """gto_retrieve_reverse_device: plans (B, ndof, T) and path_out (B, ndof, n) are device pointers; returns n."""
+        cj, cv, nc = self._closed(closed_joints, closed_values)
+        n = C.c_int32(0)
+        self._check(self.lib.gto_retrieve_reverse_device(self._h, int(B), _vp(plans), _p(cj, _pi), _p(cv, _pd), nc, _vp(path_out),
+                                                         C.byref(n), _vp(stream)), "gto_retrieve_reverse_device")
+        return int(n.value)
 
     # -------------------------------------------------------------- retiming
     def _retime_limits(self, vmax, amax):

@@ -26,6 +26,7 @@
 #include "gto_retime.h"
 #include "gto_observe.h"
 #include "gto_seed.h"
+#include "gto_retrieve.h"
 #include "gto_occupancy.h"
 #include "gto_owned.h"
 
@@ -2090,6 +2091,141 @@ int gto_ik_report_device(gto_handle* h, int32_t B, const int32_t* scene_id, cons
   return GTO_OK;
 }
 
+// The closed joints of a retrieve path as the kernels take them: distinct indices in [0, ndof)
+static int retrieve_closed(gto_handle* h, const char* who, const int32_t* closed_joints, const double* closed_values, int32_t n_closed,
+                           RetrieveClosed* cl) {
+  cl->mask = 0u;
+  for (int d = 0; d < GTO_MAX_DOF; ++d) cl->value[d] = 0.0;
+  if (n_closed < 0 || (n_closed > 0 && (!closed_joints || !closed_values)))
+    return fail(h, GTO_ERR_INVALID_ARG, std::string(who) + ": n_closed >= 0 with both closed arrays is required");
+  for (int i = 0; i < n_closed; ++i) {
+    const int d = closed_joints[i];
+    if (d < 0 || d >= h->rb.ndof || ((cl->mask >> d) & 1u))
+      return fail(h, GTO_ERR_INVALID_ARG, std::string(who) + ": closed_joints must be distinct indices in [0, ndof)");
+    cl->mask |= 1u << d;
+    cl->value[d] = closed_values[i];
+  }
+  return GTO_OK;
+}
+
+// gto_retrieve_lift and its device variant behind the handle check: the host-side checks (*empty: B = 0) and the arguments
+// that travel with the launch
+static int retrieve_lift_args(gto_handle* h, const char* who, int32_t B, const double* plans, const double* direction, double distance,
+                              int32_t K, const int32_t* closed_joints, const double* closed_values, int32_t n_closed, int32_t max_iter,
+                              double pos_tol, double rot_tol_deg, const double* path_out, bool* empty, RetrieveClosed* cl,
+                              RetrieveLine* ln) {
+  int rc = ik_check(h, who, B, max_iter, false, empty);
+  if (rc) return rc;
+  if (K < 1 || K > GTO_RETRIEVE_MAX_STEPS) return fail(h, GTO_ERR_INVALID_ARG, std::string(who) + ": 1 <= K <= 64 is required");
+  if (!direction || !std::isfinite(distance) || !std::isfinite(direction[0]) || !std::isfinite(direction[1]) || !std::isfinite(direction[2]))
+    return fail(h, GTO_ERR_INVALID_ARG, std::string(who) + ": a finite direction and distance are required");
+  if (*empty) return GTO_OK;
+  if (!plans || !path_out) return fail(h, GTO_ERR_INVALID_ARG, std::string(who) + ": null plans or path_out");
+  if ((rc = retrieve_closed(h, who, closed_joints, closed_values, n_closed, cl))) return rc;
+  for (int a = 0; a < 3; ++a) ln->dir[a] = direction[a];
+  ln->step = distance / (double)K;
+  ln->K = K, ln->pos_tol = pos_tol, ln->rot_tol_deg = rot_tol_deg;
+  return GTO_OK;
+}
+
+static int retrieve_lift_launch(gto_handle* h, int32_t B, const double* plans, const int32_t* scene_id, const double* base_pos,
+                                const RetrieveClosed& cl, const RetrieveLine& ln, int32_t max_iter, double* path_out, double* goals_out,
+                                double* err_pos_out, double* err_rot_out, int32_t* iters_out, int32_t* status_out, int32_t* reached_out,
+                                hipStream_t st) {
+  SolveParams sp = make_params(h, 1, false);  // (what ik_launch hands k_ik_solve)
+  sp.max_iter = max_iter;
+  const size_t lds = (size_t)retrieve_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt) * sizeof(double);
+  if (lds > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the retrieve kernel's LDS");
+  HIPCHK(h, raise_dynamic_lds((const void*)k_retrieve_lift, lds));
+  hipLaunchKernelGGL(k_retrieve_lift, dim3(B), dim3(256), lds, st, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_chunks, h->d_scenes,
+                     (int)h->scenes.size(), scene_id, plans, (int)h->opts.T, scene_id ? base_pos : nullptr, sp, cl, ln, path_out, goals_out,
+                     err_pos_out, err_rot_out, iters_out, status_out, reached_out);
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
+}
+
+int gto_retrieve_lift_device(gto_handle* h, int32_t B, const double* plans, const int32_t* scene_id, const double* base_pos,
+                             const double* direction, double distance, int32_t K, const int32_t* closed_joints,
+                             const double* closed_values, int32_t n_closed, int32_t max_iter, double pos_tol, double rot_tol_deg,
+                             double* path_out, double* goals_out, double* err_pos_out, double* err_rot_out, int32_t* iters_out,
+                             int32_t* status_out, int32_t* reached_out, void* stream) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  bool empty;
+  RetrieveClosed cl;
+  RetrieveLine ln;
+  const int rc = retrieve_lift_args(h, "gto_retrieve_lift_device", B, plans, direction, distance, K, closed_joints, closed_values, n_closed,
+                                    max_iter, pos_tol, rot_tol_deg, path_out, &empty, &cl, &ln);
+  if (rc || empty) return rc;
+  if (scene_id && !base_pos) return fail(h, GTO_ERR_INVALID_ARG, "gto_retrieve_lift_device: scene_id needs base_pos");
+  HIPCHK(h, hipSetDevice(h->device));
+  return retrieve_lift_launch(h, B, plans, scene_id, base_pos, cl, ln, max_iter, path_out, goals_out, err_pos_out, err_rot_out, iters_out,
+                              status_out, reached_out, stream ? (hipStream_t)stream : h->stream);
+}
+
+int gto_retrieve_lift(gto_handle* h, int32_t B, const double* plans, const int32_t* scene_id, const double* base_pos,
+                      const double* direction, double distance, int32_t K, const int32_t* closed_joints, const double* closed_values,
+                      int32_t n_closed, int32_t max_iter, double pos_tol, double rot_tol_deg, double* path_out, double* goals_out,
+                      double* err_pos_out, double* err_rot_out, int32_t* iters_out, int32_t* status_out, int32_t* reached_out) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  bool empty;
+  RetrieveClosed cl;
+  RetrieveLine ln;
+  int rc = retrieve_lift_args(h, "gto_retrieve_lift", B, plans, direction, distance, K, closed_joints, closed_values, n_closed, max_iter,
+                              pos_tol, rot_tol_deg, path_out, &empty, &cl, &ln);
+  if (rc || empty) return rc;
+  if (scene_id && (rc = check_scene_ids_host(h, scene_id, B))) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t ndof = h->rb.ndof, T = h->opts.T, k = (size_t)K;
+  std::vector<double> zeros;
+  if (scene_id && !base_pos) {
+    zeros.assign((size_t)B * 3, 0.0);
+    base_pos = zeros.data();
+  }
+  Staging io(h);
+  const double *d_plans, *d_base;
+  const int32_t* d_sid;
+  double *d_path, *d_goals, *d_ep, *d_er;
+  int32_t *d_it, *d_stat, *d_reached;
+  if ((rc = io.in(plans, B * ndof * T, &d_plans))) return rc;
+  if ((rc = io.in(scene_id, B, &d_sid))) return rc;
+  if ((rc = io.in(scene_id ? base_pos : nullptr, (size_t)B * 3, &d_base))) return rc;
+  if ((rc = io.out(path_out, B * ndof * (k + 1), &d_path))) return rc;
+  if ((rc = io.out(goals_out, B * k * 16, &d_goals))) return rc;
+  if ((rc = io.out(err_pos_out, B * k, &d_ep))) return rc;
+  if ((rc = io.out(err_rot_out, B * k, &d_er))) return rc;
+  if ((rc = io.out(iters_out, B * k, &d_it))) return rc;
+  if ((rc = io.out(status_out, B * k, &d_stat))) return rc;
+  if ((rc = io.out(reached_out, (size_t)B, &d_reached))) return rc;
+  if ((rc = retrieve_lift_launch(h, B, d_plans, d_sid, d_base, cl, ln, max_iter, d_path, d_goals, d_ep, d_er, d_it, d_stat, d_reached,
+                                 h->stream)))
+    return rc;
+  return io.finish();
+}
+
+int gto_retrieve_path_columns(gto_handle* h) {
+  if (!h || h->opts.T + h->opts.standoff_offset - 10 < 0) return -1;
+  return 9 - h->opts.standoff_offset;
+}
+
+int gto_retrieve_reverse_device(gto_handle* h, int32_t B, const double* plans, const int32_t* closed_joints, const double* closed_values,
+                                int32_t n_closed, double* path_out, int32_t* n_cols_out, void* stream) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (B < 0) return fail(h, GTO_ERR_INVALID_ARG, "gto_retrieve_reverse_device: B must be >= 0");
+  const int n_cols = gto_retrieve_path_columns(h);
+  if (n_cols < 1) return fail(h, GTO_ERR_INVALID_ARG, "gto_retrieve_reverse_device: the horizon is shorter than the stretch T + standoff_offset - 10 .. T - 2");
+  if (n_cols_out) *n_cols_out = n_cols;
+  if (B == 0) return GTO_OK;
+  if (!plans || !path_out) return fail(h, GTO_ERR_INVALID_ARG, "gto_retrieve_reverse_device: null plans or path_out");
+  RetrieveClosed cl;
+  if (int rc = retrieve_closed(h, "gto_retrieve_reverse_device", closed_joints, closed_values, n_closed, &cl)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  const long long total = (long long)B * h->rb.ndof * n_cols;
+  hipLaunchKernelGGL(k_retrieve_reverse, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream ? (hipStream_t)stream : h->stream, plans,
+                     (int)h->rb.ndof, (int)h->opts.T, n_cols, total, cl, path_out);
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
+}
+
 // Both seed entry points behind their handle check: the checks, k_seed_score and the choice.  n_seeds = 0: the plain
 // choice (k_seed_select); otherwise the ranked one into n_seeds slots per instance.
 static int seed_goalsets(gto_handle* h, const std::string& name, int32_t B, int32_t n_max, int32_t n_seeds, const int32_t* scene_id,
@@ -3430,14 +3566,15 @@ int gto_observation_check_posed(gto_observation* o, const double* points, int32_
   return GTO_OK;
 }
 
-int gto_check_plans_device(gto_handle* h, gto_observation* o, int32_t B, const double* plans, const double* base_pos,
+int gto_check_paths_device(gto_handle* h, gto_observation* o, int32_t B, int32_t Tp, const double* plans, const double* base_pos,
                            int32_t per_plan_base, int32_t* count_out, void* stream) {
   bool empty;
   if (int rc = check_plans_args(h, o, B, plans, base_pos, &empty)) return rc;
+  if (Tp < 1) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_paths: Tp must be >= 1");
   if (empty) return GTO_OK;
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-  const int T = h->opts.T, P = h->rb.n_points, ndof = h->rb.ndof;
+  const int T = Tp, P = h->rb.n_points, ndof = h->rb.ndof;
   const size_t lds = sizeof(double) * check_plans_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
   if (lds > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the collision-check kernel's LDS");
   const int tg = check_waypoints_per_group();
@@ -3559,20 +3696,35 @@ int gto_filter_grasps_device(gto_handle* h, int32_t B, int32_t n_max, gto_observ
   return GTO_OK;
 }
 
-int gto_check_plans(gto_handle* h, gto_observation* o, int32_t B, const double* plans, const double* base_pos,
+int gto_check_plans_device(gto_handle* h, gto_observation* o, int32_t B, const double* plans, const double* base_pos,
+                           int32_t per_plan_base, int32_t* count_out, void* stream) {
+  bool empty;
+  if (int rc = check_plans_args(h, o, B, plans, base_pos, &empty)) return rc;  // (before the handle's horizon is read)
+  return gto_check_paths_device(h, o, B, h->opts.T, plans, base_pos, per_plan_base, count_out, stream);
+}
+
+int gto_check_paths(gto_handle* h, gto_observation* o, int32_t B, int32_t Tp, const double* plans, const double* base_pos,
                     int32_t per_plan_base, int32_t* count_out) {
   bool empty;
   if (int rc = check_plans_args(h, o, B, plans, base_pos, &empty)) return rc;
+  if (Tp < 1) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_paths: Tp must be >= 1");
   if (empty) return GTO_OK;
   HIPCHK(h, hipSetDevice(h->device));
   Staging io(h);
   const double* d_plans;
   int32_t* d_count;
   int rc;
-  if ((rc = io.in(plans, (size_t)B * h->rb.ndof * h->opts.T, &d_plans))) return rc;
-  if ((rc = io.out(count_out, (size_t)B * h->opts.T, &d_count))) return rc;
-  if ((rc = gto_check_plans_device(h, o, B, d_plans, base_pos, per_plan_base, d_count, nullptr))) return rc;
+  if ((rc = io.in(plans, (size_t)B * h->rb.ndof * Tp, &d_plans))) return rc;
+  if ((rc = io.out(count_out, (size_t)B * Tp, &d_count))) return rc;
+  if ((rc = gto_check_paths_device(h, o, B, Tp, d_plans, base_pos, per_plan_base, d_count, nullptr))) return rc;
   return io.finish();
+}
+
+int gto_check_plans(gto_handle* h, gto_observation* o, int32_t B, const double* plans, const double* base_pos,
+                    int32_t per_plan_base, int32_t* count_out) {
+  bool empty;
+  if (int rc = check_plans_args(h, o, B, plans, base_pos, &empty)) return rc;
+  return gto_check_paths(h, o, B, h->opts.T, plans, base_pos, per_plan_base, count_out);
 }
 
 }  // extern "C"

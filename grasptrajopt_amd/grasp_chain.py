@@ -5,7 +5,8 @@ on one stream:
     goal sets compacted (gto_filter_grasps_device; ``plan_grasps``, :192-236) ->
     grasp poses (``plan_objects`` starts here, :242) -> IK (gto_solve_ik_pose_batch_device) -> err_pos / err_rot /
     collision cost and the acceptance test of :262 (gto_ik_report_device) -> accepted goal sets and seeds (gto_seed_goalsets_device) -> gto_solve_batch_device ->
-    optionally gto_check_plans_device and gto_retime_batch_device
+    optionally gto_check_plans_device, the retrieve motion after the grasp (:301-313: gto_retrieve_lift_device or
+    gto_retrieve_reverse_device, with gto_check_paths_device) and gto_retime_batch_device
 
 (with ``n_seeds`` > 1: gto_seed_goalsets_multi_device -> one gto_solve_batch_device over every object's n_seeds best seeds ->
 gto_plan_report_device -> gto_check_plans_device -> gto_select_plans_device, and the best plan of every object goes on)
@@ -23,6 +24,11 @@ import numpy as np
 
 from . import _capi
 from .synthetic import standoff_pose
+
+
+def finger_joints(desc):
+    """The robot's parameter joints that are fingers (the configs' finger_index): what the driver closes after the grasp."""
+    return [int(i) for i in desc.param_index if "finger" in desc.actuated_joint_names[int(i)]]
 
 
 class GraspChain:
@@ -119,14 +125,19 @@ class GraspChain:
     # ------------------------------------------------------------------ the chain
     def plan_objects(self, qc, ik_goals, plan_goals, n_grasps, fields, base_position, axis_standoff="x", use_standoff=True,
                      interpolate=True, pos_tol=0.01, rot_tol_deg=5.0, ik_collision_threshold=5.0, float32_solutions=True,
-                     observation=None, retime=None, n_seeds=1, max_points=5):
+                     observation=None, retime=None, n_seeds=1, max_points=5, retrieve=None):
         """B objects with up to n_max candidate grasps each.
 
         qc (B, ndof) or (ndof,); ik_goals, plan_goals (B, n_max, 4, 4): the poses IK is solved to and the poses the plan
         goes to (the shelf driver solves IK to ``RT @ standoff`` and plans to ``RT``, :256-259); n_grasps (B,) how many rows
         of an object count; fields: see ``_scene_ids``; base_position (3,) or (B, 3).  observation: an
         ``observation.Observation`` to count the solved plans' surface points inside (gto_check_plans_device).  retime: a
-        dict ``vmax, amax[, subdiv, n_samples]`` to retime the solved plans (gto_retime_batch_device).
+        dict ``vmax, amax[, subdiv, n_samples]`` to retime the solved plans (gto_retime_batch_device).  retrieve: a dict
+        ``mode`` ("lift" | "reverse") ``[, distance, steps, direction, closed_joints, closed_value, collide]`` for the motion
+        after the grasp (see ``retrieve_spec``), enqueued behind the solve (with n_seeds > 1 behind the selection) on the
+        chain's stream; the result gains retrieve_path (B, ndof, steps + 1 | n), retrieve_reached (B,) (lift: the leading
+        steps that reached their goal; reverse: n), retrieve_status (B, steps) (reverse: (B, 0)) and, with an observation,
+        retrieve_counts (B, columns).  The retrieve path is not retimed (the retimer's spline factors are per horizon T).
 
         Returns a namespace: plans (B, ndof, T), dQ (B, ndof, T-1), cost, iters, status (B,), n_accepted (B,) (0: no
         feasible grasp, the driver's ``continue``; the plan is then the solve from the constant seed to all goals),
@@ -153,7 +164,23 @@ class GraspChain:
                     self._up("n_grasps", n_grasps, np.int32), {})
 
         return self._plan(B, n_max, feed, qc, fields, base_position, axis_standoff, use_standoff, interpolate, pos_tol, rot_tol_deg,
-                          ik_collision_threshold, float32_solutions, observation, retime, n_seeds, max_points)
+                          ik_collision_threshold, float32_solutions, observation, retime, n_seeds, max_points, retrieve)
+
+    def retrieve_spec(self, retrieve):
+        """A ``retrieve`` dict with its defaults filled in: mode "lift" (straight up by ``distance`` = 0.3 m in ``steps`` = 10
+        IK steps along ``direction`` = (0, 0, 1) with the gripper's pose held; ``collide``: with the collision term of the
+        object's scene, default False as in the reference's retract) or "reverse" (the plan's last stretch backwards);
+        ``closed_joints`` (default: the robot's parameter joints that are fingers) are held at ``closed_value`` = 0."""
+        known = {"mode", "distance", "steps", "direction", "closed_joints", "closed_value", "collide"}
+        if set(retrieve) - known:
+            raise TypeError(f"retrieve: unexpected key(s) {sorted(set(retrieve) - known)}")
+        r = dict(mode="lift", distance=0.3, steps=10, direction=(0.0, 0.0, 1.0), closed_joints=None, closed_value=0.0, collide=False)
+        r.update(retrieve)
+        if r["mode"] not in ("lift", "reverse"):
+            raise ValueError('retrieve: mode is "lift" or "reverse"')
+        if r["closed_joints"] is None:
+            r["closed_joints"] = finger_joints(self.robot.desc)
+        return r
 
     def plan_grasps(self, qc, object_poses, grasps, n_grasps, observations, fields, base_position, gripper_points, check_offset,
                     ik_offset=None, world_to_base=None, max_ratio=0.01, **plan_objects_keywords):
@@ -237,7 +264,7 @@ class GraspChain:
         return n_grasps
 
     def _plan(self, B, n_max, feed, qc, fields, base_position, axis_standoff, use_standoff, interpolate, pos_tol, rot_tol_deg,
-              ik_collision_threshold, float32_solutions, observation, retime, n_seeds, max_points):
+              ik_collision_threshold, float32_solutions, observation, retime, n_seeds, max_points, retrieve=None):
         """What ``plan_objects`` and ``plan_grasps`` share: the chain from the goal sets on.  ``feed(stream, d_base)`` is called
         on the chain's stream behind the uploads of scene ids, qc and base; it returns the device arrays ik_goals, plan_goals
         (B, n_max, 16), n_grasps (B,) -- uploaded, or written by launches it enqueued -- and a dict of further device arrays
@@ -327,6 +354,24 @@ class GraspChain:
                     h.select_plans_device(M, 1, *sel, class_out=d_scls.data_ptr(), stream=st)  # every slot on its own: its class
                     h.select_plans_device(B, K, *sel, Q=d_Qs.data_ptr(), dQ=d_dQs.data_ptr(), best_slot_out=d_best.data_ptr(),
                                           class_out=d_cls.data_ptr(), Q_out=d_Q.data_ptr(), dQ_out=d_dQ.data_ptr(), stream=st)
+                if retrieve is not None:
+                    rs = self.retrieve_spec(retrieve)
+                    lift = rs["mode"] == "lift"
+                    cols = int(rs["steps"]) + 1 if lift else h.retrieve_path_columns()
+                    if cols < 1:
+                        raise ValueError("retrieve: the horizon is shorter than the stretch the reverse mode runs backwards")
+                    d_rp = self._dev("retrieve_path", (B, ndof, cols), f64)
+                    if lift:
+                        d_rreach, d_rstat = self._dev("retrieve_reached", (B,), i32), self._dev("retrieve_status", (B, cols - 1), i32)
+                        h.retrieve_lift_device(B, d_Q.data_ptr(), d_sid.data_ptr() if rs["collide"] else None, d_base.data_ptr(),
+                                               rs["direction"], rs["distance"], rs["steps"], rs["closed_joints"], rs["closed_value"],
+                                               self.ik_max_iter, pos_tol, rot_tol_deg, d_rp.data_ptr(), status_out=d_rstat.data_ptr(),
+                                               reached_out=d_rreach.data_ptr(), stream=st)
+                    else:
+                        h.retrieve_reverse(B, d_Q.data_ptr(), rs["closed_joints"], rs["closed_value"], d_rp.data_ptr(), stream=st)
+                    if observation is not None:
+                        d_rcnt = self._dev("retrieve_counts", (B, cols), i32)
+                        h.check_paths_device(observation, B, cols, d_rp.data_ptr(), d_rcnt.data_ptr(), base_pos=base, stream=st)
                 if retime is not None:
                     d_dur, d_rst = self._dev("durations", (B,), f64), self._dev("retime_status", (B,), i32)
                     h.retime_batch_device(B, d_Q.data_ptr(), retime["vmax"], retime["amax"], int(retime.get("subdiv", 2)),
@@ -340,6 +385,12 @@ class GraspChain:
                 out["counts"] = d_cnt
             if N and retime is not None:
                 out["durations"], out["retime_status"] = d_dur, d_rst
+            if N and retrieve is not None:
+                out["retrieve_path"] = d_rp
+                if lift:
+                    out["retrieve_reached"], out["retrieve_status"] = d_rreach, d_rstat
+                if observation is not None:
+                    out["retrieve_counts"] = d_rcnt
             if multi:  # (cost, iters, status and counts hold every slot's until the chosen slot's are picked below)
                 out.update(best_slot=d_best, plan_class=d_cls, slot_class=d_scls, slot_goal_index=d_gi, slot_err_pos=d_pep,
                            slot_err_rot=d_per, accepted_rows=d_rows, slot_plans=d_Qs)
@@ -352,6 +403,9 @@ class GraspChain:
         res.accept = res.accept.astype(bool)
         if float32_solutions:
             res.q_solutions = res.q_solutions.astype(np.float32)
+        if N and retrieve is not None and not lift:  # every column of the reversed stretch is the plan's own
+            res.retrieve_reached = np.full(B, cols, dtype=np.int32)
+            res.retrieve_status = np.zeros((B, 0), dtype=np.int32)
         if multi:  # the chosen slot's entries of the small per-slot arrays, picked on the host
             rows, best = np.arange(B), res.best_slot
             res.slot_cost, res.slot_iters, res.slot_status = res.cost, res.iters, res.status

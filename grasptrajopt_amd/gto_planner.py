@@ -115,3 +115,42 @@ class GTOPlanner:
         solution = self.solver.solve()
         return (solution[f"{self.robot_name}/q"].toarray(), solution[f"{self.robot_name}/dq"].toarray(),
                 solution["f"].toarray().flatten())
+
+    def retrieve_path(self, plan, mode="lift", distance=0.3, steps=10, direction=(0.0, 0.0, 1.0), closed_joints=None,
+                      closed_value=0.0, max_iter=50, pos_tol=0.01, rot_tol_deg=5.0):
+        """The motion after the grasp (examples/pybullet_gto_planning.py:301-313) for a solved ``plan`` (ndof, T), or
+        (B, ndof, T) for B of them: mode "lift" moves link_ee by ``distance`` along ``direction`` in ``steps`` IK steps, each
+        seeded from the one before, with the gripper's pose held (the tabletop driver's env.retract; pybullet's position-only
+        IK would let the held object tilt); mode "reverse" runs the plan's last stretch backwards (the shelf driver).
+        ``closed_joints`` (default: the robot's parameter joints that are fingers) are held at ``closed_value``.
+        Returns (path (ndof, steps + 1 | 9 - standoff_offset), reached): reached counts the leading steps that met their goal
+        within pos_tol / rot_tol_deg (reverse: every column).  No collision term; GraspChain's ``retrieve`` has one.  The
+        path is not retimed (the retimer's spline factors are per horizon T)."""
+        from . import _capi
+        from .grasp_chain import finger_joints
+        plan = np.asarray(plan, dtype=np.float64)
+        single = plan.ndim == 2
+        plans = np.ascontiguousarray(plan.reshape(-1, self.robot.ndof, self.T))
+        opts = _capi.default_opts()
+        opts.T, opts.Tmax, opts.standoff_offset = self.T, self.Tmax, self.standoff_offset
+        h = self.robot.solver_handle(self.link_ee, self.link_gripper, opts, role="retrieve")
+        closed = finger_joints(self.robot.desc) if closed_joints is None else closed_joints
+        if mode == "lift":
+            out = h.retrieve_lift(plans, distance, steps, direction, closed, closed_value, max_iter=max_iter, pos_tol=pos_tol,
+                                  rot_tol_deg=rot_tol_deg)
+            path, reached = out["path"], out["reached"]
+        elif mode == "reverse":
+            import torch
+            n = h.retrieve_path_columns()
+            if n < 1:
+                raise ValueError("retrieve_path: the horizon is shorter than the stretch the reverse mode runs backwards")
+            dev = torch.device("cuda", self.robot.device)
+            d_plans = torch.from_numpy(plans).to(dev)
+            d_path = torch.empty((plans.shape[0], self.robot.ndof, n), dtype=torch.float64, device=dev)
+            stream = torch.cuda.current_stream(dev)
+            h.retrieve_reverse(plans.shape[0], d_plans.data_ptr(), closed, closed_value, d_path.data_ptr(), stream=stream.cuda_stream)
+            path = d_path.cpu().numpy()  # (synchronises the stream)
+            reached = np.full(plans.shape[0], n, dtype=np.int32)
+        else:
+            raise ValueError('retrieve_path: mode is "lift" or "reverse"')
+        return (path[0], int(reached[0])) if single else (path, reached)

@@ -827,6 +827,77 @@ int gto_filter_grasps_device(gto_handle* h, int32_t B, int32_t n_max, gto_observ
                              int32_t* kept_rows_out, int32_t* n_kept_out, int32_t* n_grasps_out, double* plan_goals_out,
                              double* ik_goals_out, void* stream);
 
+/*
+ * ---- the motion after the grasp (examples/pybullet_gto_planning.py:301-313) ------------------------------------------------
+ * The driver executes the plan, closes the gripper and retrieves the object: on a table it lifts link_ee straight up
+ * (env.retract(retract_distance), :307-308; pybullet_scenereplica.py:597-613: fingers closed, ten position-only IK steps,
+ * each seeded from the one before), in a shelf it runs the plan's last stretch backwards (:309-313).  compute_reward
+ * (:574-589) judges the object after this motion.  Additions (the ABI number stays).  The `_device` entry points take device pointers and `stream`
+ * (NULL = the handle's stream), enqueue without a host synchronisation and validate host-side facts only; B = 0 returns
+ * GTO_OK without a launch; every plan's result is bit for bit the same in any batch and at any position in it.
+ *
+ * gto_retrieve_lift_device: a Cartesian straight-line chain of K IK steps per plan in ONE launch (one workgroup per plan
+ * runs the whole chain; nothing but the step's column and record is written between steps).  Per plan b:
+ *   column 0   plans[b][:, T-1] (T: the handle's horizon) with entry closed_joints[i] replaced by closed_values[i] (the
+ *              driver closes the fingers to 0); parameter joints keep these values in every column.  closed_joints: distinct
+ *              indices in [0, ndof) (GTO_ERR_INVALID_ARG otherwise); n_closed = 0 with NULL arrays closes nothing.
+ *   RT0        link_ee's pose at column 0 from the device kinematics behind gto_eval_fk: the bits gto_eval_fk returns
+ *   goal k     k = 1..K: RT0's rotation; translation p0[a] + ((double)k * (distance / K)) * direction[a], in FP64 without
+ *              contraction; direction [3] is used as given (not normalised), distance and direction finite
+ *   step k     the GTO_IK_GOAL_POINTS problem of gto_solve_ik_pose_batch_device to goal k, seeded from column k - 1: the same
+ *              projected Levenberg-Marquardt loop (the same device code), the same max_iter and the same optional collision
+ *              term (c_obs of scene scene_id[b] at base_pos[b]; scene_id NULL: no collision term, base_pos may then be NULL).
+ *              Column k is its solution.  The chain goes on after a step that misses its goal.
+ * The path, its iteration counts and statuses are bit-equal to K calls of gto_solve_ik_pose_batch_device driven from the
+ * host with the same goals.
+ * DEPARTURE from the reference: pybullet's position-only null-space IK is not available and would let the held object tilt;
+ * here the gripper's full pose is held, which is the existing point-matching pose term.
+ *   path_out [B][ndof][K+1] (required); goals_out [B][K][16]; iters_out, status_out [B][K];
+ *   err_pos_out, err_rot_out [B][K]   column k against goal k with the formulas (and the device code) of gto_ik_report_device
+ *   reached_out [B]   the number of leading steps with err_pos < pos_tol, err_rot < rot_tol_deg and a status other than
+ *                     GTO_STATUS_NUMERICAL
+ * Any output but path_out may be NULL.  1 <= K <= 64 (GTO_ERR_INVALID_ARG otherwise); more than eight optimised joints:
+ * GTO_ERR_UNSUPPORTED.  A scene id that names no scene behaves as in gto_solve_ik_pose_batch_device at every step: status
+ * GTO_STATUS_NUMERICAL, 0 iterations, the column is the clipped column before it; reached = 0.  A plan whose column 0 holds a
+ * non-finite entry: every step GTO_STATUS_NUMERICAL with 0 iterations, every column equals column 0, errors and the goals'
+ * first three rows are NaN, reached = 0; no other plan's output changes.
+ * gto_retrieve_lift: the same with host arrays (scene ids are checked on the host as in gto_solve_ik_batch; base_pos NULL
+ * with scene_id given reads as zeros).
+ */
+#define GTO_RETRIEVE_MAX_STEPS 64
+int gto_retrieve_lift_device(gto_handle* h, int32_t B, const double* plans, const int32_t* scene_id, const double* base_pos,
+                             const double* direction /*HOST*/, double distance, int32_t K,
+                             const int32_t* closed_joints /*HOST*/, const double* closed_values /*HOST*/, int32_t n_closed,
+                             int32_t max_iter, double pos_tol, double rot_tol_deg, double* path_out, double* goals_out,
+                             double* err_pos_out, double* err_rot_out, int32_t* iters_out, int32_t* status_out,
+                             int32_t* reached_out, void* stream);
+int gto_retrieve_lift(gto_handle* h, int32_t B, const double* plans, const int32_t* scene_id, const double* base_pos,
+                      const double* direction, double distance, int32_t K, const int32_t* closed_joints,
+                      const double* closed_values, int32_t n_closed, int32_t max_iter, double pos_tol, double rot_tol_deg,
+                      double* path_out, double* goals_out, double* err_pos_out, double* err_rot_out, int32_t* iters_out,
+                      int32_t* status_out, int32_t* reached_out);
+/*
+ * The shelf branch (:309-313): path_out [B][ndof][n] with n = gto_retrieve_path_columns(h) = 9 - standoff_offset (19 at the
+ * defaults): columns T + standoff_offset - 10 .. T - 2 of the plan in reverse order (plan[:, arange(standoff_offset - 10,
+ * -1)][:, ::-1]), the rows of closed_joints overwritten with closed_values (HOST arrays, as above).  The plan's last waypoint
+ * is NOT part of the path, as the reference leaves it out.  T + standoff_offset - 10 < 0 (a horizon too short for the
+ * stretch): GTO_ERR_INVALID_ARG, and gto_retrieve_path_columns returns -1 (also for a null handle).  n_cols_out: HOST, may be
+ * NULL; receives n.  Works on every handle, whatever its number of optimised joints.
+ */
+int gto_retrieve_reverse_device(gto_handle* h, int32_t B, const double* plans, const int32_t* closed_joints,
+                                const double* closed_values, int32_t n_closed, double* path_out, int32_t* n_cols_out,
+                                void* stream);
+int gto_retrieve_path_columns(gto_handle* h);
+/*
+ * The plan collision statistic on paths of any length: the contract of gto_check_plans / gto_check_plans_device with paths
+ * [B][ndof][Tp] and count_out [B][Tp], Tp >= 1 passed explicitly (GTO_ERR_INVALID_ARG otherwise): the same kernels, the same
+ * workspace rules.  With Tp = the handle's horizon the two return the same bits.
+ */
+int gto_check_paths(gto_handle* h, gto_observation* obs, int32_t B, int32_t Tp, const double* paths, const double* base_pos,
+                    int32_t per_plan_base, int32_t* count_out);
+int gto_check_paths_device(gto_handle* h, gto_observation* obs, int32_t B, int32_t Tp, const double* paths,
+                           const double* base_pos, int32_t per_plan_base, int32_t* count_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
