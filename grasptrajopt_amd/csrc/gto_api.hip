@@ -415,6 +415,7 @@ static int build_robot(const gto_robot_desc* d, int pb_merge, RobotTables& t, st
   for (int i = 0; i < GTO_MAX_DOF; ++i) rb.opt_of_dof[i] = -1;
   for (int j = 0; j < d->n_opt; ++j) {
     if (d->opt_index[j] < 0 || d->opt_index[j] >= d->ndof) return bad(GTO_ERR_INVALID_ARG, "opt_index out of range");
+    if (rb.opt_of_dof[d->opt_index[j]] >= 0) return bad(GTO_ERR_INVALID_ARG, "opt_index names a joint twice");
     rb.opt_index[j] = d->opt_index[j];
     rb.opt_of_dof[d->opt_index[j]] = j;
     rb.lower[j] = d->lower[j];

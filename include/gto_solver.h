@@ -73,6 +73,12 @@ extern "C" {
  * The small end: every count may be 1 (one frame, whose joint then sits on the root itself, one optimised joint, one
  * link, one surface point, one gripper point), frame_ee and frame_gripper may be any two frames, above every optimised
  * joint included, and no link need hang below an optimised joint (tests/small_robots.py).
+ * Joint numbering: q_index may number the actuated joints in any order (a URDF may list its joints in any order; the
+ * frames' order is not the joints').  opt_index lists distinct joints and need not be ascending, contiguous or in the
+ * order of the kinematic chain; parameter joints may lie between optimised ones.  Entry j of opt_index is optimised
+ * slot j: lower[j] and upper[j] are the limits of joint opt_index[j], and the blocks of gto_eval_obstacle_normal_eq come
+ * in slot order.  Every [ndof] axis of the entry points below is indexed by q_index's numbering.  Renumbering a robot's
+ * joints permutes those axes and changes nothing else (tests/renumbered_robots.py).
  */
 typedef struct gto_robot_desc {
   int32_t n_frames;
@@ -84,9 +90,9 @@ typedef struct gto_robot_desc {
   const double* axis;        /* [n_frames*3]  NOT yet normalised (optas/models.py:653-659)     */
   int32_t ndof;              /* actuated joints, URDF order (optas/models.py:349-354)          */
   int32_t n_opt;             /* optimised joints (optas/models.py:366-386)                     */
-  const int32_t* opt_index;  /* [n_opt]       indexes into q                                   */
-  const double* lower;       /* [n_opt]       joint limits of the optimised joints             */
-  const double* upper;       /* [n_opt]                                                        */
+  const int32_t* opt_index;  /* [n_opt]       indexes into q: distinct, in any order           */
+  const double* lower;       /* [n_opt]       joint limits of the optimised joints, lower[j]   */
+  const double* upper;       /* [n_opt]       and upper[j] those of joint opt_index[j]         */
   int32_t n_links;           /* links with surface points (gto/gto_models.py:62-80)            */
   const int32_t* link_frame; /* [n_links]     frame index of each collision link               */
   const double* visual_xyz;  /* [n_links*3]   visual origin (gto/gto_models.py:95-100)         */

@@ -1,0 +1,276 @@
+"""Robots with renumbered joints, as seeded cases for the CPU and the GPU suite (no GPU here).
+
+include/gto_solver.h puts no order on the actuated joints: q_index may number them in any order, opt_index need not be
+ascending, contiguous or in the order of the kinematic chain, and lower / upper follow opt_index.  Every robot the other
+suites use has opt_index ascending and in chain order, and all but fetch_mobile have it contiguous.  renumber(desc, pi,
+sort) is the same robot with actuated joint i renamed pi[i]; every output of every entry point must then be the original
+robot's with its joint axes permuted.  Two variants:
+  "chain"   opt_index = pi[opt_index] as it stands: only the joints' numbers change, the optimised slots and every sum over
+            them stay as they were -- the same bits are due on the GPU (and on the oracle);
+  "sorted"  opt_index = sort(pi[opt_index]), as optas would list it: the slot order changes too (View.sigma), sums over slots
+            are taken in another order, and results are held to the FP64 oracle on the renumbered robot.
+CASES (all required; pi is fixed per case, parameter joints lie between the optimised ones, and the optimised joints' chain
+order is not ascending in the new numbering -- tests/test_renumbered_robots_cpu.py asserts what each is chosen for):
+  r1      helpers.random_robot(1): 6 of 8 joints optimised, prismatic ones among them
+  r9      helpers.random_robot(9): 8 of 9 optimised, the full width of the eight-wide kernels
+  r3      helpers.random_robot(3): 3 of 16 optimised, 13 parameter joints, 21 frames
+  panda   the built-in Panda with the fingers first and the arm reversed (the plans of retrieve_ref.grasp_plans and the
+          board of retrieve_ref.board_case are reused after permuting; no parameter joint lies between optimised ones here)
+  r55     helpers.random_robot(55, n_frames=14, n_opt=10): the 16-wide step kernel (no parameter joint; evaluation and
+          trajectory solve only)
+Inputs are drawn once per case in the original numbering, as tests/test_gpu_parity.py::test_random_robots_match_oracle
+draws them: a 40^3 random band field at 0.05 m, qc inside 0.3 of the limits, goals that are the oracle's FK of configurations
+inside 0.8 of them (sets of 1 to 3), seeds from synthetic.make_seed, and a non-zero base per instance.  SEEDS holds the seed
+of each case's draw; a case whose oracle solves are not invariant under the renumbering (an accept / reject decided by
+round-off) changes its seed here and is not set aside at run time."""
+import copy
+
+import numpy as np
+
+from grasptrajopt_amd import synthetic as syn
+from grasptrajopt_amd.robot_desc import load_builtin
+from helpers import cfg_of, random_robot
+
+VARIANTS = ("chain", "sorted")
+N_MAX = 3
+MAX_ITER, IK_MAX_ITER, BASE_MAX_ITER, POSE_MAX_ITER, LIFT_MAX_ITER = 25, 40, 25, 50, 30
+LIFT_K, LIFT_DISTANCE, LIFT_DIRECTION = 4, 0.05, (0.3, -0.2, 1.1)
+CLOSED_VALUES = (0.11, -0.07)   # distinct and non-zero: a value taken by list position instead of by joint shows
+
+#          base robot                   T   B   pi (actuated joint i of the base robot is joint pi[i] here)
+CASES = {
+    "r1": ((1,), 13, 5, [5, 2, 7, 0, 6, 3, 1, 4]),
+    "r9": ((9,), 16, 6, [6, 2, 8, 0, 5, 1, 7, 3, 4]),
+    "r3": ((3,), 19, 4, [9, 2, 13, 5, 0, 11, 15, 7, 1, 12, 3, 14, 8, 4, 10, 6]),
+    "panda": ("panda", 18, 4, [8, 7, 6, 5, 4, 3, 2, 0, 1]),
+    "r55": ((55, 14, 10), 14, 4, [7, 3, 9, 0, 5, 2, 8, 1, 6, 4]),
+}
+NARROW = [k for k in CASES if k != "r55"]   # the IK, base, seed, report and retrieve kernels take up to eight optimised joints
+OFFSET = -3                                 # standoff_offset of every case (T + OFFSET - 10 >= 0: the reversed path exists)
+# case -> seed of its draw where 0 does not give invariant oracle solves (r9, seed 0: the IK without a scene creeps along a
+# flat valley to the iteration cap in four instances, and the sorted variant's cost there differs by 3e-6 relative)
+SEEDS = {"r9": 1}
+
+
+# --------------------------------------------------------------------------------------------------------- renumbering
+def renumber(desc, pi, sort):
+    """The RobotDesc of the same robot with actuated joint i renamed pi[i]."""
+    pi = np.asarray(pi, dtype=np.int64)
+    assert sorted(pi.tolist()) == list(range(desc.ndof))
+    inv = np.argsort(pi)                    # inv[new] = old
+    d = copy.deepcopy(desc)
+    d.name = f"{desc.name}_{'sorted' if sort else 'chain'}"
+    d.q_index = np.where(desc.q_index >= 0, pi[np.maximum(desc.q_index, 0)], -1).astype(np.int32)
+    d.lower, d.upper = desc.lower[inv].copy(), desc.upper[inv].copy()
+    if desc.velocity is not None:
+        d.velocity = desc.velocity[inv].copy()
+    d.actuated_joint_names = [desc.actuated_joint_names[i] for i in inv]
+    d.param_index = np.sort(pi[desc.param_index]).astype(np.int32)
+    opt = pi[desc.opt_index]
+    d.opt_index = (np.sort(opt) if sort else opt).astype(np.int32)
+    return d
+
+
+def to_new(a, pi, axis):
+    """An array whose `axis` is indexed by the original joint numbers, in the new numbering: out[pi[i]] = a[i]."""
+    return np.ascontiguousarray(np.take(np.asarray(a), np.argsort(np.asarray(pi)), axis=axis))
+
+
+def to_old(a, pi, axis):
+    """The inverse of to_new: out[i] = a[pi[i]]."""
+    return np.ascontiguousarray(np.take(np.asarray(a), np.asarray(pi), axis=axis))
+
+
+def slot_permutation(desc, pi):
+    """sigma of the sorted variant: its slot k is slot sigma[k] of the original (and of the chain-order variant)."""
+    return np.argsort(np.asarray(pi)[desc.opt_index], kind="stable")
+
+
+# --------------------------------------------------------------------------------------------------------------- cases
+class View:
+    """A case in one numbering ("original", "chain" or "sorted"): the descriptor and every joint-indexed input carried over,
+    with the attribute names tests/small_robots.Case has, so that its helpers (pose_goals, pose_restatement,
+    seed_goalset_case) and tests/retrieve_ref.py take a View."""
+
+    def __init__(self, case, variant):
+        self.case, self.variant, self.name = case, variant, case.name
+        nd = case.desc0.ndof
+        self.pi = np.arange(nd) if variant == "original" else np.asarray(case.pi, dtype=np.int64)
+        self.desc = case.desc0 if variant == "original" else renumber(case.desc0, self.pi, variant == "sorted")
+        self.sigma = slot_permutation(case.desc0, self.pi) if variant == "sorted" else np.arange(case.desc0.n_opt)
+        self.ee, self.gripper, self.ngp = case.ee, case.gripper, case.ngp
+        self.opts, self.T, self.B, self.offset, self.seed = case.opts, case.T, case.B, OFFSET, case.seed
+        self.scene, self.goals, self.goals_all = case.scene, case.goals, case.goals_all
+        self.n_goals, self.n_goals_ragged, self.S, self.base = case.n_goals, case.n_goals_ragged, case.S, case.base
+        self.qc, self.qg, self.Q0 = self.new(case.qc, 1), self.new(case.qg, 2), self.new(case.Q0, 1)
+        self.closed_joints = [int(self.pi[j]) for j in case.closed_joints]
+        self.closed_values = list(CLOSED_VALUES[:len(self.closed_joints)])
+
+    def new(self, a, axis):
+        return to_new(a, self.pi, axis)
+
+    def old(self, a, axis):
+        return to_old(a, self.pi, axis)
+
+    def slots_old(self, a, *axes):
+        """Blocks in this view's slot order carried back to the original's: out[sigma[k]] = a[k] along every axis given."""
+        a = np.asarray(a)
+        for ax in axes:
+            a = np.take(a, np.argsort(self.sigma), axis=ax)
+        return np.ascontiguousarray(a)
+
+    def oracle(self, oracle_mod):
+        o = oracle_mod.Oracle(self.desc, self.ee, self.gripper, self.opts, n_gripper_points=self.ngp)
+        o.set_scene(0, *self.scene)
+        return o
+
+    def handle(self, capi):
+        h = capi.SolverHandle(self.desc, self.ee, self.gripper, self.opts, device=0, n_gripper_points=self.ngp)
+        h.set_scene(0, *self.scene)
+        return h
+
+    def solve_args(self, ragged=False):
+        return (0, self.qc, self.goals_all if ragged else self.goals, self.n_goals_ragged if ragged else self.n_goals, self.S,
+                self.base, self.Q0)
+
+
+class Case:
+    def __init__(self, oracle_mod, name, seed=None):
+        robot, T, B, pi = CASES[name]
+        self.name, self.T, self.B, self.pi = name, T, B, list(pi)
+        self.seed = SEEDS.get(name, 0) if seed is None else seed
+        if robot == "panda":
+            cfg = cfg_of("panda")
+            d, self.ee, self.gripper, self.ngp = load_builtin("panda"), cfg["link_ee"], cfg["link_gripper"], None
+        else:
+            d, self.ee = random_robot(*robot)
+            self.gripper, self.ngp = self.ee, 40
+        self.desc0 = d
+        self.opts = oracle_mod.reference_opts(T=T, standoff_offset=OFFSET, max_iter=MAX_ITER)
+        rng = np.random.default_rng(7000 + 97 * list(CASES).index(name) + self.seed)
+        n, res = 40, 0.05
+        c_all = (0.03 * rng.random(n ** 3) * (rng.random(n ** 3) < 0.3)).astype(np.float32)
+        c_obs = (0.03 * rng.random(n ** 3) * (rng.random(n ** 3) < 0.2)).astype(np.float32)
+        self.scene = (c_all, c_obs, (n, n, n), (-1.0, -1.0, -1.0), res)
+        lo, hi = d.lower, d.upper
+        self.qc = rng.uniform(0.3 * lo, 0.3 * hi, size=(B, d.ndof))
+        self.qg = rng.uniform(0.8 * lo, 0.8 * hi, size=(B, N_MAX, d.ndof))
+        self.qg[:, :, d.param_index] = self.qc[:, None, d.param_index]
+        o = oracle_mod.Oracle(d, self.ee, self.gripper, self.opts, n_gripper_points=self.ngp)
+        fk = o.eval_fk(self.qg.reshape(-1, d.ndof))[:, d.frame_index(self.ee)]
+        self.goals_all = np.ascontiguousarray(fk.reshape(B, N_MAX, 16))
+        self.goals = np.ascontiguousarray(self.goals_all[:, :1])
+        self.n_goals = np.ones(B, dtype=np.int32)
+        self.n_goals_ragged = np.array([N_MAX, 1, 2, N_MAX, 2, 1, N_MAX, 2][:B], dtype=np.int32)
+        self.S = syn.standoff_pose(-0.05, "z")
+        self.base = rng.uniform(0.02, 0.1, size=(B, 3)) * rng.choice([-1.0, 1.0], size=(B, 3))
+        self.Q0 = np.stack([syn.make_seed(self.qc[b], self.qg[b, 0], T, d.param_index) for b in range(B)])
+        self.closed_joints = [int(j) for j in d.param_index[:2]]   # (original numbering) the joints a retrieve path closes
+        self._views = {}
+
+    def view(self, variant):
+        if variant not in self._views:
+            self._views[variant] = View(self, variant)
+        return self._views[variant]
+
+
+# ------------------------------------------------------------------------------------ inputs of the other entry points
+def lift_plans(view, fk0):
+    """(plans (B, ndof, T), scene or None): what gto_retrieve_lift runs on.  The random robots: the case's seeds, whose last
+    column is the goal configuration, in the case's own field (None).  Panda: retrieve_ref.board_case's three plans resampled
+    to the case's horizon (the last column is kept) with its board; fk0 is the eval_fk of the oracle of the ORIGINAL robot.
+    In the last plan an optimised joint ends above its limit: column 0 keeps it, the seed of step 1 is clipped."""
+    import retrieve_ref as rr
+    c = view.case
+    if c.name == "panda":
+        _, _, plans, scene = rr.board_case("panda", fk0)
+        cols = np.round(np.linspace(0, plans.shape[2] - 1, c.T)).astype(int)
+        plans = np.ascontiguousarray(plans[:, :, cols])
+    else:
+        plans, scene = c.Q0.copy(), None
+    j = int(c.desc0.opt_index[1])
+    plans[-1, j, -1] = c.desc0.upper[j] + 0.4
+    return view.new(plans, 1), scene
+
+
+def lift_bases(view, B):
+    """Per-plan non-zero bases."""
+    return np.ascontiguousarray(view.base[np.arange(B) % view.B])
+
+
+def ik_start(view):
+    """The case's qc with, in instance 0, an optimised joint below its lower limit and another above its upper limit: the
+    clip of the seed has to use each joint's own bounds."""
+    c = view.case
+    q = c.qc.copy()
+    a, b = int(c.desc0.opt_index[0]), int(c.desc0.opt_index[-1])
+    q[0, a] = c.desc0.lower[a] - 0.3
+    q[0, b] = c.desc0.upper[b] + 0.3
+    return view.new(q, 1)
+
+
+def retime_inputs(view, seed=None):
+    """(plans (5, ndof, T), vmax, amax) in the view's numbering: smooth random plans (retime_ref.random_plans on the original
+    robot); the first actuated joint stands still in plan 1 and the last in plan 2; every third joint has no velocity limit."""
+    import retime_ref as tr
+    c = view.case
+    d = c.desc0
+    plans = tr.random_plans(d, 5, c.T, seed=RETIME_SEEDS.get(c.name, 0) if seed is None else seed)
+    plans[1, 0] = plans[1, 0, 0]
+    plans[2, d.ndof - 1] = plans[2, d.ndof - 1, 0]
+    rng = np.random.default_rng(c.T)
+    vmax = rng.uniform(0.8, 1.6, d.ndof)
+    vmax[::3] = np.inf
+    amax = rng.uniform(0.4, 0.9, d.ndof)
+    return view.new(plans, 1), view.new(vmax, 0), view.new(amax, 0)
+
+
+RETIME_SEEDS = {}   # case -> seed of retime_ref.random_plans where 0 does not converge at every plan
+
+
+def seed_goalset_case(case, n_max=5):
+    """Inputs of gto_seed_goalsets_device in the ORIGINAL numbering, as tests/small_robots.seed_goalset_case draws them for four
+    instances, for the case's B: (qc, q_solutions, goals, n_goals, accept, scene ids, bases) with every row accepted in
+    instance 0, an empty mask in 1, two copies of one solution in 2 (ties in cost and distance), a NaN solution in 3, ragged
+    counts.  The solutions' parameter joints differ from qc's: the candidates have to pin them from qc."""
+    d = case.desc0
+    rng = np.random.default_rng(500 + case.seed + case.T)
+    qc = case.qc + rng.uniform(-0.02, 0.02, case.qc.shape)
+    qs = rng.uniform(0.9 * d.lower, 0.9 * d.upper, (case.B, n_max, d.ndof))
+    goals = rng.standard_normal((case.B, n_max, 16))
+    n_goals = np.array([n_max, n_max, n_max, 2, 3, 1, n_max, 4][:case.B], dtype=np.int32)
+    accept = (rng.random((case.B, n_max)) < 0.7).astype(np.uint8)
+    accept[0] = 1
+    accept[1] = 0
+    qs[2, 1] = qs[2, 0]
+    qs[2, 3] = qs[2, 0]
+    accept[2] = 1
+    qs[3, 0, int(d.opt_index[-1])] = np.nan
+    accept[3, :2] = 1
+    return qc, qs, goals, n_goals, accept, np.zeros(case.B, dtype=np.int32), case.base.copy()
+
+PATH_COLUMNS = 65   # the path of a 64-step lift: more columns than any case's horizon
+# (case, kind, columns) -> seed of cloud_cases.plan_cloud's samples where 0 leaves an undecided point
+PLAN_SEEDS = {("r9", "cloud", 65): 1, ("panda", "cloud", 65): 1, ("r55", "cloud", 14): 1}
+
+
+def plan_inputs(v0, o0, kind, T):
+    """What gto_check_plans / gto_check_paths run on, in the original numbering: depth_cases.plan_instance ("depth") or
+    cloud_cases.plan_cloud ("cloud") on the ORIGINAL robot (v0, with its oracle o0) over T columns -> (instance, the plans with
+    the instance's NaN planted, {"shared", "per_plan"} -> the oracle's counts (3, T), undecided points in all)."""
+    import cloud_cases as cc
+    import depth_cases as dc
+    world_points = lambda q, base: o0.eval_points(0, q, base, want_field=False)[0]
+    name, key = v0.name, 30 + list(CASES).index(v0.name)   # (keys 0 .. 17 are depth_cases' and small_robots')
+    if kind == "depth":
+        inst, expected = dc.plan_instance(name, v0.desc, T, world_points, key=key), dc.plan_expected
+    else:
+        inst = cc.plan_cloud(name, v0.desc, T, world_points, seed=PLAN_SEEDS.get((name, kind, T), 0), key=key)
+        expected = cc.plan_expected
+    want, undecided = {}, 0
+    for label, bases in (("shared", inst.base), ("per_plan", inst.bases)):
+        want[label], n = expected(inst, v0.desc, world_points, bases)
+        undecided += n
+    poisoned = inst.plans.copy()
+    poisoned[inst.nan_at] = np.nan
+    return inst, poisoned, want, undecided

@@ -1,0 +1,270 @@
+"""CPU: the cases of tests/renumbered_robots.py are what they are chosen for; the FP64 oracle and the numpy restatements
+give, on a robot with renumbered joints, the original robot's results with the joint axes permuted -- bit for bit where
+nothing is summed over joints and in the chain-order variant, and with equal iteration counts and statuses and values within
+the tolerance of the GPU test of the same entry point (tests/test_gpu_parity.py:1-10, :577-589; tests/test_gpu_small_robots.py
+for the base placement and the pose goals; tests/test_gpu_retrieve.py for the lift) in the sorted variant; gto_create accepts
+every renumbered descriptor and refuses an opt_index that names a joint twice.  So the GPU suite
+(tests/test_gpu_renumbered_robots.py) can compare iteration counts for equality and needs no case set aside."""
+import copy
+import re
+
+import numpy as np
+import pytest
+
+import ik_pose_ref as pref
+import renumbered_robots as rn
+import retrieve_ref as rr
+import small_robots as sr
+
+CASE_VARIANTS = [(name, v) for name in rn.CASES for v in rn.VARIANTS]
+NARROW_VARIANTS = [(name, v) for name in rn.NARROW for v in rn.VARIANTS]
+
+
+@pytest.fixture(scope="module")
+def cases(oracle_mod):
+    made = {}
+
+    def get(name):
+        if name not in made:
+            c = rn.Case(oracle_mod, name)
+            c.oracles = {}
+            made[name] = c
+        return made[name]
+    return get
+
+
+def oracle_of(oracle_mod, case, variant):
+    if variant not in case.oracles:
+        case.oracles[variant] = case.view(variant).oracle(oracle_mod)
+    return case.oracles[variant]
+
+
+def same(a, b):
+    return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+
+
+# ------------------------------------------------------------------------------------------------- the cases themselves
+def test_the_cases_are_what_they_are_chosen_for(cases):
+    for name in rn.CASES:
+        c = cases(name)
+        d0 = c.desc0
+        assert 12 <= c.T <= 20 and 4 <= c.B <= 8 and c.T + rn.OFFSET - 10 >= 0
+        assert (np.abs(c.base) >= 0.02).all() and sorted(set(c.n_goals_ragged.tolist())) == [1, 2, 3]
+        # the originals sit in the easy corner: ascending, and slot order = chain (frame) order
+        frame_of = {int(d0.q_index[f]): f for f in range(d0.n_frames) if d0.joint_type[f] != 0}
+        assert len(frame_of) == d0.ndof                                  # no two frames share a joint
+        chain_frames = [frame_of[int(j)] for j in d0.opt_index]
+        assert chain_frames == sorted(chain_frames) and d0.opt_index.tolist() == sorted(d0.opt_index.tolist())
+        for variant in rn.VARIANTS:
+            v = c.view(variant)
+            d = v.desc
+            assert sorted(d.opt_index.tolist() + d.param_index.tolist()) == list(range(d.ndof))
+            assert d.param_index.tolist() == sorted(d.param_index.tolist())
+            frames = [next(f for f in range(d.n_frames) if d.q_index[f] == j) for j in d.opt_index]
+            if variant == "chain":      # slots as they were, numbers not ascending
+                assert frames == chain_frames and d.opt_index.tolist() != sorted(d.opt_index.tolist())
+                assert (v.sigma == np.arange(d.n_opt)).all()
+            else:                       # numbers ascending, slots no longer in chain order
+                assert d.opt_index.tolist() == sorted(d.opt_index.tolist()) and frames != sorted(frames)
+                assert [chain_frames[s] for s in v.sigma] == frames and (v.sigma != np.arange(d.n_opt)).any()
+            for f in range(d.n_frames):  # the same joint, under its new number, with its own limits and name
+                if d0.q_index[f] >= 0:
+                    j0, j = int(d0.q_index[f]), int(d.q_index[f])
+                    assert j == c.pi[j0] and d.lower[j] == d0.lower[j0] and d.upper[j] == d0.upper[j0]
+                    assert d.actuated_joint_names[j] == d0.actuated_joint_names[j0]
+                    assert (j in d.opt_index) == (j0 in d0.opt_index)
+            if name not in ("panda", "r55"):   # parameter joints between the optimised ones
+                assert any(d.opt_index.min() < p < d.opt_index.max() for p in d.param_index)
+            x = np.arange(d.ndof) * 1.5
+            assert same(v.old(v.new(x, 0), 0), x) and v.new(x, 0)[c.pi[1]] == x[1]
+    d = {n: cases(n).desc0 for n in rn.CASES}
+    prismatic_opt = lambda r: any(r.joint_type[f] == 2 and r.q_index[f] in set(r.opt_index.tolist()) for f in range(r.n_frames))
+    assert (d["r1"].n_opt, d["r1"].ndof) == (6, 8) and prismatic_opt(d["r1"])
+    assert (d["r9"].n_opt, d["r9"].ndof) == (8, 9)
+    assert (d["r3"].n_opt, d["r3"].ndof, d["r3"].n_frames) == (3, 16, 21)
+    assert d["r55"].n_opt == 10 and all(d[n].n_opt <= 8 for n in rn.NARROW)
+    pv = cases("panda").view("sorted").desc
+    assert pv.param_index.tolist() == [0, 1] and [pv.actuated_joint_names[j] for j in pv.opt_index] == [f"panda_joint{k}" for k in range(7, 0, -1)]
+    for name in rn.NARROW:   # the closed joints are parameter joints, at distinct non-zero values
+        v = cases(name).view("sorted")
+        assert v.closed_joints and set(v.closed_joints) <= set(v.desc.param_index.tolist())
+        assert len(set(v.closed_values)) == len(v.closed_values) and 0.0 not in v.closed_values
+
+
+# ------------------------------------------------------------------------------------------------- evaluation: bit for bit
+@pytest.mark.parametrize("name,variant", CASE_VARIANTS)
+def test_oracle_evaluation_is_invariant_bit_for_bit(cases, oracle_mod, name, variant):
+    c = cases(name)
+    v0, v = c.view("original"), c.view(variant)
+    o0, o = oracle_of(oracle_mod, c, "original"), oracle_of(oracle_mod, c, variant)
+    q = np.random.default_rng(3).uniform(c.desc0.lower, c.desc0.upper, size=(6, c.desc0.ndof))
+    assert same(o.eval_fk(v.new(q, 1)), o0.eval_fk(q))
+    for use_obs in (False, True):
+        for x, y in zip(o.eval_points(0, v.qc, v.base[0], use_obs=use_obs), o0.eval_points(0, v0.qc, v0.base[0], use_obs=use_obs)):
+            assert same(x, y)
+    cost, dist = o.plan_cost(0, v.Q0, v.base[1])
+    cost0, dist0 = o0.plan_cost(0, v0.Q0, v0.base[1])
+    assert same(cost, cost0)
+    # the distance |q_0 - q_{T-1}| is a sum of squares over the actuated joints in joint order (orc_plan_cost): renumbering
+    # reorders it in both variants, so it is held to the 1e-14 of tests/test_gpu_parity.py::test_plan_cost_vs_oracle
+    np.testing.assert_allclose(dist, dist0, rtol=1e-14, atol=0)
+
+
+# ------------------------------------------------------------------------------------------------- the solves
+def _compare(label, variant, got, want, tols):
+    """got / want: (values in the original numbering ..., iterations, status); tols: (rtol, atol) per value.  The chain-order
+    variant: every array bit for bit."""
+    worst = [float(np.nanmax(np.abs(np.asarray(g, dtype=np.float64) - w))) if np.size(w) else 0.0 for g, w in zip(got[:-2], want[:-2])]
+    print(f"{label} [{variant}]: iterations {np.asarray(want[-2]).ravel().tolist()} max |renumbered - original| {worst}")
+    assert np.array_equal(got[-2], want[-2]) and np.array_equal(got[-1], want[-1]), label
+    if variant == "chain":
+        for g, w in zip(got, want):
+            assert same(g, w), label
+    else:
+        for g, w, (rtol, atol) in zip(got[:-2], want[:-2], tols):
+            np.testing.assert_allclose(g, w, rtol=rtol, atol=atol, err_msg=label)
+
+
+@pytest.mark.parametrize("name,variant", CASE_VARIANTS)
+def test_oracle_trajectory_solve_is_invariant(cases, oracle_mod, name, variant):
+    c = cases(name)
+    v0, v = c.view("original"), c.view(variant)
+    o0, o = oracle_of(oracle_mod, c, "original"), oracle_of(oracle_mod, c, variant)
+    nt = o.usable_cores()
+    for ragged in (False, True):
+        Q0, dQ0, f0, it0, st0 = o0.solve_batch(*v0.solve_args(ragged), n_threads=nt)
+        Q, dQ, f, it, st = o.solve_batch(*v.solve_args(ragged), n_threads=nt)
+        assert np.isin(st0, (0, 1)).all() and (it0 > 1).all()
+        _compare(f"solve_batch ragged={ragged}", variant, (v.old(Q, 1), f, it, st), (Q0, f0, it0, st0), [(0, 1e-6), (1e-8, 0)])
+        if variant == "chain":
+            assert same(v.old(dQ, 1), dQ0)
+
+
+@pytest.mark.parametrize("name,variant", NARROW_VARIANTS)
+def test_oracle_ik_and_base_placement_are_invariant(cases, oracle_mod, name, variant):
+    c = cases(name)
+    v0, v = c.view("original"), c.view(variant)
+    o0, o = oracle_of(oracle_mod, c, "original"), oracle_of(oracle_mod, c, variant)
+    nt = o.usable_cores()
+    for sid in (None, 0):
+        a = o0.solve_ik_batch(sid, rn.ik_start(v0), v0.goals[:, 0], v0.base, max_iter=rn.IK_MAX_ITER, n_threads=nt)
+        b = o.solve_ik_batch(sid, rn.ik_start(v), v.goals[:, 0], v.base, max_iter=rn.IK_MAX_ITER, n_threads=nt)
+        assert np.isin(a[3], (0, 1)).all()
+        _compare(f"solve_ik_batch scene={sid}", variant, (v.old(b[0], 1), b[1], b[2], b[3]), a, [(0, 1e-6), (1e-8, 1e-12)])
+    a = o0.solve_base_batch(v0.qc, v0.goals_all, v0.n_goals_ragged, 0.01, max_iter=rn.BASE_MAX_ITER, n_threads=nt)
+    b = o.solve_base_batch(v.qc, v.goals_all, v.n_goals_ragged, 0.01, max_iter=rn.BASE_MAX_ITER, n_threads=nt)
+    assert np.isin(a[4], (0, 1)).all()
+    _compare("solve_base_batch", variant, (b[0], v.old(b[1], 2), b[2], b[3], b[4]), a, [(0, 1e-6), (0, 1e-6), (1e-7, 1e-12)])
+
+
+@pytest.mark.parametrize("goal_kind", [pref.GTO_IK_GOAL_QUATERNION, pref.GTO_IK_GOAL_RPY])
+@pytest.mark.parametrize("name,variant", NARROW_VARIANTS)
+def test_pose_restatement_is_invariant(cases, oracle_mod, name, variant, goal_kind):
+    c = cases(name)
+    v0, v = c.view("original"), c.view(variant)
+    a = sr.pose_restatement(v0, oracle_of(oracle_mod, c, "original"), goal_kind, max_iter=rn.POSE_MAX_ITER)
+    b = sr.pose_restatement(v, oracle_of(oracle_mod, c, variant), goal_kind, max_iter=rn.POSE_MAX_ITER)
+    _compare(f"ik_pose_ref.solve kind={goal_kind}", variant, (v.old(b[0], 1), b[1], b[2], b[3]), a, [(0, 1e-9), (1e-10, 1e-15)])
+
+
+def oracle_lift(oracle_mod, c, variant):
+    """retrieve_ref.lift_chain on the oracle of a view, with the board as scene 1 on Panda -> (result, plans, scene id)."""
+    v, o = c.view(variant), oracle_of(oracle_mod, c, variant)
+    plans, scene = rn.lift_plans(v, oracle_of(oracle_mod, c, "original").eval_fk)
+    sid = 0
+    if scene is not None:
+        o.set_scene(1, *scene)
+        sid = 1
+    r = rr.lift_chain(o, v.desc, v.ee, plans, rn.LIFT_DISTANCE, rn.LIFT_K, rn.LIFT_DIRECTION, v.closed_joints, v.closed_values,
+                      scene_id=sid, base_pos=rn.lift_bases(v, len(plans)), max_iter=rn.LIFT_MAX_ITER)
+    return r, plans, sid
+
+
+@pytest.mark.parametrize("name,variant", NARROW_VARIANTS)
+def test_oracle_lift_chain_is_invariant(cases, oracle_mod, name, variant):
+    c = cases(name)
+    v = c.view(variant)
+    a, plans0, _ = oracle_lift(oracle_mod, c, "original")
+    b, plans, _ = oracle_lift(oracle_mod, c, variant)
+    assert np.isfinite(a["path"]).all() and (a["status"] != rr.STATUS_NUMERICAL).all()
+    cj0 = c.view("original").closed_joints
+    assert (a["path"][:, cj0, :] == np.asarray(rn.CLOSED_VALUES[:len(cj0)])[None, :, None]).all()
+    j = int(c.desc0.opt_index[1])   # the joint that ends out of limits: kept in column 0, clipped from column 1 on
+    assert a["path"][-1, j, 0] > c.desc0.upper[j] and (a["path"][-1, j, 1:] <= c.desc0.upper[j]).all()
+    assert np.array_equal(a["reached"], b["reached"])
+    _compare("lift_chain", variant, (v.old(b["path"], 1), b["goals"], b["err_pos"], b["iters"], b["status"]),
+             (a["path"], a["goals"], a["err_pos"], a["iters"], a["status"]), [(0, 1e-6), (0, 1e-12), (0, 1e-9)])
+    assert same(rr.reverse_path(plans, rn.OFFSET, v.closed_joints, v.closed_values),
+                v.new(rr.reverse_path(plans0, rn.OFFSET, cj0, rn.CLOSED_VALUES[:len(cj0)]), 1))
+
+
+@pytest.mark.parametrize("kind", ["depth", "cloud"])
+@pytest.mark.parametrize("name", list(rn.CASES))
+def test_plan_inputs_leave_no_point_undecided(cases, oracle_mod, name, kind):
+    """The plans of gto_check_plans and the 65-column paths of gto_check_paths: every count is decided by more than 1e-9 m, some
+    waypoints count nothing and some count points, and the NaN's waypoint is marked."""
+    c = cases(name)
+    v0 = c.view("original")
+    for T in (c.T, rn.PATH_COLUMNS):
+        assert T == c.T or T > c.T
+        inst, poisoned, want, undecided = rn.plan_inputs(v0, oracle_of(oracle_mod, c, "original"), kind, T)
+        assert undecided == 0 and poisoned.shape == (3, c.desc0.ndof, T) and np.isnan(poisoned).sum() == 1
+        p, _, t = inst.nan_at
+        for counts in want.values():
+            assert counts.shape == (3, T) and counts[p, t] == -1 and (counts > 0).any() and (counts == 0).any()
+        assert np.abs(inst.bases).min() > 0 and not same(want["shared"], want["per_plan"])
+
+
+@pytest.mark.parametrize("name", rn.NARROW)
+def test_retime_inputs_converge_in_the_restatement(cases, name):
+    """tests/retime_ref.py on the plans of gto_retime_batch: every profile converges, in every numbering, to the same bits of
+    the time grid (it takes minima over the joints' lines) and to permuted samples."""
+    import retime_ref as tr
+    c = cases(name)
+    plans0, vm0, am0 = rn.retime_inputs(c.view("original"))
+    assert np.isinf(vm0).any() and np.isfinite(vm0).any() and (np.ptp(plans0[1, 0]) == 0) and (np.ptp(plans0[2, -1]) == 0)
+    r0 = tr.retime(plans0, vm0, am0, 2, 16)
+    assert (r0["status"] == 0).all() and (r0["duration"] > 0).all()
+    for variant in rn.VARIANTS:
+        v = c.view(variant)
+        plans, vm, am = rn.retime_inputs(v)
+        assert same(v.old(plans, 1), plans0) and same(v.old(vm, 0), vm0) and same(v.old(am, 0), am0)
+        r = tr.retime(plans, vm, am, 2, 16)
+        assert (r["status"] == 0).all()
+        np.testing.assert_allclose(r["t_grid"], r0["t_grid"], rtol=1e-9)     # RTOL of tests/test_gpu_retime.py
+        np.testing.assert_allclose(v.old(r["q"], 2), r0["q"], rtol=0, atol=1e-12)   # PATH_ATOL there
+
+
+# ------------------------------------------------------------------------------------------------- gto_create
+@pytest.fixture(scope="module")
+def capi():
+    import __graft_entry__ as g
+    g.build()
+    from grasptrajopt_amd import _capi
+    return _capi
+
+
+def _create(capi, v, desc=None):
+    """'accepted' or the error text of gto_create (which validates before it looks for a device: tests/test_limits_cpu.py)."""
+    try:
+        h = capi.SolverHandle(v.desc if desc is None else desc, v.ee, v.gripper, v.opts, device=0, n_gripper_points=v.ngp)
+    except capi.GTOError as e:
+        if "(-3): no HIP device" in str(e):
+            return "accepted"
+        return str(e)
+    h.close()
+    return "accepted"
+
+
+@pytest.mark.parametrize("name", list(rn.CASES))
+def test_gto_create_accepts_renumbered_descriptors_and_refuses_a_repeated_opt_index(cases, capi, name):
+    c = cases(name)
+    for variant in ("original",) + rn.VARIANTS:
+        assert _create(capi, c.view(variant)) == "accepted", variant
+    twice = r"^gto_create failed \(-1\): " + re.escape("opt_index names a joint twice") + "$"
+    for variant in rn.VARIANTS:
+        v = c.view(variant)
+        for src, dst in ((0, v.desc.n_opt - 1), (v.desc.n_opt - 1, 0), (1, 2)):
+            d = copy.deepcopy(v.desc)
+            d.opt_index[dst] = d.opt_index[src]
+            assert re.match(twice, _create(capi, v, d)), (variant, src, dst, _create(capi, v, d))
