@@ -158,6 +158,8 @@ def _prototypes():
         "gto_retrieve_path_columns": (I, [V]),
         "gto_check_paths": (I, [V, V, I32, I32, _pd, _pd, I32, _pi]),
         "gto_check_paths_device": (I, [V, V, I32, I32, V, _pd, I32, V, V]),
+        "gto_retime_paths": (I, [V, I32, I32, _pd, _pi, _pd, _pd, I32, I32, _pd, _pd, _pd, _pd, _pd, _pd, _pi]),
+        "gto_retime_paths_device": (I, [V, I32, I32, V, V, _pd, _pd, I32, I32] + [V] * 8),
     }
 
 
@@ -915,3 +917,37 @@ class SolverHandle:
                                                      int(n_samples), _vp(duration_out), _vp(t_grid_out), _vp(sd_grid_out),
                                                      _vp(q_out), _vp(qd_out), _vp(qdd_out), _vp(status_out), _vp(stream)),
                     "gto_retime_batch_device")
+
+    def retime_paths(self, paths, vmax, amax, n_cols=None, subdiv: int = 2, n_samples: int = 100):
+        """gto_retime_paths: retime_batch for paths (B, ndof, Tp) of any length Tp >= 2, on any handle.  n_cols (B,) int:
+        path b is its first n_cols[b] columns (None: all Tp); the rest is ignored.  Returns the dict of retime_batch with
+        t_grid / sd_grid (B, Nmax), Nmax = subdiv (Tp-1) + 1: past a path's own subdiv (n_cols[b]-1) + 1 gridpoints they hold
+        the duration and 0.  A count outside [1, Tp] raises."""
+        d = self.desc
+        paths = _f64(paths)
+        if paths.ndim != 3 or paths.shape[1] != d.ndof:
+            raise ValueError(f"retime_paths: paths must be (B, {d.ndof}, Tp), got {paths.shape}")
+        B, Tp, M = paths.shape[0], paths.shape[2], int(n_samples)
+        N = max(int(subdiv) * (Tp - 1) + 1, 0)
+        nc = None if n_cols is None else _per_instance(n_cols, B)
+        vm, am = self._retime_limits(vmax, amax)
+        out = dict(duration=np.empty(B), t_grid=np.empty((B, N)), sd_grid=np.empty((B, N)),
+                   q=np.empty((B, max(M, 0), d.ndof)), qd=np.empty((B, max(M, 0), d.ndof)), qdd=np.empty((B, max(M, 0), d.ndof)),
+                   status=np.empty(B, dtype=np.int32))
+        self._check(self.lib.gto_retime_paths(self._h, B, Tp, _p(paths, _pd), _p(nc, _pi), _p(vm, _pd), _p(am, _pd), int(subdiv), M,
+                                              _p(out["duration"], _pd), _p(out["t_grid"], _pd), _p(out["sd_grid"], _pd),
+                                              _p(out["q"], _pd), _p(out["qd"], _pd), _p(out["qdd"], _pd),
+                                              _p(out["status"], _pi)), "gto_retime_paths")
+        return out
+
+    def retime_paths_device(self, B, Tp, paths, vmax, amax, n_cols=None, subdiv=2, n_samples=100, duration_out=None,
+                            t_grid_out=None, sd_grid_out=None, q_out=None, qd_out=None, qdd_out=None, status_out=None,
+                            stream=None):
+        """gto_retime_paths_device: paths (B, ndof, Tp), n_cols (B,) int32 and the outputs are device pointers (ints, e.g.
+        torch.Tensor.data_ptr()) or None; vmax / amax are host values.  A count outside [1, Tp] is not seen by the host:
+        that path gets GTO_STATUS_NUMERICAL and NaN."""
+        vm, am = self._retime_limits(vmax, amax)
+        self._check(self.lib.gto_retime_paths_device(self._h, int(B), int(Tp), _vp(paths), _vp(n_cols), _p(vm, _pd), _p(am, _pd),
+                                                     int(subdiv), int(n_samples), _vp(duration_out), _vp(t_grid_out),
+                                                     _vp(sd_grid_out), _vp(q_out), _vp(qd_out), _vp(qdd_out), _vp(status_out),
+                                                     _vp(stream)), "gto_retime_paths_device")

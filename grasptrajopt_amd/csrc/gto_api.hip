@@ -230,7 +230,8 @@ struct gto_handle {
   // published (the prior of the next call's launches until its own counts arrive)
   double items_per_job_prior = 0.0;
   std::mutex* prof_mu = nullptr;  // set while a call with several lanes (host threads) runs: guards the profiling records
-  // retiming (gto_retime_batch_device): Thomas factors of the not-a-knot system for this T, workspace grown on demand
+  // retiming (gto_retime_paths_device): Thomas factors of the not-a-knot system for every column count, workspace grown on
+  // demand
   DevBuf rt_fac, rt_S, rt_flag, rt_P1, rt_P2, rt_cap, rt_X, rt_T, rt_stat;
   bool rt_fac_ready = false;
   // collision checks against a cloud observation (gto_check_plans_device): world points, votes and per-plan bases of a chunk
@@ -3295,64 +3296,72 @@ int gto_get_scene_fields(gto_handle* h, int32_t scene_id, float* c_all_out, floa
 // ------------------------------------------------------------------ retiming under joint velocity / acceleration limits
 // (convert_plan_to_trajectory_toppra, gto/utils.py:283-323; kernels: gto_retime.h)
 
-// Thomas factors of the not-a-knot system of T uniform knots, scaled by 1/h: rows [1 2], [1 4 1] ... [1 4 1], [2 1]
-// (scipy.interpolate.CubicSpline's banded system for n >= 4; gto_create guarantees T >= 4).  [3][T]: multiplier, reciprocal
-// pivot and upper entry of every row.
-static std::vector<double> retime_factors(int T) {
-  std::vector<double> f(3 * (size_t)T, 0.0);
-  double* lo = f.data();
-  double* inv = lo + T;
-  double* up = lo + 2 * T;
+// Thomas factors of the not-a-knot system of uniform knots, scaled by 1/h: rows [1 2], [1 4 1] ... [1 4 1], [2 1]
+// (scipy.interpolate.CubicSpline's banded system for n >= 4).  Rows 0 .. C-2 do not depend on the number of knots C, so one
+// table of interior rows serves every C <= GTO_RETIME_MAX_N.  [4][GTO_RETIME_MAX_N] (GTO_RT_FAC_*): multiplier, reciprocal
+// pivot, upper entry and pivot of row i.  The last row of a system of C knots is k_retime_spline's, per lane:
+//   lo = 2 / piv[C-2];  piv = 1 - lo * up[C-2];  inv = 1 / piv      (the order of operations of the interior rows below)
+static std::vector<double> retime_factors() {
+  const int L = GTO_RETIME_MAX_N;
+  std::vector<double> f(4 * (size_t)L, 0.0);
+  double* lo = f.data() + GTO_RT_FAC_LO * L;
+  double* inv = f.data() + GTO_RT_FAC_INV * L;
+  double* up = f.data() + GTO_RT_FAC_UP * L;
+  double* pv = f.data() + GTO_RT_FAC_PIV * L;
   double piv = 1.0;
   up[0] = 2.0;
   inv[0] = 1.0 / piv;
-  for (int i = 1; i < T; ++i) {
-    const double sub = i == T - 1 ? 2.0 : 1.0, diag = i == T - 1 ? 1.0 : 4.0;
-    up[i] = i == T - 1 ? 0.0 : 1.0;
-    lo[i] = sub / piv;
-    piv = diag - lo[i] * up[i - 1];
+  pv[0] = piv;
+  for (int i = 1; i < L; ++i) {
+    up[i] = 1.0;
+    lo[i] = 1.0 / piv;
+    piv = 4.0 - lo[i] * up[i - 1];
     inv[i] = 1.0 / piv;
+    pv[i] = piv;
   }
   return f;
 }
 
-static int retime_check(gto_handle* h, int32_t B, const double* vmax, const double* amax, int32_t subdiv, int32_t M,
-                        RetimeLimits& lim, RetimeDims& d) {
-  const int ndof = h->rb.ndof, T = h->opts.T;
-  if (B < 0) return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: B must be >= 0");
-  if (!vmax || !amax) return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: null limit array");
+// what an entry point calls itself, its column count and its input array in error messages
+struct RetimeNames {
+  const char *fn, *T, *array;
+};
+static const RetimeNames RETIME_BATCH = {"gto_retime_batch", "T", "plans"}, RETIME_PATHS = {"gto_retime_paths", "Tp", "paths"};
+
+static int retime_check(gto_handle* h, const RetimeNames& nm, int32_t B, int32_t Tp, const double* vmax, const double* amax,
+                        int32_t subdiv, int32_t M, RetimeLimits& lim, RetimeDims& d) {
+  const int ndof = h->rb.ndof;
+  const std::string f = std::string(nm.fn) + ": ", Tname = nm.T;
+  if (B < 0) return fail(h, GTO_ERR_INVALID_ARG, f + "B must be >= 0");
+  if (Tp < 2) return fail(h, GTO_ERR_INVALID_ARG, f + Tname + " must be >= 2");
+  if (!vmax || !amax) return fail(h, GTO_ERR_INVALID_ARG, f + "null limit array");
   for (int j = 0; j < ndof; ++j) {
-    if (!(vmax[j] > 0.0)) return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: vmax must be > 0 (+inf: no limit)");
-    if (!(amax[j] > 0.0) || !std::isfinite(amax[j]))
-      return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: amax must be finite and > 0");
+    if (!(vmax[j] > 0.0)) return fail(h, GTO_ERR_INVALID_ARG, f + "vmax must be > 0 (+inf: no limit)");
+    if (!(amax[j] > 0.0) || !std::isfinite(amax[j])) return fail(h, GTO_ERR_INVALID_ARG, f + "amax must be finite and > 0");
     lim.vmax[j] = vmax[j], lim.amax[j] = amax[j];
   }
-  if (subdiv < 1 || M < 2) return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: subdiv must be >= 1 and M >= 2");
-  const long long N = (long long)subdiv * (T - 1) + 1;
-  if (N > GTO_RETIME_MAX_N) return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: subdiv (T-1) + 1 must be <= 1024");
+  if (subdiv < 1 || M < 2) return fail(h, GTO_ERR_INVALID_ARG, f + "subdiv must be >= 1 and M >= 2");
+  const long long N = (long long)subdiv * (Tp - 1) + 1;
+  if (N > GTO_RETIME_MAX_N) return fail(h, GTO_ERR_INVALID_ARG, f + "subdiv (" + Tname + "-1) + 1 must be <= 1024");
   if ((long long)B * std::max<long long>(N, M) * std::max(ndof, 1) > (long long)INT32_MAX * 64)
-    return fail(h, GTO_ERR_UNSUPPORTED, "gto_retime_batch: batch too large for one call");
-  d.B = B, d.ndof = ndof, d.T = T, d.N = (int)N, d.subdiv = subdiv, d.M = M;
+    return fail(h, GTO_ERR_UNSUPPORTED, f + "batch too large for one call");
+  d.B = B, d.ndof = ndof, d.Tp = Tp, d.Nmax = (int)N, d.subdiv = subdiv, d.M = M;
   return GTO_OK;
 }
 
 static unsigned retime_blocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
-int gto_retime_batch_device(gto_handle* h, int32_t B, const double* plans, const double* vmax, const double* amax,
-                            int32_t subdiv, int32_t M, double* duration_out, double* t_grid_out, double* sd_grid_out,
-                            double* q_out, double* qd_out, double* qdd_out, int32_t* status_out, void* stream) {
-  if (!h) return GTO_ERR_INVALID_ARG;
-  RetimeLimits lim = {};
-  RetimeDims d = {};
-  int rc = retime_check(h, B, vmax, amax, subdiv, M, lim, d);
-  if (rc) return rc;
-  if (B == 0) return GTO_OK;
-  if (!plans) return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: null plans");
+// the four launches of a checked call (d, lim: retime_check's); n_cols: DEVICE [B] or NULL (every path has Tp columns)
+static int retime_launch(gto_handle* h, const RetimeDims& d, const RetimeLimits& lim, const double* plans,
+                         const int32_t* n_cols, double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out,
+                         double* qd_out, double* qdd_out, int32_t* status_out, void* stream) {
+  int rc;
+  const int B = d.B, M = d.M;
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-  const size_t T = d.T, N = d.N, nd = d.ndof, nB = (size_t)B;
-  if (!h->rt_fac_ready) {  // once per handle (T is fixed for its lifetime)
-    const std::vector<double> f = retime_factors(d.T);
+  const size_t T = d.Tp, N = d.Nmax, nd = d.ndof, nB = (size_t)B;
+  if (!h->rt_fac_ready) {  // once per handle: the table serves every column count
+    const std::vector<double> f = retime_factors();
     if ((rc = ensure(h, h->rt_fac, f.size() * sizeof(double)))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->rt_fac.get(), f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(h, hipStreamSynchronize(st));
@@ -3370,35 +3379,59 @@ int gto_retime_batch_device(gto_handle* h, int32_t B, const double* plans, const
   double *X = h->rt_X.as<double>(), *Tg = h->rt_T.as<double>();
   int32_t *flag = h->rt_flag.as<int32_t>(), *stat = h->rt_stat.as<int32_t>();
   hipLaunchKernelGGL(k_retime_spline, dim3(retime_blocks((long long)B * nd, 256)), dim3(256), 0, st, plans,
-                     h->rt_fac.as<const double>(), d, S, flag);
-  hipLaunchKernelGGL(k_retime_grid, dim3(retime_blocks((long long)B * N, 256)), dim3(256), 0, st, plans, S, flag, lim, d,
-                     P1, P2, cap);
-  hipLaunchKernelGGL(k_retime_pass, dim3(B), dim3(64), 0, st, P1, P2, cap, flag, lim, d, X, Tg, stat, duration_out,
-                     t_grid_out, sd_grid_out, status_out);
+                     h->rt_fac.as<const double>(), n_cols, d, S, flag);
+  hipLaunchKernelGGL(k_retime_grid, dim3(retime_blocks((long long)B * N, 256)), dim3(256), 0, st, plans, S, flag, n_cols, lim,
+                     d, P1, P2, cap);
+  hipLaunchKernelGGL(k_retime_pass, dim3(B), dim3(64), 0, st, P1, P2, cap, flag, n_cols, lim, d, X, Tg, stat,
+                     duration_out, t_grid_out, sd_grid_out, status_out);
   if (q_out || qd_out || qdd_out)
     hipLaunchKernelGGL(k_retime_sample, dim3(retime_blocks((long long)B * M, 256)), dim3(256), 0, st, plans, S, X, Tg, stat,
-                       d, q_out, qd_out, qdd_out);
+                       n_cols, d, q_out, qd_out, qdd_out);
   HIPCHK(h, hipGetLastError());
   return GTO_OK;
 }
 
-int gto_retime_batch(gto_handle* h, int32_t B, const double* plans, const double* vmax, const double* amax, int32_t subdiv,
-                     int32_t M, double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out, double* qd_out,
-                     double* qdd_out, int32_t* status_out) {
+// the device-pointer entry points: checks, then the launches
+static int retime_device(gto_handle* h, const RetimeNames& nm, int32_t B, int32_t Tp, const double* paths,
+                         const int32_t* n_cols, const double* vmax, const double* amax, int32_t subdiv, int32_t M,
+                         double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out, double* qd_out,
+                         double* qdd_out, int32_t* status_out, void* stream) {
   if (!h) return GTO_ERR_INVALID_ARG;
   RetimeLimits lim = {};
   RetimeDims d = {};
-  int rc = retime_check(h, B, vmax, amax, subdiv, M, lim, d);
+  int rc = retime_check(h, nm, B, Tp, vmax, amax, subdiv, M, lim, d);
   if (rc) return rc;
   if (B == 0) return GTO_OK;
-  if (!plans) return fail(h, GTO_ERR_INVALID_ARG, "gto_retime_batch: null plans");
+  if (!paths) return fail(h, GTO_ERR_INVALID_ARG, std::string(nm.fn) + ": null " + nm.array);
+  return retime_launch(h, d, lim, paths, n_cols, duration_out, t_grid_out, sd_grid_out, q_out, qd_out, qdd_out, status_out,
+                       stream);
+}
+
+// the host-pointer entry points: n_cols is a HOST array here (or NULL), checked before anything is staged
+static int retime_host(gto_handle* h, const RetimeNames& nm, int32_t B, int32_t Tp, const double* paths,
+                       const int32_t* n_cols, const double* vmax, const double* amax, int32_t subdiv, int32_t M,
+                       double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out, double* qd_out,
+                       double* qdd_out, int32_t* status_out) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  RetimeLimits lim = {};
+  RetimeDims d = {};
+  int rc = retime_check(h, nm, B, Tp, vmax, amax, subdiv, M, lim, d);
+  if (rc) return rc;
+  if (B == 0) return GTO_OK;
+  if (!paths) return fail(h, GTO_ERR_INVALID_ARG, std::string(nm.fn) + ": null " + nm.array);
+  if (n_cols)
+    for (int32_t b = 0; b < B; ++b)
+      if (n_cols[b] < 1 || n_cols[b] > Tp)
+        return fail(h, GTO_ERR_INVALID_ARG, std::string(nm.fn) + ": n_cols must lie in [1, Tp]");
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t nB = (size_t)B, nd = d.ndof, T = d.T, N = d.N, nM = (size_t)M;
+  const size_t nB = (size_t)B, nd = d.ndof, T = d.Tp, N = d.Nmax, nM = (size_t)M;
   Staging io(h);
-  const double* d_plans;
+  const double* d_paths;
+  const int32_t* d_nc;
   double *d_dur, *d_t, *d_sd, *d_q, *d_qd, *d_qdd;
   int32_t* d_st;
-  if ((rc = io.in(plans, nB * nd * T, &d_plans))) return rc;
+  if ((rc = io.in(paths, nB * nd * T, &d_paths))) return rc;
+  if ((rc = io.in(n_cols, nB, &d_nc))) return rc;
   if ((rc = io.out(duration_out, nB, &d_dur))) return rc;
   if ((rc = io.out(t_grid_out, nB * N, &d_t))) return rc;
   if ((rc = io.out(sd_grid_out, nB * N, &d_sd))) return rc;
@@ -3406,9 +3439,40 @@ int gto_retime_batch(gto_handle* h, int32_t B, const double* plans, const double
   if ((rc = io.out(qd_out, nB * nM * nd, &d_qd))) return rc;
   if ((rc = io.out(qdd_out, nB * nM * nd, &d_qdd))) return rc;
   if ((rc = io.out(status_out, nB, &d_st))) return rc;
-  rc = gto_retime_batch_device(h, B, d_plans, vmax, amax, subdiv, M, d_dur, d_t, d_sd, d_q, d_qd, d_qdd, d_st, nullptr);
-  if (rc) return rc;
+  if ((rc = retime_launch(h, d, lim, d_paths, d_nc, d_dur, d_t, d_sd, d_q, d_qd, d_qdd, d_st, nullptr))) return rc;
   return io.finish();
+}
+
+int gto_retime_paths_device(gto_handle* h, int32_t B, int32_t Tp, const double* paths, const int32_t* n_cols,
+                            const double* vmax, const double* amax, int32_t subdiv, int32_t M, double* duration_out,
+                            double* t_grid_out, double* sd_grid_out, double* q_out, double* qd_out, double* qdd_out,
+                            int32_t* status_out, void* stream) {
+  return retime_device(h, RETIME_PATHS, B, Tp, paths, n_cols, vmax, amax, subdiv, M, duration_out, t_grid_out,
+                       sd_grid_out, q_out, qd_out, qdd_out, status_out, stream);
+}
+
+int gto_retime_paths(gto_handle* h, int32_t B, int32_t Tp, const double* paths, const int32_t* n_cols, const double* vmax,
+                     const double* amax, int32_t subdiv, int32_t M, double* duration_out, double* t_grid_out,
+                     double* sd_grid_out, double* q_out, double* qd_out, double* qdd_out, int32_t* status_out) {
+  return retime_host(h, RETIME_PATHS, B, Tp, paths, n_cols, vmax, amax, subdiv, M, duration_out, t_grid_out,
+                     sd_grid_out, q_out, qd_out, qdd_out, status_out);
+}
+
+// plans of the handle's horizon: gto_retime_paths with Tp = T and every column used
+int gto_retime_batch_device(gto_handle* h, int32_t B, const double* plans, const double* vmax, const double* amax,
+                            int32_t subdiv, int32_t M, double* duration_out, double* t_grid_out, double* sd_grid_out,
+                            double* q_out, double* qd_out, double* qdd_out, int32_t* status_out, void* stream) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  return retime_device(h, RETIME_BATCH, B, h->opts.T, plans, nullptr, vmax, amax, subdiv, M, duration_out,
+                       t_grid_out, sd_grid_out, q_out, qd_out, qdd_out, status_out, stream);
+}
+
+int gto_retime_batch(gto_handle* h, int32_t B, const double* plans, const double* vmax, const double* amax, int32_t subdiv,
+                     int32_t M, double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out, double* qd_out,
+                     double* qdd_out, int32_t* status_out) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  return retime_host(h, RETIME_BATCH, B, h->opts.T, plans, nullptr, vmax, amax, subdiv, M, duration_out,
+                     t_grid_out, sd_grid_out, q_out, qd_out, qdd_out, status_out);
 }
 
 }  // extern "C"

@@ -1,11 +1,13 @@
-// gto_retime.h — time-optimal retiming of plans under joint velocity and acceleration limits (gto_retime_batch[_device],
-// include/gto_solver.h).  The reference's convert_plan_to_trajectory_toppra (gto/utils.py:283-323): a not-a-knot cubic
-// spline through the T waypoints on s in [0, 1], TOPP-RA's discretisation on a grid of N = subdiv (T-1) + 1 points
+// gto_retime.h — time-optimal retiming of paths under joint velocity and acceleration limits (gto_retime_paths[_device]
+// and gto_retime_batch[_device], include/gto_solver.h).  The reference's convert_plan_to_trajectory_toppra
+// (gto/utils.py:283-323): a not-a-knot cubic spline through the C waypoints of a path on s in [0, 1] (C per path: the
+// first n_cols[b] of the Tp columns a row holds), TOPP-RA's discretisation on a grid of N = subdiv (C-1) + 1 points
 // (x = sdot^2, u = sddot, x_{i+1} = x_i + 2 Delta u_i, constraints at the gridpoints), the controllable sets by a backward
 // pass, the greedy forward pass, constant acceleration between gridpoints, M samples of q, qdot, qddot.  FP64 throughout.
 //
 //   k_retime_spline   one lane per (plan, joint): slopes of the spline at the knots (the two substitutions of the
-//                     not-a-knot system, factored once per handle on the host), finite / moving flags
+//                     not-a-knot system, factored once per handle on the host for every count at once; the last row's
+//                     three factors per lane), the parabola at C = 3, the chord at C = 2, finite / moving flags
 //   k_retime_grid     one lane per (plan, gridpoint): p1 = q'(s), p2 = q''(s) of every joint, the bound on x that does
 //                     not involve u (velocity limits; acceleration limits of joints with p1 = 0)
 //   k_retime_pass     one wave per plan: backward pass (controllable sets) and forward pass (greedy profile), times.
@@ -13,6 +15,8 @@
 //                     every lower bound, and the pairs are spread over the lanes and reduced by a cross-lane min.  One
 //                     lane per plan (every pair in one lane) measured 0.6-0.1x of this rate and was dropped.
 //   k_retime_sample   one lane per (plan, sample): binary search over the gridpoint times, evaluation on the spline
+// Rows are laid out for the largest count: paths and slopes [B][ndof][Tp], grid arrays [B][Nmax], Nmax = subdiv (Tp-1) + 1.
+// Nothing a path's arithmetic uses depends on Tp or on its place in the batch.
 #pragma once
 #include "gto_device.h"
 
@@ -29,8 +33,21 @@ struct RetimeLimits {
 };
 
 struct RetimeDims {
-  int B, ndof, T, N, subdiv, M;
+  int B, ndof, Tp, Nmax, subdiv, M;  // Tp columns per row, Nmax = subdiv (Tp-1) + 1 gridpoints per row
 };
+
+// rows of the factor table, each GTO_RETIME_MAX_N long (retime_factors, gto_api.hip)
+#define GTO_RT_FAC_LO 0
+#define GTO_RT_FAC_INV 1
+#define GTO_RT_FAC_UP 2
+#define GTO_RT_FAC_PIV 3
+
+// Columns of path b: n_cols[b] (NULL: Tp).  A count outside [1, Tp] is a device value no host has seen: 0, and the path
+// is flagged GTO_RT_NONFINITE by the spline kernel, so that nothing downstream indexes with it.
+__device__ __forceinline__ int rt_cols(const int32_t* __restrict__ n_cols, long long b, int Tp) {
+  const int C = n_cols ? n_cols[b] : Tp;
+  return C >= 1 && C <= Tp ? C : 0;
+}
 
 // flags of a (plan, joint) row
 #define GTO_RT_CONST 0
@@ -50,41 +67,66 @@ __device__ __forceinline__ void rt_piece(const double* y, const double* s, int k
   p2 = 2.0 * c1 + 6.0 * c0 * r;
 }
 
-// Spline slopes.  fac [3][T]: the Thomas factors of the not-a-knot system scaled by 1/h (rows [1 2], [1 4 1] ..., [2 1]):
-// multiplier of row i, reciprocal pivot of row i, upper entry of row i.
+// Spline slopes of scipy's CubicSpline(..., bc_type="not-a-knot") through the C waypoints of a row.
+// C >= 4: fac [4][GTO_RETIME_MAX_N], the Thomas factors of the not-a-knot system scaled by 1/h (rows [1 2], [1 4 1] ...):
+// multiplier, reciprocal pivot, upper entry and pivot of row i as if it were an interior row, which rows 0..C-2 are for
+// every C.  The last row [2 1] is eliminated here, in retime_factors' order of operations (a division, a product and a
+// difference, a division: each rounded once, so the three values are the ones a table for this C alone would hold).
+// C == 3: the parabola through the three waypoints; C == 2: the chord (rt_piece then has c0 = c1 = 0 exactly, p2 = 0);
+// C == 1: slope 0.
 __global__ __launch_bounds__(256) void k_retime_spline(const double* __restrict__ Q, const double* __restrict__ fac,
-                                                       RetimeDims d, double* __restrict__ S, int32_t* __restrict__ flag) {
+                                                       const int32_t* __restrict__ n_cols, RetimeDims d,
+                                                       double* __restrict__ S, int32_t* __restrict__ flag) {
   const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= (long long)d.B * d.ndof) return;
-  const int T = d.T;
-  const double* y = Q + id * T;
-  double* s = S + id * T;
-  const double invh = (double)(T - 1);
+  const int C = rt_cols(n_cols, id / d.ndof, d.Tp);
+  if (C == 0) {
+    flag[id] = GTO_RT_NONFINITE;
+    return;
+  }
+  const double* y = Q + id * d.Tp;
+  double* s = S + id * d.Tp;
+  const double invh = (double)(C - 1);
   bool finite = true, moving = false;
   const double y0 = y[0];
-  for (int k = 0; k < T; ++k) {
+  for (int k = 0; k < C; ++k) {
     finite = finite && isfinite(y[k]);
     moving = moving || y[k] != y0;
   }
   flag[id] = !finite ? GTO_RT_NONFINITE : moving ? GTO_RT_MOVING : GTO_RT_CONST;
   if (!finite) return;
-  const double* lo = fac;
-  const double* inv = fac + T;
-  const double* up = fac + 2 * T;
+  if (C == 1) {
+    s[0] = 0.0;
+    return;
+  }
+  double mprev = (y[1] - y[0]) * invh;
+  if (C == 2) {
+    s[0] = mprev, s[1] = mprev;
+    return;
+  }
+  double mcur = (y[2] - y[1]) * invh;
+  if (C == 3) {
+    s[0] = 0.5 * (3.0 * mprev - mcur), s[1] = 0.5 * (mprev + mcur), s[2] = 0.5 * (3.0 * mcur - mprev);
+    return;
+  }
+  const double* lo = fac + GTO_RT_FAC_LO * GTO_RETIME_MAX_N;
+  const double* inv = fac + GTO_RT_FAC_INV * GTO_RETIME_MAX_N;
+  const double* up = fac + GTO_RT_FAC_UP * GTO_RETIME_MAX_N;
+  const double lo_last = 2.0 / fac[GTO_RT_FAC_PIV * GTO_RETIME_MAX_N + C - 2];
+  const double inv_last = 1.0 / __dsub_rn(1.0, __dmul_rn(lo_last, up[C - 2]));
   // forward substitution into s; right-hand sides from the chord slopes m_k
-  double mprev = (y[1] - y[0]) * invh, mcur = (y[2] - y[1]) * invh;
   double w = 0.5 * (5.0 * mprev + mcur);
   s[0] = w;
-  for (int i = 1; i < T - 1; ++i) {
+  for (int i = 1; i < C - 1; ++i) {
     if (i > 1) mprev = mcur, mcur = (y[i + 1] - y[i]) * invh;
     w = 3.0 * (mprev + mcur) - lo[i] * w;
     s[i] = w;
   }
-  w = 0.5 * (mprev + 5.0 * mcur) - lo[T - 1] * w;
+  w = 0.5 * (mprev + 5.0 * mcur) - lo_last * w;
   // back substitution
-  double sn = w * inv[T - 1];
-  s[T - 1] = sn;
-  for (int i = T - 2; i >= 0; --i) {
+  double sn = w * inv_last;
+  s[C - 1] = sn;
+  for (int i = C - 2; i >= 0; --i) {
     sn = (s[i] - up[i] * sn) * inv[i];
     s[i] = sn;
   }
@@ -101,18 +143,21 @@ __device__ __forceinline__ bool rt_line(double a, double b, double A, double& al
   return false;
 }
 
-// p1, p2 per (plan, gridpoint, joint) [B][N][ndof] and the x cap per (plan, gridpoint) [B][N]
+// p1, p2 per (plan, gridpoint, joint) [B][Nmax][ndof] and the x cap per (plan, gridpoint) [B][Nmax]; the points past a
+// path's own N = subdiv (C-1) + 1 are left alone (nobody reads them)
 __global__ __launch_bounds__(256) void k_retime_grid(const double* __restrict__ Q, const double* __restrict__ S,
-                                                     const int32_t* __restrict__ flag, RetimeLimits lim, RetimeDims d,
-                                                     double* __restrict__ P1, double* __restrict__ P2,
-                                                     double* __restrict__ xcap) {
+                                                     const int32_t* __restrict__ flag, const int32_t* __restrict__ n_cols,
+                                                     RetimeLimits lim, RetimeDims d, double* __restrict__ P1,
+                                                     double* __restrict__ P2, double* __restrict__ xcap) {
   const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (id >= (long long)d.B * d.N) return;
-  const long long b = id / d.N;
-  const int g = (int)(id - b * d.N), T = d.T, ndof = d.ndof;
-  const int k = min(g / d.subdiv, T - 2);
-  const double r = (double)(g - k * d.subdiv) / (double)(d.N - 1);
-  const double invh = (double)(T - 1);
+  if (id >= (long long)d.B * d.Nmax) return;
+  const long long b = id / d.Nmax;
+  const int g = (int)(id - b * d.Nmax), T = d.Tp, ndof = d.ndof;
+  const int C = rt_cols(n_cols, b, T), N = d.subdiv * (C - 1) + 1;
+  if (C == 0 || g >= N) return;
+  const int k = max(min(g / d.subdiv, C - 2), 0);  // C == 1: no row is moving, rt_piece is not called
+  const double r = (double)(g - k * d.subdiv) / (double)(N - 1);
+  const double invh = (double)(C - 1);
   double cap = INFINITY;
   for (int j = 0; j < ndof; ++j) {
     const long long row = b * ndof + j;
@@ -127,7 +172,7 @@ __global__ __launch_bounds__(256) void k_retime_grid(const double* __restrict__ 
         cap = fmin(cap, v * v);
       }
       double al, bl;
-      if (!rt_line(p1, p2, lim.amax[j], al, bl) && p2 != 0.0 && g < d.N - 1)  // |p2 x| <= amax: a bound on x alone
+      if (!rt_line(p1, p2, lim.amax[j], al, bl) && p2 != 0.0 && g < N - 1)  // |p2 x| <= amax: a bound on x alone
         cap = fmin(cap, lim.amax[j] / fabs(p2));
     }
     P1[id * ndof + j] = p1;
@@ -149,23 +194,26 @@ __device__ __forceinline__ double rt_pair(double au, double bu, double al, doubl
 }
 
 // One wave per plan.  Lines 0..nm-1: the moving joints (mj); line nm: the link to the next gridpoint,
-// upper u <= (X_{i+1} - x) / (2 Delta), lower u >= -x / (2 Delta).
+// upper u <= (X_{i+1} - x) / (2 Delta), lower u >= -x / (2 Delta).  Both passes run over the plan's own N gridpoints; the
+// outputs past them hold the duration and 0 (the path has ended and rests).
 __global__ __launch_bounds__(64) void k_retime_pass(const double* __restrict__ P1, const double* __restrict__ P2,
                                                     const double* __restrict__ xcap, const int32_t* __restrict__ flag,
-                                                    RetimeLimits lim, RetimeDims d, double* __restrict__ X,
-                                                    double* __restrict__ Tg, int32_t* __restrict__ stat,
-                                                    double* __restrict__ duration_out, double* __restrict__ t_out,
-                                                    double* __restrict__ sd_out, int32_t* __restrict__ status_out) {
+                                                    const int32_t* __restrict__ n_cols, RetimeLimits lim, RetimeDims d,
+                                                    double* __restrict__ X, double* __restrict__ Tg,
+                                                    int32_t* __restrict__ stat, double* __restrict__ duration_out,
+                                                    double* __restrict__ t_out, double* __restrict__ sd_out,
+                                                    int32_t* __restrict__ status_out) {
   __shared__ double xmax[GTO_RETIME_MAX_N];
   __shared__ double la[GTO_RETIME_LINES], lb[GTO_RETIME_LINES];
   __shared__ int mj[GTO_MAX_DOF];
   const long long b = blockIdx.x;
-  const int lane = threadIdx.x, N = d.N, ndof = d.ndof;
+  const int lane = threadIdx.x, ndof = d.ndof;
+  const int N = d.subdiv * (rt_cols(n_cols, b, d.Tp) - 1) + 1;  // a bad count is flagged: N is not used then
   const int f = lane < ndof ? flag[b * ndof + lane] : GTO_RT_CONST;
   const unsigned long long bad = __ballot(f == GTO_RT_NONFINITE), mov = __ballot(f == GTO_RT_MOVING);
-  const long long o = b * N;
+  const long long o = b * d.Nmax;
   if (bad) {
-    for (int i = lane; i < N; i += 64) {
+    for (int i = lane; i < d.Nmax; i += 64) {
       X[o + i] = NAN, Tg[o + i] = NAN;
       if (t_out) t_out[o + i] = NAN;
       if (sd_out) sd_out[o + i] = NAN;
@@ -241,6 +289,10 @@ __global__ __launch_bounds__(64) void k_retime_pass(const double* __restrict__ P
       if (sd_out) sd_out[o + i + 1] = sqrt(x);
     }
   }
+  for (int i = N + lane; i < d.Nmax; i += 64) {
+    if (t_out) t_out[o + i] = t;
+    if (sd_out) sd_out[o + i] = 0.0;
+  }
   if (lane == 0) {
     const bool stall = nm > 0 && rest <= GTO_RETIME_STALL * xtop;
     const int32_t s = isfinite(t) && !stall ? GTO_STATUS_CONVERGED : GTO_STATUS_NUMERICAL;
@@ -254,14 +306,15 @@ __global__ __launch_bounds__(64) void k_retime_pass(const double* __restrict__ P
 // segment's constant acceleration, q = spline(s), qdot = p1 sdot, qddot = p1 sddot + p2 sdot^2.  [B][M][ndof]
 __global__ __launch_bounds__(256) void k_retime_sample(const double* __restrict__ Q, const double* __restrict__ S,
                                                        const double* __restrict__ X, const double* __restrict__ Tg,
-                                                       const int32_t* __restrict__ stat, RetimeDims d,
+                                                       const int32_t* __restrict__ stat,
+                                                       const int32_t* __restrict__ n_cols, RetimeDims d,
                                                        double* __restrict__ q_out, double* __restrict__ qd_out,
                                                        double* __restrict__ qdd_out) {
   const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= (long long)d.B * d.M) return;
   const long long b = id / d.M;
-  const int m = (int)(id - b * d.M), N = d.N, T = d.T, ndof = d.ndof;
-  if (stat[b] != GTO_STATUS_CONVERGED) {
+  const int m = (int)(id - b * d.M), T = d.Tp, ndof = d.ndof;
+  if (stat[b] != GTO_STATUS_CONVERGED) {  // a bad count among them
     for (int j = 0; j < ndof; ++j) {
       if (q_out) q_out[id * ndof + j] = NAN;
       if (qd_out) qd_out[id * ndof + j] = NAN;
@@ -269,7 +322,16 @@ __global__ __launch_bounds__(256) void k_retime_sample(const double* __restrict_
     }
     return;
   }
-  const double* t = Tg + b * N;
+  const int C = rt_cols(n_cols, b, T), N = d.subdiv * (C - 1) + 1;
+  if (C == 1) {  // one waypoint: the rule of a plan whose waypoints are all equal
+    for (int j = 0; j < ndof; ++j) {
+      if (q_out) q_out[id * ndof + j] = Q[(b * ndof + j) * T];
+      if (qd_out) qd_out[id * ndof + j] = 0.0;
+      if (qdd_out) qdd_out[id * ndof + j] = 0.0;
+    }
+    return;
+  }
+  const double* t = Tg + b * d.Nmax;
   const double dur = t[N - 1];
   const double tt = m == d.M - 1 ? dur : (double)m * (dur / (double)(d.M - 1));
   int lo = 0, hi = N - 2;  // the largest i in [0, N-2] with t_i <= tt
@@ -278,14 +340,14 @@ __global__ __launch_bounds__(256) void k_retime_sample(const double* __restrict_
     if (t[mid] <= tt) lo = mid;
     else hi = mid - 1;
   }
-  const double x0 = X[b * N + lo], x1 = X[b * N + lo + 1];
+  const double x0 = X[b * d.Nmax + lo], x1 = X[b * d.Nmax + lo + 1];
   const double v0 = sqrt(x0), u = (x1 - x0) * (0.5 * (double)(N - 1)), tau = tt - t[lo];
   const double sd = v0 + u * tau;
   double s = (double)lo / (double)(N - 1) + tau * (v0 + 0.5 * u * tau);
   s = fmin(fmax(s, 0.0), 1.0);
-  const int k = min(max((int)(s * (double)(T - 1)), 0), T - 2);
-  const double r = s - (double)k / (double)(T - 1);
-  const double invh = (double)(T - 1);
+  const int k = min(max((int)(s * (double)(C - 1)), 0), C - 2);
+  const double r = s - (double)k / (double)(C - 1);
+  const double invh = (double)(C - 1);
   for (int j = 0; j < ndof; ++j) {
     const long long row = b * ndof + j;
     double q, p1, p2;

@@ -6,7 +6,8 @@ on one stream:
     grasp poses (``plan_objects`` starts here, :242) -> IK (gto_solve_ik_pose_batch_device) -> err_pos / err_rot /
     collision cost and the acceptance test of :262 (gto_ik_report_device) -> accepted goal sets and seeds (gto_seed_goalsets_device) -> gto_solve_batch_device ->
     optionally gto_check_plans_device, the retrieve motion after the grasp (:301-313: gto_retrieve_lift_device or
-    gto_retrieve_reverse_device, with gto_check_paths_device) and gto_retime_batch_device
+    gto_retrieve_reverse_device, with gto_check_paths_device), gto_retime_batch_device and, for the retrieve path,
+    gto_retime_paths_device
 
 (with ``n_seeds`` > 1: gto_seed_goalsets_multi_device -> one gto_solve_batch_device over every object's n_seeds best seeds ->
 gto_plan_report_device -> gto_check_plans_device -> gto_select_plans_device, and the best plan of every object goes on)
@@ -137,7 +138,11 @@ class GraspChain:
         after the grasp (see ``retrieve_spec``), enqueued behind the solve (with n_seeds > 1 behind the selection) on the
         chain's stream; the result gains retrieve_path (B, ndof, steps + 1 | n), retrieve_reached (B,) (lift: the leading
         steps that reached their goal; reverse: n), retrieve_status (B, steps) (reverse: (B, 0)) and, with an observation,
-        retrieve_counts (B, columns).  The retrieve path is not retimed (the retimer's spline factors are per horizon T).
+        retrieve_counts (B, columns).  With retrieve AND retime the retrieve path is retimed too, under the same limits,
+        subdiv and n_samples, on the chain's stream behind the retrieve stage (gto_retime_paths_device; ``reached_only`` in
+        the retrieve dict: only columns 0 .. reached of a lift, the count made from retrieve_reached on the stream): the
+        result gains retrieve_durations, retrieve_retime_status (B,) and, with ``retrieve_samples`` set in the retime dict,
+        retrieve_q / retrieve_qd / retrieve_qdd (B, n_samples, ndof).
 
         Returns a namespace: plans (B, ndof, T), dQ (B, ndof, T-1), cost, iters, status (B,), n_accepted (B,) (0: no
         feasible grasp, the driver's ``continue``; the plan is then the solve from the constant seed to all goals),
@@ -170,11 +175,13 @@ class GraspChain:
         """A ``retrieve`` dict with its defaults filled in: mode "lift" (straight up by ``distance`` = 0.3 m in ``steps`` = 10
         IK steps along ``direction`` = (0, 0, 1) with the gripper's pose held; ``collide``: with the collision term of the
         object's scene, default False as in the reference's retract) or "reverse" (the plan's last stretch backwards);
-        ``closed_joints`` (default: the robot's parameter joints that are fingers) are held at ``closed_value`` = 0."""
-        known = {"mode", "distance", "steps", "direction", "closed_joints", "closed_value", "collide"}
+        ``closed_joints`` (default: the robot's parameter joints that are fingers) are held at ``closed_value`` = 0;
+        ``reached_only`` (lift, with a ``retime`` dict): retime columns 0 .. reached of the path, not all of it."""
+        known = {"mode", "distance", "steps", "direction", "closed_joints", "closed_value", "collide", "reached_only"}
         if set(retrieve) - known:
             raise TypeError(f"retrieve: unexpected key(s) {sorted(set(retrieve) - known)}")
-        r = dict(mode="lift", distance=0.3, steps=10, direction=(0.0, 0.0, 1.0), closed_joints=None, closed_value=0.0, collide=False)
+        r = dict(mode="lift", distance=0.3, steps=10, direction=(0.0, 0.0, 1.0), closed_joints=None, closed_value=0.0, collide=False,
+                 reached_only=False)
         r.update(retrieve)
         if r["mode"] not in ("lift", "reverse"):
             raise ValueError('retrieve: mode is "lift" or "reverse"')
@@ -377,6 +384,21 @@ class GraspChain:
                     h.retime_batch_device(B, d_Q.data_ptr(), retime["vmax"], retime["amax"], int(retime.get("subdiv", 2)),
                                           int(retime.get("n_samples", 100)), duration_out=d_dur.data_ptr(),
                                           status_out=d_rst.data_ptr(), stream=st)
+                    if retrieve is not None:  # the retrieve path on the same clock rules, behind the retrieve stage
+                        sub, ns = int(retime.get("subdiv", 2)), int(retime.get("n_samples", 100))
+                        d_nc = None
+                        if lift and rs["reached_only"]:
+                            d_nc = self._dev("retrieve_n_cols", (B,), i32)
+                            torch.add(d_rreach, 1, out=d_nc)
+                        d_rdur, d_rrst = self._dev("retrieve_durations", (B,), f64), self._dev("retrieve_retime_status", (B,), i32)
+                        d_rsamp = [None] * 3
+                        if retime.get("retrieve_samples", False):
+                            d_rsamp = [self._dev("retrieve_" + k, (B, ns, ndof), f64) for k in ("q", "qd", "qdd")]
+                        h.retime_paths_device(B, cols, d_rp.data_ptr(), retime["vmax"], retime["amax"],
+                                              n_cols=None if d_nc is None else d_nc.data_ptr(), subdiv=sub, n_samples=ns,
+                                              duration_out=d_rdur.data_ptr(), status_out=d_rrst.data_ptr(),
+                                              **{k + "_out": None if v is None else v.data_ptr()
+                                                 for k, v in zip(("q", "qd", "qdd"), d_rsamp)}, stream=st)
             out = dict(plans=d_Q, dQ=d_dQ, cost=d_f, iters=d_it, status=d_stat, n_accepted=d_nacc, seed_index=d_si, seed_cost=d_sc,
                        seed_dist=d_sd, q_solutions=d_q, err_pos=d_ep, err_rot=d_er, ik_cost=d_ic, ik_iters=d_ikit, ik_status=d_ikst,
                        accept=d_acc)
@@ -391,6 +413,9 @@ class GraspChain:
                     out["retrieve_reached"], out["retrieve_status"] = d_rreach, d_rstat
                 if observation is not None:
                     out["retrieve_counts"] = d_rcnt
+                if retime is not None:
+                    out["retrieve_durations"], out["retrieve_retime_status"] = d_rdur, d_rrst
+                    out.update({"retrieve_" + k: v for k, v in zip(("q", "qd", "qdd"), d_rsamp) if v is not None})
             if multi:  # (cost, iters, status and counts hold every slot's until the chosen slot's are picked below)
                 out.update(best_slot=d_best, plan_class=d_cls, slot_class=d_scls, slot_goal_index=d_gi, slot_err_pos=d_pep,
                            slot_err_rot=d_per, accepted_rows=d_rows, slot_plans=d_Qs)

@@ -117,15 +117,18 @@ class GTOPlanner:
                 solution["f"].toarray().flatten())
 
     def retrieve_path(self, plan, mode="lift", distance=0.3, steps=10, direction=(0.0, 0.0, 1.0), closed_joints=None,
-                      closed_value=0.0, max_iter=50, pos_tol=0.01, rot_tol_deg=5.0):
+                      closed_value=0.0, max_iter=50, pos_tol=0.01, rot_tol_deg=5.0, retime=None):
         """The motion after the grasp (examples/pybullet_gto_planning.py:301-313) for a solved ``plan`` (ndof, T), or
         (B, ndof, T) for B of them: mode "lift" moves link_ee by ``distance`` along ``direction`` in ``steps`` IK steps, each
         seeded from the one before, with the gripper's pose held (the tabletop driver's env.retract; pybullet's position-only
         IK would let the held object tilt); mode "reverse" runs the plan's last stretch backwards (the shelf driver).
         ``closed_joints`` (default: the robot's parameter joints that are fingers) are held at ``closed_value``.
         Returns (path (ndof, steps + 1 | 9 - standoff_offset), reached): reached counts the leading steps that met their goal
-        within pos_tol / rot_tol_deg (reverse: every column).  No collision term; GraspChain's ``retrieve`` has one.  The
-        path is not retimed (the retimer's spline factors are per horizon T)."""
+        within pos_tol / rot_tol_deg (reverse: every column).  No collision term; GraspChain's ``retrieve`` has one.
+        retime: a dict ``vmax, amax[, subdiv, n_samples, reached_only]`` to also retime the path under these joint limits
+        (gto_retime_paths); reached_only=True retimes columns 0 .. reached of a lift, the part that met its goals.  The
+        return value is then (path, reached, trajectory): the dict of ``SolverHandle.retime_paths`` (of one path for one
+        plan)."""
         from . import _capi
         from .grasp_chain import finger_joints
         plan = np.asarray(plan, dtype=np.float64)
@@ -153,4 +156,12 @@ class GTOPlanner:
             reached = np.full(plans.shape[0], n, dtype=np.int32)
         else:
             raise ValueError('retrieve_path: mode is "lift" or "reverse"')
-        return (path[0], int(reached[0])) if single else (path, reached)
+        if retime is None:
+            return (path[0], int(reached[0])) if single else (path, reached)
+        unknown = set(retime) - {"vmax", "amax", "subdiv", "n_samples", "reached_only"}
+        if unknown:
+            raise TypeError(f"retrieve_path: unexpected retime key(s) {sorted(unknown)}")
+        n_cols = reached + 1 if mode == "lift" and retime.get("reached_only", False) else None
+        traj = h.retime_paths(path, retime["vmax"], retime["amax"], n_cols=n_cols, subdiv=int(retime.get("subdiv", 2)),
+                              n_samples=int(retime.get("n_samples", 100)))
+        return (path[0], int(reached[0]), {k: v[0] for k, v in traj.items()}) if single else (path, reached, traj)

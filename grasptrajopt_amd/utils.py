@@ -244,6 +244,19 @@ def retime_plans(robot, plans, vlim=None, alim=0.5, subdiv: int = 2, n_samples: 
     return _retime_handle(robot, plans.shape[2]).retime_batch(plans, vlim, alim, subdiv=subdiv, n_samples=n_samples)
 
 
+def retime_paths(robot, paths, n_cols=None, vlim=None, alim=0.5, subdiv: int = 2, n_samples: int = 100):
+    """``retime_plans`` for paths (B, ndof, Tp) or one path (ndof, Tp) of any length Tp >= 2 (gto_retime_paths,
+    include/gto_solver.h): a retrieve path of ``GTOPlanner.retrieve_path``, for one.  n_cols (B,) int or None: path b is its
+    first n_cols[b] columns and the rest is ignored (a lift up to the step it reached: ``reached + 1``); t_grid and sd_grid
+    are (B, subdiv (Tp-1) + 1) and hold the duration and 0 past a path's own gridpoints.  One handle serves every Tp."""
+    paths = np.asarray(paths, dtype=np.float64)
+    if paths.ndim == 2:
+        paths = paths[None]
+    if vlim is None:
+        vlim = np.asarray(robot.velocity_actuated_joint_limits.toarray()).ravel()
+    return _retime_handle(robot, 4).retime_paths(paths, vlim, alim, n_cols=n_cols, subdiv=subdiv, n_samples=n_samples)
+
+
 def convert_plan_to_trajectory_toppra(robot, plan, is_show: bool = False):
     """gto/utils.py:283-323 on the GPU: plan (ndof, T) -> (qs_sample, qds_sample, qdds_sample, ts_sample), 100 samples of
     each, in the reference's order.  Velocity limits from the URDF for all ndof joints (the reference passes the n_opt

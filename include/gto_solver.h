@@ -903,6 +903,35 @@ int gto_check_paths(gto_handle* h, gto_observation* obs, int32_t B, int32_t Tp, 
                     int32_t per_plan_base, int32_t* count_out);
 int gto_check_paths_device(gto_handle* h, gto_observation* obs, int32_t B, int32_t Tp, const double* paths,
                            const double* base_pos, int32_t per_plan_base, int32_t* count_out, void* stream);
+/*
+ * Retiming on paths of any length, each with its own column count: the contract of gto_retime_batch /
+ * gto_retime_batch_device (above) with paths [B][ndof][Tp], Tp passed explicitly, and these differences.  Additions (the ABI
+ * number stays).  Works on every handle, whatever its horizon and its number of optimised joints.
+ *   Tp       2 <= Tp and Nmax = subdiv (Tp-1) + 1 <= 1024 (GTO_ERR_INVALID_ARG otherwise).
+ *   n_cols   [B] or NULL (every path has Tp columns): path b is columns 0 .. C_b-1 of its row, C_b = n_cols[b]; the other
+ *            columns are ignored, non-finite values there included.  Its grid has N_b = subdiv (C_b-1) + 1 points on
+ *            s_k = k/(C_b-1).  t_grid_out and sd_grid_out are [B][Nmax]; their entries i >= N_b hold the duration and 0
+ *            (the path has ended and rests).  C_b == 1 follows the rule of a plan whose waypoints are all equal: duration 0,
+ *            GTO_STATUS_CONVERGED, every sample is the waypoint, derivatives and t_grid are 0.
+ *            gto_retime_paths_device: a DEVICE array that no host sees; C_b < 1 or C_b > Tp gives GTO_STATUS_NUMERICAL and NaN
+ *            outputs for that path (all Nmax grid entries), and no other path's output changes.
+ *            gto_retime_paths: a HOST array; such a count fails the whole call with GTO_ERR_INVALID_ARG before any launch.
+ *   spline   scipy.interpolate.CubicSpline(..., bc_type="not-a-knot") for every count: the banded system at C >= 4, the
+ *            parabola through the three waypoints at C == 3, the straight line (p2 = 0) at C == 2.
+ *   N_b == 2 (C_b == 2 with subdiv == 1) has no gridpoint between its two ends, which both rest (x_0 = x_1 = 0): the one
+ *            segment's time is infinite, status GTO_STATUS_NUMERICAL by the rule above.  subdiv >= 2 retimes two columns.
+ * Every path's result is bit for bit the same in any batch, at any position in it and under any Tp >= C_b.  With n_cols NULL
+ * and Tp = the handle's horizon the outputs are gto_retime_batch's bit for bit: that call is this one with Tp = T.  The
+ * spline factors of all counts are one table per handle: the first retime call of a handle uploads it and synchronises, no
+ * later call does, whatever its Tp.  vmax / amax: HOST arrays in both variants.
+ */
+int gto_retime_paths(gto_handle* h, int32_t B, int32_t Tp, const double* paths, const int32_t* n_cols, const double* vmax,
+                     const double* amax, int32_t subdiv, int32_t M, double* duration_out, double* t_grid_out,
+                     double* sd_grid_out, double* q_out, double* qd_out, double* qdd_out, int32_t* status_out);
+int gto_retime_paths_device(gto_handle* h, int32_t B, int32_t Tp, const double* paths, const int32_t* n_cols /*DEVICE*/,
+                            const double* vmax /*HOST*/, const double* amax /*HOST*/, int32_t subdiv, int32_t M,
+                            double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out, double* qd_out,
+                            double* qdd_out, int32_t* status_out, void* stream);
 
 #ifdef __cplusplus
 }
