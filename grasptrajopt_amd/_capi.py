@@ -158,6 +158,8 @@ def _prototypes():
         "gto_retrieve_path_columns": (I, [V]),
         "gto_check_paths": (I, [V, V, I32, I32, _pd, _pd, I32, _pi]),
         "gto_check_paths_device": (I, [V, V, I32, I32, V, _pd, I32, V, V]),
+        "gto_check_held_paths": (I, [V, V, I32, I32, _pd, _pd, I32, I32, _pd, I32, _pi, _pd, _pi, _pi, _pd, I32, _pi]),
+        "gto_check_held_paths_device": (I, [V, V, I32, I32, V, V, I32, I32, V, I32, V, V, V, V, _pd, I32, V, V]),
         "gto_retime_paths": (I, [V, I32, I32, _pd, _pi, _pd, _pd, I32, I32, _pd, _pd, _pd, _pd, _pd, _pd, _pi]),
         "gto_retime_paths_device": (I, [V, I32, I32, V, V, _pd, _pd, I32, I32] + [V] * 8),
     }
@@ -828,6 +830,67 @@ class SolverHandle:
         base, per_plan = self._check_base(base_pos, int(B))
         self._check(self.lib.gto_check_paths_device(self._h, obs._ptr(), int(B), int(Tp), _vp(paths), _p(base, _pd), per_plan,
                                                     _vp(count_out), _vp(stream)), "gto_check_paths_device")
+
+    @staticmethod
+    def pad_held_points(held_points, n_held=None):
+        """(points float64 (B, P_max, 3), counts int32 (B,)) from a list of per-plan (n_i, 3) arrays, or from a padded array
+        (B, P_max, 3) with its counts (default: every row counts).  Rows behind a plan's count are zeros and read by nobody."""
+        if n_held is None and not (isinstance(held_points, np.ndarray) and held_points.ndim == 3):
+            sets = [_f64(p).reshape(-1, 3) for p in held_points]
+            counts = _i32([p.shape[0] for p in sets])
+            pts = np.zeros((len(sets), max(1, int(counts.max()) if len(sets) else 1), 3))
+            for b, p in enumerate(sets):
+                pts[b, :p.shape[0]] = p
+            return pts, counts
+        pts = _f64(held_points)
+        if pts.ndim != 3 or pts.shape[2] != 3 or pts.shape[1] < 1:
+            raise GTOError(f"held_points: a list of (n_i, 3) arrays or a padded array (B, P_max >= 1, 3); got {pts.shape}")
+        counts = _i32(np.broadcast_to(np.asarray(pts.shape[1] if n_held is None else n_held), (pts.shape[0],)))
+        return pts, counts
+
+    def check_held_paths(self, obs, paths, held_points, n_held=None, attach=None, attach_col=None, object_pose=None, labels=None,
+                         held_label=None, base_pos=(0.0, 0.0, 0.0)):
+        """gto_check_held_paths: for paths (B, ndof, Tp) the number of plan b's held points inside the observation ``obs`` at
+        every column, int32 (B, Tp), the points carried rigidly with link_ee from the configuration the object was grasped
+        at: column 0 of the path, or column ``attach_col`` (default: the last) of ``attach`` (B, ndof, ld).  held_points /
+        n_held: see ``pad_held_points``; world points at the moment of the grasp, or object-frame points with
+        object_pose (B, 4, 4).  labels (H, W) int32 with held_label (B,) or one label: pixels of a depth observation that
+        show the held object hide nothing that was seen.  -1: a column, q_att, base or object pose with a non-finite entry."""
+        paths = _f64(paths)
+        if paths.ndim != 3 or paths.shape[1] != self.desc.ndof or paths.shape[2] < 1:
+            raise GTOError(f"check_held_paths: paths must have shape (B, {self.desc.ndof}, Tp >= 1); got {paths.shape}")
+        B, Tp = paths.shape[0], paths.shape[2]
+        pts, counts = self.pad_held_points(held_points, n_held)
+        if pts.shape[0] != B or counts.shape != (B,):
+            raise GTOError(f"check_held_paths: one point set and one count per path ({B}); got {pts.shape[0]}, {counts.shape}")
+        ld = col = 0
+        if attach is not None:
+            attach = _f64(attach)
+            if attach.ndim != 3 or attach.shape[:2] != (B, self.desc.ndof):
+                raise GTOError(f"check_held_paths: attach must have shape ({B}, {self.desc.ndof}, ld); got {attach.shape}")
+            ld = attach.shape[2]
+            col = ld - 1 if attach_col is None else int(attach_col)
+        pose = None if object_pose is None else _f64(object_pose).reshape(B, 16)
+        lab = None if labels is None else _i32(labels)
+        hl = None if held_label is None else _per_instance(held_label, B)
+        base, per_plan = self._check_base(base_pos, B)
+        count = np.empty((B, Tp), dtype=np.int32)
+        self._check(self.lib.gto_check_held_paths(self._h, obs._ptr(), B, Tp, _p(paths, _pd), _p(attach, _pd), ld, col, _p(pts, _pd),
+                                                  pts.shape[1], _p(counts, _pi), _p(pose, _pd), _p(lab, _pi), _p(hl, _pi),
+                                                  _p(base, _pd), per_plan, _p(count, _pi)), "gto_check_held_paths")
+        return count
+
+    def check_held_paths_device(self, obs, B, Tp, paths, held_points, P_max, n_held, count_out, attach=None, attach_ld=0,
+                                attach_col=0, object_pose=None, labels=None, held_label=None, base_pos=(0.0, 0.0, 0.0),
+                                stream=None):
+        """gto_check_held_paths_device: paths (B, ndof, Tp), attach, held_points (B, P_max, 3), n_held (B,) int32,
+        object_pose (B, 16), labels (H, W) int32, held_label (B,) int32 and count_out (B, Tp) int32 are device pointers (or
+        None where the header allows NULL); base_pos is a host value; enqueued on ``stream`` without a host synchronisation."""
+        base, per_plan = self._check_base(base_pos, int(B))
+        self._check(self.lib.gto_check_held_paths_device(self._h, obs._ptr(), int(B), int(Tp), _vp(paths), _vp(attach), int(attach_ld),
+                                                         int(attach_col), _vp(held_points), int(P_max), _vp(n_held),
+                                                         _vp(object_pose), _vp(labels), _vp(held_label), _p(base, _pd), per_plan,
+                                                         _vp(count_out), _vp(stream)), "gto_check_held_paths_device")
 
     # -------------------------------------------------------------- the motion after the grasp
     @staticmethod

@@ -25,6 +25,7 @@
 #include "gto_cloud.h"
 #include "gto_retime.h"
 #include "gto_observe.h"
+#include "gto_held.h"
 #include "gto_seed.h"
 #include "gto_retrieve.h"
 #include "gto_occupancy.h"
@@ -236,6 +237,9 @@ struct gto_handle {
   bool rt_fac_ready = false;
   // collision checks against a cloud observation (gto_check_plans_device): world points, votes and per-plan bases of a chunk
   DevBuf ck_xyz, ck_flags, ck_base;
+  // the held object's points (gto_check_held_paths_device): the points in link_ee's frame at the grasp [B][P_max][3] and the
+  // per-plan bad flags [B]
+  DevBuf hd_p, hd_bad;
   // seed choice (gto_seed_goalsets_device): per-waypoint cost sums of the candidates [B][n_max][T]
   DevBuf sd_part;
   // base placement with resident arrays (gto_solve_base_batch_device, gto_base_report_device): the device copy of the
@@ -3790,6 +3794,121 @@ int gto_check_plans(gto_handle* h, gto_observation* o, int32_t B, const double* 
   bool empty;
   if (int rc = check_plans_args(h, o, B, plans, base_pos, &empty)) return rc;
   return gto_check_paths(h, o, B, h->opts.T, plans, base_pos, per_plan_base, count_out);
+}
+
+// What gto_check_held_paths and its device variant check before any device work (host-side facts only).  *empty: B = 0.
+static int check_held_args(gto_handle* h, const gto_observation* o, int32_t B, int32_t Tp, const double* paths, const double* attach,
+                           int32_t attach_ld, int32_t attach_col, const double* held_points, int32_t P_max, const int32_t* n_held,
+                           const int32_t* labels, const int32_t* held_label, const double* base_pos, const int32_t* count_out,
+                           bool* empty) {
+  const char* who = "gto_check_held_paths";
+  *empty = B == 0;
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (!o || !base_pos) return fail(h, GTO_ERR_INVALID_ARG, std::string(who) + ": null observation or base position");
+  if (B < 0 || Tp < 1 || P_max < 1) return fail(h, GTO_ERR_INVALID_ARG, std::string(who) + ": B >= 0, Tp >= 1 and P_max >= 1 are required");
+  if (o->device != h->device) return fail(h, GTO_ERR_INVALID_ARG, std::string(who) + ": the observation lives on another device than the handle");
+  if (attach && (attach_col < 0 || attach_col >= attach_ld))
+    return fail(h, GTO_ERR_INVALID_ARG, std::string(who) + ": attach_col must be in [0, attach_ld)");
+  if (labels && !held_label) return fail(h, GTO_ERR_INVALID_ARG, std::string(who) + ": labels without held_label");
+  if (B == 0) return GTO_OK;
+  if (B > 65535 || P_max > 65535) return fail(h, GTO_ERR_UNSUPPORTED, std::string(who) + ": at most 65535 plans of at most 65535 held points in one call");
+  if (!paths || !held_points || !n_held || !count_out) return fail(h, GTO_ERR_INVALID_ARG, std::string(who) + ": null paths, held_points, n_held or count_out");
+  return GTO_OK;
+}
+
+// The held object's points along the paths (include/gto_solver.h; kernels: gto_held.h)
+int gto_check_held_paths_device(gto_handle* h, gto_observation* o, int32_t B, int32_t Tp, const double* paths, const double* attach,
+                                int32_t attach_ld, int32_t attach_col, const double* held_points, int32_t P_max,
+                                const int32_t* n_held, const double* object_pose, const int32_t* labels, const int32_t* held_label,
+                                const double* base_pos, int32_t per_plan_base, int32_t* count_out, void* stream) {
+  bool empty;
+  if (int rc = check_held_args(h, o, B, Tp, paths, attach, attach_ld, attach_col, held_points, P_max, n_held, labels, held_label, base_pos,
+                               count_out, &empty))
+    return rc;
+  if (empty) return GTO_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  const int T = Tp, P = P_max, ndof = h->rb.ndof;
+  const size_t lds = sizeof(double) * check_plans_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
+  const size_t lds_att = sizeof(double) * held_attach_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
+  if (lds > 150 * 1024 || lds_att > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the collision-check kernel's LDS");
+  const int tg = check_waypoints_per_group();
+  const unsigned tgroups = (unsigned)((T + tg - 1) / tg);
+  int rc;
+  const double* d_base = nullptr;
+  if (per_plan_base) {  // as gto_check_paths_device: the caller's array is free on return, the copy is ordered on `st`
+    if ((rc = ensure(h, h->ck_base, (size_t)B * 3 * sizeof(double)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->ck_base.get(), base_pos, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    d_base = h->ck_base.as<const double>();
+  }
+  const double b0 = per_plan_base ? 0.0 : base_pos[0], b1 = per_plan_base ? 0.0 : base_pos[1], b2 = per_plan_base ? 0.0 : base_pos[2];
+  if ((rc = ensure(h, h->hd_p, (size_t)B * P * 3 * sizeof(double)))) return rc;
+  if ((rc = ensure(h, h->hd_bad, (size_t)B * sizeof(int32_t)))) return rc;
+  double* d_p = h->hd_p.as<double>();
+  int32_t* d_bad = h->hd_bad.as<int32_t>();
+  // attach NULL: the paths' own column 0 (the lift, whose column 0 is the plan's last waypoint)
+  const double* att = attach ? attach : paths;
+  const int att_ld = attach ? attach_ld : T, att_col = attach ? attach_col : 0;
+  HIPCHK(h, raise_dynamic_lds((const void*)k_held_attach, lds_att));
+  hipLaunchKernelGGL(k_held_attach, dim3((unsigned)B), dim3(256), lds_att, st, h->d_rb, att, att_ld, att_col, b0, b1, b2, d_base, held_points, P, n_held,
+                     object_pose, d_p, d_bad);
+  if (o->is_depth) {
+    HIPCHK(h, raise_dynamic_lds((const void*)k_check_held<true>, lds));
+    hipLaunchKernelGGL(k_check_held<true>, dim3((unsigned)B, tgroups), dim3(256), lds, st, h->d_rb, T, tg, paths, b0, b1, b2, d_base, (const double*)d_p, P,
+                       n_held, (const int32_t*)d_bad, depth_view(o), labels, held_label, (double*)nullptr, count_out);
+  } else {
+    HIPCHK(h, raise_dynamic_lds((const void*)k_check_held<false>, lds));
+    const SearchEnv env = search_env();
+    const int chunk = chunk_items(B, (long long)T * P);
+    if ((rc = ensure(h, h->ck_xyz, (size_t)chunk * T * P * 3 * sizeof(double)))) return rc;
+    if ((rc = ensure(h, h->ck_flags, (size_t)chunk * T * P))) return rc;
+    double* d_xyz = h->ck_xyz.as<double>();
+    uint8_t* d_flags = h->ck_flags.as<uint8_t>();
+    for (int i0 = 0; i0 < B; i0 += chunk) {
+      const int m = std::min(chunk, B - i0);
+      int32_t* cnt = count_out + (size_t)i0 * T;
+      hipLaunchKernelGGL(k_check_held<false>, dim3((unsigned)m, tgroups), dim3(256), lds, st, h->d_rb, T, tg, paths + (size_t)i0 * ndof * T, b0, b1, b2,
+                         d_base ? d_base + (size_t)i0 * 3 : nullptr, (const double*)d_p + (size_t)i0 * P * 3, P, n_held + i0,
+                         (const int32_t*)d_bad + i0, ObsDepthView{}, (const int32_t*)nullptr, (const int32_t*)nullptr, d_xyz, cnt);
+      obs_cloud_votes(env, st, o, d_xyz, (long)m * T * P, d_flags);
+      hipLaunchKernelGGL(k_count_flags, dim3((unsigned)(m * T)), dim3(256), 0, st, d_flags, P, cnt);
+    }
+  }
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
+}
+
+int gto_check_held_paths(gto_handle* h, gto_observation* o, int32_t B, int32_t Tp, const double* paths, const double* attach,
+                         int32_t attach_ld, int32_t attach_col, const double* held_points, int32_t P_max, const int32_t* n_held,
+                         const double* object_pose, const int32_t* labels, const int32_t* held_label, const double* base_pos,
+                         int32_t per_plan_base, int32_t* count_out) {
+  bool empty;
+  if (int rc = check_held_args(h, o, B, Tp, paths, attach, attach_ld, attach_col, held_points, P_max, n_held, labels, held_label, base_pos,
+                               count_out, &empty))
+    return rc;
+  if (empty) return GTO_OK;
+  for (int b = 0; b < B; ++b)
+    if (n_held[b] < 0 || n_held[b] > P_max) return fail(h, GTO_ERR_INVALID_ARG, "gto_check_held_paths: n_held must be in [0, P_max]");
+  HIPCHK(h, hipSetDevice(h->device));
+  Staging io(h);
+  const size_t nB = (size_t)B, nd = (size_t)h->rb.ndof;
+  const bool use_labels = labels && o->is_depth;  // (a cloud observation has no image: both are ignored)
+  const double *d_paths, *d_attach, *d_points, *d_pose;
+  const int32_t *d_nheld, *d_labels, *d_lab;
+  int32_t* d_count;
+  int rc;
+  if ((rc = io.in(paths, nB * nd * Tp, &d_paths))) return rc;
+  if ((rc = io.in(attach, attach ? nB * nd * attach_ld : 0, &d_attach))) return rc;
+  if ((rc = io.in(held_points, nB * P_max * 3, &d_points))) return rc;
+  if ((rc = io.in(n_held, nB, &d_nheld))) return rc;
+  if ((rc = io.in(object_pose, nB * 16, &d_pose))) return rc;
+  if ((rc = io.in(use_labels ? labels : nullptr, use_labels ? (size_t)o->depth.H * o->depth.W : 0, &d_labels))) return rc;
+  if ((rc = io.in(use_labels ? held_label : nullptr, nB, &d_lab))) return rc;
+  if ((rc = io.out(count_out, nB * Tp, &d_count))) return rc;
+  if ((rc = gto_check_held_paths_device(h, o, B, Tp, d_paths, d_attach, attach_ld, attach_col, d_points, P_max, d_nheld, d_pose, d_labels, d_lab,
+                                        base_pos, per_plan_base, d_count, nullptr)))
+    return rc;
+  return io.finish();
 }
 
 }  // extern "C"

@@ -57,8 +57,9 @@ __global__ void k_depth_backproject(const float* __restrict__ depth, int H, int 
 // visibility test, cost map.  best = squared distance to the nearest point of the cloud.
 // mesh_to_sdf/depth_point_cloud.py:126-141 is_outside: the query is in front of the surface the depth image saw at its pixel
 // (or projects outside the image)
-__device__ __forceinline__ bool depth_is_outside(double q0, double q1, double q2, const float* __restrict__ depth, int H, int W,
-                                                 const double* __restrict__ K, const double* __restrict__ cam_inv) {
+// *pixel: the image index iy * W + ix the query projects to, -1 when it projects outside the image
+__device__ __forceinline__ bool depth_is_outside_at(double q0, double q1, double q2, const float* __restrict__ depth, int H, int W,
+                                                    const double* __restrict__ K, const double* __restrict__ cam_inv, int* pixel) {
 #pragma clang fp contract(off)
   double pc[3], u[3];
 #pragma unroll
@@ -71,8 +72,17 @@ __device__ __forceinline__ bool depth_is_outside(double q0, double q1, double q2
   const bool fx = fabs(ux) < 9.0e18, fy = fabs(uy) < 9.0e18;
   const long ix = fx ? (long)ux : LONG_MIN, iy = fy ? (long)uy : LONG_MIN;
   bool outside = true;
-  if (ix >= 0 && iy >= 0 && ix < W && iy < H) outside = pc[2] < (double)depth[iy * W + ix];
+  *pixel = -1;
+  if (ix >= 0 && iy >= 0 && ix < W && iy < H) {
+    outside = pc[2] < (double)depth[iy * W + ix];
+    *pixel = (int)(iy * W + ix);
+  }
   return outside;
+}
+__device__ __forceinline__ bool depth_is_outside(double q0, double q1, double q2, const float* __restrict__ depth, int H, int W,
+                                                 const double* __restrict__ K, const double* __restrict__ cam_inv) {
+  int pixel;
+  return depth_is_outside_at(q0, q1, q2, depth, H, W, K, cam_inv, &pixel);
 }
 
 // The cost map of mesh_to_sdf/depth_point_cloud.py:84-89 for a signed distance `dist` (negative: inside).  The depth path

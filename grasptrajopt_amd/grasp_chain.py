@@ -6,8 +6,8 @@ on one stream:
     grasp poses (``plan_objects`` starts here, :242) -> IK (gto_solve_ik_pose_batch_device) -> err_pos / err_rot /
     collision cost and the acceptance test of :262 (gto_ik_report_device) -> accepted goal sets and seeds (gto_seed_goalsets_device) -> gto_solve_batch_device ->
     optionally gto_check_plans_device, the retrieve motion after the grasp (:301-313: gto_retrieve_lift_device or
-    gto_retrieve_reverse_device, with gto_check_paths_device), gto_retime_batch_device and, for the retrieve path,
-    gto_retime_paths_device
+    gto_retrieve_reverse_device, with gto_check_paths_device and, for the object the robot holds,
+    gto_check_held_paths_device), gto_retime_batch_device and, for the retrieve path, gto_retime_paths_device
 
 (with ``n_seeds`` > 1: gto_seed_goalsets_multi_device -> one gto_solve_batch_device over every object's n_seeds best seeds ->
 gto_plan_report_device -> gto_check_plans_device -> gto_select_plans_device, and the best plan of every object goes on)
@@ -138,7 +138,9 @@ class GraspChain:
         after the grasp (see ``retrieve_spec``), enqueued behind the solve (with n_seeds > 1 behind the selection) on the
         chain's stream; the result gains retrieve_path (B, ndof, steps + 1 | n), retrieve_reached (B,) (lift: the leading
         steps that reached their goal; reverse: n), retrieve_status (B, steps) (reverse: (B, 0)) and, with an observation,
-        retrieve_counts (B, columns).  With retrieve AND retime the retrieve path is retimed too, under the same limits,
+        retrieve_counts (B, columns); with an observation and ``held_points`` in the retrieve dict also
+        retrieve_held_counts (B, columns): how many points of the object the robot holds are inside the observation at every
+        column (gto_check_held_paths_device, enqueued behind the robot's own check).  With retrieve AND retime the retrieve path is retimed too, under the same limits,
         subdiv and n_samples, on the chain's stream behind the retrieve stage (gto_retime_paths_device; ``reached_only`` in
         the retrieve dict: only columns 0 .. reached of a lift, the count made from retrieve_reached on the stream): the
         result gains retrieve_durations, retrieve_retime_status (B,) and, with ``retrieve_samples`` set in the retime dict,
@@ -176,12 +178,18 @@ class GraspChain:
         IK steps along ``direction`` = (0, 0, 1) with the gripper's pose held; ``collide``: with the collision term of the
         object's scene, default False as in the reference's retract) or "reverse" (the plan's last stretch backwards);
         ``closed_joints`` (default: the robot's parameter joints that are fingers) are held at ``closed_value`` = 0;
-        ``reached_only`` (lift, with a ``retime`` dict): retime columns 0 .. reached of the path, not all of it."""
-        known = {"mode", "distance", "steps", "direction", "closed_joints", "closed_value", "collide", "reached_only"}
+        ``reached_only`` (lift, with a ``retime`` dict): retime columns 0 .. reached of the path, not all of it.
+        ``held_points`` (with an observation): the points of the object every plan holds, a list of B (n_i, 3) arrays or a
+        padded array (B, P_max, 3) with ``held_counts`` (B,); world points at the moment of the grasp, or object-frame points
+        with ``object_pose`` (B, 4, 4) (``plan_grasps`` places object-frame points at its own object poses when the key is
+        absent); ``labels`` (H, W) int32 and ``held_label`` (B,) or one label: the segmentation image of a depth observation
+        and the held object's label in it, whose pixels hide nothing that was seen (include/gto_solver.h)."""
+        known = {"mode", "distance", "steps", "direction", "closed_joints", "closed_value", "collide", "reached_only", "held_points",
+                 "held_counts", "object_pose", "labels", "held_label"}
         if set(retrieve) - known:
             raise TypeError(f"retrieve: unexpected key(s) {sorted(set(retrieve) - known)}")
         r = dict(mode="lift", distance=0.3, steps=10, direction=(0.0, 0.0, 1.0), closed_joints=None, closed_value=0.0, collide=False,
-                 reached_only=False)
+                 reached_only=False, held_points=None, held_counts=None, object_pose=None, labels=None, held_label=None)
         r.update(retrieve)
         if r["mode"] not in ("lift", "reverse"):
             raise ValueError('retrieve: mode is "lift" or "reverse"')
@@ -243,7 +251,7 @@ class GraspChain:
                                                   d_n.data_ptr(), check_offset, ik_offset, None if d_w is None else d_w.data_ptr(),
                                                   d_base.data_ptr(), max_ratio, d_fc.data_ptr(), d_keep.data_ptr(), d_rows.data_ptr(),
                                                   d_nk.data_ptr(), d_ng.data_ptr(), d_pg.data_ptr(), d_ikg.data_ptr(), st)
-            return d_ikg, d_pg, d_ng, dict(grasp_counts=d_fc, grasp_keep=d_keep, kept_rows=d_rows, n_kept=d_nk)
+            return d_ikg, d_pg, d_ng, dict(grasp_counts=d_fc, grasp_keep=d_keep, kept_rows=d_rows, n_kept=d_nk, _object_pose=d_op)
 
         kw = {k: p.default for k, p in inspect.signature(self.plan_objects).parameters.items() if p.default is not p.empty}
         unknown = set(plan_objects_keywords) - set(kw)
@@ -291,10 +299,30 @@ class GraspChain:
         slots = (B, K) if multi else (B,)  # leading shape of what exists once per solve instance
         f64, i32, u8 = torch.float64, torch.int32, torch.uint8
         res = SimpleNamespace()
+        rs = None if retrieve is None else self.retrieve_spec(retrieve)
         with torch.cuda.stream(self.stream):
             st = self.stream.cuda_stream
             d_sid, d_qc, d_base = self._up("sid", sid, np.int32), self._up("qc", qc, np.float64), self._up("base", base, np.float64)
             d_ikg, d_pg, d_ng, extra = feed(st, d_base)
+            d_obj_pose = extra.pop("_object_pose", None)  # plan_grasps: the poses of the objects, which the robot then holds
+
+            def upload_held():
+                """The held object's points, counts, poses and labels -> device buffers of the chain (None: nothing to check)."""
+                if rs is None or observation is None or rs["held_points"] is None:
+                    return None
+                pts, n_held = h.pad_held_points(rs["held_points"], rs["held_counts"])
+                if pts.shape[0] != B or n_held.shape != (B,):
+                    raise ValueError(f"retrieve: held_points needs one point set per object ({B})")
+                held = SimpleNamespace(P_max=pts.shape[1], points=self._up("held_points", pts, np.float64),
+                                       counts=self._up("held_counts", n_held, np.int32), pose=d_obj_pose, labels=None, label=None)
+                if rs["object_pose"] is not None:
+                    held.pose = self._up("held_pose", np.asarray(rs["object_pose"], dtype=np.float64).reshape(B, 16), np.float64)
+                if rs["labels"] is not None:
+                    held.labels = self._up("held_labels", np.asarray(rs["labels"]), np.int32)
+                if rs["held_label"] is not None:
+                    held.label = self._up("held_label", np.broadcast_to(np.asarray(rs["held_label"], dtype=np.int32), (B,)), np.int32)
+                return held
+
             # per candidate grasp: its object's scene, seed and base
             d_sid_ik = self._up("sid_ik", np.repeat(sid, n_max), np.int32)
             d_q0_ik = self._up("q0_ik", np.repeat(qc, n_max, axis=0), np.float64)
@@ -332,6 +360,9 @@ class GraspChain:
                 h.solve_ik_pose_batch_device(0, N, d_sid_ik.data_ptr(), d_q0_ik.data_ptr(), d_ikg.data_ptr(), d_base_ik.data_ptr(),
                                              self.ik_max_iter, d_q.data_ptr(), d_ikf.data_ptr(), d_ikit.data_ptr(),
                                              d_ikst.data_ptr(), st)
+                # behind the IK launch: the host's copies into pinned memory run while the GPU solves IK, and no copy is
+                # enqueued behind the solve
+                held = upload_held()
                 h.ik_report_device(N, d_sid_ik.data_ptr(), d_q.data_ptr(), d_ikg.data_ptr(), d_base_ik.data_ptr(), pos_tol,
                                    rot_tol_deg, ik_collision_threshold, d_ep.data_ptr(), d_er.data_ptr(), d_ic.data_ptr(),
                                    d_acc.data_ptr(), st)
@@ -362,7 +393,6 @@ class GraspChain:
                     h.select_plans_device(B, K, *sel, Q=d_Qs.data_ptr(), dQ=d_dQs.data_ptr(), best_slot_out=d_best.data_ptr(),
                                           class_out=d_cls.data_ptr(), Q_out=d_Q.data_ptr(), dQ_out=d_dQ.data_ptr(), stream=st)
                 if retrieve is not None:
-                    rs = self.retrieve_spec(retrieve)
                     lift = rs["mode"] == "lift"
                     cols = int(rs["steps"]) + 1 if lift else h.retrieve_path_columns()
                     if cols < 1:
@@ -379,6 +409,13 @@ class GraspChain:
                     if observation is not None:
                         d_rcnt = self._dev("retrieve_counts", (B, cols), i32)
                         h.check_paths_device(observation, B, cols, d_rp.data_ptr(), d_rcnt.data_ptr(), base_pos=base, stream=st)
+                        if held is not None:  # the object rides with link_ee from the grasp: the plan's last waypoint
+                            ptr = lambda t: None if t is None else t.data_ptr()
+                            d_hcnt = self._dev("retrieve_held_counts", (B, cols), i32)
+                            h.check_held_paths_device(observation, B, cols, d_rp.data_ptr(), held.points.data_ptr(), held.P_max,
+                                                      held.counts.data_ptr(), d_hcnt.data_ptr(), attach=None if lift else d_Q.data_ptr(),
+                                                      attach_ld=T, attach_col=T - 1, object_pose=ptr(held.pose), labels=ptr(held.labels),
+                                                      held_label=ptr(held.label), base_pos=base, stream=st)
                 if retime is not None:
                     d_dur, d_rst = self._dev("durations", (B,), f64), self._dev("retime_status", (B,), i32)
                     h.retime_batch_device(B, d_Q.data_ptr(), retime["vmax"], retime["amax"], int(retime.get("subdiv", 2)),
@@ -413,6 +450,8 @@ class GraspChain:
                     out["retrieve_reached"], out["retrieve_status"] = d_rreach, d_rstat
                 if observation is not None:
                     out["retrieve_counts"] = d_rcnt
+                    if held is not None:
+                        out["retrieve_held_counts"] = d_hcnt
                 if retime is not None:
                     out["retrieve_durations"], out["retrieve_retime_status"] = d_rdur, d_rrst
                     out.update({"retrieve_" + k: v for k, v in zip(("q", "qd", "qdd"), d_rsamp) if v is not None})

@@ -117,7 +117,9 @@ class GTOPlanner:
                 solution["f"].toarray().flatten())
 
     def retrieve_path(self, plan, mode="lift", distance=0.3, steps=10, direction=(0.0, 0.0, 1.0), closed_joints=None,
-                      closed_value=0.0, max_iter=50, pos_tol=0.01, rot_tol_deg=5.0, retime=None):
+                      closed_value=0.0, max_iter=50, pos_tol=0.01, rot_tol_deg=5.0, retime=None, observation=None,
+                      held_points=None, n_held=None, object_pose=None, labels=None, held_label=None,
+                      base_position=(0.0, 0.0, 0.0)):
         """The motion after the grasp (examples/pybullet_gto_planning.py:301-313) for a solved ``plan`` (ndof, T), or
         (B, ndof, T) for B of them: mode "lift" moves link_ee by ``distance`` along ``direction`` in ``steps`` IK steps, each
         seeded from the one before, with the gripper's pose held (the tabletop driver's env.retract; pybullet's position-only
@@ -128,7 +130,13 @@ class GTOPlanner:
         retime: a dict ``vmax, amax[, subdiv, n_samples, reached_only]`` to also retime the path under these joint limits
         (gto_retime_paths); reached_only=True retimes columns 0 .. reached of a lift, the part that met its goals.  The
         return value is then (path, reached, trajectory): the dict of ``SolverHandle.retime_paths`` (of one path for one
-        plan)."""
+        plan).
+        observation + held_points: the points of the object the robot holds (per plan (n_i, 3) world points at the moment of
+        the grasp, or a padded array with n_held; object-frame points with object_pose (4, 4) per plan) are carried with
+        link_ee along the path from the grasp configuration -- the plan's last waypoint, which is column 0 of a lift
+        and is not part of a reversed path -- and counted inside ``observation`` at every column
+        (gto_check_held_paths; labels / held_label: the segmentation image of a depth observation and the held object's
+        label).  The return value then ends with one more element, the dict ``{"held_counts": (columns,) | (B, columns)}``."""
         from . import _capi
         from .grasp_chain import finger_joints
         plan = np.asarray(plan, dtype=np.float64)
@@ -156,12 +164,27 @@ class GTOPlanner:
             reached = np.full(plans.shape[0], n, dtype=np.int32)
         else:
             raise ValueError('retrieve_path: mode is "lift" or "reverse"')
+        checks = ()
+        if held_points is not None:
+            if observation is None:
+                raise ValueError("retrieve_path: held_points need the observation they are counted in")
+            from .observation import as_observation
+            B = plans.shape[0]
+            if single and n_held is None and isinstance(held_points, np.ndarray) and held_points.ndim == 2:
+                held_points = [held_points]
+            # a lift starts at the grasp (its column 0); a reversed path leaves that column out: the plan's last waypoint
+            attach = plans if mode == "reverse" else None
+            pose = None if object_pose is None else np.broadcast_to(np.asarray(object_pose, dtype=np.float64).reshape(-1, 16), (B, 16))
+            base = np.asarray(base_position, dtype=np.float64)
+            counts = h.check_held_paths(as_observation(observation), path, held_points, n_held=n_held, attach=attach,
+                                        object_pose=pose, labels=labels, held_label=held_label, base_pos=base)
+            checks = ({"held_counts": counts[0] if single else counts},)
         if retime is None:
-            return (path[0], int(reached[0])) if single else (path, reached)
+            return ((path[0], int(reached[0])) if single else (path, reached)) + checks
         unknown = set(retime) - {"vmax", "amax", "subdiv", "n_samples", "reached_only"}
         if unknown:
             raise TypeError(f"retrieve_path: unexpected retime key(s) {sorted(unknown)}")
         n_cols = reached + 1 if mode == "lift" and retime.get("reached_only", False) else None
         traj = h.retime_paths(path, retime["vmax"], retime["amax"], n_cols=n_cols, subdiv=int(retime.get("subdiv", 2)),
                               n_samples=int(retime.get("n_samples", 100)))
-        return (path[0], int(reached[0]), {k: v[0] for k, v in traj.items()}) if single else (path, reached, traj)
+        return ((path[0], int(reached[0]), {k: v[0] for k, v in traj.items()}) if single else (path, reached, traj)) + checks

@@ -10,6 +10,8 @@ mesh_to_sdf/depth_point_cloud.py:25) and asks it many times: the grasp collision
     sdf(points)                       get_sdf / inside at world points (the bits of the stand-alone entry points)
     check_posed(points, poses)        per pose, how many of the placed points are inside (the grasp filter)
     check_plans(handle, plans, base)  per plan and waypoint, how many robot surface points are inside (the plan statistic)
+    check_held_paths(handle, paths, held_points, ...)  per path and column, how many points of the object the robot holds
+                                      are inside (the motion after the grasp)
 
 with only the counts coming back to the host.  "Inside" is ``get_sdf < 0`` of the reference except at a query that
 coincides with a cloud point (include/gto_solver.h).
@@ -118,6 +120,22 @@ class Observation:
     def check_plans(self, handle, plans, base_pos=(0.0, 0.0, 0.0)):
         """int32 (B, T): SolverHandle.check_plans of ``handle`` against this observation."""
         return handle.check_plans(self, plans, base_pos)
+
+    def check_held_paths(self, robot_or_handle, paths, held_points, n_held=None, attach=None, attach_col=None, object_pose=None,
+                         labels=None, held_label=None, base_pos=(0.0, 0.0, 0.0), link_ee=None, link_gripper=None):
+        """int32 (B, Tp): SolverHandle.check_held_paths against this observation -- per path (B, ndof, Tp) and column, how many
+        of the held object's points, carried rigidly with link_ee from the configuration of the grasp, are inside.
+        held_points: a list of per-plan (n_i, 3) arrays, or a padded array (B, P_max, 3) with n_held (B,).
+        robot_or_handle: a ``SolverHandle``, or a robot model (``GTORobotModel``) together with link_ee / link_gripper, whose
+        cached handle is used.  The other arguments: ``SolverHandle.check_held_paths``."""
+        handle = robot_or_handle
+        if not hasattr(handle, "check_held_paths"):
+            if link_ee is None:
+                raise GTOError("Observation.check_held_paths: a robot model needs link_ee (and link_gripper, default: link_ee)")
+            handle = robot_or_handle.solver_handle(link_ee, link_ee if link_gripper is None else link_gripper, _capi.default_opts(),
+                                                   role="retrieve")
+        return handle.check_held_paths(self, paths, held_points, n_held=n_held, attach=attach, attach_col=attach_col,
+                                       object_pose=object_pose, labels=labels, held_label=held_label, base_pos=base_pos)
 
 
 def as_observation(cloud_or_obs) -> Observation:

@@ -904,6 +904,59 @@ int gto_check_paths(gto_handle* h, gto_observation* obs, int32_t B, int32_t Tp, 
 int gto_check_paths_device(gto_handle* h, gto_observation* obs, int32_t B, int32_t Tp, const double* paths,
                            const double* base_pos, int32_t per_plan_base, int32_t* count_out, void* stream);
 /*
+ * The grasped object's points in collision along the motion after the grasp.  gto_check_paths counts the ROBOT's surface
+ * points; during the retrieve motion the robot carries the object, and the object is usually what meets the neighbour on the
+ * table or the shelf board above.  Here a per-plan point set rides rigidly with link_ee from the configuration q_att at which
+ * the object was grasped, and count_out [B][Tp] is the number of held points inside the observation at every column.  The
+ * reference has no counterpart (its judge is the simulator).  Additions (the ABI number stays).
+ *   paths [B][ndof][Tp], base_pos, per_plan_base   as gto_check_paths; Tp >= 1
+ *   attach, attach_ld, attach_col   q_att[b][j] = attach[((size_t)b * ndof + j) * attach_ld + attach_col].  attach NULL means
+ *                 paths, Tp, column 0: the lift, whose column 0 is the plan's last waypoint.  The reverse mode passes the
+ *                 solved plans [B][ndof][T] with attach_ld = T and attach_col = T - 1, because its path leaves the grasp
+ *                 column out.  With attach given, attach_col outside [0, attach_ld): GTO_ERR_INVALID_ARG.
+ *   held_points [B][P_max][3], n_held [B]   plan b's points are rows 0 .. n_held[b] - 1.  gto_check_held_paths_device: n_held
+ *                 lives on the device and a value outside [0, P_max] is read as clamped; gto_check_held_paths: such a value
+ *                 gives GTO_ERR_INVALID_ARG.
+ *   object_pose [B][16] or NULL   NULL: the points are in the observation's world frame at the moment of the grasp.  Given:
+ *                 they are in the object's frame and x = R p + t of object_pose_b with gto_observation_check_posed's
+ *                 expression, term for term (the products added in the order x, z, y, then the translation).
+ *   labels [H][W] int32 or NULL, held_label [B]   the segmentation image of a depth observation (the camera's mask image; the
+ *                 driver builds target_mask = mask == object_id from it) and the label of the object plan b holds.  The depth
+ *                 visibility test reads the raw image, which contains the held object: a held point at the grasp column lies
+ *                 on or behind the object's own seen surface and would always count as inside.  So for plan b a point that
+ *                 projects to a pixel whose label equals held_label[b] counts as outside: what was behind the held object was
+ *                 never seen.  labels NULL: no pixel is ignored.  Both are ignored for a cloud observation.  labels given
+ *                 with held_label NULL: GTO_ERR_INVALID_ARG (for either kind of observation).
+ * Per plan b, held point i and column t, in FP64 without contraction; E_t is link_ee's frame at column t from the device
+ * kinematics (the bits gto_eval_fk returns for link_ee, rows R | tr), E_a the same at q_att, base the plan's base:
+ *   d[a]   = (x[a] - base[a]) - E_a.tr[a]
+ *   p[c]   = (E_a.R[0][c]*d[0] + E_a.R[1][c]*d[1]) + E_a.R[2][c]*d[2]
+ *   X_t[r] = (((E_t.R[r][0]*p[0] + E_t.R[r][1]*p[1]) + E_t.R[r][2]*p[2]) + E_t.tr[r]) + base[r]
+ * count_out [b][t] = the number of i < n_held[b] with X_t inside obs: "inside" as gto_check_plans defines it for the
+ * observation's kind, plus the label rule.  n_held[b] = 0 gives zeros.  -1 for a column with a non-finite entry; -1 for EVERY
+ * column of plan b when q_att, the base or (if given) object_pose_b holds a non-finite entry; no other plan's count changes.
+ * A held point with a non-finite coordinate is not counted and changes no other point's result (for a cloud observation it
+ * goes to the search as a NaN query, which the search reports outside).  Every plan's result is bit for bit the same in any
+ * batch and at any position in it, and whatever the number of columns a workgroup takes (GTO_CHECK_TG).
+ * Two launches for a depth observation (the attach step once per plan, then one workgroup per plan and column group); a
+ * cloud observation takes the launch chain of gto_check_paths at Tp * P_max queries per plan, at most 2^24 queries at a time.
+ * GTO_ERR_INVALID_ARG: null handle, observation, base_pos, paths, held_points, n_held or count_out; B < 0, Tp < 1, P_max < 1;
+ * an observation on another device than the handle's; the cases above.  GTO_ERR_UNSUPPORTED: B or P_max above 65535.  B = 0:
+ * GTO_OK without a launch.  Works on every handle, whatever its number of optimised joints.  The _device variant takes device
+ * pointers (base_pos: HOST, as gto_check_paths_device) and enqueues on `stream` (NULL = the handle's) without a host
+ * synchronisation; the workspace lives on the handle: calls on one handle go to one stream, or the caller orders them (the
+ * rule of gto_check_plans_device).  gto_check_held_paths: the same with host arrays.
+ */
+int gto_check_held_paths(gto_handle* h, gto_observation* obs, int32_t B, int32_t Tp, const double* paths, const double* attach,
+                         int32_t attach_ld, int32_t attach_col, const double* held_points, int32_t P_max,
+                         const int32_t* n_held, const double* object_pose, const int32_t* labels, const int32_t* held_label,
+                         const double* base_pos, int32_t per_plan_base, int32_t* count_out);
+int gto_check_held_paths_device(gto_handle* h, gto_observation* obs, int32_t B, int32_t Tp, const double* paths,
+                                const double* attach, int32_t attach_ld, int32_t attach_col, const double* held_points,
+                                int32_t P_max, const int32_t* n_held, const double* object_pose, const int32_t* labels,
+                                const int32_t* held_label, const double* base_pos /*HOST*/, int32_t per_plan_base,
+                                int32_t* count_out, void* stream);
+/*
  * Retiming on paths of any length, each with its own column count: the contract of gto_retime_batch /
  * gto_retime_batch_device (above) with paths [B][ndof][Tp], Tp passed explicitly, and these differences.  Additions (the ABI
  * number stays).  Works on every handle, whatever its horizon and its number of optimised joints.
