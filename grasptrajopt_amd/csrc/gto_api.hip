@@ -3507,8 +3507,35 @@ void obs_cloud_votes(const SearchEnv& env, hipStream_t st, const gto_observation
 }
 // queries of a cloud observation per launch chain of a check: bounds the workspace (25 bytes per query)
 constexpr long long kCheckChunkQueries = 1ll << 24;
-// how many of n items (grasps, plans) of per_item >= 1 queries each go into one launch chain: at least one
-int chunk_items(int n, long long per_item) { return (int)std::min<long long>(n, std::max<long long>(1, kCheckChunkQueries / per_item)); }
+// how many of n items (grasps, plans) of per_item >= 1 queries each go into one launch chain: at least one.  An item count
+// can exceed an int (the grasp filter's run of poses): all item arithmetic is long long.
+long long chunk_items(long long n, long long per_item) { return std::min(n, std::max(1ll, kCheckChunkQueries / per_item)); }
+long long cloud_chunk(long long n_items, int rows_per_item, int P) { return chunk_items(n_items, (long long)rows_per_item * std::max(1, P)); }
+// The counts of n_items items of rows_per_item rows of P points each against a cloud observation, on `st`, one launch chain
+// per chunk: place(i0, m, d_xyz, count + i0 * rows_per_item) launches the caller's kernel for items [i0, i0 + m), which
+// writes their world points [m][rows_per_item][P][3] and marks the rows that report -1; then the votes of the samples'
+// normals and their sum per row.  d_xyz / d_flags: room for one chunk (cloud_chunk).
+template <class Place>
+void cloud_counts(const SearchEnv& env, hipStream_t st, const gto_observation* o, long long n_items, int rows_per_item, int P, double* d_xyz,
+                  uint8_t* d_flags, int32_t* count, Place place) {
+  const long long chunk = cloud_chunk(n_items, rows_per_item, P);
+  for (long long i0 = 0; i0 < n_items; i0 += chunk) {
+    const long long m = std::min(chunk, n_items - i0);
+    int32_t* cnt = count + (size_t)i0 * rows_per_item;
+    place(i0, m, d_xyz, cnt);
+    if (P) obs_cloud_votes(env, st, o, d_xyz, (long)(m * rows_per_item * P), d_flags);
+    hipLaunchKernelGGL(k_count_flags, dim3((unsigned)(m * rows_per_item)), dim3(256), 0, st, d_flags, P, cnt);
+  }
+}
+// the handle's workspace for one chunk of cloud_counts (ck_xyz, ck_flags: see the header on streams)
+int cloud_workspace(gto_handle* h, long long n_items, int rows_per_item, int P, double** d_xyz, uint8_t** d_flags) {
+  const size_t q = (size_t)cloud_chunk(n_items, rows_per_item, P) * rows_per_item * P;
+  int rc;
+  if ((rc = ensure(h, h->ck_xyz, q * 3 * sizeof(double)))) return rc;
+  if ((rc = ensure(h, h->ck_flags, q))) return rc;
+  *d_xyz = h->ck_xyz.as<double>(), *d_flags = h->ck_flags.as<uint8_t>();
+  return GTO_OK;
+}
 // What gto_check_plans and its device variant check before any device work.  *empty: nothing to do (B = 0).
 int check_plans_args(gto_handle* h, const gto_observation* o, int32_t B, const double* plans, const double* base_pos, bool* empty) {
   *empty = B == 0;
@@ -3524,6 +3551,37 @@ int check_waypoints_per_group() {
   const char* e = getenv("GTO_CHECK_TG");
   const int v = e ? atoi(e) : GTO_CHECK_TG;
   return v >= 1 && v <= GTO_CHECK_TG ? v : GTO_CHECK_TG;
+}
+int check_lds_fits(gto_handle* h, size_t lds) {
+  return lds > 150 * 1024 ? fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the collision-check kernel's LDS") : GTO_OK;
+}
+// the launch shape of the path checks (k_check_plans, k_check_held) over T columns: grid (plans, tgroups), lds bytes
+struct CheckShape {
+  size_t lds;
+  int tg;
+  unsigned tgroups;
+};
+int check_shape(gto_handle* h, int T, CheckShape* s) {
+  s->lds = sizeof(double) * check_plans_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
+  s->tg = check_waypoints_per_group();
+  s->tgroups = (unsigned)((T + s->tg - 1) / s->tg);
+  return check_lds_fits(h, s->lds);
+}
+// the base of the path checks' plans: (b0, b1, b2) for every plan, or d_base [B][3] on the device
+struct CheckBase {
+  double b0, b1, b2;
+  const double* d_base;
+};
+int stage_check_base(gto_handle* h, const double* base_pos, int32_t per_plan_base, int32_t B, hipStream_t st, CheckBase* out) {
+  *out = {per_plan_base ? 0.0 : base_pos[0], per_plan_base ? 0.0 : base_pos[1], per_plan_base ? 0.0 : base_pos[2], nullptr};
+  if (!per_plan_base) return GTO_OK;
+  // hipMemcpyAsync from pageable host memory returns once the array has been copied to the runtime's staging memory (the
+  // documented behaviour of the asynchronous copies for pageable memory): the caller's array is free on return, and the
+  // copy is ordered on `st` in front of the kernel.  ck_base is one buffer per handle: see the header on streams.
+  if (int rc = ensure(h, h->ck_base, (size_t)B * 3 * sizeof(double))) return rc;
+  HIPCHK(h, hipMemcpyAsync(h->ck_base.get(), base_pos, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  out->d_base = h->ck_base.as<const double>();
+  return GTO_OK;
 }
 }  // namespace
 
@@ -3618,17 +3676,13 @@ int gto_observation_check_posed(gto_observation* o, const double* points, int32_
   if (o->is_depth) {
     hipLaunchKernelGGL(k_check_posed<true>, dim3((unsigned)n), dim3(256), 0, 0, d_points, (int)P, d_poses, depth_view(o), (double*)nullptr, d_count);
   } else {
-    const int chunk = chunk_items(n, std::max(1, (int)P));
-    double* d_xyz = c.alloc<double>((size_t)chunk * P * 3);
-    uint8_t* d_flags = c.alloc<uint8_t>((size_t)chunk * P);
+    const size_t chunk = (size_t)cloud_chunk(n, 1, P);
+    double* d_xyz = c.alloc<double>(chunk * P * 3);
+    uint8_t* d_flags = c.alloc<uint8_t>(chunk * P);
     if (!d_xyz || !d_flags) return c.no_memory();
-    for (int i0 = 0; i0 < n; i0 += chunk) {
-      const int m = std::min(chunk, n - i0);
-      hipLaunchKernelGGL(k_check_posed<false>, dim3((unsigned)m), dim3(256), 0, 0, d_points, (int)P, d_poses + (size_t)i0 * 16, ObsDepthView{}, d_xyz,
-                         d_count + i0);
-      if (P) obs_cloud_votes(c.env, 0, o, d_xyz, (long)m * P, d_flags);
-      hipLaunchKernelGGL(k_count_flags, dim3((unsigned)m), dim3(256), 0, 0, d_flags, (int)P, d_count + i0);
-    }
+    cloud_counts(c.env, 0, o, n, 1, P, d_xyz, d_flags, d_count, [&](long long i0, long long m, double* xyz, int32_t* cnt) {
+      hipLaunchKernelGGL(k_check_posed<false>, dim3((unsigned)m), dim3(256), 0, 0, d_points, (int)P, d_poses + (size_t)i0 * 16, ObsDepthView{}, xyz, cnt);
+    });
   }
   DEPTH_TRY(c.sync());
   DEPTH_TRY(c.download(count_out, d_count, (size_t)n));
@@ -3644,42 +3698,26 @@ int gto_check_paths_device(gto_handle* h, gto_observation* o, int32_t B, int32_t
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t st = stream ? (hipStream_t)stream : h->stream;
   const int T = Tp, P = h->rb.n_points, ndof = h->rb.ndof;
-  const size_t lds = sizeof(double) * check_plans_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
-  if (lds > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the collision-check kernel's LDS");
-  const int tg = check_waypoints_per_group();
-  const SearchEnv env = search_env();
-  const unsigned tgroups = (unsigned)((T + tg - 1) / tg);
+  CheckShape sh;
+  CheckBase base;
   int rc;
-  const double* d_base = nullptr;
-  if (per_plan_base) {
-    // hipMemcpyAsync from pageable host memory returns once the array has been copied to the runtime's staging memory (the
-    // documented behaviour of the asynchronous copies for pageable memory): the caller's array is free on return, and the
-    // copy is ordered on `st` in front of the kernel.  ck_base is one buffer per handle: see the header on streams.
-    if ((rc = ensure(h, h->ck_base, (size_t)B * 3 * sizeof(double)))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->ck_base.get(), base_pos, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-    d_base = h->ck_base.as<const double>();
-  }
-  const double b0 = per_plan_base ? 0.0 : base_pos[0], b1 = per_plan_base ? 0.0 : base_pos[1], b2 = per_plan_base ? 0.0 : base_pos[2];
+  if ((rc = check_shape(h, T, &sh))) return rc;
+  if ((rc = stage_check_base(h, base_pos, per_plan_base, B, st, &base))) return rc;
   if (o->is_depth) {
-    HIPCHK(h, raise_dynamic_lds((const void*)k_check_plans<true>, lds));
+    HIPCHK(h, raise_dynamic_lds((const void*)k_check_plans<true>, sh.lds));
     if (count_out)
-      hipLaunchKernelGGL(k_check_plans<true>, dim3((unsigned)B, tgroups), dim3(256), lds, st, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_plink, T, tg, plans,
-                         b0, b1, b2, d_base, depth_view(o), (double*)nullptr, count_out);
+      hipLaunchKernelGGL(k_check_plans<true>, dim3((unsigned)B, sh.tgroups), dim3(256), sh.lds, st, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_plink, T,
+                         sh.tg, plans, base.b0, base.b1, base.b2, base.d_base, depth_view(o), (double*)nullptr, count_out);
   } else if (count_out) {
-    HIPCHK(h, raise_dynamic_lds((const void*)k_check_plans<false>, lds));
-    const int chunk = chunk_items(B, (long long)T * std::max(1, P));
-    if ((rc = ensure(h, h->ck_xyz, (size_t)chunk * T * P * 3 * sizeof(double)))) return rc;
-    if ((rc = ensure(h, h->ck_flags, (size_t)chunk * T * P))) return rc;
-    double* d_xyz = h->ck_xyz.as<double>();
-    uint8_t* d_flags = h->ck_flags.as<uint8_t>();
-    for (int i0 = 0; i0 < B; i0 += chunk) {
-      const int m = std::min(chunk, B - i0);
-      int32_t* cnt = count_out + (size_t)i0 * T;
-      hipLaunchKernelGGL(k_check_plans<false>, dim3((unsigned)m, tgroups), dim3(256), lds, st, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_plink, T, tg,
-                         plans + (size_t)i0 * ndof * T, b0, b1, b2, d_base ? d_base + (size_t)i0 * 3 : nullptr, ObsDepthView{}, d_xyz, cnt);
-      if (P) obs_cloud_votes(env, st, o, d_xyz, (long)m * T * P, d_flags);
-      hipLaunchKernelGGL(k_count_flags, dim3((unsigned)(m * T)), dim3(256), 0, st, d_flags, P, cnt);
-    }
+    HIPCHK(h, raise_dynamic_lds((const void*)k_check_plans<false>, sh.lds));
+    double* d_xyz;
+    uint8_t* d_flags;
+    if ((rc = cloud_workspace(h, B, T, P, &d_xyz, &d_flags))) return rc;
+    cloud_counts(search_env(), st, o, B, T, P, d_xyz, d_flags, count_out, [&](long long i0, long long m, double* xyz, int32_t* cnt) {
+      hipLaunchKernelGGL(k_check_plans<false>, dim3((unsigned)m, sh.tgroups), dim3(256), sh.lds, st, h->d_rb, h->d_px, h->d_py, h->d_pz, h->d_plink, T,
+                         sh.tg, plans + (size_t)i0 * ndof * T, base.b0, base.b1, base.b2, base.d_base ? base.d_base + (size_t)i0 * 3 : nullptr,
+                         ObsDepthView{}, xyz, cnt);
+    });
   }
   HIPCHK(h, hipGetLastError());
   return GTO_OK;
@@ -3729,7 +3767,7 @@ int gto_filter_grasps_device(gto_handle* h, int32_t B, int32_t n_max, gto_observ
                        points, (int)P, (int)n_max, object_pose, grasps, n_grasps, world_to_base, base_pos, coff, ioff, has_ik, ws_plan, ws_ik,
                        ws_count);
   }
-  // the cloud objects: every run of consecutive objects that name one observation takes gto_observation_check_posed's chain
+  // the cloud objects: every run of consecutive objects that name one observation is one cloud_counts over the run's poses
   if (items.size() < (size_t)B) {
     if ((rc = ensure(h, h->fg_pose, rows * 16 * sizeof(double)))) return rc;
     double* ws_pose = h->fg_pose.as<double>();
@@ -3744,17 +3782,14 @@ int gto_filter_grasps_device(gto_handle* h, int32_t B, int32_t n_max, gto_observ
       const long long n = (long long)(b1 - b0) * n_max;  // the run's poses: at most 65535 * 65535
       hipLaunchKernelGGL(k_filter_pose, dim3((unsigned)((n_max + 63) / 64), (unsigned)(b1 - b0)), dim3(64), 0, st, b0, (int)n_max, object_pose, grasps,
                          n_grasps, world_to_base, base_pos, coff, ioff, has_ik, ws_plan, ws_ik, ws_pose);
-      const long long chunk = std::min<long long>(n, std::max<long long>(1, kCheckChunkQueries / P));
-      if ((rc = ensure(h, h->ck_xyz, (size_t)chunk * P * 3 * sizeof(double)))) return rc;
-      if ((rc = ensure(h, h->ck_flags, (size_t)chunk * P))) return rc;
-      for (long long i0 = 0; i0 < n; i0 += chunk) {
-        const long long m = std::min(chunk, n - i0);
-        const size_t at = (size_t)b0 * n_max + (size_t)i0;
-        hipLaunchKernelGGL(k_check_posed<false>, dim3((unsigned)m), dim3(256), 0, st, points, (int)P, ws_pose + at * 16, ObsDepthView{},
-                           h->ck_xyz.as<double>(), ws_count + at);
-        obs_cloud_votes(env, st, obs[b0], h->ck_xyz.as<const double>(), (long)(m * P), h->ck_flags.as<uint8_t>());
-        hipLaunchKernelGGL(k_count_flags, dim3((unsigned)m), dim3(256), 0, st, h->ck_flags.as<const uint8_t>(), (int)P, ws_count + at);
-      }
+      double* d_xyz;
+      uint8_t* d_flags;
+      if ((rc = cloud_workspace(h, n, 1, P, &d_xyz, &d_flags))) return rc;
+      const size_t at = (size_t)b0 * n_max;
+      cloud_counts(env, st, obs[b0], n, 1, P, d_xyz, d_flags, ws_count + at, [&](long long i0, long long m, double* xyz, int32_t* cnt) {
+        hipLaunchKernelGGL(k_check_posed<false>, dim3((unsigned)m), dim3(256), 0, st, points, (int)P, ws_pose + (at + (size_t)i0) * 16, ObsDepthView{},
+                           xyz, cnt);
+      });
       b0 = b1;
     }
   }
@@ -3829,19 +3864,12 @@ int gto_check_held_paths_device(gto_handle* h, gto_observation* o, int32_t B, in
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t st = stream ? (hipStream_t)stream : h->stream;
   const int T = Tp, P = P_max, ndof = h->rb.ndof;
-  const size_t lds = sizeof(double) * check_plans_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
   const size_t lds_att = sizeof(double) * held_attach_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
-  if (lds > 150 * 1024 || lds_att > 150 * 1024) return fail(h, GTO_ERR_UNSUPPORTED, "robot too large for the collision-check kernel's LDS");
-  const int tg = check_waypoints_per_group();
-  const unsigned tgroups = (unsigned)((T + tg - 1) / tg);
+  CheckShape sh;
+  CheckBase base;
   int rc;
-  const double* d_base = nullptr;
-  if (per_plan_base) {  // as gto_check_paths_device: the caller's array is free on return, the copy is ordered on `st`
-    if ((rc = ensure(h, h->ck_base, (size_t)B * 3 * sizeof(double)))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->ck_base.get(), base_pos, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-    d_base = h->ck_base.as<const double>();
-  }
-  const double b0 = per_plan_base ? 0.0 : base_pos[0], b1 = per_plan_base ? 0.0 : base_pos[1], b2 = per_plan_base ? 0.0 : base_pos[2];
+  if ((rc = check_shape(h, T, &sh)) || (rc = check_lds_fits(h, lds_att))) return rc;
+  if ((rc = stage_check_base(h, base_pos, per_plan_base, B, st, &base))) return rc;
   if ((rc = ensure(h, h->hd_p, (size_t)B * P * 3 * sizeof(double)))) return rc;
   if ((rc = ensure(h, h->hd_bad, (size_t)B * sizeof(int32_t)))) return rc;
   double* d_p = h->hd_p.as<double>();
@@ -3850,29 +3878,23 @@ int gto_check_held_paths_device(gto_handle* h, gto_observation* o, int32_t B, in
   const double* att = attach ? attach : paths;
   const int att_ld = attach ? attach_ld : T, att_col = attach ? attach_col : 0;
   HIPCHK(h, raise_dynamic_lds((const void*)k_held_attach, lds_att));
-  hipLaunchKernelGGL(k_held_attach, dim3((unsigned)B), dim3(256), lds_att, st, h->d_rb, att, att_ld, att_col, b0, b1, b2, d_base, held_points, P, n_held,
-                     object_pose, d_p, d_bad);
+  hipLaunchKernelGGL(k_held_attach, dim3((unsigned)B), dim3(256), lds_att, st, h->d_rb, att, att_ld, att_col, base.b0, base.b1, base.b2, base.d_base,
+                     held_points, P, n_held, object_pose, d_p, d_bad);
   if (o->is_depth) {
-    HIPCHK(h, raise_dynamic_lds((const void*)k_check_held<true>, lds));
-    hipLaunchKernelGGL(k_check_held<true>, dim3((unsigned)B, tgroups), dim3(256), lds, st, h->d_rb, T, tg, paths, b0, b1, b2, d_base, (const double*)d_p, P,
-                       n_held, (const int32_t*)d_bad, depth_view(o), labels, held_label, (double*)nullptr, count_out);
+    HIPCHK(h, raise_dynamic_lds((const void*)k_check_held<true>, sh.lds));
+    hipLaunchKernelGGL(k_check_held<true>, dim3((unsigned)B, sh.tgroups), dim3(256), sh.lds, st, h->d_rb, T, sh.tg, paths, base.b0, base.b1, base.b2,
+                       base.d_base, (const double*)d_p, P, n_held, (const int32_t*)d_bad, depth_view(o), labels, held_label, (double*)nullptr,
+                       count_out);
   } else {
-    HIPCHK(h, raise_dynamic_lds((const void*)k_check_held<false>, lds));
-    const SearchEnv env = search_env();
-    const int chunk = chunk_items(B, (long long)T * P);
-    if ((rc = ensure(h, h->ck_xyz, (size_t)chunk * T * P * 3 * sizeof(double)))) return rc;
-    if ((rc = ensure(h, h->ck_flags, (size_t)chunk * T * P))) return rc;
-    double* d_xyz = h->ck_xyz.as<double>();
-    uint8_t* d_flags = h->ck_flags.as<uint8_t>();
-    for (int i0 = 0; i0 < B; i0 += chunk) {
-      const int m = std::min(chunk, B - i0);
-      int32_t* cnt = count_out + (size_t)i0 * T;
-      hipLaunchKernelGGL(k_check_held<false>, dim3((unsigned)m, tgroups), dim3(256), lds, st, h->d_rb, T, tg, paths + (size_t)i0 * ndof * T, b0, b1, b2,
-                         d_base ? d_base + (size_t)i0 * 3 : nullptr, (const double*)d_p + (size_t)i0 * P * 3, P, n_held + i0,
-                         (const int32_t*)d_bad + i0, ObsDepthView{}, (const int32_t*)nullptr, (const int32_t*)nullptr, d_xyz, cnt);
-      obs_cloud_votes(env, st, o, d_xyz, (long)m * T * P, d_flags);
-      hipLaunchKernelGGL(k_count_flags, dim3((unsigned)(m * T)), dim3(256), 0, st, d_flags, P, cnt);
-    }
+    HIPCHK(h, raise_dynamic_lds((const void*)k_check_held<false>, sh.lds));
+    double* d_xyz;
+    uint8_t* d_flags;
+    if ((rc = cloud_workspace(h, B, T, P, &d_xyz, &d_flags))) return rc;
+    cloud_counts(search_env(), st, o, B, T, P, d_xyz, d_flags, count_out, [&](long long i0, long long m, double* xyz, int32_t* cnt) {
+      hipLaunchKernelGGL(k_check_held<false>, dim3((unsigned)m, sh.tgroups), dim3(256), sh.lds, st, h->d_rb, T, sh.tg, paths + (size_t)i0 * ndof * T,
+                         base.b0, base.b1, base.b2, base.d_base ? base.d_base + (size_t)i0 * 3 : nullptr, (const double*)d_p + (size_t)i0 * P * 3, P,
+                         n_held + i0, (const int32_t*)d_bad + i0, ObsDepthView{}, (const int32_t*)nullptr, (const int32_t*)nullptr, xyz, cnt);
+    });
   }
   HIPCHK(h, hipGetLastError());
   return GTO_OK;

@@ -2,8 +2,8 @@
 // include/gto_solver.h).  gto_check_paths counts the ROBOT's surface points inside the observation at every column of the
 // retrieve path; during that motion the robot carries the object, and the object is what meets the neighbour on the table or
 // the shelf board above.  The held points ride rigidly with link_ee from the configuration the object was grasped at:
-//   k_held_attach        one workgroup per plan: kinematics of q_att (fk_mfma_tree, one configuration), the optional placement
-//                        of object-frame points (k_check_posed's expression), then p = E_a^-1 (x - base) per point into a
+//   k_held_attach        one workgroup per plan: kinematics of q_att (plan_cost_kinematics<1>), the optional placement
+//                        of object-frame points (place_einsum), then p = E_a^-1 (x - base) per point into a
 //                        workspace [B][P_max][3] and a per-plan bad flag.  Once per plan, not once per column group.
 //   k_check_held<true>   one workgroup per (plan, up to GTO_CHECK_TG columns) in k_check_plans' LDS layout: the columns'
 //                        kinematics, E_t of link_ee from the tree's frames, lanes over the held points with a uniform trip
@@ -16,7 +16,7 @@
 #pragma once
 #include "gto_observe.h"
 
-// k_check_plans' layout for one configuration, then E_a [12] and the bad flag
+// plan_cost_lds<1>'s layout, then E_a [12] and the bad flag
 __host__ __device__ inline int held_attach_lds_doubles(int F, int L, int n) { return plan_cost_lds_doubles_tg(1, F, L, n) + 16; }
 
 // how many points of plan b count: n_held lives on the device, so a value outside [0, P_max] is read as clamped
@@ -24,8 +24,8 @@ __device__ __forceinline__ int held_point_count(const int32_t* __restrict__ n_he
   return min(max(n_held[b], 0), P_max);
 }
 
-// rows 0..2 of link_ee's frame (row-major 3x4: R | tr) of configuration kq from the transposed frames fk_mfma_tree left
-// in s_X: the entries gto_eval_fk writes
+// rows 0..2 of link_ee's frame (row-major 3x4: R | tr) of configuration kq from the transposed frames
+// plan_cost_kinematics left in s_X: the entries gto_eval_fk writes
 __device__ __forceinline__ double held_frame_entry(const RobotDev* __restrict__ rb, const double* __restrict__ s_X, int F, int kq, int e) {
   const double* Xg = s_X + (size_t)kq * 32 * F + (rb->fk_rounds & 1) * 16 * F;
   return Xg[fkx(rb->frame_ee, 4 * (e & 3) + (e >> 2))];
@@ -43,38 +43,19 @@ __global__ __launch_bounds__(256) void k_held_attach(const RobotDev* __restrict_
                                                      int32_t* __restrict__ bad_out) {
 #pragma clang fp contract(off)
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int F = rb->n_frames, L = rb->n_links, n = rb->n_opt, ndof = rb->ndof;
+  const int F = rb->n_frames, ndof = rb->ndof;
   extern __shared__ __attribute__((aligned(16))) double smem_ha[];
-  double* s_tab = smem_ha;
-  double* s_sc = s_tab + fk_tab_doubles(F, L, n);  // [F][2]
-  double* s_X = s_sc + F * 2;
-  double* s_vis = s_X + fk_scratch_doubles(F, 1);  // (by-products of the kinematics, unused here)
-  double* s_screw = s_vis + L * 12;
-  double* s_E = smem_ha + plan_cost_lds_doubles_tg(1, F, L, n);  // [12]
+  const PlanCostLds m = plan_cost_lds<1>(rb, smem_ha);
+  double* s_E = smem_ha + plan_cost_lds_doubles_tg(1, F, rb->n_links, rb->n_opt);  // [12]
   int* s_bad = reinterpret_cast<int*>(s_E + 12);
-  const int nt = fk_tab_doubles(F, L, n);
-  for (int k = tid; k < nt; k += 256) s_tab[k] = rb->fk_tab[k];
   if (tid == 0) s_bad[0] = 0;
   __syncthreads();
   const double* qa = attach + (size_t)b * ndof * attach_ld + attach_col;
   if (tid < ndof && !isfinite(qa[(size_t)tid * attach_ld])) s_bad[0] = 1;
   __syncthreads();
   const bool q_bad = s_bad[0] != 0;
-  if (tid < F) {
-    const int jt = rb->joint_type[tid], dq = rb->q_index[tid];
-    double a = 0.0, cs = 1.0;
-    if (dq >= 0 && !q_bad) {
-      const double qv = qa[(size_t)dq * attach_ld];
-      if (jt == GTO_JOINT_REVOLUTE) sincos(qv, &a, &cs);
-      else if (jt == GTO_JOINT_PRISMATIC) a = qv;
-    }
-    s_sc[2 * tid] = a;
-    s_sc[2 * tid + 1] = cs;
-  }
-  __syncthreads();
-  fk_mfma_tree(rb, s_tab, 1, s_sc, s_X, reinterpret_cast<int*>(s_X + 32 * F + 64), tid, s_vis, s_screw, nullptr, screw_rows(n));
-  __syncthreads();
-  if (tid < 12) s_E[tid] = held_frame_entry(rb, s_X, F, 0, tid);
+  plan_cost_kinematics<1>(rb, m, 1, tid, [&](int, int dq) { return q_bad ? 0.0 : qa[(size_t)dq * attach_ld]; });
+  if (tid < 12) s_E[tid] = held_frame_entry(rb, m.X, F, 0, tid);
   __syncthreads();
   if (base_pp) b0 = base_pp[3 * (size_t)b], b1 = base_pp[3 * (size_t)b + 1], b2 = base_pp[3 * (size_t)b + 2];
   bool bad = q_bad || !(isfinite(b0) && isfinite(b1) && isfinite(b2));
@@ -95,12 +76,7 @@ __global__ __launch_bounds__(256) void k_held_attach(const RobotDev* __restrict_
     const size_t o = ((size_t)b * P_max + i) * 3;
     double x0 = held_points[o], x1 = held_points[o + 1], x2 = held_points[o + 2];
     const bool ok = i < nb && isfinite(x0) && isfinite(x1) && isfinite(x2);
-    if (object_pose) {  // k_check_posed's placement, term for term
-      const double y0 = ((M[0] * x0 + M[2] * x2) + M[1] * x1) + M[3];
-      const double y1 = ((M[4] * x0 + M[6] * x2) + M[5] * x1) + M[7];
-      const double y2 = ((M[8] * x0 + M[10] * x2) + M[9] * x1) + M[11];
-      x0 = y0, x1 = y1, x2 = y2;
-    }
+    if (object_pose) place_einsum(M, x0, x1, x2, &x0, &x1, &x2);
     const double d0 = (x0 - b0) - s_E[3], d1 = (x1 - b1) - s_E[7], d2 = (x2 - b2) - s_E[11];
     const double p0 = (s_E[0] * d0 + s_E[4] * d1) + s_E[8] * d2;
     const double p1 = (s_E[1] * d0 + s_E[5] * d1) + s_E[9] * d2;
@@ -125,18 +101,12 @@ __global__ __launch_bounds__(256) void k_check_held(const RobotDev* __restrict__
 #pragma clang fp contract(off)
   constexpr int TG = GTO_CHECK_TG;
   const int i = blockIdx.x, t0 = blockIdx.y * tg, tid = threadIdx.x;
-  const int F = rb->n_frames, L = rb->n_links, n = rb->n_opt, ndof = rb->ndof;
+  const int F = rb->n_frames, ndof = rb->ndof;
   const int ng = min(tg, T - t0);
   extern __shared__ __attribute__((aligned(16))) double smem_hk[];
-  double* s_tab = smem_hk;
-  double* s_sc = s_tab + fk_tab_doubles(F, L, n);  // [TG][F][2]
-  double* s_X = s_sc + TG * F * 2;
-  double* s_vis = s_X + fk_scratch_doubles(F, TG);  // [TG][L][12] (by-product of the kinematics, unused here)
-  double* s_screw = s_vis + TG * L * 12;            // the kinematics' screws; afterwards E_t [TG][12]
-  int* s_cnt = reinterpret_cast<int*>(s_screw + TG * screw_rows(n) * 6);  // [4][TG]
-  int* s_bad = s_cnt + 4 * TG;                                             // [TG]
-  const int nt = fk_tab_doubles(F, L, n);
-  for (int k = tid; k < nt; k += 256) s_tab[k] = rb->fk_tab[k];
+  const PlanCostLds m = plan_cost_lds<TG>(rb, smem_hk);
+  int* s_cnt = reinterpret_cast<int*>(m.red);  // [4][TG]
+  int* s_bad = s_cnt + 4 * TG;                 // [TG]
   if (tid < TG) s_bad[tid] = 0;
   __syncthreads();
   for (int idx = tid; idx < ng * ndof; idx += 256) {
@@ -144,23 +114,9 @@ __global__ __launch_bounds__(256) void k_check_held(const RobotDev* __restrict__
     if (!isfinite(paths[((size_t)i * ndof + j) * T + t0 + kq])) s_bad[kq] = 1;
   }
   __syncthreads();
-  for (int idx = tid; idx < ng * F; idx += 256) {
-    const int kq = idx / F, f = idx - kq * F;
-    const int jt = rb->joint_type[f], dq = rb->q_index[f];
-    double a = 0.0, cs = 1.0;
-    if (dq >= 0 && !s_bad[kq]) {
-      const double qv = paths[((size_t)i * ndof + dq) * T + t0 + kq];
-      if (jt == GTO_JOINT_REVOLUTE) sincos(qv, &a, &cs);
-      else if (jt == GTO_JOINT_PRISMATIC) a = qv;
-    }
-    s_sc[2 * idx] = a;
-    s_sc[2 * idx + 1] = cs;
-  }
-  __syncthreads();
-  fk_mfma_tree(rb, s_tab, ng, s_sc, s_X, reinterpret_cast<int*>(s_X + ng * 32 * F + 64), tid, s_vis, s_screw, nullptr, screw_rows(n));
-  __syncthreads();
-  double* s_E = s_screw;  // (TG * screw_rows * 6 >= TG * 12 doubles)
-  if (tid < ng * 12) s_E[tid] = held_frame_entry(rb, s_X, F, tid / 12, tid % 12);
+  plan_cost_kinematics<TG>(rb, m, ng, tid, [&](int kq, int dq) { return s_bad[kq] ? 0.0 : paths[((size_t)i * ndof + dq) * T + t0 + kq]; });
+  double* s_E = m.screw;  // the kinematics' screws are done with: E_t [TG][12] (TG * screw_rows * 6 >= TG * 12 doubles)
+  if (tid < ng * 12) s_E[tid] = held_frame_entry(rb, m.X, F, tid / 12, tid % 12);
   __syncthreads();
   if (base_pp) b0 = base_pp[3 * (size_t)i], b1 = base_pp[3 * (size_t)i + 1], b2 = base_pp[3 * (size_t)i + 2];
   const bool plan_ok = isfinite(b0) && isfinite(b1) && isfinite(b2) && bad_plan[i] == 0;

@@ -8,7 +8,7 @@
 // (mesh_to_sdf/depth_point_cloud.py:57-62, 127-141), so "get_sdf < 0" is "!is_outside" for every point that does not
 // coincide with a cloud point: the count needs no nearest-neighbour search.
 //   k_check_plans<true>   one workgroup per (plan, four waypoints): kinematics of the four configurations into LDS
-//                         (fk_mfma_tree, as k_eval_kin and k_plan_cost), lanes over the surface points in the handle's
+//                         (plan_cost_kinematics, gto_kernels.h), lanes over the surface points in the handle's
 //                         per-link order, depth_is_outside (gto_depth.h) per point, ballot + popcount per wave, the four
 //                         waves' counts through LDS, one store per waypoint
 //   k_check_posed<true>   one workgroup per pose: x = R p + t without contraction, the products added in the order
@@ -25,7 +25,7 @@
 // The grasp filter on the stream (gto_filter_grasps_device; the driver's checking stage, :203-236, for many objects):
 //   k_filter_depth        one workgroup per (row, depth object): the object's view from a device table, G = object pose x
 //                         grasp (x world_to_base), C = G x check_offset and the two goals once per workgroup (wave-uniform),
-//                         then k_check_posed<true>'s placement and counting against the object's own image
+//                         then k_check_posed<true>'s placement (place_einsum) and counting against the object's own image
 //   k_filter_pose         the same composition for the objects of a cloud observation: C goes to a workspace in the layout
 //                         k_check_posed<false> takes, whose launch chain (points, votes, k_count_flags) does the counting
 //   k_filter_compact      one wave per object: keep = count / P <= max_ratio, the kept rows' goals to their compacted
@@ -52,6 +52,23 @@ __device__ __forceinline__ void check_counts_to_lds(const int (&cnt)[TG], int ti
   }
 }
 
+// x = R p + t for a row-major pose M (3x4 or 4x4), without contraction: numpy.einsum("nij,pj->npi") adds the three
+// products of a row in the order x, z, y (numpy 2.2's unrolled inner loop) before the translation: the bits of
+// utils.grasp_collision_ratio, which tests/test_gpu_observation.py compares with
+__device__ __forceinline__ void place_einsum(const double* M, double x0, double x1, double x2, double* X0, double* X1, double* X2) {
+#pragma clang fp contract(off)  // numpy's products and sums, one rounding each
+  *X0 = ((M[0] * x0 + M[2] * x2) + M[1] * x1) + M[3];
+  *X1 = ((M[4] * x0 + M[6] * x2) + M[5] * x1) + M[7];
+  *X2 = ((M[8] * x0 + M[10] * x2) + M[9] * x1) + M[11];
+}
+
+// sum over the workgroup's four waves of a wave-uniform count; s_cnt: 4 ints of LDS.  Every thread calls it (a barrier).
+__device__ __forceinline__ int wave_counts_sum(int cnt, int tid, int* s_cnt) {
+  if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
+  __syncthreads();
+  return ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3];
+}
+
 // plans [nplans][ndof][T]; tg: waypoints per workgroup, 1..GTO_CHECK_TG (grid.y = ceil(T / tg); results do not depend on
 // it: every waypoint's kinematics are a matrix-core block of their own); base: (b0, b1, b2) for every plan, or base_pp [nplans][3].  DEPTH: count_out [nplans][T].
 // !DEPTH: xyz_out [nplans][T][P][3] and count_out [nplans][T] = -1 for a waypoint with a non-finite entry, else 0.
@@ -65,18 +82,13 @@ __global__ __launch_bounds__(256) void k_check_plans(const RobotDev* __restrict_
                                                      int32_t* __restrict__ count_out) {
   constexpr int TG = GTO_CHECK_TG;
   const int i = blockIdx.x, t0 = blockIdx.y * tg, tid = threadIdx.x;  // tg <= TG waypoints per workgroup (GTO_CHECK_TG)
-  const int F = rb->n_frames, L = rb->n_links, n = rb->n_opt, ndof = rb->ndof, P = rb->n_points;
+  const int L = rb->n_links, ndof = rb->ndof, P = rb->n_points;
   const int ng = min(tg, T - t0);
   extern __shared__ __attribute__((aligned(16))) double smem_ck[];
-  double* s_tab = smem_ck;
-  double* s_sc = s_tab + fk_tab_doubles(F, L, n);  // [TG][F][2]
-  double* s_X = s_sc + TG * F * 2;
-  double* s_vis = s_X + fk_scratch_doubles(F, TG);  // [TG][L][12]
-  double* s_screw = s_vis + TG * L * 12;            // (by-product of the kinematics, unused here)
-  int* s_cnt = reinterpret_cast<int*>(s_screw + TG * screw_rows(n) * 6);  // [4][TG]
-  int* s_bad = s_cnt + 4 * TG;                                             // [TG]
-  const int nt = fk_tab_doubles(F, L, n);
-  for (int k = tid; k < nt; k += 256) s_tab[k] = rb->fk_tab[k];
+  const PlanCostLds m = plan_cost_lds<TG>(rb, smem_ck);
+  const double* s_vis = m.vis;
+  int* s_cnt = reinterpret_cast<int*>(m.red);  // [4][TG]
+  int* s_bad = s_cnt + 4 * TG;                 // [TG]
   if (tid < TG) s_bad[tid] = 0;
   __syncthreads();
   for (int idx = tid; idx < ng * ndof; idx += 256) {
@@ -84,21 +96,7 @@ __global__ __launch_bounds__(256) void k_check_plans(const RobotDev* __restrict_
     if (!isfinite(plans[((size_t)i * ndof + j) * T + t0 + kq])) s_bad[kq] = 1;
   }
   __syncthreads();
-  for (int idx = tid; idx < ng * F; idx += 256) {
-    const int kq = idx / F, f = idx - kq * F;
-    const int jt = rb->joint_type[f], dq = rb->q_index[f];
-    double a = 0.0, cs = 1.0;
-    if (dq >= 0 && !s_bad[kq]) {
-      const double qv = plans[((size_t)i * ndof + dq) * T + t0 + kq];
-      if (jt == GTO_JOINT_REVOLUTE) sincos(qv, &a, &cs);
-      else if (jt == GTO_JOINT_PRISMATIC) a = qv;
-    }
-    s_sc[2 * idx] = a;
-    s_sc[2 * idx + 1] = cs;
-  }
-  __syncthreads();
-  fk_mfma_tree(rb, s_tab, ng, s_sc, s_X, reinterpret_cast<int*>(s_X + ng * 32 * F + 64), tid, s_vis, s_screw, nullptr, screw_rows(n));
-  __syncthreads();
+  plan_cost_kinematics<TG>(rb, m, ng, tid, [&](int kq, int dq) { return s_bad[kq] ? 0.0 : plans[((size_t)i * ndof + dq) * T + t0 + kq]; });
   if (base_pp) b0 = base_pp[3 * (size_t)i], b1 = base_pp[3 * (size_t)i + 1], b2 = base_pp[3 * (size_t)i + 2];
   const bool base_ok = isfinite(b0) && isfinite(b1) && isfinite(b2);
   int cnt[TG];
@@ -144,7 +142,6 @@ template <bool DEPTH>
 __global__ __launch_bounds__(256) void k_check_posed(const double* __restrict__ points, int P, const double* __restrict__ poses,
                                                      ObsDepthView dv, double* __restrict__ xyz_out,
                                                      int32_t* __restrict__ count_out) {
-#pragma clang fp contract(off)  // numpy's products and sums, one rounding each
   __shared__ int s_cnt[4];
   const int i = blockIdx.x, tid = threadIdx.x;
   const double* M = poses + 16 * (size_t)i;
@@ -161,11 +158,8 @@ __global__ __launch_bounds__(256) void k_check_posed(const double* __restrict__ 
     const bool live = p < P;
     const double x0 = live ? points[3 * (size_t)p] : 0.0, x1 = live ? points[3 * (size_t)p + 1] : 0.0,
                  x2 = live ? points[3 * (size_t)p + 2] : 0.0;
-    // numpy.einsum("nij,pj->npi") adds the three products of a row in the order x, z, y (numpy 2.2's unrolled inner loop):
-    // utils.grasp_collision_ratio's bits, which tests/test_gpu_observation.py compares with
-    const double X0 = ((M[0] * x0 + M[2] * x2) + M[1] * x1) + M[3];
-    const double X1 = ((M[4] * x0 + M[6] * x2) + M[5] * x1) + M[7];
-    const double X2 = ((M[8] * x0 + M[10] * x2) + M[9] * x1) + M[11];
+    double X0, X1, X2;
+    place_einsum(M, x0, x1, x2, &X0, &X1, &X2);
     if constexpr (DEPTH) {
       const bool in = live && !depth_is_outside(X0, X1, X2, dv.depth, dv.H, dv.W, dv.K, dv.cam_inv);
       cnt += __popcll(__ballot(in));
@@ -175,9 +169,8 @@ __global__ __launch_bounds__(256) void k_check_posed(const double* __restrict__ 
     }
   }
   if constexpr (DEPTH) {
-    if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
-    __syncthreads();
-    if (tid == 0) count_out[i] = ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3];
+    const int total = wave_counts_sum(cnt, tid, s_cnt);
+    if (tid == 0) count_out[i] = total;
   } else {
     if (tid == 0 && !bad) count_out[i] = 0;
   }
@@ -193,9 +186,8 @@ __global__ __launch_bounds__(256) void k_count_flags(const uint8_t* __restrict__
     const int p = p0 + tid;
     cnt += __popcll(__ballot(p < P && flags[(size_t)i * P + p] != 0));
   }
-  if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
-  __syncthreads();
-  if (tid == 0) count[i] = ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3];
+  const int total = wave_counts_sum(cnt, tid, s_cnt);
+  if (tid == 0) count[i] = total;
 }
 
 // ---- the grasp filter on the stream (gto_filter_grasps_device) ----
@@ -279,7 +271,6 @@ __global__ __launch_bounds__(256) void k_filter_depth(const FilterDepthItem* __r
                                                       const double* __restrict__ world_to_base, const double* __restrict__ base_pos,
                                                       PoseArg check_off, PoseArg ik_off, int has_ik_off, double* __restrict__ ws_plan,
                                                       double* __restrict__ ws_ik, int32_t* __restrict__ ws_count) {
-#pragma clang fp contract(off)  // the placement is k_check_posed's, term for term
   __shared__ int s_cnt[4];
   const int i = blockIdx.x, tid = threadIdx.x;
   const int b = items[blockIdx.y].obj;
@@ -302,15 +293,13 @@ __global__ __launch_bounds__(256) void k_filter_depth(const FilterDepthItem* __r
     const bool live = p < P;
     const double x0 = live ? points[3 * (size_t)p] : 0.0, x1 = live ? points[3 * (size_t)p + 1] : 0.0,
                  x2 = live ? points[3 * (size_t)p + 2] : 0.0;
-    const double X0 = ((M[0] * x0 + M[2] * x2) + M[1] * x1) + M[3];
-    const double X1 = ((M[4] * x0 + M[6] * x2) + M[5] * x1) + M[7];
-    const double X2 = ((M[8] * x0 + M[10] * x2) + M[9] * x1) + M[11];
+    double X0, X1, X2;
+    place_einsum(M, x0, x1, x2, &X0, &X1, &X2);
     const bool in = live && !depth_is_outside(X0, X1, X2, dv.depth, dv.H, dv.W, dv.K, dv.cam_inv);
     cnt += __popcll(__ballot(in));
   }
-  if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
-  __syncthreads();
-  if (tid == 0) ws_count[row] = ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3];
+  const int total = wave_counts_sum(cnt, tid, s_cnt);
+  if (tid == 0) ws_count[row] = total;
 }
 
 // grid (ceil(n_max / 64), objects of the run), objects b0 .. b0 + gridDim.y - 1 (a run of one cloud observation): one lane

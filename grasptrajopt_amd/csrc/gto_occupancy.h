@@ -132,8 +132,9 @@ __global__ __launch_bounds__(256) void k_base_report(const RobotDev* __restrict_
   const int row = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int F = rb->n_frames, ndof = rb->ndof, P = rb->n_points;
   extern __shared__ __attribute__((aligned(16))) double smem_br[];
-  // plan_cost_lds<1>'s layout, laid out here: that helper stays k_ik_report's alone, whose code (its register counts in
-  // kernel_resources.txt are pinned) the compiler arranges differently once the helper has a second caller
+  // plan_cost_lds<1>'s layout, laid out here and not through the helper: the compiler arranges k_ik_report's code (its
+  // register counts are in kernel_resources.txt) differently with every further caller of plan_cost_lds<1>; k_held_attach
+  // is one (one scalar register of k_ik_report's: DESIGN.md 7g)
   PlanCostLds m;
   m.tab = smem_br;
   m.sc = m.tab + fk_tab_doubles(F, rb->n_links, rb->n_opt);

@@ -319,7 +319,7 @@ __global__ __launch_bounds__(256) void k_plan_report(const RobotDev* __restrict_
   }
   if (!err_pos_out && !err_rot_out) return;  // (uniform)
   extern __shared__ __attribute__((aligned(16))) double smem_pr[];
-  // plan_cost_lds<1>'s layout, laid out here as in k_base_report: that helper stays k_ik_report's alone
+  // plan_cost_lds<1>'s layout, laid out here as in k_base_report (see there)
   PlanCostLds m;
   m.tab = smem_pr;
   m.sc = m.tab + fk_tab_doubles(F, rb->n_links, rb->n_opt);

@@ -208,6 +208,31 @@ def test_cloud_runs_around_a_depth_object_equal_check_posed(handle, image_obs):
     ob.close()
 
 
+def test_a_cloud_run_takes_a_second_launch_chain(handle):
+    """One object on a cloud observation with the instance of test_check_posed_takes_a_second_launch_chain: 4096 gripper points
+    at 4097 poses are 2^24 + 4096 queries, so the run's poses 0..4095 go into the first launch chain (kCheckChunkQueries =
+    2^24, gto_api.hip) and pose 4096 alone into a second.  Identity object pose and check_offset: the check pose is the grasp."""
+    from grasptrajopt_amd.observation import Observation
+    s = cc.CHUNK_POSED
+    assert cc.CHUNK_QUERIES == 1 << 24 and cc.CHUNK_QUERIES // s.P == s.n - 1
+    points, normals, pts, poses, _ = cc.chunk_posed_instance()
+    inp = gf.SimpleNamespace(points=pts, object_pose=np.eye(4)[None], grasps=poses[None], n_grasps=np.array([s.n], np.int32),
+                             world_to_base=None, base_pos=None, check_offset=np.eye(4), ik_offset=None, max_ratio=0.25)
+    obs = Observation.from_cloud(points, normals, s.k)
+    got = run_filter(handle, inp, [obs])
+    C, A, ik, bad = gf.compose(inp, 0)
+    posed = np.where(bad, -1, obs.check_posed(pts, C))
+    obs.close()
+    assert bad[2::6].all() and not np.delete(bad, np.arange(2, s.n, 6)).any()
+    assert np.array_equal(got["counts"][0], posed) and 0 < posed[4096] < s.P
+    keep = (posed >= 0) & (posed / np.float64(s.P) <= inp.max_ratio)
+    rows = np.flatnonzero(keep)
+    assert 0 < len(rows) < (~bad).sum()  # some finite rows are kept and some are not
+    assert np.array_equal(got["keep"][0].astype(bool), keep) and got["n_kept"][0] == len(rows) == got["n_grasps"][0]
+    assert np.array_equal(got["kept_rows"][0, :len(rows)], rows) and (got["kept_rows"][0, len(rows):] == -1).all()
+    assert gf.same_numbers(got["plan_goals"][0, :len(rows)], A[rows]) and gf.same_numbers(got["ik_goals"][0, :len(rows)], ik[rows])
+
+
 # ---------------------------------------------------------------------------------------------- 6. validation
 def test_the_entry_point_validates_on_the_host(capi, handle, image_obs):
     import ctypes as C
