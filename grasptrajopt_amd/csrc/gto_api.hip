@@ -30,6 +30,7 @@
 #include "gto_retrieve.h"
 #include "gto_occupancy.h"
 #include "gto_owned.h"
+#include "gto_robot.h"
 
 #define GTO_VERSION GTO_ABI_VERSION  // include/gto_solver.h
 #ifndef GTO_OBS_DEEP_PD
@@ -379,397 +380,15 @@ static ObsKernel obstacle_kernel(int np, bool deep, bool sweep, bool hot) {
   return hot ? warm[i] : cold[i];
 }
 
-// Rounds of pointer jumping that FK needs over a tree listed parents first: a frame at depth d is the product of d + 1
-// local transforms, and r rounds compose 2^r of them.
-static int fk_rounds(const int* parent, int n) {
-  int depth[GTO_MAX_FRAMES], maxd = 1, r = 0;
-  for (int i = 0; i < n; ++i) {
-    depth[i] = parent[i] < 0 ? 0 : depth[parent[i]] + 1;
-    maxd = std::max(maxd, depth[i]);
-  }
-  while ((1 << r) < maxd + 1) ++r;
-  return r;
-}
-
-// Everything gto_create uploads for a robot, built on the host from the descriptor alone.
-struct RobotTables {
-  RobotDev rb;
-  std::vector<double> px, py, pz;  // surface points sorted by link, and inside a link along a Morton curve
-  std::vector<int32_t> plink, perm;  // their links, and the descriptor's index of each
-  std::vector<Chunk> chunks;  // runs of <= 64 points of one link
-  std::vector<PbChunk> pbchunks;  // the step kernel's spheres (one dummy entry if no link moves)
-  int pb_C = 0;  // spheres in pbchunks
-};
-
-// Validates the descriptor and builds its tables; no HIP call.  GTO_OK, or an error code with its message in `why`.
-static int build_robot(const gto_robot_desc* d, int pb_merge, RobotTables& t, std::string& why) {
-  auto bad = [&](int code, const char* msg) {
-    why = msg;
-    return code;
-  };
-  RobotDev& rb = t.rb;
-  memset(&rb, 0, sizeof rb);
-  rb.n_frames = d->n_frames;
-  rb.ndof = d->ndof;
-  rb.n_opt = d->n_opt;
-  rb.n_links = d->n_links;
-  rb.n_points = d->n_points;
-  rb.n_gripper_points = d->n_gripper_points;
-  rb.frame_ee = d->frame_ee;
-  rb.frame_gripper = d->frame_gripper;
-  for (int i = 0; i < GTO_MAX_DOF; ++i) rb.opt_of_dof[i] = -1;
-  for (int j = 0; j < d->n_opt; ++j) {
-    if (d->opt_index[j] < 0 || d->opt_index[j] >= d->ndof) return bad(GTO_ERR_INVALID_ARG, "opt_index out of range");
-    if (rb.opt_of_dof[d->opt_index[j]] >= 0) return bad(GTO_ERR_INVALID_ARG, "opt_index names a joint twice");
-    rb.opt_index[j] = d->opt_index[j];
-    rb.opt_of_dof[d->opt_index[j]] = j;
-    rb.lower[j] = d->lower[j];
-    rb.upper[j] = d->upper[j];
-    if (!(d->lower[j] <= d->upper[j])) return bad(GTO_ERR_INVALID_ARG, "lower > upper");
-  }
-  for (int i = 0; i < d->n_frames; ++i) {
-    int p = d->parent[i];
-    if (p >= i || p < -1) return bad(GTO_ERR_INVALID_ARG, "frames must list parents before children");
-    int jt = d->joint_type[i];
-    if (jt != GTO_JOINT_FIXED && jt != GTO_JOINT_REVOLUTE && jt != GTO_JOINT_PRISMATIC) return bad(GTO_ERR_UNSUPPORTED, "joint type not supported (optas/models.py:865-866)");
-    if (jt != GTO_JOINT_FIXED && (d->q_index[i] < 0 || d->q_index[i] >= d->ndof)) return bad(GTO_ERR_INVALID_ARG, "q_index out of range for an actuated joint");
-    rb.parent[i] = p;
-    rb.joint_type[i] = jt;
-    rb.q_index[i] = (jt == GTO_JOINT_FIXED) ? -1 : d->q_index[i];
-    double R[9];
-    rpy2r(d->origin_rpy + 3 * i, R);
-    rt2aff(R, d->origin_xyz + 3 * i, rb.origin[i]);
-    const double* ax = d->axis + 3 * i;
-    double nrm = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-    if (jt != GTO_JOINT_FIXED && !(nrm > 0)) return bad(GTO_ERR_INVALID_ARG, "zero joint axis");
-    for (int k = 0; k < 3; ++k) rb.axis_unit[i][k] = (nrm > 0) ? ax[k] / nrm : 0.0;
-    rb.opt_of_frame[i] = -1;
-    uint32_t anc = (p >= 0) ? rb.frame_anc[p] : 0u;
-    if (rb.q_index[i] >= 0)
-      for (int j = 0; j < d->n_opt; ++j)
-        if (d->opt_index[j] == rb.q_index[i]) {
-          rb.opt_of_frame[i] = j;
-          anc |= 1u << j;
-        }
-    rb.frame_anc[i] = anc;
-  }
-  rb.fk_rounds = fk_rounds(rb.parent, d->n_frames);
-  for (int l = 0; l < d->n_links; ++l) {
-    int f = d->link_frame[l];
-    if (f < 0 || f >= d->n_frames) return bad(GTO_ERR_INVALID_ARG, "link_frame out of range");
-    rb.link_frame[l] = f;
-    rb.link_anc[l] = rb.frame_anc[f];
-    double R[9];
-    rpy2r(d->visual_rpy + 3 * l, R);
-    rt2aff(R, d->visual_xyz + 3 * l, rb.vis_origin[l]);
-  }
-  for (int v = 0; v < 2; ++v) {
-    const int NPv = v ? 16 : 8;
-    for (int e = 0; e < NPv * NPv + NPv; ++e) {
-      const int i = e < NPv * NPv ? e / NPv : e - NPv * NPv, j = e < NPv * NPv ? e % NPv : i;
-      uint32_t m = 0u;
-      if (i < d->n_opt && j < d->n_opt)
-        for (int l = 0; l < d->n_links; ++l) m |= (((rb.link_anc[l] >> i) & (rb.link_anc[l] >> j) & 1u) << l);
-      rb.entry_links[v][e] = m;
-    }
-  }
-  for (int i = 0; i < d->n_frames; ++i) rb.link_of_frame[i] = -1, rb.xst_slot[i] = -1;
-  for (int l = 0; l < d->n_links; ++l) {
-    if (rb.link_of_frame[rb.link_frame[l]] >= 0) return bad(GTO_ERR_INVALID_ARG, "two collision links on one frame");
-    rb.link_of_frame[rb.link_frame[l]] = l;
-  }
-  rb.n_xst = 0;
-  rb.frame_free_mask = 0u;
-  for (int i = 0; i < d->n_frames; ++i)
-    if (rb.opt_of_frame[i] < 0) rb.frame_free_mask |= 1u << i;
-  for (int i = 0; i < d->n_frames; ++i) {
-    const int p = rb.parent[i];
-    if (p >= 0 && p != i - 1 && rb.xst_slot[p] < 0) rb.xst_slot[p] = rb.n_xst++;
-  }
-  {  // the step kernel's walk over the tree (prebroad_tail): control words, and the widening of its culling radius
-    for (int i = 0; i < d->n_frames; ++i) {
-      const int p = rb.parent[i], l = rb.link_of_frame[i];
-      const int src = p < 0 ? 0 : (p == i - 1 ? 1 : 2 + rb.xst_slot[p]);
-      const bool moving_link = l >= 0 && (rb.frame_anc[rb.link_frame[l]] != 0u);
-      rb.pb_ctl[i] = (src & 7) | (((rb.xst_slot[i] + 1) & 7) << 4) | ((moving_link ? 1 : 0) << 8);
-      rb.pb_par[i] = -1;
-      if (rb.joint_type[i] != GTO_JOINT_FIXED && rb.opt_of_frame[i] < 0) rb.pb_par[i] = rb.pb_npar, rb.pb_parf[rb.pb_npar++] = i;
-    }
-    for (int i = 0; i < d->n_frames; ++i) {  // the frame table the tail copies into its LDS as it is
-      for (int e = 0; e < 12; ++e) rb.pb_ft[i][e] = (float)rb.origin[i][e];
-      for (int e = 0; e < 3; ++e) rb.pb_ft[i][12 + e] = (float)rb.axis_unit[i][e];
-      const int32_t w = rb.joint_type[i] | ((rb.opt_of_frame[i] + 1) << 4) | ((rb.pb_par[i] + 1) << 9);
-      std::memcpy(&rb.pb_ft[i][15], &w, sizeof w);
-    }
-    double D = 0.0, maxp = 0.0;  // no frame origin or surface point is further than D from any other
-    for (int i = 0; i < d->n_frames; ++i) {
-      const double* ox = d->origin_xyz + 3 * i;
-      D += std::sqrt(ox[0] * ox[0] + ox[1] * ox[1] + ox[2] * ox[2]);
-      if (rb.joint_type[i] == GTO_JOINT_PRISMATIC) {
-        const int j = rb.opt_of_frame[i];
-        D += j >= 0 ? std::max(std::fabs(rb.lower[j]), std::fabs(rb.upper[j])) : 2.0;
-      }
-    }
-    for (int l = 0; l < d->n_links; ++l) {
-      const double* vx = d->visual_xyz + 3 * l;
-      maxp = std::max(maxp, std::sqrt(vx[0] * vx[0] + vx[1] * vx[1] + vx[2] * vx[2]));
-    }
-    double maxr = 0.0;
-    for (int i = 0; i < d->n_points; ++i) {
-      const double* pp = d->points + 3 * i;
-      maxr = std::max(maxr, std::sqrt(pp[0] * pp[0] + pp[1] * pp[1] + pp[2] * pp[2]));
-    }
-    D += maxp + maxr;
-    rb.pb_eps = 128.0 * d->n_frames * 5.9604644775390625e-08 * D;  // four times the first-order bound 32 F 2^-24 D (gto_kernels.h, PbLayout)
-  }
-  {  // operand tables of fk_mfma_tree: the full tree, and the compact tree of the obstacle kernel (gto_device.h)
-    const int F = d->n_frames, L = d->n_links, n = d->n_opt;
-    auto hom = [](const double* aff, int a, int c) { return a < 3 ? aff[4 * a + c] : (c == 3 ? 1.0 : 0.0); };
-    // one table: nf frames (origin affine, unit axis, joint type, parent, optimised-joint slot), the links' frames and
-    // visual origins, the optimised joints' frames
-    auto build = [&](double* T0, int nf, const double (*org)[12], const double (*axu)[3], const int* jtype, const int* par,
-                     const int* optj, const int* lframe, const double (*vorg)[12], int* opt_frame_out) {
-      std::memset(T0, 0, sizeof rb.fk_tab);
-      for (int i = 0; i < nf; ++i) {
-        const double* u = axu[i];
-        const double K[3][3] = {{0, -u[2], u[1]}, {u[2], 0, -u[0]}, {-u[1], u[0], 0}};
-        double* tab = T0 + GTO_FK_STRIDE * i;
-        for (int a = 0; a < 4; ++a)
-          for (int c = 0; c < 4; ++c) {
-            const int e = (4 * a + c) ^ (5 * (i & 3));  // bank placement of the frame's entries (gto_device.h, fkx)
-            const double uu = (a < 3 && c < 3) ? u[a] * u[c] : 0.0;
-            const double dl = (a == c && a < 3) ? 1.0 : 0.0, hh = (a == 3 && c == 3) ? 1.0 : 0.0;
-            tab[e] = hom(org[i], c, a);  // transposed: a row-pattern read gives the B operand O^T (gto_device.h, fkx)
-            tab[16 + e] = hh + uu;  // M = c0 + cos c1 + sin K
-            tab[32 + e] = dl - uu;
-            if (jtype[i] == GTO_JOINT_PRISMATIC) tab[48 + e] = (a < 3 && c == 3) ? u[a] : 0.0;
-            else tab[48 + e] = (a < 3 && c < 3) ? K[a][c] : 0.0;
-          }
-        if (optj[i] >= 0) {
-          const int j = optj[i];
-          opt_frame_out[j] = i;
-          double* tu = T0 + GTO_FK_STRIDE * nf + 16 * L;
-          for (int a = 0; a < 3; ++a) tu[fkx(j, 4 * a)] = u[a];
-          tu[fkx(j, 4 * 3 + 1)] = 1.0;
-        }
-      }
-      for (int l = 0; l < L; ++l)
-        for (int a = 0; a < 4; ++a)
-          for (int c = 0; c < 4; ++c) T0[GTO_FK_STRIDE * nf + fkx(l, 4 * a + c)] = hom(vorg[l], a, c);
-      double* tI = T0 + GTO_FK_STRIDE * nf + 16 * L + 16 * n;
-      for (int l = 0; l < L; ++l) tI[l] = lframe[l];
-      for (int j = 0; j < n; ++j) {
-        tI[L + j] = opt_frame_out[j];
-        tI[L + n + j] = jtype[opt_frame_out[j]] == GTO_JOINT_PRISMATIC ? 1.0 : 0.0;
-      }
-      for (int i = 0; i < nf; ++i) tI[L + 2 * n + i] = par[i];
-    };
-    build(rb.fk_tab, F, rb.origin, rb.axis_unit, rb.joint_type, rb.parent, rb.opt_of_frame, rb.link_frame, rb.vis_origin, rb.opt_frame);
-    // the compact tree
-    static_assert(sizeof rb.fk_tab == sizeof rb.fk_tab_c, "one layout for both tables");
-    int cf[GTO_MAX_FRAMES], nc = 0;
-    double corg[GTO_MAX_FRAMES][12], caxu[GTO_MAX_FRAMES][3], cvis[GTO_MAX_LINKS][12];
-    int cpar[GTO_MAX_FRAMES], coptj[GTO_MAX_FRAMES], clf[GTO_MAX_LINKS], copt_frame[GTO_MAX_OPT];
-    for (int f = 0; f < F; ++f) cf[f] = rb.joint_type[f] != GTO_JOINT_FIXED ? nc++ : -1;
-    for (int f = 0; f < F; ++f) {
-      if (cf[f] < 0) continue;
-      const int k = cf[f];
-      double A[12];
-      std::memcpy(A, rb.origin[f], sizeof A);
-      int p = rb.parent[f];
-      for (; p >= 0 && rb.joint_type[p] == GTO_JOINT_FIXED; p = rb.parent[p]) aff_mul(rb.origin[p], A, A);
-      std::memcpy(corg[k], A, sizeof A);
-      std::memcpy(caxu[k], rb.axis_unit[f], sizeof caxu[k]);
-      cpar[k] = p >= 0 ? cf[p] : -1;
-      coptj[k] = rb.opt_of_frame[f];
-      rb.cf_orig[k] = f;
-      rb.cf_type[k] = rb.joint_type[f];
-    }
-    bool need_world = false;
-    for (int l = 0; l < L; ++l) {
-      double V[12];
-      std::memcpy(V, rb.vis_origin[l], sizeof V);
-      int g = rb.link_frame[l];
-      for (; g >= 0 && rb.joint_type[g] == GTO_JOINT_FIXED; g = rb.parent[g]) aff_mul(rb.origin[g], V, V);
-      std::memcpy(cvis[l], V, sizeof V);
-      clf[l] = g >= 0 ? cf[g] : -2;
-      need_world = need_world || g < 0;
-    }
-    if (need_world || nc == 0) {  // links that hang on fixed frames only: a frame that is the world
-      const int k = nc++;
-      const double I12[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-      std::memcpy(corg[k], I12, sizeof I12);
-      caxu[k][0] = caxu[k][1] = caxu[k][2] = 0.0;
-      cpar[k] = -1, coptj[k] = -1;
-      rb.cf_orig[k] = -1;
-      rb.cf_type[k] = GTO_JOINT_FIXED;
-      for (int l = 0; l < L; ++l)
-        if (clf[l] == -2) clf[l] = k;
-    }
-    build(rb.fk_tab_c, nc, corg, caxu, rb.cf_type, cpar, coptj, clf, cvis, copt_frame);
-    rb.n_cframes = nc;
-    rb.fk_rounds_c = fk_rounds(cpar, nc);
-  }
-  for (int i = 0; i < d->n_points; ++i)  // (before anything is indexed by it)
-    if (d->point_link[i] < 0 || d->point_link[i] >= d->n_links) return bad(GTO_ERR_INVALID_ARG, "point_link out of range");
-  // moments of the gripper point cloud
-  rb.grip_count = (double)d->n_gripper_points;
-  for (int k = 0; k < d->n_gripper_points; ++k) {
-    const double* p = d->gripper_points + 3 * k;
-    for (int r = 0; r < 3; ++r) {
-      rb.grip_mu[r] += p[r];
-      for (int c = 0; c < 3; ++c) rb.grip_M[3 * r + c] += p[r] * p[c];
-    }
-  }
-  // reach[j]: conservative bound on the displacement of any surface point per unit motion of joint j:
-  // sum of the origin offsets along the chain below the joint (+ travel of prismatic joints below it)
-  // + visual-origin offset + farthest surface point of the link, maximised over the links it moves.
-  {
-    std::vector<double> maxpt(d->n_links, 0.0);
-    for (int i = 0; i < d->n_points; ++i) {
-      const double* p = d->points + 3 * i;
-      maxpt[d->point_link[i]] = std::max(maxpt[d->point_link[i]], std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]));
-    }
-    for (int j = 0; j < d->n_opt; ++j) rb.reach[j] = 0.0;
-    for (int l = 0; l < GTO_MAX_LINKS; ++l)
-      for (int j = 0; j < GTO_MAX_OPT; ++j) rb.reach_link[l][j] = 0.0;
-    bool ok = true;
-    for (int l = 0; l < d->n_links; ++l) {
-      const double* vx = d->visual_xyz + 3 * l;
-      double below = std::sqrt(vx[0] * vx[0] + vx[1] * vx[1] + vx[2] * vx[2]) + maxpt[l];  // offsets below the current frame
-      for (int f = d->link_frame[l]; f >= 0; f = d->parent[f]) {
-        const int j = rb.opt_of_frame[f];
-        if (j >= 0) rb.reach[j] = std::max(rb.reach[j], rb.joint_type[f] == GTO_JOINT_PRISMATIC ? 1.0 : below);
-        if (j >= 0) rb.reach_link[l][j] = rb.joint_type[f] == GTO_JOINT_PRISMATIC ? 1.0 : below;
-        if (rb.joint_type[f] == GTO_JOINT_PRISMATIC) {
-          // travel of this joint moves everything below it further from the joints above
-          double travel = 1e9;
-          if (j >= 0) travel = std::max(std::fabs(rb.lower[j]), std::fabs(rb.upper[j]));
-          else travel = 2.0;  // parameter prismatic joints (torso lift, fingers): generous constant
-          if (!(travel < 1e3)) ok = false;
-          below += travel;
-        }
-        const double* ox = d->origin_xyz + 3 * f;
-        below += std::sqrt(ox[0] * ox[0] + ox[1] * ox[1] + ox[2] * ox[2]);
-      }
-    }
-    if (!ok) for (int j = 0; j < d->n_opt; ++j) rb.reach[j] = -1.0;
-    if (!ok)
-      for (int l = 0; l < GTO_MAX_LINKS; ++l)
-        for (int j = 0; j < GTO_MAX_OPT; ++j) rb.reach_link[l][j] = -1.0;
-  }
-  // points sorted by link (stable), chunk table of <= 64 link-uniform points
-  const int P = d->n_points;
-  std::vector<int32_t> perm(P);
-  for (int i = 0; i < P; ++i) perm[i] = i;
-  // sort by link, and inside a link along a Morton (Z-order) curve of the link-local coordinates, so
-  // that the 64 lanes of a chunk (and consecutive chunks) gather from neighbouring voxels/cache lines
-  std::vector<uint32_t> morton(P, 0);
-  {
-    std::vector<double> lo(3 * d->n_links, 1e300), hi(3 * d->n_links, -1e300);
-    for (int i = 0; i < P; ++i)
-      for (int a = 0; a < 3; ++a) {
-        lo[3 * d->point_link[i] + a] = std::min(lo[3 * d->point_link[i] + a], d->points[3 * i + a]);
-        hi[3 * d->point_link[i] + a] = std::max(hi[3 * d->point_link[i] + a], d->points[3 * i + a]);
-      }
-    auto spread = [](uint32_t v) {  // 10 bits -> every third bit
-      v &= 0x3ff;
-      v = (v | (v << 16)) & 0x30000ff;
-      v = (v | (v << 8)) & 0x300f00f;
-      v = (v | (v << 4)) & 0x30c30c3;
-      v = (v | (v << 2)) & 0x9249249;
-      return v;
-    };
-    for (int i = 0; i < P; ++i) {
-      const int l = d->point_link[i];
-      double ext = 1e-12;
-      for (int a = 0; a < 3; ++a) ext = std::max(ext, hi[3 * l + a] - lo[3 * l + a]);
-      uint32_t code = 0;
-      for (int a = 0; a < 3; ++a) {
-        double u = (d->points[3 * i + a] - lo[3 * l + a]) / ext;  // isotropic cells
-        uint32_t q = (uint32_t)std::min(1023.0, std::max(0.0, u * 1023.0));
-        code |= spread(q) << a;
-      }
-      morton[i] = code;
-    }
-  }
-  std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) {
-    if (d->point_link[a] != d->point_link[b]) return d->point_link[a] < d->point_link[b];
-    return morton[a] < morton[b];
-  });
-  std::vector<double> px(P), py(P), pz(P);
-  std::vector<int32_t> plink(P);
-  for (int i = 0; i < P; ++i) {
-    px[i] = d->points[3 * perm[i]];
-    py[i] = d->points[3 * perm[i] + 1];
-    pz[i] = d->points[3 * perm[i] + 2];
-    plink[i] = d->point_link[perm[i]];
-  }
-  std::vector<Chunk> chunks;
-  for (int i = 0; i < P;) {
-    int l = plink[i], j = i;
-    while (j < P && plink[j] == l && j - i < GTO_WAVE) ++j;
-    // bounding sphere: centre = mean of the chunk's points, radius = farthest point (+ a hair)
-    double cx = 0, cy = 0, cz = 0;
-    for (int k = i; k < j; ++k) { cx += px[k]; cy += py[k]; cz += pz[k]; }
-    cx /= (j - i); cy /= (j - i); cz /= (j - i);
-    double r2 = 0;
-    for (int k = i; k < j; ++k) {
-      double dx = px[k] - cx, dy = py[k] - cy, dz = pz[k] - cz;
-      r2 = std::max(r2, dx * dx + dy * dy + dz * dz);
-    }
-    chunks.push_back(Chunk{l, i, j - i, rb.link_anc[l] == 0u ? 1 : 0, cx, cy, cz, std::sqrt(r2) * (1.0 + 1e-9) + 1e-12});
-    i = j;
-  }
-  rb.n_chunks = (int)chunks.size();
-  std::vector<PbChunk> pbchunks;
-  // The step kernel's spheres: runs of pb_merge consecutive chunks of a moving link under one sphere (the chunks follow a
-  // Morton curve, so a run is a compact patch; centre = mean of its points, radius = the farthest of them).  Coarser than
-  // the obstacle kernel's own test, which stays per chunk and exact: a sphere more lists a group more, never one less.
-  // Centre in the coordinates of the link's FRAME (visual origin applied here, in double: the tail's walk stops at the frames).
-  for (size_t ci = 0; ci < chunks.size();) {
-    const Chunk& c = chunks[ci];
-    if (c.pad) { ++ci; continue; }
-    size_t cj = ci;
-    int i0 = c.start, i1 = c.start;
-    while (cj < chunks.size() && cj - ci < (size_t)pb_merge && !chunks[cj].pad && chunks[cj].link == c.link) i1 = chunks[cj].start + chunks[cj].count, ++cj;
-    double cx = 0, cy = 0, cz = 0, r2 = 0;
-    for (int k = i0; k < i1; ++k) cx += px[k], cy += py[k], cz += pz[k];
-    cx /= (i1 - i0), cy /= (i1 - i0), cz /= (i1 - i0);
-    for (int k = i0; k < i1; ++k) r2 = std::max(r2, (px[k] - cx) * (px[k] - cx) + (py[k] - cy) * (py[k] - cy) + (pz[k] - cz) * (pz[k] - cz));
-    const double* V = rb.vis_origin[c.link];
-    pbchunks.push_back(PbChunk{V[0] * cx + V[1] * cy + V[2] * cz + V[3], V[4] * cx + V[5] * cy + V[6] * cz + V[7], V[8] * cx + V[9] * cy + V[10] * cz + V[11],
-                               std::sqrt(r2) * (1.0 + 1e-9) + 1e-12, rb.link_frame[c.link], 0});
-    ci = cj;
-  }
-  t.pb_C = (int)pbchunks.size();
-  if (pbchunks.empty()) pbchunks.push_back(PbChunk{0, 0, 0, 0, 0, 0});  // (a robot none of whose links moves: the table is never read)
-  if (rb.n_chunks > GTO_MAX_ACTIVE) return bad(GTO_ERR_UNSUPPORTED, "too many surface points (max 16384, in at most 256 runs of up to 64 points of one link)");
-  t.perm = std::move(perm);
-  t.px = std::move(px), t.py = std::move(py), t.pz = std::move(pz);
-  t.plink = std::move(plink);
-  t.chunks = std::move(chunks);
-  t.pbchunks = std::move(pbchunks);
-  return GTO_OK;
-}
-
 int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device, gto_handle** out) {
   if (!d || !opts || !out) return fail(nullptr, GTO_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
   std::string why;
   if (!validate_opts(opts, why)) return fail(nullptr, GTO_ERR_INVALID_ARG, why);
-  if (d->n_frames < 1 || d->n_frames > GTO_MAX_FRAMES) return fail(nullptr, GTO_ERR_UNSUPPORTED, "n_frames out of range (max 32)");
-  if (d->n_links < 1 || d->n_links > GTO_MAX_LINKS) return fail(nullptr, GTO_ERR_UNSUPPORTED, "n_links out of range (max 32)");
-  if (d->n_opt < 1 || d->n_opt > GTO_MAX_OPT) return fail(nullptr, GTO_ERR_UNSUPPORTED, "n_opt out of range (max 16)");
-  if (d->ndof < d->n_opt || d->ndof > GTO_MAX_DOF) return fail(nullptr, GTO_ERR_UNSUPPORTED, "ndof out of range (max 32)");
-  if (d->n_points < 1) return fail(nullptr, GTO_ERR_INVALID_ARG, "robot has no surface points");
-  if (d->n_gripper_points < 1) return fail(nullptr, GTO_ERR_INVALID_ARG, "robot has no gripper points");
-  if (d->frame_ee < 0 || d->frame_ee >= d->n_frames || d->frame_gripper < 0 || d->frame_gripper >= d->n_frames)
-    return fail(nullptr, GTO_ERR_INVALID_ARG, "frame_ee / frame_gripper out of range");
   Tunables tu;
   read_tunables(tu);
   std::unique_ptr<RobotTables> t(new RobotTables());
-  if (int rc = build_robot(d, tu.pb_merge, *t, why)) return fail(nullptr, rc, why);
+  if (int rc = build_robot(d, tu.pb_merge, *t, why)) return fail(nullptr, rc, why);  // (gto_robot.h: descriptor checks, then the tables)
   const RobotDev& rb = t->rb;
   const int np = rb.n_opt <= GTO_NB ? GTO_NB : 16;
   const size_t lm_lds = np == GTO_NB ? lm_lds_bytes(opts->T, 1) : lm_wide_lds_bytes(opts->T, 16);

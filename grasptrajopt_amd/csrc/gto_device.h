@@ -46,7 +46,7 @@ struct RobotDev {
   // translation column); then per link its visual origin; then per optimised joint U = [u;0 | e4]
   // ... then link_frame [L], opt_frame [n], prismatic flag [n], parent [F] as doubles (packed for the actual F, L, n)
   double fk_tab[(GTO_FK_STRIDE + 1) * GTO_MAX_FRAMES + 17 * GTO_MAX_LINKS + 18 * GTO_MAX_OPT];
-  // The same table for the COMPACT tree the obstacle kernel walks (gto_api.hip, build_fk_tables): frames with fixed joints
+  // The same table for the COMPACT tree the obstacle kernel walks (gto_robot.h, fold_fixed_frames): frames with fixed joints
   // are folded into the origins of the moving frames below them and into the visual origins of their links (a "world"
   // frame is appended when a link hangs on fixed frames only), so the pointer jumping has fewer frames and fewer levels
   // (Panda: 12 frames / 4 rounds -> 10 / 3).  Link transforms and joint screws are the same up to the order of the
@@ -68,7 +68,8 @@ struct RobotDev {
   int32_t q_index[GTO_MAX_FRAMES];
   int32_t opt_of_frame[GTO_MAX_FRAMES];  // optimised-joint slot driven by this frame's joint, or -1
   int32_t link_of_frame[GTO_MAX_FRAMES]; // collision link attached to this frame, or -1
-  // serial FK walk of k_traj_solve: frames whose transform a later, non-adjacent child needs are parked in LDS
+  // serial FK walk of the step kernel's tail (gto_kernels.h, prebroad_tail): frames whose transform a later, non-adjacent
+  // child needs are parked in one of GTO_PB_PARK register slots
   int32_t xst_slot[GTO_MAX_FRAMES];      // parking slot of this frame's transform, or -1
   int32_t n_xst;
   uint32_t frame_free_mask;  // bit f: frame f is not the frame of an optimised joint (its joint value never changes in a solve)
@@ -88,7 +89,7 @@ struct RobotDev {
   // or 1 for a prismatic joint); < 0 disables temporal culling
   double reach[GTO_MAX_OPT];
   // reach_link[l][j]: the same bound for the points of link l alone (0 if joint j does not move it): what a step dq moves
-  // a bounding sphere of link l by, at most (emptiness certificates, k_certify in gto_kernels.h)
+  // a bounding sphere of link l by, at most (built for emptiness certificates; no kernel reads it at present)
   double reach_link[GTO_MAX_LINKS][GTO_MAX_OPT];
   // moments of the gripper point cloud p_k (gto/gto_planner.py:37): K, mu = sum p, M = sum p p^T
   double grip_count, grip_mu[3], grip_M[9];
@@ -122,6 +123,13 @@ struct SceneDev {
 struct Chunk {
   int32_t link, start, count, pad;
   double cx, cy, cz, r;  // bounding sphere of the chunk's points in the link's visual-mesh frame
+};
+#define GTO_MAX_ACTIVE 256   // chunks per robot (16 K surface points)
+// bounding sphere of a chunk of a MOVING link, centre in the coordinates of the frame that carries the link (the link's visual
+// origin applied on the host), with that frame (gto_robot.h, fill_chunks builds the table)
+struct PbChunk {
+  double cx, cy, cz, r;
+  int32_t frame, pad;
 };
 
 // ---------------------------------------------------------------- 3x4 affine helpers (row-major)
