@@ -341,11 +341,13 @@ class SolverHandle:
         return int(self.opts.T)
 
     def set_opts(self, **kw):
+        new = self.opts.copy()  # a refused call leaves self.opts as the library still has them
         for k, v in kw.items():
-            if not hasattr(self.opts, k):
+            if not hasattr(new, k):
                 raise AttributeError(k)
-            setattr(self.opts, k, v)
-        self._check(self.lib.gto_set_opts(self._h, C.byref(self.opts)), "gto_set_opts")
+            setattr(new, k, v)
+        self._check(self.lib.gto_set_opts(self._h, C.byref(new)), "gto_set_opts")
+        self.opts = new
 
     def set_scene(self, scene_id: int, c_all, c_obs, shape: Sequence[int], origin, res: float, values_only: bool = False):
         """values_only: gto_set_scene_values, the fields without the solver's records and distance fields (such a scene

@@ -329,12 +329,17 @@ const char* gto_last_error(const gto_handle* h) { return h ? h->err.c_str() : g_
 static int validate_opts(const gto_solver_opts* o, std::string& why) {
   if (o->T < 4) { why = "T must be >= 4"; return 0; }
   if (o->T > GTO_MAX_T) { why = "T must be <= 96 (GTO_MAX_T)"; return 0; }
-  if (!(o->Tmax > 0)) { why = "Tmax must be positive"; return 0; }
+  // (NaN fails every comparison: each test is written so that NaN lands in the refusal)
+  if (!(o->Tmax > 0) || !std::isfinite(o->Tmax)) { why = "Tmax must be positive and finite"; return 0; }
+  if (!(o->w_obstacle >= 0) || !std::isfinite(o->w_obstacle)) { why = "w_obstacle must be >= 0 and finite"; return 0; }
+  if (!(o->w_vel >= 0) || !std::isfinite(o->w_vel)) { why = "w_vel must be >= 0 and finite"; return 0; }
+  if (!(o->tol_step >= 0) || !std::isfinite(o->tol_step)) { why = "tol_step must be >= 0 and finite"; return 0; }
+  if (!(o->tol_rel_f >= 0) || !std::isfinite(o->tol_rel_f)) { why = "tol_rel_f must be >= 0 and finite"; return 0; }
   if (o->max_iter < 0) { why = "max_iter must be >= 0"; return 0; }
   int ts = o->T + o->standoff_offset;
   if (ts < 2 || ts > o->T - 1) { why = "standoff waypoint T+standoff_offset must lie in [2, T-1]"; return 0; }
   if (o->grad_mode != GTO_GRAD_CENTRAL_DIFF && o->grad_mode != GTO_GRAD_ZERO) { why = "unknown grad_mode"; return 0; }
-  if (!(o->lambda0 > 0)) { why = "lambda0 must be positive"; return 0; }
+  if (!(o->lambda0 > 0) || !std::isfinite(o->lambda0)) { why = "lambda0 must be positive and finite"; return 0; }
   return 1;
 }
 

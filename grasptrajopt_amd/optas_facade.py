@@ -239,10 +239,19 @@ class CasADiSolver(Solver):
         if "max_iter" in so:
             opts.max_iter = int(so["max_iter"])
         self._goal = goal
+        self._opts = opts  # this solver's own options: the handle below is shared, and keeps whatever was set on it last
         self._handle = prob.robot.solver_handle(goal.link_ee, goal.link_gripper, opts, role="planner")
-        self._handle.set_opts(max_iter=opts.max_iter, w_obstacle=opts.w_obstacle, w_vel=opts.w_vel)
+        self._apply_opts()
         self._name = prob.robot.get_name()
         return self
+
+    def _apply_opts(self) -> None:
+        """Put this solver's options on the shared handle (a host-side struct copy, no launch).  The handle is cached per
+        (role, links, T, standoff_offset): another solver on the same robot model may have left its own weights, dt or
+        iteration cap there, so every solve sets them first."""
+        o = self._opts
+        self._handle.set_opts(Tmax=o.Tmax, w_obstacle=o.w_obstacle, w_vel=o.w_vel, max_iter=o.max_iter, tol_step=o.tol_step,
+                              tol_rel_f=o.tol_rel_f, lambda0=o.lambda0, grad_mode=o.grad_mode)
 
     SCENE_ID = 0
 
@@ -290,6 +299,7 @@ class CasADiSolver(Solver):
         goals = p["tf_goal"].T.reshape(1, n, 16)
         sid = self.ensure_scene()
         S = self._goal.standoff_pose if self._goal.use_standoff else None
+        self._apply_opts()
         Q, dQ, cost, iters, status = self._handle.solve_batch(
             sid, p["qc"].reshape(1, ndof), goals, n, S, p["base_position"].reshape(1, 3), Q0[None])
         self._stats = {"iter_count": int(iters[0]), "success": bool(status[0] == 0),

@@ -145,7 +145,12 @@ void gto_destroy(gto_handle* h);
 const char* gto_last_error(const gto_handle* h); /* h may be NULL: error of the last failed create */
 
 /* Change solver options that do not alter problem dimensions (max_iter, tolerances, weights,
- * lambda0, grad_mode). T must stay the same. */
+ * lambda0, grad_mode, Tmax, standoff_offset). T must stay the same.  The options take effect at the next call; a call
+ * reads them once, when it starts.
+ * Accepted, here and by gto_create: 4 <= T <= GTO_MAX_T; Tmax and lambda0 positive and finite; w_obstacle, w_vel, tol_step
+ * and tol_rel_f finite and >= 0 (a zero weight drops its term, a zero tolerance switches its ending off); max_iter >= 0;
+ * T + standoff_offset in [2, T-1]; a known grad_mode.  Anything else is GTO_ERR_INVALID_ARG with a message that names the
+ * field, and the handle keeps the options it had. */
 int gto_set_opts(gto_handle* h, const gto_solver_opts* opts);
 
 /*
