@@ -42,7 +42,7 @@ static std::string g_create_error;
 #define GTO_SWEEP_WGS 64   // workgroups of the crew behind an itemized obstacle launch laid out over an estimate (launch_obstacle)
 
 #define GTO_MAX_LANES 8  // lanes of one solve call (streams, list sets, progress words)
-#define GTO_BASE_PIN_SLOTS 4  // calls whose small host arrays (n_goals, the filter's view table) may be in flight at once without the host waiting
+#define GTO_BASE_PIN_SLOTS 4  // calls whose small host arrays (n_goals, per-plan bases, the filter's view table) may be in flight at once without the host waiting
 #define GTO_STAGE_SLOTS 8  // host arrays of each direction that one host-pointer entry point stages (Staging)
 #define GTO_NAP_US 50      // the throttle's naps (the host thread of a lane sleep-polls two pinned words); 10-50 us change nothing
 #define GTO_NAP_FEW_US 10  // ... in launches with few instances in flight; 50-200 us change nothing either
@@ -246,7 +246,7 @@ struct gto_handle {
   // base placement with resident arrays (gto_solve_base_batch_device, gto_base_report_device): the device copy of the
   // caller's n_goals, and the per-set counts when the caller asks for the choice alone
   DevBuf bs_ng, bs_coll;
-  PinBuf bs_pin[GTO_BASE_PIN_SLOTS];           // pinned copies of n_goals, one per call in flight (pinned_to_device)
+  PinBuf bs_pin[GTO_BASE_PIN_SLOTS];           // pinned copies of the small host arrays, one per call in flight (pinned_to_device)
   hipEvent_t bs_pin_ev[GTO_BASE_PIN_SLOTS] = {};  // recorded behind the copy that reads slot k
   int bs_pin_next = 0;
   // the grasp filter (gto_filter_grasps_device): the depth objects' views, the uncompacted goals [B][n_max][16], the poses
@@ -294,7 +294,12 @@ static hipError_t pinned_alloc(PinBuf& b, size_t bytes, unsigned flags = hipHost
   return e;
 }
 
-// a buffer of at least `bytes` bytes, device or pinned: grown with 25 % + 256 B to spare, contents not kept
+// a buffer of at least `bytes` bytes, device or pinned: grown with 25 % + 256 B to spare, contents not kept.  It is regrown by
+// free and allocate while earlier calls of the handle may still be queued on its stream with the old pointer in their
+// arguments (bs_ng, ck_base, hd_p, the solver workspace: one buffer per handle).  That is safe because hipFree and
+// hipHostFree wait for the device before they release anything: a call that regrows is a host synchronisation, and a
+// stream-ordered free (hipFreeAsync on another stream) in their place would not be
+// (tests/test_gpu_stream_order.py, the runs of six calls).
 template <class Buf, class Alloc>
 static int ensure_with(gto_handle* h, Buf& b, size_t bytes, Alloc alloc) {
   if (bytes <= b.bytes()) return GTO_OK;
@@ -3199,11 +3204,12 @@ struct CheckBase {
 int stage_check_base(gto_handle* h, const double* base_pos, int32_t per_plan_base, int32_t B, hipStream_t st, CheckBase* out) {
   *out = {per_plan_base ? 0.0 : base_pos[0], per_plan_base ? 0.0 : base_pos[1], per_plan_base ? 0.0 : base_pos[2], nullptr};
   if (!per_plan_base) return GTO_OK;
-  // hipMemcpyAsync from pageable host memory returns once the array has been copied to the runtime's staging memory (the
-  // documented behaviour of the asynchronous copies for pageable memory): the caller's array is free on return, and the
-  // copy is ordered on `st` in front of the kernel.  ck_base is one buffer per handle: see the header on streams.
-  if (int rc = ensure(h, h->ck_base, (size_t)B * 3 * sizeof(double))) return rc;
-  HIPCHK(h, hipMemcpyAsync(h->ck_base.get(), base_pos, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  // Through a pinned slot of the handle (pinned_to_device), as n_goals travels: the caller's array is free on return whatever
+  // memory it lives in, and the copy is ordered on `st` in front of the kernel.  A hipMemcpyAsync straight from the caller's
+  // array was only safe for pageable memory, which the runtime stages before it returns; a page-locked array it reads when
+  // the copy RUNS, after the caller has it back (tests/test_gpu_stream_order.py).  ck_base is one buffer per handle: see the
+  // header on streams.
+  if (int rc = pinned_to_device(h, h->ck_base, base_pos, (size_t)B * 3 * sizeof(double), st)) return rc;
   out->d_base = h->ck_base.as<const double>();
   return GTO_OK;
 }

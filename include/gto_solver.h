@@ -534,7 +534,9 @@ int gto_observation_check_posed(gto_observation* obs, const double* points, int3
  * to its xyz_out.  count_out [B][T]: how many of the handle's P surface points are inside at waypoint t of plan b (the
  * evaluator calls a plan colliding when some waypoint has more than 5); -1 for a waypoint (or a base) with a non-finite
  * entry, which changes no other count.  base_pos: HOST array in both variants, [3] (per_plan_base == 0) or [B][3]; zeros
- * reproduce the evaluator's is_mobile branch.  `obs` on another device than the handle's: GTO_ERR_INVALID_ARG.
+ * reproduce the evaluator's is_mobile branch.  It is free on return in both, pageable or page-locked: the device variant copies
+ * per-plan bases through pinned memory of the handle, as gto_solve_base_batch_device copies n_goals (with four such calls of a
+ * handle still in flight the host waits for the oldest copy).  `obs` on another device than the handle's: GTO_ERR_INVALID_ARG.
  * gto_check_plans_device: plans and count_out in device memory, enqueued on `stream` (NULL = the handle's stream) without a
  * host synchronisation: it takes the Q_out of gto_solve_batch_device on the same stream as it is.  The per-plan bases and
  * (cloud observation) the world points and votes of a call live in one workspace per handle: calls on one handle go to one

@@ -1,0 +1,465 @@
+"""Cases for the tests of stream order (tests/test_gpu_stream_order.py): plain numpy, no GPU.
+
+For every stream-ordered entry point of include/gto_solver.h one builder makes the TRUE inputs of a call and a DECOY of the
+same shapes from another seed.  Only the ORDER of a call against its stream is under test here (what the entry points
+compute is held to the oracle and the restatements elsewhere), so the inputs need to be valid, not meaningful: counts in
+range, joints inside their limits, finite poses, scene ids that exist.  A read that races therefore gives a finite,
+different answer and never an invalid access.  A decoy is redrawn until every one of its arrays differs from the true one.
+
+The rig: Panda (most of these entry points refuse more than eight optimised joints), T = 8, standoff_offset = -2,
+max_iter = 3, two 32^3 scenes of synthetic.make_scene (ids 0 and 1), B in {1, 3, 5}, n_max = 3, a 12 x 16 depth observation
+(depth_cases' image builder and cameras) and a 65-point cloud observation (a sphere in the workspace, cloud_cases' normals).
+gto_retrieve_reverse_device needs T + standoff_offset - 10 >= 0, which T = 8 does not give: it, and the chain that
+contains it, run on a second handle with T_REVERSE = 12, the shortest horizon it accepts here.
+
+inputs(entry, B, T) -> case with
+  dev    {name: array}  arrays the caller keeps in device memory
+  host   {name: array}  arrays the header calls HOST: read during the call, free on return ("obs" holds the KINDS of the
+                        observations, 0 depth / 1 cloud; the test turns them into pointers)
+  outs   {name: (shape, dtype)}
+enqueue(rig, entry, case, d, hst, o, stream): the call itself; d and o map names to device pointers, hst to the caller's
+own host arrays, rig gives the handle (rig.handle(T)), rig.depth, rig.cloud (observations) and rig.occ (occupancy grid).
+"""
+import ctypes as C
+import json
+import os
+from types import SimpleNamespace
+
+import numpy as np
+
+import cloud_cases as cc
+import depth_cases as dc
+import grasp_filter_cases as gf
+from grasptrajopt_amd.robot_desc import load_builtin
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROBOT = "panda"
+T, T_REVERSE = 8, 12
+STANDOFF_OFFSET, MAX_ITER = -2, 3
+SCENE_N, SCENE_RES, SCENE_SEEDS = 32, 0.07, (1, 2)  # scene id k: make_scene(SCENE_SEEDS[k])
+BS, N_MAX, N_SEEDS = (1, 3, 5), 3, 2
+DEPTH_HW, CLOUD_N, CLOUD_K = (12, 16), 65, 11
+P_HELD, P_GRIPPER = 8, 20
+FILTER_OBS = (0, 1, 1, 0)  # depth, cloud, cloud, depth: two cloud runs around depth objects
+LIFT_K, LIFT_DISTANCE = 3, 0.1
+SUBDIV, M_SAMPLES = 2, 5
+IK_TOL = (0.6, 120.0, 1.0e30)      # pos, rot (degrees), cost: loose, so that some rows are accepted and some are not
+SELECT_TOL = (0.5, 5.0, 5)         # pos, rot, max_points of gto_select_plans_device
+EFFORT, MAX_RATIO = 0.01, 0.5
+REGROW_BS = (1, 3, 65, 7, 130, 2)  # six calls of one handle behind one hold: past the four pinned slots, with regrowth
+SENTINEL = {np.dtype(np.float64): -777.25, np.dtype(np.int32): -77, np.dtype(np.uint8): 90}
+
+ENTRIES = ["solve", "ik_pose", "ik_report", "seed", "seed_multi", "plan_report", "select_plans", "check_plans_depth",
+           "check_plans_cloud", "check_held_depth", "check_held_cloud", "filter_grasps", "retime_batch", "retime_paths",
+           "retrieve_lift", "retrieve_reverse", "solve_base", "base_report"]
+# the entry points whose header text says that they enqueue "without a host synchronisation" (the retime calls after a
+# first call of the handle): all but gto_solve_batch_device, which throttles on the GPU's progress
+NO_HOST_SYNC = [e for e in ENTRIES if e != "solve"]
+HORIZON = {"retrieve_reverse": T_REVERSE}  # (every other entry: T)
+# the runs of six calls of one handle behind one hold (REGROW_BS): the entries of each run's calls, per B
+REGROW_RUNS = {"base": ("solve_base", "base_report"), "check_paths": ("check_paths_depth",), "check_held": ("check_held_cloud",),
+               "filter_grasps": ("filter_grasps",)}
+
+
+def robot():
+    with open(os.path.join(ROOT, "grasptrajopt_amd", "data", f"{ROBOT}_cfg.json")) as fh:
+        return load_builtin(ROBOT), json.load(fh)
+
+
+def scenes():
+    from grasptrajopt_amd import synthetic as syn
+    return [syn.make_scene(s, n=SCENE_N, res=SCENE_RES) for s in SCENE_SEEDS]
+
+
+def depth_observation():
+    """depth (12 x 16 float32), K, cam: depth_cases' image builder, intrinsics and tilted camera."""
+    depth, _, K, cam = dc._image("stream_order", *DEPTH_HW, np.random.default_rng(4300))
+    return depth, K, cam
+
+
+def cloud_observation():
+    """65 samples of a sphere of 0.25 m in the arm's workspace, normals outward."""
+    n = cc._unit(np.random.default_rng(5300).normal(size=(CLOUD_N, 3)))
+    return np.ascontiguousarray(np.array([0.45, 0.0, 0.35]) + 0.25 * n), np.ascontiguousarray(n)
+
+
+def occupancy_points():
+    rng = np.random.default_rng(6300)
+    return np.ascontiguousarray(rng.uniform([0.0, -0.6, 0.05], [0.9, 0.6, 0.6], (400, 3)))
+
+
+# ---------------------------------------------------------------------------------------------- pieces
+def _joints(desc, rng, *shape):
+    return desc.lower + (desc.upper - desc.lower) * rng.random(shape + (desc.ndof,))
+
+
+def _poses(rng, *shape):
+    """Rigid poses with the origin in the workspace in front of the arm, flattened to 16."""
+    out = np.empty(shape + (16,))
+    for i in np.ndindex(*shape):
+        RT = gf.rigid(rng, 0.0, 2.0)
+        RT[:3, 3] = rng.uniform([0.3, -0.3, 0.15], [0.6, 0.3, 0.55])
+        out[i] = RT.reshape(16)
+    return out
+
+
+def _plans(desc, rng, B, Tp, q0=None):
+    """(B, ndof, Tp): from q0 to a random configuration along a smooth step with a bump, clipped to the limits; the parameter
+    joints keep q0's values."""
+    q0 = _joints(desc, rng, B) if q0 is None else q0
+    q1, bump = _joints(desc, rng, B), 0.2 * rng.standard_normal((B, desc.ndof))
+    s = np.linspace(0.0, 1.0, Tp)
+    Q = q0[:, :, None] + (q1 - q0)[:, :, None] * (s * s * (3 - 2 * s)) + bump[:, :, None] * np.sin(np.pi * s)
+    Q = np.clip(Q, desc.lower[None, :, None], desc.upper[None, :, None])
+    Q[:, desc.param_index] = q0[:, desc.param_index, None]
+    return np.ascontiguousarray(Q)
+
+
+def _counts(rng, B, lo, hi):
+    return rng.integers(lo, hi + 1, B).astype(np.int32)
+
+
+def _bases(rng, B):
+    return rng.uniform(-0.05, 0.05, (B, 3))
+
+
+def _standoff(rng, B):
+    S = np.tile(np.eye(4), (B, 1, 1))
+    S[:, 2, 3] = -0.05 - 0.1 * rng.random(B)
+    return S.reshape(B, 16)
+
+
+def _retime_outs(desc, B, Tp):
+    N = SUBDIV * (Tp - 1) + 1
+    f, nd = np.float64, desc.ndof
+    return dict(duration=((B,), f), t_grid=((B, N), f), sd_grid=((B, N), f), q=((B, M_SAMPLES, nd), f), qd=((B, M_SAMPLES, nd), f),
+                qdd=((B, M_SAMPLES, nd), f), status=((B,), np.int32))
+
+
+def _limits(desc, rng):
+    return dict(vmax=rng.uniform(1.0, 2.5, desc.ndof), amax=rng.uniform(2.0, 6.0, desc.ndof))
+
+
+def _closed(desc, rng):
+    return dict(closed_joints=rng.permutation(desc.param_index).astype(np.int32), closed_values=rng.uniform(0.0, 0.04, len(desc.param_index)))
+
+
+# ---------------------------------------------------------------------------------------------- one draw per entry point
+def _draw(entry, B, Tp, rng):
+    desc, _ = robot()
+    f, i32, u8, nd = np.float64, np.int32, np.uint8, desc.ndof
+    dev, host = {}, {}
+    if entry == "solve":
+        qc = _joints(desc, rng, B)
+        dev = dict(scene_id=_counts(rng, B, 0, 1), qc=qc, goals=_poses(rng, B, N_MAX), n_goals=_counts(rng, B, 1, N_MAX),
+                   standoff=_standoff(rng, B), base_pos=_bases(rng, B), Q0=_plans(desc, rng, B, Tp, qc))
+        outs = dict(Q=((B, nd, Tp), f), dQ=((B, nd, Tp - 1), f), cost=((B,), f), iters=((B,), i32), status=((B,), i32))
+    elif entry == "ik_pose":
+        dev = dict(scene_id=_counts(rng, B, 0, 1), q0=_joints(desc, rng, B), goals=_poses(rng, B), base_pos=_bases(rng, B))
+        outs = dict(q=((B, nd), f), cost=((B,), f), iters=((B,), i32), status=((B,), i32))
+    elif entry == "ik_report":
+        dev = dict(scene_id=_counts(rng, B, 0, 1), q=_joints(desc, rng, B), goals=_poses(rng, B), base_pos=_bases(rng, B))
+        outs = dict(err_pos=((B,), f), err_rot=((B,), f), cost=((B,), f), accept=((B,), u8))
+    elif entry in ("seed", "seed_multi"):
+        accept = (rng.random((B, N_MAX)) < 0.6).astype(u8)
+        accept[np.arange(B), rng.integers(0, N_MAX, B)] = 1
+        dev = dict(scene_id=_counts(rng, B, 0, 1), qc=_joints(desc, rng, B), goals=_poses(rng, B, N_MAX), n_goals=_counts(rng, B, 1, N_MAX),
+                   q_solutions=_joints(desc, rng, B, N_MAX), accept=accept, base_pos=_bases(rng, B))
+        if entry == "seed":
+            outs = dict(goals_out=((B, N_MAX, 16), f), n_goals_out=((B,), i32), n_accepted=((B,), i32), Q0_out=((B, nd, Tp), f),
+                        seed_index=((B,), i32), seed_cost=((B, N_MAX), f), seed_dist=((B, N_MAX), f))
+        else:
+            S = N_SEEDS
+            outs = dict(goals_out=((B, S, N_MAX, 16), f), n_goals_out=((B, S), i32), n_accepted=((B,), i32), accepted_rows=((B, N_MAX), i32),
+                        Q0_out=((B, S, nd, Tp), f), seed_index=((B, S), i32), seed_cost=((B, N_MAX), f), seed_dist=((B, N_MAX), f))
+    elif entry == "plan_report":
+        dev = dict(goals=_poses(rng, B, N_MAX), n_goals=_counts(rng, B, 1, N_MAX), standoff=_standoff(rng, B), Q=_plans(desc, rng, B, Tp))
+        outs = dict(goal_index=((B,), i32), goal_cost=((B,), f), err_pos=((B,), f), err_rot=((B,), f))
+    elif entry == "select_plans":
+        S = N_SEEDS
+        dev = dict(status=rng.integers(0, 2, (B, S)).astype(i32), cost=rng.uniform(0.1, 2.0, (B, S)), err_pos=rng.uniform(0.0, 1.0, (B, S)),
+                   err_rot=rng.uniform(0.0, 10.0, (B, S)), counts=rng.integers(0, 8, (B, S, Tp)).astype(i32),
+                   Q=_plans(desc, rng, B * S, Tp).reshape(B, S, nd, Tp), dQ=rng.uniform(-1.0, 1.0, (B, S, nd, Tp - 1)))
+        outs = dict(best_slot=((B,), i32), cls=((B,), i32), Q_out=((B, nd, Tp), f), dQ_out=((B, nd, Tp - 1), f))
+    elif entry.startswith(("check_plans_", "check_paths_")):
+        dev, host = dict(plans=_plans(desc, rng, B, Tp)), dict(base_pos=_bases(rng, B))
+        outs = dict(count=((B, Tp), i32))
+    elif entry.startswith("check_held_"):
+        dev = dict(paths=_plans(desc, rng, B, Tp), held=rng.uniform([0.2, -0.4, 0.0], [0.7, 0.4, 0.7], (B, P_HELD, 3)),
+                   n_held=_counts(rng, B, 1, P_HELD))
+        host, outs = dict(base_pos=_bases(rng, B)), dict(count=((B, Tp), i32))
+    elif entry == "filter_grasps":
+        grasps = np.stack([gf.rigid(rng, 0.1, 1.0).reshape(16) for _ in range(B * N_MAX)]).reshape(B, N_MAX, 16)
+        Sc, Si = gf.offsets(rng, True)
+        Si[1, 3] = rng.uniform(-0.05, 0.05)
+        obs = np.resize(np.array(FILTER_OBS, dtype=np.int8), B)
+        dev = dict(points=rng.uniform(-0.08, 0.08, (P_GRIPPER, 3)), object_pose=_poses(rng, B), grasps=grasps,
+                   n_grasps=_counts(rng, B, 1, N_MAX), base_pos=_bases(rng, B))
+        host = dict(obs=obs,check_offset=Sc.reshape(16), ik_offset=Si.reshape(16))
+        outs = dict(count=((B, N_MAX), i32), keep=((B, N_MAX), u8), kept_rows=((B, N_MAX), i32), n_kept=((B,), i32), n_grasps_out=((B,), i32),
+                    plan_goals=((B, N_MAX, 16), f), ik_goals=((B, N_MAX, 16), f))
+    elif entry == "retime_batch":
+        dev, host, outs = dict(plans=_plans(desc, rng, B, Tp)), _limits(desc, rng), _retime_outs(desc, B, Tp)
+    elif entry == "retime_paths":
+        dev, host = dict(paths=_plans(desc, rng, B, Tp), n_cols=_counts(rng, B, 3, Tp)), _limits(desc, rng)
+        outs = _retime_outs(desc, B, Tp)
+    elif entry == "retrieve_lift":
+        d = cc._unit(rng.normal(size=(1, 3)))[0]
+        dev = dict(plans=_plans(desc, rng, B, Tp), scene_id=_counts(rng, B, 0, 1), base_pos=_bases(rng, B))
+        host = dict(direction=np.ascontiguousarray(d), **_closed(desc, rng))
+        K = LIFT_K
+        outs = dict(path=((B, nd, K + 1), f), goals=((B, K, 16), f), err_pos=((B, K), f), err_rot=((B, K), f), iters=((B, K), i32),
+                    status=((B, K), i32), reached=((B,), i32))
+    elif entry == "retrieve_reverse":
+        dev, host = dict(plans=_plans(desc, rng, B, Tp)), _closed(desc, rng)
+        outs = dict(path=((B, nd, 9 - STANDOFF_OFFSET), f))
+    elif entry == "solve_base":
+        dev, host = dict(qc=_joints(desc, rng, B), goals=_poses(rng, B, N_MAX)), dict(n_goals=_counts(rng, B, 1, N_MAX))
+        outs = dict(y=((B, 3), f), q=((B, N_MAX, nd), f), cost=((B,), f), iters=((B,), i32), status=((B,), i32))
+    elif entry == "base_report":
+        dev = dict(qc=_joints(desc, rng, B), goals=_poses(rng, B, N_MAX), y=rng.uniform([-0.3, -0.3, -1.0], [0.3, 0.3, 1.0], (B, 3)),
+                   q=_joints(desc, rng, B, N_MAX))
+        host = dict(n_goals=_counts(rng, B, 1, N_MAX))
+        outs = dict(err_pos=((B, N_MAX), f), err_rot=((B, N_MAX), f), collision=((B,), i32), first_free=((1,), i32))
+    else:
+        raise KeyError(entry)
+    fix = lambda a: np.ascontiguousarray(a)
+    return SimpleNamespace(entry=entry, B=B, T=Tp, dev={k: fix(v) for k, v in dev.items()}, host={k: fix(v) for k, v in host.items()},
+                           outs={k: (tuple(s), np.dtype(t)) for k, (s, t) in outs.items()})
+
+
+def _seed(entry, B, Tp, draw):
+    return [9100 + draw, sum(map(ord, entry)), B, Tp]
+
+
+def flipped_obs(obs):
+    """Another valid table of observation kinds: every depth object a cloud object and the other way round."""
+    return (1 - obs).astype(np.int8)
+
+
+_CASES = {}
+
+
+def inputs(entry, B, Tp=None, decoy=False):
+    """The true inputs of a call of `entry` over B items at horizon / path length Tp, or their decoy: the next draws'
+    first whose every array differs from the true one (at B = 1 a count or a scene id of the next draw may coincide)."""
+    Tp = HORIZON.get(entry, T) if Tp is None else Tp
+    key = (entry, B, Tp, decoy)
+    if key not in _CASES:
+        true = _draw(entry, B, Tp, np.random.default_rng(_seed(entry, B, Tp, 0)))
+        case = true
+        if decoy:
+            for draw in range(1, 200):
+                case = _draw(entry, B, Tp, np.random.default_rng(_seed(entry, B, Tp, draw)))
+                if "obs" in case.host:
+                    case.host["obs"] = flipped_obs(true.host["obs"])
+                if all(not np.array_equal(a, b) for part in ("dev", "host") for a, b in zip(getattr(true, part).values(), getattr(case, part).values())):
+                    break
+            else:
+                raise AssertionError(f"{entry}, B = {B}: no decoy that differs in every array")
+        for a in list(case.dev.values()) + list(case.host.values()):
+            a.setflags(write=False)
+        _CASES[key] = case
+    return _CASES[key]
+
+
+def valid(case):
+    """The reasons why `case` is not a valid problem (empty: it is one): what keeps a racing read from an invalid access."""
+    desc, _ = robot()
+    bad = []
+    arrays = {**case.dev, **case.host}
+    for name, a in arrays.items():
+        if a.dtype.kind == "f" and not np.isfinite(a).all():
+            bad.append(f"{name}: a non-finite entry")
+    for name, hi in (("n_goals", N_MAX), ("n_grasps", N_MAX), ("n_held", P_HELD), ("n_cols", case.T)):
+        if name in arrays and not ((arrays[name] >= 1) & (arrays[name] <= hi)).all():
+            bad.append(f"{name}: outside [1, {hi}]")
+    if "scene_id" in arrays and not np.isin(arrays["scene_id"], np.arange(len(SCENE_SEEDS))).all():
+        bad.append("scene_id: a scene that does not exist")
+    for name in ("qc", "q0", "q", "q_solutions", "Q0", "Q", "plans", "paths"):
+        if name in arrays:
+            a = arrays[name]
+            q = np.moveaxis(a, -2, -1) if name in ("Q0", "Q", "plans", "paths") else a  # joints last
+            if not ((q >= desc.lower) & (q <= desc.upper)).all():
+                bad.append(f"{name}: a joint outside its limits")
+    if "closed_joints" in arrays:
+        cj = arrays["closed_joints"]
+        if len(set(cj.tolist())) != len(cj) or not ((cj >= 0) & (cj < desc.ndof)).all():
+            bad.append("closed_joints: not distinct joints of the robot")
+    if "obs" in arrays and not np.isin(arrays["obs"], (0, 1)).all():
+        bad.append("obs: an unknown kind")
+    for name in ("vmax", "amax"):
+        if name in arrays and not (arrays[name] > 0).all():
+            bad.append(f"{name}: not positive")
+    for name in ("goals", "object_pose", "grasps", "standoff", "check_offset", "ik_offset"):
+        if name in arrays:
+            M = arrays[name].reshape(-1, 4, 4)
+            if not (np.allclose(M[:, 3], [0, 0, 0, 1]) and np.allclose(M[:, :3, :3] @ np.swapaxes(M[:, :3, :3], 1, 2), np.eye(3), atol=1e-9)):
+                bad.append(f"{name}: not a rigid pose")
+    return bad
+
+
+# ---------------------------------------------------------------------------------------------- the calls
+_pd, _pi, _pv = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_void_p)
+
+
+def _v(x):
+    return None if x is None else C.c_void_p(int(x))
+
+
+def _hp(a, typ):
+    return a.ctypes.data_as(typ)
+
+
+def enqueue(rig, entry, case, d, hst, o, stream):
+    """Enqueue the call of `entry` on `stream` (a raw stream handle) through the library's C ABI: the caller's own host arrays
+    go in as they are (the binding's methods would copy them), so that the test can write over them when the call returns."""
+    B, Tp = case.B, case.T
+    hd = rig.handle(HORIZON.get(entry, T))
+    lib, h, st = hd.lib, hd._h, _v(stream)
+    D, O = (lambda k: _v(d[k])), (lambda k: _v(o[k]))
+    if entry == "solve":
+        rc = lib.gto_solve_batch_device(h, B, N_MAX, D("scene_id"), D("qc"), D("goals"), D("n_goals"), D("standoff"), D("base_pos"), D("Q0"),
+                                        O("Q"), O("dQ"), O("cost"), O("iters"), O("status"), st)
+    elif entry == "ik_pose":
+        rc = lib.gto_solve_ik_pose_batch_device(h, 0, B, D("scene_id"), D("q0"), D("goals"), D("base_pos"), MAX_ITER, O("q"), O("cost"),
+                                                O("iters"), O("status"), st)
+    elif entry == "ik_report":
+        rc = lib.gto_ik_report_device(h, B, D("scene_id"), D("q"), D("goals"), D("base_pos"), *IK_TOL, O("err_pos"), O("err_rot"), O("cost"),
+                                      O("accept"), st)
+    elif entry == "seed":
+        rc = lib.gto_seed_goalsets_device(h, B, N_MAX, D("scene_id"), D("qc"), D("goals"), D("n_goals"), D("q_solutions"), D("accept"),
+                                          D("base_pos"), 1, 0, O("goals_out"), O("n_goals_out"), O("n_accepted"), O("Q0_out"),
+                                          O("seed_index"), O("seed_cost"), O("seed_dist"), st)
+    elif entry == "seed_multi":
+        rc = lib.gto_seed_goalsets_multi_device(h, B, N_MAX, N_SEEDS, D("scene_id"), D("qc"), D("goals"), D("n_goals"), D("q_solutions"),
+                                                D("accept"), D("base_pos"), 1, 0, O("goals_out"), O("n_goals_out"), O("n_accepted"),
+                                                O("accepted_rows"), O("Q0_out"), O("seed_index"), O("seed_cost"), O("seed_dist"), st)
+    elif entry == "plan_report":
+        rc = lib.gto_plan_report_device(h, B, N_MAX, D("goals"), D("n_goals"), D("standoff"), D("Q"), O("goal_index"), O("goal_cost"),
+                                        O("err_pos"), O("err_rot"), st)
+    elif entry == "select_plans":
+        rc = lib.gto_select_plans_device(h, B, N_SEEDS, D("status"), D("cost"), D("err_pos"), D("err_rot"), D("counts"), SELECT_TOL[0],
+                                         SELECT_TOL[1], SELECT_TOL[2], D("Q"), D("dQ"), O("best_slot"), O("cls"), O("Q_out"), O("dQ_out"), st)
+    elif entry.startswith("check_plans_"):
+        rc = lib.gto_check_plans_device(h, rig.observation(entry)._ptr(), B, D("plans"), _hp(hst["base_pos"], _pd), 1, O("count"), st)
+    elif entry.startswith("check_paths_"):
+        rc = lib.gto_check_paths_device(h, rig.observation(entry)._ptr(), B, Tp, D("plans"), _hp(hst["base_pos"], _pd), 1, O("count"), st)
+    elif entry.startswith("check_held_"):
+        rc = lib.gto_check_held_paths_device(h, rig.observation(entry)._ptr(), B, Tp, D("paths"), None, 0, 0, D("held"), P_HELD, D("n_held"),
+                                             None, None, None, _hp(hst["base_pos"], _pd), 1, O("count"), st)
+    elif entry == "filter_grasps":
+        rc = lib.gto_filter_grasps_device(h, B, N_MAX, _hp(hst["obs"], _pv), D("points"), P_GRIPPER, D("object_pose"), D("grasps"),
+                                          D("n_grasps"), None, D("base_pos"), _hp(hst["check_offset"], _pd), _hp(hst["ik_offset"], _pd),
+                                          MAX_RATIO, O("count"), O("keep"), O("kept_rows"), O("n_kept"), O("n_grasps_out"), O("plan_goals"),
+                                          O("ik_goals"), st)
+    elif entry == "retime_batch":
+        rc = lib.gto_retime_batch_device(h, B, D("plans"), _hp(hst["vmax"], _pd), _hp(hst["amax"], _pd), SUBDIV, M_SAMPLES, O("duration"),
+                                         O("t_grid"), O("sd_grid"), O("q"), O("qd"), O("qdd"), O("status"), st)
+    elif entry == "retime_paths":
+        rc = lib.gto_retime_paths_device(h, B, Tp, D("paths"), D("n_cols"), _hp(hst["vmax"], _pd), _hp(hst["amax"], _pd), SUBDIV, M_SAMPLES,
+                                         O("duration"), O("t_grid"), O("sd_grid"), O("q"), O("qd"), O("qdd"), O("status"), st)
+    elif entry == "retrieve_lift":
+        cj, cv = hst["closed_joints"], hst["closed_values"]
+        rc = lib.gto_retrieve_lift_device(h, B, D("plans"), D("scene_id"), D("base_pos"), _hp(hst["direction"], _pd), LIFT_DISTANCE, LIFT_K,
+                                          _hp(cj, _pi), _hp(cv, _pd), len(cj), MAX_ITER, 0.01, 5.0, O("path"), O("goals"), O("err_pos"),
+                                          O("err_rot"), O("iters"), O("status"), O("reached"), st)
+    elif entry == "retrieve_reverse":
+        cj, cv = hst["closed_joints"], hst["closed_values"]
+        rc = lib.gto_retrieve_reverse_device(h, B, D("plans"), _hp(cj, _pi), _hp(cv, _pd), len(cj), O("path"), None, st)
+    elif entry == "solve_base":
+        rc = lib.gto_solve_base_batch_device(h, B, N_MAX, _hp(hst["n_goals"], _pi), D("qc"), D("goals"), EFFORT, MAX_ITER, O("y"), O("q"),
+                                             O("cost"), O("iters"), O("status"), st)
+    elif entry == "base_report":
+        rc = lib.gto_base_report_device(h, rig.occ._ptr(), B, N_MAX, _hp(hst["n_goals"], _pi), D("qc"), D("goals"), D("y"), D("q"),
+                                        O("err_pos"), O("err_rot"), O("collision"), O("first_free"), st)
+    else:
+        raise KeyError(entry)
+    hd._check(rc, entry)
+
+
+# ---------------------------------------------------------------------------------------------- the whole chain
+CHAIN_B = 3
+CHAIN_STEPS = ["gto_solve_ik_pose_batch_device", "gto_ik_report_device", "gto_seed_goalsets_multi_device", "gto_solve_batch_device",
+               "gto_plan_report_device", "gto_check_plans_device", "gto_select_plans_device", "gto_retime_batch_device",
+               "gto_retrieve_reverse_device", "gto_check_held_paths_device", "gto_retime_paths_device"]
+_CHAIN = {}
+
+
+def chain_inputs(decoy=False):
+    """The head of the chain from grasp poses to a retimed retrieve path, at T_REVERSE: CHAIN_B objects of N_MAX goals each,
+    N_SEEDS slots per object.  dev: what the caller uploads in front of the chain; host: the HOST arguments of its calls;
+    outs: every array a call of the chain writes (most of them are the next call's input)."""
+    if decoy not in _CHAIN:
+        desc, _ = robot()
+        B, S, n, Tp, nd = CHAIN_B, N_SEEDS, N_MAX, T_REVERSE, desc.ndof
+        for draw in range(0 if not decoy else 1, 200):
+            rng = np.random.default_rng([9700, draw])
+            scene, qc, base, goals = _counts(rng, B, 0, 1), _joints(desc, rng, B), _bases(rng, B), _poses(rng, B, n)
+            dev = dict(scene_id=scene, qc=qc, base_pos=base, goals=goals, n_goals=_counts(rng, B, 1, n),
+                       scene_rows=np.repeat(scene, n), q0_rows=np.repeat(qc, n, axis=0), base_rows=np.repeat(base, n, axis=0),
+                       scene_slots=np.repeat(scene, S), qc_slots=np.repeat(qc, S, axis=0), base_slots=np.repeat(base, S, axis=0),
+                       standoff_slots=np.repeat(_standoff(rng, B), S, axis=0),
+                       held=rng.uniform([0.2, -0.4, 0.0], [0.7, 0.4, 0.7], (B, P_HELD, 3)), n_held=_counts(rng, B, 1, P_HELD))
+            host = dict(check_base=np.repeat(base, S, axis=0), held_base=base.copy(), **_limits(desc, rng), **_closed(desc, rng))
+            case = SimpleNamespace(entry="chain", B=B, T=Tp, dev={k: np.ascontiguousarray(v) for k, v in dev.items()},
+                                   host={k: np.ascontiguousarray(v) for k, v in host.items()})
+            if not decoy or all(not np.array_equal(a, b) for part in ("dev", "host")
+                                for a, b in zip(getattr(chain_inputs(), part).values(), getattr(case, part).values())):
+                break
+        else:
+            raise AssertionError("chain: no decoy that differs in every array")
+        f, i32, u8, R, Z, Pc = np.float64, np.int32, np.uint8, B * n, B * S, 9 - STANDOFF_OFFSET
+        outs = dict(q_sol=((R, nd), f), ik_cost=((R,), f), ik_iters=((R,), i32), ik_status=((R,), i32),
+                    r_err_pos=((R,), f), r_err_rot=((R,), f), r_cost=((R,), f), accept=((R,), u8),
+                    goals_s=((B, S, n, 16), f), n_goals_s=((B, S), i32), n_acc=((B,), i32), acc_rows=((B, n), i32), Q0_s=((B, S, nd, Tp), f),
+                    seed_idx=((B, S), i32), seed_cost=((B, n), f), seed_dist=((B, n), f),
+                    Q=((Z, nd, Tp), f), dQ=((Z, nd, Tp - 1), f), cost=((Z,), f), iters=((Z,), i32), status=((Z,), i32),
+                    goal_index=((Z,), i32), goal_cost=((Z,), f), p_err_pos=((Z,), f), p_err_rot=((Z,), f), counts=((Z, Tp), i32),
+                    best=((B,), i32), cls=((B,), i32), Q_sel=((B, nd, Tp), f), dQ_sel=((B, nd, Tp - 1), f),
+                    path=((B, nd, Pc), f), held_count=((B, Pc), i32))
+        outs.update({"rt_" + k: v for k, v in _retime_outs(desc, B, Tp).items()})
+        outs.update({"rp_" + k: v for k, v in _retime_outs(desc, B, Pc).items()})
+        case.outs = {k: (tuple(s), np.dtype(t)) for k, (s, t) in outs.items()}
+        for a in list(case.dev.values()) + list(case.host.values()):
+            a.setflags(write=False)
+        _CHAIN[decoy] = case
+    return _CHAIN[decoy]
+
+
+def enqueue_chain(rig, case, d, hst, o, stream, between=lambda step: None):
+    """The eleven calls of CHAIN_STEPS on `stream`, each taking what the calls before it wrote; between(step) runs after
+    every call (the call-by-call pass synchronises the device there)."""
+    hd = rig.handle(T_REVERSE)
+    lib, h, st = hd.lib, hd._h, _v(stream)
+    B, S, n, Tp, Pc = case.B, N_SEEDS, N_MAX, case.T, 9 - STANDOFF_OFFSET
+    R, Z = B * n, B * S
+    D, O = (lambda k: _v(d[k])), (lambda k: _v(o[k]))
+    vm, am, cj, cv = _hp(hst["vmax"], _pd), _hp(hst["amax"], _pd), hst["closed_joints"], hst["closed_values"]
+    calls = [
+        lambda: lib.gto_solve_ik_pose_batch_device(h, 0, R, D("scene_rows"), D("q0_rows"), D("goals"), D("base_rows"), MAX_ITER, O("q_sol"),
+                                                   O("ik_cost"), O("ik_iters"), O("ik_status"), st),
+        lambda: lib.gto_ik_report_device(h, R, D("scene_rows"), O("q_sol"), D("goals"), D("base_rows"), *IK_TOL, O("r_err_pos"),
+                                         O("r_err_rot"), O("r_cost"), O("accept"), st),
+        lambda: lib.gto_seed_goalsets_multi_device(h, B, n, S, D("scene_id"), D("qc"), D("goals"), D("n_goals"), O("q_sol"), O("accept"),
+                                                   D("base_pos"), 1, 0, O("goals_s"), O("n_goals_s"), O("n_acc"), O("acc_rows"), O("Q0_s"),
+                                                   O("seed_idx"), O("seed_cost"), O("seed_dist"), st),
+        lambda: lib.gto_solve_batch_device(h, Z, n, D("scene_slots"), D("qc_slots"), O("goals_s"), O("n_goals_s"), D("standoff_slots"),
+                                           D("base_slots"), O("Q0_s"), O("Q"), O("dQ"), O("cost"), O("iters"), O("status"), st),
+        lambda: lib.gto_plan_report_device(h, Z, n, O("goals_s"), O("n_goals_s"), D("standoff_slots"), O("Q"), O("goal_index"),
+                                           O("goal_cost"), O("p_err_pos"), O("p_err_rot"), st),
+        lambda: lib.gto_check_plans_device(h, rig.depth._ptr(), Z, O("Q"), _hp(hst["check_base"], _pd), 1, O("counts"), st),
+        lambda: lib.gto_select_plans_device(h, B, S, O("status"), O("cost"), O("p_err_pos"), O("p_err_rot"), O("counts"), SELECT_TOL[0],
+                                            SELECT_TOL[1], SELECT_TOL[2], O("Q"), O("dQ"), O("best"), O("cls"), O("Q_sel"), O("dQ_sel"), st),
+        lambda: lib.gto_retime_batch_device(h, B, O("Q_sel"), vm, am, SUBDIV, M_SAMPLES, O("rt_duration"), O("rt_t_grid"), O("rt_sd_grid"),
+                                            O("rt_q"), O("rt_qd"), O("rt_qdd"), O("rt_status"), st),
+        lambda: lib.gto_retrieve_reverse_device(h, B, O("Q_sel"), _hp(cj, _pi), _hp(cv, _pd), len(cj), O("path"), None, st),
+        lambda: lib.gto_check_held_paths_device(h, rig.cloud._ptr(), B, Pc, O("path"), O("Q_sel"), Tp, Tp - 1, D("held"), P_HELD, D("n_held"),
+                                                None, None, None, _hp(hst["held_base"], _pd), 1, O("held_count"), st),
+        lambda: lib.gto_retime_paths_device(h, B, Pc, O("path"), None, vm, am, SUBDIV, M_SAMPLES, O("rp_duration"), O("rp_t_grid"),
+                                            O("rp_sd_grid"), O("rp_q"), O("rp_qd"), O("rp_qdd"), O("rp_status"), st),
+    ]
+    assert len(calls) == len(CHAIN_STEPS)
+    for step, call in zip(CHAIN_STEPS, calls):
+        hd._check(call(), step)
+        between(step)

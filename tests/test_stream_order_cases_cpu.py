@@ -1,0 +1,77 @@
+"""CPU: the case builders of the stream-order tests (tests/stream_order_cases.py).  A decoy has to be a valid problem, or a
+read that races would be an invalid access instead of a wrong answer, and it has to differ from the true inputs in every
+array, or a race on that array could not be seen."""
+import numpy as np
+import pytest
+
+import stream_order_cases as soc
+
+CHECK_REGROW = sorted({e for run in soc.REGROW_RUNS.values() for e in run})
+ALL_ENTRIES = soc.ENTRIES + [e for e in CHECK_REGROW if e not in soc.ENTRIES]
+
+
+def _all_cases():
+    for entry in soc.ENTRIES:
+        for B in soc.BS:
+            yield entry, B
+    for entry in CHECK_REGROW:
+        for B in soc.REGROW_BS:
+            yield entry, B
+
+
+@pytest.mark.parametrize("entry", ALL_ENTRIES)
+def test_true_inputs_and_decoys_are_valid_problems(entry):
+    for e, B in _all_cases():
+        if e != entry:
+            continue
+        for decoy in (False, True):
+            case = soc.inputs(e, B, decoy=decoy)
+            assert soc.valid(case) == [], (e, B, decoy)
+            for name in ("n_goals", "n_grasps"):
+                for part in (case.dev, case.host):
+                    if name in part:
+                        assert part[name].dtype == np.int32 and part[name].min() >= 1 and part[name].max() <= soc.N_MAX
+
+
+@pytest.mark.parametrize("entry", ALL_ENTRIES)
+def test_decoys_have_the_shapes_of_the_true_inputs_and_differ_in_every_array(entry):
+    for e, B in _all_cases():
+        if e != entry:
+            continue
+        true, decoy = soc.inputs(e, B), soc.inputs(e, B, decoy=True)
+        assert true.outs == decoy.outs
+        for part in ("dev", "host"):
+            a, b = getattr(true, part), getattr(decoy, part)
+            assert list(a) == list(b)
+            for name in a:
+                assert a[name].shape == b[name].shape and a[name].dtype == b[name].dtype, (e, B, name)
+                assert not np.array_equal(a[name], b[name]), (e, B, name)
+                assert not a[name].flags.writeable  # shared between tests: nobody changes a case
+
+
+def test_valid_notices_what_it_is_there_for():
+    case = soc.inputs("solve", 3)
+    broken = lambda **kw: soc.SimpleNamespace(**{**vars(case), "dev": {**case.dev, **kw}})
+    assert any("n_goals" in r for r in soc.valid(broken(n_goals=np.array([1, 0, 2], np.int32))))
+    assert any("n_goals" in r for r in soc.valid(broken(n_goals=np.array([1, soc.N_MAX + 1, 2], np.int32))))
+    assert any("scene_id" in r for r in soc.valid(broken(scene_id=np.array([0, 2, 1], np.int32))))
+    qc = case.dev["qc"].copy()
+    qc[1, 3] = 0.5  # the Panda's fourth joint ends at -0.0698
+    assert any("qc" in r for r in soc.valid(broken(qc=qc)))
+    goals = case.dev["goals"].copy()
+    goals[0, 0, 5] = np.nan
+    assert any("goals" in r for r in soc.valid(broken(goals=goals)))
+
+
+def test_the_rig_is_the_one_the_tests_state():
+    desc, cfg = soc.robot()
+    assert desc.n_opt <= 8 and soc.T + soc.STANDOFF_OFFSET >= 2
+    assert soc.T + soc.STANDOFF_OFFSET - 10 < 0 <= soc.T_REVERSE + soc.STANDOFF_OFFSET - 10  # why the reverse path has its own horizon
+    depth, K, cam = soc.depth_observation()
+    assert depth.shape == (12, 16) and depth.dtype == np.float32
+    pts, nrm = soc.cloud_observation()
+    assert pts.shape == nrm.shape == (65, 3) and np.allclose(np.linalg.norm(nrm, axis=1), 1.0)
+    assert soc.FILTER_OBS == (0, 1, 1, 0)
+    assert len(soc.REGROW_BS) > 4  # more calls in flight than pinned slots
+    sc = soc.scenes()
+    assert len(sc) == 2 and tuple(sc[0].shape) == (32, 32, 32) and not np.array_equal(sc[0].c_obs, sc[1].c_obs)
