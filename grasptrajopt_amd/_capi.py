@@ -162,10 +162,29 @@ def _prototypes():
         "gto_check_held_paths_device": (I, [V, V, I32, I32, V, V, I32, I32, V, I32, V, V, V, V, _pd, I32, V, V]),
         "gto_retime_paths": (I, [V, I32, I32, _pd, _pi, _pd, _pd, I32, I32, _pd, _pd, _pd, _pd, _pd, _pd, _pi]),
         "gto_retime_paths_device": (I, [V, I32, I32, V, V, _pd, _pd, I32, I32] + [V] * 8),
+        "gto_retime_paths_convex": (I, [V, I32, I32, _pd, _pi, _pd, _pd, I32, I32, D, I32, _pd, _pd, _pd, _pd, _pd, _pd, _pi, _pi]),
+        "gto_retime_paths_convex_device": (I, [V, I32, I32, V, V, _pd, _pd, I32, I32, D, I32] + [V] * 9),
     }
 
 
 PROTOTYPES = _prototypes()
+# Newton steps a path may take in the convex retiming by default: more than twice the largest count seen over the test
+# inputs
+RETIME_MAX_NEWTON = 400
+RETIME_PROFILES = ("greedy", "convex")
+
+
+def retime_profile(profile="greedy", gap_tol=1e-8, max_newton=None):
+    """The checked (profile, gap_tol, max_newton) of a retime request, for every Python layer that takes one."""
+    if profile not in RETIME_PROFILES:
+        raise ValueError(f"retime: profile must be one of {RETIME_PROFILES}, got {profile!r}")
+    gap_tol = float(gap_tol)
+    if not (np.isfinite(gap_tol) and gap_tol > 0):
+        raise ValueError(f"retime: gap_tol must be finite and > 0, got {gap_tol}")
+    max_newton = RETIME_MAX_NEWTON if max_newton is None else int(max_newton)
+    if max_newton < 1:
+        raise ValueError(f"retime: max_newton must be >= 1, got {max_newton}")
+    return profile, gap_tol, max_newton
 EXPORTED_SYMBOLS = tuple(PROTOTYPES)
 
 
@@ -1004,6 +1023,43 @@ class SolverHandle:
                                               _p(out["q"], _pd), _p(out["qd"], _pd), _p(out["qdd"], _pd),
                                               _p(out["status"], _pi)), "gto_retime_paths")
         return out
+
+    def retime_paths_convex(self, paths, vmax, amax, n_cols=None, subdiv: int = 2, n_samples: int = 100,
+                            gap_tol: float = 1e-8, max_newton: int = RETIME_MAX_NEWTON):
+        """gto_retime_paths_convex: retime_paths with the grid's time-optimal profile (a convex program per path, solved to
+        a certified relative gap gap_tol in at most max_newton Newton steps) in place of the greedy one.  Returns the dict
+        of retime_paths and iters (B,), the Newton steps taken; status 1 (GTO_STATUS_MAX_ITER): a feasible profile with valid
+        samples whose gap is not certified."""
+        d = self.desc
+        paths = _f64(paths)
+        if paths.ndim != 3 or paths.shape[1] != d.ndof:
+            raise ValueError(f"retime_paths_convex: paths must be (B, {d.ndof}, Tp), got {paths.shape}")
+        B, Tp, M = paths.shape[0], paths.shape[2], int(n_samples)
+        N = max(int(subdiv) * (Tp - 1) + 1, 0)
+        nc = None if n_cols is None else _per_instance(n_cols, B)
+        vm, am = self._retime_limits(vmax, amax)
+        out = dict(duration=np.empty(B), t_grid=np.empty((B, N)), sd_grid=np.empty((B, N)),
+                   q=np.empty((B, max(M, 0), d.ndof)), qd=np.empty((B, max(M, 0), d.ndof)), qdd=np.empty((B, max(M, 0), d.ndof)),
+                   status=np.empty(B, dtype=np.int32), iters=np.empty(B, dtype=np.int32))
+        self._check(self.lib.gto_retime_paths_convex(self._h, B, Tp, _p(paths, _pd), _p(nc, _pi), _p(vm, _pd), _p(am, _pd),
+                                                     int(subdiv), M, float(gap_tol), int(max_newton),
+                                                     _p(out["duration"], _pd), _p(out["t_grid"], _pd), _p(out["sd_grid"], _pd),
+                                                     _p(out["q"], _pd), _p(out["qd"], _pd), _p(out["qdd"], _pd),
+                                                     _p(out["status"], _pi), _p(out["iters"], _pi)), "gto_retime_paths_convex")
+        return out
+
+    def retime_paths_convex_device(self, B, Tp, paths, vmax, amax, n_cols=None, subdiv=2, n_samples=100, gap_tol=1e-8,
+                                   max_newton=RETIME_MAX_NEWTON, duration_out=None, t_grid_out=None, sd_grid_out=None,
+                                   q_out=None, qd_out=None, qdd_out=None, status_out=None, iters_out=None, stream=None):
+        """gto_retime_paths_convex_device: retime_paths_device with the convex profile; iters_out (B,) int32 is a device
+        pointer or None."""
+        vm, am = self._retime_limits(vmax, amax)
+        self._check(self.lib.gto_retime_paths_convex_device(self._h, int(B), int(Tp), _vp(paths), _vp(n_cols), _p(vm, _pd),
+                                                            _p(am, _pd), int(subdiv), int(n_samples), float(gap_tol),
+                                                            int(max_newton), _vp(duration_out), _vp(t_grid_out),
+                                                            _vp(sd_grid_out), _vp(q_out), _vp(qd_out), _vp(qdd_out),
+                                                            _vp(status_out), _vp(iters_out), _vp(stream)),
+                    "gto_retime_paths_convex_device")
 
     def retime_paths_device(self, B, Tp, paths, vmax, amax, n_cols=None, subdiv=2, n_samples=100, duration_out=None,
                             t_grid_out=None, sd_grid_out=None, q_out=None, qd_out=None, qdd_out=None, status_out=None,

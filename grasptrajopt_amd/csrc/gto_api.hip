@@ -2960,6 +2960,7 @@ struct RetimeNames {
   const char *fn, *T, *array;
 };
 static const RetimeNames RETIME_BATCH = {"gto_retime_batch", "T", "plans"}, RETIME_PATHS = {"gto_retime_paths", "Tp", "paths"};
+static const RetimeNames RETIME_CONVEX = {"gto_retime_paths_convex", "Tp", "paths"};
 
 static int retime_check(gto_handle* h, const RetimeNames& nm, int32_t B, int32_t Tp, const double* vmax, const double* amax,
                         int32_t subdiv, int32_t M, RetimeLimits& lim, RetimeDims& d) {
@@ -2982,12 +2983,23 @@ static int retime_check(gto_handle* h, const RetimeNames& nm, int32_t B, int32_t
   return GTO_OK;
 }
 
+// the options of the convex solve
+static int retime_convex_check(gto_handle* h, const RetimeNames& nm, const RetimeConvex& cv) {
+  const std::string f = std::string(nm.fn) + ": ";
+  if (!(cv.gap_tol > 0.0) || !std::isfinite(cv.gap_tol)) return fail(h, GTO_ERR_INVALID_ARG, f + "gap_tol must be finite and > 0");
+  if (cv.max_newton < 1) return fail(h, GTO_ERR_INVALID_ARG, f + "max_newton must be >= 1");
+  return GTO_OK;
+}
+
 static unsigned retime_blocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
-// the four launches of a checked call (d, lim: retime_check's); n_cols: DEVICE [B] or NULL (every path has Tp columns)
+// the four launches of a checked call (d, lim: retime_check's); n_cols: DEVICE [B] or NULL (every path has Tp columns).
+// cv: NULL for the greedy profile (k_retime_pass), else the convex solve's options (k_retime_convex in its place, which
+// also fills iters_out)
 static int retime_launch(gto_handle* h, const RetimeDims& d, const RetimeLimits& lim, const double* plans,
                          const int32_t* n_cols, double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out,
-                         double* qd_out, double* qdd_out, int32_t* status_out, void* stream) {
+                         double* qd_out, double* qdd_out, int32_t* status_out, void* stream,
+                         const RetimeConvex* cv = nullptr, int32_t* iters_out = nullptr) {
   int rc;
   const int B = d.B, M = d.M;
   HIPCHK(h, hipSetDevice(h->device));
@@ -3015,8 +3027,12 @@ static int retime_launch(gto_handle* h, const RetimeDims& d, const RetimeLimits&
                      h->rt_fac.as<const double>(), n_cols, d, S, flag);
   hipLaunchKernelGGL(k_retime_grid, dim3(retime_blocks((long long)B * N, 256)), dim3(256), 0, st, plans, S, flag, n_cols, lim,
                      d, P1, P2, cap);
-  hipLaunchKernelGGL(k_retime_pass, dim3(B), dim3(64), 0, st, P1, P2, cap, flag, n_cols, lim, d, X, Tg, stat,
-                     duration_out, t_grid_out, sd_grid_out, status_out);
+  if (cv)
+    hipLaunchKernelGGL(k_retime_convex, dim3(B), dim3(64), GTO_RT_LDS_ARRAYS * N * sizeof(double), st, P1, P2, cap, flag, n_cols, lim, d, *cv,
+                       X, Tg, stat, duration_out, t_grid_out, sd_grid_out, status_out, iters_out);
+  else
+    hipLaunchKernelGGL(k_retime_pass, dim3(B), dim3(64), 0, st, P1, P2, cap, flag, n_cols, lim, d, X, Tg, stat,
+                       duration_out, t_grid_out, sd_grid_out, status_out);
   if (q_out || qd_out || qdd_out)
     hipLaunchKernelGGL(k_retime_sample, dim3(retime_blocks((long long)B * M, 256)), dim3(256), 0, st, plans, S, X, Tg, stat,
                        n_cols, d, q_out, qd_out, qdd_out);
@@ -3028,28 +3044,31 @@ static int retime_launch(gto_handle* h, const RetimeDims& d, const RetimeLimits&
 static int retime_device(gto_handle* h, const RetimeNames& nm, int32_t B, int32_t Tp, const double* paths,
                          const int32_t* n_cols, const double* vmax, const double* amax, int32_t subdiv, int32_t M,
                          double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out, double* qd_out,
-                         double* qdd_out, int32_t* status_out, void* stream) {
+                         double* qdd_out, int32_t* status_out, void* stream, const RetimeConvex* cv = nullptr,
+                         int32_t* iters_out = nullptr) {
   if (!h) return GTO_ERR_INVALID_ARG;
   RetimeLimits lim = {};
   RetimeDims d = {};
   int rc = retime_check(h, nm, B, Tp, vmax, amax, subdiv, M, lim, d);
   if (rc) return rc;
+  if (cv && (rc = retime_convex_check(h, nm, *cv))) return rc;
   if (B == 0) return GTO_OK;
   if (!paths) return fail(h, GTO_ERR_INVALID_ARG, std::string(nm.fn) + ": null " + nm.array);
   return retime_launch(h, d, lim, paths, n_cols, duration_out, t_grid_out, sd_grid_out, q_out, qd_out, qdd_out, status_out,
-                       stream);
+                       stream, cv, iters_out);
 }
 
 // the host-pointer entry points: n_cols is a HOST array here (or NULL), checked before anything is staged
 static int retime_host(gto_handle* h, const RetimeNames& nm, int32_t B, int32_t Tp, const double* paths,
                        const int32_t* n_cols, const double* vmax, const double* amax, int32_t subdiv, int32_t M,
                        double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out, double* qd_out,
-                       double* qdd_out, int32_t* status_out) {
+                       double* qdd_out, int32_t* status_out, const RetimeConvex* cv = nullptr, int32_t* iters_out = nullptr) {
   if (!h) return GTO_ERR_INVALID_ARG;
   RetimeLimits lim = {};
   RetimeDims d = {};
   int rc = retime_check(h, nm, B, Tp, vmax, amax, subdiv, M, lim, d);
   if (rc) return rc;
+  if (cv && (rc = retime_convex_check(h, nm, *cv))) return rc;
   if (B == 0) return GTO_OK;
   if (!paths) return fail(h, GTO_ERR_INVALID_ARG, std::string(nm.fn) + ": null " + nm.array);
   if (n_cols)
@@ -3062,7 +3081,7 @@ static int retime_host(gto_handle* h, const RetimeNames& nm, int32_t B, int32_t 
   const double* d_paths;
   const int32_t* d_nc;
   double *d_dur, *d_t, *d_sd, *d_q, *d_qd, *d_qdd;
-  int32_t* d_st;
+  int32_t *d_st, *d_it;
   if ((rc = io.in(paths, nB * nd * T, &d_paths))) return rc;
   if ((rc = io.in(n_cols, nB, &d_nc))) return rc;
   if ((rc = io.out(duration_out, nB, &d_dur))) return rc;
@@ -3072,7 +3091,8 @@ static int retime_host(gto_handle* h, const RetimeNames& nm, int32_t B, int32_t 
   if ((rc = io.out(qd_out, nB * nM * nd, &d_qd))) return rc;
   if ((rc = io.out(qdd_out, nB * nM * nd, &d_qdd))) return rc;
   if ((rc = io.out(status_out, nB, &d_st))) return rc;
-  if ((rc = retime_launch(h, d, lim, d_paths, d_nc, d_dur, d_t, d_sd, d_q, d_qd, d_qdd, d_st, nullptr))) return rc;
+  if ((rc = io.out(iters_out, nB, &d_it))) return rc;
+  if ((rc = retime_launch(h, d, lim, d_paths, d_nc, d_dur, d_t, d_sd, d_q, d_qd, d_qdd, d_st, nullptr, cv, d_it))) return rc;
   return io.finish();
 }
 
@@ -3089,6 +3109,26 @@ int gto_retime_paths(gto_handle* h, int32_t B, int32_t Tp, const double* paths, 
                      double* sd_grid_out, double* q_out, double* qd_out, double* qdd_out, int32_t* status_out) {
   return retime_host(h, RETIME_PATHS, B, Tp, paths, n_cols, vmax, amax, subdiv, M, duration_out, t_grid_out,
                      sd_grid_out, q_out, qd_out, qdd_out, status_out);
+}
+
+// the grid's time optimum in place of the greedy profile (k_retime_convex in place of k_retime_pass)
+int gto_retime_paths_convex_device(gto_handle* h, int32_t B, int32_t Tp, const double* paths, const int32_t* n_cols,
+                                   const double* vmax, const double* amax, int32_t subdiv, int32_t M, double gap_tol,
+                                   int32_t max_newton, double* duration_out, double* t_grid_out, double* sd_grid_out,
+                                   double* q_out, double* qd_out, double* qdd_out, int32_t* status_out, int32_t* iters_out,
+                                   void* stream) {
+  const RetimeConvex cv = {gap_tol, max_newton};
+  return retime_device(h, RETIME_CONVEX, B, Tp, paths, n_cols, vmax, amax, subdiv, M, duration_out, t_grid_out,
+                       sd_grid_out, q_out, qd_out, qdd_out, status_out, stream, &cv, iters_out);
+}
+
+int gto_retime_paths_convex(gto_handle* h, int32_t B, int32_t Tp, const double* paths, const int32_t* n_cols,
+                            const double* vmax, const double* amax, int32_t subdiv, int32_t M, double gap_tol,
+                            int32_t max_newton, double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out,
+                            double* qd_out, double* qdd_out, int32_t* status_out, int32_t* iters_out) {
+  const RetimeConvex cv = {gap_tol, max_newton};
+  return retime_host(h, RETIME_CONVEX, B, Tp, paths, n_cols, vmax, amax, subdiv, M, duration_out, t_grid_out,
+                     sd_grid_out, q_out, qd_out, qdd_out, status_out, &cv, iters_out);
 }
 
 // plans of the handle's horizon: gto_retime_paths with Tp = T and every column used

@@ -14,6 +14,8 @@
 //                     Each stage is a two-variable LP solved exactly: every upper bound on u (a line in x) is paired with
 //                     every lower bound, and the pairs are spread over the lanes and reduced by a cross-lane min.  One
 //                     lane per plan (every pair in one lane) measured 0.6-0.1x of this rate and was dropped.
+//   k_retime_convex   one wave per plan, in place of k_retime_pass for gto_retime_paths_convex[_device]: the time optimum of
+//                     the same grid constraints by a log-barrier Newton method (below, beside the pass)
 //   k_retime_sample   one lane per (plan, sample): binary search over the gridpoint times, evaluation on the spline
 // Rows are laid out for the largest count: paths and slopes [B][ndof][Tp], grid arrays [B][Nmax], Nmax = subdiv (Tp-1) + 1.
 // Nothing a path's arithmetic uses depends on Tp or on its place in the batch.
@@ -299,6 +301,285 @@ __global__ __launch_bounds__(64) void k_retime_pass(const double* __restrict__ P
     stat[b] = s;
     if (duration_out) duration_out[b] = t;
     if (status_out) status_out[b] = s;
+  }
+}
+
+// ------------------------------------------------------------------ the grid's time optimum (gto_retime_paths_convex)
+// k_retime_convex stands where k_retime_pass stands: the same inputs from k_retime_spline / k_retime_grid, the same X, Tg
+// and stat for k_retime_sample.  It minimises T(x) = sum_i 2 Delta / (sqrt x_i + sqrt x_{i+1}) over x_1 .. x_{N-2}
+// (x_0 = x_{N-1} = 0) under 0 <= x_i <= xcap_i and, for every line (alpha, beta) of gridpoint i <= N-2,
+// |r| <= alpha with r = c (x_{i+1} - x_i) - beta x_i, c = (N-1)/2, by a log-barrier path-following Newton method:
+//   F_mu(x) = T(x) - mu sum_rows log(slack);  every term couples x_i and x_{i+1} only, so the Hessian is symmetric
+//   tridiagonal and positive definite.  A step: assemble (one lane per variable, which gathers the rows of the segments on
+//   both of its sides, so that nothing is added across lanes), factor and solve, the largest step that stays strictly inside
+//   (wave-min), backtracking on F_mu (wave-sums in a fixed order: a plan's result does not depend on its batch).
+//   lam^2 = g' H^-1 g / mu is the Newton decrement of F_mu / mu.  At lam < GTO_RT_CENTRED the iterate counts as centred:
+//   the gap bound mu (m + (lam + sqrt m) lam / (1 - lam)), m rows (m mu at the centre itself), is compared with
+//   gap_tol T(x), and either the solve ends or mu shrinks by GTO_RT_SHRINK.
+#define GTO_RT_CENTRED 0.25
+#define GTO_RT_SHRINK 0.1
+#define GTO_RT_ARMIJO 1e-4
+#define GTO_RT_BACKTRACKS 60
+
+#define GTO_RT_LDS_ARRAYS 5  // LDS arrays of Nmax doubles each: 40 KB at Nmax = 1024
+
+struct RetimeConvex {
+  double gap_tol;  // finite, > 0
+  int max_newton;  // >= 1
+};
+
+__device__ __forceinline__ double rt_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// T and the barrier sum phi = -sum log(slack) at y = x + eta dx (F_mu = T + mu phi); T = inf where y is not strictly
+// inside.  Gridpoint i owns its segment's time, its own two box rows and its lines.
+__device__ __forceinline__ void rt_convex_eval(const double* x, const double* dx, double eta, const double* al,
+                                               const double* be, const double* cap, int N, int ndof, int lane, double& T,
+                                               double& phi) {
+  const double c = 0.5 * (double)(N - 1), w = 2.0 / (double)(N - 1);
+  double Tl = 0.0, ph = 0.0;
+  bool in = true;
+  for (int i = lane; i < N - 1; i += 64) {
+    const double yi = fma(eta, dx[i], x[i]), yn = fma(eta, dx[i + 1], x[i + 1]);
+    Tl += w / (sqrt(yi) + sqrt(yn));
+    if (i >= 1) {
+      in = in && yi > 0.0;
+      ph -= log(yi);
+      const double cp = cap[i];
+      if (cp != INFINITY) {
+        in = in && cp - yi > 0.0;
+        ph -= log(cp - yi);
+      }
+    }
+    for (int j = 0; j < ndof; ++j) {
+      const double a = al[(long long)i * ndof + j];
+      if (a == INFINITY) continue;
+      const double r = c * (yn - yi) - be[(long long)i * ndof + j] * yi;
+      in = in && a - r > 0.0 && a + r > 0.0;
+      ph -= log(a - r) + log(a + r);
+    }
+  }
+  T = rt_wave_sum(in ? Tl : INFINITY);
+  phi = rt_wave_sum(ph);
+}
+
+// H dx = -g for variables 1 .. n, H = tridiag(e, dg, e) (e[v] couples v and v+1).  dg and g are overwritten by the pivots
+// and the reduced right-hand side of the L D L' factorisation, which is what the Newton decrement sums: g' H^-1 g =
+// sum g[v]^2 / dg[v].
+__device__ __forceinline__ void rt_tridiag_serial(double* dg, const double* e, double* g, double* dx, int n, int lane) {
+  if (lane == 0) {
+    double dp = dg[1], gp = g[1];
+    for (int v = 2; v <= n; ++v) {
+      const double ev = e[v - 1], m = ev / dp;
+      dp = dg[v] - m * ev;
+      gp = g[v] - m * gp;
+      dg[v] = dp, g[v] = gp;
+    }
+    double s = -gp / dp;
+    dx[n] = s;
+    for (int v = n - 1; v >= 1; --v) {
+      s = (-g[v] - e[v] * s) / dg[v];
+      dx[v] = s;
+    }
+  }
+}
+
+// One wave per plan.  al / be: p1 / p2 of k_retime_grid [B][Nmax][ndof] on entry; the kernel turns them into the lines
+// (alpha, beta) of rt_line in place, once, and reads those in every Newton step (alpha = inf: no line).  LDS: five arrays of
+// Nmax doubles (x, gradient, diagonal, off-diagonal, step; GTO_RT_LDS_ARRAYS), passed as the launch's dynamic size.
+// stat: what k_retime_sample asks, "has a profile" (GTO_STATUS_CONVERGED for GTO_STATUS_MAX_ITER too, whose feasible
+// profile is sampled); status_out: the status of the contract.
+__global__ __launch_bounds__(64) void k_retime_convex(double* __restrict__ al, double* __restrict__ be,
+                                                      const double* __restrict__ xcap, const int32_t* __restrict__ flag,
+                                                      const int32_t* __restrict__ n_cols, RetimeLimits lim, RetimeDims d,
+                                                      RetimeConvex cv, double* __restrict__ X, double* __restrict__ Tg,
+                                                      int32_t* __restrict__ stat, double* __restrict__ duration_out,
+                                                      double* __restrict__ t_out, double* __restrict__ sd_out,
+                                                      int32_t* __restrict__ status_out, int32_t* __restrict__ iters_out) {
+  extern __shared__ double rt_lds[];
+  double *x = rt_lds, *g = x + d.Nmax, *dg = g + d.Nmax, *e = dg + d.Nmax, *dx = e + d.Nmax;
+  const long long b = blockIdx.x;
+  const int lane = threadIdx.x, ndof = d.ndof;
+  const int N = d.subdiv * (rt_cols(n_cols, b, d.Tp) - 1) + 1;  // a bad count is flagged: N is not used then
+  const int f = lane < ndof ? flag[b * ndof + lane] : GTO_RT_CONST;
+  const bool bad = __ballot(f == GTO_RT_NONFINITE) != 0, moving = __ballot(f == GTO_RT_MOVING) != 0;
+  const long long o = b * d.Nmax;
+  const double w = 2.0 / (double)(N - 1), c = 0.5 * (double)(N - 1);
+  const int n = N - 2;  // variables 1 .. n
+  al += o * ndof, be += o * ndof;
+  const double* cap = xcap + o;
+  int status = GTO_STATUS_CONVERGED, it = 0;
+  if (bad) status = GTO_STATUS_NUMERICAL;
+  for (int i = lane; i < N && !bad; i += 64) x[i] = 0.0, dx[i] = 0.0;
+  __syncthreads();
+  if (!bad && moving && n >= 1) {
+    // the lines, once per plan
+    for (int k = lane; k < (N - 1) * ndof; k += 64) {
+      double a, bt;
+      rt_line(al[k], be[k], lim.amax[k % ndof], a, bt);
+      al[k] = a, be[k] = bt;
+    }
+    __syncthreads();
+    // start: x = eps 1, eps half the largest value at which every row holds; m rows
+    double top = INFINITY;
+    int rows = 0;
+    for (int i = lane; i < N - 1; i += 64) {
+      if (i >= 1) {
+        top = fmin(top, cap[i]);
+        rows += cap[i] != INFINITY ? 2 : 1;
+      }
+      const double in0 = i >= 1 ? 1.0 : 0.0, in1 = i + 1 <= n ? 1.0 : 0.0;
+      for (int j = 0; j < ndof; ++j) {
+        const double a = al[(long long)i * ndof + j];
+        if (a == INFINITY) continue;
+        const double k = fabs(c * (in1 - in0) - be[(long long)i * ndof + j] * in0);
+        if (k > 0.0) top = fmin(top, a / k);
+        rows += 2;
+      }
+    }
+    const double eps = 0.5 * rt_wave_min(top), m = rt_wave_sum((double)rows);
+    for (int v = 1 + lane; v <= n; v += 64) x[v] = eps;
+    __syncthreads();
+    double T, phi;
+    rt_convex_eval(x, dx, 0.0, al, be, cap, N, ndof, lane, T, phi);
+    double mu = T / m;
+    if (!(eps > 0.0) || !isfinite(T) || !isfinite(phi)) status = GTO_STATUS_NUMERICAL;
+    while (status == GTO_STATUS_CONVERGED) {
+      // gradient, diagonal and off-diagonal of F_mu: variable v gathers the segments v-1 and v
+      for (int v = 1 + lane; v <= n; v += 64) {
+        const double xm = x[v - 1], x0 = x[v], xp = x[v + 1];
+        const double q = sqrt(x0), S1 = sqrt(xm) + q, S2 = q + sqrt(xp), q2 = x0, q3 = x0 * q;
+        const double i1 = 1.0 / (S1 * S1), i2 = 1.0 / (S2 * S2);
+        double gv = -w * (i1 + i2) / (2.0 * q);
+        double dv = w * ((i1 + i2) / (4.0 * q3) + (i1 / S1 + i2 / S2) / (2.0 * q2));
+        double ev = v < n ? w * i2 / (2.0 * q * sqrt(xp) * S2) : 0.0;
+        gv -= mu / x0;
+        dv += mu / (x0 * x0);
+        const double cp = cap[v];
+        if (cp != INFINITY) {
+          const double is = 1.0 / (cp - x0);
+          gv += mu * is;
+          dv += mu * is * is;
+        }
+        for (int j = 0; j < ndof; ++j) {  // the lines of gridpoint v-1: r = c (x_v - x_{v-1}) - beta x_{v-1}
+          const double a = al[(long long)(v - 1) * ndof + j];
+          if (a == INFINITY) continue;
+          const double r = c * (x0 - xm) - be[(long long)(v - 1) * ndof + j] * xm;
+          const double ip = 1.0 / (a - r), im = 1.0 / (a + r);
+          gv += mu * c * (ip - im);
+          dv += mu * c * c * (ip * ip + im * im);
+        }
+        for (int j = 0; j < ndof; ++j) {  // the lines of gridpoint v: r = c (x_{v+1} - x_v) - beta x_v
+          const double a = al[(long long)v * ndof + j];
+          if (a == INFINITY) continue;
+          const double bt = be[(long long)v * ndof + j], k = -(c + bt);
+          const double r = c * (xp - x0) - bt * x0;
+          const double ip = 1.0 / (a - r), im = 1.0 / (a + r), hh = ip * ip + im * im;
+          gv += mu * k * (ip - im);
+          dv += mu * k * k * hh;
+          if (v < n) ev += mu * k * c * hh;
+        }
+        g[v] = gv, dg[v] = dv, e[v] = ev;
+      }
+      __syncthreads();
+      double dec = 0.0;
+      rt_tridiag_serial(dg, e, g, dx, n, lane);
+      __syncthreads();
+      for (int v = 1 + lane; v <= n; v += 64) dec += g[v] * g[v] / dg[v];
+      dec = rt_wave_sum(dec);  // g' H^-1 g = -(g . dx)
+      const double lam = sqrt(dec / mu);
+      if (!isfinite(lam) || !(mu > 0.0)) {
+        status = GTO_STATUS_NUMERICAL;
+        break;
+      }
+      if (lam < GTO_RT_CENTRED) {
+        if (mu * (m + (lam + sqrt(m)) * lam / (1.0 - lam)) <= cv.gap_tol * T) break;
+        mu *= GTO_RT_SHRINK;  // the next weight, from the same x: not a Newton step
+        continue;
+      }
+      if (it == cv.max_newton) {
+        status = GTO_STATUS_MAX_ITER;
+        break;
+      }
+      // the largest step that stays strictly inside
+      double room = INFINITY;
+      for (int i = lane; i < N - 1; i += 64) {
+        const double xi = x[i], xn = x[i + 1], di = dx[i], dn = dx[i + 1];
+        if (i >= 1) {
+          if (di < 0.0) room = fmin(room, xi / -di);
+          if (di > 0.0 && cap[i] != INFINITY) room = fmin(room, (cap[i] - xi) / di);
+        }
+        for (int j = 0; j < ndof; ++j) {
+          const double a = al[(long long)i * ndof + j];
+          if (a == INFINITY) continue;
+          const double bt = be[(long long)i * ndof + j];
+          const double r = c * (xn - xi) - bt * xi, dr = c * (dn - di) - bt * di;
+          if (dr > 0.0) room = fmin(room, (a - r) / dr);
+          if (dr < 0.0) room = fmin(room, (a + r) / -dr);
+        }
+      }
+      double eta = fmin(1.0, 0.99 * rt_wave_min(room));
+      // backtracking on F_mu; a difference below the round-off of F_mu counts as a decrease
+      const double F0 = T + mu * phi;
+      for (int k = 0; k < GTO_RT_BACKTRACKS; ++k, eta *= 0.5) {
+        double Tn, phin;
+        rt_convex_eval(x, dx, eta, al, be, cap, N, ndof, lane, Tn, phin);
+        if (Tn + mu * phin <= F0 - GTO_RT_ARMIJO * eta * dec + 4e-16 * fabs(F0)) {
+          __syncthreads();
+          for (int v = 1 + lane; v <= n; v += 64) x[v] = fma(eta, dx[v], x[v]);
+          T = Tn, phi = phin;
+          break;
+        }
+      }
+      __syncthreads();
+      ++it;
+    }
+  }
+  // times and outputs
+  if (status == GTO_STATUS_NUMERICAL) {
+    for (int i = lane; i < d.Nmax; i += 64) {
+      X[o + i] = NAN, Tg[o + i] = NAN;
+      if (t_out) t_out[o + i] = NAN;
+      if (sd_out) sd_out[o + i] = NAN;
+    }
+    if (lane == 0) {
+      stat[b] = GTO_STATUS_NUMERICAL;
+      if (duration_out) duration_out[b] = NAN;
+      if (status_out) status_out[b] = GTO_STATUS_NUMERICAL;
+      if (iters_out) iters_out[b] = it;
+    }
+    return;
+  }
+  __syncthreads();
+  double t = 0.0;
+  if (lane == 0) {
+    double xi = 0.0;
+    X[o] = 0.0, Tg[o] = 0.0;
+    if (t_out) t_out[o] = 0.0;
+    if (sd_out) sd_out[o] = 0.0;
+    for (int i = 1; i < N; ++i) {
+      const double xn = x[i];
+      if (moving) t += w / (sqrt(xi) + sqrt(xn));
+      xi = xn;
+      X[o + i] = xn, Tg[o + i] = t;
+      if (t_out) t_out[o + i] = t;
+      if (sd_out) sd_out[o + i] = sqrt(xn);
+    }
+  }
+  t = __shfl(t, 0, 64);
+  for (int i = N + lane; i < d.Nmax; i += 64) {
+    if (t_out) t_out[o + i] = t;
+    if (sd_out) sd_out[o + i] = 0.0;
+  }
+  if (lane == 0) {
+    const bool ok = isfinite(t);  // N = 2 with a moving joint: no variable, both ends rest, the one segment takes forever
+    stat[b] = ok ? GTO_STATUS_CONVERGED : GTO_STATUS_NUMERICAL;
+    if (duration_out) duration_out[b] = t;
+    if (status_out) status_out[b] = ok ? status : GTO_STATUS_NUMERICAL;
+    if (iters_out) iters_out[b] = it;
   }
 }
 

@@ -133,7 +133,9 @@ class GraspChain:
         goes to (the shelf driver solves IK to ``RT @ standoff`` and plans to ``RT``, :256-259); n_grasps (B,) how many rows
         of an object count; fields: see ``_scene_ids``; base_position (3,) or (B, 3).  observation: an
         ``observation.Observation`` to count the solved plans' surface points inside (gto_check_plans_device).  retime: a
-        dict ``vmax, amax[, subdiv, n_samples]`` to retime the solved plans (gto_retime_batch_device).  retrieve: a dict
+        dict ``vmax, amax[, subdiv, n_samples, profile, gap_tol, max_newton]`` to retime the solved plans
+        (gto_retime_batch_device; ``profile="convex"``: the grid's time optimum, gto_retime_paths_convex_device for the plans
+        and the retrieve path alike, which adds retime_iters / retrieve_retime_iters (B,)).  retrieve: a dict
         ``mode`` ("lift" | "reverse") ``[, distance, steps, direction, closed_joints, closed_value, collide]`` for the motion
         after the grasp (see ``retrieve_spec``), enqueued behind the solve (with n_seeds > 1 behind the selection) on the
         chain's stream; the result gains retrieve_path (B, ndof, steps + 1 | n), retrieve_reached (B,) (lift: the leading
@@ -300,6 +302,11 @@ class GraspChain:
         f64, i32, u8 = torch.float64, torch.int32, torch.uint8
         res = SimpleNamespace()
         rs = None if retrieve is None else self.retrieve_spec(retrieve)
+        convex = None  # (gap_tol, max_newton) when the retime dict asks for the grid's time optimum
+        if retime is not None and "profile" in retime:
+            from ._capi import retime_profile
+            prof = retime_profile(retime["profile"], retime.get("gap_tol", 1e-8), retime.get("max_newton"))
+            convex = prof[1:] if prof[0] == "convex" else None
         with torch.cuda.stream(self.stream):
             st = self.stream.cuda_stream
             d_sid, d_qc, d_base = self._up("sid", sid, np.int32), self._up("qc", qc, np.float64), self._up("base", base, np.float64)
@@ -418,9 +425,16 @@ class GraspChain:
                                                       held_label=ptr(held.label), base_pos=base, stream=st)
                 if retime is not None:
                     d_dur, d_rst = self._dev("durations", (B,), f64), self._dev("retime_status", (B,), i32)
-                    h.retime_batch_device(B, d_Q.data_ptr(), retime["vmax"], retime["amax"], int(retime.get("subdiv", 2)),
-                                          int(retime.get("n_samples", 100)), duration_out=d_dur.data_ptr(),
-                                          status_out=d_rst.data_ptr(), stream=st)
+                    if convex is None:
+                        h.retime_batch_device(B, d_Q.data_ptr(), retime["vmax"], retime["amax"], int(retime.get("subdiv", 2)),
+                                              int(retime.get("n_samples", 100)), duration_out=d_dur.data_ptr(),
+                                              status_out=d_rst.data_ptr(), stream=st)
+                    else:  # the plans are the Tp = T case of the paths call
+                        d_rit = self._dev("retime_iters", (B,), i32)
+                        h.retime_paths_convex_device(B, T, d_Q.data_ptr(), retime["vmax"], retime["amax"],
+                                                     subdiv=int(retime.get("subdiv", 2)), n_samples=int(retime.get("n_samples", 100)),
+                                                     gap_tol=convex[0], max_newton=convex[1], duration_out=d_dur.data_ptr(),
+                                                     status_out=d_rst.data_ptr(), iters_out=d_rit.data_ptr(), stream=st)
                     if retrieve is not None:  # the retrieve path on the same clock rules, behind the retrieve stage
                         sub, ns = int(retime.get("subdiv", 2)), int(retime.get("n_samples", 100))
                         d_nc = None
@@ -431,11 +445,18 @@ class GraspChain:
                         d_rsamp = [None] * 3
                         if retime.get("retrieve_samples", False):
                             d_rsamp = [self._dev("retrieve_" + k, (B, ns, ndof), f64) for k in ("q", "qd", "qdd")]
-                        h.retime_paths_device(B, cols, d_rp.data_ptr(), retime["vmax"], retime["amax"],
-                                              n_cols=None if d_nc is None else d_nc.data_ptr(), subdiv=sub, n_samples=ns,
-                                              duration_out=d_rdur.data_ptr(), status_out=d_rrst.data_ptr(),
-                                              **{k + "_out": None if v is None else v.data_ptr()
-                                                 for k, v in zip(("q", "qd", "qdd"), d_rsamp)}, stream=st)
+                        outs = dict(duration_out=d_rdur.data_ptr(), status_out=d_rrst.data_ptr(),
+                                    **{k + "_out": None if v is None else v.data_ptr() for k, v in zip(("q", "qd", "qdd"), d_rsamp)})
+                        if convex is None:
+                            h.retime_paths_device(B, cols, d_rp.data_ptr(), retime["vmax"], retime["amax"],
+                                                  n_cols=None if d_nc is None else d_nc.data_ptr(), subdiv=sub, n_samples=ns,
+                                                  **outs, stream=st)
+                        else:
+                            d_rrit = self._dev("retrieve_retime_iters", (B,), i32)
+                            h.retime_paths_convex_device(B, cols, d_rp.data_ptr(), retime["vmax"], retime["amax"],
+                                                         n_cols=None if d_nc is None else d_nc.data_ptr(), subdiv=sub, n_samples=ns,
+                                                         gap_tol=convex[0], max_newton=convex[1], iters_out=d_rrit.data_ptr(),
+                                                         **outs, stream=st)
             out = dict(plans=d_Q, dQ=d_dQ, cost=d_f, iters=d_it, status=d_stat, n_accepted=d_nacc, seed_index=d_si, seed_cost=d_sc,
                        seed_dist=d_sd, q_solutions=d_q, err_pos=d_ep, err_rot=d_er, ik_cost=d_ic, ik_iters=d_ikit, ik_status=d_ikst,
                        accept=d_acc)
@@ -444,6 +465,8 @@ class GraspChain:
                 out["counts"] = d_cnt
             if N and retime is not None:
                 out["durations"], out["retime_status"] = d_dur, d_rst
+                if convex is not None:
+                    out["retime_iters"] = d_rit
             if N and retrieve is not None:
                 out["retrieve_path"] = d_rp
                 if lift:
@@ -454,6 +477,8 @@ class GraspChain:
                         out["retrieve_held_counts"] = d_hcnt
                 if retime is not None:
                     out["retrieve_durations"], out["retrieve_retime_status"] = d_rdur, d_rrst
+                    if convex is not None:
+                        out["retrieve_retime_iters"] = d_rrit
                     out.update({"retrieve_" + k: v for k, v in zip(("q", "qd", "qdd"), d_rsamp) if v is not None})
             if multi:  # (cost, iters, status and counts hold every slot's until the chosen slot's are picked below)
                 out.update(best_slot=d_best, plan_class=d_cls, slot_class=d_scls, slot_goal_index=d_gi, slot_err_pos=d_pep,

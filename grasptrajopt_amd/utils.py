@@ -229,32 +229,48 @@ def _retime_handle(robot, T: int):
     return robot.solver_handle(ln, ln, o, role="util")
 
 
-def retime_plans(robot, plans, vlim=None, alim=0.5, subdiv: int = 2, n_samples: int = 100):
+def retime_plans(robot, plans, vlim=None, alim=0.5, subdiv: int = 2, n_samples: int = 100, profile: str = "greedy",
+                 gap_tol: float = 1e-8, max_newton=None):
     """Time-optimal retiming of plans (B, ndof, T) or one plan (ndof, T) on the GPU (gto_retime_batch, include/gto_solver.h):
     not-a-knot cubic spline through the waypoints on linspace(0, 1, T), joint velocity limits ``vlim`` (default: the URDF's,
     ``robot.velocity_actuated_joint_limits``) and acceleration limits ``alim`` (default 0.5 rad/s^2, gto/utils.py:295),
     TOPP-RA's discretisation on subdiv (T-1) + 1 gridpoints, constant acceleration between them.  Returns a dict of
     duration (B,), t_grid (B, N), sd_grid (B, N), q / qd / qdd (B, n_samples, ndof) at linspace(0, duration, n_samples)
-    and status (B,)."""
+    and status (B,).  profile "greedy" (the default) is TOPP-RA's forward pass; "convex" is the time optimum of the same
+    grid constraints, solved per plan to the certified relative gap ``gap_tol`` in at most ``max_newton`` Newton steps
+    (gto_retime_paths_convex with Tp = T), and adds iters (B,) to the dict."""
+    from . import _capi
+    profile, gap_tol, max_newton = _capi.retime_profile(profile, gap_tol, max_newton)
     plans = np.asarray(plans, dtype=np.float64)
     if plans.ndim == 2:
         plans = plans[None]
     if vlim is None:
         vlim = np.asarray(robot.velocity_actuated_joint_limits.toarray()).ravel()
-    return _retime_handle(robot, plans.shape[2]).retime_batch(plans, vlim, alim, subdiv=subdiv, n_samples=n_samples)
+    h = _retime_handle(robot, plans.shape[2])
+    if profile == "convex":
+        return h.retime_paths_convex(plans, vlim, alim, subdiv=subdiv, n_samples=n_samples, gap_tol=gap_tol, max_newton=max_newton)
+    return h.retime_batch(plans, vlim, alim, subdiv=subdiv, n_samples=n_samples)
 
 
-def retime_paths(robot, paths, n_cols=None, vlim=None, alim=0.5, subdiv: int = 2, n_samples: int = 100):
+def retime_paths(robot, paths, n_cols=None, vlim=None, alim=0.5, subdiv: int = 2, n_samples: int = 100,
+                 profile: str = "greedy", gap_tol: float = 1e-8, max_newton=None):
     """``retime_plans`` for paths (B, ndof, Tp) or one path (ndof, Tp) of any length Tp >= 2 (gto_retime_paths,
     include/gto_solver.h): a retrieve path of ``GTOPlanner.retrieve_path``, for one.  n_cols (B,) int or None: path b is its
     first n_cols[b] columns and the rest is ignored (a lift up to the step it reached: ``reached + 1``); t_grid and sd_grid
-    are (B, subdiv (Tp-1) + 1) and hold the duration and 0 past a path's own gridpoints.  One handle serves every Tp."""
+    are (B, subdiv (Tp-1) + 1) and hold the duration and 0 past a path's own gridpoints.  One handle serves every Tp.
+    profile, gap_tol, max_newton: as in ``retime_plans`` (gto_retime_paths_convex)."""
+    from . import _capi
+    profile, gap_tol, max_newton = _capi.retime_profile(profile, gap_tol, max_newton)
     paths = np.asarray(paths, dtype=np.float64)
     if paths.ndim == 2:
         paths = paths[None]
     if vlim is None:
         vlim = np.asarray(robot.velocity_actuated_joint_limits.toarray()).ravel()
-    return _retime_handle(robot, 4).retime_paths(paths, vlim, alim, n_cols=n_cols, subdiv=subdiv, n_samples=n_samples)
+    h = _retime_handle(robot, 4)
+    if profile == "convex":
+        return h.retime_paths_convex(paths, vlim, alim, n_cols=n_cols, subdiv=subdiv, n_samples=n_samples, gap_tol=gap_tol,
+                                     max_newton=max_newton)
+    return h.retime_paths(paths, vlim, alim, n_cols=n_cols, subdiv=subdiv, n_samples=n_samples)
 
 
 def convert_plan_to_trajectory_toppra(robot, plan, is_show: bool = False):

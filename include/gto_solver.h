@@ -992,6 +992,42 @@ int gto_retime_paths_device(gto_handle* h, int32_t B, int32_t Tp, const double* 
                             const double* vmax /*HOST*/, const double* amax /*HOST*/, int32_t subdiv, int32_t M,
                             double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out, double* qd_out,
                             double* qdd_out, int32_t* status_out, void* stream);
+/*
+ * Retiming to the grid's time optimum: the contract of gto_retime_paths / gto_retime_paths_device with steps 3 and 4 (the
+ * controllable sets and the greedy forward pass, which is not pointwise maximal on a fixed grid and can bring a profile to
+ * rest) replaced by a convex program per path.  Additions (the ABI number stays).  For path b with N = subdiv (C_b-1) + 1
+ * gridpoints, Delta = 1/(N-1), variables x_1 .. x_{N-2} and x_0 = x_{N-1} = 0:
+ *     minimise    T(x) = sum_{i=0}^{N-2} 2 Delta / (sqrt x_i + sqrt x_{i+1})        (convex in x)
+ *     subject to  0 <= x_i <= xcap_i, xcap_i the bound of step 2 that does not involve u, and for every gridpoint
+ *                 i <= N-2 and every moving joint j whose amax_j/|p1_j| and p2_j/p1_j are finite there (its line),
+ *                 -alpha + beta x_i <= (x_{i+1} - x_i)(N-1)/2 <= alpha + beta x_i,  alpha = amax_j/|p1_j|, beta = -p2_j/p1_j
+ * (exactly the constraints of steps 1 and 2; a joint without a line is in xcap_i).  The profile returned is a feasible x
+ * with T(x) <= (1 + gap_tol) T*, T* the optimum, found by a log-barrier path-following Newton method that stops when its
+ * bound on T(x) - T* falls to gap_tol T(x).  Steps 5 and 6 follow unchanged on this x.
+ *   gap_tol     finite, > 0 (GTO_ERR_INVALID_ARG otherwise); 1e-8 is the Python layers' default.
+ *   max_newton  >= 1 (GTO_ERR_INVALID_ARG otherwise): the cap on Newton steps per path.
+ *   iters_out   [B] or NULL: Newton steps taken (0 for a path that needs no solve).
+ *   status_out  GTO_STATUS_CONVERGED: the gap is certified.  GTO_STATUS_MAX_ITER: the cap was hit; the profile is still
+ *               feasible (every iterate is strictly inside) and its times and samples are valid, the gap is not certified.
+ *               GTO_STATUS_NUMERICAL: a non-finite entry or a wild count (NaN outputs), N_b == 2 (no variable: both ends
+ *               rest, duration inf, NaN samples, as in gto_retime_paths), or a non-finite iterate (NaN outputs).
+ * The rule for a profile that rests over a whole segment is not applied: resting costs infinite time, so an optimal
+ * profile does not.  Everything else is gto_retime_paths': the argument checks, HOST vmax / amax, n_cols HOST
+ * (gto_retime_paths_convex) or DEVICE with the wild-count rule (gto_retime_paths_convex_device), the fill past a path's own
+ * gridpoints, C_b == 1 and all-equal waypoints (duration 0, no solve), results bit for bit the same in any batch, at any
+ * position in it and under any Tp >= C_b, the one factor table per handle (shared with the other retime calls), stream order
+ * with no synchronisation after a handle's first retime call.  The greedy entry points are unchanged and share the
+ * workspace: calls on one handle go to one stream, or the caller orders them.
+ */
+int gto_retime_paths_convex(gto_handle* h, int32_t B, int32_t Tp, const double* paths, const int32_t* n_cols,
+                            const double* vmax, const double* amax, int32_t subdiv, int32_t M, double gap_tol,
+                            int32_t max_newton, double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out,
+                            double* qd_out, double* qdd_out, int32_t* status_out, int32_t* iters_out);
+int gto_retime_paths_convex_device(gto_handle* h, int32_t B, int32_t Tp, const double* paths, const int32_t* n_cols /*DEVICE*/,
+                                   const double* vmax /*HOST*/, const double* amax /*HOST*/, int32_t subdiv, int32_t M,
+                                   double gap_tol, int32_t max_newton, double* duration_out, double* t_grid_out,
+                                   double* sd_grid_out, double* q_out, double* qd_out, double* qdd_out, int32_t* status_out,
+                                   int32_t* iters_out, void* stream);
 
 #ifdef __cplusplus
 }
