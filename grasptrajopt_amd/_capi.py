@@ -120,6 +120,8 @@ def _prototypes():
         "gto_eval_fk": (I, [V, I32, _pd, _pd]),
         "gto_eval_points": (I, [V, I32, I32, _pd, _pd, I32, _pd, _pi, _pd, _pd]),
         "gto_eval_points_hessian": (I, [V, I32, I32, _pd, _pd, I32, _pd]),
+        "gto_set_link_inertials": (I, [V, _pd, _pd, _pd, _pd]),
+        "gto_inverse_dynamics": (I, [V, I32, _pd, _pd, _pd, _pd, _pd, _pd, _pd]),
         "gto_eval_objective": (I, [V, I32, I32, _pi, _pd, _pi, _pd, _pd, _pd, _pd, _pd, _pd, _pi]),
         "gto_eval_obstacle_normal_eq": (I, [V, I32, _pi, _pd, _pd, _pd, _pd, _pd]),
         "gto_eval_base_objective": (I, [V, I32, I32, _pi, _pd, _pd, _pd, D, _pd]),
@@ -186,6 +188,30 @@ def retime_profile(profile="greedy", gap_tol=1e-8, max_newton=None):
         raise ValueError(f"retime: max_newton must be >= 1, got {max_newton}")
     return profile, gap_tol, max_newton
 EXPORTED_SYMBOLS = tuple(PROTOTYPES)
+
+
+def payload_arrays(payload, n):
+    """(mass (n,), com (n, 3) or None, inertia (n, 6) or None) of a payload request: None, or a dict with "mass" and
+    optionally "com" and "inertia", each given once for the call or once per row.  (None, None, None) without a payload."""
+    if payload is None:
+        return None, None, None
+    unknown = set(payload) - {"mass", "com", "inertia"}
+    if unknown or "mass" not in payload:
+        raise ValueError(f"payload: a dict with 'mass' and optionally 'com', 'inertia' expected, got keys {sorted(payload)}")
+
+    def rows(x, width):
+        a = _f64(x)
+        a = a.reshape(-1, width) if a.size != width or a.ndim > 1 else a.reshape(1, width)
+        if a.shape[0] not in (1, n):
+            raise ValueError(f"payload: one value or {n} rows of {width} expected, got shape {np.shape(x)}")
+        return _f64(np.broadcast_to(a, (n, width)))
+
+    mass = rows(payload["mass"], 1).reshape(n)
+    if not (np.isfinite(mass).all() and (mass >= 0).all()):
+        raise ValueError("payload: mass must be finite and >= 0")
+    com = None if payload.get("com") is None else rows(payload["com"], 3)
+    inertia = None if payload.get("inertia") is None else rows(payload["inertia"], 6)
+    return mass, com, inertia
 
 
 def pack_robot_desc(desc: RobotDesc, link_ee: str, link_gripper: str,
@@ -337,6 +363,8 @@ class SolverHandle:
         self._h = h
         self.scenes = {}
         self._scene_gen = {}  # scene id -> number of times it was written (set_scene, scene_from_depth, share_scene, drop_scene)
+        self._inertials = None  # the description's arrays this handle uploaded last (sync_link_inertials)
+        self.sync_link_inertials()
 
     # -------------------------------------------------------------- helpers
     def _check(self, rc: int, what: str):
@@ -565,6 +593,41 @@ class SolverHandle:
         q = _f64(q).reshape(-1, self.desc.ndof)
         out = np.empty((q.shape[0], self.desc.n_frames, 4, 4))
         self._check(self.lib.gto_eval_fk(self._h, q.shape[0], _p(q, _pd), _p(out, _pd)), "gto_eval_fk")
+        return out
+
+    def set_link_inertials(self, mass, com, inertia, gravity=None):
+        """The inertials of the handle's frames (gto_set_link_inertials): mass (F,), com (F, 3), inertia (F, 6) as
+        ixx ixy ixz iyy iyz izz about the centre of mass in the frame's axes; gravity (3,) in the base frame, None =
+        (0, 0, -9.81)."""
+        F = self.desc.n_frames
+        mass, com, inertia = _f64(mass).reshape(-1), _f64(com).reshape(-1), _f64(inertia).reshape(-1)
+        if mass.size != F or com.size != 3 * F or inertia.size != 6 * F:
+            raise ValueError(f"set_link_inertials: mass ({F},), com ({F}, 3) and inertia ({F}, 6) expected")
+        g = None if gravity is None else _f64(gravity).reshape(3)
+        self._check(self.lib.gto_set_link_inertials(self._h, _p(mass, _pd), _p(com, _pd), _p(inertia, _pd), _p(g, _pd)),
+                    "gto_set_link_inertials")
+
+    def sync_link_inertials(self):
+        """Upload the description's inertials if it has any and they are not the arrays this handle uploaded last (a
+        description loaded from the packaged files has none until RobotDesc.set_link_inertials)."""
+        d = self.desc
+        if d.has_inertials and (self._inertials is None or any(a is not b for a, b in zip(
+                self._inertials, (d.frame_mass, d.frame_com, d.frame_inertia)))):
+            self.set_link_inertials(d.frame_mass, d.frame_com, d.frame_inertia)
+            self._inertials = (d.frame_mass, d.frame_com, d.frame_inertia)
+
+    def inverse_dynamics(self, q, qd, qdd, payload=None):
+        """Joint forces (n, ndof) of the rows q, qd, qdd (n, ndof) by gto_inverse_dynamics.  payload: None, or a dict with
+        "mass" and optionally "com" (in link_ee's frame) and "inertia" (ixx ixy ixz iyy iyz izz about that centre), each
+        one value for the call or one per row."""
+        q = _f64(q).reshape(-1, self.desc.ndof)
+        n = q.shape[0]
+        qd, qdd = _f64(qd).reshape(n, self.desc.ndof), _f64(qdd).reshape(n, self.desc.ndof)
+        pm, pc, pi = payload_arrays(payload, n)
+        self.sync_link_inertials()
+        out = np.empty((n, self.desc.ndof))
+        self._check(self.lib.gto_inverse_dynamics(self._h, n, _p(q, _pd), _p(qd, _pd), _p(qdd, _pd), _p(pm, _pd), _p(pc, _pd),
+                                                  _p(pi, _pd), _p(out, _pd)), "gto_inverse_dynamics")
         return out
 
     def eval_points(self, scene_id, q, base_pos, use_obs=False, want_field=True, want=None):

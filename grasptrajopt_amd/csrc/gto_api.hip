@@ -24,6 +24,7 @@
 #include "gto_depth.h"
 #include "gto_cloud.h"
 #include "gto_retime.h"
+#include "gto_dynamics.h"
 #include "gto_observe.h"
 #include "gto_held.h"
 #include "gto_seed.h"
@@ -252,6 +253,9 @@ struct gto_handle {
   // the grasp filter (gto_filter_grasps_device): the depth objects' views, the uncompacted goals [B][n_max][16], the poses
   // of the cloud objects' rows [B][n_max][16], the counts [B][n_max]
   DevBuf fg_tab, fg_plan, fg_ik, fg_pose, fg_count;
+  // the link inertials (gto_set_link_inertials): the table rt_rnea reads; none until the first call
+  DevBuf dyn_buf;
+  bool has_inertials = false;
 
   // the streams and events the handle created; the buffers above free themselves after this (gto_destroy has set the device)
   ~gto_handle() {
@@ -2159,6 +2163,55 @@ int gto_eval_fk(gto_handle* h, int32_t nq, const double* q, double* frames_out) 
   if ((rc = io.in(q, (size_t)nq * h->rb.ndof, &dq))) return rc;
   if ((rc = io.out(frames_out, (size_t)nq * h->rb.n_frames * 16, &dout))) return rc;
   if ((rc = launch_eval_kin(h, nq, dq, dout, nullptr))) return rc;
+  return io.finish();
+}
+
+// -------------------------------------------------------------------------------------------------
+// inverse dynamics (gto_dynamics.h)
+int gto_set_link_inertials(gto_handle* h, const double* mass, const double* com, const double* inertia, const double gravity[3]) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (!mass || !com || !inertia) return fail(h, GTO_ERR_INVALID_ARG, "null input array");
+  std::string why;
+  if (int rc = gto_robot::check_inertials(h->rb.n_frames, mass, com, inertia, gravity, why)) return fail(h, rc, why);
+  DynDev dyn;
+  gto_robot::fill_inertials(h->rb.n_frames, mass, com, inertia, gravity, dyn);
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // launches that read the table it replaces
+  if (!h->dyn_buf.get()) HIPCHK(h, dev_alloc(h->dyn_buf, sizeof dyn));
+  HIPCHK(h, hipMemcpy(h->dyn_buf.get(), &dyn, sizeof dyn, hipMemcpyHostToDevice));
+  h->has_inertials = true;
+  return GTO_OK;
+}
+
+int gto_inverse_dynamics(gto_handle* h, int32_t n, const double* q, const double* qd, const double* qdd, const double* payload_mass,
+                         const double* payload_com, const double* payload_inertia, double* tau_out) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (n < 0) return fail(h, GTO_ERR_INVALID_ARG, "n must be >= 0");
+  if (!h->has_inertials) return fail(h, GTO_ERR_INVALID_ARG, "no link inertials set");
+  if (n == 0) return GTO_OK;
+  if (!q || !qd || !qdd || !tau_out) return fail(h, GTO_ERR_INVALID_ARG, "null input array");
+  if (!payload_mass && (payload_com || payload_inertia)) return fail(h, GTO_ERR_INVALID_ARG, "payload_com / payload_inertia without payload_mass");
+  if (payload_mass)
+    for (int i = 0; i < n; ++i)
+      if (!(payload_mass[i] >= 0) || !std::isfinite(payload_mass[i])) return fail(h, GTO_ERR_INVALID_ARG, "payload mass must be >= 0 and finite");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t ndof = h->rb.ndof;
+  Staging io(h);
+  const double *dq, *dqd, *dqdd, *dpm, *dpc, *dpi;
+  double* dtau;
+  int rc;
+  if ((rc = io.in(q, (size_t)n * ndof, &dq))) return rc;
+  if ((rc = io.in(qd, (size_t)n * ndof, &dqd))) return rc;
+  if ((rc = io.in(qdd, (size_t)n * ndof, &dqdd))) return rc;
+  if ((rc = io.in(payload_mass, (size_t)n, &dpm))) return rc;  // (a null array: a null device pointer)
+  if ((rc = io.in(payload_com, (size_t)n * 3, &dpc))) return rc;
+  if ((rc = io.in(payload_inertia, (size_t)n * 6, &dpi))) return rc;
+  if ((rc = io.out(tau_out, (size_t)n * ndof, &dtau))) return rc;
+  const int rows = rnea_rows_per_block(h->rb.n_frames);
+  const size_t lds = sizeof(double) * GTO_RNEA_SLOTS * h->rb.n_frames * rows;
+  hipLaunchKernelGGL(k_inverse_dynamics, dim3((unsigned)((n + rows - 1) / rows)), dim3(GTO_WAVE), lds, h->stream, h->d_rb,
+                     h->dyn_buf.as<const DynDev>(), n, rows, dq, dqd, dqdd, dpm, dpc, dpi, dtau);
+  HIPCHK(h, hipGetLastError());
   return io.finish();
 }
 

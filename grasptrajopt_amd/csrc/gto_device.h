@@ -95,6 +95,15 @@ struct RobotDev {
   double grip_count, grip_mu[3], grip_M[9];
 };
 
+// Link inertials of gto_set_link_inertials, one rigid body per frame (gto_robot.h, fill_inertials; read by rt_rnea,
+// gto_dynamics.h, through scalar loads).  A massless frame has zeros everywhere.
+struct DynDev {
+  double mass[GTO_MAX_FRAMES];
+  double com[GTO_MAX_FRAMES][3];      // centre of mass in the frame's coordinates
+  double inertia[GTO_MAX_FRAMES][6];  // ixx ixy ixz iyy iyz izz about the centre of mass, in the frame's axes
+  double gravity[3];                  // base frame
+};
+
 // One voxel of the gather-friendly field layout built at gto_set_scene: the nearest-voxel cost and the
 // three central differences c[i+e_a] - c[i-e_a] (clipped neighbours, exact in FP64), 32 B, so the hot
 // loop fetches ONE record (two 16-B loads, one cache line) instead of seven scattered floats.

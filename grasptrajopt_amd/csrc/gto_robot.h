@@ -460,6 +460,58 @@ inline int fill_chunks(int pb_merge, RobotTables& t, std::string& why) {
   return GTO_OK;
 }
 
+// Every refusal of gto_set_link_inertials, in the order mass, centre of mass, inertia, gravity: finite masses >= 0; for a
+// frame with mass > 0 a finite centre of mass and a finite inertia that is positive semidefinite (Sylvester's principal
+// minors, each allowed a relative 1e-12 of the tensor's scale below zero); a finite gravity.  Reads the arrays only
+// (gravity may be null) and fills nothing.
+inline int check_inertials(int n_frames, const double* mass, const double* com, const double* inertia, const double* gravity,
+                           std::string& why) {
+  auto bad = [&](const char* msg) {
+    why = msg;
+    return GTO_ERR_INVALID_ARG;
+  };
+  for (int f = 0; f < n_frames; ++f)
+    if (!(mass[f] >= 0) || !std::isfinite(mass[f])) return bad("link mass must be >= 0 and finite");
+  for (int f = 0; f < n_frames; ++f) {
+    if (!(mass[f] > 0)) continue;
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(com[3 * f + k])) return bad("non-finite centre of mass");
+    const double* I = inertia + 6 * f;
+    double scale = 0.0;
+    for (int k = 0; k < 6; ++k) {
+      if (!std::isfinite(I[k])) return bad("non-finite link inertia");
+      scale = std::max(scale, std::fabs(I[k]));
+    }
+    const double xx = I[0], xy = I[1], xz = I[2], yy = I[3], yz = I[4], zz = I[5];
+    const double t1 = 1e-12 * scale, t2 = t1 * scale, t3 = t2 * scale;
+    const double m_xy = xx * yy - xy * xy, m_xz = xx * zz - xz * xz, m_yz = yy * zz - yz * yz;
+    const double det = xx * m_yz - xy * (xy * zz - yz * xz) + xz * (xy * yz - yy * xz);
+    if (xx < -t1 || yy < -t1 || zz < -t1 || m_xy < -t2 || m_xz < -t2 || m_yz < -t2 || det < -t3)
+      return bad("link inertia must be symmetric positive semidefinite");
+  }
+  if (gravity)
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(gravity[k])) return bad("non-finite gravity");
+  return GTO_OK;
+}
+
+// The inertial table rt_rnea reads (gto_dynamics.h).  Clears dyn, then fills mass, com and inertia of the frames with mass
+// (the other entries of a massless frame are ignored: they stay zero) and gravity (null: (0, 0, -9.81)).  Reads arrays that
+// check_inertials has passed.
+inline void fill_inertials(int n_frames, const double* mass, const double* com, const double* inertia, const double* gravity,
+                           DynDev& dyn) {
+  std::memset(&dyn, 0, sizeof dyn);
+  for (int f = 0; f < n_frames; ++f) {
+    if (!(mass[f] > 0)) continue;
+    dyn.mass[f] = mass[f];
+    for (int k = 0; k < 3; ++k) dyn.com[f][k] = com[3 * f + k];
+    for (int k = 0; k < 6; ++k) dyn.inertia[f][k] = inertia[6 * f + k];
+  }
+  dyn.gravity[2] = -9.81;
+  if (gravity)
+    for (int k = 0; k < 3; ++k) dyn.gravity[k] = gravity[k];
+}
+
 }  // namespace gto_robot
 
 // Validates the descriptor and builds its tables, for step-kernel spheres of up to pb_merge >= 1 chunks.  GTO_OK, or an

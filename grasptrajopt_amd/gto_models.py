@@ -118,6 +118,17 @@ class GTORobotModel:
         """The same for the optimised joints (optas/models.py:539-548)."""
         return DM(np.asarray(self.velocity_actuated_joint_limits.toarray()).ravel()[self.desc.opt_index])
 
+    @property
+    def effort_actuated_joint_limits(self) -> DM:
+        """URDF <limit effort> of every actuated joint (N m, or N for a prismatic joint); +inf where the URDF gives none."""
+        e = self.desc.effort
+        return DM(np.full(self.desc.ndof, np.inf) if e is None else e)
+
+    @property
+    def effort_optimized_joint_limits(self) -> DM:
+        """The same for the optimised joints."""
+        return DM(np.asarray(self.effort_actuated_joint_limits.toarray()).ravel()[self.desc.opt_index])
+
     def extract_parameter_dimensions(self, values):
         return np.asarray(values)[self.parameter_joint_indexes, :]
 

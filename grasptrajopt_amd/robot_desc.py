@@ -28,6 +28,67 @@ def _velocity_limit(v: float) -> float:
     return np.inf if v <= 0.0 or v >= 1e9 else float(v)
 
 
+def _effort_limit(e: float) -> float:
+    """A URDF effort limit; 0 (no effort attribute), >= 1e9 (no <limit> element, urdf.py) -> +inf, no limit."""
+    return np.inf if e <= 0.0 or e >= 1e9 else float(e)
+
+
+def _rpy_matrix(rpy) -> np.ndarray:
+    """rotz(yaw) @ roty(pitch) @ rotx(roll) (optas/spatialmath.py:186-211; csrc/gto_device.h rpy2r)."""
+    cr, sr, cp, sp, cy, sy = np.cos(rpy[0]), np.sin(rpy[0]), np.cos(rpy[1]), np.sin(rpy[1]), np.cos(rpy[2]), np.sin(rpy[2])
+    return (np.array([[cy, -sy, 0], [sy, cy, 0], [0, 0, 1.0]]) @ np.array([[cp, 0, sp], [0, 1.0, 0], [-sp, 0, cp]])
+            @ np.array([[1.0, 0, 0], [0, cr, -sr], [0, sr, cr]]))
+
+
+def _sym3(six) -> np.ndarray:
+    xx, xy, xz, yy, yz, zz = six
+    return np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]], dtype=np.float64)
+
+
+def _six(I) -> np.ndarray:
+    return np.array([I[0, 0], I[0, 1], I[0, 2], I[1, 1], I[1, 2], I[2, 2]])
+
+
+def link_inertial_in_link_frame(link):
+    """(mass, com (3,), inertia 3x3 about the com in the LINK frame's axes) of a URDF link: the inertial origin's rpy rotates
+    the tensor, which the URDF states in the inertial frame's axes, into the link frame (I_link = R I R^T)."""
+    R = _rpy_matrix(link.inertial_rpy)
+    return float(link.mass), np.asarray(link.inertial_xyz, dtype=np.float64), R @ _sym3(link.inertia) @ R.T
+
+
+def lump_inertials(urdf: Urdf, order: Sequence[str]):
+    """Per kept frame (the links of `order`) one rigid body: frame_mass (F,), frame_com (F, 3), frame_inertia (F, 6: ixx ixy
+    ixz iyy iyz izz about the com, in the frame's axes).  A link that is not kept is welded to its nearest kept ancestor
+    with every joint on the way at position 0 (its pose there is the product of the joint origins), and the bodies that
+    meet on one frame are merged by the parallel-axis theorem, so that no mass of the URDF is lost."""
+    fidx = {n: i for i, n in enumerate(order)}
+    F = len(order)
+    bodies: List[List] = [[] for _ in range(F)]
+    for link in urdf.links:
+        m, c, I = link_inertial_in_link_frame(link)
+        if not m > 0:
+            continue
+        cur = link.name
+        while cur not in fidx:  # pose of the pruned link in its parent, joint at 0
+            j = urdf.parent_joint[cur]
+            R = _rpy_matrix(j.rpy)
+            c, I = R @ c + np.asarray(j.xyz, dtype=np.float64), R @ I @ R.T
+            cur = j.parent
+        bodies[fidx[cur]].append((m, c, I))
+    mass, com, inertia = np.zeros(F), np.zeros((F, 3)), np.zeros((F, 6))
+    for f, bs in enumerate(bodies):
+        if not bs:
+            continue
+        mass[f] = sum(b[0] for b in bs)
+        com[f] = sum(b[0] * b[1] for b in bs) / mass[f]
+        I = np.zeros((3, 3))
+        for m, c, Ib in bs:
+            d = c - com[f]
+            I += Ib + m * (d @ d * np.eye(3) - np.outer(d, d))
+        inertia[f] = _six(I)
+    return mass, com, inertia
+
+
 @dataclass
 class RobotDesc:
     name: str
@@ -55,6 +116,14 @@ class RobotDesc:
     point_link: np.ndarray = None   # (P,) int32
     # joint velocity limits (ndof,) from <limit velocity>, +inf = no limit (optas/models.py:497-506); None = not recorded
     velocity: Optional[np.ndarray] = None
+    # joint effort limits (ndof,) from <limit effort> (N m, or N for a prismatic joint), +inf = no limit; None = not recorded
+    effort: Optional[np.ndarray] = None
+    # one rigid body per frame (the link that the frame's joint moves): mass (F,), centre of mass (F, 3) in the frame's
+    # coordinates, inertia (F, 6) as ixx ixy ixz iyy iyz izz about the centre of mass in the frame's axes.  None = not recorded
+    # (the packaged descriptions): set them with set_link_inertials or build the description from a URDF
+    frame_mass: Optional[np.ndarray] = None
+    frame_com: Optional[np.ndarray] = None
+    frame_inertia: Optional[np.ndarray] = None
 
     # ------------------------------------------------------------------ properties
     @property
@@ -93,6 +162,19 @@ class RobotDesc:
             moved[i] = (p >= 0 and moved[p]) or (self.q_index[i] in opt)
         return moved[self.link_frame]
 
+    @property
+    def has_inertials(self) -> bool:
+        return self.frame_mass is not None
+
+    def set_link_inertials(self, mass, com, inertia) -> None:
+        """Record one rigid body per frame: mass (F,), com (F, 3), inertia (F, 6), as the fields above state them."""
+        F = self.n_frames
+        mass = np.array(mass, dtype=np.float64).reshape(-1)
+        com, inertia = np.array(com, dtype=np.float64).reshape(-1, 3), np.array(inertia, dtype=np.float64).reshape(-1, 6)
+        if mass.shape != (F,) or com.shape != (F, 3) or inertia.shape != (F, 6):
+            raise ValueError(f"set_link_inertials: mass ({F},), com ({F}, 3) and inertia ({F}, 6) expected")
+        self.frame_mass, self.frame_com, self.frame_inertia = mass, com, inertia
+
     def link_points(self, link_name: str) -> np.ndarray:
         l = self.link_names.index(link_name)
         return self.points[self.point_link == l]
@@ -104,6 +186,10 @@ class RobotDesc:
                   extra_links: Sequence[str] = (), model_dir: Optional[str] = None,
                   points_per_link: int = 100, seed: int = 0,
                   keep_all_frames: bool = False) -> "RobotDesc":
+        """Frames: the links on the way from the root to a collision link or one of ``extra_links`` (every link with
+        ``keep_all_frames``).  The links that are pruned keep their inertia: each pruned subtree is lumped rigidly into its
+        nearest kept ancestor with the pruned joints at position 0 (lump_inertials).  ``effort`` holds <limit effort> of
+        every actuated joint, +inf where the URDF gives 0 or nothing."""
         actuated = [j.name for j in urdf.joints if j.type != "fixed"]
         for j in urdf.joints:
             if j.type not in _JTYPE:
@@ -111,6 +197,7 @@ class RobotDesc:
         lower = np.array([urdf.joint_map[j].lower for j in actuated], dtype=np.float64)
         upper = np.array([urdf.joint_map[j].upper for j in actuated], dtype=np.float64)
         velocity = np.array([_velocity_limit(urdf.joint_map[j].velocity) for j in actuated], dtype=np.float64)
+        effort = np.array([_effort_limit(urdf.joint_map[j].effort) for j in actuated], dtype=np.float64)
         params = [j for j in actuated if j in set(param_joints)]
         opt_index = np.array([i for i, j in enumerate(actuated) if j not in params], dtype=np.int32)
         param_index = np.array([i for i, j in enumerate(actuated) if j in params], dtype=np.int32)
@@ -166,7 +253,8 @@ class RobotDesc:
 
         desc = cls(name=urdf.name, frame_names=order, parent=parent, joint_type=jtype, q_index=qidx,
                    origin_xyz=oxyz, origin_rpy=orpy, axis=axis, actuated_joint_names=actuated,
-                   lower=lower, upper=upper, opt_index=opt_index, param_index=param_index, velocity=velocity)
+                   lower=lower, upper=upper, opt_index=opt_index, param_index=param_index, velocity=velocity, effort=effort)
+        desc.frame_mass, desc.frame_com, desc.frame_inertia = lump_inertials(urdf, order)
         desc.link_names = [l.name for l in links]
         desc.link_frame = np.array([fidx[l.name] for l in links], dtype=np.int32)
         desc.visual_xyz = np.array([l.visual_xyz for l in links], dtype=np.float64).reshape(-1, 3)
@@ -193,8 +281,13 @@ class RobotDesc:
             meta["velocity_limits"] = [float(v) if np.isfinite(v) else None for v in self.velocity]
         with open(prefix + ".json", "w") as fh:
             json.dump(meta, fh, indent=1)
+        extra = {}
+        if self.effort is not None:
+            extra["effort"] = self.effort
+        if self.has_inertials:
+            extra.update(frame_mass=self.frame_mass, frame_com=self.frame_com, frame_inertia=self.frame_inertia)
         np.savez_compressed(
-            prefix + ".npz", parent=self.parent, joint_type=self.joint_type, q_index=self.q_index,
+            prefix + ".npz", **extra, parent=self.parent, joint_type=self.joint_type, q_index=self.q_index,
             origin_xyz=self.origin_xyz, origin_rpy=self.origin_rpy, axis=self.axis, lower=self.lower,
             upper=self.upper, opt_index=self.opt_index, param_index=self.param_index,
             link_frame=self.link_frame, visual_xyz=self.visual_xyz, visual_rpy=self.visual_rpy,
@@ -214,7 +307,8 @@ class RobotDesc:
                    actuated_joint_names=meta["actuated_joint_names"], lower=z["lower"], upper=z["upper"],
                    opt_index=z["opt_index"], param_index=z["param_index"], link_names=meta["link_names"],
                    link_frame=z["link_frame"], visual_xyz=z["visual_xyz"], visual_rpy=z["visual_rpy"],
-                   points=z["points"], normals=z["normals"].astype(np.float64), point_link=z["point_link"], velocity=vel)
+                   points=z["points"], normals=z["normals"].astype(np.float64), point_link=z["point_link"], velocity=vel,
+                   **{k: z[k] for k in ("effort", "frame_mass", "frame_com", "frame_inertia") if k in z.files})
 
 
 def with_planar_base(desc: RobotDesc, xy_limit: float = 1.0, name: Optional[str] = None) -> RobotDesc:
@@ -237,7 +331,11 @@ def with_planar_base(desc: RobotDesc, xy_limit: float = 1.0, name: Optional[str]
         opt_index=np.concatenate([[0, 1, 2], desc.opt_index + 3]).astype(np.int32), param_index=(desc.param_index + 3).astype(np.int32),
         link_names=list(desc.link_names), link_frame=(desc.link_frame + 4).astype(np.int32), visual_xyz=desc.visual_xyz.copy(),
         visual_rpy=desc.visual_rpy.copy(), points=desc.points.copy(), normals=desc.normals.copy(), point_link=desc.point_link.copy(),
-        velocity=None if desc.velocity is None else np.concatenate([[np.inf, np.inf, np.inf], desc.velocity]))
+        velocity=None if desc.velocity is None else np.concatenate([[np.inf, np.inf, np.inf], desc.velocity]),
+        effort=None if desc.effort is None else np.concatenate([[np.inf, np.inf, np.inf], desc.effort]))
+    if desc.has_inertials:  # the base frames are massless
+        out.set_link_inertials(np.concatenate([np.zeros(4), desc.frame_mass]), np.concatenate([np.zeros((4, 3)), desc.frame_com]),
+                               np.concatenate([np.zeros((4, 6)), desc.frame_inertia]))
     assert out.n_frames == F0 + 4
     return out
 

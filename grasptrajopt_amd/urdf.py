@@ -7,7 +7,10 @@ a dependency here.  Semantics kept identical to what optas reads from it:
   * a joint without <origin> has zero xyz/rpy (optas/models.py:642-651), without <axis> the axis is
     (1,0,0) (optas/models.py:653-659), without <limit> the limits are -1e9/+1e9
     (optas/models.py:438-456); a <limit> lacking lower/upper yields 0 (README.md:120-121),
-  * a link's visual is its FIRST <visual>; visual origin defaults to zero (optas/models.py:629-640).
+  * a link's visual is its FIRST <visual>; visual origin defaults to zero (optas/models.py:629-640),
+  * a link's <inertial> gives its mass, the origin (xyz AND rpy) of the inertial frame in the link frame and the six
+    inertia entries about the centre of mass in the inertial frame's axes; a link without one is massless.  A <limit>
+    without effort yields 0, no <limit> 1e9, as for velocity.
 """
 from __future__ import annotations
 
@@ -29,6 +32,10 @@ class UrdfLink:
     visual_mesh: Optional[str] = None
     visual_scale: List[float] = field(default_factory=lambda: [1.0, 1.0, 1.0])
     visual_box: Optional[List[float]] = None  # <box size="x y z"> (object URDFs: surface_point_cloud.urdf_visual_meshes)
+    mass: float = 0.0  # <inertial>: 0 without one
+    inertial_xyz: List[float] = field(default_factory=lambda: [0.0, 0.0, 0.0])
+    inertial_rpy: List[float] = field(default_factory=lambda: [0.0, 0.0, 0.0])
+    inertia: List[float] = field(default_factory=lambda: [0.0] * 6)  # ixx ixy ixz iyy iyz izz, inertial frame's axes
 
 
 @dataclass
@@ -43,6 +50,7 @@ class UrdfJoint:
     lower: float
     upper: float
     velocity: float
+    effort: float = 0.0
 
 
 class Urdf:
@@ -85,6 +93,17 @@ class Urdf:
             box = vis.find("geometry/box")
             if box is not None:
                 link.visual_box = _floats(box.get("size"))
+        ine = el.find("inertial")
+        if ine is not None:
+            o = ine.find("origin")
+            if o is not None:
+                link.inertial_xyz = _floats(o.get("xyz", "0 0 0"))
+                link.inertial_rpy = _floats(o.get("rpy", "0 0 0"))
+            m = ine.find("mass")
+            link.mass = float(m.get("value", 0.0)) if m is not None else 0.0
+            t = ine.find("inertia")
+            if t is not None:
+                link.inertia = [float(t.get(k, 0.0)) for k in ("ixx", "ixy", "ixz", "iyy", "iyz", "izz")]
         return link
 
     @staticmethod
@@ -96,11 +115,12 @@ class Urdf:
         axis = _floats(ax.get("xyz")) if ax is not None else [1.0, 0.0, 0.0]
         lim = el.find("limit")
         if lim is None:
-            lower, upper, velocity = -1e9, 1e9, 1e9
+            lower, upper, velocity, effort = -1e9, 1e9, 1e9, 1e9
         else:
             lower = float(lim.get("lower", 0.0))
             upper = float(lim.get("upper", 0.0))
             velocity = float(lim.get("velocity", 0.0))
+            effort = float(lim.get("effort", 0.0))
         return UrdfJoint(
             name=el.get("name"),
             type=el.get("type"),
@@ -112,6 +132,7 @@ class Urdf:
             lower=lower,
             upper=upper,
             velocity=velocity,
+            effort=effort,
         )
 
     def get_root(self) -> str:

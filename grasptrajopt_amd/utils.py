@@ -273,6 +273,24 @@ def retime_paths(robot, paths, n_cols=None, vlim=None, alim=0.5, subdiv: int = 2
     return h.retime_paths(paths, vlim, alim, n_cols=n_cols, subdiv=subdiv, n_samples=n_samples)
 
 
+def inverse_dynamics(robot, q, qd, qdd, payload=None, link_ee=None):
+    """Joint forces tau = M(q) qdd + C(q, qd) qd + g(q) of states (n, ndof) or one state (ndof,) on the GPU
+    (gto_inverse_dynamics, include/gto_solver.h): recursive Newton-Euler over the robot's frames with the link inertials of
+    ``robot.desc`` (a description built from a URDF has them; one loaded from the packaged files gets them with
+    ``robot.desc.set_link_inertials``).  payload: None, or a dict with "mass" and optionally "com" and "inertia" (ixx ixy ixz
+    iyy iyz izz about that centre), each one value or one per state: a rigid body on ``link_ee``, stated in that link's
+    frame.  Returns (n, ndof), N m (N for a prismatic joint)."""
+    q = np.asarray(q, dtype=np.float64)
+    one = q.ndim == 1
+    if not robot.desc.has_inertials:
+        raise ValueError("inverse_dynamics: the robot description has no link inertials (RobotDesc.set_link_inertials)")
+    if payload is not None and link_ee is None:
+        raise ValueError("inverse_dynamics: a payload needs link_ee, the link that carries it")
+    ln = robot.desc.link_names[-1] if link_ee is None else link_ee
+    tau = robot.solver_handle(ln, robot.desc.link_names[-1], role="util").inverse_dynamics(q, qd, qdd, payload)
+    return tau[0] if one else tau
+
+
 def convert_plan_to_trajectory_toppra(robot, plan, is_show: bool = False):
     """gto/utils.py:283-323 on the GPU: plan (ndof, T) -> (qs_sample, qds_sample, qdds_sample, ts_sample), 100 samples of
     each, in the reference's order.  Velocity limits from the URDF for all ndof joints (the reference passes the n_opt

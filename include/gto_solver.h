@@ -378,6 +378,33 @@ int gto_eval_points(gto_handle* h, int32_t scene_id, int32_t nq, const double* q
 int gto_eval_points_hessian(gto_handle* h, int32_t scene_id, int32_t nq, const double* q /*[nq,ndof]*/,
                             const double* base_pos /*[nq,3]*/, int32_t use_obs, double* hess_out /*[nq,P,9]*/);
 
+/* ---- rigid-body dynamics.  Added without a new ABI number: gto_robot_desc is as it was. ------------------------------ */
+
+/* The inertials of the handle's frames: frame f is the rigid body that joint f moves (the indexing of parent / joint_type /
+ * q_index).  mass >= 0 and finite; mass == 0 is a massless frame whose other entries are ignored.  Where mass > 0 the centre
+ * of mass is finite and the inertia (about the centre of mass, in the frame's axes) symmetric positive semidefinite.
+ * gravity is in the base frame.  Anything else: GTO_ERR_INVALID_ARG with a message, and the handle keeps what it had.  May be
+ * repeated; a synchronising upload, like a scene.  A handle without inertials answers gto_inverse_dynamics with
+ * GTO_ERR_INVALID_ARG "no link inertials set".
+ * Replaces: the <inertial> blocks the reference's URDFs carry and its planner never reads (optas/models.py:1735-1888 takes
+ * them from urdf_parser_py). */
+int gto_set_link_inertials(gto_handle* h, const double* mass /*[n_frames]*/, const double* com /*[n_frames*3]*/,
+                           const double* inertia /*[n_frames*6]: ixx ixy ixz iyy iyz izz*/,
+                           const double gravity[3] /*NULL = (0, 0, -9.81)*/);
+
+/* Inverse dynamics tau = M(q) qdd + C(q, qd) qd + g(q) of n rows, by recursive Newton-Euler over the frame tree (fixed base;
+ * revolute / continuous, prismatic and fixed joints; branches; the gravity of gto_set_link_inertials).  The payload of a row
+ * is a rigid body on frame_ee: its mass (>= 0 and finite, 0 = none), centre of mass in frame_ee's coordinates (NULL = the
+ * frame's origin) and inertia about that centre in frame_ee's axes (NULL = a point mass); payload_mass NULL = no payload,
+ * and then the other two must be NULL.  tau_out[., j] is the generalised force of actuated joint j (N m, or N for a
+ * prismatic joint), 0 for a joint that no frame names.  FP64 throughout; a row's result depends on the row alone, not on n
+ * or its position.  Host pointers, synchronous.
+ * Replaces: the `alims` stand-in of gto/utils.py:293-298; RobotModel.rnea, optas/models.py:1735-1888 (which takes revolute
+ * chains only). */
+int gto_inverse_dynamics(gto_handle* h, int32_t n, const double* q, const double* qd, const double* qdd /*[n,ndof] each*/,
+                         const double* payload_mass /*[n] or NULL*/, const double* payload_com /*[n,3] or NULL*/,
+                         const double* payload_inertia /*[n,6] or NULL*/, double* tau_out /*[n,ndof]*/);
+
 /* Objective terms of SURVEY.md Appendix A at given trajectories Q [B, ndof, T]:
  * f_goal (min over the goal set), f_obs (incl. w_obstacle), f_vel (incl. w_vel), arg-min goal.
  * (gto/gto_planner.py:84-105, 108-131, 133-135.) */
