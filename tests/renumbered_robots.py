@@ -27,6 +27,7 @@ import copy
 
 import numpy as np
 
+import dynamics_ref as dr
 from grasptrajopt_amd import synthetic as syn
 from grasptrajopt_amd.robot_desc import load_builtin
 from helpers import cfg_of, random_robot
@@ -50,6 +51,8 @@ OFFSET = -3                                 # standoff_offset of every case (T +
 # case -> seed of its draw where 0 does not give invariant oracle solves (r9, seed 0: the IK without a scene creeps along a
 # flat valley to the iteration cap in four instances, and the sorted variant's cost there differs by 3e-6 relative)
 SEEDS = {"r9": 1}
+INERTIAL_SEEDS = {"r1": 211, "r9": 212, "r3": 213, "r55": 214}   # dynamics_ref.random_inertials (Panda: the fixture's bodies)
+DYNAMICS_ROWS = 20
 
 
 # --------------------------------------------------------------------------------------------------------- renumbering
@@ -64,6 +67,8 @@ def renumber(desc, pi, sort):
     d.lower, d.upper = desc.lower[inv].copy(), desc.upper[inv].copy()
     if desc.velocity is not None:
         d.velocity = desc.velocity[inv].copy()
+    if desc.effort is not None:
+        d.effort = desc.effort[inv].copy()
     d.actuated_joint_names = [desc.actuated_joint_names[i] for i in inv]
     d.param_index = np.sort(pi[desc.param_index]).astype(np.int32)
     opt = pi[desc.opt_index]
@@ -145,7 +150,8 @@ class Case:
         else:
             d, self.ee = random_robot(*robot)
             self.gripper, self.ngp = self.ee, 40
-        self.desc0 = d
+        # bodies for gto_inverse_dynamics, before any view copies the description (frame-indexed: a renumbering leaves them)
+        self.desc0 = d = dr.with_fixture_inertials(d, "panda") if robot == "panda" else dr.random_inertials(d, INERTIAL_SEEDS[name])
         self.opts = oracle_mod.reference_opts(T=T, standoff_offset=OFFSET, max_iter=MAX_ITER)
         rng = np.random.default_rng(7000 + 97 * list(CASES).index(name) + self.seed)
         n, res = 40, 0.05
@@ -223,6 +229,14 @@ def retime_inputs(view, seed=None):
     vmax[::3] = np.inf
     amax = rng.uniform(0.4, 0.9, d.ndof)
     return view.new(plans, 1), view.new(vmax, 0), view.new(amax, 0)
+
+
+def dynamics_inputs(view):
+    """(q, qd, qdd (20, ndof) in the view's numbering, payload (mass, com, inertia) per row): dynamics_ref.in_limit_states on
+    the original robot and the `full` payload of dynamics_cases.payloads, which rides on the case's end-effector frame."""
+    import dynamics_cases as dc
+    q, qd, qdd = dr.in_limit_states(view.case.desc0, DYNAMICS_ROWS, seed=31)
+    return view.new(q, 1), view.new(qd, 1), view.new(qdd, 1), dc.payloads(DYNAMICS_ROWS, seed=32)["full"]
 
 
 RETIME_SEEDS = {}   # case -> seed of retime_ref.random_plans where 0 does not converge at every plan

@@ -43,6 +43,7 @@ P_HELD, P_GRIPPER = 8, 20
 FILTER_OBS = (0, 1, 1, 0)  # depth, cloud, cloud, depth: two cloud runs around depth objects
 LIFT_K, LIFT_DISTANCE = 3, 0.1
 SUBDIV, M_SAMPLES = 2, 5
+CONVEX_GAP_TOL, CONVEX_MAX_NEWTON = 1e-8, 400  # (the Python layers' default, _capi.RETIME_MAX_NEWTON: the CPU test asserts it)
 IK_TOL = (0.6, 120.0, 1.0e30)      # pos, rot (degrees), cost: loose, so that some rows are accepted and some are not
 SELECT_TOL = (0.5, 5.0, 5)         # pos, rot, max_points of gto_select_plans_device
 EFFORT, MAX_RATIO = 0.01, 0.5
@@ -51,14 +52,15 @@ SENTINEL = {np.dtype(np.float64): -777.25, np.dtype(np.int32): -77, np.dtype(np.
 
 ENTRIES = ["solve", "ik_pose", "ik_report", "seed", "seed_multi", "plan_report", "select_plans", "check_plans_depth",
            "check_plans_cloud", "check_held_depth", "check_held_cloud", "filter_grasps", "retime_batch", "retime_paths",
-           "retrieve_lift", "retrieve_reverse", "solve_base", "base_report"]
+           "retime_paths_convex", "retrieve_lift", "retrieve_reverse", "solve_base", "base_report"]
 # the entry points whose header text says that they enqueue "without a host synchronisation" (the retime calls after a
 # first call of the handle): all but gto_solve_batch_device, which throttles on the GPU's progress
 NO_HOST_SYNC = [e for e in ENTRIES if e != "solve"]
 HORIZON = {"retrieve_reverse": T_REVERSE}  # (every other entry: T)
 # the runs of six calls of one handle behind one hold (REGROW_BS): the entries of each run's calls, per B
+# ("retime": the greedy and the convex call alternate on the workspace they share, rt_S ... rt_stat, which every larger B regrows)
 REGROW_RUNS = {"base": ("solve_base", "base_report"), "check_paths": ("check_paths_depth",), "check_held": ("check_held_cloud",),
-               "filter_grasps": ("filter_grasps",)}
+               "filter_grasps": ("filter_grasps",), "retime": ("retime_paths", "retime_paths_convex")}
 
 
 def robot():
@@ -200,9 +202,11 @@ def _draw(entry, B, Tp, rng):
                     plan_goals=((B, N_MAX, 16), f), ik_goals=((B, N_MAX, 16), f))
     elif entry == "retime_batch":
         dev, host, outs = dict(plans=_plans(desc, rng, B, Tp)), _limits(desc, rng), _retime_outs(desc, B, Tp)
-    elif entry == "retime_paths":
+    elif entry in ("retime_paths", "retime_paths_convex"):
         dev, host = dict(paths=_plans(desc, rng, B, Tp), n_cols=_counts(rng, B, 3, Tp)), _limits(desc, rng)
         outs = _retime_outs(desc, B, Tp)
+        if entry == "retime_paths_convex":
+            outs["iters"] = ((B,), i32)
     elif entry == "retrieve_lift":
         d = cc._unit(rng.normal(size=(1, 3)))[0]
         dev = dict(plans=_plans(desc, rng, B, Tp), scene_id=_counts(rng, B, 0, 1), base_pos=_bases(rng, B))
@@ -359,6 +363,10 @@ def enqueue(rig, entry, case, d, hst, o, stream):
     elif entry == "retime_paths":
         rc = lib.gto_retime_paths_device(h, B, Tp, D("paths"), D("n_cols"), _hp(hst["vmax"], _pd), _hp(hst["amax"], _pd), SUBDIV, M_SAMPLES,
                                          O("duration"), O("t_grid"), O("sd_grid"), O("q"), O("qd"), O("qdd"), O("status"), st)
+    elif entry == "retime_paths_convex":
+        rc = lib.gto_retime_paths_convex_device(h, B, Tp, D("paths"), D("n_cols"), _hp(hst["vmax"], _pd), _hp(hst["amax"], _pd), SUBDIV,
+                                                M_SAMPLES, CONVEX_GAP_TOL, CONVEX_MAX_NEWTON, O("duration"), O("t_grid"), O("sd_grid"), O("q"),
+                                                O("qd"), O("qdd"), O("status"), O("iters"), st)
     elif entry == "retrieve_lift":
         cj, cv = hst["closed_joints"], hst["closed_values"]
         rc = lib.gto_retrieve_lift_device(h, B, D("plans"), D("scene_id"), D("base_pos"), _hp(hst["direction"], _pd), LIFT_DISTANCE, LIFT_K,

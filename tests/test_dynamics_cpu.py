@@ -1,8 +1,10 @@
 """tests/dynamics_ref.py, the yardstick of gto_inverse_dynamics, held against physics rather than against itself; the URDF
 reader's inertial and effort fields; the lumping of pruned links (no GPU here).
 
-Three checks per robot (Panda and Fetch with the fixtures' inertials, a branched tree and a chain with prismatic joints with
-seeded bodies) over 32 seeded in-limit states, half of them with a payload on the end effector:
+Three checks per robot (Panda and Fetch with the fixtures' inertials; a branched tree, a chain with prismatic joints and the
+edge robots of tests/dynamics_cases.py with seeded bodies: one frame with an actuated root, no revolute joint, a payload on
+a frame above the joints, 32 frames with 31 joints) over 32 seeded in-limit states (the first 8 of them on the two robots of
+32 frames, FEWER_STATES), half of them with a payload on the end effector:
   1. ID(q, 0, e_j) - g, stacked, is the mass matrix sum_k m_k Jv_k^T Jv_k + Jw_k^T R_k I_k R_k^T Jw_k, built here from the
      frames' world axes (the geometric Jacobian of every body's centre of mass) and not from the recursion: 1e-12 relative.
      It is symmetric, and positive definite on the joints that move mass.
@@ -22,6 +24,8 @@ import dynamics_cases as dc
 import dynamics_ref as dr
 
 N_STATES = 32
+# the two robots of 32 frames take a third of a second per state in the finite-difference checks: the first 8 states there
+FEWER_STATES = {"limit_chain": 8, "limit_bushy": 8}
 H = 1e-3
 TRUNC_SAFETY, ROUND_ULPS = 4.0, 16.0
 EPS = 2.0 ** -52
@@ -34,7 +38,7 @@ def case(request):
     pl = dc.payloads(N_STATES, seed=6)["full"]
     payload = [None if i % 2 == 0 else (pl[0][i], pl[1][i], pl[2][i]) for i in range(N_STATES)]
     return dict(name=request.param, desc=desc, ee=desc.frame_index(ee), link_ee=ee, link_gripper=gr, ngp=ngp, q=q, qd=qd, qdd=qdd,
-                payload=payload)
+                payload=payload, n=FEWER_STATES.get(request.param, N_STATES))
 
 
 def mass_matrix(desc, q, ee, payload):
@@ -81,7 +85,7 @@ def test_forward_kinematics_of_the_yardstick(case, oracle_mod):
     d = case["desc"]
     orc = oracle_mod.Oracle(d, case["link_ee"], case["link_gripper"], oracle_mod.reference_opts(), n_gripper_points=case["ngp"])
     X = orc.eval_fk(case["q"])
-    for i in range(N_STATES):
+    for i in range(case["n"]):
         R, p, _ = dr.fk(d, case["q"][i])
         np.testing.assert_allclose(R, X[i, :, :3, :3], rtol=0, atol=1e-12)
         np.testing.assert_allclose(p, X[i, :, :3, 3], rtol=0, atol=1e-12)
@@ -90,7 +94,7 @@ def test_forward_kinematics_of_the_yardstick(case, oracle_mod):
 def test_unit_accelerations_give_the_mass_matrix(case):
     d, ee = case["desc"], case["ee"]
     zero = np.zeros(d.ndof)
-    for i in range(N_STATES):
+    for i in range(case["n"]):
         q, pl = case["q"][i], case["payload"][i]
         g = dr.inverse_dynamics(d, q, zero, zero, ee, pl)
         M = np.stack([dr.inverse_dynamics(d, q, zero, e, ee, pl) - g for e in np.eye(d.ndof)], axis=1)
@@ -106,7 +110,7 @@ def test_unit_accelerations_give_the_mass_matrix(case):
 def test_static_torques_are_the_gradient_of_the_potential(case):
     d, ee = case["desc"], case["ee"]
     zero = np.zeros(d.ndof)
-    for i in range(N_STATES):
+    for i in range(case["n"]):
         q, pl = case["q"][i], case["payload"][i]
         g = dr.inverse_dynamics(d, q, zero, zero, ee, pl)
         V = lambda x: potential(d, x, ee, pl)  # noqa: E731
@@ -119,7 +123,7 @@ def test_static_torques_are_the_gradient_of_the_potential(case):
 def test_power_is_the_rate_of_the_energy(case):
     d, ee = case["desc"], case["ee"]
     rng = np.random.default_rng(9)
-    for i in range(N_STATES):
+    for i in range(case["n"]):
         pl = case["payload"][i]
         q0, amp = case["q"][i], rng.uniform(0.05, 0.3, d.ndof)
         om, ph = rng.uniform(0.5, 2.0, d.ndof), rng.uniform(0, 2 * np.pi, d.ndof)

@@ -2,9 +2,13 @@
 which tests/test_dynamics_cpu.py holds against physics.
 
 Robots: Panda and Fetch (the fixtures' inertials; Fetch has a prismatic torso and fingers and lumped pruned links), a
-branched tree with a fixed frame inside a branch, and a chain with prismatic joints (seeded bodies).  n = 67 rows is more
-than one workgroup on every one of them (at most 64 rows each, 45 on Panda's twelve frames) and no multiple of either;
-n = 1 is the other end.  The rows: seeded in-limit states, then rows at the lower and the upper limits, rows at rest
+branched tree with a fixed frame inside a branch, a chain with prismatic joints, and the edge robots of
+tests/dynamics_cases.py (seeded bodies): one frame whose root is actuated and carries the payload, two, three (no revolute
+joint) and four frames (the payload on the fixed root, above every joint), ten frames, and two robots of 32 frames (a chain
+of 31 joints, a bushy tree).  A workgroup holds rows_per_block(F) = min(64, 65536 // (15 * F * 8)) rows of a robot of F
+frames (csrc/gto_dynamics.h: GTO_RNEA_LDS_BYTES / (GTO_RNEA_SLOTS * F * sizeof(double)), at most a wave): 64 up to eight
+frames, 45 on Panda's twelve, 17 at 32.  n = 67 rows is more than one workgroup on every one of them and a multiple of none
+of these counts (four workgroups with a ragged last one at 32 frames); n = 1 is the other end.  The rows: seeded in-limit states, then rows at the lower and the upper limits, rows at rest
 (qd = 0), and static rows (qd = qdd = 0).  Agreement: 1e-11 relative to max(1, |tau|_inf), the project's FP64 parity bar.
 """
 import ctypes as C
@@ -18,7 +22,24 @@ import dynamics_ref as dr
 pytestmark = pytest.mark.gpu
 
 N = 67
-SINGLE_ROWS = (0, 45, 66)  # the first row, one that starts a later workgroup on Panda, the last
+
+
+def rows_per_block(F):
+    """rnea_rows_per_block of csrc/gto_dynamics.h, restated from its constants."""
+    return min(64, (64 * 1024) // (15 * F * 8))
+
+
+def single_rows(F):
+    """The first row, the row that starts the second workgroup of a robot of F frames, the last."""
+    rows = rows_per_block(F)
+    return (0, rows if rows < N else 33, N - 1)
+
+
+def test_the_robots_cover_the_layouts():
+    F = {name: dc.robot(name)[0].n_frames for name in dc.NAMES}
+    rows = {rows_per_block(f) for f in F.values()}
+    assert 1 in F.values() and 64 in rows and 17 in rows and max(F.values()) == 32
+    assert all(0 < r < N and N % r != 0 for r in rows)  # more than one workgroup, the last one ragged, on every robot
 
 
 @pytest.fixture(scope="module")
@@ -64,11 +85,14 @@ def test_inverse_dynamics_matches_the_reference(case, kind):
     err = np.abs(tau - ref).max(axis=1) / np.maximum(1.0, np.abs(ref).max(axis=1))
     print(f"{case['name']} {kind}: max relative error {err.max():.3e}, |tau|_inf {np.abs(ref).max():.3f}")
     assert err.max() <= 1e-11
-    if kind != "none":  # the payload is felt (but for the row whose payload mass is 0)
+    if kind != "none":  # the payload is felt (but for the row whose payload mass is 0, and where no joint can feel it)
         base = case["ref"]["none"]
         assert np.array_equal(tau[2], case["h"].inverse_dynamics(case["q"][2], case["qd"][2], case["qdd"][2])[0])
-        assert np.abs(ref - base).max() > 1e-3
-    for i in SINGLE_ROWS:  # a row alone is the row inside the batch, bit for bit
+        if (case["name"], kind) in dc.PAYLOAD_NOT_FELT:
+            assert np.abs(ref - base).max() <= 1e-12
+        else:
+            assert np.abs(ref - base).max() > 1e-3
+    for i in single_rows(case["desc"].n_frames):  # a row alone is the row inside the batch, bit for bit
         one = case["h"].inverse_dynamics(case["q"][i], case["qd"][i], case["qdd"][i], as_dict(pl, slice(i, i + 1)))
         assert np.array_equal(one[0], tau[i]), (kind, i)
 

@@ -267,6 +267,73 @@ def test_retime(rigs, name):
             assert same(x, g0[k]), (v.variant, k)
 
 
+def _dynamics(v):
+    q, qd, qdd, pl = rn.dynamics_inputs(v)
+    return v.h.inverse_dynamics(q, qd, qdd, dict(mass=pl[0], com=pl[1], inertia=pl[2]))
+
+
+@pytest.mark.parametrize("name", ALL)
+def test_inverse_dynamics(rigs, name):
+    """A7: gto_inverse_dynamics over 20 rows with a payload (mass, centre of mass, inertia) on the end effector.  rt_rnea
+    (csrc/gto_dynamics.h) walks the FRAMES; a joint's number only addresses the loads of q, qd, qdd and the store of tau, and
+    opt_index is not read: the torques are the original robot's, permuted, bit for bit in both variants, and the variants
+    give each other's bits.  The original is held to tests/dynamics_ref.py at the 1e-11 of tests/test_gpu_dynamics.py
+    (tests/test_renumbered_robots_cpu.py: the yardstick itself is invariant bit for bit)."""
+    import dynamics_ref as dr
+    views = rigs(name)
+    v0 = views["original"]
+    q, qd, qdd, pl = rn.dynamics_inputs(v0)
+    tau0 = _dynamics(v0)
+    ref = dr.inverse_dynamics_rows(v0.desc, q, qd, qdd, v0.desc.frame_index(v0.ee), pl)
+    err = np.abs(tau0 - ref).max(axis=1) / np.maximum(1.0, np.abs(ref).max(axis=1))
+    print(f"{name}: inverse dynamics, max relative error {err.max():.3e}, |tau|_inf {np.abs(ref).max():.3f}")
+    WORST["inverse_dynamics (relative to max(1, |tau|_inf))"] = max(WORST.get("inverse_dynamics (relative to max(1, |tau|_inf))", 0.0), float(err.max()))
+    assert tau0.shape == ref.shape and np.isfinite(tau0).all() and err.max() <= 1e-11
+    assert np.abs(ref - dr.inverse_dynamics_rows(v0.desc, q, qd, qdd)).max() > 1e-3   # the payload is felt
+    got = {v.variant: _dynamics(v) for v in renumbered(views)}
+    for v in renumbered(views):
+        assert not same(got[v.variant], tau0) and same(v.old(got[v.variant], 1), tau0), v.variant
+    assert same(got["chain"], got["sorted"])   # the same q_index; opt_index is not read
+
+
+RETIME_CONVEX_GAP = 1e-8
+
+
+@pytest.mark.parametrize("name", NARROW + ["r55"])
+def test_retime_convex(rigs, name):
+    """A8: gto_retime_paths_convex on the inputs of A6, subdiv = 2, M = 16, gap_tol = 1e-8.  Per view: the restatement
+    (tests/retime_convex_ref.py on the view's own paths and limits), feasibility and the greedy call, by
+    tests/test_gpu_retime_convex._against_reference_and_greedy.  Across views: k_retime_convex sums barrier terms over the
+    joints, so a renumbered view takes other Newton steps to another point of the same certified interval: statuses are
+    equal, and both durations lie in [T*, (1 + gap_tol) T*], so |d_v - d_0| <= gap_tol min(d_v, d_0) (1 + RTOL) (the derivation
+    of that file's docstring); iteration counts need not match.  The chain and the sorted variant have the same q_index and
+    the retime kernels never read opt_index: every output bit for bit."""
+    import retime_convex_ref as cr
+    from test_gpu_retime import RTOL
+    from test_gpu_retime_convex import ALL as OUTPUTS, GAP_TOL, _against_reference_and_greedy
+    assert GAP_TOL == RETIME_CONVEX_GAP
+    views = rigs(name)
+    got = {}
+    for v in [views["original"]] + renumbered(views):
+        paths, vm, am = rn.retime_inputs(v)
+        assert np.isinf(vm).any() and np.isfinite(vm).any()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = cr.retime_paths_convex_ref(paths, None, vm, am, 2, 16, GAP_TOL)
+        got[v.variant] = g = _against_reference_and_greedy(v.h, paths, None, vm, am, 2, r, M=16)
+        assert (g["status"] == 0).all() and (g["duration"] > 0).all()
+    g0 = got["original"]
+    for variant in rn.VARIANTS:
+        g = got[variant]
+        assert same(g["status"], g0["status"]), variant
+        d, d0 = g["duration"], g0["duration"]
+        gap = np.abs(d - d0) / np.minimum(d, d0)
+        print(f"{name} {variant}: convex retime iterations {g['iters'].tolist()} / {g0['iters'].tolist()}, max |d - d_0| / min {gap.max():.3e}")
+        WORST["retime_paths_convex duration across numberings (relative)"] = max(WORST.get("retime_paths_convex duration across numberings (relative)", 0.0), float(gap.max()))
+        assert (np.abs(d - d0) <= GAP_TOL * np.minimum(d, d0) * (1 + RTOL)).all(), variant
+    for k in OUTPUTS:
+        assert same(got["chain"][k], got["sorted"][k]), k
+
+
 # =================================================================================================== B. solves and sums over slots
 def _close_blocks(a, b, rtol=1e-8):
     np.testing.assert_allclose(a, b, rtol=rtol, atol=1e-10 * max(np.abs(b).max(), 1e-30))

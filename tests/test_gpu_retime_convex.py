@@ -86,14 +86,15 @@ def _recomputed(paths, cols, g, vm, am, subdiv, M):
         np.testing.assert_allclose(g["q"][b][-1], used[:, -1], rtol=0, atol=PATH_ATOL)
 
 
-def _against_reference_and_greedy(h, paths, n_cols, vm, am, subdiv, r):
+def _against_reference_and_greedy(h, paths, n_cols, vm, am, subdiv, r, M=pr.M):
     """The convex call between two greedy calls on the same inputs: durations against the restatement's, never longer
-    than the greedy profile where that converged, and the greedy outputs bit-equal before and after."""
+    than the greedy profile where that converged, and the greedy outputs bit-equal before and after.  A path on which no
+    joint moves has nothing to solve: duration 0, no Newton step, every sample the waypoint, as the restatement has it."""
     B, _, Tp = paths.shape
     cols = [Tp] * B if n_cols is None else [int(c) for c in n_cols]
-    before = h.retime_paths(paths, vm, am, n_cols=n_cols, subdiv=subdiv, n_samples=pr.M)
-    g = h.retime_paths_convex(paths, vm, am, n_cols=n_cols, subdiv=subdiv, n_samples=pr.M, gap_tol=GAP_TOL)
-    after = h.retime_paths(paths, vm, am, n_cols=n_cols, subdiv=subdiv, n_samples=pr.M)
+    before = h.retime_paths(paths, vm, am, n_cols=n_cols, subdiv=subdiv, n_samples=M)
+    g = h.retime_paths_convex(paths, vm, am, n_cols=n_cols, subdiv=subdiv, n_samples=M, gap_tol=GAP_TOL)
+    after = h.retime_paths(paths, vm, am, n_cols=n_cols, subdiv=subdiv, n_samples=M)
     for k in KEYS + ("status",):
         assert _same(before[k], after[k]), k
     assert g["t_grid"].shape == (B, subdiv * (Tp - 1) + 1) and g["iters"].dtype == np.int32
@@ -106,6 +107,11 @@ def _against_reference_and_greedy(h, paths, n_cols, vm, am, subdiv, r):
             assert g["status"][b] == 0 and g["duration"][b] == 0 and g["iters"][b] == 0 and _same(gt, np.zeros(len(gt)))
             assert _same(g["q"][b], r["q"][b]) and _same(g["qd"][b], r["qd"][b]) and _same(g["qdd"][b], r["qdd"][b])
             continue
+        if not np.any(paths[b][:, :C] != paths[b][:, :1]):  # nothing moves
+            assert g["status"][b] == 0 and g["duration"][b] == 0 and g["iters"][b] == 0 and r["duration"][b] == 0 and r["iters"][b] == 0
+            assert np.all(gt == 0) and np.all(gs == 0) and np.all(g["q"][b] == paths[b][:, 0]) and np.all(g["q"][b] == r["q"][b])
+            assert np.all(g["qd"][b] == 0) and np.all(g["qdd"][b] == 0)
+            continue
         if pr.unavoidable_stall(C, subdiv):  # N = 2: no variable
             assert g["status"][b] == NUMERICAL and np.isinf(g["duration"][b]) and _same(gs, np.zeros(len(gs)))
             assert np.all(np.isnan(g["q"][b])) and g["iters"][b] == 0
@@ -116,7 +122,7 @@ def _against_reference_and_greedy(h, paths, n_cols, vm, am, subdiv, r):
         assert abs(d_gpu - d_ref) <= GAP_TOL * d_ref * (1 + RTOL)
         if before["status"][b] == 0:
             assert d_gpu <= before["duration"][b] * (1 + GAP_TOL)
-    _recomputed(paths, cols, g, vm, am, subdiv, pr.M)
+    _recomputed(paths, cols, g, vm, am, subdiv, M)
     return g
 
 

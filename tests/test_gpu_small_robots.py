@@ -394,3 +394,25 @@ def test_retime_against_the_restatement(rigs, kind, T, subdiv):
         one = c.h.retime_batch(plans[i:i + 1], vm, am, subdiv=subdiv, n_samples=16)
         for k in KEYS:
             assert _same(one[k][0], g[k][i]), (k, i)
+
+
+@pytest.mark.parametrize("subdiv", sr.RETIME_SUBDIVS)
+@pytest.mark.parametrize("T", [4, 5])
+@pytest.mark.parametrize("kind", sr.RETIME_KINDS)
+def test_retime_convex_against_the_restatement(rigs, kind, T, subdiv):
+    """gto_retime_paths_convex on the same plans: tests/test_gpu_retime_convex._against_reference_and_greedy (the restatement's
+    statuses and durations within the certified gap, feasibility and samples recomputed from the outputs, never longer than
+    the greedy profile, the greedy outputs untouched) at one and two joints and N = 4 gridpoints (two variables) upwards;
+    with one joint plan 1 has no moving joint: duration 0 and no Newton step."""
+    import retime_convex_ref as cr
+    from test_gpu_retime_convex import GAP_TOL, _against_reference_and_greedy
+    c = rigs((kind, T, (5, 5, 5)))
+    d, plans, vm, am = sr.retime_inputs(kind, T)
+    assert d.ndof == c.desc.ndof and subdiv * (T - 1) + 1 >= 4
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = cr.retime_paths_convex_ref(plans, None, vm, am, subdiv, 16, GAP_TOL)
+    g = _against_reference_and_greedy(c.h, plans, None, vm, am, subdiv, r, M=16)
+    assert (g["status"] == 0).all() and g["t_grid"].shape == (sr.RETIME_B, subdiv * (T - 1) + 1)
+    still = d.ndof == 1
+    assert (g["duration"] > 0).sum() == sr.RETIME_B - still and (g["iters"] > 0).sum() == sr.RETIME_B - still
+    assert not still or (g["duration"][1] == 0 and g["iters"][1] == 0)

@@ -40,10 +40,11 @@ MODES = ("late", "early", "host", "host_pinned")  # host_pinned: the caller's ho
 # are still compared with the idle pass).
 #   iters, status of the solvers   max_iter = 3 ends every solve of the rig at the cap: 3 iterations and GTO_STATUS_MAX_ITER
 #                                  for any valid input (the lift: for every step)
-#   status of the retime calls     GTO_STATUS_CONVERGED for every finite plan that moves
+#   status of the retime calls     GTO_STATUS_CONVERGED for every finite plan that moves (the convex call's iters DO differ
+#                                  with the inputs and are compared like every other output)
 _SOLVER = ("iters", "status")
 SAME_FOR_DECOY = {"solve": _SOLVER, "ik_pose": _SOLVER, "retrieve_lift": _SOLVER, "solve_base": _SOLVER, "retime_batch": ("status",),
-                  "retime_paths": ("status",), "chain": ("ik_iters", "ik_status", "iters", "status", "rt_status", "rp_status")}
+                  "retime_paths": ("status",), "retime_paths_convex": ("status",), "chain": ("ik_iters", "ik_status", "iters", "status", "rt_status", "rp_status")}
 
 
 def torch_dtype(dt):
@@ -302,10 +303,13 @@ def test_a_solve_behind_a_busy_stream(rig, lanes, mode):
 @pytest.mark.parametrize("memory", ["pageable", "pinned"])
 @pytest.mark.parametrize("run", list(soc.REGROW_RUNS))
 def test_more_calls_in_flight_than_pinned_slots_with_regrowth(rig, run, memory):
-    """Six calls (twelve for the base pair) of one fresh handle on one stream behind a hold, each with host arrays and outputs
+    """Six calls (twelve for the base pair and for the retime pair, whose greedy and convex calls alternate on the rt_*
+    workspace they share and of which k_retime_convex rewrites rt_P1 / rt_P2 in place) of one fresh handle on one stream behind
+    a hold, each with host arrays and outputs
     of its own, the host arrays overwritten as soon as their call returns.  Past four calls the pinned ring is reused, which is
-    safe only behind the slot's event; B = 65 and 130 regrow bs_ng / ck_base / the held and filter workspaces by free and
-    allocate while earlier calls are queued, which is safe only because hipFree waits for the device.  That wait also ends
+    safe only behind the slot's event; B = 65 and 130 regrow bs_ng / ck_base / the held, filter and retime workspaces by free and
+    allocate while earlier calls are queued, which is safe only because hipFree waits for the device (so does the first retime
+    call of a handle, which uploads its factor table).  That wait also ends
     the hold, so the stream is held again in front of the next call: every call is entered under a live hold."""
     import torch
     seq = [(e, B) for B in soc.REGROW_BS for e in soc.REGROW_RUNS[run]]

@@ -110,6 +110,36 @@ def test_oracle_evaluation_is_invariant_bit_for_bit(cases, oracle_mod, name, var
     np.testing.assert_allclose(dist, dist0, rtol=1e-14, atol=0)
 
 
+def test_effort_limits_follow_the_renumbering(cases):
+    """effort is joint-indexed like lower, upper and velocity: joint i's limit is joint pi[i]'s in the renumbered description."""
+    c = cases("panda")
+    e0 = c.desc0.effort
+    assert e0 is not None and np.isfinite(e0).any() and len(set(e0.tolist())) > 2   # (87, 12 and the fingers': a shift would show)
+    for variant in rn.VARIANTS:
+        e = c.view(variant).desc.effort
+        assert e is not e0 and all(e[c.pi[i]] == e0[i] for i in range(c.desc0.ndof)), variant
+        assert not same(e, e0)
+
+
+@pytest.mark.parametrize("name,variant", CASE_VARIANTS)
+def test_dynamics_yardstick_is_invariant_bit_for_bit(cases, name, variant):
+    """tests/dynamics_ref.py walks the frames and only ADDRESSES q and tau by joint number: the renumbered robot's torques are
+    the original's, permuted, in every bit -- so the GPU test's bit-equality rule is not blurred by its yardstick."""
+    import dynamics_ref as dr
+    c = cases(name)
+    v0, v = c.view("original"), c.view(variant)
+    ee = c.desc0.frame_index(c.ee)
+    q0, qd0, qdd0, pl = rn.dynamics_inputs(v0)
+    q, qd, qdd, _ = rn.dynamics_inputs(v)
+    assert same(v.old(q, 1), q0) and not same(q, q0) and v.desc.has_inertials
+    for x in ("frame_mass", "frame_com", "frame_inertia"):
+        assert same(getattr(v.desc, x), getattr(c.desc0, x))
+    want = dr.inverse_dynamics_rows(c.desc0, q0, qd0, qdd0, ee, pl)
+    got = dr.inverse_dynamics_rows(v.desc, q, qd, qdd, ee, pl)
+    assert np.abs(want).max() > 1.0 and same(v.old(got, 1), want)
+    assert not same(want, dr.inverse_dynamics_rows(c.desc0, q0, qd0, qdd0))   # the payload is felt
+
+
 # ------------------------------------------------------------------------------------------------- the solves
 def _compare(label, variant, got, want, tols):
     """got / want: (values in the original numbering ..., iterations, status); tols: (rtol, atol) per value.  The chain-order
@@ -233,6 +263,25 @@ def test_retime_inputs_converge_in_the_restatement(cases, name):
         assert (r["status"] == 0).all()
         np.testing.assert_allclose(r["t_grid"], r0["t_grid"], rtol=1e-9)     # RTOL of tests/test_gpu_retime.py
         np.testing.assert_allclose(v.old(r["q"], 2), r0["q"], rtol=0, atol=1e-12)   # PATH_ATOL there
+
+
+@pytest.mark.parametrize("name", rn.NARROW + ["r55"])
+def test_retime_inputs_have_certified_convex_profiles_in_every_numbering(cases, name):
+    """tests/retime_convex_ref.py on the same plans: every profile is certified in every numbering, and since each duration
+    then lies in [T*, (1 + gap_tol) T*] any two differ by at most gap_tol of the smaller -- the rule the GPU test holds the
+    kernel's views to.  (The restatement sums its barrier over the joints too: its views are close, not bit-equal.)"""
+    import retime_convex_ref as cr
+    c = cases(name)
+    res = {}
+    for variant in ("original",) + rn.VARIANTS:
+        plans, vm, am = rn.retime_inputs(c.view(variant))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            res[variant] = r = cr.retime_paths_convex_ref(plans, None, vm, am, 2, 16, 1e-8)
+        assert (r["status"] == 0).all() and (r["duration"] > 0).all() and (r["iters"] > 0).all() and (r["iters"] <= cr.MAX_NEWTON // 2).all()
+    d0 = res["original"]["duration"]
+    for variant in rn.VARIANTS:
+        d = res[variant]["duration"]
+        assert (np.abs(d - d0) <= 1e-8 * np.minimum(d, d0) * (1 + 1e-9)).all()
 
 
 # ------------------------------------------------------------------------------------------------- gto_create

@@ -176,6 +176,26 @@ def test_retiming_inputs_have_converged_profiles(kind, T):
         assert (r["duration"][moving] > 0).all() and (r["duration"][~moving] == 0).all()
 
 
+@pytest.mark.parametrize("T", [4, 5])
+@pytest.mark.parametrize("kind", sr.RETIME_KINDS)
+def test_retiming_inputs_have_certified_convex_profiles(kind, T):
+    """tests/retime_convex_ref.py on the same plans, down to two variables (T = 4, subdiv = 1): every moving plan is solved
+    within the Newton bound the GPU test holds the kernel to, and is never slower than the greedy profile; the plan without
+    a moving joint takes no step."""
+    import retime_convex_ref as cr
+    import retime_ref as rr
+    d, plans, vm, am = sr.retime_inputs(kind, T)
+    moving = np.any(plans != plans[:, :, :1], axis=(1, 2))
+    for subdiv in sr.RETIME_SUBDIVS:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = cr.retime_paths_convex_ref(plans, None, vm, am, subdiv, 16, 1e-8)
+        greedy = rr.retime(plans, vm, am, subdiv, 16)
+        assert (r["status"] == 0).all() and np.isfinite(r["q"]).all()
+        assert (r["iters"][moving] > 0).all() and (r["iters"] <= cr.MAX_NEWTON // 2).all() and (r["iters"][~moving] == 0).all()
+        assert (r["duration"][~moving] == 0).all() and (r["duration"][moving] > 0).all()
+        assert (r["duration"] <= greedy["duration"] * (1 + 1e-8)).all()
+
+
 def _plan_instances_are_decided(solved, cid):
     """The depth image and the sampled box that check_plans is run through: no surface point of the oracle within 1e-9 m of a
     decision, under the shared base and under the per-plan bases, and counts that are not all alike."""

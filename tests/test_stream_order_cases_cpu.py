@@ -73,5 +73,12 @@ def test_the_rig_is_the_one_the_tests_state():
     assert pts.shape == nrm.shape == (65, 3) and np.allclose(np.linalg.norm(nrm, axis=1), 1.0)
     assert soc.FILTER_OBS == (0, 1, 1, 0)
     assert len(soc.REGROW_BS) > 4  # more calls in flight than pinned slots
+    from grasptrajopt_amd import _capi
+    assert soc.CONVEX_MAX_NEWTON == _capi.RETIME_MAX_NEWTON and soc.CONVEX_GAP_TOL == 1e-8
+    assert "retime_paths_convex" in soc.NO_HOST_SYNC and soc.REGROW_RUNS["retime"] == ("retime_paths", "retime_paths_convex")
+    for B in soc.BS + soc.REGROW_BS:  # the convex call: the greedy call's arrays and an iteration count per path
+        a, b = soc.inputs("retime_paths", B), soc.inputs("retime_paths_convex", B)
+        assert list(a.dev) == list(b.dev) and list(a.host) == list(b.host) == ["vmax", "amax"]
+        assert b.outs == {**a.outs, "iters": ((B,), np.dtype(np.int32))} and b.dev["n_cols"].min() >= 3
     sc = soc.scenes()
     assert len(sc) == 2 and tuple(sc[0].shape) == (32, 32, 32) and not np.array_equal(sc[0].c_obs, sc[1].c_obs)
