@@ -166,6 +166,9 @@ def _prototypes():
         "gto_retime_paths_device": (I, [V, I32, I32, V, V, _pd, _pd, I32, I32] + [V] * 8),
         "gto_retime_paths_convex": (I, [V, I32, I32, _pd, _pi, _pd, _pd, I32, I32, D, I32, _pd, _pd, _pd, _pd, _pd, _pd, _pi, _pi]),
         "gto_retime_paths_convex_device": (I, [V, I32, I32, V, V, _pd, _pd, I32, I32, D, I32] + [V] * 9),
+        "gto_retime_paths_torque": (I, [V, I32, I32, _pd, _pi, _pd, _pd, _pd, _pd, _pd, _pd, I32, I32, D, I32, _pd, _pd, _pd, _pd,
+                                        _pd, _pd, _pd, _pi, _pi]),
+        "gto_retime_paths_torque_device": (I, [V, I32, I32, V, V, _pd, _pd, _pd, V, V, V, I32, I32, D, I32] + [V] * 10),
     }
 
 
@@ -173,7 +176,8 @@ PROTOTYPES = _prototypes()
 # Newton steps a path may take in the convex retiming by default: more than twice the largest count seen over the test
 # inputs
 RETIME_MAX_NEWTON = 400
-RETIME_PROFILES = ("greedy", "convex")
+RETIME_PROFILES = ("greedy", "convex", "torque")
+STATUS_INFEASIBLE = 3  # GTO_STATUS_INFEASIBLE: a joint cannot hold the path at rest under its torque limit
 
 
 def retime_profile(profile="greedy", gap_tol=1e-8, max_newton=None):
@@ -188,6 +192,25 @@ def retime_profile(profile="greedy", gap_tol=1e-8, max_newton=None):
         raise ValueError(f"retime: max_newton must be >= 1, got {max_newton}")
     return profile, gap_tol, max_newton
 EXPORTED_SYMBOLS = tuple(PROTOTYPES)
+
+
+def retime_torque_limits(desc, tau_max=None, need_inertials=True):
+    """The checked joint torque limits (ndof,) of a profile="torque" request: ``tau_max`` (one value or one per joint, > 0,
+    +inf = no limit), None = the description's effort limits.  Raises ValueError for anything else and for a description
+    without link inertials, which the torque rows need (need_inertials=False leaves that to the library)."""
+    if need_inertials and not desc.has_inertials:
+        raise ValueError("retime: profile 'torque' needs link inertials on the robot description (RobotDesc.set_link_inertials)")
+    if tau_max is None:
+        if desc.effort is None:
+            raise ValueError("retime: tau_max=None takes the description's effort limits, and it records none")
+        tau_max = desc.effort
+    try:
+        tm = _f64(np.broadcast_to(np.asarray(tau_max, dtype=np.float64), (desc.ndof,)))
+    except ValueError:
+        raise ValueError(f"retime: tau_max must be one value or ({desc.ndof},), got shape {np.shape(tau_max)}") from None
+    if not np.all(tm > 0):  # a NaN among them
+        raise ValueError("retime: tau_max must be > 0 (+inf: no limit)")
+    return tm
 
 
 def payload_arrays(payload, n):
@@ -1110,6 +1133,54 @@ class SolverHandle:
                                                      _p(out["q"], _pd), _p(out["qd"], _pd), _p(out["qdd"], _pd),
                                                      _p(out["status"], _pi), _p(out["iters"], _pi)), "gto_retime_paths_convex")
         return out
+
+    def retime_paths_torque(self, paths, vmax, amax, tau_max=None, payload=None, n_cols=None, subdiv: int = 2,
+                            n_samples: int = 100, gap_tol: float = 1e-8, max_newton: int = RETIME_MAX_NEWTON):
+        """gto_retime_paths_torque: retime_paths_convex with joint torque limits ``tau_max`` ((ndof,) or one value, +inf = no
+        limit; None = the description's effort limits) on top of vmax / amax, the held object included: ``payload`` is the
+        dict of ``inverse_dynamics`` ("mass" and optionally "com", "inertia" on the end-effector frame), each entry one
+        value for the call or one per path.  Returns the dict of retime_paths_convex and tau (B, n_samples, ndof), the joint
+        forces at the samples; status 3 (GTO_STATUS_INFEASIBLE): some joint cannot hold the path at rest, NaN outputs."""
+        d = self.desc
+        paths = _f64(paths)
+        if paths.ndim != 3 or paths.shape[1] != d.ndof:
+            raise ValueError(f"retime_paths_torque: paths must be (B, {d.ndof}, Tp), got {paths.shape}")
+        B, Tp, M = paths.shape[0], paths.shape[2], int(n_samples)
+        N = max(int(subdiv) * (Tp - 1) + 1, 0)
+        nc = None if n_cols is None else _per_instance(n_cols, B)
+        vm, am = self._retime_limits(vmax, amax)
+        tm = retime_torque_limits(d, tau_max, need_inertials=False)
+        pm, pc, pi = payload_arrays(payload, B)
+        self.sync_link_inertials()
+        out = dict(duration=np.empty(B), t_grid=np.empty((B, N)), sd_grid=np.empty((B, N)),
+                   q=np.empty((B, max(M, 0), d.ndof)), qd=np.empty((B, max(M, 0), d.ndof)), qdd=np.empty((B, max(M, 0), d.ndof)),
+                   tau=np.empty((B, max(M, 0), d.ndof)), status=np.empty(B, dtype=np.int32), iters=np.empty(B, dtype=np.int32))
+        self._check(self.lib.gto_retime_paths_torque(self._h, B, Tp, _p(paths, _pd), _p(nc, _pi), _p(vm, _pd), _p(am, _pd),
+                                                     _p(tm, _pd), _p(pm, _pd), _p(pc, _pd), _p(pi, _pd), int(subdiv), M,
+                                                     float(gap_tol), int(max_newton), _p(out["duration"], _pd),
+                                                     _p(out["t_grid"], _pd), _p(out["sd_grid"], _pd), _p(out["q"], _pd),
+                                                     _p(out["qd"], _pd), _p(out["qdd"], _pd), _p(out["tau"], _pd),
+                                                     _p(out["status"], _pi), _p(out["iters"], _pi)), "gto_retime_paths_torque")
+        return out
+
+    def retime_paths_torque_device(self, B, Tp, paths, vmax, amax, tau_max=None, payload_mass=None, payload_com=None,
+                                   payload_inertia=None, n_cols=None, subdiv=2, n_samples=100, gap_tol=1e-8,
+                                   max_newton=RETIME_MAX_NEWTON, duration_out=None, t_grid_out=None, sd_grid_out=None,
+                                   q_out=None, qd_out=None, qdd_out=None, tau_out=None, status_out=None, iters_out=None,
+                                   stream=None):
+        """gto_retime_paths_torque_device: retime_paths_convex_device with torque limits (host values; None = the
+        description's effort limits); payload_mass (B,), payload_com (B, 3), payload_inertia (B, 6) and tau_out
+        (B, n_samples, ndof) are device pointers or None."""
+        vm, am = self._retime_limits(vmax, amax)
+        tm = retime_torque_limits(self.desc, tau_max, need_inertials=False)
+        self.sync_link_inertials()
+        self._check(self.lib.gto_retime_paths_torque_device(self._h, int(B), int(Tp), _vp(paths), _vp(n_cols), _p(vm, _pd),
+                                                            _p(am, _pd), _p(tm, _pd), _vp(payload_mass), _vp(payload_com),
+                                                            _vp(payload_inertia), int(subdiv), int(n_samples), float(gap_tol),
+                                                            int(max_newton), _vp(duration_out), _vp(t_grid_out),
+                                                            _vp(sd_grid_out), _vp(q_out), _vp(qd_out), _vp(qdd_out),
+                                                            _vp(tau_out), _vp(status_out), _vp(iters_out), _vp(stream)),
+                    "gto_retime_paths_torque_device")
 
     def retime_paths_convex_device(self, B, Tp, paths, vmax, amax, n_cols=None, subdiv=2, n_samples=100, gap_tol=1e-8,
                                    max_newton=RETIME_MAX_NEWTON, duration_out=None, t_grid_out=None, sd_grid_out=None,

@@ -44,7 +44,7 @@ static std::string g_create_error;
 
 #define GTO_MAX_LANES 8  // lanes of one solve call (streams, list sets, progress words)
 #define GTO_BASE_PIN_SLOTS 4  // calls whose small host arrays (n_goals, per-plan bases, the filter's view table) may be in flight at once without the host waiting
-#define GTO_STAGE_SLOTS 8  // host arrays of each direction that one host-pointer entry point stages (Staging)
+#define GTO_STAGE_SLOTS 9  // host arrays of each direction that one host-pointer entry point stages (Staging): gto_retime_paths_torque has nine outputs
 #define GTO_NAP_US 50      // the throttle's naps (the host thread of a lane sleep-polls two pinned words); 10-50 us change nothing
 #define GTO_NAP_FEW_US 10  // ... in launches with few instances in flight; 50-200 us change nothing either
 // the deep-gather obstacle variant only up to this many instances in flight (two workgroups per CU: beyond that the
@@ -236,6 +236,9 @@ struct gto_handle {
   // retiming (gto_retime_paths_device): Thomas factors of the not-a-knot system for every column count, workspace grown on
   // demand
   DevBuf rt_fac, rt_S, rt_flag, rt_P1, rt_P2, rt_cap, rt_X, rt_T, rt_stat;
+  // gto_retime_paths_torque: the torque coefficients [B][Nmax][ndof] beside rt_P1 / rt_P2, and the samples [B][M][ndof] that
+  // tau_out is computed from where the caller asked for tau_out without them
+  DevBuf rt_TA, rt_TB, rt_TG, rt_q, rt_qd, rt_qdd;
   bool rt_fac_ready = false;
   // collision checks against a cloud observation (gto_check_plans_device): world points, votes and per-plan bases of a chunk
   DevBuf ck_xyz, ck_flags, ck_base;
@@ -1533,7 +1536,7 @@ class Staging {
     *dptr = h_->out[k].as<T>();
     return GTO_OK;
   }
-  int too_many() { return fail(h_, GTO_ERR_UNSUPPORTED, "internal: more than eight staged arrays of one direction"); }
+  int too_many() { return fail(h_, GTO_ERR_UNSUPPORTED, "internal: more than nine staged arrays of one direction"); }
 
   gto_handle* h_;
   int n_in_ = 0, n_out_ = 0;
@@ -3014,6 +3017,20 @@ struct RetimeNames {
 };
 static const RetimeNames RETIME_BATCH = {"gto_retime_batch", "T", "plans"}, RETIME_PATHS = {"gto_retime_paths", "Tp", "paths"};
 static const RetimeNames RETIME_CONVEX = {"gto_retime_paths_convex", "Tp", "paths"};
+static const RetimeNames RETIME_TORQUE = {"gto_retime_paths_torque", "Tp", "paths"};
+
+// what gto_retime_paths_torque adds to the convex call: the limits (checked, by value), the payload of every path
+// (DEVICE [B], [B,3], [B,6], each or all null) and tau_out (DEVICE [B,M,ndof] or null)
+// the torque entry points' own arguments as the caller gave them (tau_max HOST; the rest HOST or DEVICE like the call)
+struct RetimeTorqueArgs {
+  const double *tau_max, *pl_mass, *pl_com, *pl_inertia;
+  double* tau_out;
+};
+struct RetimeTorqueCall {
+  RetimeTorque lim;
+  const double *pl_mass, *pl_com, *pl_inertia;
+  double* tau_out;
+};
 
 static int retime_check(gto_handle* h, const RetimeNames& nm, int32_t B, int32_t Tp, const double* vmax, const double* amax,
                         int32_t subdiv, int32_t M, RetimeLimits& lim, RetimeDims& d) {
@@ -3044,15 +3061,32 @@ static int retime_convex_check(gto_handle* h, const RetimeNames& nm, const Retim
   return GTO_OK;
 }
 
+// the torque call's own arguments: inertials on the handle, tau_max, and which payload arrays come together
+static int retime_torque_check(gto_handle* h, const RetimeNames& nm, const double* tau_max, const double* payload_mass,
+                               const double* payload_com, const double* payload_inertia, RetimeTorque& lim) {
+  const std::string f = std::string(nm.fn) + ": ";
+  if (!h->has_inertials) return fail(h, GTO_ERR_INVALID_ARG, "no link inertials set");
+  if (!tau_max) return fail(h, GTO_ERR_INVALID_ARG, f + "null limit array");
+  for (int j = 0; j < h->rb.ndof; ++j) {
+    if (!(tau_max[j] > 0.0)) return fail(h, GTO_ERR_INVALID_ARG, f + "tau_max must be > 0 (+inf: no limit)");
+    lim.tau_max[j] = tau_max[j];
+  }
+  if (!payload_mass && (payload_com || payload_inertia))
+    return fail(h, GTO_ERR_INVALID_ARG, f + "payload_com / payload_inertia without payload_mass");
+  return GTO_OK;
+}
+
 static unsigned retime_blocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // the four launches of a checked call (d, lim: retime_check's); n_cols: DEVICE [B] or NULL (every path has Tp columns).
 // cv: NULL for the greedy profile (k_retime_pass), else the convex solve's options (k_retime_convex in its place, which
-// also fills iters_out)
+// also fills iters_out).  tq: NULL, or the torque call's additions: k_retime_torque_rows in front of k_retime_convex_torque,
+// and k_retime_tau behind the samples when tau_out is asked for.  Without tq the launches are what they were.
 static int retime_launch(gto_handle* h, const RetimeDims& d, const RetimeLimits& lim, const double* plans,
                          const int32_t* n_cols, double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out,
                          double* qd_out, double* qdd_out, int32_t* status_out, void* stream,
-                         const RetimeConvex* cv = nullptr, int32_t* iters_out = nullptr) {
+                         const RetimeConvex* cv = nullptr, int32_t* iters_out = nullptr,
+                         const RetimeTorqueCall* tq = nullptr) {
   int rc;
   const int B = d.B, M = d.M;
   HIPCHK(h, hipSetDevice(h->device));
@@ -3073,6 +3107,18 @@ static int retime_launch(gto_handle* h, const RetimeDims& d, const RetimeLimits&
   if ((rc = ensure(h, h->rt_X, nB * N * sizeof(double)))) return rc;
   if ((rc = ensure(h, h->rt_T, nB * N * sizeof(double)))) return rc;
   if ((rc = ensure(h, h->rt_stat, nB * sizeof(int32_t)))) return rc;
+  if (tq) {
+    for (DevBuf* w : {&h->rt_TA, &h->rt_TB, &h->rt_TG})
+      if ((rc = ensure(h, *w, nB * N * nd * sizeof(double)))) return rc;
+    if (tq->tau_out) {  // the samples tau_out is computed from, where the caller does not take them
+      if (!q_out && (rc = ensure(h, h->rt_q, nB * M * nd * sizeof(double)))) return rc;
+      if (!qd_out && (rc = ensure(h, h->rt_qd, nB * M * nd * sizeof(double)))) return rc;
+      if (!qdd_out && (rc = ensure(h, h->rt_qdd, nB * M * nd * sizeof(double)))) return rc;
+      if (!q_out) q_out = h->rt_q.as<double>();
+      if (!qd_out) qd_out = h->rt_qd.as<double>();
+      if (!qdd_out) qdd_out = h->rt_qdd.as<double>();
+    }
+  }
   double *S = h->rt_S.as<double>(), *P1 = h->rt_P1.as<double>(), *P2 = h->rt_P2.as<double>(), *cap = h->rt_cap.as<double>();
   double *X = h->rt_X.as<double>(), *Tg = h->rt_T.as<double>();
   int32_t *flag = h->rt_flag.as<int32_t>(), *stat = h->rt_stat.as<int32_t>();
@@ -3080,7 +3126,17 @@ static int retime_launch(gto_handle* h, const RetimeDims& d, const RetimeLimits&
                      h->rt_fac.as<const double>(), n_cols, d, S, flag);
   hipLaunchKernelGGL(k_retime_grid, dim3(retime_blocks((long long)B * N, 256)), dim3(256), 0, st, plans, S, flag, n_cols, lim,
                      d, P1, P2, cap);
-  if (cv)
+  const int rows = rnea_rows_per_block(h->rb.n_frames);
+  const size_t rnea_lds = sizeof(double) * GTO_RNEA_SLOTS * h->rb.n_frames * rows;
+  if (tq) {
+    double *TA = h->rt_TA.as<double>(), *TB = h->rt_TB.as<double>(), *TG = h->rt_TG.as<double>();
+    hipLaunchKernelGGL(k_retime_torque_rows, dim3(retime_blocks((long long)B * N, rows)), dim3(GTO_WAVE), rnea_lds, st, h->d_rb,
+                       h->dyn_buf.as<const DynDev>(), plans, S, flag, n_cols, P1, P2, tq->pl_mass, tq->pl_com, tq->pl_inertia, d,
+                       rows, TA, TB, TG);
+    hipLaunchKernelGGL(k_retime_convex_torque, dim3(B), dim3(64), GTO_RT_LDS_ARRAYS * N * sizeof(double), st, P1, P2, cap, flag,
+                       n_cols, lim, d, *cv, X, Tg, stat, duration_out, t_grid_out, sd_grid_out, status_out, iters_out, tq->lim,
+                       TA, TB, TG);
+  } else if (cv)
     hipLaunchKernelGGL(k_retime_convex, dim3(B), dim3(64), GTO_RT_LDS_ARRAYS * N * sizeof(double), st, P1, P2, cap, flag, n_cols, lim, d, *cv,
                        X, Tg, stat, duration_out, t_grid_out, sd_grid_out, status_out, iters_out);
   else
@@ -3089,6 +3145,10 @@ static int retime_launch(gto_handle* h, const RetimeDims& d, const RetimeLimits&
   if (q_out || qd_out || qdd_out)
     hipLaunchKernelGGL(k_retime_sample, dim3(retime_blocks((long long)B * M, 256)), dim3(256), 0, st, plans, S, X, Tg, stat,
                        n_cols, d, q_out, qd_out, qdd_out);
+  if (tq && tq->tau_out)
+    hipLaunchKernelGGL(k_retime_tau, dim3(retime_blocks((long long)B * M, rows)), dim3(GTO_WAVE), rnea_lds, st, h->d_rb,
+                       h->dyn_buf.as<const DynDev>(), (long long)B * M, M, rows, q_out, qd_out, qdd_out, tq->pl_mass, tq->pl_com,
+                       tq->pl_inertia, tq->tau_out);
   HIPCHK(h, hipGetLastError());
   return GTO_OK;
 }
@@ -3098,30 +3158,40 @@ static int retime_device(gto_handle* h, const RetimeNames& nm, int32_t B, int32_
                          const int32_t* n_cols, const double* vmax, const double* amax, int32_t subdiv, int32_t M,
                          double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out, double* qd_out,
                          double* qdd_out, int32_t* status_out, void* stream, const RetimeConvex* cv = nullptr,
-                         int32_t* iters_out = nullptr) {
+                         int32_t* iters_out = nullptr, const RetimeTorqueArgs* ta = nullptr) {
   if (!h) return GTO_ERR_INVALID_ARG;
   RetimeLimits lim = {};
   RetimeDims d = {};
+  RetimeTorqueCall tq = {};
   int rc = retime_check(h, nm, B, Tp, vmax, amax, subdiv, M, lim, d);
   if (rc) return rc;
   if (cv && (rc = retime_convex_check(h, nm, *cv))) return rc;
+  if (ta && (rc = retime_torque_check(h, nm, ta->tau_max, ta->pl_mass, ta->pl_com, ta->pl_inertia, tq.lim))) return rc;
   if (B == 0) return GTO_OK;
   if (!paths) return fail(h, GTO_ERR_INVALID_ARG, std::string(nm.fn) + ": null " + nm.array);
+  if (ta) tq.pl_mass = ta->pl_mass, tq.pl_com = ta->pl_com, tq.pl_inertia = ta->pl_inertia, tq.tau_out = ta->tau_out;
   return retime_launch(h, d, lim, paths, n_cols, duration_out, t_grid_out, sd_grid_out, q_out, qd_out, qdd_out, status_out,
-                       stream, cv, iters_out);
+                       stream, cv, iters_out, ta ? &tq : nullptr);
 }
 
 // the host-pointer entry points: n_cols is a HOST array here (or NULL), checked before anything is staged
 static int retime_host(gto_handle* h, const RetimeNames& nm, int32_t B, int32_t Tp, const double* paths,
                        const int32_t* n_cols, const double* vmax, const double* amax, int32_t subdiv, int32_t M,
                        double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out, double* qd_out,
-                       double* qdd_out, int32_t* status_out, const RetimeConvex* cv = nullptr, int32_t* iters_out = nullptr) {
+                       double* qdd_out, int32_t* status_out, const RetimeConvex* cv = nullptr, int32_t* iters_out = nullptr,
+                       const RetimeTorqueArgs* ta = nullptr) {
   if (!h) return GTO_ERR_INVALID_ARG;
   RetimeLimits lim = {};
   RetimeDims d = {};
+  RetimeTorqueCall tq = {};
   int rc = retime_check(h, nm, B, Tp, vmax, amax, subdiv, M, lim, d);
   if (rc) return rc;
   if (cv && (rc = retime_convex_check(h, nm, *cv))) return rc;
+  if (ta && (rc = retime_torque_check(h, nm, ta->tau_max, ta->pl_mass, ta->pl_com, ta->pl_inertia, tq.lim))) return rc;
+  if (ta && ta->pl_mass)
+    for (int32_t b = 0; b < B; ++b)
+      if (!(ta->pl_mass[b] >= 0) || !std::isfinite(ta->pl_mass[b]))
+        return fail(h, GTO_ERR_INVALID_ARG, std::string(nm.fn) + ": payload mass must be >= 0 and finite");
   if (B == 0) return GTO_OK;
   if (!paths) return fail(h, GTO_ERR_INVALID_ARG, std::string(nm.fn) + ": null " + nm.array);
   if (n_cols)
@@ -3145,7 +3215,14 @@ static int retime_host(gto_handle* h, const RetimeNames& nm, int32_t B, int32_t 
   if ((rc = io.out(qdd_out, nB * nM * nd, &d_qdd))) return rc;
   if ((rc = io.out(status_out, nB, &d_st))) return rc;
   if ((rc = io.out(iters_out, nB, &d_it))) return rc;
-  if ((rc = retime_launch(h, d, lim, d_paths, d_nc, d_dur, d_t, d_sd, d_q, d_qd, d_qdd, d_st, nullptr, cv, d_it))) return rc;
+  if (ta) {
+    if ((rc = io.in(ta->pl_mass, nB, &tq.pl_mass))) return rc;  // (a null array: a null device pointer)
+    if ((rc = io.in(ta->pl_com, nB * 3, &tq.pl_com))) return rc;
+    if ((rc = io.in(ta->pl_inertia, nB * 6, &tq.pl_inertia))) return rc;
+    if ((rc = io.out(ta->tau_out, nB * nM * nd, &tq.tau_out))) return rc;
+  }
+  if ((rc = retime_launch(h, d, lim, d_paths, d_nc, d_dur, d_t, d_sd, d_q, d_qd, d_qdd, d_st, nullptr, cv, d_it, ta ? &tq : nullptr)))
+    return rc;
   return io.finish();
 }
 
@@ -3182,6 +3259,31 @@ int gto_retime_paths_convex(gto_handle* h, int32_t B, int32_t Tp, const double* 
   const RetimeConvex cv = {gap_tol, max_newton};
   return retime_host(h, RETIME_CONVEX, B, Tp, paths, n_cols, vmax, amax, subdiv, M, duration_out, t_grid_out,
                      sd_grid_out, q_out, qd_out, qdd_out, status_out, &cv, iters_out);
+}
+
+// joint torque limits and the held object on top of the convex program (k_retime_torque_rows, k_retime_convex_torque)
+int gto_retime_paths_torque_device(gto_handle* h, int32_t B, int32_t Tp, const double* paths, const int32_t* n_cols,
+                                   const double* vmax, const double* amax, const double* tau_max, const double* payload_mass,
+                                   const double* payload_com, const double* payload_inertia, int32_t subdiv, int32_t M,
+                                   double gap_tol, int32_t max_newton, double* duration_out, double* t_grid_out,
+                                   double* sd_grid_out, double* q_out, double* qd_out, double* qdd_out, double* tau_out,
+                                   int32_t* status_out, int32_t* iters_out, void* stream) {
+  const RetimeConvex cv = {gap_tol, max_newton};
+  const RetimeTorqueArgs ta = {tau_max, payload_mass, payload_com, payload_inertia, tau_out};
+  return retime_device(h, RETIME_TORQUE, B, Tp, paths, n_cols, vmax, amax, subdiv, M, duration_out, t_grid_out,
+                       sd_grid_out, q_out, qd_out, qdd_out, status_out, stream, &cv, iters_out, &ta);
+}
+
+int gto_retime_paths_torque(gto_handle* h, int32_t B, int32_t Tp, const double* paths, const int32_t* n_cols,
+                            const double* vmax, const double* amax, const double* tau_max, const double* payload_mass,
+                            const double* payload_com, const double* payload_inertia, int32_t subdiv, int32_t M,
+                            double gap_tol, int32_t max_newton, double* duration_out, double* t_grid_out, double* sd_grid_out,
+                            double* q_out, double* qd_out, double* qdd_out, double* tau_out, int32_t* status_out,
+                            int32_t* iters_out) {
+  const RetimeConvex cv = {gap_tol, max_newton};
+  const RetimeTorqueArgs ta = {tau_max, payload_mass, payload_com, payload_inertia, tau_out};
+  return retime_host(h, RETIME_TORQUE, B, Tp, paths, n_cols, vmax, amax, subdiv, M, duration_out, t_grid_out,
+                     sd_grid_out, q_out, qd_out, qdd_out, status_out, &cv, iters_out, &ta);
 }
 
 // plans of the handle's horizon: gto_retime_paths with Tp = T and every column used

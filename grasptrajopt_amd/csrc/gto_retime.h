@@ -16,11 +16,15 @@
 //                     lane per plan (every pair in one lane) measured 0.6-0.1x of this rate and was dropped.
 //   k_retime_convex   one wave per plan, in place of k_retime_pass for gto_retime_paths_convex[_device]: the time optimum of
 //                     the same grid constraints by a log-barrier Newton method (below, beside the pass)
+//   k_retime_torque_rows, k_retime_convex_torque, k_retime_tau   gto_retime_paths_torque[_device]: the inverse dynamics'
+//                     coefficients along the path (three rt_rnea passes per gridpoint), the same Newton method with the joint
+//                     torque rows added, the joint forces at the samples
 //   k_retime_sample   one lane per (plan, sample): binary search over the gridpoint times, evaluation on the spline
 // Rows are laid out for the largest count: paths and slopes [B][ndof][Tp], grid arrays [B][Nmax], Nmax = subdiv (Tp-1) + 1.
 // Nothing a path's arithmetic uses depends on Tp or on its place in the batch.
 #pragma once
 #include "gto_device.h"
+#include "gto_dynamics.h"
 
 #define GTO_RETIME_MAX_N 1024             // gridpoints per plan (the pass kernel keeps the controllable sets in LDS)
 #define GTO_RETIME_LINES (GTO_MAX_DOF + 1)  // bounds on u of each side: one per moving joint, one from the next set
@@ -334,11 +338,42 @@ __device__ __forceinline__ double rt_wave_sum(double v) {
   return v;
 }
 
+// Joint torque limits of gto_retime_paths_torque, passed by value like RetimeLimits
+struct RetimeTorque {
+  double tau_max[GTO_MAX_DOF];  // > 0, +inf = no limit
+};
+// the torque coefficients of k_retime_torque_rows [Nmax][ndof] of one path (null in the instantiation without them)
+struct RetimeTorqueRows {
+  const double *ta, *tb, *tg;
+};
+
+// Torque row of gridpoint i and joint j (k = i ndof + j) on the interior variables: tau = A1 x_{i+1} + K x_i + g within
+// -+ tmax, A1 = a c (0 where x_{i+1} is the end, in1 false), K = b - a c (0 where x_i is the start, in0 false).  Returns
+// whether the row is part of the program: a joint without a limit has none, and neither has a row that holds no variable.
+__device__ __forceinline__ bool rt_torque_row(const RetimeTorqueRows& tr, long long k, double c, bool in0, bool in1, double tmax,
+                                              double& A1, double& K) {
+  if (tmax == INFINITY) return false;
+  const double ac = tr.ta[k] * c;
+  A1 = in1 ? ac : 0.0;
+  K = in0 ? tr.tb[k] - ac : 0.0;
+  return A1 != 0.0 || K != 0.0;
+}
+
+// The row's torque at (x_i, x_{i+1}) = (xi, xn): a c (xn - xi) + b xi + g, which is A1 xn + K xi + g wherever a mask is off
+// (x_0 = x_{N-1} = 0).  Written with the difference first and explicit fmas: A1 xn and K xi are each N/2 times the torque and
+// cancel, and a slack of 1e-11 tau_max would be lost in their round-off; and every site that evaluates a row (the barrier
+// sum, both neighbouring variables' gathers, the step room) gets the same bits, so that the 2x2 block a row adds to the
+// Hessian stays the rank-one matrix it is.
+__device__ __forceinline__ double rt_torque_tau(const RetimeTorqueRows& tr, long long k, double c, double xi, double xn) {
+  return fma(tr.ta[k] * c, xn - xi, fma(tr.tb[k], xi, tr.tg[k]));
+}
+
 // T and the barrier sum phi = -sum log(slack) at y = x + eta dx (F_mu = T + mu phi); T = inf where y is not strictly
-// inside.  Gridpoint i owns its segment's time, its own two box rows and its lines.
+// inside.  Gridpoint i owns its segment's time, its own two box rows, its lines and (TORQUE) its torque rows.
+template <bool TORQUE>
 __device__ __forceinline__ void rt_convex_eval(const double* x, const double* dx, double eta, const double* al,
                                                const double* be, const double* cap, int N, int ndof, int lane, double& T,
-                                               double& phi) {
+                                               double& phi, const RetimeTorque& tq, const RetimeTorqueRows& tr) {
   const double c = 0.5 * (double)(N - 1), w = 2.0 / (double)(N - 1);
   double Tl = 0.0, ph = 0.0;
   bool in = true;
@@ -361,6 +396,15 @@ __device__ __forceinline__ void rt_convex_eval(const double* x, const double* dx
       in = in && a - r > 0.0 && a + r > 0.0;
       ph -= log(a - r) + log(a + r);
     }
+    if constexpr (TORQUE)
+      for (int j = 0; j < ndof; ++j) {
+        const double tm = tq.tau_max[j];
+        double A1, K;
+        if (!rt_torque_row(tr, (long long)i * ndof + j, c, i >= 1, i + 1 <= N - 2, tm, A1, K)) continue;
+        const double r = rt_torque_tau(tr, (long long)i * ndof + j, c, yi, yn);
+        in = in && tm - r > 0.0 && tm + r > 0.0;
+        ph -= log(tm - r) + log(tm + r);
+      }
   }
   T = rt_wave_sum(in ? Tl : INFINITY);
   phi = rt_wave_sum(ph);
@@ -392,13 +436,19 @@ __device__ __forceinline__ void rt_tridiag_serial(double* dg, const double* e, d
 // Nmax doubles (x, gradient, diagonal, off-diagonal, step; GTO_RT_LDS_ARRAYS), passed as the launch's dynamic size.
 // stat: what k_retime_sample asks, "has a profile" (GTO_STATUS_CONVERGED for GTO_STATUS_MAX_ITER too, whose feasible
 // profile is sampled); status_out: the status of the contract.
-__global__ __launch_bounds__(64) void k_retime_convex(double* __restrict__ al, double* __restrict__ be,
-                                                      const double* __restrict__ xcap, const int32_t* __restrict__ flag,
-                                                      const int32_t* __restrict__ n_cols, RetimeLimits lim, RetimeDims d,
-                                                      RetimeConvex cv, double* __restrict__ X, double* __restrict__ Tg,
-                                                      int32_t* __restrict__ stat, double* __restrict__ duration_out,
-                                                      double* __restrict__ t_out, double* __restrict__ sd_out,
-                                                      int32_t* __restrict__ status_out, int32_t* __restrict__ iters_out) {
+// TORQUE (k_retime_convex_torque, gto_retime_paths_torque): the torque rows of k_retime_torque_rows join the program --
+// TA, TB, TG [B][Nmax][ndof], tau = TA u + TB x + TG at every gridpoint i <= N-2 within -+ tq.tau_max.  Before the solve
+// the wave looks at the path's own gridpoints 0 .. N-1 once: a non-finite coefficient is GTO_STATUS_NUMERICAL, a joint that
+// cannot hold the path at rest somewhere (|TG| >= tau_max) GTO_STATUS_INFEASIBLE, both with NaN outputs and no Newton step.
+// Without TORQUE the body is the one k_retime_convex had before the flag: every addition sits behind `if constexpr`.
+template <bool TORQUE>
+__device__ __forceinline__ void rt_convex_solve(double* __restrict__ al, double* __restrict__ be, const double* __restrict__ xcap,
+                                                const int32_t* __restrict__ flag, const int32_t* __restrict__ n_cols,
+                                                const RetimeLimits& lim, const RetimeDims& d, const RetimeConvex& cv,
+                                                double* __restrict__ X, double* __restrict__ Tg, int32_t* __restrict__ stat,
+                                                double* __restrict__ duration_out, double* __restrict__ t_out,
+                                                double* __restrict__ sd_out, int32_t* __restrict__ status_out,
+                                                int32_t* __restrict__ iters_out, const RetimeTorque& tq, RetimeTorqueRows tr) {
   extern __shared__ double rt_lds[];
   double *x = rt_lds, *g = x + d.Nmax, *dg = g + d.Nmax, *e = dg + d.Nmax, *dx = e + d.Nmax;
   const long long b = blockIdx.x;
@@ -413,9 +463,22 @@ __global__ __launch_bounds__(64) void k_retime_convex(double* __restrict__ al, d
   const double* cap = xcap + o;
   int status = GTO_STATUS_CONVERGED, it = 0;
   if (bad) status = GTO_STATUS_NUMERICAL;
+  if constexpr (TORQUE) {
+    tr.ta += o * ndof, tr.tb += o * ndof, tr.tg += o * ndof;
+    if (!bad) {  // the path's own gridpoints, the last one included: the robot holds there too
+      bool wild = false, over = false;
+      for (int k = lane; k < N * ndof; k += 64) {
+        const double gk = tr.tg[k];
+        wild = wild || !isfinite(tr.ta[k]) || !isfinite(tr.tb[k]) || !isfinite(gk);
+        over = over || fabs(gk) >= tq.tau_max[k % ndof];
+      }
+      if (__ballot(wild) != 0) status = GTO_STATUS_NUMERICAL;
+      else if (__ballot(over) != 0) status = GTO_STATUS_INFEASIBLE;
+    }
+  }
   for (int i = lane; i < N && !bad; i += 64) x[i] = 0.0, dx[i] = 0.0;
   __syncthreads();
-  if (!bad && moving && n >= 1) {
+  if ((TORQUE ? status == GTO_STATUS_CONVERGED : !bad) && moving && n >= 1) {
     // the lines, once per plan
     for (int k = lane; k < (N - 1) * ndof; k += 64) {
       double a, bt;
@@ -439,12 +502,22 @@ __global__ __launch_bounds__(64) void k_retime_convex(double* __restrict__ al, d
         if (k > 0.0) top = fmin(top, a / k);
         rows += 2;
       }
+      if constexpr (TORQUE)
+        for (int j = 0; j < ndof; ++j) {  // tau = (A1 + K) eps + g at x = eps 1: the side that eps moves it towards
+          const double tm = tq.tau_max[j];
+          double A1, K;
+          if (!rt_torque_row(tr, (long long)i * ndof + j, c, i >= 1, i + 1 <= n, tm, A1, K)) continue;
+          const double k = A1 + K, gk = tr.tg[(long long)i * ndof + j];
+          if (k > 0.0) top = fmin(top, (tm - gk) / k);
+          if (k < 0.0) top = fmin(top, (tm + gk) / -k);
+          rows += 2;
+        }
     }
     const double eps = 0.5 * rt_wave_min(top), m = rt_wave_sum((double)rows);
     for (int v = 1 + lane; v <= n; v += 64) x[v] = eps;
     __syncthreads();
     double T, phi;
-    rt_convex_eval(x, dx, 0.0, al, be, cap, N, ndof, lane, T, phi);
+    rt_convex_eval<TORQUE>(x, dx, 0.0, al, be, cap, N, ndof, lane, T, phi, tq, tr);
     double mu = T / m;
     if (!(eps > 0.0) || !isfinite(T) || !isfinite(phi)) status = GTO_STATUS_NUMERICAL;
     while (status == GTO_STATUS_CONVERGED) {
@@ -482,6 +555,26 @@ __global__ __launch_bounds__(64) void k_retime_convex(double* __restrict__ al, d
           dv += mu * k * k * hh;
           if (v < n) ev += mu * k * c * hh;
         }
+        if constexpr (TORQUE)
+          for (int j = 0; j < ndof; ++j) {
+            const double tm = tq.tau_max[j];
+            double A1, K;
+            // the torque row of gridpoint v-1: coefficient A1 on x_v
+            if (rt_torque_row(tr, (long long)(v - 1) * ndof + j, c, v - 1 >= 1, true, tm, A1, K)) {
+              const double r = rt_torque_tau(tr, (long long)(v - 1) * ndof + j, c, xm, x0);
+              const double ip = 1.0 / (tm - r), im = 1.0 / (tm + r);
+              gv += mu * A1 * (ip - im);
+              dv += mu * A1 * A1 * (ip * ip + im * im);
+            }
+            // the torque row of gridpoint v: coefficient K on x_v, A1 on x_{v+1}
+            if (rt_torque_row(tr, (long long)v * ndof + j, c, true, v < n, tm, A1, K)) {
+              const double r = rt_torque_tau(tr, (long long)v * ndof + j, c, x0, xp);
+              const double ip = 1.0 / (tm - r), im = 1.0 / (tm + r), hh = ip * ip + im * im;
+              gv += mu * K * (ip - im);
+              dv += mu * K * K * hh;
+              ev += mu * K * A1 * hh;  // A1 = 0 at v = n
+            }
+          }
         g[v] = gv, dg[v] = dv, e[v] = ev;
       }
       __syncthreads();
@@ -520,13 +613,23 @@ __global__ __launch_bounds__(64) void k_retime_convex(double* __restrict__ al, d
           if (dr > 0.0) room = fmin(room, (a - r) / dr);
           if (dr < 0.0) room = fmin(room, (a + r) / -dr);
         }
+        if constexpr (TORQUE)
+          for (int j = 0; j < ndof; ++j) {
+            const double tm = tq.tau_max[j];
+            double A1, K;
+            if (!rt_torque_row(tr, (long long)i * ndof + j, c, i >= 1, i + 1 <= n, tm, A1, K)) continue;
+            const double r = rt_torque_tau(tr, (long long)i * ndof + j, c, xi, xn);
+            const double dr = fma(tr.ta[(long long)i * ndof + j] * c, dn - di, tr.tb[(long long)i * ndof + j] * di);
+            if (dr > 0.0) room = fmin(room, (tm - r) / dr);
+            if (dr < 0.0) room = fmin(room, (tm + r) / -dr);
+          }
       }
       double eta = fmin(1.0, 0.99 * rt_wave_min(room));
       // backtracking on F_mu; a difference below the round-off of F_mu counts as a decrease
       const double F0 = T + mu * phi;
       for (int k = 0; k < GTO_RT_BACKTRACKS; ++k, eta *= 0.5) {
         double Tn, phin;
-        rt_convex_eval(x, dx, eta, al, be, cap, N, ndof, lane, Tn, phin);
+        rt_convex_eval<TORQUE>(x, dx, eta, al, be, cap, N, ndof, lane, Tn, phin, tq, tr);
         if (Tn + mu * phin <= F0 - GTO_RT_ARMIJO * eta * dec + 4e-16 * fabs(F0)) {
           __syncthreads();
           for (int v = 1 + lane; v <= n; v += 64) x[v] = fma(eta, dx[v], x[v]);
@@ -539,16 +642,16 @@ __global__ __launch_bounds__(64) void k_retime_convex(double* __restrict__ al, d
     }
   }
   // times and outputs
-  if (status == GTO_STATUS_NUMERICAL) {
+  if (status == GTO_STATUS_NUMERICAL || (TORQUE && status == GTO_STATUS_INFEASIBLE)) {
     for (int i = lane; i < d.Nmax; i += 64) {
       X[o + i] = NAN, Tg[o + i] = NAN;
       if (t_out) t_out[o + i] = NAN;
       if (sd_out) sd_out[o + i] = NAN;
     }
     if (lane == 0) {
-      stat[b] = GTO_STATUS_NUMERICAL;
+      stat[b] = GTO_STATUS_NUMERICAL;  // no profile to sample
       if (duration_out) duration_out[b] = NAN;
-      if (status_out) status_out[b] = GTO_STATUS_NUMERICAL;
+      if (status_out) status_out[b] = TORQUE ? status : GTO_STATUS_NUMERICAL;
       if (iters_out) iters_out[b] = it;
     }
     return;
@@ -581,6 +684,98 @@ __global__ __launch_bounds__(64) void k_retime_convex(double* __restrict__ al, d
     if (status_out) status_out[b] = ok ? status : GTO_STATUS_NUMERICAL;
     if (iters_out) iters_out[b] = it;
   }
+}
+
+__global__ __launch_bounds__(64) void k_retime_convex(double* __restrict__ al, double* __restrict__ be,
+                                                      const double* __restrict__ xcap, const int32_t* __restrict__ flag,
+                                                      const int32_t* __restrict__ n_cols, RetimeLimits lim, RetimeDims d,
+                                                      RetimeConvex cv, double* __restrict__ X, double* __restrict__ Tg,
+                                                      int32_t* __restrict__ stat, double* __restrict__ duration_out,
+                                                      double* __restrict__ t_out, double* __restrict__ sd_out,
+                                                      int32_t* __restrict__ status_out, int32_t* __restrict__ iters_out) {
+  const RetimeTorque none = {};
+  rt_convex_solve<false>(al, be, xcap, flag, n_cols, lim, d, cv, X, Tg, stat, duration_out, t_out, sd_out, status_out, iters_out,
+                         none, {nullptr, nullptr, nullptr});
+}
+
+__global__ __launch_bounds__(64) void k_retime_convex_torque(
+    double* __restrict__ al, double* __restrict__ be, const double* __restrict__ xcap, const int32_t* __restrict__ flag,
+    const int32_t* __restrict__ n_cols, RetimeLimits lim, RetimeDims d, RetimeConvex cv, double* __restrict__ X,
+    double* __restrict__ Tg, int32_t* __restrict__ stat, double* __restrict__ duration_out, double* __restrict__ t_out,
+    double* __restrict__ sd_out, int32_t* __restrict__ status_out, int32_t* __restrict__ iters_out, RetimeTorque tq,
+    const double* __restrict__ TA, const double* __restrict__ TB, const double* __restrict__ TG) {
+  rt_convex_solve<true>(al, be, xcap, flag, n_cols, lim, d, cv, X, Tg, stat, duration_out, t_out, sd_out, status_out, iters_out,
+                        tq, {TA, TB, TG});
+}
+
+// The torque coefficients of every (path, gridpoint) row id = b Nmax + i, i < N_b: with the path's payload on frame_ee,
+//   TG = ID(q, 0, 0),  TA = ID(q, 0, p1) - TG,  TB = ID(q, p1, p2) - TG      [B][Nmax][ndof] each,
+// so that tau = TA u + TB x + TG along the path (inverse dynamics is affine in qdd and quadratic in qd, and qd = p1 sd,
+// qdd = p1 u + p2 x).  q: the spline's value at the gridpoint (rt_piece; the first waypoint of a row flagged constant, and of
+// every row at C = 1); p1, p2: k_retime_grid's, which hold 0 on the constant rows.  One lane per row, `rows` of them per
+// 64-lane workgroup with k_inverse_dynamics' LDS layout; three rt_rnea passes over the lane's own column.  A joint that no
+// frame names keeps 0.  A path flagged non-finite (a wild count among them) is left alone: k_retime_convex_torque does not
+// read its rows.  A payload mass that is negative or not finite (a device value no host has seen) makes the row's TG NaN.
+__global__ __launch_bounds__(GTO_WAVE) void k_retime_torque_rows(
+    const RobotDev* __restrict__ rb, const DynDev* __restrict__ dyn, const double* __restrict__ Q, const double* __restrict__ S,
+    const int32_t* __restrict__ flag, const int32_t* __restrict__ n_cols, const double* __restrict__ P1,
+    const double* __restrict__ P2, const double* __restrict__ pl_mass, const double* __restrict__ pl_com,
+    const double* __restrict__ pl_inertia, RetimeDims d, int rows, double* __restrict__ TA, double* __restrict__ TB,
+    double* __restrict__ TG) {
+  extern __shared__ __attribute__((aligned(16))) double smem_rnea[];
+  const int lane = threadIdx.x;
+  const long long id = (long long)blockIdx.x * rows + lane;
+  if (lane >= rows || id >= (long long)d.B * d.Nmax) return;
+  const long long b = id / d.Nmax;
+  const int g = (int)(id - b * d.Nmax), T = d.Tp, ndof = d.ndof;
+  const int C = rt_cols(n_cols, b, T), N = d.subdiv * (C - 1) + 1;
+  if (C == 0 || g >= N) return;
+  const int32_t* fl = flag + b * ndof;
+  for (int j = 0; j < ndof; ++j)
+    if (fl[j] == GTO_RT_NONFINITE) return;
+  const int k = max(min(g / d.subdiv, C - 2), 0);  // as in k_retime_grid
+  const double r = (double)(g - k * d.subdiv) / (double)(N - 1);
+  const double invh = (double)(C - 1);
+  const double *y = Q + b * ndof * T, *s = S + b * ndof * T;
+  const double *p1 = P1 + id * ndof, *p2 = P2 + id * ndof;
+  double *ta = TA + id * ndof, *tb = TB + id * ndof, *tg = TG + id * ndof;
+  const RneaPayload pl = rnea_payload(pl_mass, pl_com, pl_inertia, (size_t)b);
+  const bool mass_ok = pl.m >= 0.0 && isfinite(pl.m);
+  for (int j = 0; j < ndof; ++j) ta[j] = 0.0, tb[j] = 0.0, tg[j] = mass_ok ? 0.0 : NAN;
+  if (!mass_ok) return;
+  auto q = [&](int j) {
+    if (fl[j] != GTO_RT_MOVING) return y[(long long)j * T];
+    double qv, d1, d2;
+    rt_piece(y + (long long)j * T, s + (long long)j * T, k, r, invh, qv, d1, d2);
+    return qv;
+  };
+  auto zero = [](int) { return 0.0; };
+  double* st = smem_rnea + lane;
+  rt_rnea(rb, dyn, pl, st, rows, q, zero, zero, [&](int j, double v) { tg[j] = v; });
+  rt_rnea(rb, dyn, pl, st, rows, q, zero, [&](int j) { return p1[j]; }, [&](int j, double v) { ta[j] = v - tg[j]; });
+  rt_rnea(rb, dyn, pl, st, rows, q, [&](int j) { return p1[j]; }, [&](int j) { return p2[j]; },
+          [&](int j, double v) { tb[j] = v - tg[j]; });
+}
+
+// tau_out [B][M][ndof] of gto_retime_paths_torque: k_inverse_dynamics over the B M sample rows (q, qd, qdd of
+// k_retime_sample), the payload of row id being its path's, b = id / M.  The same arithmetic on the same values: the bits of
+// gto_inverse_dynamics on these rows with the payload repeated per sample.
+__global__ __launch_bounds__(GTO_WAVE) void k_retime_tau(const RobotDev* __restrict__ rb, const DynDev* __restrict__ dyn, long long n,
+                                                         int M, int rows, const double* __restrict__ q, const double* __restrict__ qd,
+                                                         const double* __restrict__ qdd, const double* __restrict__ pl_mass,
+                                                         const double* __restrict__ pl_com, const double* __restrict__ pl_inertia,
+                                                         double* __restrict__ tau_out) {
+  extern __shared__ __attribute__((aligned(16))) double smem_rnea[];
+  const int lane = threadIdx.x;
+  const long long row = (long long)blockIdx.x * rows + lane;
+  if (lane >= rows || row >= n) return;
+  const int ndof = rb->ndof;
+  const double *qr = q + row * ndof, *qdr = qd + row * ndof, *qddr = qdd + row * ndof;
+  double* tr = tau_out + row * ndof;
+  for (int j = 0; j < ndof; ++j) tr[j] = 0.0;
+  const RneaPayload pl = rnea_payload(pl_mass, pl_com, pl_inertia, (size_t)(row / M));
+  rt_rnea(rb, dyn, pl, smem_rnea + lane, rows, [&](int j) { return qr[j]; }, [&](int j) { return qdr[j]; },
+          [&](int j) { return qddr[j]; }, [&](int j, double v) { tr[j] = v; });
 }
 
 // Samples at linspace(0, duration, M) (numpy's values): the segment i with t_i <= t < t_{i+1}, s and sdot under the

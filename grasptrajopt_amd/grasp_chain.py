@@ -133,9 +133,13 @@ class GraspChain:
         goes to (the shelf driver solves IK to ``RT @ standoff`` and plans to ``RT``, :256-259); n_grasps (B,) how many rows
         of an object count; fields: see ``_scene_ids``; base_position (3,) or (B, 3).  observation: an
         ``observation.Observation`` to count the solved plans' surface points inside (gto_check_plans_device).  retime: a
-        dict ``vmax, amax[, subdiv, n_samples, profile, gap_tol, max_newton]`` to retime the solved plans
+        dict ``vmax, amax[, subdiv, n_samples, profile, gap_tol, max_newton, tau_max, payload]`` to retime the solved plans
         (gto_retime_batch_device; ``profile="convex"``: the grid's time optimum, gto_retime_paths_convex_device for the plans
-        and the retrieve path alike, which adds retime_iters / retrieve_retime_iters (B,)).  retrieve: a dict
+        and the retrieve path alike, which adds retime_iters / retrieve_retime_iters (B,); ``profile="torque"``: that optimum
+        under the joint torque limits ``tau_max`` too (None: the description's effort limits), gto_retime_paths_torque_device
+        -- the approach plans with an empty hand, the retrieve path with ``payload``, the dict of
+        ``SolverHandle.inverse_dynamics`` with one value per call or per object; with ``retrieve_samples`` the result also
+        has retrieve_tau (B, n_samples, ndof)).  retrieve: a dict
         ``mode`` ("lift" | "reverse") ``[, distance, steps, direction, closed_joints, closed_value, collide]`` for the motion
         after the grasp (see ``retrieve_spec``), enqueued behind the solve (with n_seeds > 1 behind the selection) on the
         chain's stream; the result gains retrieve_path (B, ndof, steps + 1 | n), retrieve_reached (B,) (lift: the leading
@@ -303,10 +307,14 @@ class GraspChain:
         res = SimpleNamespace()
         rs = None if retrieve is None else self.retrieve_spec(retrieve)
         convex = None  # (gap_tol, max_newton) when the retime dict asks for the grid's time optimum
+        torque = None  # the checked tau_max and per-object payload arrays when it asks for torque limits on top
         if retime is not None and "profile" in retime:
             from ._capi import retime_profile
             prof = retime_profile(retime["profile"], retime.get("gap_tol", 1e-8), retime.get("max_newton"))
-            convex = prof[1:] if prof[0] == "convex" else None
+            convex = prof[1:] if prof[0] in ("convex", "torque") else None
+            if prof[0] == "torque":  # checked here, before anything is enqueued
+                from ._capi import payload_arrays, retime_torque_limits
+                torque = dict(tau_max=retime_torque_limits(d, retime.get("tau_max")), payload=payload_arrays(retime.get("payload"), B))
         with torch.cuda.stream(self.stream):
             st = self.stream.cuda_stream
             d_sid, d_qc, d_base = self._up("sid", sid, np.int32), self._up("qc", qc, np.float64), self._up("base", base, np.float64)
@@ -429,6 +437,12 @@ class GraspChain:
                         h.retime_batch_device(B, d_Q.data_ptr(), retime["vmax"], retime["amax"], int(retime.get("subdiv", 2)),
                                               int(retime.get("n_samples", 100)), duration_out=d_dur.data_ptr(),
                                               status_out=d_rst.data_ptr(), stream=st)
+                    elif torque is not None:  # the approach: the hand is empty
+                        d_rit = self._dev("retime_iters", (B,), i32)
+                        h.retime_paths_torque_device(B, T, d_Q.data_ptr(), retime["vmax"], retime["amax"], tau_max=torque["tau_max"],
+                                                     subdiv=int(retime.get("subdiv", 2)), n_samples=int(retime.get("n_samples", 100)),
+                                                     gap_tol=convex[0], max_newton=convex[1], duration_out=d_dur.data_ptr(),
+                                                     status_out=d_rst.data_ptr(), iters_out=d_rit.data_ptr(), stream=st)
                     else:  # the plans are the Tp = T case of the paths call
                         d_rit = self._dev("retime_iters", (B,), i32)
                         h.retime_paths_convex_device(B, T, d_Q.data_ptr(), retime["vmax"], retime["amax"],
@@ -442,7 +456,7 @@ class GraspChain:
                             d_nc = self._dev("retrieve_n_cols", (B,), i32)
                             torch.add(d_rreach, 1, out=d_nc)
                         d_rdur, d_rrst = self._dev("retrieve_durations", (B,), f64), self._dev("retrieve_retime_status", (B,), i32)
-                        d_rsamp = [None] * 3
+                        d_rsamp, d_rtau = [None] * 3, None
                         if retime.get("retrieve_samples", False):
                             d_rsamp = [self._dev("retrieve_" + k, (B, ns, ndof), f64) for k in ("q", "qd", "qdd")]
                         outs = dict(duration_out=d_rdur.data_ptr(), status_out=d_rrst.data_ptr(),
@@ -451,6 +465,18 @@ class GraspChain:
                             h.retime_paths_device(B, cols, d_rp.data_ptr(), retime["vmax"], retime["amax"],
                                                   n_cols=None if d_nc is None else d_nc.data_ptr(), subdiv=sub, n_samples=ns,
                                                   **outs, stream=st)
+                        elif torque is not None:  # the retrieve motion carries each object's payload
+                            d_rrit = self._dev("retrieve_retime_iters", (B,), i32)
+                            d_pl = [None if a is None else self._up("retime_payload_" + k, a, np.float64).data_ptr()
+                                    for k, a in zip(("mass", "com", "inertia"), torque["payload"])]
+                            if d_rsamp[0] is not None:
+                                d_rtau = self._dev("retrieve_tau", (B, ns, ndof), f64)
+                            h.retime_paths_torque_device(B, cols, d_rp.data_ptr(), retime["vmax"], retime["amax"],
+                                                         tau_max=torque["tau_max"], payload_mass=d_pl[0], payload_com=d_pl[1],
+                                                         payload_inertia=d_pl[2], n_cols=None if d_nc is None else d_nc.data_ptr(),
+                                                         subdiv=sub, n_samples=ns, gap_tol=convex[0], max_newton=convex[1],
+                                                         iters_out=d_rrit.data_ptr(), tau_out=None if d_rtau is None else d_rtau.data_ptr(),
+                                                         **outs, stream=st)
                         else:
                             d_rrit = self._dev("retrieve_retime_iters", (B,), i32)
                             h.retime_paths_convex_device(B, cols, d_rp.data_ptr(), retime["vmax"], retime["amax"],
@@ -480,6 +506,8 @@ class GraspChain:
                     if convex is not None:
                         out["retrieve_retime_iters"] = d_rrit
                     out.update({"retrieve_" + k: v for k, v in zip(("q", "qd", "qdd"), d_rsamp) if v is not None})
+                    if d_rtau is not None:
+                        out["retrieve_tau"] = d_rtau
             if multi:  # (cost, iters, status and counts hold every slot's until the chosen slot's are picked below)
                 out.update(best_slot=d_best, plan_class=d_cls, slot_class=d_scls, slot_goal_index=d_gi, slot_err_pos=d_pep,
                            slot_err_rot=d_per, accepted_rows=d_rows, slot_plans=d_Qs)

@@ -127,9 +127,11 @@ class GTOPlanner:
         ``closed_joints`` (default: the robot's parameter joints that are fingers) are held at ``closed_value``.
         Returns (path (ndof, steps + 1 | 9 - standoff_offset), reached): reached counts the leading steps that met their goal
         within pos_tol / rot_tol_deg (reverse: every column).  No collision term; GraspChain's ``retrieve`` has one.
-        retime: a dict ``vmax, amax[, subdiv, n_samples, reached_only, profile, gap_tol, max_newton]`` to also retime the path
-        under these joint limits (gto_retime_paths; ``profile="convex"``: the grid's time optimum, gto_retime_paths_convex,
-        whose dict also has ``iters``); reached_only=True retimes columns 0 .. reached of a lift, the part that met its goals.  The
+        retime: a dict ``vmax, amax[, subdiv, n_samples, reached_only, profile, gap_tol, max_newton, tau_max, payload]`` to
+        also retime the path under these joint limits (gto_retime_paths; ``profile="convex"``: the grid's time optimum,
+        gto_retime_paths_convex, whose dict also has ``iters``; ``profile="torque"``: that optimum under the joint torque limits
+        ``tau_max`` (None: the description's effort limits) with the held object ``payload`` on link_ee, the dict of
+        ``utils.inverse_dynamics``, gto_retime_paths_torque, whose dict also has ``tau``); reached_only=True retimes columns 0 .. reached of a lift, the part that met its goals.  The
         return value is then (path, reached, trajectory): the dict of ``SolverHandle.retime_paths`` (of one path for one
         plan).
         observation + held_points: the points of the object the robot holds (per plan (n_i, 3) world points at the moment of
@@ -143,6 +145,10 @@ class GTOPlanner:
         plan = np.asarray(plan, dtype=np.float64)
         single = plan.ndim == 2
         plans = np.ascontiguousarray(plan.reshape(-1, self.robot.ndof, self.T))
+        torque = None  # a torque request is checked before the handle is made: (tau_max, payload dict)
+        if retime is not None and retime.get("profile") == "torque":
+            _capi.payload_arrays(retime.get("payload"), plans.shape[0])
+            torque = (_capi.retime_torque_limits(self.robot.desc, retime.get("tau_max")), retime.get("payload"))
         opts = _capi.default_opts()
         opts.T, opts.Tmax, opts.standoff_offset = self.T, self.Tmax, self.standoff_offset
         h = self.robot.solver_handle(self.link_ee, self.link_gripper, opts, role="retrieve")
@@ -182,14 +188,17 @@ class GTOPlanner:
             checks = ({"held_counts": counts[0] if single else counts},)
         if retime is None:
             return ((path[0], int(reached[0])) if single else (path, reached)) + checks
-        unknown = set(retime) - {"vmax", "amax", "subdiv", "n_samples", "reached_only", "profile", "gap_tol", "max_newton"}
+        unknown = set(retime) - {"vmax", "amax", "subdiv", "n_samples", "reached_only", "profile", "gap_tol", "max_newton", "tau_max", "payload"}
         if unknown:
             raise TypeError(f"retrieve_path: unexpected retime key(s) {sorted(unknown)}")
         n_cols = reached + 1 if mode == "lift" and retime.get("reached_only", False) else None
         profile, gap_tol, max_newton = _capi.retime_profile(retime.get("profile", "greedy"), retime.get("gap_tol", 1e-8),
                                                             retime.get("max_newton"))
         kw = dict(n_cols=n_cols, subdiv=int(retime.get("subdiv", 2)), n_samples=int(retime.get("n_samples", 100)))
-        if profile == "convex":
+        if profile == "torque":
+            traj = h.retime_paths_torque(path, retime["vmax"], retime["amax"], tau_max=torque[0], payload=torque[1],
+                                         gap_tol=gap_tol, max_newton=max_newton, **kw)
+        elif profile == "convex":
             traj = h.retime_paths_convex(path, retime["vmax"], retime["amax"], gap_tol=gap_tol, max_newton=max_newton, **kw)
         else:
             traj = h.retime_paths(path, retime["vmax"], retime["amax"], **kw)

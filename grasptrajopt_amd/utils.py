@@ -229,8 +229,27 @@ def _retime_handle(robot, T: int):
     return robot.solver_handle(ln, ln, o, role="util")
 
 
+def _torque_request(robot, tau_max, payload, B, link_ee):
+    """The checked (tau_max, payload, link_ee) of a profile="torque" request, before any handle is made."""
+    from . import _capi
+    tm = _capi.retime_torque_limits(robot.desc, tau_max)
+    _capi.payload_arrays(payload, B)
+    if payload is not None and link_ee is None:
+        raise ValueError("retime: a payload needs link_ee, the link that carries it")
+    return tm, payload, robot.desc.link_names[-1] if link_ee is None else link_ee
+
+
+def _torque_handle(robot, T: int, link_ee: str):
+    """_retime_handle with link_ee as the end effector: the frame the payload rides on."""
+    from . import _capi
+    o = _capi.default_opts()
+    o.T = int(T)
+    o.standoff_offset = max(int(o.standoff_offset), 2 - int(T))
+    return robot.solver_handle(link_ee, robot.desc.link_names[-1], o, role="util")
+
+
 def retime_plans(robot, plans, vlim=None, alim=0.5, subdiv: int = 2, n_samples: int = 100, profile: str = "greedy",
-                 gap_tol: float = 1e-8, max_newton=None):
+                 gap_tol: float = 1e-8, max_newton=None, tau_max=None, payload=None, link_ee=None):
     """Time-optimal retiming of plans (B, ndof, T) or one plan (ndof, T) on the GPU (gto_retime_batch, include/gto_solver.h):
     not-a-knot cubic spline through the waypoints on linspace(0, 1, T), joint velocity limits ``vlim`` (default: the URDF's,
     ``robot.velocity_actuated_joint_limits``) and acceleration limits ``alim`` (default 0.5 rad/s^2, gto/utils.py:295),
@@ -238,14 +257,23 @@ def retime_plans(robot, plans, vlim=None, alim=0.5, subdiv: int = 2, n_samples: 
     duration (B,), t_grid (B, N), sd_grid (B, N), q / qd / qdd (B, n_samples, ndof) at linspace(0, duration, n_samples)
     and status (B,).  profile "greedy" (the default) is TOPP-RA's forward pass; "convex" is the time optimum of the same
     grid constraints, solved per plan to the certified relative gap ``gap_tol`` in at most ``max_newton`` Newton steps
-    (gto_retime_paths_convex with Tp = T), and adds iters (B,) to the dict."""
+    (gto_retime_paths_convex with Tp = T), and adds iters (B,) to the dict.  profile "torque" is that optimum under joint
+    torque limits as well (gto_retime_paths_torque): ``tau_max`` ((ndof,) or one value, +inf = none; default: the URDF's
+    effort limits, ``robot.desc.effort``) bounds the inverse dynamics along the path, with ``payload`` (the dict of
+    ``inverse_dynamics``, one value per call or per plan) on ``link_ee``; it needs link inertials on the description and adds
+    iters and tau (B, n_samples, ndof); status 3: some joint cannot hold the path at rest."""
     from . import _capi
     profile, gap_tol, max_newton = _capi.retime_profile(profile, gap_tol, max_newton)
     plans = np.asarray(plans, dtype=np.float64)
     if plans.ndim == 2:
         plans = plans[None]
+    if profile == "torque":  # checked before the robot is asked for anything but its description
+        tm, payload, ee = _torque_request(robot, tau_max, payload, plans.shape[0], link_ee)
     if vlim is None:
         vlim = np.asarray(robot.velocity_actuated_joint_limits.toarray()).ravel()
+    if profile == "torque":
+        return _torque_handle(robot, plans.shape[2], ee).retime_paths_torque(
+            plans, vlim, alim, tau_max=tm, payload=payload, subdiv=subdiv, n_samples=n_samples, gap_tol=gap_tol, max_newton=max_newton)
     h = _retime_handle(robot, plans.shape[2])
     if profile == "convex":
         return h.retime_paths_convex(plans, vlim, alim, subdiv=subdiv, n_samples=n_samples, gap_tol=gap_tol, max_newton=max_newton)
@@ -253,19 +281,26 @@ def retime_plans(robot, plans, vlim=None, alim=0.5, subdiv: int = 2, n_samples: 
 
 
 def retime_paths(robot, paths, n_cols=None, vlim=None, alim=0.5, subdiv: int = 2, n_samples: int = 100,
-                 profile: str = "greedy", gap_tol: float = 1e-8, max_newton=None):
+                 profile: str = "greedy", gap_tol: float = 1e-8, max_newton=None, tau_max=None, payload=None, link_ee=None):
     """``retime_plans`` for paths (B, ndof, Tp) or one path (ndof, Tp) of any length Tp >= 2 (gto_retime_paths,
     include/gto_solver.h): a retrieve path of ``GTOPlanner.retrieve_path``, for one.  n_cols (B,) int or None: path b is its
     first n_cols[b] columns and the rest is ignored (a lift up to the step it reached: ``reached + 1``); t_grid and sd_grid
     are (B, subdiv (Tp-1) + 1) and hold the duration and 0 past a path's own gridpoints.  One handle serves every Tp.
-    profile, gap_tol, max_newton: as in ``retime_plans`` (gto_retime_paths_convex)."""
+    profile, gap_tol, max_newton, tau_max, payload, link_ee: as in ``retime_plans`` (gto_retime_paths_convex,
+    gto_retime_paths_torque)."""
     from . import _capi
     profile, gap_tol, max_newton = _capi.retime_profile(profile, gap_tol, max_newton)
     paths = np.asarray(paths, dtype=np.float64)
     if paths.ndim == 2:
         paths = paths[None]
+    if profile == "torque":
+        tm, payload, ee = _torque_request(robot, tau_max, payload, paths.shape[0], link_ee)
     if vlim is None:
         vlim = np.asarray(robot.velocity_actuated_joint_limits.toarray()).ravel()
+    if profile == "torque":
+        return _torque_handle(robot, 4, ee).retime_paths_torque(
+            paths, vlim, alim, tau_max=tm, payload=payload, n_cols=n_cols, subdiv=subdiv, n_samples=n_samples, gap_tol=gap_tol,
+            max_newton=max_newton)
     h = _retime_handle(robot, 4)
     if profile == "convex":
         return h.retime_paths_convex(paths, vlim, alim, n_cols=n_cols, subdiv=subdiv, n_samples=n_samples, gap_tol=gap_tol,

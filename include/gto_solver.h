@@ -64,6 +64,7 @@ extern "C" {
 #define GTO_STATUS_CONVERGED 0
 #define GTO_STATUS_MAX_ITER 1
 #define GTO_STATUS_NUMERICAL 2
+#define GTO_STATUS_INFEASIBLE 3 /* gto_retime_paths_torque only: a joint cannot hold the path at rest under its torque limit */
 
 /*
  * Robot description: the facts the reference pulls from the URDF through optas.RobotModel
@@ -1054,6 +1055,49 @@ int gto_retime_paths_convex_device(gto_handle* h, int32_t B, int32_t Tp, const d
                                    const double* vmax /*HOST*/, const double* amax /*HOST*/, int32_t subdiv, int32_t M,
                                    double gap_tol, int32_t max_newton, double* duration_out, double* t_grid_out,
                                    double* sd_grid_out, double* q_out, double* qd_out, double* qdd_out, int32_t* status_out,
+                                   int32_t* iters_out, void* stream);
+/*
+ * Retiming under joint torque limits with the held object as payload: the program of gto_retime_paths_convex kept whole
+ * (variables, objective, xcap, acceleration lines, certificate, statuses) plus, for every gridpoint i <= N-2 and every
+ * joint j with a finite tau_max_j,
+ *     -tau_max_j <= a_ij c (x_{i+1} - x_i) + b_ij x_i + g_ij <= tau_max_j,        c = (N-1)/2,
+ *     g_i = ID(q_i, 0, 0),   a_i = ID(q_i, 0, p1_i) - g_i,   b_i = ID(q_i, p1_i, p2_i) - g_i,
+ * ID the inverse dynamics of gto_inverse_dynamics with the path's payload on frame_ee, q_i / p1_i / p2_i the spline's value
+ * and derivatives at the gridpoint (p1 = p2 = 0 on a joint that does not move): the generalised force along the path is
+ * a u + b x + g exactly.  The rows stand for EVERY joint a frame names, moving or not (a joint that stands still must still
+ * hold); a row whose coefficients on x_1 .. x_{N-2} are both zero is left out.  Additions (the ABI number stays).
+ *   tau_max          [ndof] HOST: > 0, +inf = no limit (GTO_ERR_INVALID_ARG for a NaN or an entry <= 0).
+ *   payload_*        [B], [B,3], [B,6] or NULL, one rigid body per path: the payload rules of gto_inverse_dynamics.
+ *                    gto_retime_paths_torque (HOST) refuses a mass that is negative or not finite, and com / inertia
+ *                    without a mass; gto_retime_paths_torque_device reads DEVICE arrays that no host sees.
+ *   tau_out          [B,M,ndof] or NULL: ID(q, qd, qdd) at the M samples with the path's payload, bit for bit what
+ *                    gto_inverse_dynamics gives on those rows; NaN where the samples are NaN.
+ *   status_out       those of gto_retime_paths_convex, and GTO_STATUS_INFEASIBLE: a path with finite entries (moving or
+ *                    not, C_b == 1 included) with |g_ij| >= tau_max_j at some gridpoint 0 .. N-1 (the last one too: the
+ *                    robot holds there) -- x = eps 1 is strictly inside for small eps exactly when there is none.  NaN
+ *                    outputs and 0 iterations, as for GTO_STATUS_NUMERICAL; no other path's output changes.  A path with
+ *                    a non-finite a, b or g is GTO_STATUS_NUMERICAL (a payload on the device with a NaN in it, or a mass
+ *                    that is negative or not finite).
+ * A handle without inertials answers GTO_ERR_INVALID_ARG "no link inertials set".  Everything else is
+ * gto_retime_paths_convex's: the argument checks (under this call's name), HOST vmax / amax, the n_cols rules, the fill past
+ * a path's own gridpoints, results bit for bit the same in any batch and at any position (the payload travels with its
+ * path), the shared workspace and factor table, stream order with no synchronisation after a handle's first retime call.
+ * The greedy and convex entry points are unchanged, launch for launch.
+ * Replaces: the `alims` stand-in of gto/utils.py:293-298 (0.5 rad/s^2 for what a motor can do).
+ */
+int gto_retime_paths_torque(gto_handle* h, int32_t B, int32_t Tp, const double* paths, const int32_t* n_cols,
+                            const double* vmax, const double* amax, const double* tau_max /*[ndof] HOST: > 0, +inf = none*/,
+                            const double* payload_mass /*[B] or NULL*/, const double* payload_com /*[B,3] or NULL*/,
+                            const double* payload_inertia /*[B,6] or NULL*/, int32_t subdiv, int32_t M, double gap_tol,
+                            int32_t max_newton, double* duration_out, double* t_grid_out, double* sd_grid_out, double* q_out,
+                            double* qd_out, double* qdd_out, double* tau_out /*[B,M,ndof] or NULL*/, int32_t* status_out,
+                            int32_t* iters_out);
+int gto_retime_paths_torque_device(gto_handle* h, int32_t B, int32_t Tp, const double* paths, const int32_t* n_cols /*DEVICE*/,
+                                   const double* vmax /*HOST*/, const double* amax /*HOST*/, const double* tau_max /*HOST*/,
+                                   const double* payload_mass /*DEVICE*/, const double* payload_com /*DEVICE*/,
+                                   const double* payload_inertia /*DEVICE*/, int32_t subdiv, int32_t M, double gap_tol,
+                                   int32_t max_newton, double* duration_out, double* t_grid_out, double* sd_grid_out,
+                                   double* q_out, double* qd_out, double* qdd_out, double* tau_out, int32_t* status_out,
                                    int32_t* iters_out, void* stream);
 
 #ifdef __cplusplus
