@@ -169,6 +169,9 @@ def _prototypes():
         "gto_retime_paths_torque": (I, [V, I32, I32, _pd, _pi, _pd, _pd, _pd, _pd, _pd, _pd, I32, I32, D, I32, _pd, _pd, _pd, _pd,
                                         _pd, _pd, _pd, _pi, _pi]),
         "gto_retime_paths_torque_device": (I, [V, I32, I32, V, V, _pd, _pd, _pd, V, V, V, I32, I32, D, I32] + [V] * 10),
+        "gto_forward_dynamics": (I, [V, I32, _pd, _pd, _pd, _pd, _pd, _pd, _pi, _pd, _pd, _pi]),
+        "gto_track_rollout": (I, [V, I32, I32] + [_pd] * 7 + [D, D, I32] + [_pd] * 6 + [_pi, I32] + [_pd] * 5 + [_pi] * 3),
+        "gto_track_rollout_device": (I, [V, I32, I32] + [V] * 4 + [_pd] * 3 + [D, D, I32] + [V] * 6 + [_pi, I32] + [V] * 9),
     }
 
 
@@ -178,6 +181,8 @@ PROTOTYPES = _prototypes()
 RETIME_MAX_NEWTON = 400
 RETIME_PROFILES = ("greedy", "convex", "torque")
 STATUS_INFEASIBLE = 3  # GTO_STATUS_INFEASIBLE: a joint cannot hold the path at rest under its torque limit
+TRACK_FEEDFORWARD = {"none": 0, "gravity": 1, "full": 2}  # the feedforward of gto_track_rollout by name
+TRACK_KEYS = ("q", "qd", "t", "err_max", "err_end", "sat_steps", "steps", "status")
 
 
 def retime_profile(profile="greedy", gap_tol=1e-8, max_newton=None):
@@ -211,6 +216,42 @@ def retime_torque_limits(desc, tau_max=None, need_inertials=True):
     if not np.all(tm > 0):  # a NaN among them
         raise ValueError("retime: tau_max must be > 0 (+inf: no limit)")
     return tm
+
+
+def track_controller(desc, kp, kd, tau_max=None, dt=1e-3, settle=0.0, n_samples=100, feedforward="full", locked=None,
+                     need_inertials=True):
+    """The checked host arguments of a rollout request, for every Python layer that takes one: (kp, kd, tau_max (ndof,),
+    dt, settle, n_samples, feedforward 0 / 1 / 2, locked (ndof,) int32 or None).  Gains: one value or one per joint, finite
+    and >= 0; tau_max: retime_torque_limits' rules (None = the description's effort limits); feedforward: a name of
+    TRACK_FEEDFORWARD or its number; locked: None (every joint that is not optimised) or one flag per joint.  A description
+    without link inertials is refused (need_inertials=False leaves that to the library)."""
+    def gains(x, what):
+        try:
+            a = _f64(np.broadcast_to(np.asarray(x, dtype=np.float64), (desc.ndof,)))
+        except ValueError:
+            raise ValueError(f"track: {what} must be one value or ({desc.ndof},), got shape {np.shape(x)}") from None
+        if not (np.isfinite(a).all() and (a >= 0).all()):
+            raise ValueError(f"track: {what} must be finite and >= 0")
+        return a
+
+    kp, kd = gains(kp, "kp"), gains(kd, "kd")
+    tm = retime_torque_limits(desc, tau_max, need_inertials)
+    dt, settle, n_samples = float(dt), float(settle), int(n_samples)
+    if not (np.isfinite(dt) and dt > 0):
+        raise ValueError(f"track: dt must be finite and > 0, got {dt}")
+    if not (np.isfinite(settle) and settle >= 0):
+        raise ValueError(f"track: settle must be finite and >= 0, got {settle}")
+    if n_samples < 2:
+        raise ValueError(f"track: n_samples must be >= 2, got {n_samples}")
+    ff = TRACK_FEEDFORWARD.get(feedforward, feedforward)
+    if isinstance(ff, bool) or ff not in (0, 1, 2):
+        raise ValueError(f"track: feedforward must be one of {sorted(TRACK_FEEDFORWARD)} or 0, 1, 2, got {feedforward!r}")
+    if locked is not None:
+        lk = np.asarray(locked)
+        if lk.shape != (desc.ndof,):
+            raise ValueError(f"track: locked must be ({desc.ndof},), got shape {lk.shape}")
+        locked = _i32(lk != 0)
+    return kp, kd, tm, dt, settle, n_samples, int(ff), locked
 
 
 def payload_arrays(payload, n):
@@ -652,6 +693,76 @@ class SolverHandle:
         self._check(self.lib.gto_inverse_dynamics(self._h, n, _p(q, _pd), _p(qd, _pd), _p(qdd, _pd), _p(pm, _pd), _p(pc, _pd),
                                                   _p(pi, _pd), _p(out, _pd)), "gto_inverse_dynamics")
         return out
+
+    def forward_dynamics(self, q, qd, tau, payload=None, locked=None, want_mass_matrix=False):
+        """Accelerations (n, ndof) that the joint forces tau cause at the rows q, qd (n, ndof), by gto_forward_dynamics, and
+        the status (n,) of every row (2: a non-finite row or a free joint that moves no mass, NaN there).  payload: the dict
+        of inverse_dynamics.  locked: None (every joint that is not optimised stands still) or one flag per joint.  Returns
+        (qdd, status), and the symmetrised mass matrix (n, ndof, ndof) as a third entry with want_mass_matrix."""
+        nd = self.desc.ndof
+        q = _f64(q).reshape(-1, nd)
+        n = q.shape[0]
+        qd, tau = _f64(qd).reshape(n, nd), _f64(tau).reshape(n, nd)
+        pm, pc, pi = payload_arrays(payload, n)
+        lk = None
+        if locked is not None:
+            lk = np.asarray(locked)
+            if lk.shape != (nd,):
+                raise ValueError(f"forward_dynamics: locked must be ({nd},), got shape {lk.shape}")
+            lk = _i32(lk != 0)
+        self.sync_link_inertials()
+        qdd, status = np.empty((n, nd)), np.empty(n, dtype=np.int32)
+        Mm = np.empty((n, nd, nd)) if want_mass_matrix else None
+        self._check(self.lib.gto_forward_dynamics(self._h, n, _p(q, _pd), _p(qd, _pd), _p(tau, _pd), _p(pm, _pd), _p(pc, _pd),
+                                                  _p(pi, _pd), _p(lk, _pi), _p(qdd, _pd), _p(Mm, _pd), _p(status, _pi)),
+                    "gto_forward_dynamics")
+        return (qdd, status, Mm) if want_mass_matrix else (qdd, status)
+
+    def track_rollout(self, duration, q_ref, qd_ref, qdd_ref, kp, kd, tau_max=None, dt=1e-3, settle=0.0, n_samples=100,
+                      feedforward="full", model_payload=None, plant_payload=None, locked=None):
+        """gto_track_rollout: roll the B references (duration (B,), samples (B, M, ndof) at linspace(0, duration, M)) forward
+        under tau = clip(ff + kp (q_ref - q) + kd (qd_ref - qd), +-tau_max), evaluated every ``dt`` and held, on the plant
+        with ``plant_payload`` in the hand while the feedforward believes ``model_payload`` (each the dict of
+        inverse_dynamics, one value for the call or one per path).  Returns a dict: q, qd (B, n_samples, ndof), t
+        (B, n_samples), err_max, err_end (B,), sat_steps, steps, status (B,) int32."""
+        d = self.desc
+        q_ref = _f64(q_ref)
+        if q_ref.ndim != 3 or q_ref.shape[2] != d.ndof:
+            raise ValueError(f"track_rollout: q_ref must be (B, M, {d.ndof}), got {q_ref.shape}")
+        B, M = q_ref.shape[:2]
+        qd_ref, qdd_ref = _f64(qd_ref).reshape(q_ref.shape), _f64(qdd_ref).reshape(q_ref.shape)
+        duration = _f64(duration).reshape(B)
+        kp, kd, tm, dt, settle, Mo, ff, lk = track_controller(d, kp, kd, tau_max, dt, settle, n_samples, feedforward, locked, need_inertials=False)
+        mm, mc, mi = payload_arrays(model_payload, B)
+        pm, pc, pi = payload_arrays(plant_payload, B)
+        self.sync_link_inertials()
+        out = dict(q=np.empty((B, Mo, d.ndof)), qd=np.empty((B, Mo, d.ndof)), t=np.empty((B, Mo)), err_max=np.empty(B),
+                   err_end=np.empty(B), sat_steps=np.empty(B, dtype=np.int32), steps=np.empty(B, dtype=np.int32),
+                   status=np.empty(B, dtype=np.int32))
+        self._check(self.lib.gto_track_rollout(self._h, B, M, _p(duration, _pd), _p(q_ref, _pd), _p(qd_ref, _pd), _p(qdd_ref, _pd),
+                                               _p(kp, _pd), _p(kd, _pd), _p(tm, _pd), dt, settle, ff, _p(mm, _pd), _p(mc, _pd),
+                                               _p(mi, _pd), _p(pm, _pd), _p(pc, _pd), _p(pi, _pd), _p(lk, _pi), Mo,
+                                               _p(out["q"], _pd), _p(out["qd"], _pd), _p(out["t"], _pd), _p(out["err_max"], _pd),
+                                               _p(out["err_end"], _pd), _p(out["sat_steps"], _pi), _p(out["steps"], _pi),
+                                               _p(out["status"], _pi)), "gto_track_rollout")
+        return out
+
+    def track_rollout_device(self, B, M, duration, q_ref, qd_ref, qdd_ref, kp, kd, tau_max=None, dt=1e-3, settle=0.0,
+                             n_samples=100, feedforward="full", model_payload=(None, None, None),
+                             plant_payload=(None, None, None), locked=None, q_out=None, qd_out=None, t_out=None, err_max=None,
+                             err_end=None, sat_steps=None, steps=None, status_out=None, stream=None):
+        """gto_track_rollout_device: duration (B,), the samples (B, M, ndof), the payloads ((mass (B,), com (B, 3), inertia
+        (B, 6)) each, any of them None) and the outputs are device pointers (ints, e.g. torch.Tensor.data_ptr()) or None;
+        the gains, limits, clock and ``locked`` are host values.  One launch on ``stream``, nothing else."""
+        kp, kd, tm, dt, settle, Mo, ff, lk = track_controller(self.desc, kp, kd, tau_max, dt, settle, n_samples, feedforward, locked,
+                                                              need_inertials=False)
+        self.sync_link_inertials()
+        self._check(self.lib.gto_track_rollout_device(self._h, int(B), int(M), _vp(duration), _vp(q_ref), _vp(qd_ref), _vp(qdd_ref),
+                                                      _p(kp, _pd), _p(kd, _pd), _p(tm, _pd), dt, settle, ff,
+                                                      *[_vp(a) for a in tuple(model_payload) + tuple(plant_payload)], _p(lk, _pi), Mo,
+                                                      _vp(q_out), _vp(qd_out), _vp(t_out), _vp(err_max), _vp(err_end),
+                                                      _vp(sat_steps), _vp(steps), _vp(status_out), _vp(stream)),
+                    "gto_track_rollout_device")
 
     def eval_points(self, scene_id, q, base_pos, use_obs=False, want_field=True, want=None):
         """World surface points, voxel offsets, field values and field gradients of configurations q (nq, ndof).

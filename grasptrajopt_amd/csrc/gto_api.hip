@@ -25,6 +25,7 @@
 #include "gto_cloud.h"
 #include "gto_retime.h"
 #include "gto_dynamics.h"
+#include "gto_forward.h"
 #include "gto_observe.h"
 #include "gto_held.h"
 #include "gto_seed.h"
@@ -44,7 +45,7 @@ static std::string g_create_error;
 
 #define GTO_MAX_LANES 8  // lanes of one solve call (streams, list sets, progress words)
 #define GTO_BASE_PIN_SLOTS 4  // calls whose small host arrays (n_goals, per-plan bases, the filter's view table) may be in flight at once without the host waiting
-#define GTO_STAGE_SLOTS 9  // host arrays of each direction that one host-pointer entry point stages (Staging): gto_retime_paths_torque has nine outputs
+#define GTO_STAGE_SLOTS 10  // host arrays of each direction that one host-pointer entry point stages (Staging): gto_track_rollout has ten inputs
 #define GTO_NAP_US 50      // the throttle's naps (the host thread of a lane sleep-polls two pinned words); 10-50 us change nothing
 #define GTO_NAP_FEW_US 10  // ... in launches with few instances in flight; 50-200 us change nothing either
 // the deep-gather obstacle variant only up to this many instances in flight (two workgroups per CU: beyond that the
@@ -1536,7 +1537,7 @@ class Staging {
     *dptr = h_->out[k].as<T>();
     return GTO_OK;
   }
-  int too_many() { return fail(h_, GTO_ERR_UNSUPPORTED, "internal: more than nine staged arrays of one direction"); }
+  int too_many() { return fail(h_, GTO_ERR_UNSUPPORTED, "internal: more than ten staged arrays of one direction"); }
 
   gto_handle* h_;
   int n_in_ = 0, n_out_ = 0;
@@ -2217,6 +2218,180 @@ int gto_inverse_dynamics(gto_handle* h, int32_t n, const double* q, const double
   HIPCHK(h, hipGetLastError());
   return io.finish();
 }
+
+}  // extern "C"
+
+// -------------------------------------------------------------------------------------------------
+// forward dynamics and the tracking rollout (gto_forward.h)
+// The joint lists of a call.  A joint is free when some actuated frame names it and `locked` (HOST [ndof], NULL = every
+// joint that is not optimised) does not mark it.  columns_of_named: the mass-matrix columns of every named joint
+// (gto_forward_dynamics' M_out) or of the free ones only.
+static FdSets fd_sets(const gto_handle* h, const int32_t* locked, bool columns_of_named) {
+  FdSets s = {};
+  const RobotDev& rb = h->rb;
+  s.ndof = rb.ndof;
+  bool named[GTO_MAX_DOF] = {};
+  for (int f = 0; f < rb.n_frames; ++f)
+    if (rb.joint_type[f] != GTO_JOINT_FIXED && rb.q_index[f] >= 0) named[rb.q_index[f]] = true;
+  for (int j = 0; j < rb.ndof; ++j) {
+    const bool lk = locked ? locked[j] != 0 : rb.opt_of_dof[j] < 0;
+    const bool fr = named[j] && !lk;
+    s.is_free[j] = fr ? 1 : 0;
+    if (fr) s.fr[s.nf++] = j;
+    if (columns_of_named ? named[j] : fr) s.col[s.nc++] = j;
+  }
+  return s;
+}
+
+// which payload arrays come together, and the masses where the host sees them (n > 0)
+static int payload_check(gto_handle* h, const std::string& f, int32_t n, const double* mass, const double* com, const double* inertia) {
+  if (!mass && (com || inertia)) return fail(h, GTO_ERR_INVALID_ARG, f + "payload_com / payload_inertia without payload_mass");
+  if (mass)
+    for (int32_t i = 0; i < n; ++i)
+      if (!(mass[i] >= 0) || !std::isfinite(mass[i])) return fail(h, GTO_ERR_INVALID_ARG, f + "payload mass must be >= 0 and finite");
+  return GTO_OK;
+}
+
+extern "C" int gto_forward_dynamics(gto_handle* h, int32_t n, const double* q, const double* qd, const double* tau,
+                                    const double* payload_mass, const double* payload_com, const double* payload_inertia,
+                                    const int32_t* locked, double* qdd_out, double* M_out, int32_t* status_out) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (n < 0) return fail(h, GTO_ERR_INVALID_ARG, "n must be >= 0");
+  if (!h->has_inertials) return fail(h, GTO_ERR_INVALID_ARG, "no link inertials set");
+  if (n == 0) return GTO_OK;
+  if (!q || !qd || !tau || !qdd_out) return fail(h, GTO_ERR_INVALID_ARG, "null input array");
+  int rc;
+  if ((rc = payload_check(h, "", n, payload_mass, payload_com, payload_inertia))) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t ndof = h->rb.ndof;
+  const FdSets sets = fd_sets(h, locked, true);
+  Staging io(h);
+  const double *dq, *dqd, *dtau, *dpm, *dpc, *dpi;
+  double *dqdd, *dM;
+  int32_t* dst;
+  if ((rc = io.in(q, (size_t)n * ndof, &dq))) return rc;
+  if ((rc = io.in(qd, (size_t)n * ndof, &dqd))) return rc;
+  if ((rc = io.in(tau, (size_t)n * ndof, &dtau))) return rc;
+  if ((rc = io.in(payload_mass, (size_t)n, &dpm))) return rc;  // (a null array: a null device pointer)
+  if ((rc = io.in(payload_com, (size_t)n * 3, &dpc))) return rc;
+  if ((rc = io.in(payload_inertia, (size_t)n * 6, &dpi))) return rc;
+  if ((rc = io.out(qdd_out, (size_t)n * ndof, &dqdd))) return rc;
+  if ((rc = io.out(M_out, (size_t)n * ndof * ndof, &dM))) return rc;
+  if ((rc = io.out(status_out, (size_t)n, &dst))) return rc;
+  const int F = h->rb.n_frames, rows = fd_rows_per_block(F, (int)ndof);
+  const size_t lds = sizeof(double) * (GTO_RNEA_SLOTS * F + fd_work_doubles((int)ndof, GTO_FD_VECS)) * rows +
+                     sizeof(int) * (3 * GTO_MAX_DOF + rows);
+  hipLaunchKernelGGL(k_forward_dynamics, dim3((unsigned)((n + rows - 1) / rows)), dim3(GTO_WAVE), lds, h->stream, h->d_rb,
+                     h->dyn_buf.as<const DynDev>(), sets, n, rows, dq, dqd, dtau, dpm, dpc, dpi, dqdd, dM, dst);
+  HIPCHK(h, hipGetLastError());
+  return io.finish();
+}
+
+// the host arrays and scalars of a rollout call, checked into the kernel's arguments
+static int track_check(gto_handle* h, int32_t B, int32_t M, const double* kp, const double* kd, const double* tau_max, double dt,
+                       double settle, int32_t feedforward, int32_t Mo, const double* const pay[6], TrackParams& prm) {
+  const std::string f = "gto_track_rollout: ";
+  if (B < 0) return fail(h, GTO_ERR_INVALID_ARG, f + "B must be >= 0");
+  if (M < 2 || Mo < 2) return fail(h, GTO_ERR_INVALID_ARG, f + "M and Mo must be >= 2");
+  if (!h->has_inertials) return fail(h, GTO_ERR_INVALID_ARG, "no link inertials set");
+  if (!kp || !kd || !tau_max) return fail(h, GTO_ERR_INVALID_ARG, f + "null gain or limit array");
+  for (int j = 0; j < h->rb.ndof; ++j) {
+    if (!(kp[j] >= 0.0) || !std::isfinite(kp[j]) || !(kd[j] >= 0.0) || !std::isfinite(kd[j]))
+      return fail(h, GTO_ERR_INVALID_ARG, f + "kp and kd must be finite and >= 0");
+    if (!(tau_max[j] > 0.0)) return fail(h, GTO_ERR_INVALID_ARG, f + "tau_max must be > 0 (+inf: no limit)");
+    prm.kp[j] = kp[j], prm.kd[j] = kd[j], prm.tau_max[j] = tau_max[j];
+  }
+  if (!(dt > 0.0) || !std::isfinite(dt)) return fail(h, GTO_ERR_INVALID_ARG, f + "dt must be finite and > 0");
+  if (!(settle >= 0.0) || !std::isfinite(settle)) return fail(h, GTO_ERR_INVALID_ARG, f + "settle must be finite and >= 0");
+  if (feedforward < 0 || feedforward > 2) return fail(h, GTO_ERR_INVALID_ARG, f + "feedforward must be 0, 1 or 2");
+  for (int k = 0; k < 2; ++k)
+    if (!pay[3 * k] && (pay[3 * k + 1] || pay[3 * k + 2]))
+      return fail(h, GTO_ERR_INVALID_ARG, f + "payload_com / payload_inertia without payload_mass");
+  if ((long long)B * std::max(M, Mo) * std::max(h->rb.ndof, 1) > (long long)INT32_MAX * 64)
+    return fail(h, GTO_ERR_UNSUPPORTED, f + "batch too large for one call");
+  prm.dt = dt, prm.settle = settle, prm.B = B, prm.M = M, prm.Mo = Mo, prm.feedforward = feedforward;
+  prm.G = track_group_lanes(h->rb.n_frames, h->rb.ndof);
+  prm.P = track_paths_per_block(h->rb.n_frames, h->rb.ndof, prm.G);
+  return GTO_OK;
+}
+
+// the one launch of a checked call, on `st`
+static int track_launch(gto_handle* h, const TrackParams& prm, const FdSets& sets, const TrackRef& ref, const TrackPayloads& pay,
+                        const TrackOut& out, hipStream_t st) {
+  const int F = h->rb.n_frames, ndof = h->rb.ndof;
+  const size_t lds = sizeof(double) * ((size_t)GTO_RNEA_SLOTS * F * prm.P * prm.G + (size_t)fd_work_doubles(ndof, GTO_TR_VECS) * prm.P + 3 * ndof) +
+                     sizeof(int) * (3 * GTO_MAX_DOF + 4 * prm.P + 1);
+  hipLaunchKernelGGL(k_track_rollout, dim3((unsigned)((prm.B + prm.P - 1) / prm.P)), dim3(GTO_WAVE), lds, st, h->d_rb,
+                     h->dyn_buf.as<const DynDev>(), prm, sets, ref, pay, out);
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
+}
+
+extern "C" int gto_track_rollout_device(gto_handle* h, int32_t B, int32_t M, const double* duration, const double* q_ref,
+                                        const double* qd_ref, const double* qdd_ref, const double* kp, const double* kd,
+                                        const double* tau_max, double dt, double settle, int32_t feedforward,
+                                        const double* model_payload_mass, const double* model_payload_com,
+                                        const double* model_payload_inertia, const double* plant_payload_mass,
+                                        const double* plant_payload_com, const double* plant_payload_inertia,
+                                        const int32_t* locked, int32_t Mo, double* q_out, double* qd_out, double* t_out,
+                                        double* err_max, double* err_end, int32_t* sat_steps, int32_t* steps, int32_t* status_out,
+                                        void* stream) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  const double* const pay[6] = {model_payload_mass, model_payload_com, model_payload_inertia,
+                                plant_payload_mass, plant_payload_com, plant_payload_inertia};
+  TrackParams prm = {};
+  if (int rc = track_check(h, B, M, kp, kd, tau_max, dt, settle, feedforward, Mo, pay, prm)) return rc;
+  if (B == 0) return GTO_OK;
+  if (!duration || !q_ref || !qd_ref || !qdd_ref) return fail(h, GTO_ERR_INVALID_ARG, "gto_track_rollout: null reference array");
+  HIPCHK(h, hipSetDevice(h->device));
+  return track_launch(h, prm, fd_sets(h, locked, false), {duration, q_ref, qd_ref, qdd_ref},
+                      {pay[0], pay[1], pay[2], pay[3], pay[4], pay[5]},
+                      {q_out, qd_out, t_out, err_max, err_end, sat_steps, steps, status_out}, stream ? (hipStream_t)stream : h->stream);
+}
+
+extern "C" int gto_track_rollout(gto_handle* h, int32_t B, int32_t M, const double* duration, const double* q_ref, const double* qd_ref,
+                                 const double* qdd_ref, const double* kp, const double* kd, const double* tau_max, double dt,
+                                 double settle, int32_t feedforward, const double* model_payload_mass,
+                                 const double* model_payload_com, const double* model_payload_inertia,
+                                 const double* plant_payload_mass, const double* plant_payload_com,
+                                 const double* plant_payload_inertia, const int32_t* locked, int32_t Mo, double* q_out,
+                                 double* qd_out, double* t_out, double* err_max, double* err_end, int32_t* sat_steps,
+                                 int32_t* steps, int32_t* status_out) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  const double* const pay[6] = {model_payload_mass, model_payload_com, model_payload_inertia,
+                                plant_payload_mass, plant_payload_com, plant_payload_inertia};
+  TrackParams prm = {};
+  int rc;
+  if ((rc = track_check(h, B, M, kp, kd, tau_max, dt, settle, feedforward, Mo, pay, prm))) return rc;
+  for (int k = 0; k < 2; ++k)
+    if ((rc = payload_check(h, "gto_track_rollout: ", B, pay[3 * k], pay[3 * k + 1], pay[3 * k + 2]))) return rc;
+  if (B == 0) return GTO_OK;
+  if (!duration || !q_ref || !qd_ref || !qdd_ref) return fail(h, GTO_ERR_INVALID_ARG, "gto_track_rollout: null reference array");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t nB = (size_t)B, nd = h->rb.ndof, nM = (size_t)M, nO = (size_t)Mo;
+  Staging io(h);
+  TrackRef ref = {};
+  const double* dp[6];
+  TrackOut out = {};
+  if ((rc = io.in(duration, nB, &ref.duration))) return rc;
+  if ((rc = io.in(q_ref, nB * nM * nd, &ref.q))) return rc;
+  if ((rc = io.in(qd_ref, nB * nM * nd, &ref.qd))) return rc;
+  if ((rc = io.in(qdd_ref, nB * nM * nd, &ref.qdd))) return rc;
+  for (int k = 0; k < 6; ++k)  // (a null array: a null device pointer)
+    if ((rc = io.in(pay[k], nB * (k % 3 == 0 ? 1 : k % 3 == 1 ? 3 : 6), &dp[k]))) return rc;
+  if ((rc = io.out(q_out, nB * nO * nd, &out.q))) return rc;
+  if ((rc = io.out(qd_out, nB * nO * nd, &out.qd))) return rc;
+  if ((rc = io.out(t_out, nB * nO, &out.t))) return rc;
+  if ((rc = io.out(err_max, nB, &out.err_max))) return rc;
+  if ((rc = io.out(err_end, nB, &out.err_end))) return rc;
+  if ((rc = io.out(sat_steps, nB, &out.sat_steps))) return rc;
+  if ((rc = io.out(steps, nB, &out.steps))) return rc;
+  if ((rc = io.out(status_out, nB, &out.status))) return rc;
+  if ((rc = track_launch(h, prm, fd_sets(h, locked, false), ref, {dp[0], dp[1], dp[2], dp[3], dp[4], dp[5]}, out, h->stream))) return rc;
+  return io.finish();
+}
+
+extern "C" {
 
 int gto_eval_points(gto_handle* h, int32_t scene_id, int32_t nq, const double* q, const double* base_pos, int32_t use_obs,
                     double* xyz_out, int32_t* offset_out, double* value_out, double* grad_out) {

@@ -126,7 +126,7 @@ class GraspChain:
     # ------------------------------------------------------------------ the chain
     def plan_objects(self, qc, ik_goals, plan_goals, n_grasps, fields, base_position, axis_standoff="x", use_standoff=True,
                      interpolate=True, pos_tol=0.01, rot_tol_deg=5.0, ik_collision_threshold=5.0, float32_solutions=True,
-                     observation=None, retime=None, n_seeds=1, max_points=5, retrieve=None):
+                     observation=None, retime=None, n_seeds=1, max_points=5, retrieve=None, track=None):
         """B objects with up to n_max candidate grasps each.
 
         qc (B, ndof) or (ndof,); ik_goals, plan_goals (B, n_max, 4, 4): the poses IK is solved to and the poses the plan
@@ -150,7 +150,14 @@ class GraspChain:
         subdiv and n_samples, on the chain's stream behind the retrieve stage (gto_retime_paths_device; ``reached_only`` in
         the retrieve dict: only columns 0 .. reached of a lift, the count made from retrieve_reached on the stream): the
         result gains retrieve_durations, retrieve_retime_status (B,) and, with ``retrieve_samples`` set in the retime dict,
-        retrieve_q / retrieve_qd / retrieve_qdd (B, n_samples, ndof).
+        retrieve_q / retrieve_qd / retrieve_qdd (B, n_samples, ndof).  track: a dict ``kp, kd[, tau_max, dt, settle,
+        feedforward, model_payload, plant_payload, locked]`` (the keywords of ``utils.track_trajectories``) to roll the
+        retimed trajectories forward under that joint controller (gto_track_rollout_device), on the chain's stream behind the
+        retime calls with no further synchronisation; it needs ``retime``.  The approach is rolled out with an empty hand;
+        the retrieve path with each object's payload in the hand -- ``plant_payload``, default the retime dict's ``payload``
+        -- which the controller knows unless ``model_payload`` says otherwise.  The result gains track_err_max,
+        track_err_end, track_sat_steps, track_status (B,) and, with retrieve, the four retrieve_track_*.  The chain keeps the
+        samples the rollout reads in its own device buffers.  track=None leaves the chain launch for launch what it is.
 
         Returns a namespace: plans (B, ndof, T), dQ (B, ndof, T-1), cost, iters, status (B,), n_accepted (B,) (0: no
         feasible grasp, the driver's ``continue``; the plan is then the solve from the constant seed to all goals),
@@ -177,7 +184,7 @@ class GraspChain:
                     self._up("n_grasps", n_grasps, np.int32), {})
 
         return self._plan(B, n_max, feed, qc, fields, base_position, axis_standoff, use_standoff, interpolate, pos_tol, rot_tol_deg,
-                          ik_collision_threshold, float32_solutions, observation, retime, n_seeds, max_points, retrieve)
+                          ik_collision_threshold, float32_solutions, observation, retime, n_seeds, max_points, retrieve, track)
 
     def retrieve_spec(self, retrieve):
         """A ``retrieve`` dict with its defaults filled in: mode "lift" (straight up by ``distance`` = 0.3 m in ``steps`` = 10
@@ -285,7 +292,7 @@ class GraspChain:
         return n_grasps
 
     def _plan(self, B, n_max, feed, qc, fields, base_position, axis_standoff, use_standoff, interpolate, pos_tol, rot_tol_deg,
-              ik_collision_threshold, float32_solutions, observation, retime, n_seeds, max_points, retrieve=None):
+              ik_collision_threshold, float32_solutions, observation, retime, n_seeds, max_points, retrieve=None, track=None):
         """What ``plan_objects`` and ``plan_grasps`` share: the chain from the goal sets on.  ``feed(stream, d_base)`` is called
         on the chain's stream behind the uploads of scene ids, qc and base; it returns the device arrays ik_goals, plan_goals
         (B, n_max, 16), n_grasps (B,) -- uploaded, or written by launches it enqueued -- and a dict of further device arrays
@@ -315,6 +322,33 @@ class GraspChain:
             if prof[0] == "torque":  # checked here, before anything is enqueued
                 from ._capi import payload_arrays, retime_torque_limits
                 torque = dict(tau_max=retime_torque_limits(d, retime.get("tau_max")), payload=payload_arrays(retime.get("payload"), B))
+        tr = None  # the checked controller and payload arrays of a track request, before anything is enqueued
+        if track is not None:
+            from ._capi import payload_arrays, track_controller
+            from .gto_planner import TRACK_OPTIONS
+            if retime is None:
+                raise ValueError("plan_objects: track needs retime, the trajectories it rolls out")
+            unknown = set(track) - (TRACK_OPTIONS - {"n_samples"})
+            if unknown or "kp" not in track or "kd" not in track:
+                raise TypeError(f"plan_objects: track needs kp and kd and takes {sorted(TRACK_OPTIONS - {'n_samples'})}, got {sorted(track)}")
+            plant = track.get("plant_payload", retime.get("payload"))
+            tr = dict(ctl={k: v for k, v in track.items() if not k.endswith("_payload")}, plant=payload_arrays(plant, B),
+                      model=payload_arrays(track.get("model_payload", plant), B))
+            track_controller(d, **tr["ctl"])
+
+        def rollout(tag, M_ref, d_duration, d_samples, model, plant):
+            """One gto_track_rollout_device behind the retime call that wrote d_duration and d_samples; returns its outputs."""
+            outs = dict(err_max=self._dev(tag + "err_max", (B,), f64), err_end=self._dev(tag + "err_end", (B,), f64),
+                        sat_steps=self._dev(tag + "sat_steps", (B,), i32), status=self._dev(tag + "status", (B,), i32))
+            up = lambda kind, pl: [None if a is None else self._up(f"{tag}{kind}_{k}", a, np.float64).data_ptr()  # noqa: E731
+                                   for k, a in zip(("mass", "com", "inertia"), pl)]
+            h.track_rollout_device(B, M_ref, d_duration.data_ptr(), *[t.data_ptr() for t in d_samples], n_samples=2,
+                                   model_payload=up("model", model), plant_payload=up("plant", plant),
+                                   err_max=outs["err_max"].data_ptr(), err_end=outs["err_end"].data_ptr(),
+                                   sat_steps=outs["sat_steps"].data_ptr(), status_out=outs["status"].data_ptr(), stream=st, **tr["ctl"])
+            return {tag + k: v for k, v in outs.items()}
+
+        tracked = {}
         with torch.cuda.stream(self.stream):
             st = self.stream.cuda_stream
             d_sid, d_qc, d_base = self._up("sid", sid, np.int32), self._up("qc", qc, np.float64), self._up("base", base, np.float64)
@@ -433,22 +467,28 @@ class GraspChain:
                                                       held_label=ptr(held.label), base_pos=base, stream=st)
                 if retime is not None:
                     d_dur, d_rst = self._dev("durations", (B,), f64), self._dev("retime_status", (B,), i32)
+                    samp = {}  # the approach's samples, kept only for the rollout
+                    if tr is not None:
+                        d_tsamp = [self._dev("track_ref_" + k, (B, int(retime.get("n_samples", 100)), ndof), f64) for k in ("q", "qd", "qdd")]
+                        samp = {k + "_out": v.data_ptr() for k, v in zip(("q", "qd", "qdd"), d_tsamp)}
                     if convex is None:
                         h.retime_batch_device(B, d_Q.data_ptr(), retime["vmax"], retime["amax"], int(retime.get("subdiv", 2)),
                                               int(retime.get("n_samples", 100)), duration_out=d_dur.data_ptr(),
-                                              status_out=d_rst.data_ptr(), stream=st)
+                                              status_out=d_rst.data_ptr(), stream=st, **samp)
                     elif torque is not None:  # the approach: the hand is empty
                         d_rit = self._dev("retime_iters", (B,), i32)
                         h.retime_paths_torque_device(B, T, d_Q.data_ptr(), retime["vmax"], retime["amax"], tau_max=torque["tau_max"],
                                                      subdiv=int(retime.get("subdiv", 2)), n_samples=int(retime.get("n_samples", 100)),
                                                      gap_tol=convex[0], max_newton=convex[1], duration_out=d_dur.data_ptr(),
-                                                     status_out=d_rst.data_ptr(), iters_out=d_rit.data_ptr(), stream=st)
+                                                     status_out=d_rst.data_ptr(), iters_out=d_rit.data_ptr(), stream=st, **samp)
                     else:  # the plans are the Tp = T case of the paths call
                         d_rit = self._dev("retime_iters", (B,), i32)
                         h.retime_paths_convex_device(B, T, d_Q.data_ptr(), retime["vmax"], retime["amax"],
                                                      subdiv=int(retime.get("subdiv", 2)), n_samples=int(retime.get("n_samples", 100)),
                                                      gap_tol=convex[0], max_newton=convex[1], duration_out=d_dur.data_ptr(),
-                                                     status_out=d_rst.data_ptr(), iters_out=d_rit.data_ptr(), stream=st)
+                                                     status_out=d_rst.data_ptr(), iters_out=d_rit.data_ptr(), stream=st, **samp)
+                    if tr is not None:  # the approach: the hand is empty, and the controller knows it
+                        tracked.update(rollout("track_", int(retime.get("n_samples", 100)), d_dur, d_tsamp, (None,) * 3, (None,) * 3))
                     if retrieve is not None:  # the retrieve path on the same clock rules, behind the retrieve stage
                         sub, ns = int(retime.get("subdiv", 2)), int(retime.get("n_samples", 100))
                         d_nc = None
@@ -459,8 +499,11 @@ class GraspChain:
                         d_rsamp, d_rtau = [None] * 3, None
                         if retime.get("retrieve_samples", False):
                             d_rsamp = [self._dev("retrieve_" + k, (B, ns, ndof), f64) for k in ("q", "qd", "qdd")]
+                        d_rref = d_rsamp  # what the rollout reads: the caller's samples, or buffers of the chain's own
+                        if tr is not None and d_rsamp[0] is None:
+                            d_rref = [self._dev("retrieve_track_ref_" + k, (B, ns, ndof), f64) for k in ("q", "qd", "qdd")]
                         outs = dict(duration_out=d_rdur.data_ptr(), status_out=d_rrst.data_ptr(),
-                                    **{k + "_out": None if v is None else v.data_ptr() for k, v in zip(("q", "qd", "qdd"), d_rsamp)})
+                                    **{k + "_out": None if v is None else v.data_ptr() for k, v in zip(("q", "qd", "qdd"), d_rref)})
                         if convex is None:
                             h.retime_paths_device(B, cols, d_rp.data_ptr(), retime["vmax"], retime["amax"],
                                                   n_cols=None if d_nc is None else d_nc.data_ptr(), subdiv=sub, n_samples=ns,
@@ -483,10 +526,13 @@ class GraspChain:
                                                          n_cols=None if d_nc is None else d_nc.data_ptr(), subdiv=sub, n_samples=ns,
                                                          gap_tol=convex[0], max_newton=convex[1], iters_out=d_rrit.data_ptr(),
                                                          **outs, stream=st)
+                        if tr is not None:  # the object is in the hand now
+                            tracked.update(rollout("retrieve_track_", ns, d_rdur, d_rref, tr["model"], tr["plant"]))
             out = dict(plans=d_Q, dQ=d_dQ, cost=d_f, iters=d_it, status=d_stat, n_accepted=d_nacc, seed_index=d_si, seed_cost=d_sc,
                        seed_dist=d_sd, q_solutions=d_q, err_pos=d_ep, err_rot=d_er, ik_cost=d_ic, ik_iters=d_ikit, ik_status=d_ikst,
                        accept=d_acc)
             out.update(extra)
+            out.update(tracked)
             if d_cnt is not None:
                 out["counts"] = d_cnt
             if N and retime is not None:

@@ -9,6 +9,10 @@ from .synthetic import standoff_pose
 from .utils import interpolate_waypoints
 
 
+# the keys of a track= request: the keywords of utils.track_trajectories
+TRACK_OPTIONS = frozenset(("kp", "kd", "tau_max", "dt", "settle", "n_samples", "feedforward", "model_payload", "plant_payload", "locked"))
+
+
 class GTOPlanner:
     def __init__(self, robot, link_ee, link_gripper, collision_avoidance=True, standoff_distance=-0.1,
                  standoff_offset=-10):
@@ -119,7 +123,7 @@ class GTOPlanner:
     def retrieve_path(self, plan, mode="lift", distance=0.3, steps=10, direction=(0.0, 0.0, 1.0), closed_joints=None,
                       closed_value=0.0, max_iter=50, pos_tol=0.01, rot_tol_deg=5.0, retime=None, observation=None,
                       held_points=None, n_held=None, object_pose=None, labels=None, held_label=None,
-                      base_position=(0.0, 0.0, 0.0)):
+                      base_position=(0.0, 0.0, 0.0), track=None):
         """The motion after the grasp (examples/pybullet_gto_planning.py:301-313) for a solved ``plan`` (ndof, T), or
         (B, ndof, T) for B of them: mode "lift" moves link_ee by ``distance`` along ``direction`` in ``steps`` IK steps, each
         seeded from the one before, with the gripper's pose held (the tabletop driver's env.retract; pybullet's position-only
@@ -139,7 +143,12 @@ class GTOPlanner:
         link_ee along the path from the grasp configuration -- the plan's last waypoint, which is column 0 of a lift
         and is not part of a reversed path -- and counted inside ``observation`` at every column
         (gto_check_held_paths; labels / held_label: the segmentation image of a depth observation and the held object's
-        label).  The return value then ends with one more element, the dict ``{"held_counts": (columns,) | (B, columns)}``."""
+        label).  The return value then ends with one more element, the dict ``{"held_counts": (columns,) | (B, columns)}``.
+        track: a dict ``kp, kd[, tau_max, dt, settle, n_samples, feedforward, model_payload, plant_payload, locked]`` (the
+        keywords of ``utils.track_trajectories``) to also roll the retimed trajectory forward under that joint controller
+        (gto_track_rollout); it needs ``retime``.  model_payload and plant_payload default to the retime's payload, on
+        link_ee.  The trajectory dict gains ``track_q, track_qd, track_t, track_err_max, track_err_end, track_sat_steps,
+        track_steps, track_status``."""
         from . import _capi
         from .grasp_chain import finger_joints
         plan = np.asarray(plan, dtype=np.float64)
@@ -149,6 +158,17 @@ class GTOPlanner:
         if retime is not None and retime.get("profile") == "torque":
             _capi.payload_arrays(retime.get("payload"), plans.shape[0])
             torque = (_capi.retime_torque_limits(self.robot.desc, retime.get("tau_max")), retime.get("payload"))
+        if track is not None:  # checked before the handle is made, like the torque request
+            if retime is None:
+                raise ValueError("retrieve_path: track needs retime, the trajectory it rolls out")
+            unknown = set(track) - TRACK_OPTIONS
+            if unknown or "kp" not in track or "kd" not in track:
+                raise TypeError(f"retrieve_path: track needs kp and kd and takes {sorted(TRACK_OPTIONS)}, got {sorted(track)}")
+            track = dict(track)
+            for k in ("model_payload", "plant_payload"):
+                track.setdefault(k, retime.get("payload"))
+                _capi.payload_arrays(track[k], plans.shape[0])
+            _capi.track_controller(self.robot.desc, **{k: v for k, v in track.items() if not k.endswith("_payload")})
         opts = _capi.default_opts()
         opts.T, opts.Tmax, opts.standoff_offset = self.T, self.Tmax, self.standoff_offset
         h = self.robot.solver_handle(self.link_ee, self.link_gripper, opts, role="retrieve")
@@ -202,4 +222,7 @@ class GTOPlanner:
             traj = h.retime_paths_convex(path, retime["vmax"], retime["amax"], gap_tol=gap_tol, max_newton=max_newton, **kw)
         else:
             traj = h.retime_paths(path, retime["vmax"], retime["amax"], **kw)
+        if track is not None:
+            rolled = h.track_rollout(traj["duration"], traj["q"], traj["qd"], traj["qdd"], **track)
+            traj.update({"track_" + k: v for k, v in rolled.items()})
         return ((path[0], int(reached[0]), {k: v[0] for k, v in traj.items()}) if single else (path, reached, traj)) + checks

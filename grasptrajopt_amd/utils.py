@@ -326,6 +326,54 @@ def inverse_dynamics(robot, q, qd, qdd, payload=None, link_ee=None):
     return tau[0] if one else tau
 
 
+def forward_dynamics(robot, q, qd, tau, payload=None, link_ee=None, locked=None):
+    """Joint accelerations that the forces ``tau`` cause at states (n, ndof) or one state (ndof,) on the GPU
+    (gto_forward_dynamics, include/gto_solver.h): the inverse of ``inverse_dynamics`` on the free joints, with the same
+    inertials and payload rules.  locked: None (every joint that is not optimised stands still: Panda's fingers, Fetch's
+    torso and head) or one flag per joint; locked joints get 0.  Returns (n, ndof); a row with a non-finite entry, or with a
+    free joint that moves no mass, is NaN."""
+    q = np.asarray(q, dtype=np.float64)
+    one = q.ndim == 1
+    if not robot.desc.has_inertials:
+        raise ValueError("forward_dynamics: the robot description has no link inertials (RobotDesc.set_link_inertials)")
+    if payload is not None and link_ee is None:
+        raise ValueError("forward_dynamics: a payload needs link_ee, the link that carries it")
+    ln = robot.desc.link_names[-1] if link_ee is None else link_ee
+    qdd = robot.solver_handle(ln, robot.desc.link_names[-1], role="util").forward_dynamics(q, qd, tau, payload, locked)[0]
+    return qdd[0] if one else qdd
+
+
+def track_trajectories(robot, retimed, kp, kd, tau_max=None, dt=1e-3, settle=0.0, n_samples=100, feedforward="full",
+                       model_payload=None, plant_payload=None, locked=None, link_ee=None):
+    """Roll retimed trajectories forward under a torque-limited joint controller on the GPU (gto_track_rollout,
+    include/gto_solver.h).  retimed: the dict any ``retime_plans`` / ``retime_paths`` profile returns (duration (B,), q / qd /
+    qdd (B, M, ndof)).  Every ``dt`` the controller sets tau = clip(ff + kp (q_ref - q) + kd (qd_ref - qd), +-tau_max) and
+    holds it while the plant integrates (RK4); ``settle`` seconds follow the reference's end.  kp, kd: one value or one per
+    joint; tau_max: None = the description's effort limits; feedforward: "none", "gravity" (the model's holding torque at
+    q_ref) or "full" (its inverse dynamics along the reference).  model_payload is what the controller believes the hand
+    holds, plant_payload what it holds (each the dict of ``inverse_dynamics`` on ``link_ee``, one value or one per
+    trajectory).  locked: as in ``forward_dynamics``; locked joints stand at the reference's start.  Returns a dict: q, qd
+    (B, n_samples, ndof) and t (B, n_samples), the state after step floor(m steps / (n_samples - 1)); err_max, err_end
+    (B,), the largest and the last |q - q_ref| over the free joints; sat_steps, steps, status (B,) (2: NaN outputs)."""
+    from . import _capi
+    if not robot.desc.has_inertials:
+        raise ValueError("track_trajectories: the robot description has no link inertials (RobotDesc.set_link_inertials)")
+    missing = [k for k in ("duration", "q", "qd", "qdd") if k not in retimed]
+    if missing:
+        raise ValueError(f"track_trajectories: retimed lacks {missing}: the dict of retime_plans / retime_paths expected")
+    B = np.shape(retimed["duration"])[0]
+    _capi.track_controller(robot.desc, kp, kd, tau_max, dt, settle, n_samples, feedforward, locked)
+    for pl in (model_payload, plant_payload):
+        _capi.payload_arrays(pl, B)
+        if pl is not None and link_ee is None:
+            raise ValueError("track_trajectories: a payload needs link_ee, the link that carries it")
+    ln = robot.desc.link_names[-1] if link_ee is None else link_ee
+    h = robot.solver_handle(ln, robot.desc.link_names[-1], role="util")
+    return h.track_rollout(retimed["duration"], retimed["q"], retimed["qd"], retimed["qdd"], kp, kd, tau_max=tau_max, dt=dt,
+                           settle=settle, n_samples=n_samples, feedforward=feedforward, model_payload=model_payload,
+                           plant_payload=plant_payload, locked=locked)
+
+
 def convert_plan_to_trajectory_toppra(robot, plan, is_show: bool = False):
     """gto/utils.py:283-323 on the GPU: plan (ndof, T) -> (qs_sample, qds_sample, qdds_sample, ts_sample), 100 samples of
     each, in the reference's order.  Velocity limits from the URDF for all ndof joints (the reference passes the n_opt

@@ -1100,6 +1100,88 @@ int gto_retime_paths_torque_device(gto_handle* h, int32_t B, int32_t Tp, const d
                                    double* q_out, double* qd_out, double* qdd_out, double* tau_out, int32_t* status_out,
                                    int32_t* iters_out, void* stream);
 
+/* ---- forward dynamics and the tracking rollout.  Additions (the ABI number stays). ------------------------------------- */
+
+/* Forward dynamics of n rows: the accelerations qdd that the joint forces tau cause at the state (q, qd), with the payload
+ * rules of gto_inverse_dynamics (ID below).  A joint is FREE when some actuated frame names it and `locked` does not mark
+ * it; locked == NULL locks every joint that is not one of the handle's optimised joints (the parameter joints: Panda's
+ * fingers, Fetch's torso and head), and a joint no frame names is always locked.  Locked joints get qdd = 0: a constraint
+ * force holds them, and it is not reported.  On the free joints M_ff qdd_f = (tau - c)_f is solved by a Cholesky
+ * factorisation in FP64, with c = ID(q, qd, 0) and the mass matrix from M e_j = ID(q, 0, e_j) - ID(q, 0, 0), symmetrised
+ * (M_ij <- (M_ij + M_ji) / 2) before it is factored, the free joints in ascending order.
+ *   locked      [ndof] HOST or NULL: non-zero = locked.
+ *   M_out       [n, ndof, ndof] or NULL: the symmetrised mass matrix, exactly symmetric; the columns of locked joints that a
+ *               frame names included, zero rows and columns for joints no frame names.
+ *   status_out  [n] or NULL: GTO_STATUS_CONVERGED, or GTO_STATUS_NUMERICAL for a row with a non-finite entry in q, qd or
+ *               tau, a pivot <= 0 (a free joint that moves no mass) or a non-finite solution: that row of qdd_out and of
+ *               M_out is NaN, and no other row changes.
+ * A handle without inertials answers GTO_ERR_INVALID_ARG "no link inertials set"; n < 0, a null q / qd / tau / qdd_out, a
+ * payload mass that is negative or not finite, com / inertia without a mass: GTO_ERR_INVALID_ARG before any launch; n = 0:
+ * GTO_OK.  A row's result depends on the row alone, bit for bit, at any n and position.  Host pointers, synchronous.
+ * Replaces: the simulated robot behind env.robot.execute_plan (examples/pybullet_gto_planning.py:301,313), together with
+ * gto_track_rollout. */
+int gto_forward_dynamics(gto_handle* h, int32_t n, const double* q, const double* qd, const double* tau /*[n,ndof] each*/,
+                         const double* payload_mass /*[n] or NULL*/, const double* payload_com /*[n,3] or NULL*/,
+                         const double* payload_inertia /*[n,6] or NULL*/, const int32_t* locked /*[ndof] HOST or NULL*/,
+                         double* qdd_out /*[n,ndof]*/, double* M_out /*[n,ndof,ndof] or NULL*/,
+                         int32_t* status_out /*[n] or NULL*/);
+
+/*
+ * Roll B retimed trajectories forward under a torque-limited joint controller.  The reference of path b is what every
+ * retime entry point returns: duration[b] and the samples q_ref, qd_ref, qdd_ref [B, M, ndof] at linspace(0, duration, M),
+ * M >= 2.  Between samples q_ref(t) is the cubic Hermite interpolant of (q_m, qd_m), qd_ref(t) its derivative and
+ * qdd_ref(t) linear between the qdd_m; from t = duration on (at once when duration = 0) it is the last sample with zero
+ * derivatives, for `settle` more seconds.  The controller is evaluated once per control period dt, at the period's start
+ * t = k dt, and its torque is held over the period:
+ *     tau = clip( ff(t) + kp o (q_ref - q) + kd o (qd_ref - qd), +-tau_max ),
+ * ff = 0 (feedforward = 0), ID_model(q_ref, 0, 0) (1) or ID_model(q_ref, qd_ref, qdd_ref) (2).  The plant integrates
+ * qdd = FD_plant(q, qd, tau) over the period with one classical RK4 step.  ID_model and FD_plant are gto_inverse_dynamics
+ * and gto_forward_dynamics on the handle's inertials with two SEPARATE payloads per path: model_payload_* is what the
+ * controller believes, plant_payload_* what the hand really holds (each [B], [B,3], [B,6] or NULL, the payload rules of
+ * gto_inverse_dynamics).  The start state is q_ref[0], and qd_ref[0] on the free joints.  Locked joints (the `locked`
+ * rule of gto_forward_dynamics) stand at q_ref[0] with zero velocity for the whole rollout, in the plant and in the
+ * feedforward alike; whatever else the reference says about them is ignored, and they are left out of every error
+ * measure.  Joint limits are not enforced and there is no contact model.  K_b = ceil((duration_b + settle) / dt) steps,
+ * 1 <= K_b <= 2^20.
+ *   kp, kd      [ndof] HOST: finite, >= 0.       tau_max  [ndof] HOST: > 0, +inf = no limit.
+ *   dt > 0, settle >= 0, both finite; feedforward in {0, 1, 2}; M >= 2; Mo >= 2.  Anything else, a handle without inertials
+ *   ("no link inertials set"), a null reference array, com / inertia without a mass and (gto_track_rollout, HOST arrays) a
+ *   payload mass that is negative or not finite: GTO_ERR_INVALID_ARG before any launch.  B = 0: GTO_OK without one.
+ * Outputs, any of which may be NULL:
+ *   q_out, qd_out [B, Mo, ndof], t_out [B, Mo]: sample m is the state after step k_m = floor(m K_b / (Mo - 1)) (integer
+ *               arithmetic), t = k_m dt; nothing is interpolated.  Sample 0 is the start state, sample Mo - 1 the last.
+ *   err_max     [B] the largest |q - q_ref| over the steps and the free joints, measured at the period ends.
+ *   err_end     [B] the same at the last step.
+ *   sat_steps   [B] the periods in which the clip changed a free joint's torque.
+ *   steps       [B] K_b.
+ *   status_out  [B] GTO_STATUS_CONVERGED, or GTO_STATUS_NUMERICAL: a duration that is negative or not finite, a non-finite
+ *               sample of a free joint (or first position of a locked one), K_b out of range, a payload mass on the device
+ *               that is negative or not finite, a pivot <= 0, or a state that stops being finite.  Every output of that
+ *               path is NaN then, sat_steps and steps are 0, and no other path changes.
+ * gto_track_rollout takes HOST arrays and is synchronous.  gto_track_rollout_device: every per-path array (duration, the
+ * samples, the payloads, the outputs) is in DEVICE memory and unseen by the host; kp, kd, tau_max and locked are HOST
+ * arrays that travel as kernel arguments; one launch enqueued on `stream` (NULL = the handle's) with no allocation and no
+ * synchronisation at all.  Its results are bit for bit the host variant's, and every path's result is bit for bit the same
+ * in any batch and at any position in it.
+ */
+int gto_track_rollout(gto_handle* h, int32_t B, int32_t M, const double* duration /*[B]*/, const double* q_ref,
+                      const double* qd_ref, const double* qdd_ref /*[B,M,ndof] each*/, const double* kp, const double* kd,
+                      const double* tau_max /*[ndof] HOST each*/, double dt, double settle, int32_t feedforward,
+                      const double* model_payload_mass, const double* model_payload_com, const double* model_payload_inertia,
+                      const double* plant_payload_mass, const double* plant_payload_com, const double* plant_payload_inertia,
+                      const int32_t* locked /*[ndof] HOST or NULL*/, int32_t Mo, double* q_out, double* qd_out /*[B,Mo,ndof]*/,
+                      double* t_out /*[B,Mo]*/, double* err_max, double* err_end /*[B]*/, int32_t* sat_steps, int32_t* steps,
+                      int32_t* status_out /*[B]*/);
+int gto_track_rollout_device(gto_handle* h, int32_t B, int32_t M, const double* duration /*DEVICE*/, const double* q_ref,
+                             const double* qd_ref, const double* qdd_ref /*DEVICE*/, const double* kp, const double* kd,
+                             const double* tau_max /*HOST*/, double dt, double settle, int32_t feedforward,
+                             const double* model_payload_mass, const double* model_payload_com,
+                             const double* model_payload_inertia, const double* plant_payload_mass,
+                             const double* plant_payload_com, const double* plant_payload_inertia /*DEVICE*/,
+                             const int32_t* locked /*HOST*/, int32_t Mo, double* q_out, double* qd_out, double* t_out,
+                             double* err_max, double* err_end, int32_t* sat_steps, int32_t* steps, int32_t* status_out,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

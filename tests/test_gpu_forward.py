@@ -1,0 +1,537 @@
+"""gto_forward_dynamics, gto_track_rollout and gto_track_rollout_device (csrc/gto_forward.h: fd_solve, k_forward_dynamics,
+k_track_rollout) against tests/forward_ref.py, which tests/test_forward_cpu.py holds against physics, and the Python layers
+above them.
+
+Forward dynamics: the 11 robots of tests/dynamics_cases.py at n = 67 rows (more than one workgroup on every robot: a
+workgroup holds fd_rows(F, ndof) = min(64, 63488 // ((15 F + ndof^2 + 7 ndof) 8 + 4)) rows) and n = 1; payload absent, mass
+only, full; locked NULL, none, all but one, all.  Where `locked` leaves a joint free that moves no mass (the seeded robots
+have a massless frame each) the case locks that joint too; the massless free joint has a test of its own.
+
+Rollout: Panda, Fetch, prismatic_chain and limit_chain (32 frames, 16 free joints under locked = NULL: 18 passes in three
+rounds of the 8 lanes a path gets there), B = 5, M = 9, Mo = 7, dt = 2 ms, at most 30 steps (5 on limit_chain, whose numpy
+restatement takes a quarter of a second per step), every feedforward mode, the plant's payload not the model's, one case that saturates.
+Tolerance of q_out, qd_out, err_max, err_end: 16 d, d the largest difference between the restatement run with its two
+mass-matrix orderings (Jacobian sum / unit-acceleration columns) over these very cases, measured on the CPU with
+forward_ref.rollout_batch(columns=False) against (columns=True); the GPU's frame-local arithmetic is a third ordering of the
+same sums, and the factor covers its contraction into FMAs.  Measured, the largest over the four modes of each robot:
+    panda 4.33e-15   fetch 5.67e-12   prismatic_chain 1.57e-12   limit_chain 1.44e-11
+so d = ROLLOUT_D = 1.44e-11 (the seeded bodies of the generated robots make worse-conditioned mass matrices than Panda's).
+The same for the energy drifts of the free fall at h = 0.02 and 0.01: 2.84e-14 and 1.42e-14, ENERGY_D = 2.84e-14 (one unit
+of round-off of an energy of 103 J is 2.3e-14).
+No case's own | |tau| - tau_max | comes within 1e-9 relative of a clip decision: the smallest margin over all of them is
+4.4e-3 (measured there, asserted here again on the restatement's run), so sat_steps and steps must be equal.
+"""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import dynamics_cases as dc
+import dynamics_ref as dr
+import forward_ref as fr
+from test_dynamics_cpu import mass_matrix
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+N = 67
+ROLLOUT_ROBOTS = ("panda", "fetch", "prismatic_chain", "limit_chain")
+ROLLOUT_D = 1.44e-11
+ENERGY_D = 2.84e-14
+B, M, MO, DT = 5, 9, 7, 2e-3
+
+
+def same(a, b):
+    """Bit for bit; a NaN equals a NaN."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.dtype != b.dtype or a.shape != b.shape:
+        return False
+    if a.dtype == np.float64:
+        return bool(((a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))).all())
+    return bool((a == b).all())
+
+
+def fd_rows(F, ndof):
+    """fd_rows_per_block of csrc/gto_forward.h, restated from its constants."""
+    return min(64, (64 * 1024 - 2048) // ((15 * F + ndof * ndof + 7 * ndof) * 8 + 4))
+
+
+def as_dict(pl, rows=slice(None)):
+    if pl is None:
+        return None
+    return {k: v[rows] for k, v in zip(("mass", "com", "inertia"), pl) if v is not None}
+
+
+@pytest.fixture(scope="module")
+def capi():
+    import __graft_entry__ as g
+    g.build()
+    from grasptrajopt_amd import _capi
+    return _capi
+
+
+# ------------------------------------------------------------------------------------------------ forward dynamics
+@pytest.fixture(scope="module", params=dc.NAMES)
+def case(request, capi):
+    desc, ee, gr, ngp = dc.robot(request.param)
+    h = capi.SolverHandle(desc, ee, gr, device=0, n_gripper_points=ngp)
+    q, qd, _ = dr.in_limit_states(desc, N, seed=31)
+    qd[62:] = 0.0  # rows at rest
+    tau = np.random.default_rng(32).uniform(-15.0, 15.0, q.shape)
+    pls = dc.payloads(N, seed=33)
+    eef = desc.frame_index(ee)
+    ref = {}  # the mass matrix (Jacobian sum) and the bias of every row, once per payload kind
+    for kind, pl in pls.items():
+        Ms, cs = [], []
+        for i in range(N):
+            p = None if pl is None else (pl[0][i], None if pl[1] is None else pl[1][i], None if pl[2] is None else pl[2][i])
+            Ms.append(mass_matrix(desc, q[i], eef, p))
+            cs.append(dr.inverse_dynamics(desc, q[i], qd[i], np.zeros(desc.ndof), eef, p))
+        ref[kind] = (np.stack(Ms), np.stack(cs))
+    named = fr.named_joints(desc)
+    moving = named & (np.diag(ref["none"][0][0]) > 0)
+    one = np.ones(desc.ndof, dtype=np.int32)
+    if moving.any():
+        one[np.flatnonzero(moving)[0]] = 0
+    massless_opt = fr.free_joints(desc) & ~moving
+    locked = {"null": None if not massless_opt.any() else (~(fr.free_joints(desc) & moving)).astype(np.int32),
+              "none": (~moving).astype(np.int32), "all_but_one": one, "all": np.ones(desc.ndof, dtype=np.int32)}
+    yield dict(name=request.param, desc=desc, h=h, ee=eef, q=q, qd=qd, tau=tau, payloads=pls, ref=ref, locked=locked, named=named,
+               moving=moving, null_is_default=not massless_opt.any())
+    h.close()
+
+
+def test_the_robots_cover_the_layouts():
+    shapes = {name: (dc.robot(name)[0].n_frames, dc.robot(name)[0].ndof) for name in dc.NAMES}
+    rows = {fd_rows(*s) for s in shapes.values()}
+    assert 64 in rows and min(rows) <= 4 and all(r < N for r in rows)  # more than one workgroup on every robot
+
+
+@pytest.mark.parametrize("kind", ["none", "mass", "full"])
+def test_forward_dynamics_matches_the_reference(case, kind):
+    d, h, pl = case["desc"], case["h"], case["payloads"][kind]
+    Mref, cref = case["ref"][kind]
+    q, qd, tau = case["q"], case["qd"], case["tau"]
+    rows = fd_rows(d.n_frames, d.ndof)
+    assert case["null_is_default"] or case["name"] not in ("panda", "fetch")  # locked = NULL itself runs on the real robots
+    for lname, locked in case["locked"].items():
+        qdd, status, Mout = h.forward_dynamics(q, qd, tau, as_dict(pl), locked, want_mass_matrix=True)
+        free = fr.free_joints(d, locked)
+        assert (status == 0).all() and np.isfinite(qdd).all() and (qdd[:, ~free] == 0).all(), (lname, status)
+        if lname == "all":
+            assert not free.any() and not qdd.any()
+        assert np.array_equal(Mout, Mout.transpose(0, 2, 1))  # exactly symmetric
+        assert not Mout[:, ~case["named"], :].any() and not Mout[:, :, ~case["named"]].any()
+        scaleM = np.abs(Mref).max(axis=(1, 2))
+        errM = np.abs(Mout - Mref).max(axis=(1, 2)) / scaleM
+        worst_rt = worst_q = 0.0
+        for i in range(N):
+            p = None if pl is None else (pl[0][i], None if pl[1] is None else pl[1][i], None if pl[2] is None else pl[2][i])
+            if free.any():
+                Mff = Mref[i][np.ix_(free, free)]
+                want = np.linalg.solve(Mff, (tau[i] - cref[i])[free])
+                tol = 1e-11 * np.linalg.cond(Mff) * max(1.0, np.abs(want).max())
+                worst_q = max(worst_q, np.abs(qdd[i, free] - want).max() / tol)
+                back = dr.inverse_dynamics(d, q[i], qd[i], qdd[i], case["ee"], p)
+                scale = max(1.0, np.abs(tau[i]).max(), (np.abs(Mref[i]) @ np.abs(qdd[i])).max())
+                worst_rt = max(worst_rt, np.abs(back - tau[i])[free].max() / scale)
+        print(f"{case['name']} {kind} locked={lname}: round trip {worst_rt:.2e}, qdd error / tolerance {worst_q:.2e}, M {errM.max():.2e}")
+        assert worst_rt <= 1e-11 and worst_q <= 1.0 and errM.max() <= 1e-11
+        for i in (0, min(rows, N - 2), N - 1):  # a row alone is the row inside the batch, bit for bit
+            a, s, Ma = h.forward_dynamics(q[i], qd[i], tau[i], as_dict(pl, slice(i, i + 1)), locked, want_mass_matrix=True)
+            assert same(a[0], qdd[i]) and s[0] == 0 and same(Ma[0], Mout[i]), (lname, i)
+
+
+def test_rows_that_fail_fail_alone(case):
+    d, h = case["desc"], case["h"]
+    q, qd, tau = case["q"].copy(), case["qd"].copy(), case["tau"].copy()
+    locked = case["locked"]["none"]
+    good, s0, M0 = h.forward_dynamics(q, qd, tau, None, locked, want_mass_matrix=True)
+    q[3, 0], qd[40, d.ndof - 1], tau[N - 1, 0] = np.nan, np.inf, np.nan
+    got, s, Mg = h.forward_dynamics(q, qd, tau, None, locked, want_mass_matrix=True)
+    bad = np.zeros(N, dtype=bool)
+    bad[[3, 40, N - 1]] = True
+    assert (s[bad] == 2).all() and (s[~bad] == 0).all()
+    assert np.isnan(got[bad]).all() and np.isnan(Mg[bad]).all() and same(got[~bad], good[~bad]) and same(Mg[~bad], M0[~bad])
+    massless = case["named"] & ~case["moving"]
+    if massless.any():  # freed, the joint that moves no mass is a pivot of 0: every row, and nothing else is touched
+        got, s = h.forward_dynamics(case["q"], case["qd"], case["tau"], None, np.zeros(d.ndof, dtype=np.int32))
+        assert (s == 2).all() and np.isnan(got).all()
+
+
+def test_a_massless_finger_is_numerical_alone(capi):
+    desc, ee, gr, _ = dc.robot("panda")
+    h = capi.SolverHandle(desc, ee, gr, device=0)
+    q, qd, _ = dr.in_limit_states(desc, 4, seed=34)
+    tau = np.ones_like(q)
+    none = np.zeros(desc.ndof, dtype=np.int32)
+    good = h.forward_dynamics(q, qd, tau, None, none)
+    assert (good[1] == 0).all()
+    mass = desc.frame_mass.copy()
+    mass[desc.frame_index("panda_rightfinger")] = 0.0
+    try:
+        h.set_link_inertials(mass, desc.frame_com, desc.frame_inertia)
+        qdd, s = h.forward_dynamics(q, qd, tau, None, none)
+        assert (s == 2).all() and np.isnan(qdd).all()
+        qdd, s = h.forward_dynamics(q, qd, tau)  # the fingers locked: the arm does not care
+        assert (s == 0).all() and np.isfinite(qdd).all()
+    finally:
+        h.set_link_inertials(desc.frame_mass, desc.frame_com, desc.frame_inertia)
+    assert same(h.forward_dynamics(q, qd, tau, None, none)[0], good[0])
+    h.close()
+
+
+def test_refusals_leave_the_handle_and_the_outputs_alone(capi):
+    from grasptrajopt_amd.robot_desc import load_builtin
+    desc, ee, gr, _ = dc.robot("panda")
+    h = capi.SolverHandle(load_builtin("panda"), ee, gr, device=0)
+    nd = desc.ndof
+    q = np.zeros((2, nd))
+    with pytest.raises(capi.GTOError, match=r"\(-1\): no link inertials set$"):
+        h.forward_dynamics(q, q, q)
+    with pytest.raises(capi.GTOError, match=r"\(-1\): no link inertials set$"):
+        h.track_rollout(np.ones(2), np.zeros((2, 3, nd)), np.zeros((2, 3, nd)), np.zeros((2, 3, nd)), 1.0, 1.0, tau_max=10.0)
+    h.set_link_inertials(desc.frame_mass, desc.frame_com, desc.frame_inertia)
+    good = h.forward_dynamics(q, q, q)[0]
+    pd, pi = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    p = lambda a: None if a is None else a.ctypes.data_as(pd if a.dtype == np.float64 else pi)  # noqa: E731
+    out, st = np.full((2, nd), 7.0), np.full(2, 7, dtype=np.int32)
+    lib = h.lib
+    for mass, com, why in ((np.array([1.0, -0.5]), None, "payload mass must be >= 0 and finite"),
+                           (np.array([np.nan, 1.0]), None, "payload mass must be >= 0 and finite"),
+                           (None, np.zeros((2, 3)), "payload_com / payload_inertia without payload_mass")):
+        rc = lib.gto_forward_dynamics(h._h, 2, p(q), p(q), p(q), p(mass), p(com), None, None, p(out), None, p(st))
+        assert rc == -1 and lib.gto_last_error(h._h).decode() == why and (out == 7.0).all() and (st == 7).all()
+    assert lib.gto_forward_dynamics(h._h, 2, p(q), None, p(q), None, None, None, None, p(out), None, None) == -1
+    assert lib.gto_forward_dynamics(h._h, -1, p(q), p(q), p(q), None, None, None, None, p(out), None, None) == -1
+    assert lib.gto_forward_dynamics(h._h, 0, None, None, None, None, None, None, None, None, None, None) == 0
+    # the rollout's host arrays and scalars
+    ref = np.zeros((2, 3, nd))
+    dur, one, eff = np.ones(2), np.ones(nd), np.full(nd, 50.0)
+
+    def roll(kp=one, kd=one, tm=eff, dt=1e-3, settle=0.0, ff=2, M=3, Mo=4, mm=None, mc=None, pm=None, dur_=dur):
+        return lib.gto_track_rollout(h._h, 2, M, p(dur_), p(ref), p(ref), p(ref), p(kp), p(kd), p(tm), dt, settle, ff, p(mm), p(mc), None,
+                                     p(pm), None, None, None, Mo, p(out), None, None, None, None, None, None, p(st))
+
+    neg, nan, zero = one.copy(), one.copy(), eff.copy()
+    neg[2], nan[nd - 1], zero[0] = -1.0, np.nan, 0.0
+    for kw, why in ((dict(kp=neg), "kp and kd must be finite and >= 0"), (dict(kd=nan), "kp and kd must be finite and >= 0"),
+                    (dict(kp=np.full(nd, np.inf)), "kp and kd must be finite and >= 0"),
+                    (dict(tm=zero), "tau_max must be > 0 (+inf: no limit)"), (dict(tm=nan), "tau_max must be > 0 (+inf: no limit)"),
+                    (dict(dt=0.0), "dt must be finite and > 0"), (dict(dt=np.inf), "dt must be finite and > 0"),
+                    (dict(settle=-1.0), "settle must be finite and >= 0"), (dict(settle=np.nan), "settle must be finite and >= 0"),
+                    (dict(ff=3), "feedforward must be 0, 1 or 2"), (dict(ff=-1), "feedforward must be 0, 1 or 2"),
+                    (dict(M=1), "M and Mo must be >= 2"), (dict(Mo=1), "M and Mo must be >= 2"),
+                    (dict(mm=np.array([1.0, -1.0])), "payload mass must be >= 0 and finite"),
+                    (dict(pm=np.array([np.inf, 1.0])), "payload mass must be >= 0 and finite"),
+                    (dict(mc=np.zeros((2, 3))), "payload_com / payload_inertia without payload_mass"),
+                    (dict(dur_=None), "null reference array")):
+        assert roll(**kw) == -1 and lib.gto_last_error(h._h).decode() == "gto_track_rollout: " + why, kw
+        assert (out == 7.0).all() and (st == 7).all()
+    assert same(h.forward_dynamics(q, q, q)[0], good)
+    h.close()
+
+
+@pytest.mark.parametrize("name", ["panda", "fetch"])
+def test_utils_forward_dynamics_is_the_abi_call(name, capi):
+    from grasptrajopt_amd import utils
+    from grasptrajopt_amd.gto_models import GTORobotModel
+    from grasptrajopt_amd.robot_desc import load_builtin
+    d, ee, gr, _ = dc.robot(name)
+    h = capi.SolverHandle(d, ee, gr, device=0)
+    q, qd, tau = dr.in_limit_states(d, 9, seed=35)
+    robot = GTORobotModel(desc=d, device=0)
+    pl = as_dict(dc.payloads(9, seed=36)["full"])
+    assert same(utils.forward_dynamics(robot, q, qd, tau, payload=pl, link_ee=ee), h.forward_dynamics(q, qd, tau, pl)[0])
+    lk = np.zeros(d.ndof, dtype=np.int32)
+    lk[1] = 1
+    assert same(utils.forward_dynamics(robot, q, qd, tau, locked=lk), h.forward_dynamics(q, qd, tau, None, lk)[0])
+    one = utils.forward_dynamics(robot, q[3], qd[3], tau[3])
+    assert one.shape == (d.ndof,) and same(one, h.forward_dynamics(q[3], qd[3], tau[3])[0][0])
+    with pytest.raises(ValueError, match="needs link_ee"):
+        utils.forward_dynamics(robot, q[3], qd[3], tau[3], payload={"mass": 1.0})
+    bare = GTORobotModel(desc=load_builtin(name), device=0)
+    with pytest.raises(ValueError, match="no link inertials"):
+        utils.forward_dynamics(bare, q, qd, tau)
+    h.close()
+    for hh in robot._handles.values():
+        hh.close()
+
+
+# ------------------------------------------------------------------------------------------------ the rollout
+# durations of the five paths as multiples of the robot's longest (30 steps of 2 ms with the settle time); the fourth path
+# carries a NaN
+DURATIONS = np.array([0.05, 0.024, 0.0, 0.03, 0.013])
+SCALE = {"panda": 1.0, "fetch": 1.0, "prismatic_chain": 1.0, "limit_chain": 0.1}
+SETTLE = {"panda": 0.01, "fetch": 0.01, "prismatic_chain": 0.01, "limit_chain": 0.004}  # 5 steps, 2 on the slow one
+MODES = ("none", "gravity", "full", "saturating")
+
+
+def rollout_case(name):
+    """The inputs of the rollout cases of one robot: seeded smooth references from an in-limit start, gains, limits, payloads."""
+    desc, ee, gr, ngp = dc.robot(name)
+    rng = np.random.default_rng(41)
+    free = fr.free_joints(desc)
+    q0, _, _ = dr.in_limit_states(desc, B, seed=42)
+    dur = DURATIONS * SCALE[name]
+    amp = np.where(free, rng.uniform(-0.005, 0.005, (B, desc.ndof)), 0.0)
+    T = np.maximum(dur, 1e-3)[:, None, None]
+    x = np.linspace(0.0, 1.0, M)[None, :, None]
+    s, sd, sdd = 0.5 * (1 - np.cos(np.pi * x)), 0.5 * np.pi * np.sin(np.pi * x) / T, 0.5 * np.pi ** 2 * np.cos(np.pi * x) / T ** 2
+    q = q0[:, None, :] + amp[:, None, :] * s
+    qd, qdd = amp[:, None, :] * sd, amp[:, None, :] * sdd
+    eef = desc.frame_index(ee)
+    g = np.abs(np.stack([dr.inverse_dynamics(desc, q0[b], 0 * q0[b], 0 * q0[b], eef) for b in range(B)])).max(axis=0)
+    tau_max = np.where(free, 3.0 * np.maximum(g, 1.0) + 20.0, np.inf)
+    j = int(np.flatnonzero(free)[np.argmax(g[free])])
+    weak = tau_max.copy()
+    weak[j] = 0.4 * np.abs(dr.inverse_dynamics(desc, q0[0], 0 * q0[0], 0 * q0[0], eef))[j] + 1e-3  # path 0 cannot hold there
+    kp, kd = np.where(free, 200.0, 0.0), np.where(free, 10.0, 0.0)
+    model = dc.payloads(B, seed=43)["mass"]
+    plant = dc.payloads(B, seed=44)["full"]
+    return dict(desc=desc, ee=ee, eef=eef, gr=gr, ngp=ngp, dur=dur, q=q, qd=qd, qdd=qdd, kp=kp, kd=kd, tau_max=tau_max, weak=weak,
+                model=model, plant=plant, free=free, settle=SETTLE[name])
+
+
+def mode_args(c, mode):
+    return dict(feedforward={"none": 0, "gravity": 1, "full": 2, "saturating": 2}[mode], tau_max=c["weak"] if mode == "saturating" else c["tau_max"])
+
+
+def with_nan(c):
+    q = c["q"].copy()
+    q[3, M // 2, int(np.flatnonzero(c["free"])[0])] = np.nan
+    return q
+
+
+def gpu_rollout(h, c, mode, q=None, rows=slice(None), n_samples=MO):
+    a = mode_args(c, mode)
+    return h.track_rollout(c["dur"][rows], (c["q"] if q is None else q)[rows], c["qd"][rows], c["qdd"][rows], c["kp"], c["kd"],
+                           tau_max=a["tau_max"], dt=DT, settle=c["settle"], n_samples=n_samples, feedforward=a["feedforward"],
+                           model_payload=as_dict(c["model"], rows), plant_payload=as_dict(c["plant"], rows))
+
+
+@pytest.fixture(scope="module", params=ROLLOUT_ROBOTS)
+def roll(request, capi):
+    c = rollout_case(request.param)
+    c["name"] = request.param
+    c["h"] = capi.SolverHandle(c["desc"], c["ee"], c["gr"], device=0, n_gripper_points=c["ngp"])
+    yield c
+    c["h"].close()
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_rollout_matches_the_restatement(roll, mode):
+    c, h = roll, roll["h"]
+    a = mode_args(c, mode)
+    qn = with_nan(c)
+    want = fr.rollout_batch(c["desc"], c["eef"], c["dur"], qn, c["qd"], c["qdd"], c["kp"], c["kd"], a["tau_max"], dt=DT, settle=c["settle"],
+                            n_samples=MO, feedforward=a["feedforward"], model_payload=c["model"], plant_payload=c["plant"])
+    got = gpu_rollout(h, c, mode, qn)
+    assert want["clip_margin"].min() > 1e-9  # no clip decision hangs on round-off
+    assert want["status"].tolist() == [0, 0, 0, 2, 0] and got["status"].tolist() == [0, 0, 0, 2, 0]
+    assert np.array_equal(got["steps"], want["steps"]) and np.array_equal(got["sat_steps"], want["sat_steps"])
+    assert got["steps"].max() <= 60 and got["steps"][2] == round(c["settle"] / DT) and got["steps"][3] == 0 and got["sat_steps"][3] == 0
+    if mode == "saturating":
+        assert got["sat_steps"][0] > got["steps"][0] // 2
+    assert same(got["t"], want["t"])
+    tol = 16 * ROLLOUT_D
+    err = {k: np.nanmax(np.abs(got[k] - want[k])) for k in ("q", "qd", "err_max", "err_end")}
+    print(f"{c['name']} {mode}: steps {got['steps'].tolist()} sat {got['sat_steps'].tolist()} differences {err}, allowed {tol:.2e}")
+    for k in ("q", "qd", "t", "err_max", "err_end"):
+        assert np.isnan(got[k][3]).all() and np.isfinite(np.delete(got[k], 3, axis=0)).all()
+    assert max(err.values()) <= tol
+    # the NaN path's neighbours are bit for bit what they are without it
+    clean = gpu_rollout(h, c, mode)
+    for k in got:
+        assert same(np.delete(got[k], 3, axis=0), np.delete(clean[k], 3, axis=0)), k
+    assert clean["status"][3] == 0
+
+
+def test_energy_drift_matches_the_restatement(capi):
+    """The free fall of tests/test_forward_cpu.py's check 2 at h = 0.02 and 0.01."""
+    desc, ee, gr, _ = dc.robot("panda")
+    eef = desc.frame_index(ee)
+    h = capi.SolverHandle(desc, ee, gr, device=0)
+    q, qd, _ = dr.in_limit_states(desc, 1, seed=9)
+    free = fr.free_joints(desc)
+    q0, qd0 = q[0], np.where(free, 0.5 * qd[0], 0.0)
+    E0 = fr.energy(desc, q0, qd0, eef)
+    ref = np.stack([q0, q0])[None], np.stack([qd0, qd0])[None], np.zeros((1, 2, desc.ndof))
+    for step in (0.02, 0.01):
+        want = fr.rollout(desc, eef, 0.2, ref[0][0], ref[1][0], ref[2][0], 0.0, 0.0, np.inf, dt=step, n_samples=2, feedforward=0)
+        got = h.track_rollout([0.2], *ref, 0.0, 0.0, tau_max=np.inf, dt=step, n_samples=2, feedforward="none")
+        dw = fr.energy(desc, want["q"][1], want["qd"][1], eef) - E0
+        dg = fr.energy(desc, got["q"][0, 1], got["qd"][0, 1], eef) - E0
+        print(f"h = {step}: energy drift gpu {dg:.6e}, restatement {dw:.6e}")
+        assert got["status"][0] == 0 and got["steps"][0] == want["steps"] and abs(dg - dw) <= 16 * ENERGY_D
+    h.close()
+
+
+def test_a_path_is_the_same_in_any_batch(roll):
+    c, h = roll, roll["h"]
+    five = gpu_rollout(h, c, "full")
+    for b in range(B):
+        alone = gpu_rollout(h, c, "full", rows=slice(b, b + 1))
+        for k in five:
+            assert same(alone[k][0], five[k][b]), (b, k)
+    idx = np.arange(70) % B
+    idx[[0, 69]] = [4, 1]
+    c70 = dict(c, dur=c["dur"][idx], q=c["q"][idx], qd=c["qd"][idx], qdd=c["qdd"][idx],
+               model=tuple(None if a is None else a[idx] for a in c["model"]), plant=tuple(None if a is None else a[idx] for a in c["plant"]))
+    many = gpu_rollout(h, c70, "full")
+    for k in five:
+        assert same(many[k], five[k][idx]), k
+    other = gpu_rollout(h, c, "full", n_samples=12)  # more samples than some paths have steps: repeated states, the same numbers
+    for k in ("err_max", "err_end", "sat_steps", "steps", "status"):
+        assert same(other[k], five[k])
+    assert same(other["q"][:, -1], five["q"][:, -1]) and same(other["q"][:, 0], c["q"][:, 0])
+
+
+def device_rollout(h, c, mode, tensors, stream):
+    import torch
+    a = mode_args(c, mode)
+    out = dict(q=torch.full((B, MO, c["desc"].ndof), 7.0, dtype=torch.float64, device="cuda:0"),
+               qd=torch.full((B, MO, c["desc"].ndof), 7.0, dtype=torch.float64, device="cuda:0"),
+               t=torch.full((B, MO), 7.0, dtype=torch.float64, device="cuda:0"),
+               err_max=torch.full((B,), 7.0, dtype=torch.float64, device="cuda:0"),
+               err_end=torch.full((B,), 7.0, dtype=torch.float64, device="cuda:0"),
+               sat_steps=torch.full((B,), 7, dtype=torch.int32, device="cuda:0"), steps=torch.full((B,), 7, dtype=torch.int32, device="cuda:0"),
+               status=torch.full((B,), 7, dtype=torch.int32, device="cuda:0"))
+    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    h.track_rollout_device(B, M, ptr(tensors["dur"]), ptr(tensors["q"]), ptr(tensors["qd"]), ptr(tensors["qdd"]), c["kp"], c["kd"],
+                           tau_max=a["tau_max"], dt=DT, settle=c["settle"], n_samples=MO, feedforward=a["feedforward"],
+                           model_payload=[ptr(x) for x in tensors["model"]], plant_payload=[ptr(x) for x in tensors["plant"]],
+                           q_out=ptr(out["q"]), qd_out=ptr(out["qd"]), t_out=ptr(out["t"]), err_max=ptr(out["err_max"]),
+                           err_end=ptr(out["err_end"]), sat_steps=ptr(out["sat_steps"]), steps=ptr(out["steps"]),
+                           status_out=ptr(out["status"]), stream=stream.cuda_stream)
+    return out
+
+
+def to_device(c, q):
+    import torch
+    cu = lambda a: None if a is None else torch.from_numpy(np.array(a, order="C")).to("cuda:0")  # noqa: E731
+    return dict(dur=cu(c["dur"]), q=cu(q), qd=cu(c["qd"]), qdd=cu(c["qdd"]), model=[cu(a) for a in c["model"]],
+                plant=[cu(a) for a in c["plant"]])
+
+
+def test_device_variant_equals_the_host_variant_and_keeps_stream_order(roll):
+    import time
+    import torch
+    import held_stream as hs
+    c, h = roll, roll["h"]
+    qn = with_nan(c)
+    want = gpu_rollout(h, c, "saturating", qn)
+    stream = torch.cuda.Stream(device="cuda:0")
+    with hs.Scenario() as sc:
+        true = sc.keep(to_device(c, qn))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = sc.keep(device_rollout(h, c, "saturating", true, stream))
+        t_host = time.perf_counter() - t0
+        stream.synchronize()
+        for k in want:
+            assert same(out[k].cpu().numpy(), want[k]), k
+        # behind a busy stream: the inputs arrive on the stream after the hold, the call must not run ahead of them
+        blank = lambda x: None if x is None else torch.zeros_like(x)  # noqa: E731
+        late = sc.keep({k: ([blank(x) for x in v] if isinstance(v, list) else blank(v)) for k, v in true.items()})
+        event = hs.hold(stream, hs.hold_ms(t_host))
+        with torch.cuda.stream(stream):
+            for k, v in true.items():
+                for dst, src in zip(late[k] if isinstance(v, list) else [late[k]], v if isinstance(v, list) else [v]):
+                    if src is not None:
+                        dst.copy_(src, non_blocking=True)
+        out2 = sc.keep(device_rollout(h, c, "saturating", late, stream))
+        returned_while_held = hs.still_held(event)
+        stream.synchronize()
+        print(f"{c['name']}: returned while the stream was held: {returned_while_held}, enqueue {1e3 * t_host:.3f} ms")
+        for k in want:
+            assert same(out2[k].cpu().numpy(), want[k]), k
+        assert returned_while_held  # no synchronisation inside the call
+
+
+# ------------------------------------------------------------------------------------------------ the Python layers
+TRACK_OUT = ("err_max", "err_end", "sat_steps", "status")
+
+
+def test_chain_planner_and_utils_go_through_the_rollout(capi):
+    """The fixture of tests/test_gpu_retime_torque.py's layer test: two objects with three grasps each, a lift of four steps."""
+    import grasptrajopt_amd as g
+    from grasptrajopt_amd import utils
+    from grasptrajopt_amd.grasp_chain import GraspChain
+    from test_gpu_grasp_chain import chain_setup
+    nb, n, ns = 2, 3, 30
+    cfg, robot, fields, RT = chain_setup("panda", nb * n, seed=21)
+    dr.with_fixture_inertials(robot.desc, "panda")
+    RT = RT.reshape(nb, n, 4, 4)
+    qc = np.array(cfg["default_pose"], dtype=np.float64)
+    chain = GraspChain(robot, cfg["link_ee"], cfg["link_gripper"])
+    chain.max_iter = 20
+    vm, am = robot.desc.velocity, np.full(robot.ndof, 0.5)
+    held = dict(mass=[2.0, 0.5], com=[[0.0, 0.0, 0.05], [0.02, 0.0, 0.0]])
+    rt = dict(vmax=vm, amax=am, n_samples=ns, profile="torque", payload=held)
+    args, kw = (qc, RT, RT, [n, n], fields[0], np.array([0.01, -0.02, 0.0])), dict(axis_standoff=cfg["axis_standoff"])
+    lift = dict(mode="lift", distance=0.1, steps=4)
+    kp = np.array([600.0, 600, 600, 600, 250, 150, 50, 0, 0])
+    kd = np.array([50.0, 50, 50, 20, 20, 20, 10, 0, 0])
+    trk = dict(kp=kp, kd=kd, dt=4e-3, settle=0.02, feedforward="full")
+    h = chain._handle
+    plain = chain.plan_objects(*args, retrieve=lift, retime=dict(rt, retrieve_samples=True), **kw)
+    none = chain.plan_objects(*args, retrieve=lift, retime=dict(rt, retrieve_samples=True), track=None, **kw)
+    tracked = chain.plan_objects(*args, retrieve=lift, retime=dict(rt, retrieve_samples=True), track=trk, **kw)
+    new = {p + k for p in ("track_", "retrieve_track_") for k in TRACK_OUT}
+    assert set(vars(none)) == set(vars(plain)) and set(vars(tracked)) == set(vars(plain)) | new
+    for k, v in vars(plain).items():  # the option changes nothing else, and without it the chain is what it was
+        assert same(v, getattr(none, k)) and same(v, getattr(tracked, k)), k
+    approach = h.retime_paths_torque(tracked.plans, vm, am, n_samples=ns)  # an empty hand
+    want = h.track_rollout(approach["duration"], approach["q"], approach["qd"], approach["qdd"], **trk)
+    for k in TRACK_OUT:
+        assert same(getattr(tracked, "track_" + k), want[k]), k
+    assert (want["status"] == 0).all() and (want["steps"] > 100).all()
+    want = h.track_rollout(tracked.retrieve_durations, tracked.retrieve_q, tracked.retrieve_qd, tracked.retrieve_qdd,
+                           model_payload=held, plant_payload=held, **trk)
+    for k in TRACK_OUT:
+        assert same(getattr(tracked, "retrieve_track_" + k), want[k]), k
+    assert (want["status"] == 0).all()
+    # the chain's own sample buffers, and a controller that does not know what it holds
+    blind = chain.plan_objects(*args, retrieve=lift, retime=rt, track=dict(trk, model_payload=None), **kw)
+    assert not hasattr(blind, "retrieve_q") and same(blind.track_err_max, tracked.track_err_max)
+    want = h.track_rollout(tracked.retrieve_durations, tracked.retrieve_q, tracked.retrieve_qd, tracked.retrieve_qdd,
+                           model_payload=None, plant_payload=held, **trk)
+    for k in TRACK_OUT:
+        assert same(getattr(blind, "retrieve_track_" + k), want[k]), k
+    assert blind.retrieve_track_err_max[0] > tracked.retrieve_track_err_max[0]  # 2 kg nobody told the controller about
+    with pytest.raises(ValueError, match="needs retime"):
+        chain.plan_objects(*args, retrieve=lift, track=trk, **kw)
+    with pytest.raises(TypeError, match="kp and kd"):
+        chain.plan_objects(*args, retrieve=lift, retime=rt, track=dict(kp=kp), **kw)
+    with pytest.raises(ValueError, match="kp"):
+        chain.plan_objects(*args, retrieve=lift, retime=rt, track=dict(trk, kp=-1.0), **kw)
+    # GTOPlanner.retrieve_path: the same rollout of the first object's retrieve path
+    planner = g.GTOPlanner(robot, cfg["link_ee"], cfg["link_gripper"])
+    one = dict(mass=2.0, com=[0.0, 0.0, 0.05])
+    path, reached, traj = planner.retrieve_path(tracked.plans[0], "lift", distance=0.1, steps=4, retime=dict(rt, payload=one),
+                                                track=dict(trk, n_samples=11))
+    assert {"track_" + k for k in capi.TRACK_KEYS} <= set(traj) and traj["track_q"].shape == (11, robot.ndof)
+    for k in TRACK_OUT:
+        assert traj["track_" + k] == getattr(tracked, "retrieve_track_" + k)[0], k
+    with pytest.raises(ValueError, match="needs retime"):
+        planner.retrieve_path(tracked.plans[0], "lift", distance=0.1, steps=4, track=trk)
+    with pytest.raises(TypeError, match="kp and kd"):
+        planner.retrieve_path(tracked.plans[0], "lift", distance=0.1, steps=4, retime=dict(rt, payload=one), track=dict(trk, gain=1))
+    # utils.track_trajectories on a retimed dict
+    retimed = utils.retime_paths(robot, tracked.retrieve_path, alim=am, n_samples=ns, profile="torque", payload=held, link_ee=cfg["link_ee"])
+    u = utils.track_trajectories(robot, retimed, kp, kd, dt=4e-3, settle=0.02, n_samples=9, model_payload=held, plant_payload=held,
+                                 link_ee=cfg["link_ee"])
+    want = h.track_rollout(retimed["duration"], retimed["q"], retimed["qd"], retimed["qdd"], kp, kd, dt=4e-3, settle=0.02, n_samples=9,
+                           model_payload=held, plant_payload=held)
+    assert set(u) == set(capi.TRACK_KEYS)
+    for k in u:
+        assert same(u[k], want[k]), k
+    for k in TRACK_OUT:
+        assert same(u[k], getattr(tracked, "retrieve_track_" + k)), k
+    with pytest.raises(ValueError, match="needs link_ee"):
+        utils.track_trajectories(robot, retimed, kp, kd, plant_payload=held)
+    with pytest.raises(ValueError, match="lacks"):
+        utils.track_trajectories(robot, dict(duration=retimed["duration"]), kp, kd)
+    chain.close() if hasattr(chain, "close") else None
