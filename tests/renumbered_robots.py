@@ -242,6 +242,153 @@ def dynamics_inputs(view):
 RETIME_SEEDS = {}   # case -> seed of retime_ref.random_plans where 0 does not converge at every plan
 
 
+# ------------------------------------------------------------------- forward dynamics, the rollout and the torque retime
+FORWARD_SETTINGS = ("null", "default", "all_but_one", "half")
+HALF_SEEDS = {}     # case -> seed of the `half` list where 0 leaves the free joints contiguous in one of the numberings
+ROLLOUT_B, ROLLOUT_M, ROLLOUT_MO, ROLLOUT_DT = 3, 9, 7, 2e-3
+ROLLOUT_DURATIONS = np.array([0.029, 0.0, 0.013])
+# case -> (scale of ROLLOUT_DURATIONS, settle time): 20, 5 and 12 steps; 5, 2 and 4 on the robots whose restatement is slow
+ROLLOUT_CLOCK = {"r1": (1.0, 0.01), "r9": (1.0, 0.01), "panda": (1.0, 0.01), "r3": (0.2, 0.004), "r55": (0.2, 0.004)}
+ROLLOUT_MODES = ("full", "saturating")
+ROLLOUT_LOCKS = ("default", "freed")
+ROLLOUT_SEEDS = {}  # case -> seed of rollout_inputs where 0 brings a clip decision within 1e-9 of its limit
+TORQUE_SEEDS = {"r9": 2}   # case -> seed of torque_limits where 0 leaves no path with an active torque row
+# case -> whether some path has an active torque row (its duration is above the convex call's by more than 10 gap_tol).  r3
+# and r55 have none at any seed: with the payload the static torques grow to at most 1.07 and 1.32 times the unloaded ones, the
+# limits start at 1.5 times those, and under amax <= 0.9 rad/s^2 the inertial torques are a few percent of the static ones
+# (tests/test_renumbered_robots_cpu.py asserts both).  There the limits still reach the GPU per joint: they span two
+# orders of magnitude, and one applied to another joint makes a path INFEASIBLE.
+TORQUE_ACTIVE = {"r1": True, "r9": True, "r3": False, "panda": True, "r55": False}
+# the largest difference of the rollout's restatement between its two mass-matrix orderings / between the original and the
+# renumbered description over rollout_inputs' cases (both modes, both locks), measured on the CPU; r1's comes from the list
+# that frees a parameter joint
+ROLLOUT_D_MEASURED = {"r1": (5.71e-10, 4.96e-12), "r9": (1.47e-11, 5.89e-13), "r3": (2.21e-14, 8.89e-16), "panda": (2.17e-14, 2.51e-16),
+                      "r55": (2.63e-11, 1.65e-12)}
+ROLLOUT_D = 5.71e-10
+
+
+def moving_joints(case):
+    """(ndof,) bool, original numbering: the joints some frame names that move mass.  The others (dynamics_ref.random_inertials
+    leaves a massless frame; a massless leaf's joint moves nothing) are a pivot of 0 when free: every list below locks them."""
+    import forward_ref as fr
+    from test_dynamics_cpu import mass_matrix
+    d = case.desc0
+    q = dr.in_limit_states(d, DYNAMICS_ROWS, seed=31)[0][0]
+    return fr.named_joints(d) & (np.diag(mass_matrix(d, q, d.frame_index(case.ee), None)) > 0)
+
+
+def locked_lists(case):
+    """setting -> `locked` of gto_forward_dynamics in the ORIGINAL numbering ((ndof,) int32, or None = NULL): NULL itself (an
+    explicit list where NULL would free a joint that moves no mass), the explicit list equal to the default, all but one, and
+    a seeded half of the joints."""
+    import forward_ref as fr
+    d = case.desc0
+    moving = moving_joints(case)
+    default = fr.free_joints(d) & moving
+    one = np.ones(d.ndof, dtype=bool)
+    one[np.flatnonzero(moving)[moving.sum() // 2]] = False
+    rng = np.random.default_rng(HALF_SEEDS.get(case.name, 0))
+    half = np.ones(d.ndof, dtype=bool)
+    half[rng.choice(np.flatnonzero(moving), size=max(2, moving.sum() // 2), replace=False)] = False
+    out = {"null": None if np.array_equal(default, fr.free_joints(d)) else ~default, "default": ~default, "all_but_one": one, "half": half}
+    return {k: None if v is None else v.astype(np.int32) for k, v in out.items()}
+
+
+def contiguous(joints):
+    """Whether a set of joint numbers is one run i, i + 1, ..."""
+    j = np.sort(np.asarray(joints))
+    return len(j) == 0 or int(j[-1] - j[0]) == len(j) - 1
+
+
+def forward_inputs(view):
+    """(q, qd, tau (20, ndof), payload, setting -> locked) in the view's numbering: the states and the `full` payload of
+    dynamics_inputs, seeded joint forces, and locked_lists, all drawn on the original robot."""
+    c = view.case
+    q, qd, _, pl = dynamics_inputs(view)
+    tau = np.random.default_rng(33).uniform(-15.0, 15.0, (DYNAMICS_ROWS, c.desc0.ndof))
+    return q, qd, view.new(tau, 1), pl, {k: None if v is None else view.new(v, 0) for k, v in locked_lists(c).items()}
+
+
+def rollout_locks(case):
+    """lock -> `locked` of gto_track_rollout in the ORIGINAL numbering: the default (NULL, or the explicit list where NULL
+    would free a joint that moves no mass) and `freed`, the default with the first parameter joint that moves mass freed
+    (r55 has no parameter joint: there the middle optimised joint is locked instead)."""
+    import forward_ref as fr
+    d = case.desc0
+    moving = moving_joints(case)
+    default = fr.free_joints(d) & moving
+    freed = default.copy()
+    param = [int(j) for j in d.param_index if moving[j]]
+    if param:
+        freed[param[0]] = True
+    else:
+        freed[int(d.opt_index[d.n_opt // 2])] = False
+    return {"default": None if np.array_equal(default, fr.free_joints(d)) else (~default).astype(np.int32), "freed": (~freed).astype(np.int32)}
+
+
+def rollout_inputs(view, mode="full", seed=None):
+    """dict of the arguments of gto_track_rollout in the view's numbering, built on the original robot as
+    tests/test_gpu_forward.rollout_case builds them: three smooth references from in-limit starts in which every named joint
+    moves (path 1 has duration 0), gains and limits that differ from joint to joint (a value read by position shows), the
+    model's payload not the plant's.  mode "saturating": the default-free joint with the largest static torque cannot hold
+    path 0."""
+    import dynamics_cases as dc
+    import forward_ref as fr
+    c = view.case
+    d = c.desc0
+    nd, eef = d.ndof, d.frame_index(c.ee)
+    rng = np.random.default_rng(410 + (ROLLOUT_SEEDS.get(c.name, 0) if seed is None else seed))
+    named, free = fr.named_joints(d), fr.free_joints(d) & moving_joints(c)
+    scale, settle = ROLLOUT_CLOCK[c.name]
+    dur = ROLLOUT_DURATIONS * scale
+    q0 = dr.in_limit_states(d, ROLLOUT_B, seed=42)[0]
+    amp = np.where(named, rng.uniform(0.001, 0.005, (ROLLOUT_B, nd)) * rng.choice([-1.0, 1.0], (ROLLOUT_B, nd)), 0.0)
+    T = np.maximum(dur, 1e-3)[:, None, None]
+    x = np.linspace(0.0, 1.0, ROLLOUT_M)[None, :, None]
+    s, sd, sdd = 0.5 * (1 - np.cos(np.pi * x)), 0.5 * np.pi * np.sin(np.pi * x) / T, 0.5 * np.pi ** 2 * np.cos(np.pi * x) / T ** 2
+    q = q0[:, None, :] + amp[:, None, :] * s
+    qd, qdd = amp[:, None, :] * sd, amp[:, None, :] * sdd
+    g = np.abs(np.stack([dr.inverse_dynamics(d, q0[b], 0 * q0[b], 0 * q0[b], eef) for b in range(ROLLOUT_B)]))
+    tau_max = np.where(named, (3.0 * np.maximum(g.max(axis=0), 1.0) + 20.0) * rng.uniform(1.0, 1.5, nd), np.inf)
+    if mode == "saturating":
+        j = int(np.flatnonzero(free)[np.argmax(g.max(axis=0)[free])])
+        tau_max[j] = 0.4 * g[0, j] + 1e-3
+    kp, kd = np.where(named, rng.uniform(100.0, 300.0, nd), 0.0), np.where(named, rng.uniform(5.0, 15.0, nd), 0.0)
+    return dict(duration=dur, q=view.new(q, 2), qd=view.new(qd, 2), qdd=view.new(qdd, 2), kp=view.new(kp, 0), kd=view.new(kd, 0),
+                tau_max=view.new(tau_max, 0), dt=ROLLOUT_DT, settle=settle, n_samples=ROLLOUT_MO, feedforward=2,
+                model=dc.payloads(ROLLOUT_B, seed=43)["mass"], plant=dc.payloads(ROLLOUT_B, seed=44)["full"],
+                locks={k: None if v is None else view.new(v, 0) for k, v in rollout_locks(c).items()})
+
+
+def rollout_restatement(view, a, lock, columns=False):
+    """tests/forward_ref.rollout_batch on the view's own description and inputs (a: rollout_inputs(view, ...))."""
+    import forward_ref as fr
+    return fr.rollout_batch(view.desc, view.desc.frame_index(view.ee), a["duration"], a["q"], a["qd"], a["qdd"], a["kp"], a["kd"], a["tau_max"],
+                            model_payload=a["model"], plant_payload=a["plant"], dt=a["dt"], settle=a["settle"], n_samples=a["n_samples"],
+                            feedforward=a["feedforward"], locked=a["locks"][lock], columns=columns)
+
+
+def torque_payload():
+    import dynamics_cases as dc
+    return dc.payloads(5, seed=32)["full"]
+
+
+def torque_limits(view, seed=None):
+    """tau_max (ndof,) in the view's numbering, drawn per joint on the original robot by the rule of
+    tests/test_gpu_retime_torque._other: 1.5 to 3 times the largest static torque along the paths of retime_inputs (subdiv 2),
+    +inf for a joint that carries none."""
+    import retime_torque_ref as tr
+    c = view.case
+    d = c.desc0
+    fee = d.frame_index(c.ee)
+    paths = retime_inputs(c.view("original"))[0]
+    z, top = np.zeros(d.ndof), np.zeros(d.ndof)
+    for p in paths:
+        top = np.maximum(top, np.abs(np.array([dr.inverse_dynamics(d, qi, z, z, fee) for qi in tr.path_points(p, 2)[0]])).max(axis=0))
+    rng = np.random.default_rng(520 + (TORQUE_SEEDS.get(c.name, 0) if seed is None else seed))
+    return view.new(np.where(top > 1e-9, rng.uniform(1.5, 3.0, d.ndof) * top, np.inf), 0)
+
+
 def seed_goalset_case(case, n_max=5):
     """Inputs of gto_seed_goalsets_device in the ORIGINAL numbering, as tests/small_robots.seed_goalset_case draws them for four
     instances, for the case's B: (qc, q_solutions, goals, n_goals, accept, scene ids, bases) with every row accepted in

@@ -333,6 +333,35 @@ def retime_inputs(kind, T, seed=None):
     return d, plans, rng.uniform(0.8, 1.6, d.ndof), np.full(d.ndof, 0.5)
 
 
+# kind -> seed of the link inertials (dynamics_ref.random_inertials) the torque retime runs with
+RETIME_INERTIAL_SEEDS = {"chain_1": 301, "chain_2": 302, "one_point": 303}
+# (kind, T, subdiv) -> seed of the torque limits' factors, where another than 0 is wanted
+RETIME_TORQUE_SEEDS = {}
+# (one-joint kind, T) -> whether the joint can hold plan 1, which stands still, with its payload of 1.52 kg.  chain_1 at T = 5:
+# the loaded static torque there is more than 3 times the largest unloaded one along the paths, so no factor of the rule
+# holds it and the plan is INFEASIBLE at every seed (tests/test_small_robots_cpu.py)
+RETIME_STILL_HELD = {("chain_1", 4): True, ("chain_1", 5): False, ("one_point", 4): True, ("one_point", 5): True}
+
+
+def retime_torque_inputs(kind, T, subdiv, seed=None):
+    """(desc with link inertials, end-effector frame index, plans, vmax, amax, tau_max, payload) of gto_retime_paths_torque on
+    the plans and limits of retime_inputs: the `full` payload of dynamics_cases.payloads on the kind's end effector, and
+    tau_max by the rule of tests/test_gpu_retime_torque._other, 1.5 to 3 times the largest static torque of the unloaded
+    robot along the paths at this subdivision, +inf for a joint that carries none."""
+    import dynamics_cases as dcs
+    import dynamics_ref as dr
+    import retime_torque_ref as tr
+    d, plans, vm, am = retime_inputs(kind, T)
+    dr.random_inertials(d, RETIME_INERTIAL_SEEDS[kind])
+    fee = d.frame_index(Robot(kind).ee)
+    z, top = np.zeros(d.ndof), np.zeros(d.ndof)
+    for p in plans:
+        top = np.maximum(top, np.abs(np.array([dr.inverse_dynamics(d, qi, z, z, fee) for qi in tr.path_points(p, subdiv)[0]])).max(axis=0))
+    rng = np.random.default_rng([530, T, subdiv, RETIME_TORQUE_SEEDS.get((kind, T, subdiv), 0) if seed is None else seed])
+    tm = np.where(top > 1e-9, rng.uniform(1.5, 3.0, d.ndof) * top, np.inf)
+    return d, fee, plans, vm, am, tm, dcs.payloads(RETIME_B, seed=32)["full"]
+
+
 def seed_goalset_case(case, n_max=5):
     """Inputs of gto_seed_goalsets_device on a case's robot and scene, in the order of tests/seed_cases.seed_case_wide:
     (qc, q_solutions, goals, n_goals, accept, scene ids, bases) for B instances: every row accepted, an empty mask, two

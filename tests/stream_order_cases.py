@@ -30,6 +30,7 @@ import numpy as np
 import cloud_cases as cc
 import depth_cases as dc
 import grasp_filter_cases as gf
+import dynamics_ref as dr
 from grasptrajopt_amd.robot_desc import load_builtin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,22 +51,27 @@ EFFORT, MAX_RATIO = 0.01, 0.5
 REGROW_BS = (1, 3, 65, 7, 130, 2)  # six calls of one handle behind one hold: past the four pinned slots, with regrowth
 SENTINEL = {np.dtype(np.float64): -777.25, np.dtype(np.int32): -77, np.dtype(np.uint8): 90}
 
+TRACK_M, TRACK_MO, TRACK_DT, TRACK_SETTLE = 5, 4, 2e-3, 0.004  # the rollout: durations below 16 ms, 10 steps at the most
 ENTRIES = ["solve", "ik_pose", "ik_report", "seed", "seed_multi", "plan_report", "select_plans", "check_plans_depth",
            "check_plans_cloud", "check_held_depth", "check_held_cloud", "filter_grasps", "retime_batch", "retime_paths",
-           "retime_paths_convex", "retrieve_lift", "retrieve_reverse", "solve_base", "base_report"]
+           "retime_paths_convex", "retime_paths_torque", "track_rollout", "retrieve_lift", "retrieve_reverse", "solve_base", "base_report"]
 # the entry points whose header text says that they enqueue "without a host synchronisation" (the retime calls after a
-# first call of the handle): all but gto_solve_batch_device, which throttles on the GPU's progress
+# first call of the handle: "stream order with no synchronisation after a handle's first retime call", which the torque call
+# takes over from the convex one; the rollout: "no allocation and no synchronisation at all"): all but gto_solve_batch_device,
+# which throttles on the GPU's progress
 NO_HOST_SYNC = [e for e in ENTRIES if e != "solve"]
 HORIZON = {"retrieve_reverse": T_REVERSE}  # (every other entry: T)
 # the runs of six calls of one handle behind one hold (REGROW_BS): the entries of each run's calls, per B
-# ("retime": the greedy and the convex call alternate on the workspace they share, rt_S ... rt_stat, which every larger B regrows)
+# ("retime": the greedy, the convex and the torque call take turns on the workspace they share, rt_S ... rt_stat, which every
+# larger B regrows; the torque call regrows rt_TA, rt_TB and rt_TG on top)
 REGROW_RUNS = {"base": ("solve_base", "base_report"), "check_paths": ("check_paths_depth",), "check_held": ("check_held_cloud",),
-               "filter_grasps": ("filter_grasps",), "retime": ("retime_paths", "retime_paths_convex")}
+               "filter_grasps": ("filter_grasps",), "retime": ("retime_paths", "retime_paths_convex", "retime_paths_torque")}
 
 
 def robot():
+    """Panda with the link inertials of tests/golden (the torque retime and the rollout need them; no other entry reads them)."""
     with open(os.path.join(ROOT, "grasptrajopt_amd", "data", f"{ROBOT}_cfg.json")) as fh:
-        return load_builtin(ROBOT), json.load(fh)
+        return dr.with_fixture_inertials(load_builtin(ROBOT), ROBOT), json.load(fh)
 
 
 def scenes():
@@ -142,6 +148,25 @@ def _limits(desc, rng):
     return dict(vmax=rng.uniform(1.0, 2.5, desc.ndof), amax=rng.uniform(2.0, 6.0, desc.ndof))
 
 
+def _payload(rng, B, prefix):
+    """A rigid body per path: mass, centre of mass, inertia (positive definite) as ixx ixy ixz iyy iyz izz."""
+    A = rng.uniform(-0.08, 0.08, (B, 3, 3))
+    I = A @ A.transpose(0, 2, 1) + 1e-4 * np.eye(3)
+    six = np.stack([I[:, 0, 0], I[:, 0, 1], I[:, 0, 2], I[:, 1, 1], I[:, 1, 2], I[:, 2, 2]], axis=1)
+    return {prefix + "mass": rng.uniform(0.2, 1.5, B), prefix + "com": rng.uniform(-0.05, 0.05, (B, 3)), prefix + "inertia": six}
+
+
+def _references(desc, rng, B):
+    """duration (B,) and q_ref, qd_ref, qdd_ref (B, TRACK_M, ndof) of the rollout: a small smooth move from a configuration well
+    inside the limits, with seeded velocities and accelerations beside it (a valid reference, not a consistent one)."""
+    lo, hi = desc.lower, desc.upper
+    q0 = lo + (hi - lo) * rng.uniform(0.25, 0.75, (B, desc.ndof))
+    amp = np.minimum(0.01, 0.2 * (hi - lo)) * rng.uniform(-1.0, 1.0, (B, desc.ndof))
+    x = np.linspace(0.0, 1.0, TRACK_M)
+    q = q0[:, None, :] + amp[:, None, :] * (0.5 * (1 - np.cos(np.pi * x)))[None, :, None]
+    return dict(duration=rng.uniform(0.004, 0.016, B), q_ref=q, qd_ref=rng.uniform(-0.3, 0.3, q.shape), qdd_ref=rng.uniform(-2.0, 2.0, q.shape))
+
+
 def _closed(desc, rng):
     return dict(closed_joints=rng.permutation(desc.param_index).astype(np.int32), closed_values=rng.uniform(0.0, 0.04, len(desc.param_index)))
 
@@ -207,6 +232,17 @@ def _draw(entry, B, Tp, rng):
         outs = _retime_outs(desc, B, Tp)
         if entry == "retime_paths_convex":
             outs["iters"] = ((B,), i32)
+    elif entry == "retime_paths_torque":  # limits above the Panda's own: every path can be held, with its payload
+        dev = dict(paths=_plans(desc, rng, B, Tp), n_cols=_counts(rng, B, 3, Tp), **_payload(rng, B, "payload_"))
+        host = dict(**_limits(desc, rng), tau_max=desc.effort * rng.uniform(1.2, 2.0, nd))
+        outs = dict(_retime_outs(desc, B, Tp), tau=((B, M_SAMPLES, nd), f), iters=((B,), i32))
+    elif entry == "track_rollout":  # the arm's limits around what holding takes: some periods clip, some do not
+        dev = dict(**_references(desc, rng, B), model_mass=rng.uniform(0.2, 1.5, B), **_payload(rng, B, "plant_"))
+        locked = np.isin(np.arange(nd), desc.param_index).astype(i32)  # the fingers, and one joint of the arm
+        locked[desc.opt_index[rng.integers(0, desc.n_opt)]] = 1
+        host = dict(kp=rng.uniform(100.0, 300.0, nd), kd=rng.uniform(5.0, 15.0, nd), tau_max=rng.uniform(8.0, 40.0, nd), locked=locked)
+        outs = dict(q=((B, TRACK_MO, nd), f), qd=((B, TRACK_MO, nd), f), t=((B, TRACK_MO), f), err_max=((B,), f), err_end=((B,), f),
+                    sat_steps=((B,), i32), steps=((B,), i32), status=((B,), i32))
     elif entry == "retrieve_lift":
         d = cc._unit(rng.normal(size=(1, 3)))[0]
         dev = dict(plans=_plans(desc, rng, B, Tp), scene_id=_counts(rng, B, 0, 1), base_pos=_bases(rng, B))
@@ -280,7 +316,7 @@ def valid(case):
             bad.append(f"{name}: outside [1, {hi}]")
     if "scene_id" in arrays and not np.isin(arrays["scene_id"], np.arange(len(SCENE_SEEDS))).all():
         bad.append("scene_id: a scene that does not exist")
-    for name in ("qc", "q0", "q", "q_solutions", "Q0", "Q", "plans", "paths"):
+    for name in ("qc", "q0", "q", "q_solutions", "q_ref", "Q0", "Q", "plans", "paths"):
         if name in arrays:
             a = arrays[name]
             q = np.moveaxis(a, -2, -1) if name in ("Q0", "Q", "plans", "paths") else a  # joints last
@@ -292,9 +328,21 @@ def valid(case):
             bad.append("closed_joints: not distinct joints of the robot")
     if "obs" in arrays and not np.isin(arrays["obs"], (0, 1)).all():
         bad.append("obs: an unknown kind")
-    for name in ("vmax", "amax"):
+    for name in ("vmax", "amax", "tau_max"):
         if name in arrays and not (arrays[name] > 0).all():
             bad.append(f"{name}: not positive")
+    for name in ("kp", "kd", "duration", "payload_mass", "model_mass", "plant_mass"):
+        if name in arrays and not (arrays[name] >= 0).all():
+            bad.append(f"{name}: negative")
+    for name in ("payload_inertia", "plant_inertia"):
+        if name in arrays:
+            I = arrays[name][:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, 3, 3)
+            if not (np.linalg.eigvalsh(I) > 0).all():
+                bad.append(f"{name}: not positive definite")
+    if "locked" in arrays and not (np.isin(arrays["locked"], (0, 1)).all() and (arrays["locked"] == 0).any()):
+        bad.append("locked: not flags, or no free joint")
+    if "duration" in arrays and not np.ceil((arrays["duration"].max() + TRACK_SETTLE) / TRACK_DT) <= 10:
+        bad.append("duration: more than 10 steps")
     for name in ("goals", "object_pose", "grasps", "standoff", "check_offset", "ik_offset"):
         if name in arrays:
             M = arrays[name].reshape(-1, 4, 4)
@@ -367,6 +415,16 @@ def enqueue(rig, entry, case, d, hst, o, stream):
         rc = lib.gto_retime_paths_convex_device(h, B, Tp, D("paths"), D("n_cols"), _hp(hst["vmax"], _pd), _hp(hst["amax"], _pd), SUBDIV,
                                                 M_SAMPLES, CONVEX_GAP_TOL, CONVEX_MAX_NEWTON, O("duration"), O("t_grid"), O("sd_grid"), O("q"),
                                                 O("qd"), O("qdd"), O("status"), O("iters"), st)
+    elif entry == "retime_paths_torque":
+        rc = lib.gto_retime_paths_torque_device(h, B, Tp, D("paths"), D("n_cols"), _hp(hst["vmax"], _pd), _hp(hst["amax"], _pd),
+                                                _hp(hst["tau_max"], _pd), D("payload_mass"), D("payload_com"), D("payload_inertia"), SUBDIV,
+                                                M_SAMPLES, CONVEX_GAP_TOL, CONVEX_MAX_NEWTON, O("duration"), O("t_grid"), O("sd_grid"), O("q"),
+                                                O("qd"), O("qdd"), O("tau"), O("status"), O("iters"), st)
+    elif entry == "track_rollout":
+        rc = lib.gto_track_rollout_device(h, B, TRACK_M, D("duration"), D("q_ref"), D("qd_ref"), D("qdd_ref"), _hp(hst["kp"], _pd),
+                                          _hp(hst["kd"], _pd), _hp(hst["tau_max"], _pd), TRACK_DT, TRACK_SETTLE, 2, D("model_mass"), None, None,
+                                          D("plant_mass"), D("plant_com"), D("plant_inertia"), _hp(hst["locked"], _pi), TRACK_MO, O("q"),
+                                          O("qd"), O("t"), O("err_max"), O("err_end"), O("sat_steps"), O("steps"), O("status"), st)
     elif entry == "retrieve_lift":
         cj, cv = hst["closed_joints"], hst["closed_values"]
         rc = lib.gto_retrieve_lift_device(h, B, D("plans"), D("scene_id"), D("base_pos"), _hp(hst["direction"], _pd), LIFT_DISTANCE, LIFT_K,

@@ -173,6 +173,69 @@ def test_reference_interpolation():
     assert np.array_equal(a, q[-1]) and not b.any()
 
 
+def test_the_rollout_cases_cover_the_workgroup_layouts():
+    """tests/test_gpu_forward.py's restatement of track_group_lanes / track_paths_per_block against the header's own functions
+    would need the GPU library; here: the formula on the robots the GPU test names, and what the smallest ones are there for."""
+    import test_gpu_forward as tg
+    assert tg.track_layout(1, 1) == (16, 4) and tg.track_layout(32, 31) == (8, 1) and tg.track_layout(12, 9) == (16, 2)
+    # one path at G lanes: (15 F G + ndof^2 + 15 ndof) 8 + 16 bytes of the 63488 a workgroup has
+    assert (15 * 32 * 16 + 31 * 31 + 15 * 31) * 8 + 16 > 63488 >= (15 * 32 * 8 + 31 * 31 + 15 * 31) * 8 + 16
+    tg.test_the_rollout_robots_cover_the_layouts()
+    four = [n for n, lay in tg.ROLLOUT_LAYOUTS.items() if lay == (16, 4)]
+    assert sorted(four) == ["chain_1", "ee_above_joints", "prismatic_only", "root_joint"]
+    assert tg.B == 5 and -(-tg.B // 4) == 2 and tg.B % 4 == 1  # a full workgroup of four paths and one with a single valid group
+    steps = np.ceil((tg.DURATIONS + 0.01) / tg.DT)
+    assert len(set(steps.tolist())) == 5  # five different step counts share the barriers
+
+
+@pytest.mark.parametrize("name", ["chain_1", "panda"])
+def test_locked_joints_in_the_restatement(name):
+    """The `locked` rules of include/gto_solver.h as tests/forward_ref.py states them, on the cases of
+    tests/test_gpu_forward.test_rollout_with_locked_joints: a locked joint stands at its first reference position whatever its
+    reference does later (a NaN there included), only a NaN in that first position fails the path, and with every joint locked
+    nothing moves and nothing is in error."""
+    import test_gpu_forward as tg
+    c = tg.locked_case(name)
+    res = {}
+    for setting in ("all", "moving_nan", "first_nan"):
+        lk, q, qd, qdd = tg.locked_inputs(c, setting)
+        res[setting] = w = tg.locked_restatement(c, lk, q, qd, qdd)
+        free = fr.free_joints(c["desc"], lk)
+        good = w["status"] == 0
+        assert good.tolist() == [True, setting != "first_nan", True, True, True] and w["steps"][good].max() <= tg.LOCKED_MAX_STEPS[name]
+        assert np.array_equal(w["q"][good][:, :, ~free], np.broadcast_to(q[good][:, :1, ~free], w["q"][good][:, :, ~free].shape))
+        assert not w["qd"][good][:, :, ~free].any() and w["clip_margin"].min() > 1e-9
+    assert not res["all"]["err_max"].any() and not res["all"]["sat_steps"].any() and (res["all"]["steps"] > 0).all()
+    lk, q, qd, qdd = tg.locked_inputs(c, "moving_nan")
+    j = c["jl"]
+    assert np.isnan(q[:, :, j]).any() and np.isnan(qd[:, :, j]).any() and np.isnan(qdd[:, :, j]).any() and np.isfinite(q[:, 0, j]).all()
+    fq, fqd, fqdd = c["q"].copy(), c["qd"].copy(), c["qdd"].copy()
+    fq[:, :, j], fqd[:, :, j], fqdd[:, :, j] = fq[:, :1, j], 0.0, 0.0
+    flat = tg.locked_restatement(c, lk, fq, fqd, fqdd)
+    for k in ("q", "qd", "t", "err_max", "err_end", "sat_steps", "steps", "status"):
+        assert np.array_equal(res["moving_nan"][k], flat[k]), k
+    clean = tg.locked_restatement(c, lk, c["q"], c["qd"], c["qdd"])
+    keep = np.arange(tg.B) != 1
+    for k in ("q", "qd", "err_max", "sat_steps"):
+        assert np.array_equal(res["first_nan"][k][keep], clean[k][keep]), k
+
+
+def test_the_clock_edges_in_the_restatement():
+    """ceil((duration + settle) / dt) of tests/test_gpu_forward.test_the_clock_edges is exact at dt = 2^-9: 8 periods exactly,
+    none at all, and GTO_TRACK_MAX_STEPS + 1 of them."""
+    import test_gpu_forward as tg
+    c = tg.clock_case()
+    assert tg.MAX_STEPS == fr.MAX_STEPS and np.ceil(c["dur"] / tg.CLOCK_DT).tolist() == [8, 4, 6, 10] and c["dur"][0] / tg.CLOCK_DT == 8.0
+    edge = c["dur"].copy()
+    edge[1], edge[3] = 0.0, (tg.MAX_STEPS + 0.5) * tg.CLOCK_DT
+    assert np.ceil(edge[3] / tg.CLOCK_DT) == tg.MAX_STEPS + 1
+    w = tg.clock_restatement(c, edge)
+    assert w["status"].tolist() == [0, 2, 0, 2] and w["steps"].tolist() == [8, 0, 6, 0] and np.isnan(w["q"][[1, 3]]).all()
+    just = tg.clock_restatement(dict(c, q=c["q"][:1], qd=c["qd"][:1], qdd=c["qdd"][:1], model=tuple(a if a is None else a[:1] for a in c["model"]),
+                                     plant=tuple(a if a is None else a[:1] for a in c["plant"])), np.array([0.0]))
+    assert just["status"].tolist() == [2]
+
+
 def test_exported_symbols_and_bindings():
     from grasptrajopt_amd import _capi, utils
     from grasptrajopt_amd.grasp_chain import GraspChain

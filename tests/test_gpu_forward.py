@@ -7,15 +7,20 @@ workgroup holds fd_rows(F, ndof) = min(64, 63488 // ((15 F + ndof^2 + 7 ndof) 8 
 only, full; locked NULL, none, all but one, all.  Where `locked` leaves a joint free that moves no mass (the seeded robots
 have a massless frame each) the case locks that joint too; the massless free joint has a test of its own.
 
-Rollout: Panda, Fetch, prismatic_chain and limit_chain (32 frames, 16 free joints under locked = NULL: 18 passes in three
-rounds of the 8 lanes a path gets there), B = 5, M = 9, Mo = 7, dt = 2 ms, at most 30 steps (5 on limit_chain, whose numpy
+Rollout: Panda, Fetch, prismatic_chain, limit_chain (32 frames, 16 free joints under locked = NULL: 18 passes in three
+rounds of the 8 lanes a path gets there) and four of the smallest robots (root_joint, chain_1, prismatic_only,
+ee_above_joints: four paths of 16 lanes share a workgroup there, ROLLOUT_LAYOUTS), B = 5, M = 9, Mo = 7, dt = 2 ms, at most 30 steps (5 on limit_chain, whose numpy
 restatement takes a quarter of a second per step), every feedforward mode, the plant's payload not the model's, one case that saturates.
 Tolerance of q_out, qd_out, err_max, err_end: 16 d, d the largest difference between the restatement run with its two
 mass-matrix orderings (Jacobian sum / unit-acceleration columns) over these very cases, measured on the CPU with
 forward_ref.rollout_batch(columns=False) against (columns=True); the GPU's frame-local arithmetic is a third ordering of the
 same sums, and the factor covers its contraction into FMAs.  Measured, the largest over the four modes of each robot:
     panda 4.33e-15   fetch 5.67e-12   prismatic_chain 1.57e-12   limit_chain 1.44e-11
-so d = ROLLOUT_D = 1.44e-11 (the seeded bodies of the generated robots make worse-conditioned mass matrices than Panda's).
+    root_joint 6.61e-15   chain_1 6.16e-14   prismatic_only 4.72e-16   ee_above_joints 3.49e-11
+so d = ROLLOUT_D = 3.49e-11 (the seeded bodies of the generated robots make worse-conditioned mass matrices than Panda's).
+The clock's edges (Panda, dt = 2^-9 s): 3.72e-15, under ROLLOUT_D.  The locked settings have a d per robot, LOCKED_D, measured
+the same way over the five settings: panda 5.60e-13, chain_1 8.78e-15, limit_chain 6.10e-10 (all 31 joints free under a
+reference that asks for 1000 rad/s^2: every step saturates and err_max reaches 0.34 rad in three steps).
 The same for the energy drifts of the free fall at h = 0.02 and 0.01: 2.84e-14 and 1.42e-14, ENERGY_D = 2.84e-14 (one unit
 of round-off of an energy of 103 J is 2.3e-14).
 No case's own | |tau| - tau_max | comes within 1e-9 relative of a clip decision: the smallest margin over all of them is
@@ -36,8 +41,12 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 67
-ROLLOUT_ROBOTS = ("panda", "fetch", "prismatic_chain", "limit_chain")
-ROLLOUT_D = 1.44e-11
+ROLLOUT_ROBOTS = ("panda", "fetch", "prismatic_chain", "limit_chain", "root_joint", "chain_1", "prismatic_only", "ee_above_joints")
+LOCKED_ROBOTS = ("panda", "chain_1", "limit_chain")
+# (G lanes per path, P paths per workgroup) of k_track_rollout, as track_layout restates them
+ROLLOUT_LAYOUTS = {"panda": (16, 2), "fetch": (16, 2), "prismatic_chain": (16, 3), "limit_chain": (8, 1), "root_joint": (16, 4),
+                   "chain_1": (16, 4), "prismatic_only": (16, 4), "ee_above_joints": (16, 4)}
+ROLLOUT_D = 3.49e-11
 ENERGY_D = 2.84e-14
 B, M, MO, DT = 5, 9, 7, 2e-3
 
@@ -55,6 +64,17 @@ def same(a, b):
 def fd_rows(F, ndof):
     """fd_rows_per_block of csrc/gto_forward.h, restated from its constants."""
     return min(64, (64 * 1024 - 2048) // ((15 * F + ndof * ndof + 7 * ndof) * 8 + 4))
+
+
+def track_layout(F, ndof):
+    """(G, P) of k_track_rollout: track_group_lanes and track_paths_per_block of csrc/gto_forward.h, restated from its
+    constants (15 rt_rnea slots per frame and lane, 15 work vectors and four ints per path, 64 KB less 2048 bytes)."""
+    room = 64 * 1024 - 2048
+    path = lambda G: (15 * F * G + ndof * ndof + 15 * ndof) * 8 + 16  # noqa: E731
+    G = 16
+    while G > 1 and path(G) > room:
+        G //= 2
+    return G, min(room // path(G), 64 // G)
 
 
 def as_dict(pl, rows=slice(None)):
@@ -263,18 +283,20 @@ def test_utils_forward_dynamics_is_the_abi_call(name, capi):
 # durations of the five paths as multiples of the robot's longest (30 steps of 2 ms with the settle time); the fourth path
 # carries a NaN
 DURATIONS = np.array([0.05, 0.024, 0.0, 0.03, 0.013])
-SCALE = {"panda": 1.0, "fetch": 1.0, "prismatic_chain": 1.0, "limit_chain": 0.1}
-SETTLE = {"panda": 0.01, "fetch": 0.01, "prismatic_chain": 0.01, "limit_chain": 0.004}  # 5 steps, 2 on the slow one
+SCALE = {"limit_chain": 0.1}
+SETTLE = {"limit_chain": 0.004}  # 5 steps; 2 on the slow one
 MODES = ("none", "gravity", "full", "saturating")
 
 
-def rollout_case(name):
-    """The inputs of the rollout cases of one robot: seeded smooth references from an in-limit start, gains, limits, payloads."""
+def rollout_case(name, free=None, scale=None):
+    """The inputs of the rollout cases of one robot: seeded smooth references from an in-limit start, gains, limits, payloads.
+    free: the joints that move and are controlled (None: the ones locked = NULL leaves free); scale: of DURATIONS (None:
+    the robot's SCALE)."""
     desc, ee, gr, ngp = dc.robot(name)
     rng = np.random.default_rng(41)
-    free = fr.free_joints(desc)
+    free = fr.free_joints(desc) if free is None else free
     q0, _, _ = dr.in_limit_states(desc, B, seed=42)
-    dur = DURATIONS * SCALE[name]
+    dur = DURATIONS * (SCALE.get(name, 1.0) if scale is None else scale)
     amp = np.where(free, rng.uniform(-0.005, 0.005, (B, desc.ndof)), 0.0)
     T = np.maximum(dur, 1e-3)[:, None, None]
     x = np.linspace(0.0, 1.0, M)[None, :, None]
@@ -291,7 +313,7 @@ def rollout_case(name):
     model = dc.payloads(B, seed=43)["mass"]
     plant = dc.payloads(B, seed=44)["full"]
     return dict(desc=desc, ee=ee, eef=eef, gr=gr, ngp=ngp, dur=dur, q=q, qd=qd, qdd=qdd, kp=kp, kd=kd, tau_max=tau_max, weak=weak,
-                model=model, plant=plant, free=free, settle=SETTLE[name])
+                model=model, plant=plant, free=free, settle=SETTLE.get(name, 0.01))
 
 
 def mode_args(c, mode):
@@ -318,6 +340,17 @@ def roll(request, capi):
     c["h"] = capi.SolverHandle(c["desc"], c["ee"], c["gr"], device=0, n_gripper_points=c["ngp"])
     yield c
     c["h"].close()
+
+
+def test_the_rollout_robots_cover_the_layouts():
+    """The three workgroup layouts of k_track_rollout: four paths of 16 lanes (all 64 lanes busy, the five paths fill one
+    workgroup and leave a second with one valid group of four), two or three paths, and one path of 8 lanes."""
+    layouts = {name: track_layout(dc.robot(name)[0].n_frames, dc.robot(name)[0].ndof) for name in ROLLOUT_ROBOTS}
+    assert layouts == ROLLOUT_LAYOUTS
+    seen = set(layouts.values())
+    assert (16, 4) in seen and seen & {(16, 2), (16, 3)} and (8, 1) in seen
+    assert all(layouts[name] == (16, 4) for name in ("root_joint", "chain_1", "prismatic_only", "ee_above_joints"))
+    assert {layouts[name] for name in LOCKED_ROBOTS} == {(16, 2), (16, 4), (8, 1)}
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -388,20 +421,22 @@ def test_a_path_is_the_same_in_any_batch(roll):
     assert same(other["q"][:, -1], five["q"][:, -1]) and same(other["q"][:, 0], c["q"][:, 0])
 
 
-def device_rollout(h, c, mode, tensors, stream):
+def device_rollout(h, c, mode, tensors, stream, dt=DT, settle=None, locked=None):
     import torch
     a = mode_args(c, mode)
-    out = dict(q=torch.full((B, MO, c["desc"].ndof), 7.0, dtype=torch.float64, device="cuda:0"),
-               qd=torch.full((B, MO, c["desc"].ndof), 7.0, dtype=torch.float64, device="cuda:0"),
-               t=torch.full((B, MO), 7.0, dtype=torch.float64, device="cuda:0"),
-               err_max=torch.full((B,), 7.0, dtype=torch.float64, device="cuda:0"),
-               err_end=torch.full((B,), 7.0, dtype=torch.float64, device="cuda:0"),
-               sat_steps=torch.full((B,), 7, dtype=torch.int32, device="cuda:0"), steps=torch.full((B,), 7, dtype=torch.int32, device="cuda:0"),
-               status=torch.full((B,), 7, dtype=torch.int32, device="cuda:0"))
+    nb = tensors["dur"].shape[0]
+    out = dict(q=torch.full((nb, MO, c["desc"].ndof), 7.0, dtype=torch.float64, device="cuda:0"),
+               qd=torch.full((nb, MO, c["desc"].ndof), 7.0, dtype=torch.float64, device="cuda:0"),
+               t=torch.full((nb, MO), 7.0, dtype=torch.float64, device="cuda:0"),
+               err_max=torch.full((nb,), 7.0, dtype=torch.float64, device="cuda:0"),
+               err_end=torch.full((nb,), 7.0, dtype=torch.float64, device="cuda:0"),
+               sat_steps=torch.full((nb,), 7, dtype=torch.int32, device="cuda:0"), steps=torch.full((nb,), 7, dtype=torch.int32, device="cuda:0"),
+               status=torch.full((nb,), 7, dtype=torch.int32, device="cuda:0"))
     ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
-    h.track_rollout_device(B, M, ptr(tensors["dur"]), ptr(tensors["q"]), ptr(tensors["qd"]), ptr(tensors["qdd"]), c["kp"], c["kd"],
-                           tau_max=a["tau_max"], dt=DT, settle=c["settle"], n_samples=MO, feedforward=a["feedforward"],
-                           model_payload=[ptr(x) for x in tensors["model"]], plant_payload=[ptr(x) for x in tensors["plant"]],
+    h.track_rollout_device(nb, M, ptr(tensors["dur"]), ptr(tensors["q"]), ptr(tensors["qd"]), ptr(tensors["qdd"]), c["kp"], c["kd"],
+                           tau_max=a["tau_max"], dt=dt, settle=c["settle"] if settle is None else settle, n_samples=MO,
+                           feedforward=a["feedforward"], model_payload=[ptr(x) for x in tensors["model"]],
+                           plant_payload=[ptr(x) for x in tensors["plant"]], locked=locked,
                            q_out=ptr(out["q"]), qd_out=ptr(out["qd"]), t_out=ptr(out["t"]), err_max=ptr(out["err_max"]),
                            err_end=ptr(out["err_end"]), sat_steps=ptr(out["sat_steps"]), steps=ptr(out["steps"]),
                            status_out=ptr(out["status"]), stream=stream.cuda_stream)
@@ -448,6 +483,186 @@ def test_device_variant_equals_the_host_variant_and_keeps_stream_order(roll):
         for k in want:
             assert same(out2[k].cpu().numpy(), want[k]), k
         assert returned_while_held  # no synchronisation inside the call
+
+
+# ------------------------------------------------------------------------------------------------ locked joints
+LOCKED_SETTINGS = ("none", "all_but_one", "all", "moving_nan", "first_nan")
+# (scale of DURATIONS, settle time): at most 8 steps on Panda, whose restatement with nine free joints takes 80 ms per step,
+# and at most 3 on limit_chain, where 31 joints are free (33 passes over 8 lanes)
+LOCKED_CLOCK = {"panda": (0.2, 0.004), "chain_1": (1.0, 0.01), "limit_chain": (0.1, 0.0009)}
+LOCKED_MAX_STEPS = {"panda": 8, "chain_1": 30, "limit_chain": 3}
+# d of these cases, measured as ROLLOUT_D is (the largest over the five settings of a robot; the head of the file)
+LOCKED_D = {"panda": 5.60e-13, "chain_1": 8.78e-15, "limit_chain": 6.10e-10}
+
+
+def locked_case(name):
+    """rollout_case with every named joint moving in the reference and under control, gains and limits that differ from
+    joint to joint, and what the `locked` settings need: moving (the joints that move mass at the start state), jl (a
+    joint locked = NULL leaves free, the middle one of them: the settings moving_nan and first_nan lock it too)."""
+    desc = dc.robot(name)[0]
+    named = fr.named_joints(desc)
+    c = rollout_case(name, free=named, scale=LOCKED_CLOCK[name][0])
+    c["settle"] = LOCKED_CLOCK[name][1]
+    rng = np.random.default_rng(45)
+    c["kp"], c["kd"] = np.where(named, rng.uniform(100.0, 300.0, desc.ndof), 0.0), np.where(named, rng.uniform(5.0, 15.0, desc.ndof), 0.0)
+    c["tau_max"] = c["tau_max"] * rng.uniform(1.0, 1.5, desc.ndof)
+    c["moving"] = named & (np.diag(mass_matrix(desc, c["q"][0, 0], c["eef"], None)) > 0)
+    default = np.flatnonzero(fr.free_joints(desc))
+    c["jl"] = int(default[len(default) // 2])
+    return c
+
+
+def locked_inputs(c, setting):
+    """(locked (ndof,) int32, q, qd, qdd) of a setting."""
+    nd = c["desc"].ndof
+    q, qd, qdd = c["q"].copy(), c["qd"].copy(), c["qdd"].copy()
+    if setting == "none":  # massless joints excepted: freed, they are a pivot of 0
+        lk = ~c["moving"]
+    elif setting == "all_but_one":
+        lk = np.ones(nd, dtype=bool)
+        lk[np.flatnonzero(c["moving"])[c["moving"].sum() // 2]] = False
+    elif setting == "all":
+        lk = np.ones(nd, dtype=bool)
+    else:
+        lk = ~fr.free_joints(c["desc"])
+        j = c["jl"]
+        lk[j] = True
+        assert (np.abs(q[:, -1, j] - q[:, 0, j]) > 1e-4).all()  # its reference moves, on the path of duration 0 too
+        if setting == "moving_nan":  # whatever the reference says about a locked joint past its first position is ignored
+            q[0, 1, j] = qd[0, 0, j] = qdd[0, M - 1, j] = q[1, M - 1, j] = qd[4, M // 2, j] = np.nan
+        else:
+            q[1, 0, j] = np.nan
+    return lk.astype(np.int32), q, qd, qdd
+
+
+@pytest.fixture(scope="module", params=LOCKED_ROBOTS)
+def lock(request, capi):
+    c = locked_case(request.param)
+    c["name"] = request.param
+    c["h"] = capi.SolverHandle(c["desc"], c["ee"], c["gr"], device=0, n_gripper_points=c["ngp"])
+    yield c
+    c["h"].close()
+
+
+def locked_rollout(h, c, lk, q, qd, qdd):
+    return h.track_rollout(c["dur"], q, qd, qdd, c["kp"], c["kd"], tau_max=c["tau_max"], dt=DT, settle=c["settle"], n_samples=MO,
+                           feedforward=2, model_payload=as_dict(c["model"]), plant_payload=as_dict(c["plant"]), locked=lk)
+
+
+def locked_restatement(c, lk, q, qd, qdd, **kw):
+    return fr.rollout_batch(c["desc"], c["eef"], c["dur"], q, qd, qdd, c["kp"], c["kd"], c["tau_max"], dt=DT, settle=c["settle"],
+                            n_samples=MO, feedforward=2, model_payload=c["model"], plant_payload=c["plant"], locked=lk, **kw)
+
+
+@pytest.mark.parametrize("setting", LOCKED_SETTINGS)
+def test_rollout_with_locked_joints(lock, setting):
+    """The rollout's `locked` argument with other lists than the default, each against forward_ref.rollout_batch(locked=...)
+    at 16 d, d = LOCKED_D of the robot."""
+    c, h = lock, lock["h"]
+    tol = 16 * LOCKED_D[c["name"]]
+    lk, q, qd, qdd = locked_inputs(c, setting)
+    free = fr.free_joints(c["desc"], lk)
+    want = locked_restatement(c, lk, q, qd, qdd)
+    got = locked_rollout(h, c, lk, q, qd, qdd)
+    bad = np.zeros(B, dtype=bool)
+    bad[1] = setting == "first_nan"
+    assert want["clip_margin"].min() > 1e-9
+    assert np.array_equal(want["status"], np.where(bad, 2, 0)) and np.array_equal(got["status"], want["status"])
+    assert np.array_equal(got["steps"], want["steps"]) and np.array_equal(got["sat_steps"], want["sat_steps"])
+    assert got["steps"].max() <= LOCKED_MAX_STEPS[c["name"]] and same(got["t"], want["t"])
+    err = {k: np.abs(got[k][~bad] - want[k][~bad]).max() for k in ("q", "qd", "err_max", "err_end")}
+    print(f"{c['name']} locked {setting}: {int(free.sum())} free, steps {got['steps'].tolist()} differences {err}, allowed {tol:.2e}")
+    for k in ("q", "qd", "t", "err_max", "err_end"):
+        assert np.isnan(got[k][bad]).all() and np.isfinite(got[k][~bad]).all()
+    assert max(err.values()) <= tol
+    # a locked joint stands at its first position with no velocity, whatever its reference does
+    assert same(got["q"][~bad][:, :, ~free], np.broadcast_to(q[~bad][:, :1, ~free], got["q"][~bad][:, :, ~free].shape))
+    assert not got["qd"][~bad][:, :, ~free].any()
+    if setting == "none":
+        assert free.sum() == c["moving"].sum() and (c["name"] != "limit_chain" or free.sum() == 31)
+    if setting == "all":
+        assert not free.any() and same(got["q"], np.broadcast_to(q[:, :1], got["q"].shape)) and not got["qd"].any()
+        assert not got["err_max"].any() and not got["err_end"].any() and not got["sat_steps"].any() and (got["steps"] > 0).all()
+    if setting == "moving_nan":  # bit for bit the run with that joint's reference flattened
+        j = c["jl"]
+        fq, fqd, fqdd = c["q"].copy(), c["qd"].copy(), c["qdd"].copy()
+        fq[:, :, j], fqd[:, :, j], fqdd[:, :, j] = fq[:, :1, j], 0.0, 0.0
+        flat = locked_rollout(h, c, lk, fq, fqd, fqdd)
+        for k in got:
+            assert same(got[k], flat[k]), k
+    if setting == "first_nan":  # the neighbours are what they are without it
+        clean = locked_rollout(h, c, lk, c["q"], c["qd"], c["qdd"])
+        assert (clean["status"] == 0).all()
+        for k in got:
+            assert same(got[k][~bad], clean[k][~bad]), k
+
+
+# ------------------------------------------------------------------------------------------------ the clock's edges
+MAX_STEPS = 1 << 20  # GTO_TRACK_MAX_STEPS
+CLOCK_DT = 2.0 ** -9  # a power of two: (duration + settle) / dt below is exact
+# the clean durations of the four paths in periods: 8 exactly; the others end inside a period
+CLOCK_PERIODS = np.array([8.0, 3.3, 5.3, 9.5])
+
+
+def clock_case():
+    c = rollout_case("panda")
+    nb = len(CLOCK_PERIODS)
+    return dict(c, dur=CLOCK_PERIODS * CLOCK_DT, q=c["q"][:nb], qd=c["qd"][:nb], qdd=c["qdd"][:nb], settle=0.0,
+                model=tuple(None if a is None else a[:nb] for a in c["model"]), plant=tuple(None if a is None else a[:nb] for a in c["plant"]))
+
+
+def clock_restatement(c, dur, **kw):
+    return fr.rollout_batch(c["desc"], c["eef"], dur, c["q"], c["qd"], c["qdd"], c["kp"], c["kd"], c["tau_max"], dt=CLOCK_DT, settle=0.0,
+                            n_samples=MO, feedforward=2, model_payload=c["model"], plant_payload=c["plant"], **kw)
+
+
+def test_the_clock_edges(capi):
+    """Through gto_track_rollout_device, where the device alone sees the durations and the payload masses: a path with no
+    period at all, one with GTO_TRACK_MAX_STEPS + 1 of them (it must fail at once: a workgroup walks to the largest step
+    count of its GOOD paths), payload masses of -1 and NaN, and beside them a path of exactly 8 periods."""
+    import torch
+    c = clock_case()
+    h = capi.SolverHandle(c["desc"], c["ee"], c["gr"], device=0, n_gripper_points=c["ngp"])
+    stream = torch.cuda.Stream(device="cuda:0")
+    assert (8 * CLOCK_DT) / CLOCK_DT == 8.0 and np.ceil((MAX_STEPS + 0.5) * CLOCK_DT / CLOCK_DT) == MAX_STEPS + 1
+
+    def run(dur=None, model_mass=None, plant_mass=None):
+        cc = dict(c, dur=c["dur"] if dur is None else dur)
+        if model_mass is not None:
+            cc["model"] = (model_mass,) + tuple(c["model"][1:])
+        if plant_mass is not None:
+            cc["plant"] = (plant_mass,) + tuple(c["plant"][1:])
+        tensors = to_device(cc, cc["q"])
+        out = device_rollout(h, cc, "full", tensors, stream, dt=CLOCK_DT, settle=0.0)
+        stream.synchronize()
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    clean = run()
+    want = clock_restatement(c, c["dur"])
+    assert want["clip_margin"].min() > 1e-9 and want["steps"].tolist() == [8, 4, 6, 10]
+    assert (clean["status"] == 0).all() and np.array_equal(clean["steps"], want["steps"]) and np.array_equal(clean["sat_steps"], want["sat_steps"])
+    assert same(clean["t"], want["t"])
+    err = {k: np.abs(clean[k] - want[k]).max() for k in ("q", "qd", "err_max", "err_end")}
+    print(f"clock: steps {clean['steps'].tolist()} differences {err}, allowed {16 * ROLLOUT_D:.2e}")
+    assert max(err.values()) <= 16 * ROLLOUT_D
+    edge = c["dur"].copy()
+    edge[1], edge[3] = 0.0, (MAX_STEPS + 0.5) * CLOCK_DT
+    m, p = c["model"][0], c["plant"][0]
+    cases = {"no period, too many": (dict(dur=edge), [1, 3]),
+             "plant mass": (dict(plant_mass=np.array([p[0], -1.0, p[2], np.nan])), [1, 3]),
+             "model mass": (dict(model_mass=np.array([np.nan, m[1], -1.0, m[3]])), [0, 2])}
+    assert clock_restatement(c, edge)["status"].tolist() == [0, 2, 0, 2]
+    for what, (kw, rows) in cases.items():
+        got = run(**kw)
+        bad = np.zeros(len(edge), dtype=bool)
+        bad[rows] = True
+        assert np.array_equal(got["status"], np.where(bad, 2, 0)), (what, got["status"])
+        assert not got["steps"][bad].any() and not got["sat_steps"][bad].any(), what
+        for k in got:
+            if k in ("q", "qd", "t", "err_max", "err_end"):
+                assert np.isnan(got[k][bad]).all(), (what, k)
+            assert same(got[k][~bad], clean[k][~bad]), (what, k)
+    h.close()
 
 
 # ------------------------------------------------------------------------------------------------ the Python layers

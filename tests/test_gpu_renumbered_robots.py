@@ -334,6 +334,157 @@ def test_retime_convex(rigs, name):
         assert same(got["chain"][k], got["sorted"][k]), k
 
 
+def _payload_dict(pl):
+    return dict(mass=pl[0], com=pl[1], inertia=pl[2])
+
+
+@pytest.mark.parametrize("name", ALL)
+def test_forward_dynamics(rigs, name):
+    """A9: gto_forward_dynamics on the 20 states of A7 with seeded joint forces and the `full` payload, under four `locked`
+    settings (rn.locked_lists: NULL, the explicit list equal to it, all but one, a seeded half whose free joints are
+    contiguous in neither numbering).  fd_sets (csrc/gto_api.hip) takes NULL from opt_of_dof and fd_solve eliminates the free
+    joints in ascending joint NUMBER.  Per view, against tests/forward_ref.py and the Jacobian-sum mass matrix on the original
+    robot, permuted, at the bars of tests/test_gpu_forward.py: qdd 1e-11 cond(M_ff) max(1, |qdd|), round trip 1e-11, M 1e-11
+    relative.  M_out's columns are independent rt_rnea passes and its symmetrisation is pairwise: the same bits in all
+    three views after permuting back.  qdd: the chain and sorted variants have the same joint numbers and no slot is read,
+    the same bits; original against renumbered only to the bar (another elimination order)."""
+    import dynamics_ref as dr
+    import forward_ref as fr
+    views = rigs(name)
+    v0 = views["original"]
+    d0, ee = v0.desc, v0.desc.frame_index(v0.ee)
+    q0, qd0, tau0, pl, locks0 = rn.forward_inputs(v0)
+    n = len(q0)
+    row = lambda i: (pl[0][i], pl[1][i], pl[2][i])  # noqa: E731
+    out = {}
+    for setting in rn.FORWARD_SETTINGS:
+        free = fr.free_joints(d0, locks0[setting])
+        assert free.any()
+        ref = [fr.forward_dynamics(d0, q0[i], qd0[i], tau0[i], ee, row(i), locks0[setting]) for i in range(n)]
+        got = {}
+        for v in [v0] + renumbered(views):
+            q, qd, tau, _, locks = rn.forward_inputs(v)
+            qdd, status, Mv = v.h.forward_dynamics(q, qd, tau, _payload_dict(pl), locks[setting], want_mass_matrix=True)
+            a, Ma = v.old(qdd, 1), v.old(v.old(Mv, 1), 2)
+            assert (status == 0).all() and np.isfinite(a).all() and not a[:, ~free].any(), (setting, v.variant)
+            worst_q = worst_rt = worst_M = 0.0
+            for i in range(n):
+                want, Mref = ref[i]
+                Mff = Mref[np.ix_(free, free)]
+                tol = 1e-11 * np.linalg.cond(Mff) * max(1.0, np.abs(want).max())
+                worst_q = max(worst_q, np.abs(a[i] - want).max() / tol)
+                back = dr.inverse_dynamics(d0, q0[i], qd0[i], a[i], ee, row(i))
+                scale = max(1.0, np.abs(tau0[i]).max(), (np.abs(Mref) @ np.abs(a[i])).max())
+                worst_rt = max(worst_rt, np.abs(back - tau0[i])[free].max() / scale)
+                worst_M = max(worst_M, np.abs(Ma[i] - Mref).max() / np.abs(Mref).max())
+            print(f"{name} {v.variant} locked={setting}: qdd error / tolerance {worst_q:.2e}, round trip {worst_rt:.2e}, M {worst_M:.2e}")
+            for key, x in (("forward_dynamics qdd (of its tolerance)", worst_q), ("forward_dynamics round trip", worst_rt), ("forward_dynamics M (relative)", worst_M)):
+                WORST[key] = max(WORST.get(key, 0.0), x)
+            assert worst_q <= 1.0 and worst_rt <= 1e-11 and worst_M <= 1e-11, (setting, v.variant)
+            got[v.variant] = (qdd, Mv, a, Ma)
+        for variant in rn.VARIANTS:
+            assert same(got[variant][3], got["original"][3]), (setting, variant)            # M_out: the same bits in every numbering
+            assert setting != "null" or not same(got[variant][0], got["original"][0]), variant  # (the joint axes did move)
+        assert same(got["chain"][0], got["sorted"][0]) and same(got["chain"][1], got["sorted"][1]), setting
+        out[setting] = got
+    for variant in ("original",) + rn.VARIANTS:   # the explicit list equal to the default is the default
+        assert locks0["null"] is None and same(out["null"][variant][0], out["default"][variant][0]), variant
+        assert not same(out["null"][variant][0], out["half"][variant][0])
+
+
+ROLLOUT_STEPS = {"r3": 6, "r55": 6}
+
+
+@pytest.mark.parametrize("mode", rn.ROLLOUT_MODES)
+@pytest.mark.parametrize("name", ALL)
+def test_track_rollout(rigs, name, mode):
+    """A10: gto_track_rollout on three paths built on the original robot (rn.rollout_inputs), feedforward full, and the
+    variant where one joint cannot hold; kp, kd and tau_max differ from joint to joint; locked = NULL and an explicit list
+    that frees a parameter joint.  Per view against tests/forward_ref.rollout_batch on the ORIGINAL robot, permuted: steps,
+    sat_steps and status equal, t bit for bit, q, qd, err_max, err_end within 16 d.  d = rn.ROLLOUT_D = 5.71e-10 is the largest
+    difference of the restatement over these very cases between its two mass-matrix orderings (columns=False / True) and
+    between the original and the renumbered description, measured on the CPU (tests/test_renumbered_robots_cpu.py holds the
+    restatement to them); per case, orderings / numberings:
+        r1 5.71e-10 / 4.96e-12   r9 1.47e-11 / 5.89e-13   r3 2.21e-14 / 8.89e-16   panda 2.17e-14 / 2.51e-16   r55 2.63e-11 / 1.65e-12
+    (r1's with the list that frees a parameter joint: 1.68e-14 under the default).  No clip decision of the restatement comes
+    within 1e-9 relative of its limit (the smallest margin: 2.4e-3).  The chain and the sorted variant: the same joint numbers,
+    no slot is read, every output bit for bit."""
+    views = rigs(name)
+    v0 = views["original"]
+    a0 = rn.rollout_inputs(v0, mode)
+    tol = 16 * rn.ROLLOUT_D
+    for lock in rn.ROLLOUT_LOCKS:
+        want = rn.rollout_restatement(v0, a0, lock)
+        assert want["clip_margin"].min() > 1e-9 and (want["status"] == 0).all()
+        assert want["steps"].max() <= ROLLOUT_STEPS.get(name, 20) and want["steps"].min() >= 2
+        if mode == "saturating":
+            assert want["sat_steps"][0] > want["steps"][0] // 2
+        got = {}
+        for v in [v0] + renumbered(views):
+            a = rn.rollout_inputs(v, mode)
+            g = v.h.track_rollout(a["duration"], a["q"], a["qd"], a["qdd"], a["kp"], a["kd"], tau_max=a["tau_max"], dt=a["dt"],
+                                  settle=a["settle"], n_samples=a["n_samples"], feedforward=a["feedforward"],
+                                  model_payload={"mass": a["model"][0]}, plant_payload=_payload_dict(a["plant"]), locked=a["locks"][lock])
+            got[v.variant] = g
+            for k in ("steps", "sat_steps", "status"):
+                assert np.array_equal(g[k], want[k]), (lock, v.variant, k, g[k], want[k])
+            assert same(g["t"], want["t"]), (lock, v.variant)
+            err = {k: float(np.abs((v.old(g[k], 2) if k in ("q", "qd") else g[k]) - want[k]).max()) for k in ("q", "qd", "err_max", "err_end")}
+            print(f"{name} {mode} {lock} {v.variant}: steps {g['steps'].tolist()} sat {g['sat_steps'].tolist()} differences {err}, allowed {tol:.2e}")
+            WORST["track_rollout q, qd, err_max, err_end"] = max(WORST.get("track_rollout q, qd, err_max, err_end", 0.0), max(err.values()))
+            assert max(err.values()) <= tol, (lock, v.variant)
+        for k in got["chain"]:
+            assert same(got["chain"][k], got["sorted"][k]), (lock, k)
+        assert not same(got["chain"]["q"], got["original"]["q"])
+
+
+@pytest.mark.parametrize("name", ALL)
+def test_retime_torque(rigs, name):
+    """A11: gto_retime_paths_torque on the inputs of A8 with the `full` payload and tau_max drawn per joint on the original
+    robot (rn.torque_limits: 1.5 to 3 times the largest static torque along the paths, +inf for a joint that carries none).
+    Per view: tests/test_gpu_retime_torque._against_reference with the restatement on the ORIGINAL robot (it compares
+    statuses and durations, recomputes the limits and the torques from the view's own outputs, and holds tau_out to
+    gto_inverse_dynamics of the returned samples in that view, bit for bit).  Across views: equal statuses and durations
+    within gap_tol, the rule of A8; the chain and the sorted variant bit for bit.  Where rn.TORQUE_ACTIVE says so at least one
+    path has an active torque row, longer than the convex call's by more than 10 gap_tol; r3 and r55 have none at any seed
+    (tests/test_renumbered_robots_cpu.py shows why), and there no path may be longer."""
+    import retime_torque_ref as tr
+    from test_gpu_retime import RTOL
+    from test_gpu_retime_torque import ALL as OUTPUTS, GAP_TOL, _against_reference
+    assert GAP_TOL == RETIME_CONVEX_GAP
+    views = rigs(name)
+    v0 = views["original"]
+    fee, pl = v0.desc.frame_index(v0.ee), rn.torque_payload()
+    paths0, vm0, am0 = rn.retime_inputs(v0)
+    tm0 = rn.torque_limits(v0)
+    assert np.isfinite(tm0).sum() >= 2 and len(set(tm0[np.isfinite(tm0)].tolist())) == np.isfinite(tm0).sum()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = tr.retime_paths_torque_ref(v0.desc, fee, paths0, None, vm0, am0, tm0, pl, 2, 16, GAP_TOL)
+    got = {}
+    for v in [v0] + renumbered(views):
+        paths, vm, am = rn.retime_inputs(v)
+        tm = rn.torque_limits(v)
+        assert same(v.old(tm, 0), tm0)
+        g, convex = _against_reference(v.desc, fee, v.h, paths, None, vm, am, tm, pl, 2, r, M=16)
+        got[v.variant] = g
+        ok = g["status"] == 0
+        active = ok & (g["duration"] > convex["duration"] * (1 + 10 * GAP_TOL))
+        print(f"{name} {v.variant}: torque retime status {g['status'].tolist()} active {active.tolist()} iterations {g['iters'].tolist()}")
+        assert active.any() == rn.TORQUE_ACTIVE[name], v.variant
+    g0 = got["original"]
+    ok = g0["status"] == 0
+    for variant in rn.VARIANTS:
+        g = got[variant]
+        assert same(g["status"], g0["status"]), variant
+        d, d0 = g["duration"][ok], g0["duration"][ok]
+        gap = np.abs(d - d0) / np.minimum(d, d0)
+        key = "retime_paths_torque duration across numberings (relative)"
+        WORST[key] = max(WORST.get(key, 0.0), float(gap.max()))
+        assert (np.abs(d - d0) <= GAP_TOL * np.minimum(d, d0) * (1 + RTOL)).all(), variant
+    for k in OUTPUTS:
+        assert same(got["chain"][k], got["sorted"][k]), k
+
+
 # =================================================================================================== B. solves and sums over slots
 def _close_blocks(a, b, rtol=1e-8):
     np.testing.assert_allclose(a, b, rtol=rtol, atol=1e-10 * max(np.abs(b).max(), 1e-30))

@@ -416,3 +416,43 @@ def test_retime_convex_against_the_restatement(rigs, kind, T, subdiv):
     still = d.ndof == 1
     assert (g["duration"] > 0).sum() == sr.RETIME_B - still and (g["iters"] > 0).sum() == sr.RETIME_B - still
     assert not still or (g["duration"][1] == 0 and g["iters"][1] == 0)
+
+
+@pytest.mark.parametrize("subdiv", sr.RETIME_SUBDIVS)
+@pytest.mark.parametrize("T", [4, 5])
+@pytest.mark.parametrize("kind", sr.RETIME_KINDS)
+def test_retime_torque_against_the_restatement(capi, kind, T, subdiv):
+    """gto_retime_paths_torque on the same plans and limits with seeded link inertials, the `full` payload and tau_max at 1.5 to
+    3 times the unloaded robot's largest static torque (sr.retime_torque_inputs): tests/test_gpu_retime_torque._against_reference
+    (the restatement's statuses and durations within the certified gap, limits and torques recomputed from the outputs,
+    tau_out bit for bit gto_inverse_dynamics of the samples).  With one joint plan 1 stands still: duration 0, no Newton step
+    and tau the static torque at every sample where the joint can hold the payload, INFEASIBLE and NaN where it cannot
+    (sr.RETIME_STILL_HELD, asserted on the CPU).  Without any finite limit the call is the convex call, bit for bit."""
+    import dynamics_ref as dr
+    import retime_torque_ref as tr
+    from test_gpu_retime import KEYS, _same
+    from test_gpu_retime_torque import GAP_TOL, INFEASIBLE, _against_reference
+    d, fee, plans, vm, am, tm, pl = sr.retime_torque_inputs(kind, T, subdiv)
+    r0 = sr.Robot(kind, seed=sr.SEEDS.get((kind, T, (5, 5, 5)), 0))
+    h = capi.SolverHandle(d, r0.ee, r0.gripper, device=0, n_gripper_points=r0.n_gripper_points)
+    try:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = tr.retime_paths_torque_ref(d, fee, plans, None, vm, am, tm, pl, subdiv, 16, GAP_TOL)
+        g, convex = _against_reference(d, fee, h, plans, None, vm, am, tm, pl, subdiv, r, M=16)
+        assert np.isfinite(tm).all() and np.isin(g["status"], (0, INFEASIBLE)).all() and (g["status"] == 0).sum() >= 2
+        if d.ndof == 1:
+            held = sr.RETIME_STILL_HELD[kind, T]
+            assert g["status"][1] == (0 if held else INFEASIBLE) and g["iters"][1] == 0
+            if held:
+                static = dr.inverse_dynamics(d, plans[1][:, 0], np.zeros(1), np.zeros(1), fee, tr.payload_of(pl, 1))
+                want = h.inverse_dynamics(plans[1][:, 0], np.zeros(1), np.zeros(1), {k: v[1:2] for k, v in zip(("mass", "com", "inertia"), pl)})
+                assert g["duration"][1] == 0 and _same(g["tau"][1], np.tile(want, (16, 1)))
+                assert np.abs(g["tau"][1] - static).max() <= 1e-11 * max(1.0, np.abs(static).max())
+            else:
+                assert np.isnan(g["duration"][1]) and np.isnan(g["tau"][1]).all()
+        free = h.retime_paths_torque(plans, vm, am, tau_max=np.inf, payload={k: v for k, v in zip(("mass", "com", "inertia"), pl)},
+                                     subdiv=subdiv, n_samples=16, gap_tol=GAP_TOL)
+        for k in KEYS + ("status", "iters"):  # no row is added: the convex call's arithmetic
+            assert _same(free[k], convex[k]), k
+    finally:
+        h.close()

@@ -41,10 +41,14 @@ MODES = ("late", "early", "host", "host_pinned")  # host_pinned: the caller's ho
 #   iters, status of the solvers   max_iter = 3 ends every solve of the rig at the cap: 3 iterations and GTO_STATUS_MAX_ITER
 #                                  for any valid input (the lift: for every step)
 #   status of the retime calls     GTO_STATUS_CONVERGED for every finite plan that moves (the convex call's iters DO differ
-#                                  with the inputs and are compared like every other output)
+#                                  with the inputs and are compared like every other output); the torque call's limits
+#                                  lie above the Panda's own, so no path of the rig is INFEASIBLE
+#   status, steps of the rollout   every path of the rig is followed to its end; steps = ceil((duration + settle) / dt) is one
+#                                  of 4 .. 10 and may come out the same for a few paths
 _SOLVER = ("iters", "status")
 SAME_FOR_DECOY = {"solve": _SOLVER, "ik_pose": _SOLVER, "retrieve_lift": _SOLVER, "solve_base": _SOLVER, "retime_batch": ("status",),
-                  "retime_paths": ("status",), "retime_paths_convex": ("status",), "chain": ("ik_iters", "ik_status", "iters", "status", "rt_status", "rp_status")}
+                  "retime_paths": ("status",), "retime_paths_convex": ("status",), "retime_paths_torque": ("status",),
+                  "track_rollout": ("status", "steps"), "chain": ("ik_iters", "ik_status", "iters", "status", "rt_status", "rp_status")}
 
 
 def torch_dtype(dt):
@@ -303,8 +307,10 @@ def test_a_solve_behind_a_busy_stream(rig, lanes, mode):
 @pytest.mark.parametrize("memory", ["pageable", "pinned"])
 @pytest.mark.parametrize("run", list(soc.REGROW_RUNS))
 def test_more_calls_in_flight_than_pinned_slots_with_regrowth(rig, run, memory):
-    """Six calls (twelve for the base pair and for the retime pair, whose greedy and convex calls alternate on the rt_*
-    workspace they share and of which k_retime_convex rewrites rt_P1 / rt_P2 in place) of one fresh handle on one stream behind
+    """Six calls (twelve for the base pair, eighteen for the three retime calls, whose greedy, convex and torque calls take
+    turns on the rt_* workspace they share, of which k_retime_convex rewrites rt_P1 / rt_P2 in place and to which the torque
+    call adds rt_TA / rt_TB / rt_TG: the torque call at B = 65 is still queued when the greedy call at B = 130 regrows the
+    workspace) of one fresh handle on one stream behind
     a hold, each with host arrays and outputs
     of its own, the host arrays overwritten as soon as their call returns.  Past four calls the pinned ring is reused, which is
     safe only behind the slot's event; B = 65 and 130 regrow bs_ng / ck_base / the held, filter and retime workspaces by free and

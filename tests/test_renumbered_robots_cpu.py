@@ -284,6 +284,125 @@ def test_retime_inputs_have_certified_convex_profiles_in_every_numbering(cases, 
         assert (np.abs(d - d0) <= 1e-8 * np.minimum(d, d0) * (1 + 1e-9)).all()
 
 
+# ------------------------------------------------------------------- forward dynamics, the rollout and the torque retime
+@pytest.mark.parametrize("name", list(rn.CASES))
+def test_locked_lists_are_what_they_are_chosen_for(cases, name):
+    """rn.locked_lists / rn.rollout_locks: every joint of these robots moves mass, so NULL is passed as NULL; the explicit list
+    equals it; the seeded half leaves free joints that are one run of numbers in neither numbering (a kernel that took a
+    joint's place in the list for its number, or the other way round, is then wrong in every view); and the rollout's second
+    list frees a parameter joint where the robot has one."""
+    import forward_ref as fr
+    c = cases(name)
+    d0, pi = c.desc0, np.asarray(c.pi)
+    moving = rn.moving_joints(c)
+    assert moving.all() and fr.named_joints(d0).all()
+    lists = rn.locked_lists(c)
+    assert list(lists) == list(rn.FORWARD_SETTINGS) and lists["null"] is None
+    assert np.array_equal(lists["default"] == 0, fr.free_joints(d0)) and (lists["all_but_one"] == 0).sum() == 1
+    free = np.flatnonzero(lists["half"] == 0)
+    assert 2 <= len(free) <= d0.ndof // 2 + 1 and not rn.contiguous(free) and not rn.contiguous(pi[free])
+    for variant in rn.VARIANTS:
+        v = c.view(variant)
+        q, qd, tau, pl, locks = rn.forward_inputs(v)
+        q0, qd0, tau0, _, locks0 = rn.forward_inputs(c.view("original"))
+        assert same(v.old(q, 1), q0) and same(v.old(tau, 1), tau0) and not same(tau, tau0) and locks["null"] is None
+        for k in rn.FORWARD_SETTINGS[1:]:
+            assert same(v.old(locks[k], 0), locks0[k]) and locks[k].dtype == np.int32
+            assert np.array_equal(fr.free_joints(v.desc, locks[k]), v.new(fr.free_joints(d0, locks0[k]), 0))
+        assert np.array_equal(fr.free_joints(v.desc), v.new(fr.free_joints(d0), 0))   # NULL follows opt_index, not the position
+        if name != "r55":
+            assert not np.array_equal(fr.free_joints(v.desc), np.arange(d0.ndof) < d0.n_opt)
+    rl = rn.rollout_locks(c)
+    assert rl["default"] is None
+    freed = np.flatnonzero(rl["freed"] == 0)
+    if len(d0.param_index):
+        assert set(freed) == set(d0.opt_index.tolist()) | {int(d0.param_index[0])}
+    else:
+        assert len(freed) == d0.n_opt - 1
+
+
+@pytest.mark.parametrize("name", list(rn.CASES))
+def test_forward_dynamics_yardstick_is_invariant(cases, name):
+    """tests/forward_ref.forward_dynamics on the renumbered description gives the original's accelerations and mass matrix,
+    permuted: the matrix bit for bit (a sum over the bodies, entry by entry), the solve to the GPU test's bar (LAPACK
+    eliminates in the list's order)."""
+    import forward_ref as fr
+    c = cases(name)
+    v0, v = c.view("original"), c.view("sorted")
+    ee = c.desc0.frame_index(c.ee)
+    q0, qd0, tau0, pl, locks0 = rn.forward_inputs(v0)
+    q, qd, tau, _, locks = rn.forward_inputs(v)
+    for setting in rn.FORWARD_SETTINGS:
+        free = fr.free_joints(c.desc0, locks0[setting])
+        for i in range(0, rn.DYNAMICS_ROWS, 5):
+            row = (pl[0][i], pl[1][i], pl[2][i])
+            a0, M0 = fr.forward_dynamics(c.desc0, q0[i], qd0[i], tau0[i], ee, row, locks0[setting])
+            a, M = fr.forward_dynamics(v.desc, q[i], qd[i], tau[i], ee, row, locks[setting])
+            assert np.isfinite(a0).all() and same(v.old(v.old(M, 0), 1), M0)
+            tol = 1e-11 * np.linalg.cond(M0[np.ix_(free, free)]) * max(1.0, np.abs(a0).max())
+            assert np.abs(v.old(a, 0) - a0).max() <= tol and not a0[~free].any()
+
+
+@pytest.mark.parametrize("mode", rn.ROLLOUT_MODES)
+@pytest.mark.parametrize("name", list(rn.CASES))
+def test_rollout_restatement_is_invariant_and_no_clip_hangs_on_round_off(cases, name, mode):
+    """tests/forward_ref.rollout_batch on rn.rollout_inputs: no clip decision within 1e-9 relative of its limit (so steps and
+    sat_steps can be compared for equality), at most 20 steps (6 on r3 and r55), gains and limits that differ from joint to
+    joint, and on the renumbered description the original's results, permuted, well inside rn.ROLLOUT_D (the two mass-matrix
+    orderings of the restatement, rn.ROLLOUT_D_MEASURED, differ by more than the two numberings do)."""
+    c = cases(name)
+    v0, v = c.view("original"), c.view("sorted")
+    a0, a = rn.rollout_inputs(v0, mode), rn.rollout_inputs(v, mode)
+    named = np.isfinite(a0["tau_max"])
+    assert named.all() and all(len(set(a0[k].tolist())) == c.desc0.ndof for k in ("kp", "kd", "tau_max"))
+    assert same(v.old(a["kp"], 0), a0["kp"]) and not same(a["kp"], a0["kp"]) and same(v.old(a["q"], 2), a0["q"])
+    assert rn.ROLLOUT_D == max(x for pair in rn.ROLLOUT_D_MEASURED.values() for x in pair)
+    for lock in rn.ROLLOUT_LOCKS:
+        w0, w = rn.rollout_restatement(v0, a0, lock), rn.rollout_restatement(v, a, lock)
+        assert w0["clip_margin"].min() > 1e-9 and (w0["status"] == 0).all()
+        assert w0["steps"].max() <= (6 if name in ("r3", "r55") else 20) and w0["steps"].min() >= 2
+        if mode == "saturating":
+            assert w0["sat_steps"][0] > w0["steps"][0] // 2
+        for k in ("steps", "sat_steps", "status"):
+            assert np.array_equal(w[k], w0[k]), (lock, k)
+        assert same(w["t"], w0["t"])
+        diff = max(float(np.abs((v.old(w[k], 2) if k in ("q", "qd") else w[k]) - w0[k]).max()) for k in ("q", "qd", "err_max", "err_end"))
+        print(f"{name} {mode} {lock}: original against renumbered restatement {diff:.2e}, margin {w0['clip_margin'].min():.2e}")
+        assert diff <= rn.ROLLOUT_D
+
+
+@pytest.mark.parametrize("name", list(rn.CASES))
+def test_torque_limits_bind_where_the_gpu_test_says(cases, name):
+    """tests/retime_torque_ref.py on the inputs of A11 (original numbering): where rn.TORQUE_ACTIVE says so some path is
+    solved and longer than its convex profile by more than 10 gap_tol, a torque row is active.  r3 and r55 have none and can
+    have none: the payload raises no static torque to 1.5 times the unloaded one, where the limits begin."""
+    import dynamics_ref as dr
+    import retime_convex_ref as cr
+    import retime_torque_ref as tr
+    c = cases(name)
+    d, v0 = c.desc0, c.view("original")
+    fee, pl = d.frame_index(c.ee), rn.torque_payload()
+    paths, vm, am = rn.retime_inputs(v0)
+    tm = rn.torque_limits(v0)
+    assert np.isfinite(tm).sum() >= 2 and len(set(tm[np.isfinite(tm)].tolist())) == np.isfinite(tm).sum()
+    for variant in rn.VARIANTS:
+        assert same(c.view(variant).old(rn.torque_limits(c.view(variant)), 0), tm)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = tr.retime_paths_torque_ref(d, fee, paths, None, vm, am, tm, pl, 2, 16, 1e-8)
+        convex = cr.retime_paths_convex_ref(paths, None, vm, am, 2, 16, 1e-8)
+    ok = r["status"] == 0
+    active = ok & (r["duration"] > convex["duration"] * (1 + 1e-7))
+    print(f"{name}: status {r['status'].tolist()}, torque / convex duration {(r['duration'] / convex['duration']).tolist()}")
+    assert np.isin(r["status"], (0, tr.GTO_STATUS_INFEASIBLE)).all() and ok.any() and active.any() == rn.TORQUE_ACTIVE[name]
+    if not rn.TORQUE_ACTIVE[name]:
+        z = np.zeros(d.ndof)
+        grids = [tr.path_points(p, 2)[0] for p in paths]
+        bare = np.max([np.abs(np.array([dr.inverse_dynamics(d, qi, z, z, fee) for qi in q])).max(axis=0) for q in grids], axis=0)
+        held = np.max([np.abs(np.array([dr.inverse_dynamics(d, qi, z, z, fee, tr.payload_of(pl, b)) for qi in q])).max(axis=0)
+                       for b, q in enumerate(grids)], axis=0)
+        assert (bare > 1e-9).all() and (held / bare).max() < 1.4, held / bare
+
+
 # ------------------------------------------------------------------------------------------------- gto_create
 @pytest.fixture(scope="module")
 def capi():

@@ -196,6 +196,35 @@ def test_retiming_inputs_have_certified_convex_profiles(kind, T):
         assert (r["duration"] <= greedy["duration"] * (1 + 1e-8)).all()
 
 
+@pytest.mark.parametrize("T", [4, 5])
+@pytest.mark.parametrize("kind", sr.RETIME_KINDS)
+def test_torque_retiming_inputs_are_what_the_gpu_test_takes_them_for(kind, T):
+    """tests/retime_torque_ref.py on sr.retime_torque_inputs: every joint of every kind feels gravity (a finite limit each:
+    no kind is the convex call in disguise), every path is solved or INFEASIBLE, at least two are solved, and the plan that
+    stands still is held exactly where sr.RETIME_STILL_HELD says -- chain_1 at T = 5 at no factor of the rule."""
+    import dynamics_ref as dr
+    import retime_convex_ref as cr
+    import retime_torque_ref as tr
+    for subdiv in sr.RETIME_SUBDIVS:
+        d, fee, plans, vm, am, tm, pl = sr.retime_torque_inputs(kind, T, subdiv)
+        assert d.has_inertials and np.isfinite(tm).all() and (tm > 0).all() and tm.shape == (d.ndof,)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = tr.retime_paths_torque_ref(d, fee, plans, None, vm, am, tm, pl, subdiv, 16, 1e-8)
+            convex = cr.retime_paths_convex_ref(plans, None, vm, am, subdiv, 16, 1e-8)
+        ok = r["status"] == 0
+        assert np.isin(r["status"], (0, tr.GTO_STATUS_INFEASIBLE)).all() and ok.sum() >= 2
+        assert (r["duration"][ok] >= convex["duration"][ok] * (1 - 1e-8)).all()
+        if d.ndof == 1:
+            assert bool(ok[1]) == sr.RETIME_STILL_HELD[kind, T] and r["iters"][1] == 0
+            z = np.zeros(1)
+            g = abs(dr.inverse_dynamics(d, plans[1][:, 0], z, z, fee, tr.payload_of(pl, 1))[0])
+            if ok[1]:
+                assert r["duration"][1] == 0 and np.allclose(np.abs(r["tau"][1]), g, rtol=1e-12) and g < tm[0]
+            else:  # out of the rule's reach: 3 times the unloaded robot's largest static torque does not hold it
+                top = max(np.abs(np.array([dr.inverse_dynamics(d, qi, z, z, fee) for qi in tr.path_points(p, subdiv)[0]])).max() for p in plans)
+                assert g > 3.0 * top
+
+
 def _plan_instances_are_decided(solved, cid):
     """The depth image and the sampled box that check_plans is run through: no surface point of the oracle within 1e-9 m of a
     decision, under the shared base and under the per-plan bases, and counts that are not all alike."""
