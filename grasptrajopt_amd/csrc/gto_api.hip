@@ -96,6 +96,7 @@ struct Tunables {
   bool obs_tg_given = false;  // GTO_OBS_TG was set: it is the group size of every robot, the wide ones included
   int few_instances = 192;  // GTO_FEW_INSTANCES: launches with at most this many instances in flight count as few
   int step_nw_few = 8;  // GTO_STEP_NW_FEW: wavefronts per workgroup of the step kernel in launches with few instances in flight (4 or 8)
+  int step_tclass = 1;  // GTO_STEP_TCLASS=0: the narrow step kernels' 96-waypoint instantiation at every T (tests, A/B runs; same results)
   int slots = 512;  // GTO_SLOTS: instances in flight per lane of a solve call; a finished instance hands its slot to the next one
   // lanes of a solve call (gto_solve_batch_device): at most lanes_max, each with at least lane_min instances; a lane with
   // at most adopt_below instances left hands them to lane 0 (0: never).  gto_set_lanes / GTO_LANES, GTO_LANE_MIN, GTO_ADOPT
@@ -146,6 +147,7 @@ static void read_tunables(Tunables& t) {
       {"GTO_OBS_TG_FEW_TAIL", &Tunables::obs_tg_few_tail, nullptr, nullptr, 1, GTO_MAX_TG},
       {"GTO_OBS_TG_WIDE", &Tunables::obs_tg_wide, nullptr, nullptr, 1, GTO_MAX_TG},
       {"GTO_FEW_INSTANCES", &Tunables::few_instances, nullptr, nullptr, INT_MIN, INT_MAX},
+      {"GTO_STEP_TCLASS", &Tunables::step_tclass, nullptr, nullptr, 0, 1},
   };
   for (const Row& r : rows) {
     const char* e = getenv(r.name);
@@ -473,6 +475,8 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
   for (int v = 0; v < 8 && e == hipSuccess; ++v) e = raise_dynamic_lds((const void*)obstacle_kernel(np, v & 1, v & 2, v & 4), lds);
   if (e == hipSuccess) e = wide ? raise_dynamic_lds((const void*)k_lm_step_wide<16>, lm_lds) : raise_dynamic_lds((const void*)k_lm_step<4, 1>, lm_lds);
   if (e == hipSuccess && !wide) e = raise_dynamic_lds((const void*)k_lm_step<8, GTO_KSPEC>, lm_lds_bytes(opts->T, spec_kmax));
+  if (e == hipSuccess && !wide) e = raise_dynamic_lds((const void*)k_lm_step_short<4, 1>, lm_lds);
+  if (e == hipSuccess && !wide) e = raise_dynamic_lds((const void*)k_lm_step_short<8, GTO_KSPEC>, lm_lds_bytes(opts->T, spec_kmax));
   if (e == hipSuccess && !wide) e = raise_dynamic_lds((const void*)k_seed_broad, lm_lds);
   if (e != hipSuccess) { gto_destroy(h); return fail(nullptr, GTO_ERR_HIP, "hipFuncSetAttribute failed"); }
   *out = h;
@@ -1256,15 +1260,20 @@ static int enqueue_round(gto_handle* h, const SolveCall& c, LaneCtx& ln, int lan
   lsp.k_eval = ln.k_prev;  // the goal workgroups skip fresh instances themselves: k_lm_init already produced the seed's goal terms
   int rc;
   if ((rc = launch_obstacle(h, ln.st, ln.bp, lsp, B, p.obs))) return rc;
+  // the narrow step kernels by class of trajectory length: the instantiation unrolled for GTO_STEP_T_SHORT waypoints where
+  // the call's T allows it (same results; GTO_STEP_TCLASS=0: the general one at every T)
+  const bool t_short = h->tu.step_tclass && T <= GTO_STEP_T_SHORT;
   if (h->profiling && (rc = prof_begin(h, ln.st, p.step == STEP_FEW ? GTO_PROF_STEP_FEW : GTO_PROF_STEP, p.in_flight))) return rc;
   if (p.step == STEP_FEW) {
     lsp.k_acc = p.k_acc, lsp.k_rej = p.k_rej, lsp.spec_streak = p.spec_streak;
     lsp.pb_next = 0, lsp.static_pos = 0;
-    hipLaunchKernelGGL((k_lm_step<8, GTO_KSPEC>), dim3(p.span), dim3(512), lm_lds_bytes(T, p.k_next), ln.st, h->d_rb, ln.bp, lsp, B);
+    if (t_short) hipLaunchKernelGGL((k_lm_step_short<8, GTO_KSPEC>), dim3(p.span), dim3(512), lm_lds_bytes(T, p.k_next), ln.st, h->d_rb, ln.bp, lsp, B);
+    else hipLaunchKernelGGL((k_lm_step<8, GTO_KSPEC>), dim3(p.span), dim3(512), lm_lds_bytes(T, p.k_next), ln.st, h->d_rb, ln.bp, lsp, B);
   } else if (p.step == STEP_FULL) {
     lsp.k_acc = lsp.k_rej = 1;
     lsp.pb_next = p.pb_next, lsp.static_pos = p.static_pos;
-    hipLaunchKernelGGL((k_lm_step<4, 1>), dim3(p.span), dim3(256), h->lm_lds, ln.st, h->d_rb, ln.bp, lsp, B);
+    if (t_short) hipLaunchKernelGGL((k_lm_step_short<4, 1>), dim3(p.span), dim3(256), h->lm_lds, ln.st, h->d_rb, ln.bp, lsp, B);
+    else hipLaunchKernelGGL((k_lm_step<4, 1>), dim3(p.span), dim3(256), h->lm_lds, ln.st, h->d_rb, ln.bp, lsp, B);
   } else {
     hipLaunchKernelGGL(k_lm_step_wide<16>, dim3(p.in_flight), dim3(GTO_WIDE_NT), h->lm_lds, ln.st, h->d_rb, ln.bp, lsp, B,
                        h->zws.as<double>() + (size_t)c.lane_zws[lane_index] * (T - 2) * h->np * h->np);
