@@ -96,6 +96,7 @@ struct Tunables {
   bool obs_tg_given = false;  // GTO_OBS_TG was set: it is the group size of every robot, the wide ones included
   int few_instances = 192;  // GTO_FEW_INSTANCES: launches with at most this many instances in flight count as few
   int step_nw_few = 8;  // GTO_STEP_NW_FEW: wavefronts per workgroup of the step kernel in launches with few instances in flight (4 or 8)
+  int step_texact = 1;  // GTO_STEP_TEXACT=0: no kernel compiled for one trajectory length: at T = GTO_STEP_T_EXACT the choice GTO_STEP_TCLASS makes (tests, A/B runs; same results)
   int step_tclass = 1;  // GTO_STEP_TCLASS=0: the narrow step kernels' 96-waypoint instantiation at every T (tests, A/B runs; same results)
   int slots = 512;  // GTO_SLOTS: instances in flight per lane of a solve call; a finished instance hands its slot to the next one
   // lanes of a solve call (gto_solve_batch_device): at most lanes_max, each with at least lane_min instances; a lane with
@@ -148,6 +149,7 @@ static void read_tunables(Tunables& t) {
       {"GTO_OBS_TG_WIDE", &Tunables::obs_tg_wide, nullptr, nullptr, 1, GTO_MAX_TG},
       {"GTO_FEW_INSTANCES", &Tunables::few_instances, nullptr, nullptr, INT_MIN, INT_MAX},
       {"GTO_STEP_TCLASS", &Tunables::step_tclass, nullptr, nullptr, 0, 1},
+      {"GTO_STEP_TEXACT", &Tunables::step_texact, nullptr, nullptr, 0, 1},
   };
   for (const Row& r : rows) {
     const char* e = getenv(r.name);
@@ -205,6 +207,7 @@ struct gto_handle {
   Tunables tu;  // the GTO_* knobs, read at gto_create
   int spec_kmax = 1;  // candidates per step the eight-wave step kernel's LDS has room for at this T
   DevBuf dbg;  // GTO_DEBUG_TIMING: the kernels' phase stamps (long long[256])
+  std::atomic<int> dbg_step_launches[2] = {{0}, {0}};  // ... and the call's narrow step launches: [1] of k_lm_step_t50, [0] of the others
   // buffers of the scene that the last gto_set_scene replaced: the next replacement of the same size takes them instead of
   // going through hipMalloc / hipFree (fourteen calls of 0.2-0.3 ms each: most of a small scene's upload time)
   std::vector<DevBuf> spare;
@@ -477,6 +480,8 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
   if (e == hipSuccess && !wide) e = raise_dynamic_lds((const void*)k_lm_step<8, GTO_KSPEC>, lm_lds_bytes(opts->T, spec_kmax));
   if (e == hipSuccess && !wide) e = raise_dynamic_lds((const void*)k_lm_step_short<4, 1>, lm_lds);
   if (e == hipSuccess && !wide) e = raise_dynamic_lds((const void*)k_lm_step_short<8, GTO_KSPEC>, lm_lds_bytes(opts->T, spec_kmax));
+  if (e == hipSuccess && !wide) e = raise_dynamic_lds((const void*)k_lm_step_t50<4, 1>, lm_lds);
+  if (e == hipSuccess && !wide) e = raise_dynamic_lds((const void*)k_lm_step_t50<8, GTO_KSPEC>, lm_lds_bytes(opts->T, spec_kmax));
   if (e == hipSuccess && !wide) e = raise_dynamic_lds((const void*)k_seed_broad, lm_lds);
   if (e != hipSuccess) { gto_destroy(h); return fail(nullptr, GTO_ERR_HIP, "hipFuncSetAttribute failed"); }
   *out = h;
@@ -1263,16 +1268,22 @@ static int enqueue_round(gto_handle* h, const SolveCall& c, LaneCtx& ln, int lan
   // the narrow step kernels by class of trajectory length: the instantiation unrolled for GTO_STEP_T_SHORT waypoints where
   // the call's T allows it (same results; GTO_STEP_TCLASS=0: the general one at every T)
   const bool t_short = h->tu.step_tclass && T <= GTO_STEP_T_SHORT;
+  // ... and at the one length the reference and every shipped configuration run at, the instantiation with T a constant
+  // (k_lm_step_t50: same results; GTO_STEP_TEXACT=0: the choice above)
+  const bool t_exact = h->tu.step_texact && T == GTO_STEP_T_EXACT;
+  if (h->dbg && p.step != STEP_WIDE) h->dbg_step_launches[t_exact ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
   if (h->profiling && (rc = prof_begin(h, ln.st, p.step == STEP_FEW ? GTO_PROF_STEP_FEW : GTO_PROF_STEP, p.in_flight))) return rc;
   if (p.step == STEP_FEW) {
     lsp.k_acc = p.k_acc, lsp.k_rej = p.k_rej, lsp.spec_streak = p.spec_streak;
     lsp.pb_next = 0, lsp.static_pos = 0;
-    if (t_short) hipLaunchKernelGGL((k_lm_step_short<8, GTO_KSPEC>), dim3(p.span), dim3(512), lm_lds_bytes(T, p.k_next), ln.st, h->d_rb, ln.bp, lsp, B);
+    if (t_exact) hipLaunchKernelGGL((k_lm_step_t50<8, GTO_KSPEC>), dim3(p.span), dim3(512), lm_lds_bytes(T, p.k_next), ln.st, h->d_rb, ln.bp, lsp, B);
+    else if (t_short) hipLaunchKernelGGL((k_lm_step_short<8, GTO_KSPEC>), dim3(p.span), dim3(512), lm_lds_bytes(T, p.k_next), ln.st, h->d_rb, ln.bp, lsp, B);
     else hipLaunchKernelGGL((k_lm_step<8, GTO_KSPEC>), dim3(p.span), dim3(512), lm_lds_bytes(T, p.k_next), ln.st, h->d_rb, ln.bp, lsp, B);
   } else if (p.step == STEP_FULL) {
     lsp.k_acc = lsp.k_rej = 1;
     lsp.pb_next = p.pb_next, lsp.static_pos = p.static_pos;
-    if (t_short) hipLaunchKernelGGL((k_lm_step_short<4, 1>), dim3(p.span), dim3(256), h->lm_lds, ln.st, h->d_rb, ln.bp, lsp, B);
+    if (t_exact) hipLaunchKernelGGL((k_lm_step_t50<4, 1>), dim3(p.span), dim3(256), h->lm_lds, ln.st, h->d_rb, ln.bp, lsp, B);
+    else if (t_short) hipLaunchKernelGGL((k_lm_step_short<4, 1>), dim3(p.span), dim3(256), h->lm_lds, ln.st, h->d_rb, ln.bp, lsp, B);
     else hipLaunchKernelGGL((k_lm_step<4, 1>), dim3(p.span), dim3(256), h->lm_lds, ln.st, h->d_rb, ln.bp, lsp, B);
   } else {
     hipLaunchKernelGGL(k_lm_step_wide<16>, dim3(p.in_flight), dim3(GTO_WIDE_NT), h->lm_lds, ln.st, h->d_rb, ln.bp, lsp, B,
@@ -1449,6 +1460,8 @@ static int print_debug_stamps(gto_handle* h, hipStream_t st) {
   HIPCHK(h, hipMemcpy(t, h->dbg.get(), sizeof t, hipMemcpyDeviceToHost));
   fprintf(stderr, "[gto dbg] step-kernel phases (cycles) P0+P1 %lld | P2 %lld | diag %lld | dense %lld | back %lld | P4 %lld | P5 %lld | s_dense %lld\n",
           t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4], t[6] - t[5], t[7] - t[6], t[9]);
+  fprintf(stderr, "[gto dbg] narrow step launches of the call: %d of k_lm_step_t50 (T = %d a constant), %d of the others\n",
+          h->dbg_step_launches[1].exchange(0), GTO_STEP_T_EXACT, h->dbg_step_launches[0].exchange(0));
   if (h->np != GTO_NB)
     fprintf(stderr, "[gto dbg] wide step kernel, sweeps (cycles): downward: %lld in %lld dense inversions, sweep %lld | upward: %lld in %lld dense inversions, sweep %lld\n",
             t[56], t[57], t[58], t[59], t[60], t[61]);

@@ -10,7 +10,8 @@ function symbols of the device image embedded in libgto_hip.so) and the sums for
   tail alone             the eight-wave step kernel and the two obstacle variants of the tail
 
 The step kernels are listed as a call with T <= GTO_STEP_T_SHORT launches them (k_lm_step_short) and as any other call
-does (k_lm_step); a library without the short instantiation (an older build) gives the second set only.
+does (k_lm_step); a library without the short instantiation (an older build) gives the second set only.  A library with the
+instantiation for T = GTO_STEP_T_EXACT (k_lm_step_t50) gets a third set, listed last.
 
 usage: python tools/code_footprint.py [--lib libgto_hip.so] [-o OUT.txt]
 """
@@ -27,6 +28,8 @@ STEP_FULL = "_Z9k_lm_stepILi4ELi1EEvPK8RobotDev9BatchPtrs11SolveParamsi"
 STEP_FEW = "_Z9k_lm_stepILi8ELi4EEvPK8RobotDev9BatchPtrs11SolveParamsi"
 STEP_FULL_SHORT = "_Z15k_lm_step_shortILi4ELi1EEvPK8RobotDev9BatchPtrs11SolveParamsi"
 STEP_FEW_SHORT = "_Z15k_lm_step_shortILi8ELi4EEvPK8RobotDev9BatchPtrs11SolveParamsi"
+STEP_FULL_T50 = "_Z13k_lm_step_t50ILi4ELi1EEvPK8RobotDev9BatchPtrs11SolveParamsi"
+STEP_FEW_T50 = "_Z13k_lm_step_t50ILi8ELi4EEvPK8RobotDev9BatchPtrs11SolveParamsi"
 OBS = "_Z15k_obstacle_gramILi8ELi%dELb%dELb1EE"  # <8, DEEP, ITEMIZED, true>
 OBS_ITEM, OBS_TAIL, OBS_TAIL_DEEP = OBS % (1, 1), OBS % (1, 0), OBS % (8, 0)
 CREW = "obstacle_gram_crew"
@@ -86,12 +89,14 @@ def report(lib):
         raise SystemExit(f"{lib}: kernels missing from the code object: {missing}")
     kb = lambda n: f"{sizes[n]:7d} B  {sizes[n] / 1024.0:6.1f} KB"
     lines = [f"library: {os.path.basename(lib)}", "", "solve-loop kernels (function symbol sizes):"]
-    names = [STEP_FULL_SHORT, STEP_FEW_SHORT, STEP_FULL, STEP_FEW, obs_item, crew, obs_tail, obs_deep]
+    names = [STEP_FULL_SHORT, STEP_FEW_SHORT, STEP_FULL, STEP_FEW, obs_item, crew, obs_tail, obs_deep, STEP_FULL_T50, STEP_FEW_T50]
     for n in names:
         if n in sizes:
             lines.append(f"  {kb(n)}  {n}")
     classes = [("T <= 50 (k_lm_step_short)", STEP_FULL_SHORT, STEP_FEW_SHORT)] if STEP_FULL_SHORT in sizes and STEP_FEW_SHORT in sizes else []
     classes.append(("any T (k_lm_step)", STEP_FULL, STEP_FEW))
+    if STEP_FULL_T50 in sizes and STEP_FEW_T50 in sizes:
+        classes.append(("T = 50 (k_lm_step_t50)", STEP_FULL_T50, STEP_FEW_T50))
     for title, full, few in classes:
         item = sizes[obs_item] + (sizes[crew] if crew else 0)
         tail = sizes[few] + sizes[obs_tail] + sizes[obs_deep]

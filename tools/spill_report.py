@@ -22,7 +22,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEFAULT_KERNELS = ("k_lm_stepILi4ELi1", "k_lm_stepILi8ELi4", "k_lm_step_wide", "k_seed_broad", "k_obstacle_gramILi8ELi1")
+DEFAULT_KERNELS = ("k_lm_stepILi4ELi1", "k_lm_stepILi8ELi4", "k_lm_step_wide", "k_seed_broad", "k_obstacle_gramILi8ELi1",
+                   "k_lm_step_shortILi4ELi1", "k_lm_step_shortILi8ELi4", "k_lm_step_t50ILi4ELi1", "k_lm_step_t50ILi8ELi4")
 INSN = re.compile(r"^\s+([a-z][a-z0-9_]+)\b(.*)$")
 LABEL = re.compile(r"^(\.LBB\d+_\d+):")
 WRITELANE = re.compile(r"^\s*(v\d+),")
