@@ -172,6 +172,9 @@ def _prototypes():
         "gto_forward_dynamics": (I, [V, I32, _pd, _pd, _pd, _pd, _pd, _pd, _pi, _pd, _pd, _pi]),
         "gto_track_rollout": (I, [V, I32, I32] + [_pd] * 7 + [D, D, I32] + [_pd] * 6 + [_pi, I32] + [_pd] * 5 + [_pi] * 3),
         "gto_track_rollout_device": (I, [V, I32, I32] + [V] * 4 + [_pd] * 3 + [D, D, I32] + [V] * 6 + [_pi, I32] + [V] * 9),
+        "gto_set_self_pairs": (I, [V, _pi]),
+        "gto_self_clearance": (I, [V, I32, I32, _pd, D, _pd, _pi]),
+        "gto_self_clearance_device": (I, [V, I32, I32, V, D, V, V, V]),
     }
 
 
@@ -197,6 +200,52 @@ def retime_profile(profile="greedy", gap_tol=1e-8, max_newton=None):
         raise ValueError(f"retime: max_newton must be >= 1, got {max_newton}")
     return profile, gap_tol, max_newton
 EXPORTED_SYMBOLS = tuple(PROTOTYPES)
+
+
+def self_pair_rows(mask, n_links):
+    """The words gto_set_self_pairs takes, int32 (L,), of an (L, L) link-pair mask: bit b of word a is mask[a, b].  The
+    library judges symmetry and the diagonal."""
+    m = np.asarray(mask)
+    if m.shape != (n_links, n_links):
+        raise ValueError(f"set_self_pairs: the mask must be ({n_links}, {n_links}), got shape {m.shape}")
+    words = ((m != 0).astype(np.uint64) << np.arange(n_links, dtype=np.uint64)[None, :]).sum(axis=1)
+    return words.astype(np.uint32).view(np.int32)
+
+
+SELF_CHECK_OPTIONS = frozenset(("clearance", "cutoff", "mask", "q_ref"))  # the keys of a self_check= request
+
+
+def self_check_request(desc, spec):
+    """The checked (clearance, cutoff, mask) of a self-clearance request, for every Python layer that takes one.  ``spec``:
+    a dict with any of ``clearance`` (metres, > 0; default: the description's point_spacing(), a property of the sampling),
+    ``cutoff`` (metres, > 0, +inf allowed; default 2 x clearance: beyond it the check reports "far" and costs little),
+    ``mask`` ((L, L) bool; default RobotDesc.self_pairs at ``q_ref`` with this clearance) and ``q_ref`` (ndof,): a pose known
+    to be good, the configs' default_pose, whose close pairs say nothing."""
+    spec = {} if spec is None else dict(spec)
+    if set(spec) - SELF_CHECK_OPTIONS:
+        raise TypeError(f"self_check: unexpected key(s) {sorted(set(spec) - SELF_CHECK_OPTIONS)}")
+    clearance = desc.point_spacing() if spec.get("clearance") is None else float(spec["clearance"])
+    cutoff = 2.0 * clearance if spec.get("cutoff") is None else float(spec["cutoff"])
+    if not clearance > 0 or not cutoff > 0:
+        raise ValueError(f"self_check: clearance and cutoff must be > 0, got {clearance} and {cutoff}")
+    mask = spec.get("mask")
+    if mask is None:
+        mask = desc.self_pairs(q_ref=spec.get("q_ref"), clearance=clearance)
+    self_pair_rows(mask, desc.n_links)  # (the shape)
+    return clearance, cutoff, np.asarray(mask) != 0
+
+
+def self_check_summary(d2, pair, clearance, prefix="self_"):
+    """Per path, from the per-column d2 (B, Tp) and pair (B, Tp, 2) of gto_self_clearance: <prefix>d2 (B,) the smallest d2
+    over the columns (NaN if a column is NaN), <prefix>pair (B, 2) the pair at that column ((-1, -1) for NaN or far) and
+    <prefix>clear (B,) bool: every column's distance is at least ``clearance`` (a NaN column is not clear)."""
+    d2, pair = np.asarray(d2), np.asarray(pair)
+    B = d2.shape[0]
+    bad = np.isnan(d2).any(axis=1)
+    col = np.where(bad, np.isnan(d2).argmax(axis=1), np.where(np.isnan(d2), np.inf, d2).argmin(axis=1))
+    rows = np.arange(B)
+    return {prefix + "d2": d2[rows, col], prefix + "pair": pair[rows, col].astype(np.int32),
+            prefix + "clear": ~bad & (np.sqrt(np.where(np.isnan(d2), 0.0, d2)) >= clearance).all(axis=1)}
 
 
 def retime_torque_limits(desc, tau_max=None, need_inertials=True):
@@ -1048,6 +1097,36 @@ class SolverHandle:
         base, per_plan = self._check_base(base_pos, int(B))
         self._check(self.lib.gto_check_paths_device(self._h, obs._ptr(), int(B), int(Tp), _vp(paths), _p(base, _pd), per_plan,
                                                     _vp(count_out), _vp(stream)), "gto_check_paths_device")
+
+    def set_self_pairs(self, mask):
+        """gto_set_self_pairs: the link pairs self_clearance compares, an (L, L) bool array, symmetric with a false
+        diagonal (RobotDesc.self_pairs builds one); None: back to every pair of distinct links, what a new handle uses."""
+        if mask is None:
+            self._check(self.lib.gto_set_self_pairs(self._h, None), "gto_set_self_pairs")
+            return
+        rows = self_pair_rows(mask, self.desc.n_links)
+        self._check(self.lib.gto_set_self_pairs(self._h, _p(rows, _pi)), "gto_set_self_pairs")
+
+    def self_clearance(self, paths, cutoff=np.inf):
+        """gto_self_clearance: for paths (B, ndof, Tp) the robot's smallest distance from itself at every column, over the
+        pairs of set_self_pairs.  Returns a dict: d2 (B, Tp) float64 squared metres, min(d2, cutoff^2); pair (B, Tp, 2) int32
+        the closest link pair (a < b), (-1, -1) where nothing is closer than the cutoff; dist = sqrt(d2).  A column with a
+        non-finite entry: NaN and (-1, -1)."""
+        paths = _f64(paths)
+        if paths.ndim != 3 or paths.shape[1] != self.desc.ndof or paths.shape[2] < 1:
+            raise GTOError(f"self_clearance: paths must have shape (B, {self.desc.ndof}, Tp >= 1); got {paths.shape}")
+        B, Tp = paths.shape[0], paths.shape[2]
+        d2, pair = np.empty((B, Tp)), np.empty((B, Tp, 2), dtype=np.int32)
+        self._check(self.lib.gto_self_clearance(self._h, B, Tp, _p(paths, _pd), float(cutoff), _p(d2, _pd), _p(pair, _pi)),
+                    "gto_self_clearance")
+        return dict(d2=d2, pair=pair, dist=np.sqrt(d2))
+
+    def self_clearance_device(self, B, Tp, paths, d2_out, pair_out, cutoff=np.inf, stream=None):
+        """gto_self_clearance_device: paths (B, ndof, Tp) float64, d2_out (B, Tp) float64 and pair_out (B, Tp, 2) int32 are
+        device pointers (ints, e.g. torch.Tensor.data_ptr()); one launch on ``stream`` (None: the handle's), no
+        synchronisation and no allocation."""
+        self._check(self.lib.gto_self_clearance_device(self._h, int(B), int(Tp), _vp(paths), float(cutoff), _vp(d2_out),
+                                                       _vp(pair_out), _vp(stream)), "gto_self_clearance_device")
 
     @staticmethod
     def pad_held_points(held_points, n_held=None):

@@ -31,6 +31,8 @@
 #include "gto_seed.h"
 #include "gto_retrieve.h"
 #include "gto_occupancy.h"
+#include "gto_selfcheck.h"
+#include "gto_selfpairs.h"
 #include "gto_owned.h"
 #include "gto_robot.h"
 
@@ -265,6 +267,9 @@ struct gto_handle {
   // the link inertials (gto_set_link_inertials): the table rt_rnea reads; none until the first call
   DevBuf dyn_buf;
   bool has_inertials = false;
+  // the link pairs of gto_self_clearance (gto_set_self_pairs; gto_create: every pair of distinct links): travels as a kernel
+  // argument, so a call in flight keeps the mask it was launched with
+  SelfPairs self_pairs = {};
 
   // the streams and events the handle created; the buffers above free themselves after this (gto_destroy has set the device)
   ~gto_handle() {
@@ -453,6 +458,7 @@ int gto_create(const gto_robot_desc* d, const gto_solver_opts* opts, int device,
   h->opts = *opts;
   h->tu = tu;
   std::memcpy(&h->rb, &rb, sizeof rb);
+  gto_selfpairs::all_distinct_pairs(rb.n_links, h->self_pairs.rows);
   h->pb_C = t->pb_C;
   h->pbchunks = t->pbchunks;
   h->np = np;
@@ -3851,6 +3857,58 @@ int gto_check_plans(gto_handle* h, gto_observation* o, int32_t B, const double* 
   bool empty;
   if (int rc = check_plans_args(h, o, B, plans, base_pos, &empty)) return rc;
   return gto_check_paths(h, o, B, h->opts.T, plans, base_pos, per_plan_base, count_out);
+}
+
+// ---- the robot's clearance from itself (include/gto_solver.h; kernel: gto_selfcheck.h) ----
+int gto_set_self_pairs(gto_handle* h, const int32_t* rows) {
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (!rows) {
+    gto_selfpairs::all_distinct_pairs(h->rb.n_links, h->self_pairs.rows);
+    return GTO_OK;
+  }
+  std::string why;
+  if (int rc = gto_selfpairs::check_self_pairs(h->rb.n_links, rows, why)) return fail(h, rc, why);
+  for (int a = 0; a < GTO_MAX_LINKS; ++a) h->self_pairs.rows[a] = a < h->rb.n_links ? (uint32_t)rows[a] : 0u;
+  return GTO_OK;
+}
+
+int gto_self_clearance_device(gto_handle* h, int32_t B, int32_t Tp, const double* paths, double cutoff, double* d2_out,
+                              int32_t* pair_out, void* stream) {
+  std::string why;
+  if (int rc = gto_selfpairs::check_self_clearance_args(B, Tp, cutoff, why)) return fail(h, rc, why);
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (B == 0) return GTO_OK;
+  if (!paths || !d2_out || !pair_out) return fail(h, GTO_ERR_INVALID_ARG, "gto_self_clearance: null paths, d2_out or pair_out");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  const size_t lds = sizeof(double) * self_clearance_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt, h->rb.n_chunks);
+  if (int rc = check_lds_fits(h, lds)) return rc;
+  const int tg = check_waypoints_per_group();
+  HIPCHK(h, raise_dynamic_lds((const void*)k_self_clearance, lds));
+  hipLaunchKernelGGL(k_self_clearance, dim3((unsigned)B, (unsigned)((Tp + tg - 1) / tg)), dim3(256), lds, st, h->d_rb, h->d_px, h->d_py, h->d_pz,
+                     h->d_chunks, (int)Tp, tg, paths, h->self_pairs, cutoff, d2_out, pair_out);
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
+}
+
+int gto_self_clearance(gto_handle* h, int32_t B, int32_t Tp, const double* paths, double cutoff, double* d2_out,
+                       int32_t* pair_out) {
+  std::string why;
+  if (int rc = gto_selfpairs::check_self_clearance_args(B, Tp, cutoff, why)) return fail(h, rc, why);
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (B == 0) return GTO_OK;
+  if (!paths || !d2_out || !pair_out) return fail(h, GTO_ERR_INVALID_ARG, "gto_self_clearance: null paths, d2_out or pair_out");
+  HIPCHK(h, hipSetDevice(h->device));
+  Staging io(h);
+  const double* d_paths;
+  double* d_d2;
+  int32_t* d_pair;
+  int rc;
+  if ((rc = io.in(paths, (size_t)B * h->rb.ndof * Tp, &d_paths))) return rc;
+  if ((rc = io.out(d2_out, (size_t)B * Tp, &d_d2))) return rc;
+  if ((rc = io.out(pair_out, (size_t)B * Tp * 2, &d_pair))) return rc;
+  if ((rc = gto_self_clearance_device(h, B, Tp, d_paths, cutoff, d_d2, d_pair, nullptr))) return rc;
+  return io.finish();
 }
 
 // What gto_check_held_paths and its device variant check before any device work (host-side facts only).  *empty: B = 0.

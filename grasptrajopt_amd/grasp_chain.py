@@ -126,7 +126,7 @@ class GraspChain:
     # ------------------------------------------------------------------ the chain
     def plan_objects(self, qc, ik_goals, plan_goals, n_grasps, fields, base_position, axis_standoff="x", use_standoff=True,
                      interpolate=True, pos_tol=0.01, rot_tol_deg=5.0, ik_collision_threshold=5.0, float32_solutions=True,
-                     observation=None, retime=None, n_seeds=1, max_points=5, retrieve=None, track=None):
+                     observation=None, retime=None, n_seeds=1, max_points=5, retrieve=None, track=None, self_check=None):
         """B objects with up to n_max candidate grasps each.
 
         qc (B, ndof) or (ndof,); ik_goals, plan_goals (B, n_max, 4, 4): the poses IK is solved to and the poses the plan
@@ -158,6 +158,15 @@ class GraspChain:
         -- which the controller knows unless ``model_payload`` says otherwise.  The result gains track_err_max,
         track_err_end, track_sat_steps, track_status (B,) and, with retrieve, the four retrieve_track_*.  The chain keeps the
         samples the rollout reads in its own device buffers.  track=None leaves the chain launch for launch what it is.
+        self_check: a dict ``[clearance, cutoff, mask, q_ref]`` (``_capi.self_check_request``; {} for the defaults) to
+        measure the robot's clearance from ITSELF along the selected plan and, with retrieve, along the retrieve path
+        (gto_self_clearance_device, one launch each on the chain's stream in front of the one synchronisation).  The result
+        gains self_d2 (B,) (the smallest squared distance over the plan's waypoints, metres^2, at most cutoff^2; NaN for a
+        plan with a non-finite waypoint), self_pair (B, 2) (the closest link pair there, (-1, -1) when far), self_clear (B,)
+        (every waypoint at least ``clearance`` away) and their retrieve_self_* counterparts.  plan_class and the selection
+        do not read them.  Like the retime and retrieve results, the keys are absent when the call holds no candidate grasp
+        at all (B * n_max = 0): nothing was solved, so nothing is checked.  self_check=None leaves the chain launch for
+        launch what it is.
 
         Returns a namespace: plans (B, ndof, T), dQ (B, ndof, T-1), cost, iters, status (B,), n_accepted (B,) (0: no
         feasible grasp, the driver's ``continue``; the plan is then the solve from the constant seed to all goals),
@@ -184,7 +193,8 @@ class GraspChain:
                     self._up("n_grasps", n_grasps, np.int32), {})
 
         return self._plan(B, n_max, feed, qc, fields, base_position, axis_standoff, use_standoff, interpolate, pos_tol, rot_tol_deg,
-                          ik_collision_threshold, float32_solutions, observation, retime, n_seeds, max_points, retrieve, track)
+                          ik_collision_threshold, float32_solutions, observation, retime, n_seeds, max_points, retrieve, track,
+                          self_check)
 
     def retrieve_spec(self, retrieve):
         """A ``retrieve`` dict with its defaults filled in: mode "lift" (straight up by ``distance`` = 0.3 m in ``steps`` = 10
@@ -292,7 +302,8 @@ class GraspChain:
         return n_grasps
 
     def _plan(self, B, n_max, feed, qc, fields, base_position, axis_standoff, use_standoff, interpolate, pos_tol, rot_tol_deg,
-              ik_collision_threshold, float32_solutions, observation, retime, n_seeds, max_points, retrieve=None, track=None):
+              ik_collision_threshold, float32_solutions, observation, retime, n_seeds, max_points, retrieve=None, track=None,
+              self_check=None):
         """What ``plan_objects`` and ``plan_grasps`` share: the chain from the goal sets on.  ``feed(stream, d_base)`` is called
         on the chain's stream behind the uploads of scene ids, qc and base; it returns the device arrays ik_goals, plan_goals
         (B, n_max, 16), n_grasps (B,) -- uploaded, or written by launches it enqueued -- and a dict of further device arrays
@@ -348,7 +359,18 @@ class GraspChain:
                                    sat_steps=outs["sat_steps"].data_ptr(), status_out=outs["status"].data_ptr(), stream=st, **tr["ctl"])
             return {tag + k: v for k, v in outs.items()}
 
+        sc = None if self_check is None else _capi.self_check_request(d, self_check)  # before anything is enqueued
+        d_self = {}  # the per-column results of the self-clearance launches: prefix -> (d2, pair)
+
+        def self_clearance(prefix, cols, d_paths):
+            """One gto_self_clearance_device on the chain's stream behind whatever wrote d_paths (B, ndof, cols)."""
+            d_d2, d_pair = self._dev(prefix + "d2_cols", (B, cols), f64), self._dev(prefix + "pair_cols", (B, cols, 2), i32)
+            h.self_clearance_device(B, cols, d_paths.data_ptr(), d_d2.data_ptr(), d_pair.data_ptr(), cutoff=sc[1], stream=st)
+            d_self[prefix] = (d_d2, d_pair)
+
         tracked = {}
+        if sc is not None:
+            h.set_self_pairs(sc[2])  # (a host fact of the handle: the launches below carry it as an argument)
         with torch.cuda.stream(self.stream):
             st = self.stream.cuda_stream
             d_sid, d_qc, d_base = self._up("sid", sid, np.int32), self._up("qc", qc, np.float64), self._up("base", base, np.float64)
@@ -441,6 +463,8 @@ class GraspChain:
                     h.select_plans_device(M, 1, *sel, class_out=d_scls.data_ptr(), stream=st)  # every slot on its own: its class
                     h.select_plans_device(B, K, *sel, Q=d_Qs.data_ptr(), dQ=d_dQs.data_ptr(), best_slot_out=d_best.data_ptr(),
                                           class_out=d_cls.data_ptr(), Q_out=d_Q.data_ptr(), dQ_out=d_dQ.data_ptr(), stream=st)
+                if sc is not None:  # the selected plan
+                    self_clearance("self_", T, d_Q)
                 if retrieve is not None:
                     lift = rs["mode"] == "lift"
                     cols = int(rs["steps"]) + 1 if lift else h.retrieve_path_columns()
@@ -455,6 +479,8 @@ class GraspChain:
                                                reached_out=d_rreach.data_ptr(), stream=st)
                     else:
                         h.retrieve_reverse(B, d_Q.data_ptr(), rs["closed_joints"], rs["closed_value"], d_rp.data_ptr(), stream=st)
+                    if sc is not None:
+                        self_clearance("retrieve_self_", cols, d_rp)
                     if observation is not None:
                         d_rcnt = self._dev("retrieve_counts", (B, cols), i32)
                         h.check_paths_device(observation, B, cols, d_rp.data_ptr(), d_rcnt.data_ptr(), base_pos=base, stream=st)
@@ -533,6 +559,8 @@ class GraspChain:
                        accept=d_acc)
             out.update(extra)
             out.update(tracked)
+            for prefix, (d_d2, d_pair) in d_self.items():
+                out["_" + prefix + "d2_cols"], out["_" + prefix + "pair_cols"] = d_d2, d_pair
             if d_cnt is not None:
                 out["counts"] = d_cnt
             if N and retime is not None:
@@ -562,7 +590,12 @@ class GraspChain:
                 host[k].copy_(v, non_blocking=True)
         self.stream.synchronize()  # the one host synchronisation of the call
         for k, v in host.items():
-            setattr(res, k, v.numpy().copy())
+            if not k.startswith("_"):
+                setattr(res, k, v.numpy().copy())
+        for prefix in d_self:  # per plan: the closest column's d2 and pair, and whether every column is clear
+            found = _capi.self_check_summary(host["_" + prefix + "d2_cols"].numpy(), host["_" + prefix + "pair_cols"].numpy(), sc[0], prefix)
+            for k, v in found.items():
+                setattr(res, k, v.copy())
         res.accept = res.accept.astype(bool)
         if float32_solutions:
             res.q_solutions = res.q_solutions.astype(np.float32)

@@ -120,10 +120,17 @@ class GTOPlanner:
         return (solution[f"{self.robot_name}/q"].toarray(), solution[f"{self.robot_name}/dq"].toarray(),
                 solution["f"].toarray().flatten())
 
+    def self_clearance(self, plan, clearance=None, cutoff=None, mask=None, q_ref=None):
+        """The robot's distance from itself at every waypoint of a solved ``plan`` (ndof, T) or (B, ndof, T):
+        ``utils.self_clearance`` (dict d2, dist, pair, clear).  The solve has no self-collision term: a plan whose wrist
+        passes through the base is found here, not by the solver."""
+        from .utils import self_clearance
+        return self_clearance(self.robot, plan, clearance=clearance, cutoff=cutoff, mask=mask, q_ref=q_ref)
+
     def retrieve_path(self, plan, mode="lift", distance=0.3, steps=10, direction=(0.0, 0.0, 1.0), closed_joints=None,
                       closed_value=0.0, max_iter=50, pos_tol=0.01, rot_tol_deg=5.0, retime=None, observation=None,
                       held_points=None, n_held=None, object_pose=None, labels=None, held_label=None,
-                      base_position=(0.0, 0.0, 0.0), track=None):
+                      base_position=(0.0, 0.0, 0.0), track=None, self_check=None):
         """The motion after the grasp (examples/pybullet_gto_planning.py:301-313) for a solved ``plan`` (ndof, T), or
         (B, ndof, T) for B of them: mode "lift" moves link_ee by ``distance`` along ``direction`` in ``steps`` IK steps, each
         seeded from the one before, with the gripper's pose held (the tabletop driver's env.retract; pybullet's position-only
@@ -148,12 +155,18 @@ class GTOPlanner:
         keywords of ``utils.track_trajectories``) to also roll the retimed trajectory forward under that joint controller
         (gto_track_rollout); it needs ``retime``.  model_payload and plant_payload default to the retime's payload, on
         link_ee.  The trajectory dict gains ``track_q, track_qd, track_t, track_err_max, track_err_end, track_sat_steps,
-        track_steps, track_status``."""
+        track_steps, track_status``.
+        self_check: a dict ``[clearance, cutoff, mask, q_ref]`` (``_capi.self_check_request``; {} for the defaults) to also
+        measure the robot's clearance from itself along the path (gto_self_clearance).  The dict at the end of the return
+        value -- the one that holds held_counts, added if there is none -- gains ``self_d2`` (the smallest squared distance
+        over the columns), ``self_pair`` (2,) and ``self_clear`` per plan."""
         from . import _capi
         from .grasp_chain import finger_joints
         plan = np.asarray(plan, dtype=np.float64)
         single = plan.ndim == 2
         plans = np.ascontiguousarray(plan.reshape(-1, self.robot.ndof, self.T))
+        if self_check is not None:  # checked before the handle is made
+            self_check = _capi.self_check_request(self.robot.desc, self_check)
         torque = None  # a torque request is checked before the handle is made: (tau_max, payload dict)
         if retime is not None and retime.get("profile") == "torque":
             _capi.payload_arrays(retime.get("payload"), plans.shape[0])
@@ -206,6 +219,11 @@ class GTOPlanner:
             counts = h.check_held_paths(as_observation(observation), path, held_points, n_held=n_held, attach=attach,
                                         object_pose=pose, labels=labels, held_label=held_label, base_pos=base)
             checks = ({"held_counts": counts[0] if single else counts},)
+        if self_check is not None:
+            h.set_self_pairs(self_check[2])
+            sc = h.self_clearance(path, cutoff=self_check[1])
+            found = _capi.self_check_summary(sc["d2"], sc["pair"], self_check[0])
+            checks = (dict(checks[0] if checks else {}, **{k: v[0] if single else v for k, v in found.items()}),)
         if retime is None:
             return ((path[0], int(reached[0])) if single else (path, reached)) + checks
         unknown = set(retime) - {"vmax", "amax", "subdiv", "n_samples", "reached_only", "profile", "gap_tol", "max_newton", "tau_max", "payload"}

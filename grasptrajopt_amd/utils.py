@@ -308,6 +308,27 @@ def retime_paths(robot, paths, n_cols=None, vlim=None, alim=0.5, subdiv: int = 2
     return h.retime_paths(paths, vlim, alim, n_cols=n_cols, subdiv=subdiv, n_samples=n_samples)
 
 
+def self_clearance(robot, plans, clearance=None, cutoff=None, mask=None, q_ref=None):
+    """The robot's distance from itself along ``plans`` (B, ndof, Tp) or (ndof, Tp), any Tp >= 1, on the GPU
+    (gto_self_clearance): what the reference learns when PyBullet executes a plan that folds the arm into itself
+    (examples/pybullet_gto_planning.py:301).  clearance: metres, default the description's point_spacing(); cutoff: default
+    2 x clearance (distances beyond it are reported as the cutoff, with pair (-1, -1)); mask: (L, L) bool link pairs,
+    default ``RobotDesc.self_pairs(q_ref, clearance)``; q_ref: a pose known to be good, e.g. the config's default_pose.
+    Returns a dict: d2 (squared metres), dist, pair (.., 2), clear = dist >= clearance (a column with a non-finite entry
+    has d2 = NaN and is not clear)."""
+    from ._capi import self_check_request
+    plans = np.asarray(plans, dtype=np.float64)
+    single = plans.ndim == 2
+    paths = np.ascontiguousarray(plans.reshape(-1, robot.desc.ndof, plans.shape[-1]))
+    clearance, cutoff, mask = self_check_request(robot.desc, dict(clearance=clearance, cutoff=cutoff, mask=mask, q_ref=q_ref))
+    h = _retime_handle(robot, 50)
+    h.set_self_pairs(mask)
+    out = h.self_clearance(paths, cutoff=cutoff)
+    with np.errstate(invalid="ignore"):
+        out["clear"] = out["dist"] >= clearance
+    return {k: v[0] for k, v in out.items()} if single else out
+
+
 def inverse_dynamics(robot, q, qd, qdd, payload=None, link_ee=None):
     """Joint forces tau = M(q) qdd + C(q, qd) qd + g(q) of states (n, ndof) or one state (ndof,) on the GPU
     (gto_inverse_dynamics, include/gto_solver.h): recursive Newton-Euler over the robot's frames with the link inertials of

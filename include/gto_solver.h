@@ -1181,6 +1181,34 @@ int gto_track_rollout_device(gto_handle* h, int32_t B, int32_t M, const double* 
                              const int32_t* locked /*HOST*/, int32_t Mo, double* q_out, double* qd_out, double* t_out,
                              double* err_max, double* err_end, int32_t* sat_steps, int32_t* steps, int32_t* status_out,
                              void* stream);
+/*
+ * The robot's clearance from itself along a path.  Every other check judges a plan against the scene; the solver has no
+ * self-collision term and neither has the reference, where a plan that folds the arm into itself shows only when PyBullet
+ * executes it (examples/pybullet_gto_planning.py:301): these replace nothing there.  Additions (the ABI number stays).
+ * For a column q_t of a path, the handle's pair mask M (symmetric, zero diagonal) and a cutoff c in metres (+inf allowed):
+ *   d2(t) = min over points p of link a, p' of link b, a < b, M[a][b] set, of |X_p(q_t) - X_p'(q_t)|^2
+ * X is gto_eval_points' world point at base 0 (the base cancels), bit for bit, and the squared distance is
+ * (dx*dx + dy*dy) + dz*dz in FP64 without contraction: squared metres on purpose, a pure function of products and sums.
+ *   d2_out   [B][Tp]     min(d2, c*c)
+ *   pair_out [B][Tp][2]  the closest link pair (a, b), a < b; of two pairs at the same d2 the lexicographically smaller;
+ *                        (-1, -1) when nothing is closer than the cutoff or no pair is enabled (d2_out is c*c then)
+ * A column with a non-finite entry gives d2_out = NaN and pair_out = (-1, -1) and changes no other column.  Every column's
+ * result is bit for bit the same in any batch, at any position, whatever the cutoff culls and whatever the number of
+ * columns a workgroup takes (GTO_CHECK_TG): the sphere tests only ever drop pairs that are strictly farther than the answer.
+ *   gto_set_self_pairs   rows [n_links] HOST: bit b of rows[a] enables the pair (a, b) (the 32 bits of an unsigned word; the
+ *                        header types it int32_t).  GTO_ERR_INVALID_ARG, before any device call and with the handle's mask
+ *                        unchanged, for a bit at or above n_links, a set diagonal bit or an asymmetric mask.  NULL: back to
+ *                        the mask a new handle has, every pair of distinct links.  Calls already enqueued keep their mask.
+ *   paths [B][ndof][Tp], Tp >= 1, as gto_check_paths takes them.  B = 0: GTO_OK without a launch.  Tp < 1, B < 0, a NaN or
+ *   non-positive cutoff, a null array: GTO_ERR_INVALID_ARG before any device call.  Works on every handle, whatever its T.
+ * gto_self_clearance takes HOST arrays and is synchronous.  gto_self_clearance_device takes DEVICE arrays: one launch on
+ * `stream` (NULL = the handle's), no synchronisation, no allocation, no workspace on the handle.
+ */
+int gto_set_self_pairs(gto_handle* h, const int32_t* rows /*[n_links] HOST*/);
+int gto_self_clearance(gto_handle* h, int32_t B, int32_t Tp, const double* paths, double cutoff, double* d2_out,
+                       int32_t* pair_out);
+int gto_self_clearance_device(gto_handle* h, int32_t B, int32_t Tp, const double* paths, double cutoff, double* d2_out,
+                              int32_t* pair_out, void* stream);
 
 #ifdef __cplusplus
 }
