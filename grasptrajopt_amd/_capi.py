@@ -175,6 +175,8 @@ def _prototypes():
         "gto_set_self_pairs": (I, [V, _pi]),
         "gto_self_clearance": (I, [V, I32, I32, _pd, D, _pd, _pi]),
         "gto_self_clearance_device": (I, [V, I32, I32, V, D, V, V, V]),
+        "gto_held_clearance": (I, [V, I32, I32, _pd, _pd, I32, I32, _pd, I32, _pi, _pd, _pd, I32, I32, D, _pd, _pi, _pi]),
+        "gto_held_clearance_device": (I, [V, I32, I32, V, V, I32, I32, V, I32, V, V, _pd, I32, I32, D, V, V, V, V]),
     }
 
 
@@ -245,6 +247,57 @@ def self_check_summary(d2, pair, clearance, prefix="self_"):
     col = np.where(bad, np.isnan(d2).argmax(axis=1), np.where(np.isnan(d2), np.inf, d2).argmin(axis=1))
     rows = np.arange(B)
     return {prefix + "d2": d2[rows, col], prefix + "pair": pair[rows, col].astype(np.int32),
+            prefix + "clear": ~bad & (np.sqrt(np.where(np.isnan(d2), 0.0, d2)) >= clearance).all(axis=1)}
+
+
+def held_link_mask(links, n_links):
+    """The link_mask word of gto_held_clearance (a Python int, the bits of an unsigned 32-bit word as int32) of an (L,)
+    bool array of enabled collision links."""
+    m = np.asarray(links)
+    if m.shape != (n_links,):
+        raise ValueError(f"held_clearance: links must be ({n_links},), got shape {m.shape}")
+    word = sum(1 << l for l in range(n_links) if m[l])
+    return int(np.array([word], dtype=np.uint32).view(np.int32)[0])
+
+
+HELD_CLEARANCE_OPTIONS = frozenset(("clearance", "cutoff", "links", "ignore"))  # the keys of a held_clearance= request
+
+
+def held_clearance_request(desc, link_ee, spec):
+    """The checked (clearance, cutoff, links) of a held-clearance request, for every Python layer that takes one.  ``spec``:
+    a dict with any of ``clearance`` (metres, > 0; default: the description's point_spacing()), ``cutoff`` (metres, > 0,
+    +inf allowed; default 2 x clearance: beyond it the check reports "far" and costs little), ``links`` ((L,) bool, the
+    collision links the held object is measured against; default RobotDesc.held_links(link_ee, ignore)) and ``ignore``
+    (link names the default leaves out)."""
+    spec = {} if spec is None else dict(spec)
+    if set(spec) - HELD_CLEARANCE_OPTIONS:
+        raise TypeError(f"held_clearance: unexpected key(s) {sorted(set(spec) - HELD_CLEARANCE_OPTIONS)}")
+    clearance = desc.point_spacing() if spec.get("clearance") is None else float(spec["clearance"])
+    cutoff = 2.0 * clearance if spec.get("cutoff") is None else float(spec["cutoff"])
+    if not clearance > 0 or not cutoff > 0:
+        raise ValueError(f"held_clearance: clearance and cutoff must be > 0, got {clearance} and {cutoff}")
+    links = spec.get("links")
+    if links is None:
+        links = desc.held_links(link_ee, ignore=spec.get("ignore") or ())
+    elif spec.get("ignore"):
+        links = np.array(links, dtype=bool)
+        links[[desc.link_names.index(n) for n in spec["ignore"]]] = False
+    held_link_mask(links, desc.n_links)  # (the shape)
+    return clearance, cutoff, np.asarray(links) != 0
+
+
+def held_clearance_summary(d2, link, point, clearance, prefix="held_self_"):
+    """Per path, from the per-column d2, link and point (B, Tp) of gto_held_clearance: <prefix>d2 (B,) the smallest d2 over
+    the columns (NaN if a column is NaN), <prefix>col (B,) that column (the first NaN column of a path with one),
+    <prefix>link and <prefix>point (B,) the link and the held point there (-1 for NaN or far) and <prefix>clear (B,) bool:
+    every column's distance is at least ``clearance`` (a NaN column is not clear)."""
+    d2, link, point = np.asarray(d2), np.asarray(link), np.asarray(point)
+    B = d2.shape[0]
+    bad = np.isnan(d2).any(axis=1)
+    col = np.where(bad, np.isnan(d2).argmax(axis=1), np.where(np.isnan(d2), np.inf, d2).argmin(axis=1))
+    rows = np.arange(B)
+    return {prefix + "d2": d2[rows, col], prefix + "col": col.astype(np.int32), prefix + "link": link[rows, col].astype(np.int32),
+            prefix + "point": point[rows, col].astype(np.int32),
             prefix + "clear": ~bad & (np.sqrt(np.where(np.isnan(d2), 0.0, d2)) >= clearance).all(axis=1)}
 
 
@@ -1145,6 +1198,27 @@ class SolverHandle:
         counts = _i32(np.broadcast_to(np.asarray(pts.shape[1] if n_held is None else n_held), (pts.shape[0],)))
         return pts, counts
 
+    def _held_inputs(self, who, paths, held_points, n_held, attach, attach_col, object_pose, base_pos):
+        """The checked host arrays the held-point entry points share: (paths, points, counts, attach, attach_ld, attach_col,
+        pose, base, per_plan_base)."""
+        paths = _f64(paths)
+        if paths.ndim != 3 or paths.shape[1] != self.desc.ndof or paths.shape[2] < 1:
+            raise GTOError(f"{who}: paths must have shape (B, {self.desc.ndof}, Tp >= 1); got {paths.shape}")
+        B = paths.shape[0]
+        pts, counts = self.pad_held_points(held_points, n_held)
+        if pts.shape[0] != B or counts.shape != (B,):
+            raise GTOError(f"{who}: one point set and one count per path ({B}); got {pts.shape[0]}, {counts.shape}")
+        ld = col = 0
+        if attach is not None:
+            attach = _f64(attach)
+            if attach.ndim != 3 or attach.shape[:2] != (B, self.desc.ndof):
+                raise GTOError(f"{who}: attach must have shape ({B}, {self.desc.ndof}, ld); got {attach.shape}")
+            ld = attach.shape[2]
+            col = ld - 1 if attach_col is None else int(attach_col)
+        pose = None if object_pose is None else _f64(object_pose).reshape(B, 16)
+        base, per_plan = self._check_base(base_pos, B)
+        return paths, pts, counts, attach, ld, col, pose, base, per_plan
+
     def check_held_paths(self, obs, paths, held_points, n_held=None, attach=None, attach_col=None, object_pose=None, labels=None,
                          held_label=None, base_pos=(0.0, 0.0, 0.0)):
         """gto_check_held_paths: for paths (B, ndof, Tp) the number of plan b's held points inside the observation ``obs`` at
@@ -1153,24 +1227,11 @@ class SolverHandle:
         n_held: see ``pad_held_points``; world points at the moment of the grasp, or object-frame points with
         object_pose (B, 4, 4).  labels (H, W) int32 with held_label (B,) or one label: pixels of a depth observation that
         show the held object hide nothing that was seen.  -1: a column, q_att, base or object pose with a non-finite entry."""
-        paths = _f64(paths)
-        if paths.ndim != 3 or paths.shape[1] != self.desc.ndof or paths.shape[2] < 1:
-            raise GTOError(f"check_held_paths: paths must have shape (B, {self.desc.ndof}, Tp >= 1); got {paths.shape}")
+        paths, pts, counts, attach, ld, col, pose, base, per_plan = self._held_inputs("check_held_paths", paths, held_points, n_held,
+                                                                                      attach, attach_col, object_pose, base_pos)
         B, Tp = paths.shape[0], paths.shape[2]
-        pts, counts = self.pad_held_points(held_points, n_held)
-        if pts.shape[0] != B or counts.shape != (B,):
-            raise GTOError(f"check_held_paths: one point set and one count per path ({B}); got {pts.shape[0]}, {counts.shape}")
-        ld = col = 0
-        if attach is not None:
-            attach = _f64(attach)
-            if attach.ndim != 3 or attach.shape[:2] != (B, self.desc.ndof):
-                raise GTOError(f"check_held_paths: attach must have shape ({B}, {self.desc.ndof}, ld); got {attach.shape}")
-            ld = attach.shape[2]
-            col = ld - 1 if attach_col is None else int(attach_col)
-        pose = None if object_pose is None else _f64(object_pose).reshape(B, 16)
         lab = None if labels is None else _i32(labels)
         hl = None if held_label is None else _per_instance(held_label, B)
-        base, per_plan = self._check_base(base_pos, B)
         count = np.empty((B, Tp), dtype=np.int32)
         self._check(self.lib.gto_check_held_paths(self._h, obs._ptr(), B, Tp, _p(paths, _pd), _p(attach, _pd), ld, col, _p(pts, _pd),
                                                   pts.shape[1], _p(counts, _pi), _p(pose, _pd), _p(lab, _pi), _p(hl, _pi),
@@ -1188,6 +1249,38 @@ class SolverHandle:
                                                          int(attach_col), _vp(held_points), int(P_max), _vp(n_held),
                                                          _vp(object_pose), _vp(labels), _vp(held_label), _p(base, _pd), per_plan,
                                                          _vp(count_out), _vp(stream)), "gto_check_held_paths_device")
+
+    def held_clearance(self, paths, held_points, n_held=None, attach=None, attach_col=None, object_pose=None,
+                       base_pos=(0.0, 0.0, 0.0), links=None, cutoff=np.inf):
+        """gto_held_clearance: for paths (B, ndof, Tp) the smallest distance between plan b's held points and the surface
+        points of the collision links ``links`` ((L,) bool; None: every link) at every column, the points carried rigidly with
+        link_ee as in ``check_held_paths`` (same paths, held_points / n_held, attach / attach_col, object_pose, base_pos).
+        Returns a dict: d2 (B, Tp) float64 squared metres, min(d2, cutoff^2); link and point (B, Tp) int32, the closest link
+        and held point, -1 where nothing is closer than the cutoff; dist = sqrt(d2).  NaN and -1: a column, q_att, base or
+        object pose with a non-finite entry."""
+        paths, pts, counts, attach, ld, col, pose, base, per_plan = self._held_inputs("held_clearance", paths, held_points, n_held,
+                                                                                      attach, attach_col, object_pose, base_pos)
+        B, Tp = paths.shape[0], paths.shape[2]
+        mask = held_link_mask(np.ones(self.desc.n_links, dtype=bool) if links is None else links, self.desc.n_links)
+        d2, link, point = np.empty((B, Tp)), np.empty((B, Tp), dtype=np.int32), np.empty((B, Tp), dtype=np.int32)
+        self._check(self.lib.gto_held_clearance(self._h, B, Tp, _p(paths, _pd), _p(attach, _pd), ld, col, _p(pts, _pd), pts.shape[1],
+                                                _p(counts, _pi), _p(pose, _pd), _p(base, _pd), per_plan, mask, float(cutoff),
+                                                _p(d2, _pd), _p(link, _pi), _p(point, _pi)), "gto_held_clearance")
+        return dict(d2=d2, link=link, point=point, dist=np.sqrt(d2))
+
+    def held_clearance_device(self, B, Tp, paths, held_points, P_max, n_held, d2_out, link_out=None, point_out=None, attach=None,
+                              attach_ld=0, attach_col=0, object_pose=None, base_pos=(0.0, 0.0, 0.0), links=None, cutoff=np.inf,
+                              stream=None):
+        """gto_held_clearance_device: paths (B, ndof, Tp), attach, held_points (B, P_max, 3), n_held (B,) int32, object_pose
+        (B, 16), d2_out (B, Tp) float64, link_out and point_out (B, Tp) int32 are device pointers (or None where the header
+        allows NULL); base_pos and links ((L,) bool; None: every link) are host values; two launches on ``stream`` without a
+        host synchronisation."""
+        base, per_plan = self._check_base(base_pos, int(B))
+        mask = held_link_mask(np.ones(self.desc.n_links, dtype=bool) if links is None else links, self.desc.n_links)
+        self._check(self.lib.gto_held_clearance_device(self._h, int(B), int(Tp), _vp(paths), _vp(attach), int(attach_ld), int(attach_col),
+                                                       _vp(held_points), int(P_max), _vp(n_held), _vp(object_pose), _p(base, _pd),
+                                                       per_plan, mask, float(cutoff), _vp(d2_out), _vp(link_out), _vp(point_out),
+                                                       _vp(stream)), "gto_held_clearance_device")
 
     # -------------------------------------------------------------- the motion after the grasp
     @staticmethod

@@ -33,6 +33,8 @@
 #include "gto_occupancy.h"
 #include "gto_selfcheck.h"
 #include "gto_selfpairs.h"
+#include "gto_heldclear.h"
+#include "gto_heldargs.h"
 #include "gto_owned.h"
 #include "gto_robot.h"
 
@@ -4009,6 +4011,81 @@ int gto_check_held_paths(gto_handle* h, gto_observation* o, int32_t B, int32_t T
   if ((rc = io.out(count_out, nB * Tp, &d_count))) return rc;
   if ((rc = gto_check_held_paths_device(h, o, B, Tp, d_paths, d_attach, attach_ld, attach_col, d_points, P_max, d_nheld, d_pose, d_labels, d_lab,
                                         base_pos, per_plan_base, d_count, nullptr)))
+    return rc;
+  return io.finish();
+}
+
+// The held object's clearance from the robot's own links (include/gto_solver.h; kernels: gto_held.h, gto_heldclear.h)
+int gto_held_clearance_device(gto_handle* h, int32_t B, int32_t Tp, const double* paths, const double* attach, int32_t attach_ld,
+                              int32_t attach_col, const double* held_points, int32_t P_max, const int32_t* n_held,
+                              const double* object_pose, const double* base_pos, int32_t per_plan_base, int32_t link_mask,
+                              double cutoff, double* d2_out, int32_t* link_out, int32_t* point_out, void* stream) {
+  std::string why;
+  bool empty;
+  if (int rc = gto_heldargs::check_held_clearance_args(h ? h->rb.n_links : GTO_MAX_LINKS, B, Tp, paths, attach, attach_ld, attach_col,
+                                                       held_points, P_max, n_held, base_pos, link_mask, cutoff, d2_out, why, &empty))
+    return fail(h, rc, why);
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (empty) return GTO_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  const int T = Tp, P = P_max;
+  const size_t lds_att = sizeof(double) * held_attach_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt);
+  const size_t lds = sizeof(double) * held_clearance_lds_doubles(h->rb.n_frames, h->rb.n_links, h->rb.n_opt, h->rb.n_chunks);
+  CheckBase base;
+  int rc;
+  if ((rc = check_lds_fits(h, lds_att)) || (rc = check_lds_fits(h, lds))) return rc;
+  if ((rc = stage_check_base(h, base_pos, per_plan_base, B, st, &base))) return rc;
+  if ((rc = ensure(h, h->hd_p, (size_t)B * P * 3 * sizeof(double)))) return rc;
+  if ((rc = ensure(h, h->hd_bad, (size_t)B * sizeof(int32_t)))) return rc;
+  double* d_p = h->hd_p.as<double>();
+  int32_t* d_bad = h->hd_bad.as<int32_t>();
+  // attach NULL: the paths' own column 0, as in gto_check_held_paths_device
+  const double* att = attach ? attach : paths;
+  const int att_ld = attach ? attach_ld : T, att_col = attach ? attach_col : 0;
+  const int tg = check_waypoints_per_group();
+  HIPCHK(h, raise_dynamic_lds((const void*)k_held_attach, lds_att));
+  HIPCHK(h, raise_dynamic_lds((const void*)k_held_clearance, lds));
+  hipLaunchKernelGGL(k_held_attach, dim3((unsigned)B), dim3(256), lds_att, st, h->d_rb, att, att_ld, att_col, base.b0, base.b1, base.b2, base.d_base,
+                     held_points, P, n_held, object_pose, d_p, d_bad);
+  hipLaunchKernelGGL(k_held_clearance, dim3((unsigned)B, (unsigned)((T + tg - 1) / tg)), dim3(256), lds, st, h->d_rb, h->d_px, h->d_py, h->d_pz,
+                     h->d_chunks, T, tg, paths, (const double*)d_p, P, n_held, (const int32_t*)d_bad, (uint32_t)link_mask, cutoff, d2_out,
+                     link_out, point_out);
+  HIPCHK(h, hipGetLastError());
+  return GTO_OK;
+}
+
+int gto_held_clearance(gto_handle* h, int32_t B, int32_t Tp, const double* paths, const double* attach, int32_t attach_ld,
+                       int32_t attach_col, const double* held_points, int32_t P_max, const int32_t* n_held, const double* object_pose,
+                       const double* base_pos, int32_t per_plan_base, int32_t link_mask, double cutoff, double* d2_out,
+                       int32_t* link_out, int32_t* point_out) {
+  std::string why;
+  bool empty;
+  if (int rc = gto_heldargs::check_held_clearance_args(h ? h->rb.n_links : GTO_MAX_LINKS, B, Tp, paths, attach, attach_ld, attach_col,
+                                                       held_points, P_max, n_held, base_pos, link_mask, cutoff, d2_out, why, &empty))
+    return fail(h, rc, why);
+  if (!h) return GTO_ERR_INVALID_ARG;
+  if (empty) return GTO_OK;
+  for (int b = 0; b < B; ++b)
+    if (n_held[b] < 0 || n_held[b] > P_max) return fail(h, GTO_ERR_INVALID_ARG, "gto_held_clearance: n_held must be in [0, P_max]");
+  HIPCHK(h, hipSetDevice(h->device));
+  Staging io(h);
+  const size_t nB = (size_t)B, nd = (size_t)h->rb.ndof;
+  const double *d_paths, *d_attach, *d_points, *d_pose;
+  const int32_t* d_nheld;
+  double* d_d2;
+  int32_t *d_link, *d_point;
+  int rc;
+  if ((rc = io.in(paths, nB * nd * Tp, &d_paths))) return rc;
+  if ((rc = io.in(attach, attach ? nB * nd * attach_ld : 0, &d_attach))) return rc;
+  if ((rc = io.in(held_points, nB * P_max * 3, &d_points))) return rc;
+  if ((rc = io.in(n_held, nB, &d_nheld))) return rc;
+  if ((rc = io.in(object_pose, nB * 16, &d_pose))) return rc;
+  if ((rc = io.out(d2_out, nB * Tp, &d_d2))) return rc;
+  if ((rc = io.out(link_out, link_out ? nB * Tp : 0, &d_link))) return rc;
+  if ((rc = io.out(point_out, point_out ? nB * Tp : 0, &d_point))) return rc;
+  if ((rc = gto_held_clearance_device(h, B, Tp, d_paths, d_attach, attach_ld, attach_col, d_points, P_max, d_nheld, d_pose, base_pos,
+                                      per_plan_base, link_mask, cutoff, d_d2, d_link, d_point, nullptr)))
     return rc;
   return io.finish();
 }

@@ -146,7 +146,12 @@ class GraspChain:
         steps that reached their goal; reverse: n), retrieve_status (B, steps) (reverse: (B, 0)) and, with an observation,
         retrieve_counts (B, columns); with an observation and ``held_points`` in the retrieve dict also
         retrieve_held_counts (B, columns): how many points of the object the robot holds are inside the observation at every
-        column (gto_check_held_paths_device, enqueued behind the robot's own check).  With retrieve AND retime the retrieve path is retimed too, under the same limits,
+        column (gto_check_held_paths_device, enqueued behind the robot's own check); with ``held_points`` and ``held_clearance``
+        in the retrieve dict (no observation needed) also retrieve_held_self_d2, retrieve_held_self_col,
+        retrieve_held_self_link, retrieve_held_self_point and retrieve_held_self_clear (B,): the held points' smallest
+        squared distance from the robot's own links over the path's columns, where, and whether every column keeps the
+        clearance (gto_held_clearance_device, one call on the chain's stream in front of the one synchronisation;
+        ``_capi.held_clearance_summary``).  With retrieve AND retime the retrieve path is retimed too, under the same limits,
         subdiv and n_samples, on the chain's stream behind the retrieve stage (gto_retime_paths_device; ``reached_only`` in
         the retrieve dict: only columns 0 .. reached of a lift, the count made from retrieve_reached on the stream): the
         result gains retrieve_durations, retrieve_retime_status (B,) and, with ``retrieve_samples`` set in the retime dict,
@@ -206,13 +211,17 @@ class GraspChain:
         padded array (B, P_max, 3) with ``held_counts`` (B,); world points at the moment of the grasp, or object-frame points
         with ``object_pose`` (B, 4, 4) (``plan_grasps`` places object-frame points at its own object poses when the key is
         absent); ``labels`` (H, W) int32 and ``held_label`` (B,) or one label: the segmentation image of a depth observation
-        and the held object's label in it, whose pixels hide nothing that was seen (include/gto_solver.h)."""
+        and the held object's label in it, whose pixels hide nothing that was seen (include/gto_solver.h).
+        ``held_clearance`` (with ``held_points``; no observation needed): a dict ``[clearance, cutoff, links, ignore]``
+        (``_capi.held_clearance_request``; {} for the defaults) to measure the held points' clearance from the robot's own
+        links along the retrieve path (gto_held_clearance_device)."""
         known = {"mode", "distance", "steps", "direction", "closed_joints", "closed_value", "collide", "reached_only", "held_points",
-                 "held_counts", "object_pose", "labels", "held_label"}
+                 "held_counts", "object_pose", "labels", "held_label", "held_clearance"}
         if set(retrieve) - known:
             raise TypeError(f"retrieve: unexpected key(s) {sorted(set(retrieve) - known)}")
         r = dict(mode="lift", distance=0.3, steps=10, direction=(0.0, 0.0, 1.0), closed_joints=None, closed_value=0.0, collide=False,
-                 reached_only=False, held_points=None, held_counts=None, object_pose=None, labels=None, held_label=None)
+                 reached_only=False, held_points=None, held_counts=None, object_pose=None, labels=None, held_label=None,
+                 held_clearance=None)
         r.update(retrieve)
         if r["mode"] not in ("lift", "reverse"):
             raise ValueError('retrieve: mode is "lift" or "reverse"')
@@ -324,6 +333,11 @@ class GraspChain:
         f64, i32, u8 = torch.float64, torch.int32, torch.uint8
         res = SimpleNamespace()
         rs = None if retrieve is None else self.retrieve_spec(retrieve)
+        hc = None  # the checked (clearance, cutoff, links) of a held_clearance request, before anything is enqueued
+        if rs is not None and rs["held_clearance"] is not None:
+            if rs["held_points"] is None:
+                raise ValueError("retrieve: held_clearance needs held_points, the points it measures")
+            hc = _capi.held_clearance_request(d, self.link_ee, rs["held_clearance"])
         convex = None  # (gap_tol, max_newton) when the retime dict asks for the grid's time optimum
         torque = None  # the checked tau_max and per-object payload arrays when it asks for torque limits on top
         if retime is not None and "profile" in retime:
@@ -379,7 +393,7 @@ class GraspChain:
 
             def upload_held():
                 """The held object's points, counts, poses and labels -> device buffers of the chain (None: nothing to check)."""
-                if rs is None or observation is None or rs["held_points"] is None:
+                if rs is None or rs["held_points"] is None or (observation is None and hc is None):
                     return None
                 pts, n_held = h.pad_held_points(rs["held_points"], rs["held_counts"])
                 if pts.shape[0] != B or n_held.shape != (B,):
@@ -491,6 +505,13 @@ class GraspChain:
                                                       held.counts.data_ptr(), d_hcnt.data_ptr(), attach=None if lift else d_Q.data_ptr(),
                                                       attach_ld=T, attach_col=T - 1, object_pose=ptr(held.pose), labels=ptr(held.labels),
                                                       held_label=ptr(held.label), base_pos=base, stream=st)
+                    if hc is not None:  # the object against the arm that carries it: needs no observation
+                        d_hc = (self._dev("retrieve_held_self_d2_cols", (B, cols), f64), self._dev("retrieve_held_self_link_cols", (B, cols), i32),
+                                self._dev("retrieve_held_self_point_cols", (B, cols), i32))
+                        h.held_clearance_device(B, cols, d_rp.data_ptr(), held.points.data_ptr(), held.P_max, held.counts.data_ptr(),
+                                                *[t.data_ptr() for t in d_hc], attach=None if lift else d_Q.data_ptr(), attach_ld=T,
+                                                attach_col=T - 1, object_pose=None if held.pose is None else held.pose.data_ptr(),
+                                                base_pos=base, links=hc[2], cutoff=hc[1], stream=st)
                 if retime is not None:
                     d_dur, d_rst = self._dev("durations", (B,), f64), self._dev("retime_status", (B,), i32)
                     samp = {}  # the approach's samples, kept only for the rollout
@@ -575,6 +596,8 @@ class GraspChain:
                     out["retrieve_counts"] = d_rcnt
                     if held is not None:
                         out["retrieve_held_counts"] = d_hcnt
+                if hc is not None:
+                    out["_held_d2_cols"], out["_held_link_cols"], out["_held_point_cols"] = d_hc
                 if retime is not None:
                     out["retrieve_durations"], out["retrieve_retime_status"] = d_rdur, d_rrst
                     if convex is not None:
@@ -594,6 +617,11 @@ class GraspChain:
                 setattr(res, k, v.numpy().copy())
         for prefix in d_self:  # per plan: the closest column's d2 and pair, and whether every column is clear
             found = _capi.self_check_summary(host["_" + prefix + "d2_cols"].numpy(), host["_" + prefix + "pair_cols"].numpy(), sc[0], prefix)
+            for k, v in found.items():
+                setattr(res, k, v.copy())
+        if "_held_d2_cols" in host:  # per plan: the closest column of the held object against the robot's own links
+            found = _capi.held_clearance_summary(*[host[f"_held_{k}_cols"].numpy() for k in ("d2", "link", "point")], hc[0],
+                                                 "retrieve_held_self_")
             for k, v in found.items():
                 setattr(res, k, v.copy())
         res.accept = res.accept.astype(bool)

@@ -130,7 +130,7 @@ class GTOPlanner:
     def retrieve_path(self, plan, mode="lift", distance=0.3, steps=10, direction=(0.0, 0.0, 1.0), closed_joints=None,
                       closed_value=0.0, max_iter=50, pos_tol=0.01, rot_tol_deg=5.0, retime=None, observation=None,
                       held_points=None, n_held=None, object_pose=None, labels=None, held_label=None,
-                      base_position=(0.0, 0.0, 0.0), track=None, self_check=None):
+                      base_position=(0.0, 0.0, 0.0), track=None, self_check=None, held_clearance=None):
         """The motion after the grasp (examples/pybullet_gto_planning.py:301-313) for a solved ``plan`` (ndof, T), or
         (B, ndof, T) for B of them: mode "lift" moves link_ee by ``distance`` along ``direction`` in ``steps`` IK steps, each
         seeded from the one before, with the gripper's pose held (the tabletop driver's env.retract; pybullet's position-only
@@ -159,7 +159,13 @@ class GTOPlanner:
         self_check: a dict ``[clearance, cutoff, mask, q_ref]`` (``_capi.self_check_request``; {} for the defaults) to also
         measure the robot's clearance from itself along the path (gto_self_clearance).  The dict at the end of the return
         value -- the one that holds held_counts, added if there is none -- gains ``self_d2`` (the smallest squared distance
-        over the columns), ``self_pair`` (2,) and ``self_clear`` per plan."""
+        over the columns), ``self_pair`` (2,) and ``self_clear`` per plan.
+        held_clearance: a dict ``[clearance, cutoff, links, ignore]`` (``_capi.held_clearance_request``; {} for the defaults)
+        to also measure the held points' clearance from the robot's own links along the path (gto_held_clearance): the
+        object against the arm that carries it.  It needs ``held_points`` and no observation (without one the counts are
+        not computed and ``held_counts`` is absent).  The dict at the end of the return value gains ``held_self_d2`` (the
+        smallest squared distance over the columns), ``held_self_col``, ``held_self_link``, ``held_self_point`` and
+        ``held_self_clear`` per plan."""
         from . import _capi
         from .grasp_chain import finger_joints
         plan = np.asarray(plan, dtype=np.float64)
@@ -167,6 +173,10 @@ class GTOPlanner:
         plans = np.ascontiguousarray(plan.reshape(-1, self.robot.ndof, self.T))
         if self_check is not None:  # checked before the handle is made
             self_check = _capi.self_check_request(self.robot.desc, self_check)
+        if held_clearance is not None:
+            if held_points is None:
+                raise ValueError("retrieve_path: held_clearance needs held_points, the points it measures")
+            held_clearance = _capi.held_clearance_request(self.robot.desc, self.link_ee, held_clearance)
         torque = None  # a torque request is checked before the handle is made: (tau_max, payload dict)
         if retime is not None and retime.get("profile") == "torque":
             _capi.payload_arrays(retime.get("payload"), plans.shape[0])
@@ -206,9 +216,8 @@ class GTOPlanner:
             raise ValueError('retrieve_path: mode is "lift" or "reverse"')
         checks = ()
         if held_points is not None:
-            if observation is None:
+            if observation is None and held_clearance is None:
                 raise ValueError("retrieve_path: held_points need the observation they are counted in")
-            from .observation import as_observation
             B = plans.shape[0]
             if single and n_held is None and isinstance(held_points, np.ndarray) and held_points.ndim == 2:
                 held_points = [held_points]
@@ -216,9 +225,18 @@ class GTOPlanner:
             attach = plans if mode == "reverse" else None
             pose = None if object_pose is None else np.broadcast_to(np.asarray(object_pose, dtype=np.float64).reshape(-1, 16), (B, 16))
             base = np.asarray(base_position, dtype=np.float64)
-            counts = h.check_held_paths(as_observation(observation), path, held_points, n_held=n_held, attach=attach,
-                                        object_pose=pose, labels=labels, held_label=held_label, base_pos=base)
-            checks = ({"held_counts": counts[0] if single else counts},)
+            found = {}
+            if observation is not None:
+                from .observation import as_observation
+                counts = h.check_held_paths(as_observation(observation), path, held_points, n_held=n_held, attach=attach,
+                                            object_pose=pose, labels=labels, held_label=held_label, base_pos=base)
+                found["held_counts"] = counts[0] if single else counts
+            if held_clearance is not None:
+                hc = h.held_clearance(path, held_points, n_held=n_held, attach=attach, object_pose=pose, base_pos=base,
+                                      links=held_clearance[2], cutoff=held_clearance[1])
+                summary = _capi.held_clearance_summary(hc["d2"], hc["link"], hc["point"], held_clearance[0])
+                found.update({k: v[0] if single else v for k, v in summary.items()})
+            checks = (found,)
         if self_check is not None:
             h.set_self_pairs(self_check[2])
             sc = h.self_clearance(path, cutoff=self_check[1])

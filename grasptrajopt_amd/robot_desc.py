@@ -225,18 +225,22 @@ class RobotDesc:
             worst = max(worst, float(np.median(np.sqrt(d2.min(1)))))
         return worst
 
-    def joints_between(self, la: int, lb: int) -> int:
-        """Non-fixed joints on the tree path between the frames of links la and lb."""
+    def frame_joints_between(self, fa: int, fb: int) -> int:
+        """Non-fixed joints on the tree path between the frames fa and fb."""
         def chain(f):
             out = []
             while f >= 0:
                 out.append(int(f))
                 f = self.parent[f]
             return out
-        ca, cb = chain(self.link_frame[la]), chain(self.link_frame[lb])
+        ca, cb = chain(fa), chain(fb)
         common = set(ca) & set(cb)
         path = [f for f in ca if f not in common] + [f for f in cb if f not in common]
         return sum(1 for f in path if self.joint_type[f] != JOINT_FIXED)
+
+    def joints_between(self, la: int, lb: int) -> int:
+        """Non-fixed joints on the tree path between the frames of links la and lb."""
+        return self.frame_joints_between(self.link_frame[la], self.link_frame[lb])
 
     def self_pairs(self, q_ref=None, clearance=None, ignore=()) -> np.ndarray:
         """(L, L) bool, symmetric with a false diagonal: the link pairs the self-clearance check compares
@@ -262,6 +266,18 @@ class RobotDesc:
             a, b = self.link_names.index(na), self.link_names.index(nb)
             M[min(a, b), max(a, b)] = False
         return M | M.T
+
+    def held_links(self, link_ee: str, ignore=()) -> np.ndarray:
+        """(L,) bool: the collision links a held object is measured against (gto_held_clearance's link_mask).  The object
+        rides with the frame ``link_ee``.  A link is enabled unless
+          (a) fewer than two non-fixed joints lie on the tree path between its frame and link_ee's frame: hand, fingers and
+              the wrist link touch the object by construction (rule (a) of self_pairs);
+          (b) ``ignore`` names it."""
+        fe = self.frame_index(link_ee)
+        out = np.array([self.frame_joints_between(self.link_frame[l], fe) >= 2 for l in range(self.n_links)], dtype=bool)
+        for name in ignore:
+            out[self.link_names.index(name)] = False
+        return out
 
     # ------------------------------------------------------------------ construction
     @classmethod

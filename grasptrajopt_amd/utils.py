@@ -329,6 +329,34 @@ def self_clearance(robot, plans, clearance=None, cutoff=None, mask=None, q_ref=N
     return {k: v[0] for k, v in out.items()} if single else out
 
 
+def held_clearance(robot, paths, link_ee, held_points, n_held=None, attach=None, attach_col=None, object_pose=None,
+                   base_position=(0.0, 0.0, 0.0), clearance=None, cutoff=None, links=None, ignore=()):
+    """The held object's distance from the robot's own links along ``paths`` (B, ndof, Tp) or (ndof, Tp), any Tp >= 1, on
+    the GPU (gto_held_clearance): the object rides with ``link_ee`` from the grasp configuration -- column 0 of the path,
+    or column ``attach_col`` (default: the last) of ``attach`` -- and a wrist that folds back drives it into the forearm or
+    the base, which no other check sees.  held_points / n_held / object_pose: as ``SolverHandle.check_held_paths`` takes
+    them (one (n, 3) array for one path).  clearance: metres, default the description's point_spacing(); cutoff: default
+    2 x clearance (distances beyond it are reported as the cutoff, with link and point -1); links: (L,) bool, default
+    ``RobotDesc.held_links(link_ee, ignore)``.  Returns a dict: d2 (squared metres), dist, link, point, clear = dist >=
+    clearance (a column with a non-finite entry has d2 = NaN and is not clear)."""
+    from ._capi import held_clearance_request
+    paths = np.asarray(paths, dtype=np.float64)
+    single = paths.ndim == 2
+    paths = np.ascontiguousarray(paths.reshape(-1, robot.desc.ndof, paths.shape[-1]))
+    clearance, cutoff, links = held_clearance_request(robot.desc, link_ee, dict(clearance=clearance, cutoff=cutoff, links=links,
+                                                                                ignore=ignore))
+    if single:
+        if n_held is None and isinstance(held_points, np.ndarray) and held_points.ndim == 2:
+            held_points = [held_points]
+        attach = None if attach is None else np.asarray(attach, dtype=np.float64).reshape(1, robot.desc.ndof, -1)
+    out = _torque_handle(robot, 50, link_ee).held_clearance(paths, held_points, n_held=n_held, attach=attach, attach_col=attach_col,
+                                                            object_pose=object_pose, base_pos=base_position, links=links,
+                                                            cutoff=cutoff)
+    with np.errstate(invalid="ignore"):
+        out["clear"] = out["dist"] >= clearance
+    return {k: v[0] for k, v in out.items()} if single else out
+
+
 def inverse_dynamics(robot, q, qd, qdd, payload=None, link_ee=None):
     """Joint forces tau = M(q) qdd + C(q, qd) qd + g(q) of states (n, ndof) or one state (ndof,) on the GPU
     (gto_inverse_dynamics, include/gto_solver.h): recursive Newton-Euler over the robot's frames with the link inertials of

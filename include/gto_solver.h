@@ -1209,6 +1209,53 @@ int gto_self_clearance(gto_handle* h, int32_t B, int32_t Tp, const double* paths
                        int32_t* pair_out);
 int gto_self_clearance_device(gto_handle* h, int32_t B, int32_t Tp, const double* paths, double cutoff, double* d2_out,
                               int32_t* pair_out, void* stream);
+/*
+ * The held object's clearance from the robot's own links along a path.  gto_check_held_paths judges the object's points
+ * against the observation and gto_self_clearance the robot's links against each other (the handle's links: the object's
+ * points are not robot points); these judge the pair that is left, the object against the arm that carries it.  Nothing in
+ * the reference does: a box driven into the forearm shows there when PyBullet executes the plan
+ * (examples/pybullet_gto_planning.py:301).  Additions (the ABI number stays).
+ * paths, attach, attach_ld, attach_col, held_points, P_max, n_held, object_pose, base_pos and per_plan_base mean exactly
+ * what they mean for gto_check_held_paths[_device], with the same limits (65535 plans of 65535 points: GTO_ERR_UNSUPPORTED
+ * beyond), the same clamping of a device-resident n_held to [0, P_max] and the same error codes; there is no observation,
+ * no labels and no held_label.  For plan b, column t, the link mask m and a cutoff c in metres (+inf allowed), in FP64
+ * without contraction:
+ *   p        the held point in link_ee's frame at the grasp configuration: the attach step of gto_check_held_paths, term
+ *            for term (d[a] = (x[a] - base[a]) - E_a.tr[a]; p[c] = (E_a.R[0][c]*d[0] + E_a.R[1][c]*d[1]) + E_a.R[2][c]*d[2])
+ *   Y_t[r] = ((E_t.R[r][0]*p[0] + E_t.R[r][1]*p[1]) + E_t.R[r][2]*p[2]) + E_t.tr[r]
+ *            that header's X_t without the final + base: the base cancels against the robot's points
+ *   X_p'     gto_eval_points' world point of robot surface point p' at base 0, bit for bit
+ *   d2(b,t) = min over held points i < n_held[b] with finite coordinates and robot points p' of the links l with bit l of m
+ *            set, of (dx*dx + dy*dy) + dz*dz, d = Y_t,i - X_p'
+ *   d2_out    [B][Tp]  min(d2, c*c)
+ *   link_out  [B][Tp]  the collision link l and
+ *   point_out [B][Tp]  the held point i that attain the minimum; of several at the same d2 the lexicographically smallest
+ *                      (l, i); both -1 when nothing is closer than the cutoff.  Either may be NULL.
+ * n_held[b] = 0, an empty mask, or enabled links without points: c*c and -1.  A column with a non-finite entry: NaN and -1,
+ * and no other column changes.  Every column of a plan whose q_att, base or object pose holds a non-finite entry: NaN and
+ * -1.  A held point with a non-finite coordinate is skipped and changes no other point's result.  Every column's result is
+ * bit for bit the same in any batch, at any position, whatever the cutoff culls and whatever the number of columns a
+ * workgroup takes (GTO_CHECK_TG): the sphere tests only ever drop (held point, chunk) pairs that are strictly farther than
+ * the answer.  Works on every handle, whatever its number of optimised joints or its T.
+ *   link_mask  bit l enables collision link l of the handle (the 32 bits of an unsigned word; the header types it int32_t,
+ *              as gto_set_self_pairs' rows).  0 is legal: everything is far.  RobotDesc.held_links builds the planners' mask.
+ *   GTO_ERR_INVALID_ARG before any device call: a mask bit at or above n_links, a NaN or non-positive cutoff, B < 0, Tp < 1,
+ *   P_max < 1, attach_col outside [0, attach_ld), a null paths, held_points, n_held, base_pos or d2_out; the host variant
+ *   also for an n_held outside [0, P_max].  B = 0: GTO_OK without a launch.
+ * gto_held_clearance takes HOST arrays and is synchronous.  gto_held_clearance_device takes DEVICE arrays (base_pos HOST,
+ * free on return): two launches on `stream` (NULL = the handle's), the attach step and the clearance kernel, with no
+ * synchronisation and no allocation once the handle's workspace has grown to the call's size.  The attach step's workspace
+ * is the one gto_check_held_paths_device uses: calls that share a handle go to one stream.
+ */
+int gto_held_clearance(gto_handle* h, int32_t B, int32_t Tp, const double* paths, const double* attach, int32_t attach_ld,
+                       int32_t attach_col, const double* held_points, int32_t P_max, const int32_t* n_held,
+                       const double* object_pose, const double* base_pos, int32_t per_plan_base, int32_t link_mask,
+                       double cutoff, double* d2_out, int32_t* link_out, int32_t* point_out);
+int gto_held_clearance_device(gto_handle* h, int32_t B, int32_t Tp, const double* paths, const double* attach,
+                              int32_t attach_ld, int32_t attach_col, const double* held_points, int32_t P_max,
+                              const int32_t* n_held, const double* object_pose, const double* base_pos /*HOST*/,
+                              int32_t per_plan_base, int32_t link_mask, double cutoff, double* d2_out, int32_t* link_out,
+                              int32_t* point_out, void* stream);
 
 #ifdef __cplusplus
 }
